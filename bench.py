@@ -7,7 +7,7 @@ One "step" = one pass of the hot path over one batch of synthetic input already 
 Workload = BASELINE.json configs[1]: "DSPH --dataset flickr25k --output-dim 64, ViT-B/32 bf16, 1xMI355X,
 batch=256" (per-GPU batch fixed as N grows -> weak scaling).  Random-init weights, synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,11 @@ Rank 0 prints ONE JSON line.  Extra objects:
   cpu_baseline the oracle (numpy fp32 restatement of the reference path) timed on the host cores, rank 0, N=1.
   map_eval     secondary metric: wall-clock of the 4 calc_map_k directions (64-bit, MIRFlickr scale), codes
                resident; not part of `value`.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: image_hash / text_hash
+(tanh hash outputs, batch x bits), image_codes / text_codes (their sign() codes) and loss (the HyP loss, a scalar).  Weights
+and the synthetic batch are seeded, so the same arguments give the same inputs on every run and two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -173,13 +178,24 @@ def flip_rates(clip, heads, image, text):
     return out
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """arrays: name -> tensor, written as out_dir/<name>.npy in float32 (at most `budget` bytes in all)."""
+    host = {name: t.detach().float().cpu().numpy() for name, t in sorted(arrays.items())}
+    total = sum(v.nbytes for v in host.values())
+    assert total <= budget, f"--dump-outputs: {total} bytes of outputs exceed {budget}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline: ms_per_step = their wall-clock / --steps")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region of exactly --steps steps is run this many times; value = the MEDIAN region (value_runs lists min / median / max)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="run the timed region of exactly --steps steps this many times (default once, so --steps is the number of "
+                         "timed steps); value = the MEDIAN region (value_runs lists min / median / max)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (configs[1]: 256)")
     ap.add_argument("--seq-len", type=int, default=77)
     ap.add_argument("--bits", type=int, default=64)
@@ -204,7 +220,11 @@ def main():
     ap.add_argument("--no-config-legs", action="store_true", help="skip the one-number-per-BASELINE-config legs (bench_configs.py)")
     ap.add_argument("--map-queries", type=int, default=5000)
     ap.add_argument("--map-db", type=int, default=15015)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:     # started bare: become the launcher of N ranks (before any GPU call)
         sys.exit(self_launch(a.gpus))
 
@@ -230,16 +250,18 @@ def main():
     hyp = HyP(numclass=C, output_dim=K, hypseed=0, alpha=0.8).to(dev)
     image, text, label = synthetic_batch(B, L, C, 1814 + rank, dev)
 
-    def tower(encode, head, x):
-        h = head(encode(x))
-        N.pack_codes(N.sign_codes(h), validate=False)
-        return h
+    last = {}       # the outputs of the most recent step (references only: nothing is copied on the timed path)
+
+    def tower(encode, head, x, side):
+        return finish(head, encode(x), side)
 
     towers = "serial" if a.no_overlap_towers else a.towers
 
-    def finish(head, feat):
+    def finish(head, feat, side):
         h = head(feat)
-        N.pack_codes(N.sign_codes(h), validate=False)
+        codes = N.sign_codes(h)
+        N.pack_codes(codes, validate=False)
+        last[side + "_hash"], last[side + "_codes"] = h, codes
         return h
 
     n_pair_streams = max(1, int(os.environ.get("CMH_PAIR_STREAMS", "2")))      # (diagnostic: more alternating streams)
@@ -260,25 +282,27 @@ def main():
                 cur = torch.cuda.current_stream(dev)
                 with torch.cuda.stream(s2):
                     fi, ft = clip.encode_pair(image, text)
-                    hi, ht = finish(img_head, fi), finish(txt_head, ft)
+                    hi, ht = finish(img_head, fi, "image"), finish(txt_head, ft, "text")
                 cur.wait_stream(s2)          # the exchange step and the loss stay on the caller's stream
                 hi.record_stream(cur)
                 ht.record_stream(cur)
             elif how == "pair":       # both towers in lock-step: layer i of both is one grouped GEMM launch (csrc/encoders.hip)
                 fi, ft = clip.encode_pair(image, text)
-                hi, ht = finish(img_head, fi), finish(txt_head, ft)
+                hi, ht = finish(img_head, fi, "image"), finish(txt_head, ft, "text")
             elif how in ("streams", "pipelined"):   # the two towers are independent until the loss: one HIP stream each (streams.py)
-                hi, ht = overlapped(lambda: tower(clip.encode_image, img_head, image),
-                                    lambda: tower(clip.encode_text, txt_head, text), inputs_ready=True if how == "pipelined" else None)
+                hi, ht = overlapped(lambda: tower(clip.encode_image, img_head, image, "image"),
+                                    lambda: tower(clip.encode_text, txt_head, text, "text"), inputs_ready=True if how == "pipelined" else None)
             else:
-                hi = tower(clip.encode_image, img_head, image)
-                ht = tower(clip.encode_text, txt_head, text)
+                hi = tower(clip.encode_image, img_head, image, "image")
+                ht = tower(clip.encode_text, txt_head, text, "text")
             if dist_on:   # the path's one exchange step: fused all-gather of the per-rank code blocks
                 fused, widths = du.fuse_columns(hi, ht, label)
                 hi_g, ht_g, lab_g = du.split_columns(du.all_gather_rows(fused), widths)
             else:
                 hi_g, ht_g, lab_g = hi, ht, label
-            return hyp(hi_g, ht_g, lab_g)
+            loss = hyp(hi_g, ht_g, lab_g)
+            last["loss"] = loss
+            return loss
 
     def barrier():
         torch.cuda.synchronize()
@@ -304,9 +328,9 @@ def main():
             torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
         return float(el.item())
 
-    # The timed region: EXACTLY --steps steps between two barrier + synchronize pairs, MAX over the ranks - run `reps` times back to
-    # back (boxes of this pool differ by 10 % and the clock moves with the load: one 0.08 s sample cannot show a 1-3 % change).
-    # `value` / `ms_per_step` are the MEDIAN region's; `value_runs` carries min / median / max of the same regions.
+    # The timed region: EXACTLY --steps steps between two barrier + synchronize pairs, MAX over the ranks.  By default it runs once,
+    # so --steps is the number of timed steps; --repeats R runs it R times back to back (the clock moves with the load: one short
+    # region cannot show a 1-3 % change).  `value` / `ms_per_step` are the MEDIAN region's; `value_runs` carries min / median / max.
     region_s = []
     for _ in range(reps):
         barrier()
@@ -315,6 +339,8 @@ def main():
             loss = step()
         barrier()
         region_s.append(max_over_ranks(time.perf_counter() - t0))
+    if a.dump_outputs and rank == 0:      # the last timed step's outputs, before any later leg runs the step again
+        dump_outputs(a.dump_outputs, last)
     if overlap:
         # With the towers on two streams a GEMM's start-to-end time includes the time its workgroups wait for CUs held by
         # the other tower's kernel, so per-launch HIP events (and rocprofv3's kernel trace) no longer time the kernel.  The
