@@ -27,7 +27,7 @@ def test_colsum(R, C, dt):
     torch.testing.assert_close(out, ref, rtol=1e-5, atol=1e-4 * R ** 0.5)
 
 
-@pytest.mark.parametrize("M,d", [(3, 128), (100, 512), (1000, 768), (33, 1024)])
+@pytest.mark.parametrize("M,d", [(3, 128), (100, 512), (1000, 768), (33, 1024), (12800, 768), (19712, 512)])
 @pytest.mark.parametrize("xdt,gdt", [(torch.float32, torch.float32), (torch.float16, torch.bfloat16)])
 def test_layernorm_backward(M, d, xdt, gdt):
     import backward_ops as B
@@ -91,7 +91,62 @@ def test_attention_backward(B, T, d, causal, kpm, mode):
     torch.testing.assert_close(dqkv.cpu().double(), ref, **tol)
 
 
-@pytest.mark.parametrize("M,N,K", [(160, 256, 64), (333, 512, 128), (1000, 3072, 768)])
+@pytest.mark.parametrize("B,T,d,causal,kpm", [(256, 50, 768, 0, False), (256, 77, 512, 1, False), (256, 77, 512, 1, True)])
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_attention_backward_at_tower_shapes(B, T, d, causal, kpm, mode):
+    """attention_backward at the towers' shapes: 12 heads x 50 image tokens, 8 heads x 77 causal caption tokens, and the latter with
+    ragged key padding (1..77 visible keys per row).  Checker: the fp64 statement of the backward on the SAME rounded operands
+    (q, k, v, dO as the kernel reads them): P = softmax(Q K^T / 8 + masks), dV = P^T dO, dS = P o (dO V^T - D) / 8, dQ = dS K,
+    dK = dS^T Q, with D = rowsum(dO o O).  The f32 kernel forms D from the GPU forward's o, so O is that o here; the bf16 kernel at
+    T <= 96 (the MFMA kernel) never reads o - it forms D = rowsum(P o dP) from its own f32 P and dP - so O is the exact P V.
+    f32: the bound of test_attention_backward.  bf16, per Q / K / V slice against that slice: S and dP are f32 sums of exact products
+    of the bf16 operands; what the kernel rounds is P and dS (to bf16, each at most 2^-9 relative, as the operands of its dV / dQ / dK
+    MFMAs) and every output (2^-9 relative).  So an element is off by at most ~2^-9 of itself plus 2^-9 of the sum of |products| it
+    adds up - asserted as 1e-2 of the slice's max - and since those roundings are unbiased and independent, the slice's error 2-norm
+    stays near 2^-9 of the slice's 2-norm: asserted <= 4e-3 (twice 2^-9), which a slice scaled by 1 % does not meet.  Measured on
+    MI355X: at most 4.6e-3 of a slice's max, 2.4e-3 of its 2-norm."""
+    import backward_ops as Bo
+    import cmh_native as N
+    g = torch.Generator().manual_seed(B + T + d + 7 * causal + kpm)
+    qkv = torch.randn(B * T, 3 * d, generator=g)
+    dout = torch.randn(B * T, d, generator=g)
+    mask = None
+    if kpm:
+        vis = torch.randint(1, T + 1, (B,), generator=g)
+        vis[0], vis[1] = 1, T
+        mask = torch.arange(T)[None, :] >= vis[:, None]              # trailing pads; key 0 always visible
+    dt = torch.bfloat16 if mode == "bf16" else torch.float32
+    qd, dd = qkv.to(dt).to(DEV), dout.to(dt).to(DEV)
+    md = None if mask is None else mask.to(DEV)
+    o_gpu = N.attention(qd, B, T, causal, md)
+    dqkv = Bo.attention_backward(qd, o_gpu, dd, B, T, causal, md)
+    H = d // 64
+    q, k, v = qd.double().view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)                     # [B, H, T, 64] each
+    do = dd.double().view(B, T, H, 64).permute(0, 2, 1, 3)
+    s = q @ k.transpose(-1, -2) / 8.0
+    if causal:
+        s = s + torch.full((T, T), float("-inf"), dtype=torch.float64, device=DEV).triu(1)
+    if md is not None:
+        s = s.masked_fill(md[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, -1)
+    o = o_gpu.double().view(B, T, H, 64).permute(0, 2, 1, 3) if mode == "f32" else p @ v
+    dv = p.transpose(-1, -2) @ do
+    ds = p * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True)) / 8.0
+    ref = torch.stack((ds @ k, ds.transpose(-1, -2) @ q, dv)).permute(1, 3, 0, 2, 4).reshape(B * T, 3 * d)
+    got = dqkv.double()
+    if mode == "f32":
+        torch.testing.assert_close(got, ref, rtol=1e-4, atol=1e-5)
+        return
+    worst = [0.0, 0.0]
+    for i, name in enumerate("QKV"):
+        r, e = ref[:, i * d:(i + 1) * d], got[:, i * d:(i + 1) * d] - ref[:, i * d:(i + 1) * d]
+        emax, enorm = float(e.abs().max() / r.abs().max()), float(e.norm() / r.norm())
+        worst = [max(worst[0], emax), max(worst[1], enorm)]
+        assert emax <= 1e-2 and enorm <= 4e-3, (name, emax, enorm)
+    print(f"attention backward bf16 B={B} T={T} d={d}: worst {worst[0]:.2e} of a slice's max, {worst[1]:.2e} of its 2-norm")
+
+
+@pytest.mark.parametrize("M,N,K", [(160, 256, 64), (333, 512, 128), (1000, 3072, 768), (12800, 3072, 768), (10499, 2048, 512)])
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
 def test_gemm_epilogue_mul_dquickgelu(M, N, K, mode):
     """dgrad through c_fc's QuickGELU: out = (dY . W^T) * d/dv[v sigmoid(1.702 v)] at the saved pre-activation."""
