@@ -421,6 +421,217 @@ int launch_attention_bwd_bf16(const void* qkv, const void* dout, void* dqkv, int
   }
 }
 
+// ============================================================================================================================
+// Tiled backward for T > 128 (both dtypes): the whole-sequence images above outgrow LDS there (f32 needs ~259 KB at T = 197).
+// One 256-thread workgroup per (batch, head) still owns the sequence, but only 32-row tiles of Q / K / V / dO and a 32 x 32 score
+// tile live in LDS (f32, 41 KB) beside three per-row f32 vectors: the softmax max m_i, 1 / l_i, and D_i = sum_j P_ij dP_ij.
+//   pass 1: per query tile, online over the key tiles (D rescaled like the sum) -> m_i, 1 / l_i, D_i
+//   pass 2: per key tile, sweep the query tiles: P, dS recomputed, dV += P^T dO, dK += dS^T Q in registers
+//   pass 3: per query tile, sweep the key tiles: dS recomputed, dQ += dS K in registers
+// D is formed from the kernel's own P and dP, as the MFMA kernel above does; the forward's o is not read.  Then sum_j dS_ij cancels
+// to the rounding of the kernel's own sums (a row with one visible key gets dS = 0 exactly), where dO . o left an f32 residual
+// that the 577 queries of ViT-L/14@336px add up in dK.
+// Every output element is one thread's fixed-order sum: no atomics, bit-reproducible.  S and dO V^T are formed three times each;
+// VALU only (an MFMA form for the bf16 mode is the next step).  A row whose keys are all masked gets P = 0, not 0 / 0.
+constexpr int kAttnBwdMaxT = 4096;   // the tiled kernel's per-row vectors: 48 KB of LDS at this length
+constexpr int kAbTile = 32;              // rows per Q / K / V / dO tile
+constexpr int kAbLD = 65;                // f32 row stride of those tiles (65: the key-indexed reads of a wave hit distinct banks)
+constexpr int kAbLS = kAbTile + 1;       // f32 row stride of the score tiles
+
+static size_t attention_bwd_tiled_lds(int Tmax) {
+  return (static_cast<size_t>(4) * kAbTile * kAbLD + static_cast<size_t>(2) * kAbTile * kAbLS + static_cast<size_t>(3) * Tmax) * 4;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_bwd_tiled_kernel(const T* __restrict__ qkv, const T* __restrict__ dout, T* __restrict__ dqkv, int B, int Tmax,
+                                                                  int d, int causal, const uint8_t* __restrict__ kpm,
+                                                                  const int32_t* __restrict__ seq_off) {
+  extern __shared__ float smem[];
+  float* sQ = smem;                          // [32][65]
+  float* sK = sQ + kAbTile * kAbLD;
+  float* sV = sK + kAbTile * kAbLD;
+  float* sDO = sV + kAbTile * kAbLD;
+  float* sP = sDO + kAbTile * kAbLD;         // [32 q][33]
+  float* sDS = sP + kAbTile * kAbLS;
+  float* rowM = sDS + kAbTile * kAbLS;       // [Tmax]
+  float* rowIL = rowM + Tmax;
+  float* rowD = rowIL + Tmax;
+  const int heads = d / HDB;
+  const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
+  const int Tn = seq_off ? seq_off[b + 1] - seq_off[b] : Tmax;
+  const size_t ld = static_cast<size_t>(3) * d;
+  const size_t row0 = seq_off ? static_cast<size_t>(seq_off[b]) : static_cast<size_t>(b) * Tmax;
+  const T* qb = qkv + row0 * ld + h * HDB;             // q: +0, k: +d, v: +2d
+  const T* dob = dout + row0 * d + h * HDB;
+  T* dqb = dqkv + row0 * ld + h * HDB;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int ntile = (Tn + kAbTile - 1) / kAbTile;
+
+  auto load_tile = [&](float* buf, const T* base, size_t stride, int r0) {      // rows >= Tn are zeros
+    for (int idx = tid; idx < kAbTile * HDB; idx += 256) {
+      const int r = idx >> 6, c = idx & 63;
+      buf[r * kAbLD + c] = r0 + r < Tn ? ab_ld<T>(base, static_cast<size_t>(r0 + r) * stride + c) : 0.f;
+    }
+  };
+  auto dot = [&](const float* a, const float* bm) {
+    float acc = 0.f;
+#pragma unroll 16
+    for (int c = 0; c < HDB; ++c) acc += a[c] * bm[c];
+    return acc;
+  };
+  auto key_ok = [&](int q, int key) {
+    bool ok = q < Tn && key < Tn && !(causal && key > q);
+    if (ok && kpm) ok = kpm[static_cast<size_t>(b) * Tmax + key] == 0;
+    return ok;
+  };
+
+  // ---- pass 1: row max, 1 / sum and D, online over the key tiles --------------------------------------------------------------
+  for (int qt = 0; qt < ntile; ++qt) {
+    const int q0 = qt * kAbTile;
+    load_tile(sQ, qb, ld, q0);
+    load_tile(sDO, dob, d, q0);
+    float m_run[kAbTile / 4], l_run[kAbTile / 4], d_run[kAbTile / 4];      // wave wid owns rows wid, wid + 4, ... of the tile
+#pragma unroll
+    for (int k = 0; k < kAbTile / 4; ++k) { m_run[k] = -1e30f; l_run[k] = 0.f; d_run[k] = 0.f; }
+    for (int kt = 0; kt < ntile; ++kt) {
+      const int k0 = kt * kAbTile;
+      __syncthreads();                       // the previous tile's readers are done with sK / sV / sP / sDS
+      load_tile(sK, qb + d, ld, k0);
+      load_tile(sV, qb + 2 * d, ld, k0);
+      __syncthreads();
+      for (int idx = tid; idx < kAbTile * kAbTile; idx += 256) {
+        const int i = idx >> 5, j = idx & 31;
+        const float s = dot(sQ + i * kAbLD, sK + j * kAbLD) * 0.125f;
+        sP[i * kAbLS + j] = key_ok(q0 + i, k0 + j) ? s : -1e30f;
+        sDS[i * kAbLS + j] = dot(sDO + i * kAbLD, sV + j * kAbLD);          // dP
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kAbTile / 4; ++k) {
+        const int i = wid + 4 * k;
+        const float s = lane < kAbTile ? sP[i * kAbLS + lane] : -1e30f;
+        float mx = s;
+#pragma unroll
+        for (int of = 32; of > 0; of >>= 1) mx = fmaxf(mx, __shfl_xor(mx, of, 64));
+        const float mn = fmaxf(m_run[k], mx);
+        float p = s > -1e29f ? expf(s - mn) : 0.f;
+        float pd = s > -1e29f ? p * sDS[i * kAbLS + lane] : 0.f;
+#pragma unroll
+        for (int of = 32; of > 0; of >>= 1) { p += __shfl_xor(p, of, 64); pd += __shfl_xor(pd, of, 64); }
+        const float alpha = expf(m_run[k] - mn);
+        l_run[k] = l_run[k] * alpha + p;
+        d_run[k] = d_run[k] * alpha + pd;
+        m_run[k] = mn;
+      }
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < kAbTile / 4; ++k) {
+        const int i = q0 + wid + 4 * k;
+        if (i < Tn) {
+          const float il = l_run[k] > 0.f ? 1.0f / l_run[k] : 0.f;
+          rowM[i] = m_run[k]; rowIL[i] = il; rowD[i] = d_run[k] * il;
+        }
+      }
+    }
+    __syncthreads();                         // sQ is reloaded by the next tile
+  }
+
+  // P and dS of one 32 x 32 tile (sQ, sK, sV, sDO loaded) into sP / sDS
+  auto p_ds_tile = [&](int q0, int k0) {
+    for (int idx = tid; idx < kAbTile * kAbTile; idx += 256) {
+      const int i = idx >> 5, j = idx & 31, q = q0 + i;
+      float p = 0.f, ds = 0.f;
+      if (key_ok(q, k0 + j)) {
+        p = expf(dot(sQ + i * kAbLD, sK + j * kAbLD) * 0.125f - rowM[q]) * rowIL[q];
+        ds = p * (dot(sDO + i * kAbLD, sV + j * kAbLD) - rowD[q]) * 0.125f;
+      }
+      sP[i * kAbLS + j] = p;
+      sDS[i * kAbLS + j] = ds;
+    }
+  };
+  const int c = lane;                        // output column of this thread; its rows are wid + 4k
+  // ---- pass 2: dV = P^T dO, dK = dS^T Q over key tiles ---------------------------------------------------------------------
+  for (int kt = 0; kt < ntile; ++kt) {
+    const int k0 = kt * kAbTile;
+    float dv[kAbTile / 4], dk[kAbTile / 4];
+#pragma unroll
+    for (int k = 0; k < kAbTile / 4; ++k) dv[k] = dk[k] = 0.f;
+    load_tile(sK, qb + d, ld, k0);
+    load_tile(sV, qb + 2 * d, ld, k0);
+    for (int qt = 0; qt < ntile; ++qt) {
+      const int q0 = qt * kAbTile;
+      load_tile(sQ, qb, ld, q0);
+      load_tile(sDO, dob, d, q0);
+      __syncthreads();
+      p_ds_tile(q0, k0);
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kAbTile / 4; ++k) {
+        const int j = wid + 4 * k;
+        float av = dv[k], ak = dk[k];
+#pragma unroll 8
+        for (int i = 0; i < kAbTile; ++i) {
+          av += sP[i * kAbLS + j] * sDO[i * kAbLD + c];
+          ak += sDS[i * kAbLS + j] * sQ[i * kAbLD + c];
+        }
+        dv[k] = av; dk[k] = ak;
+      }
+      __syncthreads();                       // sQ / sDO / sP / sDS are rewritten by the next query tile
+    }
+#pragma unroll
+    for (int k = 0; k < kAbTile / 4; ++k) {
+      const int j = k0 + wid + 4 * k;
+      if (j < Tn) {
+        ab_st<T>(dqb + d, static_cast<size_t>(j) * ld + c, dk[k]);
+        ab_st<T>(dqb + 2 * d, static_cast<size_t>(j) * ld + c, dv[k]);
+      }
+    }
+  }
+  // ---- pass 3: dQ = dS K over query tiles ------------------------------------------------------------------------------------
+  for (int qt = 0; qt < ntile; ++qt) {
+    const int q0 = qt * kAbTile;
+    float dq[kAbTile / 4];
+#pragma unroll
+    for (int k = 0; k < kAbTile / 4; ++k) dq[k] = 0.f;
+    load_tile(sQ, qb, ld, q0);
+    load_tile(sDO, dob, d, q0);
+    for (int kt = 0; kt < ntile; ++kt) {
+      const int k0 = kt * kAbTile;
+      load_tile(sK, qb + d, ld, k0);
+      load_tile(sV, qb + 2 * d, ld, k0);
+      __syncthreads();
+      p_ds_tile(q0, k0);
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kAbTile / 4; ++k) {
+        const int i = wid + 4 * k;
+        float aq = dq[k];
+#pragma unroll 8
+        for (int j = 0; j < kAbTile; ++j) aq += sDS[i * kAbLS + j] * sK[j * kAbLD + c];
+        dq[k] = aq;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < kAbTile / 4; ++k) {
+      const int i = q0 + wid + 4 * k;
+      if (i < Tn) ab_st<T>(dqb, static_cast<size_t>(i) * ld + c, dq[k]);
+    }
+  }
+}
+
+template <typename T>
+static int launch_attention_bwd_tiled(const void* qkv, const void* dout, void* dqkv, int B, int T_, int d, int causal,
+                                      const uint8_t* kpm, const int32_t* seq_off, hipStream_t st) {
+  const size_t lds = attention_bwd_tiled_lds(T_);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_tiled_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(lds)) != hipSuccess) return fail(CMH_ERR_LAUNCH, "attention_backward: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL(attention_bwd_tiled_kernel<T>, dim3(B * (d / HDB)), dim3(256), lds, st, static_cast<const T*>(qkv),
+                     static_cast<const T*>(dout), static_cast<T*>(dqkv), B, T_, d, causal, kpm, seq_off);
+  return CMH_OK;
+}
+
 }  // namespace cmh
 
 using namespace cmh;
@@ -431,7 +642,14 @@ int launch_attention_backward(int dtype, const void* qkv, const void* o, const v
   CMH_CHECK_ARG(qkv && o && dout && dqkv && B > 0 && T > 0, "attention_backward: bad arguments");
   CMH_CHECK_ARG(dtype == CMH_F32 || dtype == CMH_BF16, "attention_backward: bad dtype");
   CMH_CHECK_ARG(d % HDB == 0, "attention_backward: width %d is not a multiple of 64", d);
-  CMH_CHECK_ARG(T <= 128, "attention_backward: T=%d > 128 is not built (both CLIP towers have T <= 77)", T);
+  CMH_CHECK_ARG(T <= kAttnBwdMaxT, "attention_backward: T=%d > %d is not built", T, kAttnBwdMaxT);
+  if (T > 128) {                            // the tiled kernel (ViT-B/16, ViT-L/14 image towers); T <= 128 routes as before
+    const int rc = dtype == CMH_F32 ? launch_attention_bwd_tiled<float>(qkv, dout, dqkv, B, T, d, causal, key_padding_mask, seq_off, st)
+                                    : launch_attention_bwd_tiled<bf16_t>(qkv, dout, dqkv, B, T, d, causal, key_padding_mask, seq_off, st);
+    if (rc) return rc;
+    CMH_CHECK_LAUNCH("attention_backward_tiled");
+    return CMH_OK;
+  }
   const size_t lds = (static_cast<size_t>(2) * T * 65 + static_cast<size_t>(T) * (T + 1) + T) * 4;
   const dim3 grid(B * (d / HDB));
   if (dtype == CMH_F32) {

@@ -21,6 +21,8 @@ import mith_ops as M
 from model.base.model import CLIP, Transformer, VisionTransformer, _fill_blocks, convert_weights, no_backward  # noqa: F401
 from streams import overlapped
 
+MITH_MAX_PATCH_TOKENS = 80     # kLtaMaxL of csrc/mith.hip: the token aggregation keeps a sample's tokens in LDS
+
 
 class ViT(VisionTransformer):
     """model/MITH.py:49-82: returns (seq_tokens [g*g, B, E], attn_weight=None, cls_token [B, E])."""
@@ -61,6 +63,9 @@ def build_model(state_dict: dict):
     vision_layers = len([k for k in state_dict if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
     vision_patch_size = state_dict["visual.conv1.weight"].shape[-1]
     grid_size = round((state_dict["visual.positional_embedding"].shape[0] - 1) ** 0.5)
+    if grid_size * grid_size > MITH_MAX_PATCH_TOKENS:
+        raise NotImplementedError(f"MITH's token aggregation (mith_lta) is built for at most {MITH_MAX_PATCH_TOKENS} tokens per sample; "
+                                  f"this checkpoint has {grid_size * grid_size} image patches (ViT-B/32 has 49)")
     embed_dim = state_dict["text_projection"].shape[1]
     tw = state_dict["ln_final.weight"].shape[0]
     layers = len(set(k.split(".")[2] for k in state_dict if k.startswith("transformer.resblocks")))

@@ -178,6 +178,8 @@ def _fill_blocks(resblocks, dt: int, keep: list, act_amax=None):
     return arr
 
 
+FP8_MAX_IMAGE_TOKENS = 128   # the fp8 mode's e4m3-output attention (csrc/attention.hip) is built for T <= 128 (ViT-B/32: 50)
+
 _DT = {"f32": N.F32, "fp32": N.F32, "float32": N.F32, "bf16": N.BF16, "bfloat16": N.BF16, "fp8": N.FP8, "e4m3": N.FP8}
 
 
@@ -203,6 +205,7 @@ class CLIP(nn.Module):
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
         self.initialize_parameters()
         self._gemm_dtype = _DT[os.environ.get("CMH_GEMM_DTYPE", "f32").lower()]
+        self._check_fp8_tokens(self._gemm_dtype)
         self._vit_cache = _TowerCache()
         self._txt_cache = _TowerCache()
         self.assume_frozen = False     # True: skip the per-call parameter-version scan (pure inference)
@@ -242,8 +245,16 @@ class CLIP(nn.Module):
     def set_gemm_dtype(self, name: str):
         """"f32" (parity mode), "bf16" (throughput mode) or "fp8" (BASELINE configs[4]: the blocks' four GEMMs on e4m3 operands;
         inference only; activation scales come from `calibrate_fp8`, run on the first batch if it was not called)."""
-        self._gemm_dtype = _DT[name.lower()]
+        dt = _DT[name.lower()]
+        self._check_fp8_tokens(dt)
+        self._gemm_dtype = dt
         return self
+
+    def _check_fp8_tokens(self, dt):
+        tokens = self.visual.positional_embedding.shape[0]
+        if dt == N.FP8 and tokens > FP8_MAX_IMAGE_TOKENS:
+            raise N.NativeError(f"the fp8 mode is built for at most {FP8_MAX_IMAGE_TOKENS} image tokens; this checkpoint has {tokens} "
+                                "(ViT-B/16 and larger): use set_gemm_dtype('bf16' | 'f32')")
 
     def calibrate_fp8(self, image=None, text=None, reset=True):
         """Calibration pass of the fp8 mode: runs the batch(es) in bf16 mode and records, per block, the largest magnitude of the
