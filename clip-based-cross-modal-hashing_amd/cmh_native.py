@@ -106,6 +106,7 @@ SIGNATURES = {
     "cmh_set_gemm_rows": (C.c_int, [_i32]),
     "cmh_set_gemm_grouped": (C.c_int, [_i32]),
     "cmh_set_gemm_lc": (C.c_int, [_i32]),
+    "cmh_gemm_route": (C.c_int, [_i32] * 8),
     "cmh_set_grad_stream16": (C.c_int, [_i32]),
     "cmh_set_text_token_packing": (C.c_int, [_i32]),
     "cmh_linear_gemm_grouped": (C.c_int, [_i32, C.POINTER(GemmProblem), C.POINTER(GemmProblem), _i32, _p]),
@@ -426,8 +427,20 @@ def set_grad_stream16(on: int):
 
 
 def set_gemm_lc(mode: int):
-    """Loader / consumer GEMM kernel (csrc/gemm_lc.hip): 0 never, 1 every eligible launch, 2 all but QuickGELU launches, 3 cost model."""
+    """Loader / consumer GEMM kernels (csrc/gemm_lc.hip): -1 environment (CMH_GEMM_LC, unset = 8), 0 the wide kernel only, 1 the 8-wave
+    kernel for every eligible launch, 4 the 12-wave 128-row form, 7 the fp8 QKV form, 8 per-launch cost model over the wide kernel and
+    both 12-wave forms (the default), 9 the 12-wave 160-row form for every eligible launch."""
     check(lib().cmh_set_gemm_lc(int(mode)), "cmh_set_gemm_lc")
+
+
+def gemm_route(a, b=None, epi=0, dt=None):
+    """Which kernel takes a bf16 launch of shape a = (M, N, K) (grouped with b) under the current set_gemm_lc mode, without launching
+    it: 0 the wide kernel, 1 the 8-wave loader / consumer kernel, 2 the 12-wave 128-row form, 3 the 12-wave 160-row form."""
+    mb, nb, kb = b if b is not None else (0, 0, 0)
+    rc = lib().cmh_gemm_route(BF16 if dt is None else dt, *a, mb, nb, kb, int(epi))
+    if rc < 0:
+        raise NativeError(f"cmh_gemm_route: {lib().cmh_last_error()}")
+    return rc
 
 
 def gemm_tuning(tile_rows: int = -1, order_group: int = -1):

@@ -64,6 +64,9 @@ struct LcProblem {
 __device__ __forceinline__ int lc_swz(int row, int chunk) { return row * lcRowBytes + ((chunk ^ (row & 7)) << 4); }
 
 #define LC_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
+// a plain LDS load (the 12-wave forms): the compiler places its `s_waitcnt lgkmcnt` and knows the register is not valid before it
+typedef const __attribute__((address_space(3))) lc_u32x4_t* lc_lds_u4p;
+__device__ __forceinline__ lc_u32x4_t lc_lds_read(uint32_t addr) { return *reinterpret_cast<lc_lds_u4p>(static_cast<size_t>(addr)); }
 
 #ifdef LC_STAMPS   // diagnostic build only (tools/lc_stamps.py; make BUILD=build_st EXTRA=-DLC_STAMPS): per workgroup, MFMA wave 0: shader-clock
                    // ticks (s_memtime) of the whole kernel, until the first stage, inside the K loops, inside the epilogues; and the 100 MHz
@@ -631,7 +634,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
   int pend_idx = 8;                                // next parked piece to store (8: none)
   char* pend_base = nullptr;
   uint32_t pend_off0 = 0, pend_ldn = 0;
-  [[maybe_unused]] int res_kt = -1, res_tile = -1;      // RES != 0: at K-step res_kt (-1: never) the residual rows of tile res_tile are fetched into pend
+  [[maybe_unused]] int res_kt = -1;                     // RES != 0: at K-step res_kt (-1: never) the residual rows (residual_of) are fetched into pend
 
   void* out = O0;
   int N = N0, M = M0, nk = nk0;
@@ -654,19 +657,27 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[7]; break;
     }
   };
-  // the fp16 residual rows of tile `ti` into the (free) parked-piece registers, in the packed 16-byte layout of the output
-  [[maybe_unused]] auto fetch_residual = [&](int ti) __attribute__((always_inline)) {
+  // the residual rows the K loop fetches (RES 1: the next tile's, RES 2: this tile's): a uniform base (&residual[m0 + wm * 64][n0 + wn * 64]),
+  // the row stride and the rows that exist from there, formed at the tile's start - the K loop only loads
+  [[maybe_unused]] const uint16_t* rq_base = nullptr;
+  [[maybe_unused]] int rq_ld = 0, rq_rows = 0;
+  [[maybe_unused]] auto residual_of = [&](int ti) __attribute__((always_inline)) {
     bool second; int m0, n0;
     tile_of(ti, second, m0, n0);
-    const uint16_t* res16 = reinterpret_cast<const uint16_t*>(second ? R1 : R0);
-    const int Nn = second ? N1 : N0, Mp = second ? M1 : M0;
-    const int col = n0 + wn * 64 + (fq & 1) * 16 + (fq & 2) * 4;
+    rq_ld = second ? N1 : N0;
+    rq_rows = (second ? M1 : M0) - (m0 + wm * 64);
+    rq_base = reinterpret_cast<const uint16_t*>(second ? R1 : R0) + static_cast<size_t>(m0 + wm * 64) * rq_ld + n0 + wn * 64;
+  };
+  // the fetch: this lane's row of each row block (clamped to the last real row: rows past M are never stored) x 8 consecutive n, into
+  // the (free) parked-piece registers, in the packed 16-byte layout of the output
+  [[maybe_unused]] auto fetch_residual = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      int m = m0 + wm * 64 + b * 16 + frow;
-      m = m < Mp ? m : Mp - 1;
+      int r = b * 16 + frow;
+      r = r < rq_rows ? r : rq_rows - 1;
 #pragma unroll
-      for (int pr = 0; pr < 2; ++pr) pend[2 * b + pr] = *reinterpret_cast<const lc_u32x4_t*>(res16 + static_cast<size_t>(m) * Nn + col + 32 * pr);
+      for (int pr = 0; pr < 2; ++pr)
+        pend[2 * b + pr] = *reinterpret_cast<const lc_u32x4_t*>(rq_base + static_cast<size_t>(r) * rq_ld + (fq & 1) * 16 + (fq & 2) * 4 + 32 * pr);
     }
   };
   // piece (b, pr) of a fetched residual, brought to the accumulator layout (v_permlane16_swap) and ADDED to the two n-fragments it covers
@@ -678,28 +689,17 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     acc[2 * pr + 1][b][0] += f16lo_to_f32(s0[1]); acc[2 * pr + 1][b][1] += f16hi_to_f32(s0[1]);
     acc[2 * pr + 1][b][2] += f16lo_to_f32(s1[1]); acc[2 * pr + 1][b][3] += f16hi_to_f32(s1[1]);
   };
-#define L2_WAIT5(cnt, r0, r1, r2, r3, r4) \
-  asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4)::"memory")
-#define L2_WAIT1(cnt, r0) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(r0)::"memory")
-#define L2_WAIT_ALLW(cnt) asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(fw[0]), "+v"(fw[1]), "+v"(fw[2]), "+v"(fw[3])::"memory")
-#define L2_READ_W(a, addr)                                                       \
-  do {                                                                           \
-    if constexpr ((a) == 0) LC_READ(fw[0], addr, 0);                             \
-    else if constexpr ((a) == 1) LC_READ(fw[1], addr, 2048);                     \
-    else if constexpr ((a) == 2) LC_READ(fw[2], addr, 4096);                     \
-    else LC_READ(fw[3], addr, 6144);                                             \
-  } while (0)
-#define L2_READ_X(fx, b, addr)                                                   \
-  do {                                                                           \
-    if constexpr ((b) == 0) LC_READ(fx[0], addr, 0);                             \
-    else if constexpr ((b) == 1) LC_READ(fx[1], addr, 2048);                     \
-    else if constexpr ((b) == 2) LC_READ(fx[2], addr, 4096);                     \
-    else LC_READ(fx[3], addr, 6144);                                             \
-  } while (0)
+// The fragment reads are plain LDS loads: the compiler counts their returns and waits in front of each first use, so no copy, spill or
+// reuse of a fragment register can come between a read and its wait.  The one wait the protocol itself needs - every read of this
+// stage has landed before the barrier - is an explicit lgkmcnt(0), which the compiler sees as well.
+#define L2_WAIT_ALL() __builtin_amdgcn_s_waitcnt(0xC07F)      // lgkmcnt(0), vmcnt / expcnt untouched
+#define L2_READ_W(a, addr) fw[a] = lc_lds_read((addr) + (a) * 2048)
+#define L2_READ_X(fx, b, addr) fx[b] = lc_lds_read((addr) + (b) * 2048)
 
   int cur = 0;
   if constexpr (RES == 1) {                        // the first tile's accumulators start as its residual rows (0 + r: the wide kernel's bits)
-    fetch_residual(0);
+    residual_of(0);
+    fetch_residual();
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -710,21 +710,20 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       for (int pr = 0; pr < 2; ++pr) add_piece(b, pr, pend[2 * b + pr]);
   }
   __builtin_amdgcn_s_barrier();                    // stage 0 has landed
+  asm volatile("" ::: "memory");
   L2_READ_X(fxa, 0, aX); L2_READ_X(fxa, 1, aX); L2_READ_X(fxa, 2, aX); L2_READ_X(fxa, 3, aX);
   L2_READ_W(0, aW); L2_READ_W(1, aW); L2_READ_W(2, aW); L2_READ_W(3, aW);
 
-  // One K-step.  LDS returns a wave's reads in order; at the top of half 0 the outstanding ones are X''0..3, W''0, W''1, W''2, W''3
-  // (issued in half 1 of the K-step before): fragment W''0 has landed when 3 younger reads may still fly; W''a (a >= 1) when 7 may
-  // (the rest of the W'' plus the four X' and the a W' reads issued since).  Half 1: X'0..3, W'0 | W'1 | W'2 | W'3 -> 3, 2, then all.
+  // One K-step.  Half 0 multiplies (fxa, fw) = k 0..31 and reads k 32..63 of the same stage (fxb; fw in place); half 1 multiplies those,
+  // passes the barrier once every read of this stage has landed, and reads k 0..31 of the next stage (fxa; fw in place).  Every wait
+  // in front of an MFMA is the compiler's.
   auto kstep = [&](int kt) __attribute__((always_inline)) {
     const uint32_t bo = static_cast<uint32_t>(cur) * lcSTG;
     const uint32_t w1 = (aW + bo) ^ 64u, x1 = (aX + bo) ^ 64u;
-    L2_WAIT5(3, fxa[0], fxa[1], fxa[2], fxa[3], fw[0]);
     __builtin_amdgcn_sched_barrier(0);
 #define L2_MFMA0(a, b) acc[a][b] = mfma(fw[a], fxa[b], acc[a][b])
 #define L2_GROUP0(a)                                                                                   \
   do {                                                                                                 \
-    if constexpr ((a) > 0) { L2_WAIT1(7, fw[a]); __builtin_amdgcn_sched_barrier(0); }                  \
     if constexpr ((a) == 0) L2_READ_X(fxb, 0, x1);                                                     \
     L2_MFMA0(a, 0);                                                                                    \
     if constexpr ((a) == 0) L2_READ_X(fxb, 1, x1);                                                     \
@@ -747,7 +746,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (RES != 0) {
-      if (kt == res_kt) { fetch_residual(res_tile); __builtin_amdgcn_sched_barrier(0); }
+      if (kt == res_kt) { fetch_residual(); __builtin_amdgcn_sched_barrier(0); }
     }
     L2_GROUP0(2); L2_GROUP0(3);
 #undef L2_GROUP0
@@ -756,16 +755,14 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     const uint32_t bn = static_cast<uint32_t>(nxt) * lcSTG;
     const uint32_t w0 = aW + bn, x0 = aX + bn;
 #define L2_MFMA1(a, b) acc[a][b] = mfma(fw[a], fxb[b], acc[a][b])
-    L2_WAIT5(3, fxb[0], fxb[1], fxb[2], fxb[3], fw[0]);
     __builtin_amdgcn_sched_barrier(0);
     L2_MFMA1(0, 0); L2_MFMA1(0, 1); L2_MFMA1(0, 2); L2_MFMA1(0, 3);
     __builtin_amdgcn_sched_barrier(0);
-    L2_WAIT1(2, fw[1]);
-    __builtin_amdgcn_sched_barrier(0);
     L2_MFMA1(1, 0); L2_MFMA1(1, 1); L2_MFMA1(1, 2); L2_MFMA1(1, 3);
     __builtin_amdgcn_sched_barrier(0);
-    L2_WAIT_ALLW(0);                               // every fragment of this stage is in registers
+    L2_WAIT_ALL();                                 // every fragment of this stage is in registers
     __builtin_amdgcn_s_barrier();                  // ... in every MFMA wave; the next stage has landed
+    asm volatile("" ::: "memory");                 // (no LDS load moves across it)
     __builtin_amdgcn_sched_barrier(0);
     L2_READ_X(fxa, 0, x0);
     L2_MFMA1(2, 0);
@@ -798,11 +795,12 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
-    if constexpr (RES == 1) { res_tile = ti + 1; res_kt = ti + 1 < my_tiles ? 4 : -1; }      // the NEXT tile's rows, once the parked pieces are out
-    // this tile's own rows, at the same K-step: the registers are free from there on.  (Fetched at K-step nk - 3 instead, ONE build of
-    // this kernel returned garbage in the first row block of some lanes, run to run; the same source rebuilt with a diagnostic macro
-    // beside it - and nk - 6 / - 2 / - 1 - did not.  Not reproduced since, not understood: tools/lc2_stress.py hammers the kept form.)
-    if constexpr (RES == 2) { res_tile = ti; res_kt = 4; }
+    if constexpr (RES == 1) { res_kt = ti + 1 < my_tiles ? 4 : -1; if (ti + 1 < my_tiles) residual_of(ti + 1); }      // the NEXT tile's rows, once the parked pieces are out
+    // this tile's own rows, at the same K-step: the registers are free from there on.  (A build that fetched at K-step nk - 3 once
+    // returned garbage in some lanes' first row block - the symptom of the peeled build above, whose residual addresses went through
+    // scratch inside the K loop.  Both things that build depended on are gone: the addresses are formed here, outside the K loop, and
+    // no fragment register is read before a wait the compiler did not place: DESIGN 4.5.)
+    if constexpr (RES == 2) { res_kt = 4; residual_of(ti); }
     if constexpr (RES != 0) asm volatile("" : "+s"(res_kt));
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("" : "+s"(kt));
@@ -814,8 +812,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       const uint32_t ab = lds_base + 3 * lcSTG + (ti & 1) * 1024 + (wn * 64 + fq * 4) * 4;
       lc_f32x4_t bv[4];
 #pragma unroll
-      for (int a = 0; a < 4; ++a) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[a]) : "v"(ab), "n"(a * 64));
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3])::"memory");
+      for (int a = 0; a < 4; ++a) bv[a] = __builtin_bit_cast(lc_f32x4_t, lc_lds_read(ab + a * 64));
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -892,12 +889,424 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       }
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads issued past the last stage
-#undef L2_WAIT5
-#undef L2_WAIT1
-#undef L2_WAIT_ALLW
+#undef L2_WAIT_ALL
 #undef L2_READ_W
 #undef L2_READ_X
+}
+
+// ---- "lc3": the 12-wave form on the wide kernel's 160-row tile ----------------------------------------------------------------------
+// lc2's 128-row tile is all that its register split holds (64 accumulators + 48 fragment + 32 parked registers), and M = 12 800 is 100
+// row tiles of 128 against the wide kernel's 80 of 160: QKV needs 4 rounds of 256 CUs instead of 3, out_proj / c_proj 2 instead of 1.
+// Here the tile is 160 x 256 (8 MFMA waves of 80 x 64: 5 X and 4 W fragments), and the 168 VGPRs of three waves per SIMD hold it as
+// 80 accumulators + 36 fragment registers + 32 parked-output registers:
+//  - BOTH operands' fragments are refilled in place.  A half-step runs W-outer (group a = fw[a] x fx[0..4]); fw[a] is refilled right
+//    after its group (15 MFMAs before its next use), fx[b] right after the last group's MFMA (3, b) (4 MFMAs before its next use,
+//    covered by the SIMD's other MFMA wave).  Every per-element MFMA chain is lc2's / the wide kernel's: the same bits.
+//  - the parked outputs are row blocks 0..3 (8 pieces, two per K-step under the next tile's first four K-steps); row block 4 leaves
+//    from the epilogue itself; the residual of row blocks 0..3 comes into the freed registers at K-step 4 (RES 1: the next tile's,
+//    RES 2: this tile's), row block 4's is loaded by the epilogue.
+//  - the fragment reads are plain LDS loads: the compiler counts their returns (`s_waitcnt lgkmcnt`) and knows a register is not valid
+//    before its wait, so no copy, spill or reuse of a fragment register can slip between a read and its wait (lc2 reads the same way;
+//    tools/lc_hazards.py checks both).  The residual rows' addresses are formed at the tile's start, outside the K loop.
+constexpr int lc3BM = 160;
+constexpr int lc3STG = lcWBytes + lc3BM * lcRowBytes;      // 52 KB per stage: 3 stages + 2 bias rows = 158 KB of LDS
+
+template <bool GRP, int RES, bool F16O>
+__global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p1, int epi) {
+  __shared__ __attribute__((aligned(1024))) char lds[3 * lc3STG + 2 * 1024];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const char* const X0 = p0.X; const char* const W0 = p0.W; const float* const B0 = p0.bias; void* const O0 = p0.out;
+  const void* const R0 = p0.residual;
+  const int N0 = p0.N, K0 = p0.K;
+  const char* const X1 = p1.X; const char* const W1 = p1.W; const float* const B1 = p1.bias; void* const O1 = p1.out;
+  const void* const R1 = p1.residual;
+  const int N1 = p1.N, K1 = p1.K;
+  int M0 = p0.Mub;
+  if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
+  M0 = __builtin_amdgcn_readfirstlane(M0);
+  int M1 = 0;
+  if constexpr (GRP) {
+    M1 = p1.Mub;
+    if (p1.m_dev) { const int md = *p1.m_dev; M1 = md < M1 ? md : M1; }
+    M1 = __builtin_amdgcn_readfirstlane(M1);
+  }
+  const int tiles_n0 = N0 / lcBN, tiles_n1 = GRP ? N1 / lcBN : 1;
+  const int total0 = tiles_n0 * ((M0 + lc3BM - 1) / lc3BM);
+  const int total1 = GRP ? tiles_n1 * ((M1 + lc3BM - 1) / lc3BM) : 0;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
+  const int q0 = total0 >> 3, r0 = total0 & 7, q1 = total1 >> 3, r1 = total1 & 7;
+  const int lo0 = xcd < r0 ? xcd * (q0 + 1) : r0 * (q0 + 1) + (xcd - r0) * q0, len0 = xcd < r0 ? q0 + 1 : q0;
+  const int lo1 = xcd < r1 ? xcd * (q1 + 1) : r1 * (q1 + 1) + (xcd - r1) * q1, len1 = xcd < r1 ? q1 + 1 : q1;
+  const int n_first = slot < len0 ? (len0 - slot + per - 1) / per : 0;
+  const int span = len0 + len1;
+  const int my_tiles = slot < span ? (span - slot + per - 1) / per : 0;
+  if (my_tiles == 0) return;
+  const int nk0 = K0 / 64, nk1 = GRP ? K1 / 64 : 0;
+  const int S = n_first * nk0 + (my_tiles - n_first) * nk1;
+  auto tile_of = [&](int ti, bool& second, int& m0, int& n0) {
+    const int j = slot + ti * per;
+    second = GRP && ti >= n_first;
+    const int logical = second ? lo1 + (j - len0) : lo0 + j;
+    const int tn_cnt = second ? tiles_n1 : tiles_n0;
+    const int tm = logical / tn_cnt;
+    m0 = tm * lc3BM;
+    n0 = (logical - tm * tn_cnt) * lcBN;
+  };
+
+  if (wid < 4) {
+    // ---- loader waves: lc2's, with 20 X pieces per stage (5 per wave): 13 pieces per wave and stage ----
+    const int sub = lane >> 3, ch = lane & 7;
+    uint32_t offW[8], offX[5];
+    const char* Wt = nullptr;
+    const char* Xt = nullptr;
+    const char* Bt = nullptr;
+    int i_nk = 0;
+    int w_prob = -1;
+    auto set_tile = [&](int ti) {
+      bool second; int m0, n0;
+      tile_of(ti, second, m0, n0);
+      const uint32_t rs = static_cast<uint32_t>(second ? K1 : K0) * 2;
+      if (w_prob != static_cast<int>(second)) {
+        w_prob = static_cast<int>(second);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int row = (wid * 8 + i) * 8 + sub;
+          offW[i] = static_cast<uint32_t>(row) * rs + ((ch ^ (row & 7)) << 4);
+        }
+      }
+      i_nk = second ? nk1 : nk0;
+      const int Mp = second ? M1 : M0;
+      Wt = (second ? W1 : W0) + static_cast<size_t>(n0) * rs;
+      Xt = second ? X1 : X0;
+      Bt = reinterpret_cast<const char*>((second ? B1 : B0) + n0);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        const int row = (wid * 5 + i) * 8 + sub;
+        int xr = m0 + row;
+        xr = xr < Mp ? xr : Mp - 1;
+        offX[i] = static_cast<uint32_t>(xr) * rs + ((ch ^ (row & 7)) << 4);
+      }
+    };
+    int i_tile = 0, i_kt = 0, ibuf = 0;
+    set_tile(0);
+    const bool bias_wave = wid == 0 && (epi & EPI_BIAS);
+    auto issue_stage = [&]() {
+      char* base = lds + ibuf * lc3STG;
+      const uint32_t koff = static_cast<uint32_t>(i_kt) * lcRowBytes;
+      if (i_kt == 0 && bias_wave)      // older than the stage's pieces: every wait that retires the stage retires it
+        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Bt + lane * 16), (lc_lptr_t)(lds + 3 * lc3STG + (i_tile & 1) * 1024), 16, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Wt + koff + offW[i]), (lc_lptr_t)(base + (wid * 8 + i) * 1024), 16, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 5; ++i)
+        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Xt + koff + offX[i]), (lc_lptr_t)(base + lcWBytes + (wid * 5 + i) * 1024), 16, 0, 0);
+      ibuf = ibuf == 2 ? 0 : ibuf + 1;
+      if (++i_kt == i_nk) {
+        i_kt = 0;
+        if (++i_tile < my_tiles) set_tile(i_tile);
+      }
+    };
+    issue_stage();
+    if (S > 1) issue_stage();
+    if (S > 2) issue_stage();
+    if (S > 2) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");        // stage 0 landed; two younger stages may fly
+    else if (S > 1) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (int s = 0; s < S; ++s) {
+      if (s + 2 < S) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (s + 3 < S) issue_stage();
+    }
+    return;
+  }
+
+  // ---- MFMA waves ----
+  const int c = wid - 4;
+  const int wm = c >> 2, wn = c & 3;              // 2 (m) x 4 (n) waves of 80 x 64; the two waves of a SIMD share wn
+  const int frow = lane & 15, fq = lane >> 4;
+  const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lc_lptr_t)lds));
+  const uint32_t aW = lds_base + lc_swz(wn * 64 + frow, fq);
+  const uint32_t aX = lds_base + lcWBytes + lc_swz(wm * 80 + frow, fq);      // (80 rows = 10 x 8: the swizzle's row & 7 is frow & 7)
+
+  lc_f32x4_t acc[4][5];                            // [n-fragment][m-fragment]
+  lc_u32x4_t fw[4], fx[5];
+  lc_u32x4_t pend[8];                              // row blocks 0..3 of the previous tile's packed outputs: piece (b, pr) at 2 b + pr
+  int pend_idx = 8;
+  char* pend_base = nullptr;
+  uint32_t pend_off0 = 0, pend_ldn = 0;
+  [[maybe_unused]] int res_kt = -1;
+  // the residual rows the K loop fetches (RES 1: the next tile's, RES 2: this tile's), set at the tile's start
+  [[maybe_unused]] const uint16_t* rq_base = nullptr;
+  [[maybe_unused]] int rq_ld = 0, rq_rows = 0;     // row stride (elements), rows left from the tile's first row (clamp)
+
+  void* out = O0;
+  int N = N0, M = M0, nk = nk0;
+  [[maybe_unused]] auto to_problem1 = [&]() { out = O1; N = N1; M = M1; nk = nk1; };
+  if constexpr (GRP) { if (n_first == 0) to_problem1(); }
+
+  auto mfma = [&](const lc_u32x4_t& w, const lc_u32x4_t& x, const lc_f32x4_t& cin) __attribute__((always_inline)) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lc_bf16x8_t, w), __builtin_bit_cast(lc_bf16x8_t, x), cin, 0, 0, 0);
+  };
+  auto store_pending = [&](int idx) __attribute__((always_inline)) {
+    char* p = pend_base + (pend_off0 + static_cast<uint32_t>(idx >> 1) * 16u * pend_ldn + static_cast<uint32_t>(idx & 1) * 64u);
+    switch (idx) {
+      case 0: *reinterpret_cast<lc_u32x4_t*>(p) = pend[0]; break;
+      case 1: *reinterpret_cast<lc_u32x4_t*>(p) = pend[1]; break;
+      case 2: *reinterpret_cast<lc_u32x4_t*>(p) = pend[2]; break;
+      case 3: *reinterpret_cast<lc_u32x4_t*>(p) = pend[3]; break;
+      case 4: *reinterpret_cast<lc_u32x4_t*>(p) = pend[4]; break;
+      case 5: *reinterpret_cast<lc_u32x4_t*>(p) = pend[5]; break;
+      case 6: *reinterpret_cast<lc_u32x4_t*>(p) = pend[6]; break;
+      default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[7]; break;
+    }
+  };
+  // residual tile `ti`: uniform base (&residual[m0 + wm * 80][n0 + wn * 64]), row stride, rows that exist from there
+  [[maybe_unused]] auto residual_of = [&](int ti, const uint16_t*& base, int& ld, int& rows) __attribute__((always_inline)) {
+    bool second; int m0, n0;
+    tile_of(ti, second, m0, n0);
+    ld = second ? N1 : N0;
+    rows = (second ? M1 : M0) - (m0 + wm * 80);
+    base = reinterpret_cast<const uint16_t*>(second ? R1 : R0) + static_cast<size_t>(m0 + wm * 80) * ld + n0 + wn * 64;
+  };
+  // piece (b, pr) of a residual: this lane's row (clamped to the last real row: rows past M are never stored) x 8 consecutive n
+  [[maybe_unused]] auto res_piece = [&](const uint16_t* base, int ld, int rows, int b, int pr) __attribute__((always_inline)) {
+    int r = b * 16 + frow;
+    r = r < rows ? r : rows - 1;
+    return *reinterpret_cast<const lc_u32x4_t*>(base + static_cast<size_t>(r) * ld + (fq & 1) * 16 + (fq & 2) * 4 + 32 * pr);
+  };
+  [[maybe_unused]] auto add_piece = [&](int b, int pr, const lc_u32x4_t& qv) __attribute__((always_inline)) {
+    const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(qv[0], qv[2], false, false);
+    const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(qv[1], qv[3], false, false);
+    acc[2 * pr][b][0] += f16lo_to_f32(s0[0]); acc[2 * pr][b][1] += f16hi_to_f32(s0[0]);
+    acc[2 * pr][b][2] += f16lo_to_f32(s1[0]); acc[2 * pr][b][3] += f16hi_to_f32(s1[0]);
+    acc[2 * pr + 1][b][0] += f16lo_to_f32(s0[1]); acc[2 * pr + 1][b][1] += f16hi_to_f32(s0[1]);
+    acc[2 * pr + 1][b][2] += f16lo_to_f32(s1[1]); acc[2 * pr + 1][b][3] += f16hi_to_f32(s1[1]);
+  };
+
+  int cur = 0;
+  if constexpr (RES == 1) {                        // the first tile's accumulators start as its residual rows (0 + r: the wide kernel's bits)
+    const uint16_t* rb; int ld, rows;
+    residual_of(0, rb, ld, rows);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 5; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr) add_piece(b, pr, res_piece(rb, ld, rows, b, pr));
+  }
+  __builtin_amdgcn_s_barrier();                    // stage 0 has landed
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int b = 0; b < 5; ++b) fx[b] = lc_lds_read(aX + b * 2048);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) fw[a] = lc_lds_read(aW + a * 2048);
+
+  // One half-step: group a = fw[a] x fx[0..4], W-outer; fw[a] refilled from (wsrc) after its group, fx[b] from (xsrc) after MFMA (3, b)
+  // and fw[3] last.  `mid` runs between groups 1 and 2 (half 0: the parked stores and the residual fetch; half 1: every read of this
+  // stage has landed in every wave - the barrier - before the first read of the next stage)
+#define L3_GROUP(a)                                                                                    \
+  do {                                                                                                 \
+    acc[a][0] = mfma(fw[a], fx[0], acc[a][0]);                                                         \
+    acc[a][1] = mfma(fw[a], fx[1], acc[a][1]);                                                         \
+    acc[a][2] = mfma(fw[a], fx[2], acc[a][2]);                                                         \
+    acc[a][3] = mfma(fw[a], fx[3], acc[a][3]);                                                         \
+    acc[a][4] = mfma(fw[a], fx[4], acc[a][4]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+#define L3_LAST(wsrc, xsrc)                                                                            \
+  do {                                                                                                 \
+    acc[3][0] = mfma(fw[3], fx[0], acc[3][0]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[0] = lc_lds_read((xsrc));                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    acc[3][1] = mfma(fw[3], fx[1], acc[3][1]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[1] = lc_lds_read((xsrc) + 2048);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    acc[3][2] = mfma(fw[3], fx[2], acc[3][2]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[2] = lc_lds_read((xsrc) + 4096);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    acc[3][3] = mfma(fw[3], fx[3], acc[3][3]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[3] = lc_lds_read((xsrc) + 6144);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    acc[3][4] = mfma(fw[3], fx[4], acc[3][4]);                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[4] = lc_lds_read((xsrc) + 8192);                                                                \
+    fw[3] = lc_lds_read((wsrc) + 6144);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+#define L3_REFILL_W(a, wsrc)                                                                           \
+  do {                                                                                                 \
+    fw[a] = lc_lds_read((wsrc) + (a) * 2048);                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+
+  auto kstep = [&](int kt) __attribute__((always_inline)) {
+    const uint32_t bo = static_cast<uint32_t>(cur) * lc3STG;
+    const uint32_t w1 = (aW + bo) ^ 64u, x1 = (aX + bo) ^ 64u;      // k 32..63 of this stage
+    // ---------------- half 0 ----------------
+    L3_GROUP(0); L3_REFILL_W(0, w1);
+    L3_GROUP(1); L3_REFILL_W(1, w1);
+    if (pend_idx < 8) {                               // two 16-byte pieces of the previous tile per K-step: gone after four
+      store_pending(pend_idx); store_pending(pend_idx + 1);
+      pend_idx += 2;
+      asm volatile("" : "+s"(pend_idx));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (RES != 0) {
+      if (kt == res_kt) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int pr = 0; pr < 2; ++pr) pend[2 * b + pr] = res_piece(rq_base, rq_ld, rq_rows, b, pr);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    L3_GROUP(2); L3_REFILL_W(2, w1);
+    L3_LAST(w1, x1);
+    // ---------------- half 1 ----------------
+    const int nxt = cur == 2 ? 0 : cur + 1;
+    const uint32_t bn = static_cast<uint32_t>(nxt) * lc3STG;
+    const uint32_t w0 = aW + bn, x0 = aX + bn;      // k 0..31 of the next stage
+    L3_GROUP(0);
+    L3_GROUP(1);
+    __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): every fragment of this stage is in registers ...
+    __builtin_amdgcn_s_barrier();                  // ... in every MFMA wave; the next stage has landed
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    L3_REFILL_W(0, w0); L3_REFILL_W(1, w0);
+    L3_GROUP(2); L3_REFILL_W(2, w0);
+    L3_LAST(w0, x0);
+    cur = nxt;
+  };
+
+  for (int ti = 0; ti < my_tiles; ++ti) {
+    bool second; int m0, n0;
+    tile_of(ti, second, m0, n0);
+    if constexpr (GRP) { if (ti == n_first && ti > 0) to_problem1(); }
+    if constexpr (RES != 1) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 5; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
+    if constexpr (RES == 1) { res_kt = ti + 1 < my_tiles ? 4 : -1; if (ti + 1 < my_tiles) residual_of(ti + 1, rq_base, rq_ld, rq_rows); }
+    if constexpr (RES == 2) { res_kt = 4; residual_of(ti, rq_base, rq_ld, rq_rows); }
+    if constexpr (RES != 0) asm volatile("" : "+s"(res_kt));
+    for (int kt = 0; kt < nk; ++kt) {
+      asm volatile("" : "+s"(kt));
+      kstep(kt);
+    }
+    // nk >= 8 (host): every parked piece has left after four K-steps
+
+    // row block 4's residual (not parked): RES 2 this tile's, RES 1 the next tile's
+    [[maybe_unused]] lc_u32x4_t r4[2];
+    if constexpr (RES == 2) { r4[0] = res_piece(rq_base, rq_ld, rq_rows, 4, 0); r4[1] = res_piece(rq_base, rq_ld, rq_rows, 4, 1); }
+    if constexpr (RES == 1) {
+      if (res_kt >= 0) { r4[0] = res_piece(rq_base, rq_ld, rq_rows, 4, 0); r4[1] = res_piece(rq_base, rq_ld, rq_rows, 4, 1); }
+    }
+    if (epi & EPI_BIAS) {
+      const uint32_t ab = lds_base + 3 * lc3STG + (ti & 1) * 1024 + (wn * 64 + fq * 4) * 4;
+      lc_f32x4_t bv[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) bv[a] = __builtin_bit_cast(lc_f32x4_t, lc_lds_read(ab + a * 64));
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 5; ++b) acc[a][b] += bv[a];
+    }
+    if (epi & EPI_QUICKGELU) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 5; ++b)
+#pragma unroll
+          for (int j = 0; j < 4; j += 2) {
+            const lc_f32x2_t v = {acc[a][b][j], acc[a][b][j + 1]};
+            const lc_f32x2_t t = v * lc_f32x2_t{-2.4554669595930157f, -2.4554669595930157f};
+            const lc_f32x2_t d = lc_f32x2_t{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + lc_f32x2_t{1.0f, 1.0f};
+            const lc_f32x2_t o = v * lc_f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+            acc[a][b][j] = o[0];
+            acc[a][b][j + 1] = o[1];
+          }
+    }
+    if constexpr (RES == 2) {                        // long K: the residual behind the bias
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) add_piece(b, pr, pend[2 * b + pr]);
+      add_piece(4, 0, r4[0]); add_piece(4, 1, r4[1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      char* const obase = static_cast<char*>(out) + (static_cast<size_t>(m0) * N + n0) * 2;       // uniform
+      const uint32_t ldn = static_cast<uint32_t>(N) * 2;
+      const uint32_t off0 = static_cast<uint32_t>(wm * 80 + frow) * ldn + static_cast<uint32_t>(wn * 64 + (fq & 1) * 16 + (fq & 2) * 4) * 2;
+      const bool full = m0 + lc3BM <= M;
+      lc_u32x4_t own4[2];                            // row block 4: stored here
+#pragma unroll
+      for (int b = 0; b < 5; ++b)
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+          uint32_t lo[2], hi[2];
+#pragma unroll
+          for (int w = 0; w < 2; ++w) {
+            if constexpr (F16O) {
+              lo[w] = pack_f16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
+              hi[w] = pack_f16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
+            } else {
+              lo[w] = pack_bf16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
+              hi[w] = pack_bf16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
+            }
+          }
+          const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(lo[0], hi[0], false, false);
+          const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(lo[1], hi[1], false, false);
+          if constexpr (RES == 1) {                  // the rotation: this piece's accumulators restart as the next tile's residual piece
+            const lc_u32x4_t nextres = b < 4 ? pend[2 * b + pr] : r4[pr];
+            acc[2 * pr][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            acc[2 * pr + 1][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            if (res_kt >= 0) add_piece(b, pr, nextres);
+          }
+          const lc_u32x4_t val = {s0[0], s1[0], s0[1], s1[1]};
+          if (b < 4) pend[2 * b + pr] = val;
+          else own4[pr] = val;
+        }
+      if (!(epi & 256)) {
+        if (full) {
+#pragma unroll
+          for (int pr = 0; pr < 2; ++pr) *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + 64u * ldn + pr * 64)) = own4[pr];
+        } else if (m0 + wm * 80 + 64 + frow < M) {
+#pragma unroll
+          for (int pr = 0; pr < 2; ++pr) *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + 64u * ldn + pr * 64)) = own4[pr];
+        }
+      }
+      pend_base = obase; pend_off0 = off0; pend_ldn = ldn;
+      if (full && ti + 1 < my_tiles && !(epi & 256)) {
+        pend_idx = 0;                              // the next tile's first four K-steps carry row blocks 0..3 out
+        asm volatile("" : "+s"(pend_idx));
+      } else if (!(epi & 256)) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int pr = 0; pr < 2; ++pr)
+            if (m0 + wm * 80 + b * 16 + frow < M)
+              *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + static_cast<uint32_t>(b * 16) * ldn + pr * 64)) = pend[2 * b + pr];
+      }
+    }
+  }
+#undef L3_GROUP
+#undef L3_LAST
+#undef L3_REFILL_W
 }
 
 int gemm_lc_mode();
@@ -1153,24 +1562,66 @@ bool gemm_lc2q_takes(int N, int K, int epi) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static int lc_env_mode() { static const int m = []() { const char* e = getenv("CMH_GEMM_LC"); return e ? atoi(e) : 0; }(); return m; }
-static int g_lc_mode = -1;         // cmh_set_gemm_lc: -1 = environment (CMH_GEMM_LC, default 0 = off)
+static int lc_env_mode() { static const int m = []() { const char* e = getenv("CMH_GEMM_LC"); return e ? atoi(e) : 8; }(); return m; }
+static int g_lc_mode = -1;         // cmh_set_gemm_lc: -1 = environment (CMH_GEMM_LC, default 8 = per-launch route; 0 = the wide kernel only)
 int gemm_lc_mode() { return g_lc_mode < 0 ? lc_env_mode() : g_lc_mode; }
 void gemm_lc_set_mode(int m) { g_lc_mode = m; }
 
 // bf16 operands, 16-bit output, the forward epilogues of a transformer block (bias, + QuickGELU, + fp16 residual), N % 256 == 0
 bool gemm_lc_takes(int dt, int N, int K, int epi) {
   if (dt != CMH_BF16 || N % lcBN != 0 || K % 64 != 0 || K < 256) return false;      // >= 4 K-steps per tile: the bias slots' reuse distance
-  if (gemm_lc_mode() >= 4) {      // the 12-wave form (lc2): its parked stores need 8 K-steps per tile
+  if (gemm_lc_mode() >= 4) {      // the 12-wave forms (lc2, lc3): their parked stores need 8 K-steps per tile
     if (K < 512) return false;
-    if (gemm_lc_mode() >= 5 && (epi & EPI_QUICKGELU)) return false;
-    if (gemm_lc_mode() == 6 && (epi & EPI_RESIDUAL) && K / 64 > 16) return false;      // 6: QKV and out_proj only (where it measured level or better)
   }
   if (!(epi & (EPI_OUT_BF16 | EPI_OUT_F16)) || ((epi & EPI_OUT_BF16) && (epi & EPI_OUT_F16))) return false;
   if (epi & ~(EPI_BIAS | EPI_QUICKGELU | EPI_RESIDUAL | EPI_RES_F16 | EPI_OUT_BF16 | EPI_OUT_F16 | 256)) return false;
   if ((epi & EPI_RESIDUAL) && !((epi & EPI_RES_F16) && (epi & EPI_OUT_F16))) return false;      // a residual = the fp16 stream, in and out
   if ((epi & EPI_RESIDUAL) && (epi & EPI_QUICKGELU)) return false;
   return true;
+}
+
+// Which kernel takes a bf16 launch (b: the second problem of a grouped launch): 0 the wide kernel, 1 the 8-wave lc kernel, 2 the
+// 12-wave form on 128-row tiles (lc2), 3 on 160-row tiles (lc3).  Mode 8 (the default) prices the wide kernel (`wide_cost`, the units
+// of gemm_wide.hip's tile-height model: the worst workgroup's K-steps + 4 per tile, x rows / 32 x 10 + 6) against the 160-row form
+// in the same units - the kernel's static tile assignment replayed for its tile height - times what a K-step of it costs against
+// the wide kernel's (profiles/r06_a_lc_per_shape.txt), and takes the cheaper.
+static long long lc_cost(const GemmProblem& a, const GemmProblem* b, int rows, int cus) {
+  auto likely = [](const GemmProblem& g) { return g.m_dev && g.m_hint > 0 && g.m_hint <= g.M ? g.m_hint : g.M; };
+  auto tiles_of = [&](int M, int N) { return (N / lcBN) * ((M + rows - 1) / rows); };
+  const int total = tiles_of(a.M, a.N) + (b ? tiles_of(b->M, b->N) : 0);
+  const int per = (total < cus ? ((total + 7) & ~7) : cus) >> 3;
+  const int t0 = tiles_of(likely(a), a.N), t1 = b ? tiles_of(likely(*b), b->N) : 0;
+  const int nk0 = a.K / 64, nk1 = b ? b->K / 64 : 0;
+  long long worst = 0;
+  for (int x = 0; x < 8; ++x) {
+    const int len0 = (t0 >> 3) + (x < (t0 & 7)), len1 = (t1 >> 3) + (x < (t1 & 7));
+    for (int sl = 0; sl < per; ++sl) {
+      const int n0 = sl < len0 ? (len0 - sl + per - 1) / per : 0;
+      const int nall = sl < len0 + len1 ? (len0 + len1 - sl + per - 1) / per : 0;
+      const long long c = static_cast<long long>(n0) * (nk0 + 4) + static_cast<long long>(nall - n0) * (nk1 + 4);
+      worst = c > worst ? c : worst;
+    }
+  }
+  return worst * (10 * (rows / 32) + 6);
+}
+static int lc_cus();
+bool gemm_lc_res_first(int epi, int K);
+int gemm_lc_form(int dt, const GemmProblem& a, const GemmProblem* b, int epi, long long wide_cost) {
+  const int mode = gemm_lc_mode();
+  if (!gemm_lc_takes(dt, a.N, a.K, epi) || (b && (!gemm_lc_takes(dt, b->N, b->K, epi) || gemm_lc_res_first(epi, a.K) != gemm_lc_res_first(epi, b->K))))
+    return 0;
+  if (mode >= 1 && mode <= 3) return 1;
+  if (mode == 4) return 2;
+  if (mode == 9) return 3;
+  if (mode != 8) return 0;
+  // The 160-row form against the wide kernel: its K-step priced at 56/64 of the wide kernel's (83 % MFMA issue against 65-72 %), its
+  // tiles by the same static assignment.  It never takes a residual launch: its residual forms spill 27-28 scratch instructions per
+  // tile in the epilogue (none in the K loop) and measured 1.02-1.5 x the wide kernel on all six (profiles/r06_a_lc_per_shape.txt).
+  // The 128-row form (lc2) is not routed: with its reads compiler-counted it measured 1.08 x on grouped out_proj, the one block launch
+  // where the hand-counted form had won (0.93; profiles/r06_d_route_ab.txt), and it stays an opt-in (mode 4).
+  if (epi & EPI_RESIDUAL) return 0;
+  if (lc_cost(a, b, lc3BM, lc_cus()) * 56 / 64 < wide_cost) return 3;
+  return 0;
 }
 
 // the wide kernel's residual-first rule (gemm_wide.hip, res_first): per GEMM
@@ -1191,7 +1642,7 @@ static int lc_cus() {
 }
 
 // b == nullptr: one problem.  The problem with the longer K goes first (its tiles are the long jobs of the static schedule).
-int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int form) {
   for (const GemmProblem* g : {&a, b}) {
     if (!g) continue;
     if (static_cast<size_t>(g->M) * g->K * 2 >= (1ull << 32) || static_cast<size_t>(lcBN) * g->K * 2 >= (1ull << 32))
@@ -1205,7 +1656,32 @@ int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStrea
   const int total = tiles_of(a) + (b ? tiles_of(*b) : 0);
   const int grid = total < cus ? ((total + 7) & ~7) : cus;     // sized for the upper bounds: workgroups without a tile exit at once
   const LcProblem P0 = prob(a), P1 = b ? prob(*b) : LcProblem{};
-  if (gemm_lc_mode() >= 4) {
+  if (form == 3) {      // the 160-row 12-wave form
+    const int grid3 = [&]() {
+      const int t = (a.N / lcBN) * ((a.M + lc3BM - 1) / lc3BM) + (b ? (b->N / lcBN) * ((b->M + lc3BM - 1) / lc3BM) : 0);
+      return t < cus ? ((t + 7) & ~7) : cus;
+    }();
+    const int res3 = !(epi & EPI_RESIDUAL) ? 0 : (gemm_lc_res_first(epi, a.K) ? 1 : 2);
+    const bool f16 = (epi & EPI_OUT_F16) != 0;
+#define LC3_GO(G, R, F)                                                                                                       \
+  do {                                                                                                                       \
+    if (ev0) hipExtLaunchKernelGGL((gemm_lc3_kernel<G, R, F>), dim3(grid3), dim3(768), 0, st, ev0, ev1, 0, P0, P1, epi);     \
+    else hipLaunchKernelGGL((gemm_lc3_kernel<G, R, F>), dim3(grid3), dim3(768), 0, st, P0, P1, epi);                         \
+  } while (0)
+#define LC3_GO_G(G)                                                                                                           \
+  do {                                                                                                                       \
+    if (res3 == 1) LC3_GO(G, 1, true);                                                                                       \
+    else if (res3 == 2) LC3_GO(G, 2, true);                                                                                  \
+    else if (f16) LC3_GO(G, 0, true);                                                                                        \
+    else LC3_GO(G, 0, false);                                                                                                \
+  } while (0)
+    if (b) LC3_GO_G(true); else LC3_GO_G(false);
+#undef LC3_GO_G
+#undef LC3_GO
+    CMH_CHECK_LAUNCH("gemm (lc3)");
+    return 0;
+  }
+  if (form == 2) {
     const int res2 = !(epi & EPI_RESIDUAL) ? 0 : (gemm_lc_res_first(epi, a.K) ? 1 : 2);
     const bool f16 = (epi & EPI_OUT_F16) != 0;
 #define LC2_GO(G, R, F)                                                                                                       \
@@ -1271,7 +1747,7 @@ extern "C" int cmh_debug_lc_stamps(unsigned long long* host_out) {
 #endif
 
 extern "C" int cmh_set_gemm_lc(int32_t mode) {
-  CMH_CHECK_ARG(mode >= -1 && mode <= 7, "set_gemm_lc: mode %d (-1 environment, 0 off, 1 every eligible launch, 2 all but QuickGELU launches, 3 by cost model, 4 / 5 / 6 the 12-wave form for every block launch / without the QuickGELU ones / for QKV and out_proj only)", mode);
+  CMH_CHECK_ARG(mode >= -1 && mode <= 9 && mode != 5 && mode != 6, "set_gemm_lc: mode %d (-1 environment, 0 the wide kernel only, 1 every eligible launch, 2 all but QuickGELU launches, 3 by cost model, 4 the 12-wave 128-row form for every block launch, 7 fp8 QKV, 8 per-launch route (default), 9 the 12-wave 160-row form for every block launch)", mode);
   cmh::gemm_lc_set_mode(mode);
   return CMH_OK;
 }

@@ -1398,7 +1398,8 @@ void gemm_wide_time_next(hipEvent_t start, hipEvent_t stop) { g_wide_ev0 = start
 int gemm_lc_mode();
 bool gemm_lc_takes(int dt, int N, int K, int epi);
 bool gemm_lc_res_first(int epi, int K);
-int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int form);
+int gemm_lc_form(int dt, const GemmProblem& a, const GemmProblem* b, int epi, long long wide_cost);
 bool g_force_rows_set();
 int launch_gemm_lc2q(const GemmProblem& g, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 bool gemm_lc2q_takes(int N, int K, int epi);
@@ -1637,14 +1638,19 @@ int launch_gemm_wide_tn_multi(const TnMultiJob* jobs, int n, float* partials, si
   return 0;
 }
 
+static long long wide_plain_cost(int dt, const GemmProblem& g, int epi, int cus);
+static int wide_route(int dt, const GemmProblem& a, const GemmProblem* b, int epi);
 int launch_gemm_wide(int dt, const void* A, const void* W, const float* bias, const float* residual, void* out,
                      int M, int N, int K, int epi, hipStream_t st, const float* colscale, float alpha, float oscale,
                      const int32_t* m_dev, int m_hint) {
-  if (wide_goes_lc(dt, epi) && gemm_lc_takes(dt, N, K, epi)) {
+  {
     const GemmProblem g{A, W, bias, residual, out, M, N, K, m_dev, m_hint, nullptr, 1.f, 1.f};
-    const int rc = launch_gemm_lc(g, nullptr, epi, st, g_wide_ev0, g_wide_ev1);
-    g_wide_ev0 = g_wide_ev1 = nullptr;
-    return rc;
+    const int form = wide_route(dt, g, nullptr, epi);
+    if (form) {
+      const int rc = launch_gemm_lc(g, nullptr, epi, st, g_wide_ev0, g_wide_ev1, form);
+      g_wide_ev0 = g_wide_ev1 = nullptr;
+      return rc;
+    }
   }
   if (dt == CMH_FP8 && !g_force_rows_set() && gemm_lc2q_takes(N, K, epi)) {      // the 12-wave form on e4m3 operands (experiment, CMH_GEMM_LC=7)
     const GemmProblem g{A, W, bias, residual, out, M, N, K, m_dev, m_hint, colscale, alpha, oscale};
@@ -1799,12 +1805,24 @@ static long long wide_grouped_cost(int dt, const GemmProblem& a, const GemmProbl
   return cost(mf);
 }
 
+// Which kernel takes a launch (b: the second problem of a grouped launch): 0 this file's wide kernel, else the gemm_lc.hip form
+// gemm_lc_form names (1 the 8-wave kernel, 2 the 12-wave 128-row form, 3 the 12-wave 160-row form).  Host-only; cmh_gemm_route
+// asks it without launching.
+static int wide_route(int dt, const GemmProblem& a, const GemmProblem* b, int epi) {
+  if (!wide_goes_lc(dt, epi) || !gemm_lc_takes(dt, a.N, a.K, epi)) return 0;
+  if (!b) return gemm_lc_form(dt, a, nullptr, epi, wide_plain_cost(dt, a, epi, wide_cus()));
+  if (!gemm_lc_takes(dt, b->N, b->K, epi) || gemm_lc_res_first(epi, a.K) != gemm_lc_res_first(epi, b->K)) return 0;
+  return gemm_lc_form(dt, a, b, epi, wide_grouped_cost(dt, a, *b, epi, wide_cus(), nullptr));
+}
+
 int launch_gemm_wide_grouped(int dt, const GemmProblem& a, const GemmProblem& b, int epi, hipStream_t st) {
-  if (wide_goes_lc(dt, epi) && gemm_lc_takes(dt, a.N, a.K, epi) && gemm_lc_takes(dt, b.N, b.K, epi) &&
-      gemm_lc_res_first(epi, a.K) == gemm_lc_res_first(epi, b.K)) {
-    const int rc = launch_gemm_lc(a, &b, epi, st, g_wide_ev0, g_wide_ev1);
-    g_wide_ev0 = g_wide_ev1 = nullptr;
-    return rc;
+  {
+    const int form = wide_route(dt, a, &b, epi);
+    if (form) {
+      const int rc = launch_gemm_lc(a, &b, epi, st, g_wide_ev0, g_wide_ev1, form);
+      g_wide_ev0 = g_wide_ev1 = nullptr;
+      return rc;
+    }
   }
   const size_t esz = dt == CMH_F32 ? 4 : (dt == CMH_FP8 ? 1 : 2);
   for (const GemmProblem* g : {&a, &b})
@@ -1855,6 +1873,14 @@ int launch_gemm_wide_grouped(int dt, const GemmProblem& a, const GemmProblem& b,
 }
 
 }  // namespace cmh
+
+extern "C" int cmh_gemm_route(int32_t dt, int32_t Ma, int32_t Na, int32_t Ka, int32_t Mb, int32_t Nb, int32_t Kb, int32_t epi) {
+  using namespace cmh;
+  CMH_CHECK_ARG(Ma > 0 && Na > 0 && Ka > 0 && Mb >= 0, "gemm_route: shape %d x %d x %d / %d rows", Ma, Na, Ka, Mb);
+  const GemmProblem a{nullptr, nullptr, nullptr, nullptr, nullptr, Ma, Na, Ka, nullptr, 0, nullptr, 1.f, 1.f};
+  const GemmProblem b{nullptr, nullptr, nullptr, nullptr, nullptr, Mb, Nb, Kb, nullptr, 0, nullptr, 1.f, 1.f};
+  return wide_route(dt, a, Mb > 0 ? &b : nullptr, epi);
+}
 
 extern "C" int cmh_gemm_tuning(int32_t tile_rows, int32_t order_group) {
   using namespace cmh;

@@ -251,10 +251,16 @@ int cmh_set_gemm_rows(int32_t on);
  * LDS-DMA, the other four only multiply; 128 x 256 tiles; bf16 operands with 16-bit outputs and the forward epilogues of a transformer
  * block: bias, + QuickGELU, + fp16 residual; plain and grouped launches).  Same bits per output element as the wide kernel (same MFMA
  * chain over K, same epilogue order).  mode 0: never; 1: every launch it can take; 2: every such launch without QuickGELU;
- * 3: where the host's cost model expects it to be faster; 4 / 5 / 6: the 12-wave form (4 staging + 8 MFMA waves, stores deferred) for
- * every block launch with K >= 512 / for those without QuickGELU / for QKV and out_proj only, the wide kernel elsewhere; 7: the form on e4m3 operands (fp8 QKV launches); -1: the environment's
- * CMH_GEMM_LC (default).  Process-wide, not thread-safe. */
+ * 3: where the host's cost model expects it to be faster; 4: the 12-wave form (4 staging + 8 MFMA waves, stores deferred, 128-row
+ * tiles) for every block launch with K >= 512, the wide kernel elsewhere; 7: the form on e4m3 operands (fp8 QKV launches);
+ * 8: per bf16 launch, whichever of the wide kernel, the 12-wave 128-row form and the 12-wave 160-row form the cost model prices lowest;
+ * 9: the 12-wave 160-row form for every block launch with K >= 512; -1: the environment's CMH_GEMM_LC (default; unset = 8,
+ * CMH_GEMM_LC=0 = the wide kernel only).  Process-wide, not thread-safe. */
 int cmh_set_gemm_lc(int32_t mode);
+/* Which kernel the current cmh_set_gemm_lc mode gives a launch of operand type dt (CMH_BF16, ...) and epilogue flags epi:
+ * Ma x Na x Ka alone (Mb = 0) or grouped with Mb x Nb x Kb.  0 the wide kernel, 1 the 8-wave loader / consumer kernel, 2 the
+ * 12-wave 128-row form, 3 the 12-wave 160-row form.  Host-only: nothing is launched.  Returns -1 on a bad shape. */
+int cmh_gemm_route(int32_t dt, int32_t Ma, int32_t Na, int32_t Ka, int32_t Mb, int32_t Nb, int32_t Kb, int32_t epi);
 
 /* encode_image / encode_text return one pooled row per sample (model/base/model.py:247-250, 366-370), and past the last block's
  * attention every operation is row-wise, so cmh_vit_encode / cmh_text_encode[_packed] carry only those B rows through the last
