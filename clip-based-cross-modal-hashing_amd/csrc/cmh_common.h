@@ -164,8 +164,20 @@ int launch_layernorm_x(const void* x, int x_f16, const int32_t* row_index, const
 int launch_layernorm_h2b_pair(const void* x0, const float* w0, const float* b0, void* out0, int M0, int d0, const int32_t* md0,
                                const void* x1, const float* w1, const float* b1, void* out1, int M1, int d1, const int32_t* md1,
                                hipStream_t st);
-// image [B,3,R,R] f32 -> patches [B*g*g, 3*p*p] (dt)
-int launch_patchify(const float* image, void* patches, int dt, int B, int R, int p, hipStream_t st);
+// conv1's patch-matrix K for patch p in GEMM dtype dt (fp8 mode: its conv1 is the bf16 mode's): 3p^2 where the patch matrix suits the
+// GEMMs as it is (p % 4 == 0 for the float4 gather, 3p^2 a multiple of the K-step).  Otherwise (ViT-L/14: 588) the patch matrix and
+// the conv1 weight get zero columns up to a multiple of 256: the forward GEMM needs the K-step (64 / 32), and the conv1 weight
+// gradient - a GEMM whose N is this K - needs N % 128 (launch_gemm) and N % 256 for the wide kernel and its split-K.  588 -> 768,
+// the K that patch 16 runs with.
+static inline int conv1_k(int p, int dt) {
+  const int pk = 3 * p * p, ks = dt == CMH_F32 ? 32 : 64;
+  return p % 4 == 0 && pk % ks == 0 ? pk : static_cast<int>(align_up(static_cast<size_t>(pk), 256));
+}
+// image [B,3,R,R] f32 -> patches [B*g*g, ld] (dt), columns [0, 3p^2) the patch, [3p^2, ld) zeros; ld >= 3p^2
+int launch_patchify(const float* image, void* patches, int dt, int B, int R, int p, int ld, hipStream_t st);
+// dst[r, 0:cols) = src[r, 0:cols), dst[r, cols:ldd) = 0 for r < rows; elements of esz = 2 or 4 bytes (the padded conv1 weight and the
+// compaction of its gradient)
+int launch_copy_cols(const void* src, int lds, void* dst, int ldd, int rows, int cols, int esz, hipStream_t st);
 // tokens: x[b,0]=cls+pos[0]; x[b,1+i]=patch_out[b*g2+i]+pos[1+i]; then ln_pre -> x f32|f16 [B*(g2+1), d]
 int launch_vit_assemble_lnpre(const float* patch_out, const float* cls, const float* pos,
                               const float* lnw, const float* lnb, void* x, int x_f16, int B, int g2, int d,

@@ -11,7 +11,7 @@
 //                      CMH_RESID_F16=0, widths that are not a multiple of 256 or a taps request keep it fp32.
 //   h    e   [M, d]    LayerNorm output / attention output (GEMM A operand)
 //   qkv  e   [M, 3d]   packed in_proj output            (vision: patch_out f32 [B*g2, d] aliases it)
-//   mlp  e   [M, 4d]   c_fc output after QuickGELU      (vision: patches e [B*g2, 3p^2] aliases it)
+//   mlp  e   [M, 4d]   c_fc output after QuickGELU      (vision: patches e [B*g2, pk] aliases it, pk = conv1_k: 3p^2 or padded)
 //   rows i32 [B]       pooled row per sample (class token / EOT token)
 //   pool e   [B, d]    ln_post / ln_final of the pooled rows
 #include <cstdlib>
@@ -52,10 +52,11 @@ struct TowerBufs {
   int32_t* rows;
   void* pool;
   int32_t* seq;     // [B + 2] packed text: row offsets of the captions, seq[B] = the packed row count (read by the kernels themselves)
+  void* conv1_w;    // vision, K-padded conv1 only: the weight with zero columns [d, pk] e
   size_t total;
 };
 
-static TowerBufs carve(void* ws, size_t M, size_t B, size_t d, size_t e, size_t extra_qkv, size_t extra_mlp) {
+static TowerBufs carve(void* ws, size_t M, size_t B, size_t d, size_t e, size_t extra_qkv, size_t extra_mlp, size_t conv1_w_bytes = 0) {
   Arena a(ws);
   TowerBufs t;
   t.x = static_cast<float*>(a.take(M * d * 4));
@@ -66,6 +67,7 @@ static TowerBufs carve(void* ws, size_t M, size_t B, size_t d, size_t e, size_t 
   t.rows = static_cast<int32_t*>(a.take(B * 4));
   t.pool = a.take(B * d * e);
   t.seq = static_cast<int32_t*>(a.take((B + 2) * 4));
+  t.conv1_w = a.take(conv1_w_bytes);
   t.total = a.off;
   return t;
 }
@@ -350,8 +352,9 @@ extern "C" size_t cmh_vit_workspace_bytes(const cmh_vit_weights* w, int32_t batc
   if (!w || batch <= 0 || w->patch <= 0) return 0;
   const size_t g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, d = w->width;
   const size_t e = w->gemm_dtype == CMH_F32 ? 4 : 2;   // fp8 mode: sized like bf16 (conv1 and the stream are the bf16 mode's)
-  const size_t B = batch, pk = 3ull * w->patch * w->patch;
-  return carve(nullptr, B * T, B, d, e, B * g2 * d * 4, B * g2 * pk * e).total;
+  const size_t B = batch, pk = 3ull * w->patch * w->patch, pkp = conv1_k(w->patch, w->gemm_dtype);
+  // the patch matrix [B*g2, pkp] aliases the MLP buffer, which carve sizes for the larger of the two
+  return carve(nullptr, B * T, B, d, e, B * g2 * d * 4, B * g2 * pkp * e, pkp != pk ? d * pkp * e : 0).total;
 }
 
 // validation + everything before the first block: conv1 as a patch-matrix GEMM, [class ; patches] + positional, ln_pre
@@ -363,33 +366,40 @@ static int vit_begin(const cmh_vit_weights* w, const float* image, int32_t batch
   CMH_CHECK_ARG(batch > 0, "vit_encode: batch %d", batch);
   int rc = check_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
   if (rc) return rc;
-  CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0 && w->patch % 4 == 0, "vit_encode: resolution %d / patch %d",
-                w->resolution, w->patch);
+  CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0, "vit_encode: resolution %d / patch %d", w->resolution, w->patch);
   const int dtb = w->gemm_dtype, d = w->width, B = batch;   // dtb: arithmetic of the blocks' GEMMs
   const int dt = dtb == CMH_FP8 ? CMH_BF16 : dtb;             // everything outside the blocks (conv1, LayerNorms, projections)
   const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T;
-  const int pk = 3 * w->patch * w->patch;
+  const int pk = 3 * w->patch * w->patch, pkp = conv1_k(w->patch, dt);    // pkp != pk: the K-padded conv1
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   CMH_CHECK_ARG(!amax || dtb == CMH_BF16, "vit_calibrate_fp8: weights must be the bf16 mode's");
-  CMH_CHECK_ARG(pk % (dt == CMH_F32 ? 32 : 64) == 0, "vit_encode: 3*patch^2 = %d not a multiple of the GEMM K-step", pk);
+  CMH_CHECK_ARG(dtb != CMH_FP8 || pkp == pk, "fp8 mode: patch %d (3*patch^2 = %d) needs the K-padded conv1, which is not built for fp8",
+                w->patch, pk);
   const size_t need = cmh_vit_workspace_bytes(w, batch);
   if (workspace_bytes < need) return fail(CMH_ERR_WORKSPACE, "vit_encode: workspace %zu < %zu bytes", workspace_bytes, need);
   CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "vit_encode: workspace must be 256-byte aligned");
   TowerBufs& t = r.t;
-  t = carve(workspace, static_cast<size_t>(M), B, d, e, static_cast<size_t>(B) * g2 * d * 4, static_cast<size_t>(B) * g2 * pk * e);
+  t = carve(workspace, static_cast<size_t>(M), B, d, e, static_cast<size_t>(B) * g2 * d * 4, static_cast<size_t>(B) * g2 * pkp * e,
+            pkp != pk ? static_cast<size_t>(d) * pkp * e : 0);
   t.xh = resid_f16(dtb, d, taps);
   r.dtb = dtb; r.d = d; r.B = B; r.T = T; r.M = M; r.causal = 0;
   void* patches = t.mlp;
   float* patch_out = static_cast<float*>(t.qkv);
 
-  // conv1 (kernel = stride = patch, no bias) as patch-matrix GEMM  (model.py:215,231-235)
+  // conv1 (kernel = stride = patch, no bias) as patch-matrix GEMM  (model.py:215,231-235).  K-padded (conv1_k): the patch rows and
+  // a copy of the weight carry zero columns pk..pkp-1, which add exact zeros - the K = pk product in the same k order.
   if (image_b) {
     CMH_CHECK_ARG(batch_a > 0 && batch_a < B, "vit_encode: split batch %d of %d", batch_a, B);
-    if ((rc = launch_patchify(image, patches, dt, batch_a, w->resolution, w->patch, st))) return rc;
-    if ((rc = launch_patchify(image_b, static_cast<char*>(patches) + static_cast<size_t>(batch_a) * g2 * pk * e, dt, B - batch_a, w->resolution,
-                              w->patch, st))) return rc;
-  } else if ((rc = launch_patchify(image, patches, dt, B, w->resolution, w->patch, st))) return rc;
-  if ((rc = launch_gemm(dt, patches, w->conv1_w, nullptr, nullptr, patch_out, B * g2, d, pk, 0, st))) return rc;
+    if ((rc = launch_patchify(image, patches, dt, batch_a, w->resolution, w->patch, pkp, st))) return rc;
+    if ((rc = launch_patchify(image_b, static_cast<char*>(patches) + static_cast<size_t>(batch_a) * g2 * pkp * e, dt, B - batch_a, w->resolution,
+                              w->patch, pkp, st))) return rc;
+  } else if ((rc = launch_patchify(image, patches, dt, B, w->resolution, w->patch, pkp, st))) return rc;
+  const void* conv1_w = w->conv1_w;
+  if (pkp != pk) {
+    if ((rc = launch_copy_cols(w->conv1_w, pk, t.conv1_w, pkp, d, pk, static_cast<int>(e), st))) return rc;
+    conv1_w = t.conv1_w;
+  }
+  if ((rc = launch_gemm(dt, patches, conv1_w, nullptr, nullptr, patch_out, B * g2, d, pkp, 0, st))) return rc;
   // [class ; patches] + positional, ln_pre  (:237-239)
   if ((rc = launch_vit_assemble_lnpre(patch_out, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                                       w->ln_pre_b, t.x, t.xh, B, g2, d, st))) return rc;

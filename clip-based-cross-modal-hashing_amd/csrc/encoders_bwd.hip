@@ -46,7 +46,7 @@ struct LayerTape { void *x_in, *h1, *qkv, *attn, *x_mid, *h2, *pre, *act; };   /
 struct TrainBufs {
   std::vector<LayerTape> L;
   void* x_last;        // [M,d] xs   output of the last block
-  void* patches;       // vision: [B*g2, pk] e
+  void* patches;       // vision: [B*g2, pk] e   (pk = conv1_k: 3p^2, or padded with zero columns)
   float* x_pre;        // vision: [M,d] f32 tokens + positional before ln_pre;   text: unused
   float* patch_out;    // vision: [B*g2, d] f32
   int32_t* rows;       // [B] pooled row of every sample
@@ -71,13 +71,16 @@ struct TrainBufs {
   void* red;           // reduction workspace
   size_t red_bytes;
   size_t tAB_bytes;
+  void* conv1_w;       // vision, K-padded conv1 only: [d, pk] e   the weight with zero columns
+  float* conv1_dw;     // vision, K-padded conv1 only: [d, pk] f32 its gradient before the compaction to [d, 3p^2]
   size_t total;
 };
 
 size_t pad64(size_t m) { return (m + 63) / 64 * 64; }
 
+// pk: conv1's patch-matrix K (conv1_k); conv1_padded: pk is the padded K, so the padded weight and its gradient get buffers too
 TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t xs, int layers, size_t g2rows, size_t pk,
-                      size_t embed) {
+                      size_t embed, bool conv1_padded = false) {
   Carver a(ws);
   TrainBufs t;
   t.L.resize(layers);
@@ -127,6 +130,8 @@ TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t x
   rb = batched > rb ? batched : rb;
   t.red_bytes = rb;
   t.red = a.take(rb);
+  t.conv1_w = a.take(conv1_padded ? d * pk * e : 0);
+  t.conv1_dw = a.take<float>(conv1_padded ? d * pk * 4 : 0);
   t.total = a.off;
   return t;
 }
@@ -616,7 +621,8 @@ extern "C" size_t cmh_vit_train_bytes(const cmh_vit_weights* w, int32_t batch) {
   if (!w || batch <= 0 || w->patch <= 0) return 0;
   const size_t g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, d = w->width, B = batch;
   const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = train_xh(w->gemm_dtype, w->width) ? 2 : 4;
-  return carve_train(nullptr, B * T, B, d, e, xs, w->layers, B * g2, 3ull * w->patch * w->patch, w->embed_dim).total;
+  const int pkp = conv1_k(w->patch, w->gemm_dtype);
+  return carve_train(nullptr, B * T, B, d, e, xs, w->layers, B * g2, pkp, w->embed_dim, pkp != 3 * w->patch * w->patch).total;
 }
 
 static int vit_forward_train_impl(const cmh_vit_weights* w, const float* image, int32_t batch, float* feat, float* tokens_out,
@@ -625,18 +631,24 @@ static int vit_forward_train_impl(const cmh_vit_weights* w, const float* image, 
   int rc = check_train_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
   if (rc) return rc;
   CMH_CHECK_ARG(w->layers > 0, "vit_forward_train: no layers");
-  CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0 && w->patch % 4 == 0, "vit_forward_train: resolution / patch");
+  CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0, "vit_forward_train: resolution / patch");
   const int dt = w->gemm_dtype, d = w->width, B = batch;
   const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T, pk = 3 * w->patch * w->patch;
-  CMH_CHECK_ARG(pk % (dt == CMH_F32 ? 32 : 64) == 0, "vit_forward_train: 3*patch^2 = %d not a multiple of the GEMM K-step", pk);
+  const int pkp = conv1_k(w->patch, dt);      // pkp != pk: the K-padded conv1 (encoders.hip: vit_begin)
   if (tape_bytes < cmh_vit_train_bytes(w, batch)) return fail(CMH_ERR_WORKSPACE, "vit_forward_train: tape too small");
   CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "vit_forward_train: tape must be 256-byte aligned");
   const int xh = train_xh(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pk, w->embed_dim);
-  if ((rc = launch_patchify(image, t.patches, dt, B, w->resolution, w->patch, st))) return rc;
-  if ((rc = launch_gemm(dt, t.patches, w->conv1_w, nullptr, nullptr, t.patch_out, B * g2, d, pk, 0, st))) return rc;
+  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, w->embed_dim,
+                            pkp != pk);
+  if ((rc = launch_patchify(image, t.patches, dt, B, w->resolution, w->patch, pkp, st))) return rc;
+  const void* conv1_w = w->conv1_w;
+  if (pkp != pk) {
+    if ((rc = launch_copy_cols(w->conv1_w, pk, t.conv1_w, pkp, d, pk, static_cast<int>(e), st))) return rc;
+    conv1_w = t.conv1_w;
+  }
+  if ((rc = launch_gemm(dt, t.patches, conv1_w, nullptr, nullptr, t.patch_out, B * g2, d, pkp, 0, st))) return rc;
   // x_pre = [cls ; patches] + positional (kept for ln_pre's backward), x_0 = ln_pre(x_pre)
   if ((rc = launch_vit_assemble(t.patch_out, w->class_embedding, w->positional_embedding, t.x_pre, B, g2, d, st))) return rc;
   if ((rc = launch_layernorm_any(t.x_pre, kF32, nullptr, w->ln_pre_w, w->ln_pre_b, t.L[0].x_in, xkind(xh), M, d, st))) return rc;
@@ -683,10 +695,11 @@ static int vit_backward_impl(const cmh_vit_weights* w, int32_t batch, const floa
   if (tape_bytes < cmh_vit_train_bytes(w, batch)) return fail(CMH_ERR_WORKSPACE, "vit_backward: tape too small");
   const int dt = w->gemm_dtype, d = w->width, B = batch, E = w->embed_dim;
   const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T, pk = 3 * w->patch * w->patch;
+  const int pkp = conv1_k(w->patch, dt);
   const int xh = train_xh(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pk, E);
+  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, E, pkp != pk);
   const bool tail = !dtokens && train_pooled_tail();
   if (layer_hi == w->layers) {
     if ((rc = zero_pad_buffers(t, static_cast<size_t>(M), st))) return rc;
@@ -713,7 +726,11 @@ static int vit_backward_impl(const cmh_vit_weights* w, int32_t batch, const floa
   if (hipMemcpy2DAsync(t.dx, static_cast<size_t>(g2) * d * 4, t.dx2 + d, static_cast<size_t>(T) * d * 4, static_cast<size_t>(g2) * d * 4,
                        B, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "vit_backward: compaction failed");
   if ((rc = zero_pad_buffers(t, static_cast<size_t>(B) * g2, st))) return rc;
-  return wgrad(dt, t.dx, kF32, d, t.patches, ekind(dt), pk, B * g2, gr->conv1_w, nullptr, t, st);
+  if (pkp == pk) return wgrad(dt, t.dx, kF32, d, t.patches, ekind(dt), pk, B * g2, gr->conv1_w, nullptr, t, st);
+  // K-padded conv1: dW [d, pkp] into scratch (its pad columns are dY^T . 0), then the caller's [d, 3, p, p] = its first pk columns -
+  // the gradient is a view into the trainer's flat gradient buffer, so exactly d * pk contiguous floats are written
+  if ((rc = wgrad(dt, t.dx, kF32, d, t.patches, ekind(dt), pkp, B * g2, t.conv1_dw, nullptr, t, st))) return rc;
+  return launch_copy_cols(t.conv1_dw, pkp, gr->conv1_w, pk, d, pk, 4, st);
 }
 
 extern "C" int cmh_set_grad_stream16(int32_t on) {

@@ -292,12 +292,74 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
   }
 }
 
-int launch_patchify(const float* image, void* patches, int dt, int B, int R, int p, hipStream_t st) {
-  CMH_CHECK_ARG(p % 4 == 0 && R % p == 0, "patchify: resolution %d / patch %d unsupported", R, p);
-  const size_t total4 = static_cast<size_t>(B) * 3 * R * R / 4;
-  const int blocks = static_cast<int>(total4 / 256 + 1 < 4096 ? total4 / 256 + 1 : 4096);
-  hipLaunchKernelGGL(patchify_kernel, dim3(blocks), dim3(256), 0, st, image, patches, dt == CMH_BF16, B, R, p);
+// any p with R % p == 0, rows of ld >= 3p^2 elements (the K-padded conv1, cmh_common.h: conv1_k).  One work item per image pixel:
+// the lanes of a wave read 64 consecutive floats of the image (coalesced along x) and write them to runs of p consecutive elements
+// of the patch rows (one patch row of one channel is contiguous in the image and in the patch row).  The work items past the pixels
+// write the pad columns [3p^2, ld) as zeros, one element each, on every call: the patch matrix aliases scratch that earlier layers
+// leave dirty.
+__global__ __launch_bounds__(256) void patchify_any_kernel(const float* __restrict__ image, void* __restrict__ patches, int out_bf16,
+                                                           int B, int R, int p, int ld) {
+  const int g = R / p, pk = 3 * p * p, pad = ld - pk;
+  const size_t pixels = static_cast<size_t>(B) * 3 * R * R;
+  const size_t total = pixels + static_cast<size_t>(B) * g * g * pad;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<size_t>(gridDim.x) * blockDim.x) {
+    size_t o;
+    float v = 0.f;
+    if (i < pixels) {
+      const int x = static_cast<int>(i % R);
+      const size_t r = i / R;                                        // image row (b, c, y)
+      const int y = static_cast<int>(r % R), c = static_cast<int>((r / R) % 3);
+      const size_t b = r / (static_cast<size_t>(R) * 3);
+      v = image[i];
+      o = ((b * g + y / p) * g + x / p) * ld + static_cast<size_t>(c * p + y % p) * p + x % p;
+    } else {
+      const size_t j = i - pixels;
+      o = (j / pad) * ld + pk + j % pad;
+    }
+    if (out_bf16) static_cast<bf16_t*>(patches)[o] = f32_to_bf16(v);
+    else static_cast<float*>(patches)[o] = v;
+  }
+}
+
+int launch_patchify(const float* image, void* patches, int dt, int B, int R, int p, int ld, hipStream_t st) {
+  CMH_CHECK_ARG(p > 0 && R % p == 0 && ld >= 3 * p * p, "patchify: resolution %d / patch %d / row stride %d unsupported", R, p, ld);
+  if (p % 4 == 0 && ld == 3 * p * p) {
+    const size_t total4 = static_cast<size_t>(B) * 3 * R * R / 4;
+    const int blocks = static_cast<int>(total4 / 256 + 1 < 4096 ? total4 / 256 + 1 : 4096);
+    hipLaunchKernelGGL(patchify_kernel, dim3(blocks), dim3(256), 0, st, image, patches, dt == CMH_BF16, B, R, p);
+  } else {
+    const size_t g = R / p, total = static_cast<size_t>(B) * 3 * R * R + static_cast<size_t>(B) * g * g * (ld - 3 * p * p);
+    const int blocks = static_cast<int>(total / 256 + 1 < 8192 ? total / 256 + 1 : 8192);
+    hipLaunchKernelGGL(patchify_any_kernel, dim3(blocks), dim3(256), 0, st, image, patches, dt == CMH_BF16, B, R, p, ld);
+  }
   CMH_CHECK_LAUNCH("patchify");
+  return CMH_OK;
+}
+
+template <typename E>
+__global__ __launch_bounds__(256) void copy_cols_kernel(const E* __restrict__ src, int lds, E* __restrict__ dst, int ldd, int rows,
+                                                        int cols) {
+  const size_t total = static_cast<size_t>(rows) * ldd;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<size_t>(gridDim.x) * blockDim.x) {
+    const size_t r = i / ldd;
+    const int c = static_cast<int>(i % ldd);
+    dst[i] = c < cols ? src[r * lds + c] : E(0);
+  }
+}
+
+int launch_copy_cols(const void* src, int lds, void* dst, int ldd, int rows, int cols, int esz, hipStream_t st) {
+  CMH_CHECK_ARG((esz == 2 || esz == 4) && rows > 0 && cols > 0 && cols <= lds && cols <= ldd, "copy_cols: bad shape");
+  const size_t total = static_cast<size_t>(rows) * ldd;
+  const int blocks = static_cast<int>(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
+  if (esz == 2)
+    hipLaunchKernelGGL(copy_cols_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, static_cast<const uint16_t*>(src), lds,
+                       static_cast<uint16_t*>(dst), ldd, rows, cols);
+  else
+    hipLaunchKernelGGL(copy_cols_kernel<uint32_t>, dim3(blocks), dim3(256), 0, st, static_cast<const uint32_t*>(src), lds,
+                       static_cast<uint32_t*>(dst), ldd, rows, cols);
+  CMH_CHECK_LAUNCH("copy_cols");
   return CMH_OK;
 }
 

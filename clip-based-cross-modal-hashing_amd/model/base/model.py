@@ -252,6 +252,10 @@ class CLIP(nn.Module):
 
     def _check_fp8_tokens(self, dt):
         tokens = self.visual.positional_embedding.shape[0]
+        p = self.visual.conv1.weight.shape[-1]
+        if dt == N.FP8 and (p % 4 or 3 * p * p % 64):
+            raise N.NativeError(f"the fp8 mode is not built for patch {p}: its conv1 (K = 3*{p}^2 = {3 * p * p}) needs the K-padded "
+                                "patch matrix, built for the f32 and bf16 modes only: use set_gemm_dtype('bf16' | 'f32')")
         if dt == N.FP8 and tokens > FP8_MAX_IMAGE_TOKENS:
             raise N.NativeError(f"the fp8 mode is built for at most {FP8_MAX_IMAGE_TOKENS} image tokens; this checkpoint has {tokens} "
                                 "(ViT-B/16 and larger): use set_gemm_dtype('bf16' | 'f32')")
