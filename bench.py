@@ -7,16 +7,21 @@ One "step" = one pass of the hot path over one batch of synthetic input already 
 Workload = BASELINE.json configs[1]: "DSPH --dataset flickr25k --output-dim 64, ViT-B/32 bf16, 1xMI355X,
 batch=256" (per-GPU batch fixed as N grows -> weak scaling).  Random-init weights, synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, the warm-up steps, the timed steps,
+the outputs of --dump-outputs and the line.  --full adds everything else the benchmark measures, among it:
   roofline     dominant kernel (the MFMA GEMM): algorithmic FLOPs / HIP-event launch durations, live, over
-               the timed region (cmh_prof_gemm_*), vs the dense MFMA peak of the dtype.
+               the timed region (cmh_prof_gemm_*), vs the dense MFMA peak of the dtype.  With the towers on two
+               streams (the default) it takes a pass of its own, so a plain run carries it only in the
+               single-stream modes (--towers pair / serial), where the timed region itself measures it.
   cpu_baseline the oracle (numpy fp32 restatement of the reference path) timed on the host cores, rank 0, N=1.
   map_eval     secondary metric: wall-clock of the 4 calc_map_k directions (64-bit, MIRFlickr scale), codes
                resident; not part of `value`.
+and value_dense_text, towers_ab, the f32 / fp8 legs, loss_fwd, train_step, input_pipeline and one leg per other
+BASELINE config (bench_configs.py).  The --no-* options switch single legs of a --full run off.
 
 --dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: image_hash / text_hash
 (tanh hash outputs, batch x bits), image_codes / text_codes (their sign() codes) and loss (the HyP loss, a scalar).  Weights
@@ -207,8 +212,8 @@ def main():
     ap.add_argument("--no-input-pipeline", action="store_true")
     ap.add_argument("--no-dense-text", action="store_true", help="skip the extra timed pass with all text positions computed")
     ap.add_argument("--train-step", action="store_true",
-                    help="also time the training step when --gpus > 1 (default: single-GPU runs only, so that the secondary "
-                         "metric's gradient all-reduce can never stall the headline scaling line)")
+                    help="with --full, also time the training step when --gpus > 1 (default: single-GPU runs only, so that the "
+                         "secondary metric's gradient all-reduce can never stall the headline scaling line)")
     ap.add_argument("--towers", default="pair2", choices=["pair", "pair2", "streams", "pipelined", "serial"],
                     help="how a step runs the two towers: pair = in lock-step on one stream, layer i of both sharing its launches "
                          "(cmh_clip_encode_pair); pair2 (default) = the same, consecutive independent batches alternating between two HIP "
@@ -222,6 +227,9 @@ def main():
     ap.add_argument("--map-db", type=int, default=15015)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg as well (roofline pass, dense-text pass, towers_ab, precision legs, "
+                         "map_eval, loss_fwd, train_step, input_pipeline, config legs, cpu_baseline); default: the headline alone")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -341,20 +349,22 @@ def main():
         region_s.append(max_over_ranks(time.perf_counter() - t0))
     if a.dump_outputs and rank == 0:      # the last timed step's outputs, before any later leg runs the step again
         dump_outputs(a.dump_outputs, last)
-    if overlap:
-        # With the towers on two streams a GEMM's start-to-end time includes the time its workgroups wait for CUs held by
-        # the other tower's kernel, so per-launch HIP events (and rocprofv3's kernel trace) no longer time the kernel.  The
-        # roofline leg therefore re-runs the same K steps with the towers serialized, right after the timed region.
-        N.prof_gemm_begin(a.steps * 128)
-        for _ in range(a.steps):
-            step(how="pair" if towers == "pair2" else "serial")
-        barrier()
-    prof_steps = a.steps if overlap else a.steps * reps
-    all_ms, all_flops, all_launches = N.prof_gemm_end()
-    by_kernel = N.prof_gemm_by_kernel()
-    # the dominant kernel is gemm_wide_kernel (every GEMM of M >= 10 k rows); the M = 256 launches of the pooled-row tail and of the
-    # final projections run on gemm_rows_kernel and are reported beside it, not averaged into it
-    gemm_ms, gemm_flops, gemm_launches = by_kernel["gemm_wide_kernel"]
+    roofline_on = not overlap or a.full       # overlapped towers need a pass of their own for it: --full only
+    if roofline_on:
+        if overlap:
+            # With the towers on two streams a GEMM's start-to-end time includes the time its workgroups wait for CUs held by
+            # the other tower's kernel, so per-launch HIP events (and rocprofv3's kernel trace) no longer time the kernel.  The
+            # roofline leg therefore re-runs the same K steps with the towers serialized, right after the timed region.
+            N.prof_gemm_begin(a.steps * 128)
+            for _ in range(a.steps):
+                step(how="pair" if towers == "pair2" else "serial")
+            barrier()
+        prof_steps = a.steps if overlap else a.steps * reps
+        all_ms, all_flops, all_launches = N.prof_gemm_end()
+        by_kernel = N.prof_gemm_by_kernel()
+        # the dominant kernel is gemm_wide_kernel (every GEMM of M >= 10 k rows); the M = 256 launches of the pooled-row tail and of
+        # the final projections run on gemm_rows_kernel and are reported beside it, not averaged into it
+        gemm_ms, gemm_flops, gemm_launches = by_kernel["gemm_wide_kernel"]
     srt = sorted(region_s)
     elapsed = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
     assert torch.isfinite(loss).item(), "non-finite loss"
@@ -366,7 +376,7 @@ def main():
     rows_c, rows_d = clip.last_text_rows if clip.last_text_rows else (B * L, B * L)
     flops_pair = FLOP_IMG + text_flops(L) * rows_c / rows_d
     value_dense = None
-    if clip.pack_text and not a.no_dense_text:
+    if a.full and clip.pack_text and not a.no_dense_text:
         clip.pack_text = False
         for _ in range(2):
             step()
@@ -378,7 +388,6 @@ def main():
         value_dense = pairs / max_over_ranks(time.perf_counter() - td0)
         clip.pack_text = True
     peak = PEAK_TFLOPS[a.dtype]
-    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
 
     def gemm_algorithmic_bytes(text_rows):
         """operand + result bytes of the gemm_wide_kernel launches of one step, each tensor counted once (bf16 mode: bf16 operands
@@ -400,15 +409,6 @@ def main():
         if towers in ("pair", "pair2"):      # layer i of both towers is ONE launch: 45 grouped launches + conv1
             n //= 2
         return total, n + 1
-    # HBM-side bytes per GEMM launch cannot be counted from inside this process: they come from the two rocprofv3 --pmc
-    # passes of this same command (tools/pmc_bench_traffic.sh), committed under profiles/; null if absent / other dtype.
-    traffic, traffic_src = None, None
-    import glob
-    tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic.json")))      # the latest round's passes
-    if a.dtype == "bf16" and tfiles:
-        with open(tfiles[-1]) as fh:
-            traffic = json.load(fh)["traffic_bytes_per_launch"]
-        traffic_src = f"profiles/{os.path.basename(tfiles[-1])} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, (2*FETCH+WRITE)*1024)"
     out = {
         "metric": "image+text pairs/s encoded+hashed per GPU; mAP@K eval wallclock (64-bit)",
         "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -437,31 +437,42 @@ def main():
                               "computed (synthetic captions: EOT uniform in positions 3..75)"},
         "value_dense_text": None if value_dense is None else round(value_dense, 2),
         "end_to_end_tflops_per_gpu": round(value / world * flops_pair / 1e12, 2),
-        "roofline": {"bound": "mfma", "kernel": "cmh::gemm_wide_kernel<%s, 1, *>%s" % ("0" if a.dtype == "f32" else "1", " (grouped launches: layer i of both "
-                     "towers per launch)" if towers in ("pair", "pair2") else ""),
-                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                     "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": round(gemm_algorithmic_bytes(rows_c)[0] / gemm_algorithmic_bytes(rows_c)[1]),
-                     "launches": int(gemm_launches),
-                     "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
-                     "timing": "HIP events stamped by the dispatch itself (hipExtLaunchKernelGGL start/stop events on the launch "
-                               "stream): the kernel's own begin-to-end time, as rocprofv3's kernel trace reports it",
-                     "other_gemm_kernels": {k: {"launches": int(v[2]), "ms_per_step": round(v[0] / prof_steps, 4),
-                                                "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 2) if v[0] > 0 else 0.0}
-                                            for k, v in by_kernel.items() if k != "gemm_wide_kernel" and v[2] > 0},
-                     "all_gemm_launches": {"launches": int(all_launches), "ms_per_step": round(all_ms / prof_steps, 4),
-                                           "tflops": round(all_flops / (all_ms * 1e-3) / 1e12, 2) if all_ms > 0 else 0.0},
-                     "measured_in": ("the timed region" if not overlap else
-                                     "a second pass of the same K steps on ONE stream (the lock-step pair path, batch after batch): in the "
-                                     "timed region the launches of two batches overlap, so per-launch events would not time the kernel; "
-                                     "value/ms_per_step are from the overlapped region (towers_ab.pair holds a roofline measured in ITS "
-                                     "timed region)" if towers == "pair2" else
-                                     "a second pass of the same K steps with the two towers serialized (per-launch events "
-                                     "overlap when the towers share the GPU); value/ms_per_step are from the overlapped region"),
-                     "gemm_ms_per_step_serialized": round(gemm_ms / prof_steps, 4)},
     }
+    if roofline_on:
+        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # HBM-side bytes per GEMM launch cannot be counted from inside this process: they come from the two rocprofv3 --pmc
+        # passes of this same command (tools/pmc_bench_traffic.sh), committed under profiles/; null if absent / other dtype.
+        traffic, traffic_src = None, None
+        import glob
+        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_gemm_traffic.json")))      # the latest round's passes
+        if a.dtype == "bf16" and tfiles:
+            with open(tfiles[-1]) as fh:
+                traffic = json.load(fh)["traffic_bytes_per_launch"]
+            traffic_src = f"profiles/{os.path.basename(tfiles[-1])} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, (2*FETCH+WRITE)*1024)"
+        out["roofline"] = {"bound": "mfma", "kernel": "cmh::gemm_wide_kernel<%s, 1, *>%s" % ("0" if a.dtype == "f32" else "1", " (grouped launches: layer i of both "
+                            "towers per launch)" if towers in ("pair", "pair2") else ""),
+                            "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                            "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                            "algorithmic_bytes_per_launch": round(gemm_algorithmic_bytes(rows_c)[0] / gemm_algorithmic_bytes(rows_c)[1]),
+                            "launches": int(gemm_launches),
+                            "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
+                            "timing": "HIP events stamped by the dispatch itself (hipExtLaunchKernelGGL start/stop events on the launch "
+                                      "stream): the kernel's own begin-to-end time, as rocprofv3's kernel trace reports it",
+                            "other_gemm_kernels": {k: {"launches": int(v[2]), "ms_per_step": round(v[0] / prof_steps, 4),
+                                                       "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 2) if v[0] > 0 else 0.0}
+                                                   for k, v in by_kernel.items() if k != "gemm_wide_kernel" and v[2] > 0},
+                            "all_gemm_launches": {"launches": int(all_launches), "ms_per_step": round(all_ms / prof_steps, 4),
+                                                  "tflops": round(all_flops / (all_ms * 1e-3) / 1e12, 2) if all_ms > 0 else 0.0},
+                            "measured_in": ("the timed region" if not overlap else
+                                            "a second pass of the same K steps on ONE stream (the lock-step pair path, batch after batch): in the "
+                                            "timed region the launches of two batches overlap, so per-launch events would not time the kernel; "
+                                            "value/ms_per_step are from the overlapped region (towers_ab.pair holds a roofline measured in ITS "
+                                            "timed region)" if towers == "pair2" else
+                                            "a second pass of the same K steps with the two towers serialized (per-launch events "
+                                            "overlap when the towers share the GPU); value/ms_per_step are from the overlapped region"),
+                            "gemm_ms_per_step_serialized": round(gemm_ms / prof_steps, 4)}
 
-    if world == 1 and not a.no_towers_ab:
+    if a.full and world == 1 and not a.no_towers_ab:
         # The other ways to run a step's two towers, timed on this very box (one region of --steps steps each), and - in the single-stream
         # lock-step mode, where launches do not overlap - the GEMM roofline measured IN that timed region by the dispatches' own events
         ab = {}
@@ -496,7 +507,7 @@ def main():
                       "region; pair2: pair with consecutive batches alternating between two streams")
         out["towers_ab"] = ab
 
-    if world == 1 and a.dtype != "f32" and not a.no_precision_legs:      # (step() holds a collective when world > 1: single-GPU runs only)
+    if a.full and world == 1 and a.dtype != "f32" and not a.no_precision_legs:      # (step() holds a collective when world > 1: single-GPU runs only)
         try:
             # the precision story of the benchmarked mode: sign flips against the f32 parity mode on this very batch, and the same
             # step timed in f32 mode (towers serialized so that the per-launch events time the kernels)
@@ -572,7 +583,7 @@ def main():
             out["fp8_mode"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
             clip.set_gemm_dtype(a.dtype)
 
-    if not a.no_map_eval:
+    if a.full and not a.no_map_eval:
         # secondary metric: 4 x calc_map_k at MIRFlickr scale, 64-bit, codes resident; queries sharded over ranks
         Q, Nn = a.map_queries, a.map_db
         g = torch.Generator().manual_seed(1234)
@@ -611,7 +622,7 @@ def main():
                            "stable_tie_order": {"ms": round(ms_st, 3), "mAP_i2t": round(float(maps_st[0]), 6),
                                                 "note": "CMH_TIE_STABLE (ties by index): not the reference's ranking"}}
 
-    if rank == 0:
+    if a.full and rank == 0:
         # SURVEY 8(d), N x N loss kernels: time per step and share of the step (HyP on the rank's batch; tools/loss_scale_bench.py
         # has the global-batch sizes of an N-GPU step)
         with torch.no_grad():
@@ -627,7 +638,7 @@ def main():
             lus = e0.elapsed_time(e1) / 20 * 1e3
         out["loss_fwd"] = {"us": round(lus, 1), "share_of_step": round(lus * 1e-3 / out["ms_per_step"], 4), "what": f"HyP forward, batch {B}, {K} bits, {C} classes"}
 
-    if not a.no_train_step and (world == 1 or a.train_step):
+    if a.full and not a.no_train_step and (world == 1 or a.train_step):
         try:
             # secondary metric: the reference's actual inner loop (train/DSPH/hash_train.py:49-73) - tape-keeping forward of both
             # towers, heads, HyP loss, backward through everything, fused BertAdam + SGD on the proxies; same batch, weights not frozen
@@ -676,7 +687,7 @@ def main():
             out["train_step"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
             clip.assume_frozen = True
 
-    if rank == 0 and not a.no_input_pipeline:
+    if a.full and rank == 0 and not a.no_input_pipeline:
         try:
             # secondary metric: the input pipeline that feeds the step — image transform of a raw batch on the GPU
             # (500x375 / 375x500 decoded images -> 224x224 normalised floats, bit-identical to Pillow + torchvision) and the
@@ -737,7 +748,7 @@ def main():
         except Exception as exc:
             out["input_pipeline"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
-    if rank == 0 and world == 1 and not a.no_config_legs:
+    if a.full and rank == 0 and world == 1 and not a.no_config_legs:
         # one timed number for each of the other BASELINE.json configs (the headline above is configs[1]); each leg builds its own
         # model, so the headline's is released first
         import gc
@@ -760,7 +771,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cb = cpu_baseline(L, K)
         out["cpu_baseline"] = cb
     if rank == 0:

@@ -85,7 +85,7 @@ def test_bench_self_launch_two_ranks_end_to_end():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CMH_FORCE_DIST")}
     env.update(CMH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--batch", "32",
-           "--no-cpu-baseline", "--no-dense-text", "--map-queries", "64", "--map-db", "500", "--train-step"]
+           "--full", "--no-cpu-baseline", "--no-dense-text", "--map-queries", "64", "--map-db", "500", "--train-step"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 for bm in auto 128 auto 128; do
   if [ $bm = auto ]; then unset CMH_GEMM_BM; else export CMH_GEMM_BM=$bm; fi
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train-step --no-dense-text --no-input-pipeline --no-config-legs --no-map-eval 2>/dev/null | python3 -c "
+  python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-train-step --no-dense-text --no-input-pipeline --no-config-legs --no-map-eval 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 f = d['fp8_mode']

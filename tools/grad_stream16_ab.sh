@@ -2,7 +2,7 @@
 # 20-step DSPH training leg, alternating on one box.  usage (GPU box): bash tools/grad_stream16_ab.sh
 R=$GRAFT_REPO_ROOT
 for s in 1 0 1 0; do
-  CMH_GRAD_STREAM16=$s python3 $R/bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-config-legs --no-input-pipeline --no-map-eval \
+  CMH_GRAD_STREAM16=$s python3 $R/bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline --no-config-legs --no-input-pipeline --no-map-eval \
     --no-dense-text --no-towers-ab --no-precision-legs 2>$R/gpurun_out/stream16_err.txt |
     python3 -c "
 import json, sys

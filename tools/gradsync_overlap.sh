@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT
 for d in 0 1 0 1; do
   CMH_FORCE_DIST=1 CMH_DIST_BACKEND=nccl CMH_GRADSYNC_DEFER=$d MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29500 + d + RANDOM % 200)) RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 \
-    python3 $R/bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-config-legs --no-input-pipeline --no-map-eval --no-dense-text --no-towers-ab --no-precision-legs 2>$R/gpurun_out/gradsync_err.txt |
+    python3 $R/bench.py --steps 10 --warmup 3 --repeats 1 --full --no-cpu-baseline --no-config-legs --no-input-pipeline --no-map-eval --no-dense-text --no-towers-ab --no-precision-legs 2>"${TMPDIR:-/tmp}/gradsync_err.txt" |
     python3 -c "
 import json, sys
 r = json.loads([ln for ln in sys.stdin.read().splitlines() if ln.startswith('{') and '\"metric\"' in ln][-1])
