@@ -21,6 +21,7 @@ BASE_FLAGS = [
     ("--gemm-dtype", str, "f32", "encoder GEMM arithmetic: f32 = reference parity, bf16 = throughput, fp8 = e4m3 block GEMMs, inference only (this build)"),
     ("--data-dir", str, "", "directory with index.mat / caption.mat|txt / label.mat (this build; upstream hard-codes it)"),
     ("--synthetic-size", int, 2000, "items of the synthetic dataset (this build)"),
+    ("--eval-curves", str2bool, False, "test(): also log P@H<=2 / P@N and store the precision-recall and top-N curves in the .mat (this build)"),
 ]
 
 

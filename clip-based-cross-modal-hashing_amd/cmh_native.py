@@ -143,6 +143,9 @@ SIGNATURES = {
     "cmh_map_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
     "cmh_hamming_map": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _i32, _i32, _p, _p, _p,
                                   _p, _sz, _p]),
+    "cmh_retrieval_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_hamming_hist": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _sz, _p]),
+    "cmh_hamming_topk": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
     "cmh_dchmt_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -653,6 +656,53 @@ def hamming_map(q_planes, q_lab, r_planes, r_lab, bits, classes, topk=None, tie_
                                 0 if topk is None else int(topk), tie_order, depth_limit, ptr(ap), ptr(mp), ptr(perm),
                                 ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_map")
     return mp[0], ap, perm
+
+
+def _retrieval_operands(what, q_planes, r_planes, bits, q_lab, r_lab):
+    (qs, qn), (rs, rn) = q_planes, r_planes
+    require_gpu(qs, qn, rs, rn, q_lab, r_lab)
+    Q, N = qs.shape[0], rs.shape[0]
+    W = (int(bits) + 31) // 32
+    if (q_lab is None) != (r_lab is None):
+        raise NativeError(f"{what}: labels on one side only")
+    LW = 0 if q_lab is None else q_lab.shape[1]
+    fit(what, (qs, (Q, W)), (qn, (Q, W)), (rs, (N, W)), (rn, (N, W)), (q_lab, (Q, LW)), (r_lab, (N, LW)))
+    for t in (qs, qn, rs, rn, q_lab, r_lab):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise NativeError(f"{what}: packed operands are contiguous int32 tensors (pack_codes / pack_labels)")
+    return qs, qn, rs, rn, Q, N, LW
+
+
+def hamming_hist(q_planes, r_planes, bits, q_lab=None, r_lab=None):
+    """-> counts int32 [Q, 2*bits+1, 2]: counts[i, h, 1] = database items at calc_hammingDist == h/2 from query i that share a
+    label with it, counts[i, h, 0] = the others (everything without labels)."""
+    qs, qn, rs, rn, Q, N, LW = _retrieval_operands("hamming_hist", q_planes, r_planes, bits, q_lab, r_lab)
+    dev = qs.device
+    counts = torch.empty(Q, 2 * int(bits) + 1, 2, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_retrieval_workspace_bytes(Q, N, int(bits)), dev, "retrieval")
+    check(lib().cmh_hamming_hist(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), 32 * LW,
+                                 ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_hist")
+    return counts
+
+
+def hamming_topk(q_planes, r_planes, bits, k, q_lab=None, r_lab=None, want_counts=False):
+    """The k nearest database items of every query, ordered by (distance, database index) = the first k columns of
+    torch.sort(hamming_dist, stable=True).  -> (idx int32 [Q, k], dist f32 [Q, k], rel uint8 [Q, k] or None without labels)
+    [+ counts as hamming_hist with want_counts]."""
+    qs, qn, rs, rn, Q, N, LW = _retrieval_operands("hamming_topk", q_planes, r_planes, bits, q_lab, r_lab)
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= N:
+        raise NativeError(f"hamming_topk: k={k} outside [1, N={N}]")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    rel = torch.empty(Q, k, dtype=torch.uint8, device=dev) if LW else None
+    counts = torch.empty(Q, 2 * int(bits) + 1, 2, dtype=torch.int32, device=dev) if want_counts else None
+    ws = workspace(lib().cmh_retrieval_workspace_bytes(Q, N, int(bits)), dev, "retrieval")
+    check(lib().cmh_hamming_topk(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), 32 * LW, k,
+                                 ptr(idx), ptr(dist), ptr(rel), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_hamming_topk")
+    return (idx, dist, rel, counts) if want_counts else (idx, dist, rel)
 
 
 # ------------------------------------------------------------------------------------------ losses

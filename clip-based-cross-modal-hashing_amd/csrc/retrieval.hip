@@ -1,0 +1,470 @@
+// Retrieval on packed codes: distance histograms by relevance and top-k search (the consumers of the codes that the reference leaves
+// to an offline MATLAB step: the PR_cruve/*.mat files of train/base.py::save_mat exist to draw precision-recall and top-N curves).
+//   calc_hammingDist :8-13   0.5*(K - q.r)   -> half-units h = K - q.r in [0, 2K], AND/XOR + popcount on the bit planes
+//   calc_neighbor    :42-45  (la.lb^T > 0)   -> any(la & lb)
+//
+// A distance takes at most 2K+1 values, so both results come from counting, never from sorting:
+//   cmh_hamming_hist  counts[q, h, rel]                                  (one pass over the database)
+//   cmh_hamming_topk  the first k columns of torch.sort(hamm, stable=True): the histogram gives, per query, the radius h* at which
+//                     the cumulative count reaches k and the exclusive prefix off[h] of every bin below it; a second pass over the
+//                     database is a STABLE COUNTING SORT restricted to h <= h*: item j goes to column off[h] + (items of the same
+//                     h before j), and is dropped when that column is >= k (only the tie group at h* loses members: its first
+//                     k - count(< h*) items in index order stay).
+//
+// Mapping: LANES OWN QUERIES.  A 64-thread workgroup holds 64 queries (their code words in registers); database words are
+// wave-uniform, so they arrive through the scalar cache and every item costs each lane 5 VALU operations per 32 bits.  Each lane
+// has a private column of counters, word index = bin * 64 + lane: the 64 lanes of one LDS instruction hit 64 different words in 32
+// banks, two lanes per bank in different 32-lane groups, so an increment never meets a same-address or a bank conflict however the
+// distances cluster around K/2 (lanes that own database items would all increment the few bins around K/2 of one query).  The same
+// column is what makes the second pass trivial: a lane walks the database in index order, so its private cursor per bin IS the
+// stable rank, and the tie rule needs no extra code.
+// The database is cut into S chunks (grid = query tiles x chunks) to fill the chip; a chunk holds <= 65 532 items, so one 32-bit
+// word per (bin, lane) carries both counters of the pass (low half: all items, high half: the relevant ones).  Every workgroup
+// leaves its column image [bin][lane] in the workspace; reduce_kernel adds the images up (no atomics on the output: counts are
+// written once) and turns them into exclusive prefixes over the chunks, radius_kernel scans the bins per query.
+// LDS per workgroup: (2K+1) * 256 bytes: 33 KiB at 64 bit (4 per CU), 64.25 KiB at 128 bit (2 per CU).  Wider codes (up to 2048 bit:
+// 4097 bins = 1 MiB per tile) keep the columns in the workspace and increment them with global atomics: same code, same results,
+// not fast.
+#include "cmh_common.h"
+
+namespace cmh {
+namespace {
+
+constexpr int kRetMaxWords = 64;           // bits, classes <= 2048
+constexpr int kRetMaxN = (1 << 19) - 1;    // as the ranking kernel
+constexpr int kLdsBits = 128;              // columns in LDS up to this code length
+constexpr int kChunkMax = 65532;           // items per chunk: two 16-bit counters per word (a multiple of the unroll)
+constexpr size_t kImageCap = size_t(256) << 20;   // bytes of column images per batch of query tiles
+
+struct RetArgs {
+  const uint32_t *qs, *qn, *ql;      // (the database planes are kernel parameters of their own: `__restrict__` there is what tells the
+                                     // compiler that the select pass's stores never touch them, so their loads stay on the scalar unit)
+  int Q, N, bits, W, LW, bins, tiles, S, chunk, k;
+  uint32_t* img;      // [S][tiles][bins][64]
+  uint32_t* off;      // [tiles][bins][64]
+  int32_t* hstar;     // [tiles * 64]
+  uint32_t* counts;   // [Q][bins][2] or null
+  int32_t* idx;       // [Q][k]
+  float* dist;        // [Q][k]
+  uint8_t* rel;       // [Q][k] or null
+};
+
+// Label words per item: LT > 0 = that many, in registers; LAB_NONE = no labels; LAB_ANY = any number, the query's staged in LDS.
+enum { LAB_NONE = 0, LAB_ANY = -1 };
+
+// A tile's query operands: WT > 0 = exactly WT code words per plane, in registers; WT = 0 = any number, staged in LDS as [word][lane].
+template <int WT, int LT>
+struct Tile {
+  static constexpr int WR = WT > 0 ? WT : 1, LR = LT > 0 ? LT : 1;
+  uint32_t s[WR], n[WR], l[LR];
+  const uint32_t* st;      // staged words: sign [W][64], nz [W][64] (WT = 0), then label [LW][64] (LAB_ANY)
+  int W, LW, bits, lane;
+
+  __device__ __forceinline__ void load(const RetArgs& a, int q, int lane_, uint32_t* stage) {
+    W = a.W; LW = a.LW; bits = a.bits; lane = lane_; st = stage;
+    // the query's nz words are cut to `bits` bits: whatever the planes hold behind the code, 0 <= h <= 2 * bits (h indexes the column)
+    const uint32_t last = (bits & 31) ? (1u << (bits & 31)) - 1u : 0xffffffffu;
+    if (WT > 0) {
+#pragma unroll
+      for (int w = 0; w < WR; ++w) {
+        s[w] = a.qs[static_cast<size_t>(q) * WT + w];
+        n[w] = a.qn[static_cast<size_t>(q) * WT + w] & (w == WT - 1 ? last : 0xffffffffu);
+      }
+    } else {
+      for (int w = 0; w < W; ++w) {
+        stage[w * 64 + lane] = a.qs[static_cast<size_t>(q) * W + w];
+        stage[(W + w) * 64 + lane] = a.qn[static_cast<size_t>(q) * W + w] & (w == W - 1 ? last : 0xffffffffu);
+      }
+    }
+    if (LT > 0) {
+#pragma unroll
+      for (int w = 0; w < LR; ++w) l[w] = a.ql[static_cast<size_t>(q) * LT + w];
+    }
+    if (LT == LAB_ANY)
+      for (int w = 0; w < LW; ++w) stage[((WT ? 0 : 2 * W) + w) * 64 + lane] = a.ql[static_cast<size_t>(q) * LW + w];
+  }
+  // half-units of calc_hammingDist against one database item (its words are wave-uniform)
+  __device__ __forceinline__ int half(const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn) const {
+    int both = 0, diff = 0;
+    if (WT > 0) {
+#pragma unroll
+      for (int w = 0; w < WR; ++w) {
+        const uint32_t nz = n[w] & rn[w];
+        both += __popc(nz);
+        diff += __popc((s[w] ^ rs[w]) & nz);
+      }
+    } else {
+      for (int w = 0; w < W; ++w) {
+        const uint32_t nz = st[(W + w) * 64 + lane] & rn[w];
+        both += __popc(nz);
+        diff += __popc((st[w * 64 + lane] ^ rs[w]) & nz);
+      }
+    }
+    return bits - both + 2 * diff;
+  }
+  __device__ __forceinline__ uint32_t relevant(const uint32_t* __restrict__ rl) const {
+    if (LT == LAB_NONE) return 0u;
+    uint32_t any = 0;
+    if (LT > 0) {
+#pragma unroll
+      for (int w = 0; w < LR; ++w) any |= l[w] & rl[w];
+    } else {
+      for (int w = 0; w < LW; ++w) any |= st[((WT ? 0 : 2 * W) + w) * 64 + lane] & rl[w];
+    }
+    return any ? 1u : 0u;
+  }
+};
+
+__host__ __device__ inline size_t stage_words(int WT, int LT, int W, int LW) {
+  return static_cast<size_t>((WT ? 0 : 2 * W) + (LT == LAB_ANY ? LW : 0)) * 64;
+}
+
+// The words of U consecutive database items, U * WT <= 16 per plane: constant offsets from one wave-uniform address, so each plane
+// arrives in one or two wide scalar loads.  A scalar load can only be waited for together with everything else in flight on its
+// counter, so per-word loads inside the item loop cost a full round trip each (a first version: ~840 cycles per item at 128 bit
+// against ~110 of vector work).  The passes therefore keep two groups in registers and issue the fetch of one right BEHIND the
+// first use of the other (where the wait sits): it is in flight while the rest of that group is worked on.
+template <int WT, int LT>
+struct Group {
+  static constexpr int U = WT == 1 ? 16 : WT == 2 ? 8 : 4, NW = U * (WT > 0 ? WT : 1), NL = U * (LT > 0 ? LT : 1);
+  uint32_t s[NW], n[NW], l[NL];
+  __device__ __forceinline__ void load(const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn, const uint32_t* __restrict__ rl,
+                                       int j, bool labels) {
+    const uint32_t* __restrict__ ps = rs + static_cast<size_t>(j) * WT;
+    const uint32_t* __restrict__ pn = rn + static_cast<size_t>(j) * WT;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { s[i] = ps[i]; n[i] = pn[i]; }
+    if (LT > 0 && labels) {
+      const uint32_t* __restrict__ pl = rl + static_cast<size_t>(j) * LT;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) l[i] = pl[i];
+    }
+  }
+};
+
+// ---- pass 1: per (query tile, chunk) the column image: word [h][lane] = items at h | relevant items at h << 16 ------------------
+template <int WT, int LT, bool GLOB>
+__global__ __launch_bounds__(64) void hist_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
+                                                  const uint32_t* __restrict__ rl) {
+  extern __shared__ uint32_t smem[];
+  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their column
+  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  uint32_t* col = GLOB ? image : smem;
+  Tile<WT, LT> t;
+  t.load(a, q, lane, smem + (GLOB ? 0 : a.bins * 64));
+  if (!GLOB)
+    for (int h = 0; h < a.bins; ++h) col[h * 64 + lane] = 0u;
+  __syncthreads();
+  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  int j = jb;
+  if (WT > 0) {
+    using G = Group<WT, LT>;
+    auto work = [&](const G& g, int j0, int u0, int u1) {
+#pragma unroll
+      for (int u = u0; u < u1; ++u) {
+        const int h = t.half(g.s + u * WT, g.n + u * WT);
+        const uint32_t r = LT > 0 ? t.relevant(g.l + u * LT) : t.relevant(rl + static_cast<size_t>(j0 + u) * a.LW);
+        atomicAdd(&col[h * 64 + lane], 1u + (r << 16));
+      }
+    };
+    const int groups = (je - jb) / G::U;
+    G ga, gb;                                                       // two register sets: one is fetched while the other is worked on
+    int g = 0;
+    if (groups > 0) ga.load(rs, rn, rl, jb, true);
+    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
+      work(ga, j, 0, 1);                                           // the wait for ga's words (and for everything else in flight) sits here
+      __builtin_amdgcn_sched_barrier(0);
+      gb.load(rs, rn, rl, j + G::U, true);                                  // ... so gb's fetch is issued behind it and flies during the rest of ga
+      __builtin_amdgcn_sched_barrier(0);
+      work(ga, j, 1, G::U);
+      work(gb, j + G::U, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, true);         // (behind the last pair: a group once more, no branch)
+      __builtin_amdgcn_sched_barrier(0);
+      work(gb, j + G::U, 1, G::U);
+    }
+    if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+  }
+  for (; j < je; ++j) {
+    const int h = t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W);
+    const uint32_t r = t.relevant(rl + static_cast<size_t>(j) * a.LW);
+    atomicAdd(&col[h * 64 + lane], 1u + (r << 16));
+  }
+  if (!GLOB) {
+    __syncthreads();
+    for (int h = 0; h < a.bins; ++h) image[h * 64 + lane] = col[h * 64 + lane];
+  }
+}
+
+// ---- the images of a tile summed over the chunks -> counts; with `select` also: each image becomes the exclusive prefix over the
+//      chunks before it (items only) and off[tile][h][lane] = items at h
+__global__ __launch_bounds__(256) void reduce_kernel(RetArgs a, int select) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= stride) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t hb = t >> 6;
+  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
+  uint32_t tot = 0, rel = 0;
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * stride + t];
+    if (select) a.img[c * stride + t] = tot;
+    tot += v & 0xffffu;
+    rel += v >> 16;
+  }
+  const int q = tile * 64 + lane;
+  if (a.counts && q < a.Q) {
+    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
+    o[0] = tot - rel;
+    o[1] = rel;
+  }
+  if (select) a.off[t] = tot;
+}
+
+// ---- per query: off becomes the exclusive prefix over the bins up to the radius h* where the cumulative count reaches k ---------
+__global__ __launch_bounds__(64) void radius_kernel(RetArgs a) {
+  const int lane = threadIdx.x, tile = blockIdx.x;
+  uint32_t* base = a.off + static_cast<size_t>(tile) * a.bins * 64 + lane;
+  uint32_t run = 0;
+  int hs = -1;
+  for (int h0 = 0; h0 < a.bins && hs < 0; h0 += 8) {
+    uint32_t v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = h0 + u < a.bins ? base[static_cast<size_t>(h0 + u) * 64] : 0u;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (h0 + u < a.bins && hs < 0) {
+        base[static_cast<size_t>(h0 + u) * 64] = run;
+        run += v[u];
+        if (run >= static_cast<uint32_t>(a.k)) hs = h0 + u;
+      }
+    }
+  }
+  a.hstar[tile * 64 + lane] = tile * 64 + lane < a.Q ? hs : -1;      // (k <= N = the sum of a query's bins: always found)
+}
+
+// ---- pass 2: the stable counting sort of the items at h <= h* ---------------------------------------------------------------------
+template <int WT, int LT, bool GLOB>
+__global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
+                                                    const uint32_t* __restrict__ rl) {
+  extern __shared__ uint32_t smem[];
+  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  const uint32_t* off = a.off + static_cast<size_t>(tile) * a.bins * 64;
+  uint32_t* cur = GLOB ? image : smem;
+  Tile<WT, LT> t;
+  t.load(a, q, lane, smem + (GLOB ? 0 : a.bins * 64));
+  const int hs = a.hstar[tile * 64 + lane];        // -1 behind the last query: such a lane selects nothing
+  int hmax = hs;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int other = __shfl_xor(hmax, o, 64);
+    hmax = hmax > other ? hmax : other;
+  }
+  // cursor of bin h = items at smaller h (all chunks) + items at h in the chunks before this one
+  for (int h = 0; h <= hmax; ++h) cur[h * 64 + lane] = off[h * 64 + lane] + image[h * 64 + lane];
+  __syncthreads();
+  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  const uint32_t k = static_cast<uint32_t>(a.k);
+  auto place = [&](int j, int h) {
+    if (h <= hs) {
+      const uint32_t p = atomicAdd(&cur[h * 64 + lane], 1u);
+      if (p < k) {
+        const size_t o = static_cast<size_t>(q) * k + p;
+        a.idx[o] = j;
+        a.dist[o] = 0.5f * static_cast<float>(h);
+        if (a.rel) a.rel[o] = static_cast<uint8_t>(t.relevant(rl + static_cast<size_t>(j) * a.LW));
+      }
+    }
+  };
+  int j = jb;
+  if (WT > 0) {
+    using G = Group<WT, LT>;
+    auto work = [&](const G& g, int j0, int u0, int u1) {
+#pragma unroll
+      for (int u = u0; u < u1; ++u) place(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
+    };
+    const int groups = (je - jb) / G::U;
+    G ga, gb;
+    int g = 0;
+    if (groups > 0) ga.load(rs, rn, rl, jb, false);
+    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
+      work(ga, j, 0, 1);                                           // the wait for ga's words (and for everything else in flight) sits here
+      __builtin_amdgcn_sched_barrier(0);
+      gb.load(rs, rn, rl, j + G::U, false);                                  // ... so gb's fetch is issued behind it and flies during the rest of ga
+      __builtin_amdgcn_sched_barrier(0);
+      work(ga, j, 1, G::U);
+      work(gb, j + G::U, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, false);         // (behind the last pair: a group once more, no branch)
+      __builtin_amdgcn_sched_barrier(0);
+      work(gb, j + G::U, 1, G::U);
+    }
+    if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+  }
+  for (; j < je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+struct Plan {
+  int bins, W, tiles, S, chunk, tb;      // tb = query tiles per batch (the images of one batch fit kImageCap)
+  bool glob;
+  size_t tile_words() const { return static_cast<size_t>(bins) * 64; }
+  size_t bytes() const { return ((static_cast<size_t>(S) + 1) * tb * tile_words() + static_cast<size_t>(tb) * 64) * 4 + 256; }
+};
+
+// CUs of the current device; 256 (MI355X) where none answers (the workspace query also serves callers without a GPU)
+int cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+      (void)hipGetLastError();
+      return 256;
+    }
+    return n;
+  }();
+  return cus;
+}
+
+Plan make_plan(int Q, int64_t N, int bits) {
+  Plan p;
+  p.bins = 2 * bits + 1;
+  p.W = (bits + 31) / 32;
+  p.glob = bits > kLdsBits;
+  p.tiles = (Q + 63) / 64;
+  const int n = static_cast<int>(N);
+  const int smin = (n + kChunkMax - 1) / kChunkMax;
+  // one round of workgroups: as many chunks as fill the chip's resident slots once (equal work per workgroup: a second, partly
+  // filled round would only wait for its last members).  Resident per CU: what the columns leave of the 160 KiB of LDS.
+  const size_t lds = p.glob ? 0 : static_cast<size_t>(p.bins) * 256;
+  const int per_cu = p.glob ? 8 : static_cast<int>((160 * 1024) / lds) < 8 ? static_cast<int>((160 * 1024) / lds) : 8;
+  int s = cu_count() * per_cu / p.tiles;
+  const int by256 = (n + 255) / 256;
+  s = s < by256 ? s : by256;
+  s = s < (p.glob ? 32 : 256) ? s : (p.glob ? 32 : 256);      // (an image of the wide codes is up to 1 MiB per tile)
+  s = s > smin ? s : smin;
+  s = s > 1 ? s : 1;
+  p.chunk = ((n + s - 1) / s + 3) & ~3;
+  p.S = (n + p.chunk - 1) / p.chunk;
+  const size_t per_tile = (static_cast<size_t>(p.S) + 1) * p.tile_words() * 4;
+  size_t tb = kImageCap / per_tile;
+  tb = tb < 1 ? 1 : tb;
+  p.tb = tb < static_cast<size_t>(p.tiles) ? static_cast<int>(tb) : p.tiles;
+  return p;
+}
+
+template <int WT, int LT, bool GLOB>
+int launch_pass(bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(a.bins) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
+  const void* fn = select ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB>) : reinterpret_cast<const void*>(hist_kernel<WT, LT, GLOB>);
+  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "retrieval: cannot reserve %zu bytes of LDS", lds);
+  if (select) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl);
+  else hipLaunchKernelGGL((hist_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl);
+  CMH_CHECK_LAUNCH(select ? "hamming_topk select" : "hamming_hist");
+  return CMH_OK;
+}
+
+template <int WT, bool GLOB>
+int launch_labels(bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  if (a.LW == 0) return launch_pass<WT, LAB_NONE, GLOB>(select, a, rs, rn, rl, st);
+  if (!GLOB && a.LW == 1) return launch_pass<WT, 1, GLOB>(select, a, rs, rn, rl, st);      // <= 32 classes (MIRFlickr 24, NUS-WIDE 21)
+  if (!GLOB && a.LW == 3) return launch_pass<WT, 3, GLOB>(select, a, rs, rn, rl, st);      // 65..96 classes (MS-COCO 80)
+  return launch_pass<WT, LAB_ANY, GLOB>(select, a, rs, rn, rl, st);
+}
+
+int launch_any(bool glob, bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  if (glob) return launch_labels<0, true>(select, a, rs, rn, rl, st);
+  if (a.W == 1) return launch_labels<1, false>(select, a, rs, rn, rl, st);
+  if (a.W == 2) return launch_labels<2, false>(select, a, rs, rn, rl, st);
+  if (a.W == 3) return launch_labels<3, false>(select, a, rs, rn, rl, st);
+  return launch_labels<4, false>(select, a, rs, rn, rl, st);
+}
+
+int check_shape(const char* what, int Q, int64_t N, int bits, int classes, bool labels) {
+  CMH_CHECK_ARG(Q > 0 && Q <= 65535 && N > 0, "%s: Q=%d N=%lld", what, Q, static_cast<long long>(N));
+  CMH_CHECK_ARG(N <= kRetMaxN, "%s: N=%lld exceeds %d", what, static_cast<long long>(N), kRetMaxN);
+  CMH_CHECK_ARG(bits > 0 && bits <= 32 * kRetMaxWords, "%s: bits=%d unsupported", what, bits);
+  CMH_CHECK_ARG(!labels || (classes > 0 && classes <= 32 * kRetMaxWords), "%s: classes=%d unsupported", what, classes);
+  return CMH_OK;
+}
+
+// hist (k == 0) or hist + select (k > 0), in batches of query tiles
+int run(const char* what, const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+        const uint32_t* r_nz, const uint32_t* r_label, int Q, int64_t N, int bits, int classes, int k, int32_t* idx, float* dist,
+        uint8_t* rel, uint32_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const Plan p = make_plan(Q, N, bits);
+  if (!workspace || workspace_bytes < p.bytes()) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, p.bytes());
+  RetArgs a;
+  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = q_label ? (classes + 31) / 32 : 0; a.bins = p.bins;
+  a.S = p.S; a.chunk = p.chunk; a.k = k;
+  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  const bool select = k > 0;
+  for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
+    const int q0 = t0 * 64;
+    a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
+    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
+    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
+    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
+    a.ql = q_label ? q_label + static_cast<size_t>(q0) * a.LW : nullptr;
+    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
+    a.img = base;
+    a.off = base + static_cast<size_t>(a.S) * stride;
+    a.hstar = reinterpret_cast<int32_t*>(a.off + stride);
+    a.counts = counts ? counts + static_cast<size_t>(q0) * a.bins * 2 : nullptr;
+    a.idx = idx ? idx + static_cast<size_t>(q0) * k : nullptr;
+    a.dist = dist ? dist + static_cast<size_t>(q0) * k : nullptr;
+    a.rel = rel ? rel + static_cast<size_t>(q0) * k : nullptr;
+    if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
+      return fail(CMH_ERR_LAUNCH, "%s: memset failed", what);
+    int rc = launch_any(p.glob, false, a, r_sign, r_nz, r_label, st);
+    if (rc != CMH_OK) return rc;
+    hipLaunchKernelGGL(reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, select ? 1 : 0);
+    CMH_CHECK_LAUNCH("retrieval reduce");
+    if (select) {
+      hipLaunchKernelGGL(radius_kernel, dim3(a.tiles), dim3(64), 0, st, a);
+      CMH_CHECK_LAUNCH("retrieval radius");
+      rc = launch_any(p.glob, true, a, r_sign, r_nz, r_label, st);
+      if (rc != CMH_OK) return rc;
+    }
+  }
+  return CMH_OK;
+}
+
+}  // namespace
+}  // namespace cmh
+
+using namespace cmh;
+
+extern "C" size_t cmh_retrieval_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
+  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
+  return make_plan(Q, N, bits).bytes();
+}
+
+extern "C" int cmh_hamming_hist(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                                const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                                uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && counts, "hamming_hist: null pointer");
+  CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_hist: labels on one side only");
+  const int rc = check_shape("hamming_hist", Q, N, bits, classes, q_label != nullptr);
+  if (rc != CMH_OK) return rc;
+  return run("hamming_hist", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, 0, nullptr, nullptr, nullptr, counts,
+             workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" int cmh_hamming_topk(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                                const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                                int64_t k, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && idx && dist, "hamming_topk: null pointer");
+  CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_topk: labels on one side only");
+  CMH_CHECK_ARG(!rel || q_label, "hamming_topk: hit flags asked for without labels");
+  CMH_CHECK_ARG(k >= 1 && k <= CMH_TOPK_MAX, "hamming_topk: k=%lld outside [1, %d]", static_cast<long long>(k), CMH_TOPK_MAX);
+  const int rc = check_shape("hamming_topk", Q, N, bits, classes, q_label != nullptr);
+  if (rc != CMH_OK) return rc;
+  CMH_CHECK_ARG(k <= N, "hamming_topk: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
+  return run("hamming_topk", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist, rel,
+             counts, workspace, workspace_bytes, as_stream(stream));
+}

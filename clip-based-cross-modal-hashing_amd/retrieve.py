@@ -1,0 +1,53 @@
+"""Top-k search in the codes a trainer saved: serves the PR_cruve/<bits>-ours-<dataset>-<mode>.mat files of TrainBase.save_mat
+(q_img q_txt r_img r_txt q_l r_l), no model needed.
+
+    python retrieve.py --codes result/DSPH/flickr25k/64/PR_cruve/64-ours-flickr25k-i2t.mat --direction i2t --k 10 --queries 0:5
+
+prints one line per query: its number, then `index:distance` (`index:distance:hit` when the file has labels) for the k nearest
+database items, nearest first, ties by database index."""
+import argparse
+import sys
+
+DIRECTIONS = {"i2t": ("q_img", "r_txt"), "t2i": ("q_txt", "r_img"), "i2i": ("q_img", "r_img"), "t2t": ("q_txt", "r_txt")}
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--codes", required=True, help=".mat file written by a trainer (save_mat)")
+    p.add_argument("--direction", choices=sorted(DIRECTIONS), default="i2t", help="query side -> database side")
+    p.add_argument("--k", type=int, default=10, help="neighbours per query")
+    p.add_argument("--queries", default=":", help="slice a:b of the file's queries (default: all)")
+    return p.parse_args(argv)
+
+
+def query_slice(text, n):
+    a, _, b = text.partition(":")
+    lo, hi = (int(a) if a else 0), (int(b) if b else n)
+    if not 0 <= lo <= hi <= n:
+        raise SystemExit(f"--queries {text}: outside 0:{n}")
+    return lo, hi
+
+
+def main(argv=None):
+    args = parse(argv)
+    import scipy.io as scio
+    import torch
+
+    from utils.retrieval import CodeIndex
+    q_key, r_key = DIRECTIONS[args.direction]
+    m = scio.loadmat(args.codes)
+    lo, hi = query_slice(args.queries, m[q_key].shape[0])
+    index = CodeIndex.from_mat(args.codes, side=r_key)
+    queries = torch.from_numpy(m[q_key][lo:hi]).float()
+    labels = torch.from_numpy(m["q_l"][lo:hi]).float() if index.labels is not None and "q_l" in m else None
+    if hi == lo:
+        return 0
+    out = [t.cpu().numpy() for t in index.search(queries, args.k, labels)]
+    for i in range(hi - lo):
+        cols = [f"{out[0][i, j]}:{out[1][i, j]:g}" + (f":{out[2][i, j]}" if len(out) == 3 else "") for j in range(args.k)]
+        print(lo + i, " ".join(cols))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -341,13 +341,33 @@ class TrainBase(object):
         mAPi2t, mAPt2i, mAPi2i, mAPt2t = self._four_maps(query_img, query_txt, retrieval_img, retrieval_txt)
         self.max_mapt2i = max(self.max_mapt2i, mAPt2i)
         self.logger.info(f">>>>>> MAP(i->t): {mAPi2t}, MAP(t->i): {mAPt2i}, MAP(t->t): {mAPt2t}, MAP(i->i): {mAPi2i}")
-        self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name)
+        extra = self._eval_curves(query_img, query_txt, retrieval_img, retrieval_txt) if getattr(self.args, "eval_curves", False) else None
+        self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
+
+    def _eval_curves(self, query_img, query_txt, retrieval_img, retrieval_txt):
+        """--eval-curves: precision-recall by Hamming radius and top-N precision for the four directions (utils/retrieval.py), the
+        curves the reference's users draw offline from the .mat file.  Every rank holds all codes (like _map); only the main one
+        writes."""
+        from utils import retrieval as R
+        sides = {"i2t": (query_img, retrieval_txt), "t2i": (query_txt, retrieval_img),
+                 "i2i": (query_img, retrieval_img), "t2t": (query_txt, retrieval_txt)}
+        topn = tuple(n for n in R.DEFAULT_TOPN if n <= retrieval_img.shape[0])
+        extra = {"curve_topn": torch.tensor(topn).numpy()}
+        for name, (q, r) in sides.items():
+            p, rc, counts = R.pr_curve(q, r, self.query_labels, self.retrieval_labels)
+            tp, tr, _ = R.topn_precision(q, r, self.query_labels, self.retrieval_labels, topn)
+            extra.update({f"pr_precision_{name}": p.numpy(), f"pr_recall_{name}": rc.numpy(), f"pr_counts_{name}": counts.cpu().numpy(),
+                          f"topn_precision_{name}": tp.numpy(), f"topn_recall_{name}": tr.numpy()})
+            at = {n: float(tp[topn.index(n)]) for n in (100, 500, 1000) if n in topn}
+            shown = [f"P@H<=2: {float(p[min(4, p.numel() - 1)]):.6f}"] + [f"P@{n}: {v:.6f}" for n, v in at.items()]      # radius 2 = half-distance 4
+            self.logger.info(f">>>>>> curves({name}): " + ", ".join(shown))
+        return extra
 
     def compute_loss(self):
         raise NotImplementedError("Function of 'compute_loss' doesn't implement.")
 
-    def save_mat(self, query_img, query_txt, retrieval_img, retrieval_txt, mode_name="i2t"):
+    def save_mat(self, query_img, query_txt, retrieval_img, retrieval_txt, mode_name="i2t", extra=None):
         """PR_cruve/<bits>-ours-<dataset>-<mode>.mat with q_img q_txt r_img r_txt q_l r_l (train/base.py:328-349)."""
         if not getattr(self.args, "save_mat", True) or not getattr(self, "is_main", True):
             return
@@ -359,5 +379,7 @@ class TrainBase(object):
             'r_img': retrieval_img.cpu().detach().numpy(), 'r_txt': retrieval_txt.cpu().detach().numpy(),
             'q_l': self.query_labels.numpy(), 'r_l': self.retrieval_labels.numpy(),
         }
+        if extra:
+            result_dict.update(extra)
         scio.savemat(os.path.join(save_dir, str(self.args.output_dim) + "-ours-" + self.args.dataset + "-" + mode_name + ".mat"), result_dict)
         self.logger.info(f">>>>>> save best {mode_name} data!")

@@ -420,6 +420,28 @@ int cmh_hamming_map(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t
 int cmh_map_mean(const float* ap, int32_t Q, float* map, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Retrieval on the same packed operands (csrc/retrieval.hip): what the reference leaves to an offline step on the
+ * .mat files under PR_cruve/ of train/base.py::save_mat. Distances are calc_hammingDist's (utils/calc_utils.py:8-13) in half-units
+ * h = K - q.r, 0 <= h <= 2K; relevance is calc_neighbor's test (:42-45).  Labels are optional: pass both label pointers or
+ * neither (classes is then ignored).  Q <= 65535, N <= 524287, bits <= 2048, classes <= 2048.
+ * ------------------------------------------------------------------------------------------- */
+#define CMH_TOPK_MAX 524287   /* largest k of cmh_hamming_topk: the select keeps no list of k entries, so it is the largest N */
+size_t cmh_retrieval_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+/* counts u32 [Q, 2K+1, 2]: counts[i, h, 1] = database items at half-distance h from query i that share a label with it,
+ * counts[i, h, 0] = the others (all of them without labels): precision / recall by Hamming radius, tie-free. */
+int cmh_hamming_hist(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                     const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                     uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* The k nearest database items of EVERY query (also of one without relevant items, which cmh_hamming_map skips), ordered by
+ * (distance, database index): the first k columns of torch.sort(calc_hammingDist(q, r), stable=True) and of the CMH_TIE_STABLE
+ * ranking.  1 <= k <= min(N, CMH_TOPK_MAX).  idx i32 [Q, k]; dist f32 [Q, k] = 0.5 * h exactly; rel u8 [Q, k] (optional, needs
+ * labels) = the item is relevant; counts (optional) as cmh_hamming_hist. */
+int cmh_hamming_topk(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                     const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                     int64_t k, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */
 size_t cmh_loss_workspace_bytes(int32_t B, int32_t K, int32_t C);

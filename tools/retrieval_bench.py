@@ -1,0 +1,108 @@
+"""Top-k search and distance histograms (csrc/retrieval.hip) against the only route to the same neighbours without them:
+hamming_map(tie_order=TIE_STABLE, want_perm=True)[2][:, :k], a full sort of N per query and a [Q, N] int32 ranking.
+
+Shapes: 5000 x 15 015 x 64 bit (bench.py's default --map-db) and 5000 x 190 834 x 128 bit (NUS-WIDE).  Packed, resident operands;
+every leg warmed up; legs alternate (ranking, topk k=100, topk k=1000, histogram) x REGIONS in one process; device events around each
+region; a region of the new legs is several calls (a single one is too short to time) and is reported per call.  The outputs of the
+two routes are compared on the timed inputs.  One JSON line per shape (also into --out).
+
+Floors of one pass over the database, from the shapes (printed with the line):
+  bytes     query tiles x N x (2 W + LW) x 4 B: the database is re-read once per tile of 64 queries, from L2 (34.5 TB/s aggregate);
+  increments  query tiles x N wave-wide LDS increments, one per 4 LDS cycles per CU (the cost of a 32-bit LDS write instruction),
+            256 CUs at 2.4 GHz;
+  valu      query tiles x N x (5 W + 8) wave-wide vector instructions of 4 cycles on 1024 SIMDs at 2.4 GHz (and / xor / and / two
+            popcounts and their sums per word, the distance, the relevance test, the address).
+The search makes two passes (the second without increments for most items)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "clip-based-cross-modal-hashing_amd"))
+
+SHAPES = {"flickr_15015_64": (5000, 15015, 64, 24), "nuswide_190834_128": (5000, 190834, 128, 21)}
+REGIONS = 5
+
+
+def floors_ms(Q, n, bits, classes, passes):
+    tiles, W, LW = (Q + 63) // 64, (bits + 31) // 32, (classes + 31) // 32
+    by = tiles * n * (2 * W + LW) * 4 / 34.5e12
+    inc = tiles * n * 4 / (256 * 2.4e9)
+    valu = tiles * n * (5 * W + 8) * 4 / (1024 * 2.4e9)
+    out = {"bytes": by * 1e3 * passes, "increments": inc * 1e3, "valu": valu * 1e3 * passes}
+    out["bound"] = max(out, key=out.get)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument("--reps", type=int, default=5, help="calls per timed region of the new legs")
+    ap.add_argument("--out", default="", help="append the JSON lines to this file")
+    args = ap.parse_args()
+    import torch
+    import cmh_native as N
+    if not torch.cuda.is_available():
+        raise SystemExit("retrieval_bench needs a GPU: nothing is measured without one")
+    dev = torch.device("cuda:0")
+    for name in args.shapes:
+        Q, n, K, C = SHAPES[name]
+        g = torch.Generator().manual_seed(1)
+        rL = (torch.rand(n, C, generator=g) < 0.1).float()
+        qL = (torch.rand(Q, C, generator=g) < 0.1).float()
+        rL[:, 0] = 1.0                                            # every query has relevant items: the ranking skips none
+        qL[:, 0] = 1.0
+        Wm = torch.randn(C, K, generator=g)
+        mk = lambda lab: torch.sign(lab @ Wm + 0.5 * torch.randn(lab.shape[0], K, generator=g) + 1e-3).to(dev)
+        rp, qp = N.pack_codes(mk(rL)), N.pack_codes(mk(qL))
+        rl, ql = N.pack_labels(rL.to(dev)), N.pack_labels(qL.to(dev))
+        legs = {
+            "ranking": (1, lambda: N.hamming_map(qp, ql, rp, rl, K, C, tie_order=N.TIE_STABLE, want_perm=True)[2][:, :1000]),
+            "topk100": (args.reps, lambda: N.hamming_topk(qp, rp, K, 100, ql, rl)),
+            "topk1000": (args.reps, lambda: N.hamming_topk(qp, rp, K, 1000, ql, rl)),
+            "hist": (args.reps, lambda: N.hamming_hist(qp, rp, K, ql, rl)),
+        }
+        # warm-up, and the outputs of the two routes on the timed inputs
+        perm = legs["ranking"][1]()
+        i100, i1000, counts = legs["topk100"][1](), legs["topk1000"][1](), legs["hist"][1]()
+        same = bool(torch.equal(i1000[0], perm)) and bool(torch.equal(i100[0], perm[:, :100]))
+        full = N.hamming_dist((qp[0][:64].contiguous(), qp[1][:64].contiguous()), rp, K)
+        same = same and bool(torch.equal(i1000[1][:64], full.gather(1, i1000[0][:64].long())))
+        same = same and bool((counts.long().sum((1, 2)) == n).all())
+        del perm, full
+        torch.cuda.synchronize()
+        times = {k: [] for k in legs}
+        for _ in range(REGIONS):
+            for leg, (reps, fn) in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    out = fn()
+                e1.record()
+                e1.synchronize()
+                del out
+                times[leg].append(e0.elapsed_time(e1) / reps)
+        line = {"tool": "retrieval_bench", "shape": name, "Q": Q, "N": n, "bits": K, "classes": C, "regions": REGIONS,
+                "outputs_equal": same, "ms": {}}
+        for leg, ts in times.items():
+            line["ms"][leg] = {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
+        for leg, passes in (("topk100", 2), ("topk1000", 2), ("hist", 1)):
+            fl = floors_ms(Q, n, K, C, passes)
+            line["ms"][leg]["floor_ms"] = {k: (round(v, 4) if k != "bound" else v) for k, v in fl.items()}
+            line["ms"][leg]["share_of_floor"] = round(fl[fl["bound"]] / line["ms"][leg]["median"], 4)
+            line["ms"][leg]["ranking_min_over_max"] = round(line["ms"]["ranking"]["min"] / line["ms"][leg]["max"], 2)
+        line["new_slowest_beats_ranking_fastest"] = all(line["ms"][leg]["max"] < line["ms"]["ranking"]["min"] for leg in ("topk100", "topk1000"))
+        text = json.dumps(line)
+        print(text, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(text + "\n")
+        if not same:
+            raise SystemExit(f"{name}: the two routes disagree")
+
+
+if __name__ == "__main__":
+    main()
