@@ -18,7 +18,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "cmh_common.h"
+#include "encoder_blocks.h"
 
 namespace cmh {
 
@@ -32,20 +32,8 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-struct Arena {
-  char* base;
-  size_t off = 0;
-  explicit Arena(void* p) : base(static_cast<char*>(p)) {}
-  void* take(size_t bytes) {
-    void* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  }
-};
-
 struct TowerBufs {
   float* x;
-  int xh = 0;   // x holds fp16 (bf16 mode, see header)
   void* h;
   void* qkv;
   void* mlp;
@@ -59,14 +47,14 @@ struct TowerBufs {
 static TowerBufs carve(void* ws, size_t M, size_t B, size_t d, size_t e, size_t extra_qkv, size_t extra_mlp, size_t conv1_w_bytes = 0) {
   Arena a(ws);
   TowerBufs t;
-  t.x = static_cast<float*>(a.take(M * d * 4));
+  t.x = a.take<float>(M * d * 4);
   t.h = a.take(M * d * e);
   size_t qkv_b = M * 3 * d * e, mlp_b = M * 4 * d * e;
   t.qkv = a.take(qkv_b > extra_qkv ? qkv_b : extra_qkv);
   t.mlp = a.take(mlp_b > extra_mlp ? mlp_b : extra_mlp);
-  t.rows = static_cast<int32_t*>(a.take(B * 4));
+  t.rows = a.take<int32_t>(B * 4);
   t.pool = a.take(B * d * e);
-  t.seq = static_cast<int32_t*>(a.take((B + 2) * 4));
+  t.seq = a.take<int32_t>((B + 2) * 4);
   t.conv1_w = a.take(conv1_w_bytes);
   t.total = a.off;
   return t;
@@ -79,68 +67,165 @@ static int tap(const cmh_taps* taps, int idx, const float* x, size_t bytes, hipS
   return CMH_OK;
 }
 
+// ---- the block recipe -------------------------------------------------------------------------------------------------------------
 // One ResidualAttentionBlock (model/base/model.py:191-196):
 //   x += out_proj(attn(in_proj(ln_1(x))));  x += c_proj(QuickGELU(c_fc(ln_2(x))))
+// This is the only statement of its launch sequence: inference and training, one tower or two in lock-step, every arithmetic mode,
+// full-size or pooled tail are options of block_forward (fields of Lane, encoder_blocks.h), so that the paths the tests compare bit for
+// bit run the same launches by construction.  The two stage helpers below hide the arithmetic mode and the tower count.
 // fp8 mode (CMH_FP8): the four GEMMs on e4m3 operands.  Activations are quantised by their producers with the per-tensor
 // scales of cmh_block_weights.act_scale (LayerNorm -> launch_layernorm_q, attention -> its fp8 store, QuickGELU -> the c_fc
 // epilogue); the GEMM epilogues undo act_scale * colscale[n].  Residual stream fp16, qkv bf16 (attention is the bf16 kernel).
-static int run_block_fp8(const cmh_block_weights& w, const TowerBufs& t, int B, int T, int d, int causal, const uint8_t* kpm,
-                         hipStream_t st, int M, const int32_t* seq_off, const int32_t* md = nullptr, int mh = -1) {
+static int check_lane(const Lane& l) {
+  CMH_CHECK_ARG(!l.amax || l.dtb == CMH_BF16, "fp8 calibration runs in bf16 mode");
+  if (l.dtb != CMH_FP8) return CMH_OK;
+  const cmh_block_weights& w = *l.w;
   const float* a = w.act_scale;
-  CMH_CHECK_ARG(t.xh, "fp8 mode runs on the fp16 residual stream (width %% 256 == 0, no taps)");
+  CMH_CHECK_ARG(l.xh, "fp8 mode runs on the fp16 residual stream (width %% 256 == 0, no taps)");
   CMH_CHECK_ARG(w.in_proj_cs && w.out_proj_cs && w.fc_cs && w.proj_cs, "fp8 mode: weight scales missing");
   CMH_CHECK_ARG(a[0] > 0.f && a[1] > 0.f && a[2] > 0.f && a[3] > 0.f, "fp8 mode: activation scales missing (run the calibration pass)");
-  const int rx = EPI_BIAS | EPI_RESIDUAL | EPI_RES_F16 | EPI_OUT_F16;
-  int rc;
-  if ((rc = launch_layernorm_q(t.x, w.ln1_w, w.ln1_b, t.h, 1.0f / a[0], M, d, st, md))) return rc;
-  if ((rc = launch_gemm_fp8(t.h, w.in_proj_w, w.in_proj_cs, a[0], w.in_proj_b, nullptr, t.qkv, 1.f, M, 3 * d, d, EPI_BIAS | EPI_OUT_BF16, st, md, mh))) return rc;
-  if ((rc = launch_attention_varlen(t.qkv, t.h, CMH_BF16, B, T, d, causal, kpm, seq_off, st, 1.0f / a[1]))) return rc;
-  if ((rc = launch_gemm_fp8(t.h, w.out_proj_w, w.out_proj_cs, a[1], w.out_proj_b, t.x, t.x, 1.f, M, d, d, rx, st, md, mh))) return rc;
-  if ((rc = launch_layernorm_q(t.x, w.ln2_w, w.ln2_b, t.h, 1.0f / a[2], M, d, st, md))) return rc;
-  if ((rc = launch_gemm_fp8(t.h, w.fc_w, w.fc_cs, a[2], w.fc_b, nullptr, t.mlp, 1.0f / a[3], M, 4 * d, d,
-                            EPI_BIAS | EPI_QUICKGELU | EPI_OUT_FP8, st, md, mh))) return rc;
-  if ((rc = launch_gemm_fp8(t.mlp, w.proj_w, w.proj_cs, a[3], w.proj_b, t.x, t.x, 1.f, M, d, 4 * d, rx, st, md, mh))) return rc;
   return CMH_OK;
 }
 
-static int run_block(const cmh_block_weights& w, int dt, const TowerBufs& t, int B, int T, int d, int causal,
-                     const uint8_t* kpm, hipStream_t st, int rows = -1, const int32_t* seq_off = nullptr,
-                     float* amax = nullptr,     // amax [4] (bf16 mode): running maxima of the four GEMM inputs (fp8 calibration)
-                     const int32_t* md = nullptr, int mh = -1) {   // md: the packed row count on the device (rows = upper bound)
-  const int M = rows >= 0 ? rows : B * T;      // packed variable-length text: `rows` real rows, T = the longest sequence
-  if (dt == CMH_FP8) return run_block_fp8(w, t, B, T, d, causal, kpm, st, M, seq_off, md, mh);
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  const int rx = EPI_BIAS | EPI_RESIDUAL | (t.xh ? EPI_RES_F16 | EPI_OUT_F16 : 0);
-  int rc;
-  if (amax) {   // the calibration pass: the same kernels, with a reduction after each producer
-    CMH_CHECK_ARG(dt == CMH_BF16, "fp8 calibration runs in bf16 mode");
-    const size_t n = static_cast<size_t>(M) * d;
-    if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w.ln1_w, w.ln1_b, t.h, 1, M, d, st))) return rc;
-    if ((rc = launch_amax(t.h, kBF16, n, amax + 0, st))) return rc;
-    if ((rc = launch_gemm(dt, t.h, w.in_proj_w, w.in_proj_b, nullptr, t.qkv, M, 3 * d, d, EPI_BIAS | obf, st))) return rc;
-    if ((rc = launch_attention_varlen(t.qkv, t.h, dt, B, T, d, causal, kpm, seq_off, st))) return rc;
-    if ((rc = launch_amax(t.h, kBF16, n, amax + 1, st))) return rc;
-    if ((rc = launch_gemm(dt, t.h, w.out_proj_w, w.out_proj_b, t.x, t.x, M, d, d, rx, st))) return rc;
-    if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w.ln2_w, w.ln2_b, t.h, 1, M, d, st))) return rc;
-    if ((rc = launch_amax(t.h, kBF16, n, amax + 2, st))) return rc;
-    if ((rc = launch_gemm(dt, t.h, w.fc_w, w.fc_b, nullptr, t.mlp, M, 4 * d, d, EPI_BIAS | EPI_QUICKGELU | obf, st))) return rc;
-    if ((rc = launch_amax(t.mlp, kBF16, n * 4, amax + 3, st))) return rc;
-    return launch_gemm(dt, t.mlp, w.proj_w, w.proj_b, t.x, t.x, M, d, 4 * d, rx, st);
+// GEMM operand i of a block: 0 ln_1's output, 1 the attention's, 2 ln_2's, 3 QuickGELU's.  fp8 mode: its producer stores
+// e4m3(v * 1 / scale(i)), the GEMM that reads it multiplies scale(i) back (alpha); calibration: amax[i] is its running maximum.
+enum { OP_LN1 = 0, OP_ATTN = 1, OP_LN2 = 2, OP_ACT = 3 };
+static float scale(const Lane& l, int i) { return l.w->act_scale[i]; }
+static int amax_stage(const Lane& l, int i, const void* v, size_t n, hipStream_t st) {
+  return l.amax ? launch_amax(v, kBF16, n, l.amax + i, st) : CMH_OK;
+}
+
+struct Rows { int M; const int32_t* md; int mh; };     // a stage's row count: upper bound, the count on the device, its likely value
+static Rows head_rows(const Lane& l) { return Rows{l.M, l.md, l.mh}; }
+static Rows tail_rows(const Lane& l) { return l.pooled ? Rows{l.B, nullptr, -1} : head_rows(l); }
+
+// LayerNorm stage (OP_LN1 | OP_LN2) of one tower or two
+struct LnArgs { const void* x; const float *g, *b; void* out; Rows r; };
+static LnArgs ln_args(const Lane& l, int op) {
+  if (op == OP_LN1) return LnArgs{l.x_in, l.w->ln1_w, l.w->ln1_b, l.h1, head_rows(l)};
+  return LnArgs{l.x_mid, l.w->ln2_w, l.w->ln2_b, l.h2, tail_rows(l)};
+}
+static int ln_stage(const Lane* const* L, int n, int op, hipStream_t st) {
+  const LnArgs p = ln_args(*L[0], op);
+  int rc = 1;
+  if (n == 2 && L[0]->dtb == CMH_BF16 && L[0]->xh && L[1]->xh) {     // fp16 stream -> bf16 rows: both towers' rows in one launch
+    const LnArgs q = ln_args(*L[1], op);
+    rc = launch_layernorm_h2b_pair(p.x, p.g, p.b, p.out, p.r.M, L[0]->d, p.r.md, q.x, q.g, q.b, q.out, q.r.M, L[1]->d, q.r.md, st);
+    if (rc < 0) return rc;
   }
-  if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w.ln1_w, w.ln1_b, t.h, dt == CMH_BF16, M, d, st, md))) return rc;
-  if ((rc = launch_gemm(dt, t.h, w.in_proj_w, w.in_proj_b, nullptr, t.qkv, M, 3 * d, d, EPI_BIAS | obf, st, md, mh))) return rc;
-  if ((rc = launch_attention_varlen(t.qkv, t.h, dt, B, T, d, causal, kpm, seq_off, st))) return rc;
-  if ((rc = launch_gemm(dt, t.h, w.out_proj_w, w.out_proj_b, t.x, t.x, M, d, d, rx, st, md, mh))) return rc;
-  if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w.ln2_w, w.ln2_b, t.h, dt == CMH_BF16, M, d, st, md))) return rc;
-  if ((rc = launch_gemm(dt, t.h, w.fc_w, w.fc_b, nullptr, t.mlp, M, 4 * d, d, EPI_BIAS | EPI_QUICKGELU | obf, st, md, mh))) return rc;
-  return launch_gemm(dt, t.mlp, w.proj_w, w.proj_b, t.x, t.x, M, d, 4 * d, rx, st, md, mh);
+  for (int i = 0; i < n; ++i) {
+    const Lane& l = *L[i];
+    const LnArgs a = i ? ln_args(l, op) : p;
+    if (rc > 0) {      // (no pair kernel for these widths: one launch per tower)
+      const int r1 = l.dtb == CMH_FP8 ? launch_layernorm_q(a.x, a.g, a.b, a.out, 1.0f / scale(l, op), a.r.M, l.d, st, a.r.md)
+                                      : launch_layernorm_x(a.x, l.xh, nullptr, a.g, a.b, a.out, l.dtb == CMH_BF16, a.r.M, l.d, st, a.r.md);
+      if (r1) return r1;
+    }
+    if (int r2 = amax_stage(l, op, a.out, static_cast<size_t>(a.r.M) * l.d, st)) return r2;
+  }
+  return CMH_OK;
+}
+
+// GEMM stage of one tower (launch_gemm / launch_gemm_fp8) or two (launch_gemm_grouped): everything about the four GEMMs in one table
+enum { G_IN_PROJ, G_OUT_PROJ, G_FC, G_PROJ };
+static bool fc_pre_fused(const Lane& l) {     // the N % 256 == 0 GEMM kernel stores the pre-activation from its epilogue
+  static const bool fuse_act = []() { const char* e = getenv("CMH_FUSE_PRE"); return !(e && e[0] == '0'); }();
+  return l.dtb == CMH_BF16 && (4 * l.d) % 256 == 0 && fuse_act;
+}
+static GemmProblem gemm_problem(const Lane& l, int which, int* epi) {
+  const cmh_block_weights& w = *l.w;
+  const bool q = l.dtb == CMH_FP8;
+  const int d = l.d;
+  const int obf = l.dtb == CMH_F32 ? 0 : EPI_OUT_BF16;
+  const int rx = EPI_BIAS | EPI_RESIDUAL | (l.xh ? EPI_RES_F16 | EPI_OUT_F16 : 0);
+  struct Row { const void* A; const void* W; const float* bias; const float* cs; const void* res; void* out; int N, K, op; float oscale; int epi; };
+  const Row tab[4] = {
+      {l.h1, w.in_proj_w, w.in_proj_b, w.in_proj_cs, nullptr, l.qkv, 3 * d, d, OP_LN1, 1.f, EPI_BIAS | obf},
+      {l.pooled ? l.attn_p : l.attn, w.out_proj_w, w.out_proj_b, w.out_proj_cs, l.pooled ? l.x_mid : l.x_in, l.x_mid, d, d, OP_ATTN, 1.f, rx},
+      {l.h2, w.fc_w, w.fc_b, w.fc_cs, nullptr, l.act, 4 * d, d, OP_LN2, q ? 1.0f / scale(l, OP_ACT) : 1.f,
+       EPI_BIAS | EPI_QUICKGELU | (q ? EPI_OUT_FP8 : obf)},
+      {l.act, w.proj_w, w.proj_b, w.proj_cs, l.x_mid, l.x_out, d, 4 * d, OP_ACT, 1.f, rx}};
+  Row r = tab[which];
+  if (which == G_FC && l.pre) {
+    // training keeps c_fc's pre-activation.  One launch (EPI_SAVE_PRE): the activation from the f32 accumulator into act, the bf16
+    // pre-activation into pre through the residual slot; else the GEMM writes pre and QuickGELU is a pass of its own (block_tail)
+    if (fc_pre_fused(l)) { r.res = l.pre; r.epi |= EPI_SAVE_PRE; }
+    else { r.out = l.pre; r.epi &= ~EPI_QUICKGELU; }
+  }
+  const Rows m = which == G_IN_PROJ ? head_rows(l) : tail_rows(l);
+  *epi = r.epi;
+  return GemmProblem{r.A, r.W, r.bias, static_cast<const float*>(r.res), r.out, m.M, r.N, r.K, m.md, m.mh, q ? r.cs : nullptr,
+                     q ? scale(l, r.op) : 1.f, r.oscale};
+}
+static int gemm_stage(const Lane* const* L, int n, int which, hipStream_t st) {
+  int epi = 0, epi_b = 0;
+  const GemmProblem p = gemm_problem(*L[0], which, &epi);
+  if (n == 2) return launch_gemm_grouped(L[0]->dtb, p, gemm_problem(*L[1], which, &epi_b), epi, st);
+  if (L[0]->dtb == CMH_FP8)
+    return launch_gemm_fp8(p.A, p.W, p.colscale, p.alpha, p.bias, p.residual, p.out, p.oscale, p.M, p.N, p.K, epi, st, p.m_dev, p.m_hint);
+  return launch_gemm(L[0]->dtb, p.A, p.W, p.bias, p.residual, p.out, p.M, p.N, p.K, epi, st, p.m_dev, p.m_hint);
+}
+
+// everything behind the attention: row-wise, so on the pooled rows only where the lane says so
+static int block_tail(const Lane* const* L, int n, hipStream_t st) {
+  int rc;
+  for (int i = 0; i < n; ++i) {
+    const Lane& l = *L[i];
+    const int xe = l.xh ? 2 : 4, e = l.dtb == CMH_FP8 ? 1 : l.dtb == CMH_BF16 ? 2 : 4;      // (fp8: the attention stored e4m3)
+    if (l.pooled && (rc = launch_gather_rows2(l.x_in, l.x_mid, l.d * xe, l.attn, l.attn_p, l.d * e, l.pooled, l.B, st))) return rc;
+  }
+  if ((rc = gemm_stage(L, n, G_OUT_PROJ, st))) return rc;
+  if ((rc = ln_stage(L, n, OP_LN2, st))) return rc;
+  if ((rc = gemm_stage(L, n, G_FC, st))) return rc;
+  for (int i = 0; i < n; ++i) {
+    const Lane& l = *L[i];
+    const size_t n_act = static_cast<size_t>(tail_rows(l).M) * 4 * l.d;
+    if (l.pre && !fc_pre_fused(l) &&
+        (rc = cmh_quick_gelu(l.pre, l.act, static_cast<int64_t>(n_act), l.dtb == CMH_BF16 ? kBF16 : kF32, st))) return rc;
+    if ((rc = amax_stage(l, OP_ACT, l.act, n_act, st))) return rc;
+  }
+  return gemm_stage(L, n, G_PROJ, st);
+}
+
+// ---- both towers in lock-step (round 4: grouped launches) ---------------------------------------------------------------------------
+// The image and the text tower are 12 blocks of the same four GEMMs (model/base/model.py:167-207, built twice by CLIP.__init__:
+// :254-306); run one after the other - or on two streams - every GEMM is a launch of its own whose fixed third (first stage landing
+// on 256 CUs at once, last tile's epilogue and store drain) the short-K text launches cannot amortise, and whose last round leaves
+// CUs idle.  Here layer i of BOTH towers is one grouped launch of the wide kernel (gemm_wide.hip, GRP): ~50 GEMM launches per encoded
+// batch instead of ~100, text tiles filling the image launches' last round.  Every output element sees the arithmetic of the
+// single-tower path: the features are bit-identical (tests/test_gpu_grouped.py).
+int block_forward(const Lane& a, const Lane* b, hipStream_t st) {
+  const Lane* const L[2] = {&a, b};
+  const int n = b ? 2 : 1;
+  int rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = check_lane(*L[i]))) return rc;
+  CMH_CHECK_ARG(n == 1 || a.xh == b->xh,
+                "block_forward: the towers' residual streams differ in kind (the caller runs such towers one by one)");
+  if ((rc = ln_stage(L, n, OP_LN1, st))) return rc;
+  if ((rc = gemm_stage(L, n, G_IN_PROJ, st))) return rc;
+  // (the two attentions stay two launches: one launch for both - each side's body compiled for its own key-tile count - runs every
+  // wave at the wider side's register budget, 2 waves per SIMD instead of 3 for the image side: 36.3 us against 16.6 + 16.1,
+  // profiles/r04_j_bench_kernel_stats.csv; removed again)
+  for (int i = 0; i < n; ++i) {
+    const Lane& l = *L[i];
+    const bool q = l.dtb == CMH_FP8;
+    if ((rc = launch_attention_varlen(l.qkv, l.attn, q ? CMH_BF16 : l.dtb, l.B, l.T, l.d, l.causal, l.kpm, l.seq_off, st,
+                                      q ? 1.0f / scale(l, OP_ATTN) : 0.f))) return rc;
+    if ((rc = amax_stage(l, OP_ATTN, l.attn, static_cast<size_t>(l.M) * l.d, st))) return rc;
+  }
+  if (n == 2 && (a.pooled || b->pooled)) {      // the rest of the last block on the pooled rows of each tower (few-row kernels)
+    if ((rc = block_tail(&L[0], 1, st))) return rc;
+    return block_tail(&L[1], 1, st);
+  }
+  return block_tail(L, n, st);
 }
 
 // The LAST block when only the pooled feature is wanted (encode_image / encode_text, model/base/model.py:247-250, 366-370): after its
 // attention nothing mixes rows any more - out_proj, ln_2, the MLP, ln_post / ln_final and the projection are all row-wise - so only the
 // B pooled rows (class token / EOT) are carried through them: three GEMMs of M = B instead of M = B*T.  Every kept row sees the
 // arithmetic of the full-size path (same kernels, same K order), so the features are bit-identical.  The compact rows live in the qkv
-// scratch, which is dead once the attention has run; *x_pooled [B, d] is the block's output (residual-stream type).
+// scratch, which is dead once the attention has run (pool_the_tail).
 static int g_pooled_tail = -1;   // -1: from the environment (default on)
 bool pooled_tail_enabled() {
   static const bool env_on = []() { const char* e = getenv("CMH_POOLED_TAIL"); return !(e && !strcmp(e, "0")); }();
@@ -154,134 +239,24 @@ bool text_token_packing() {
   return g_pack_tokens < 0 ? env_on : g_pack_tokens != 0;
 }
 
-static int run_block_pooled(const cmh_block_weights& w, int dtb, const TowerBufs& t, int B, int T, int d, int causal,
-                            const uint8_t* kpm, hipStream_t st, int M, const int32_t* seq_off, void** x_pooled,
-                            const int32_t* md = nullptr, int mh = -1,
-                            bool head_done = false) {   // ln_1, QKV and the attention have run already (run_block_pair)
-  const int dt = dtb == CMH_FP8 ? CMH_BF16 : dtb;
-  const size_t e = dt == CMH_BF16 ? 2 : 4, xe = t.xh ? 2 : 4;
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  const int rx = EPI_BIAS | EPI_RESIDUAL | (t.xh ? EPI_RES_F16 | EPI_OUT_F16 : 0);
-  const float* a = w.act_scale;
-  char* scratch = static_cast<char*>(t.qkv);
-  float* xp = reinterpret_cast<float*>(scratch);
-  void* hp = scratch + align_up(static_cast<size_t>(B) * d * 4, 256);
-  int rc;
-  if (dtb == CMH_FP8) {
-    CMH_CHECK_ARG(t.xh && w.in_proj_cs && w.out_proj_cs && w.fc_cs && w.proj_cs && a[0] > 0.f && a[1] > 0.f && a[2] > 0.f && a[3] > 0.f,
-                  "fp8 mode: scales missing (run the calibration pass)");
-    if (!head_done) {
-      if ((rc = launch_layernorm_q(t.x, w.ln1_w, w.ln1_b, t.h, 1.0f / a[0], M, d, st, md))) return rc;
-      if ((rc = launch_gemm_fp8(t.h, w.in_proj_w, w.in_proj_cs, a[0], w.in_proj_b, nullptr, t.qkv, 1.f, M, 3 * d, d, EPI_BIAS | EPI_OUT_BF16, st, md, mh))) return rc;
-      if ((rc = launch_attention_varlen(t.qkv, t.h, CMH_BF16, B, T, d, causal, kpm, seq_off, st, 1.0f / a[1]))) return rc;
-    }
-    if ((rc = launch_gather_rows2(t.x, xp, static_cast<int>(d * xe), t.h, hp, d, t.rows, B, st))) return rc;
-    if ((rc = launch_gemm_fp8(hp, w.out_proj_w, w.out_proj_cs, a[1], w.out_proj_b, xp, xp, 1.f, B, d, d, rx, st))) return rc;
-    if ((rc = launch_layernorm_q(xp, w.ln2_w, w.ln2_b, hp, 1.0f / a[2], B, d, st))) return rc;
-    if ((rc = launch_gemm_fp8(hp, w.fc_w, w.fc_cs, a[2], w.fc_b, nullptr, t.mlp, 1.0f / a[3], B, 4 * d, d,
-                              EPI_BIAS | EPI_QUICKGELU | EPI_OUT_FP8, st))) return rc;
-    if ((rc = launch_gemm_fp8(t.mlp, w.proj_w, w.proj_cs, a[3], w.proj_b, xp, xp, 1.f, B, d, 4 * d, rx, st))) return rc;
-  } else {
-    if (!head_done) {
-      if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w.ln1_w, w.ln1_b, t.h, dt == CMH_BF16, M, d, st, md))) return rc;
-      if ((rc = launch_gemm(dt, t.h, w.in_proj_w, w.in_proj_b, nullptr, t.qkv, M, 3 * d, d, EPI_BIAS | obf, st, md, mh))) return rc;
-      if ((rc = launch_attention_varlen(t.qkv, t.h, dt, B, T, d, causal, kpm, seq_off, st))) return rc;
-    }
-    if ((rc = launch_gather_rows2(t.x, xp, static_cast<int>(d * xe), t.h, hp, static_cast<int>(d * e), t.rows, B, st))) return rc;
-    if ((rc = launch_gemm(dt, hp, w.out_proj_w, w.out_proj_b, xp, xp, B, d, d, rx, st))) return rc;
-    if ((rc = launch_layernorm_x(xp, t.xh, nullptr, w.ln2_w, w.ln2_b, hp, dt == CMH_BF16, B, d, st))) return rc;
-    if ((rc = launch_gemm(dt, hp, w.fc_w, w.fc_b, nullptr, t.mlp, B, 4 * d, d, EPI_BIAS | EPI_QUICKGELU | obf, st))) return rc;
-    if ((rc = launch_gemm(dt, t.mlp, w.proj_w, w.proj_b, xp, xp, B, d, 4 * d, rx, st))) return rc;
-  }
-  *x_pooled = xp;
-  return CMH_OK;
-}
-
-// ---- both towers in lock-step (round 4: grouped launches) ---------------------------------------------------------------------------
-// The image and the text tower are 12 blocks of the same four GEMMs (model/base/model.py:167-207, built twice by CLIP.__init__:
-// :254-306); run one after the other - or on two streams - every GEMM is a launch of its own whose fixed third (first stage landing
-// on 256 CUs at once, last tile's epilogue and store drain) the short-K text launches cannot amortise, and whose last round leaves
-// CUs idle.  Here layer i of BOTH towers is one grouped launch of the wide kernel (gemm_wide.hip, GRP): ~50 GEMM launches per encoded
-// batch instead of ~100, text tiles filling the image launches' last round.  Every output element sees the arithmetic of the
-// single-tower path: the features are bit-identical (tests/test_gpu_grouped.py).
-struct TowerRun {
+// One tower of an encode call: its lane over the workspace buffers (one stream, updated in place)
+struct TowerRun : Lane {
   TowerBufs t;
-  int dtb = 0, d = 0, B = 0, T = 0, M = 0, causal = 0;   // M: rows (an upper bound when md is set)
-  const int32_t* seq_off = nullptr;                      // packed text: per-caption row offsets
-  const int32_t* md = nullptr;                           // packed text: the row count on the device
-  int mh = -1;                                           // ... and its likely value (tile heights only)
   bool packed_tokens = false;                            // packed text, every kept row is an output (the MITH trunk)
 };
-
-static GemmProblem problem_of(const TowerRun& r, const void* A, const void* W, const float* bias, const void* residual, void* out, int N,
-                              int K, const float* colscale = nullptr, float alpha = 1.f, float oscale = 1.f) {
-  return GemmProblem{A, W, bias, static_cast<const float*>(residual), out, r.M, N, K, r.md, r.mh, colscale, alpha, oscale};
+static void lane_in_place(TowerRun& r) {
+  r.x_in = r.x_mid = r.x_out = r.t.x;
+  r.h1 = r.attn = r.h2 = r.t.h;
+  r.qkv = r.t.qkv;
+  r.act = r.t.mlp;
 }
-
-// the full-size part of a block for both towers: ln_1, QKV, attention (then, unless `upto_attention`, out_proj, ln_2, c_fc, c_proj)
-static int run_block_pair(const cmh_block_weights& wa, const cmh_block_weights& wb, const TowerRun& a, const TowerRun& b, hipStream_t st,
-                          bool upto_attention) {
-  const int dtb = a.dtb;
-  int rc;
-  if (dtb == CMH_FP8) {
-    for (const auto* pr : {&a, &b}) {
-      const cmh_block_weights& w = pr == &a ? wa : wb;
-      const float* s = w.act_scale;
-      CMH_CHECK_ARG(pr->t.xh, "fp8 mode runs on the fp16 residual stream (width %% 256 == 0, no taps)");
-      CMH_CHECK_ARG(w.in_proj_cs && w.out_proj_cs && w.fc_cs && w.proj_cs, "fp8 mode: weight scales missing");
-      CMH_CHECK_ARG(s[0] > 0.f && s[1] > 0.f && s[2] > 0.f && s[3] > 0.f, "fp8 mode: activation scales missing (run the calibration pass)");
-    }
-    const float *sa = wa.act_scale, *sb = wb.act_scale;
-    const int rx = EPI_BIAS | EPI_RESIDUAL | EPI_RES_F16 | EPI_OUT_F16;
-    if ((rc = launch_layernorm_q(a.t.x, wa.ln1_w, wa.ln1_b, a.t.h, 1.0f / sa[0], a.M, a.d, st, a.md))) return rc;
-    if ((rc = launch_layernorm_q(b.t.x, wb.ln1_w, wb.ln1_b, b.t.h, 1.0f / sb[0], b.M, b.d, st, b.md))) return rc;
-    if ((rc = launch_gemm_grouped(CMH_FP8, problem_of(a, a.t.h, wa.in_proj_w, wa.in_proj_b, nullptr, a.t.qkv, 3 * a.d, a.d, wa.in_proj_cs, sa[0]),
-                                  problem_of(b, b.t.h, wb.in_proj_w, wb.in_proj_b, nullptr, b.t.qkv, 3 * b.d, b.d, wb.in_proj_cs, sb[0]),
-                                  EPI_BIAS | EPI_OUT_BF16, st))) return rc;
-    // (the two attentions stay two launches: one launch for both - each side's body compiled for its own key-tile count - runs every
-    // wave at the wider side's register budget, 2 waves per SIMD instead of 3 for the image side: 36.3 us against 16.6 + 16.1,
-    // profiles/r04_j_bench_kernel_stats.csv; removed again)
-    if ((rc = launch_attention_varlen(a.t.qkv, a.t.h, CMH_BF16, a.B, a.T, a.d, a.causal, nullptr, a.seq_off, st, 1.0f / sa[1]))) return rc;
-    if ((rc = launch_attention_varlen(b.t.qkv, b.t.h, CMH_BF16, b.B, b.T, b.d, b.causal, nullptr, b.seq_off, st, 1.0f / sb[1]))) return rc;
-    if (upto_attention) return CMH_OK;
-    if ((rc = launch_gemm_grouped(CMH_FP8, problem_of(a, a.t.h, wa.out_proj_w, wa.out_proj_b, a.t.x, a.t.x, a.d, a.d, wa.out_proj_cs, sa[1]),
-                                  problem_of(b, b.t.h, wb.out_proj_w, wb.out_proj_b, b.t.x, b.t.x, b.d, b.d, wb.out_proj_cs, sb[1]), rx, st))) return rc;
-    if ((rc = launch_layernorm_q(a.t.x, wa.ln2_w, wa.ln2_b, a.t.h, 1.0f / sa[2], a.M, a.d, st, a.md))) return rc;
-    if ((rc = launch_layernorm_q(b.t.x, wb.ln2_w, wb.ln2_b, b.t.h, 1.0f / sb[2], b.M, b.d, st, b.md))) return rc;
-    if ((rc = launch_gemm_grouped(CMH_FP8, problem_of(a, a.t.h, wa.fc_w, wa.fc_b, nullptr, a.t.mlp, 4 * a.d, a.d, wa.fc_cs, sa[2], 1.0f / sa[3]),
-                                  problem_of(b, b.t.h, wb.fc_w, wb.fc_b, nullptr, b.t.mlp, 4 * b.d, b.d, wb.fc_cs, sb[2], 1.0f / sb[3]),
-                                  EPI_BIAS | EPI_QUICKGELU | EPI_OUT_FP8, st))) return rc;
-    return launch_gemm_grouped(CMH_FP8, problem_of(a, a.t.mlp, wa.proj_w, wa.proj_b, a.t.x, a.t.x, a.d, 4 * a.d, wa.proj_cs, sa[3]),
-                               problem_of(b, b.t.mlp, wb.proj_w, wb.proj_b, b.t.x, b.t.x, b.d, 4 * b.d, wb.proj_cs, sb[3]), rx, st);
-  }
-  const int dt = dtb;
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  CMH_CHECK_ARG(a.t.xh == b.t.xh, "run_block_pair: the towers' residual streams differ in kind (the caller runs such towers one by one)");
-  const int rx = EPI_BIAS | EPI_RESIDUAL | (a.t.xh ? EPI_RES_F16 | EPI_OUT_F16 : 0);
-  const bool ln_pair = dt == CMH_BF16 && a.t.xh && b.t.xh;     // fp16 stream -> bf16 rows: both towers' rows in one launch
-  rc = ln_pair ? launch_layernorm_h2b_pair(a.t.x, wa.ln1_w, wa.ln1_b, a.t.h, a.M, a.d, a.md, b.t.x, wb.ln1_w, wb.ln1_b, b.t.h, b.M, b.d, b.md, st) : 1;
-  if (rc < 0) return rc;
-  if (rc > 0) {
-    if ((rc = launch_layernorm_x(a.t.x, a.t.xh, nullptr, wa.ln1_w, wa.ln1_b, a.t.h, dt == CMH_BF16, a.M, a.d, st, a.md))) return rc;
-    if ((rc = launch_layernorm_x(b.t.x, b.t.xh, nullptr, wb.ln1_w, wb.ln1_b, b.t.h, dt == CMH_BF16, b.M, b.d, st, b.md))) return rc;
-  }
-  if ((rc = launch_gemm_grouped(dt, problem_of(a, a.t.h, wa.in_proj_w, wa.in_proj_b, nullptr, a.t.qkv, 3 * a.d, a.d),
-                                problem_of(b, b.t.h, wb.in_proj_w, wb.in_proj_b, nullptr, b.t.qkv, 3 * b.d, b.d), EPI_BIAS | obf, st))) return rc;
-  if ((rc = launch_attention_varlen(a.t.qkv, a.t.h, dt, a.B, a.T, a.d, a.causal, nullptr, a.seq_off, st))) return rc;
-  if ((rc = launch_attention_varlen(b.t.qkv, b.t.h, dt, b.B, b.T, b.d, b.causal, nullptr, b.seq_off, st))) return rc;
-  if (upto_attention) return CMH_OK;
-  if ((rc = launch_gemm_grouped(dt, problem_of(a, a.t.h, wa.out_proj_w, wa.out_proj_b, a.t.x, a.t.x, a.d, a.d),
-                                problem_of(b, b.t.h, wb.out_proj_w, wb.out_proj_b, b.t.x, b.t.x, b.d, b.d), rx, st))) return rc;
-  rc = ln_pair ? launch_layernorm_h2b_pair(a.t.x, wa.ln2_w, wa.ln2_b, a.t.h, a.M, a.d, a.md, b.t.x, wb.ln2_w, wb.ln2_b, b.t.h, b.M, b.d, b.md, st) : 1;
-  if (rc < 0) return rc;
-  if (rc > 0) {
-    if ((rc = launch_layernorm_x(a.t.x, a.t.xh, nullptr, wa.ln2_w, wa.ln2_b, a.t.h, dt == CMH_BF16, a.M, a.d, st, a.md))) return rc;
-    if ((rc = launch_layernorm_x(b.t.x, b.t.xh, nullptr, wb.ln2_w, wb.ln2_b, b.t.h, dt == CMH_BF16, b.M, b.d, st, b.md))) return rc;
-  }
-  if ((rc = launch_gemm_grouped(dt, problem_of(a, a.t.h, wa.fc_w, wa.fc_b, nullptr, a.t.mlp, 4 * a.d, a.d),
-                                problem_of(b, b.t.h, wb.fc_w, wb.fc_b, nullptr, b.t.mlp, 4 * b.d, b.d), EPI_BIAS | EPI_QUICKGELU | obf, st))) return rc;
-  return launch_gemm_grouped(dt, problem_of(a, a.t.mlp, wa.proj_w, wa.proj_b, a.t.x, a.t.x, a.d, 4 * a.d),
-                             problem_of(b, b.t.mlp, wb.proj_w, wb.proj_b, b.t.x, b.t.x, b.d, 4 * b.d), rx, st);
+// the pooled tail (above) for the block that runs next: the gathered residual rows [B, d] at the start of the qkv scratch - they
+// become the block's output, x_out - and the gathered operand rows behind them
+static void pool_the_tail(TowerRun& r) {
+  char* scratch = static_cast<char*>(r.t.qkv);
+  r.pooled = r.t.rows;
+  r.x_mid = r.x_out = scratch;
+  r.attn_p = r.h2 = scratch + align_up(static_cast<size_t>(r.B) * r.d * 4, 256);
 }
 
 // The packed row count of the LAST finished call for a (batch, seq_len), as a hint for the next call's tile heights: every call
@@ -312,18 +287,42 @@ static int rows_hint_exchange(const int32_t* count_dev, int B, int L, hipStream_
   return out;
 }
 
-static int final_projection(int dt, const void* pool, const void* w_t, float* feat, int B, int embed, int d,
-                            hipStream_t st) {
+int final_projection(int dt, const void* pool, const void* w_t, float* feat, int B, int embed, int d, hipStream_t st) {
   const int bk = dt == CMH_F32 ? 32 : 64;
   if (embed % 128 == 0 && d % bk == 0) return launch_gemm(dt, pool, w_t, nullptr, nullptr, feat, B, embed, d, 0, st);
   return launch_small_linear(dt, pool, w_t, nullptr, nullptr, 1.f, CMH_ACT_NONE, feat, B, embed, d, st);
 }
 
-// fp16 residual stream?  (bf16 mode only; the residual GEMMs must take the wide kernel; taps are defined on an f32 stream)
-static int resid_f16(int dt, int d, const cmh_taps* taps) {
+int resid_f16(int dt, int d) {
   static const bool off = []() { const char* e = getenv("CMH_RESID_F16"); return e && !strcmp(e, "0"); }();
-  if (dt == CMH_FP8) return d % 256 == 0 && !taps;
-  return dt == CMH_BF16 && d % 256 == 0 && !taps && !off;
+  return dt == CMH_BF16 && d % 256 == 0 && !off;
+}
+// ... of an inference tower: the fp8 mode always runs on it; taps are defined on an f32 stream
+static int tower_xh(int dtb, int d, const cmh_taps* taps) {
+  if (taps) return 0;
+  return dtb == CMH_FP8 ? d % 256 == 0 : resid_f16(dtb, d);
+}
+
+// K-padded (conv1_k): the patch rows and a copy of the weight carry zero columns pk..pkp-1, which add exact zeros - the K = pk
+// product in the same k order.
+int conv1_stem(const cmh_vit_weights* w, int dt, const float* image, const float* image_b, int batch_a, int B, void* patches,
+               void* conv1_w_pad, float* patch_out, hipStream_t st) {
+  const int g = w->resolution / w->patch, g2 = g * g, d = w->width;
+  const int pk = 3 * w->patch * w->patch, pkp = conv1_k(w->patch, dt);    // pkp != pk: the K-padded conv1
+  const size_t e = dt == CMH_BF16 ? 2 : 4;
+  int rc;
+  if (image_b) {
+    CMH_CHECK_ARG(batch_a > 0 && batch_a < B, "vit_encode: split batch %d of %d", batch_a, B);
+    if ((rc = launch_patchify(image, patches, dt, batch_a, w->resolution, w->patch, pkp, st))) return rc;
+    if ((rc = launch_patchify(image_b, static_cast<char*>(patches) + static_cast<size_t>(batch_a) * g2 * pkp * e, dt, B - batch_a, w->resolution,
+                              w->patch, pkp, st))) return rc;
+  } else if ((rc = launch_patchify(image, patches, dt, B, w->resolution, w->patch, pkp, st))) return rc;
+  const void* conv1_w = w->conv1_w;
+  if (pkp != pk) {
+    if ((rc = launch_copy_cols(w->conv1_w, pk, conv1_w_pad, pkp, d, pk, static_cast<int>(e), st))) return rc;
+    conv1_w = conv1_w_pad;
+  }
+  return launch_gemm(dt, patches, conv1_w, nullptr, nullptr, patch_out, B * g2, d, pkp, 0, st);
 }
 
 static int check_tower(int dt, int width, int layers, int embed, const cmh_block_weights* blocks) {
@@ -381,50 +380,50 @@ static int vit_begin(const cmh_vit_weights* w, const float* image, int32_t batch
   TowerBufs& t = r.t;
   t = carve(workspace, static_cast<size_t>(M), B, d, e, static_cast<size_t>(B) * g2 * d * 4, static_cast<size_t>(B) * g2 * pkp * e,
             pkp != pk ? static_cast<size_t>(d) * pkp * e : 0);
-  t.xh = resid_f16(dtb, d, taps);
-  r.dtb = dtb; r.d = d; r.B = B; r.T = T; r.M = M; r.causal = 0;
-  void* patches = t.mlp;
+  r.dtb = dtb; r.xh = tower_xh(dtb, d, taps); r.d = d; r.B = B; r.T = T; r.M = M; r.causal = 0;
+  lane_in_place(r);
   float* patch_out = static_cast<float*>(t.qkv);
-
-  // conv1 (kernel = stride = patch, no bias) as patch-matrix GEMM  (model.py:215,231-235).  K-padded (conv1_k): the patch rows and
-  // a copy of the weight carry zero columns pk..pkp-1, which add exact zeros - the K = pk product in the same k order.
-  if (image_b) {
-    CMH_CHECK_ARG(batch_a > 0 && batch_a < B, "vit_encode: split batch %d of %d", batch_a, B);
-    if ((rc = launch_patchify(image, patches, dt, batch_a, w->resolution, w->patch, pkp, st))) return rc;
-    if ((rc = launch_patchify(image_b, static_cast<char*>(patches) + static_cast<size_t>(batch_a) * g2 * pkp * e, dt, B - batch_a, w->resolution,
-                              w->patch, pkp, st))) return rc;
-  } else if ((rc = launch_patchify(image, patches, dt, B, w->resolution, w->patch, pkp, st))) return rc;
-  const void* conv1_w = w->conv1_w;
-  if (pkp != pk) {
-    if ((rc = launch_copy_cols(w->conv1_w, pk, t.conv1_w, pkp, d, pk, static_cast<int>(e), st))) return rc;
-    conv1_w = t.conv1_w;
-  }
-  if ((rc = launch_gemm(dt, patches, conv1_w, nullptr, nullptr, patch_out, B * g2, d, pkp, 0, st))) return rc;
+  if ((rc = conv1_stem(w, dt, image, image_b, batch_a, B, /*patches=*/t.mlp, t.conv1_w, patch_out, st))) return rc;
   // [class ; patches] + positional, ln_pre  (:237-239)
   if ((rc = launch_vit_assemble_lnpre(patch_out, w->class_embedding, w->positional_embedding, w->ln_pre_w,
-                                      w->ln_pre_b, t.x, t.xh, B, g2, d, st))) return rc;
+                                      w->ln_pre_b, t.x, r.xh, B, g2, d, st))) return rc;
   return tap(taps, 0, t.x, static_cast<size_t>(M) * d * 4, st);
 }
 
 // ln_post (+ proj) after the last block: on every token (MITH trunk) and / or on the class token
-static int vit_finish(const cmh_vit_weights* w, const TowerRun& r, void* x_pooled, float* feat, float* tokens_out, hipStream_t st) {
+static int vit_finish(const cmh_vit_weights* w, const TowerRun& r, float* feat, float* tokens_out, hipStream_t st) {
   const TowerBufs& t = r.t;
+  const void* x_pooled = r.pooled ? r.x_out : nullptr;      // the last block ran its tail on the pooled rows
   const int dt = r.dtb == CMH_FP8 ? CMH_BF16 : r.dtb, d = r.d, B = r.B, T = r.T, M = r.M;
   int rc;
   if (tokens_out) {
     // MITH trunk (model/MITH.py:70-80): ln_post and proj on EVERY token
-    if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w->ln_post_w, w->ln_post_b, t.h, dt == CMH_BF16, M, d, st))) return rc;
+    if ((rc = launch_layernorm_x(t.x, r.xh, nullptr, w->ln_post_w, w->ln_post_b, t.h, dt == CMH_BF16, M, d, st))) return rc;
     if ((rc = final_projection(dt, t.h, w->proj_t, tokens_out, M, w->embed_dim, d, st))) return rc;
   }
   if (feat) {
     // ln_post on the class token, @ proj  (:247-250)
     if (x_pooled) {
-      if ((rc = launch_layernorm_x(x_pooled, t.xh, nullptr, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
+      if ((rc = launch_layernorm_x(x_pooled, r.xh, nullptr, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
     } else {
       if ((rc = launch_iota_rows(t.rows, B, T, st))) return rc;
-      if ((rc = launch_layernorm_x(t.x, t.xh, t.rows, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
+      if ((rc = launch_layernorm_x(t.x, r.xh, t.rows, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
     }
     if ((rc = final_projection(dt, t.pool, w->proj_t, feat, B, w->embed_dim, d, st))) return rc;
+  }
+  return CMH_OK;
+}
+
+// every block of one tower, in place; pool_last: the last block's tail runs on the pooled rows only
+static int run_tower(TowerRun& r, const cmh_block_weights* blocks, int layers, bool pool_last, float* amax, const cmh_taps* taps,
+                     hipStream_t st) {
+  int rc;
+  for (int i = 0; i < layers; ++i) {
+    r.w = &blocks[i];
+    r.amax = amax ? amax + 4 * i : nullptr;
+    if (pool_last && i == layers - 1) pool_the_tail(r);
+    if ((rc = block_forward(r, nullptr, st))) return rc;
+    if ((rc = tap(taps, 1 + i, r.t.x, static_cast<size_t>(r.B) * r.T * r.d * 4, st))) return rc;
   }
   return CMH_OK;
 }
@@ -435,20 +434,10 @@ static int vit_encode_impl(const cmh_vit_weights* w, const float* image, int32_t
   TowerRun r;
   int rc = vit_begin(w, image, batch, feat || tokens_out, workspace, workspace_bytes, taps, st, amax, r);
   if (rc) return rc;
-  const TowerBufs& t = r.t;
-  const int dtb = r.dtb, d = r.d, B = r.B, T = r.T, M = r.M;
   const bool tail = feat && !tokens_out && !taps && !amax && w->layers > 0 && pooled_tail_enabled();
-  void* x_pooled = nullptr;
-  if (tail && (rc = launch_iota_rows(t.rows, B, T, st))) return rc;
-  for (int i = 0; i < w->layers; ++i) {
-    if (tail && i == w->layers - 1) {
-      if ((rc = run_block_pooled(w->blocks[i], dtb, t, B, T, d, /*causal=*/0, nullptr, st, M, nullptr, &x_pooled))) return rc;
-      break;
-    }
-    if ((rc = run_block(w->blocks[i], dtb, t, B, T, d, /*causal=*/0, nullptr, st, -1, nullptr, amax ? amax + 4 * i : nullptr))) return rc;
-    if ((rc = tap(taps, 1 + i, t.x, static_cast<size_t>(M) * d * 4, st))) return rc;
-  }
-  return vit_finish(w, r, x_pooled, feat, tokens_out, st);
+  if (tail && (rc = launch_iota_rows(r.t.rows, r.B, r.T, st))) return rc;
+  if ((rc = run_tower(r, w->blocks, w->layers, tail, amax, taps, st))) return rc;
+  return vit_finish(w, r, feat, tokens_out, st);
 }
 
 extern "C" int cmh_vit_encode(const cmh_vit_weights* w, const float* image, int32_t batch, float* feat,
@@ -472,7 +461,7 @@ extern "C" size_t cmh_text_workspace_bytes(const cmh_text_weights* w, int32_t ba
 // validation + everything before the first block: the pack plan (packed mode), token + positional embedding, the EOT rows
 static int text_begin(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len, const uint8_t* key_padding_mask,
                       bool want_out, bool tokens_wanted, void* workspace, size_t workspace_bytes, const cmh_taps* taps, hipStream_t st,
-                      int32_t* packed_rows_out, float* amax, TowerRun& r, bool pack_tokens_req = false) {
+                      bool packed, int32_t* rows_out, float* amax, TowerRun& r, bool pack_tokens_req = false) {   // rows_out: optional
   CMH_CHECK_ARG(w && tokens && want_out && workspace, "text_encode: null pointer");
   CMH_CHECK_ARG(batch > 0 && seq_len > 0, "text_encode: batch %d seq_len %d", batch, seq_len);
   int rc = check_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
@@ -487,7 +476,8 @@ static int text_begin(const cmh_text_weights* w, const int64_t* tokens, int32_t 
   CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "text_encode: workspace must be 256-byte aligned");
   TowerBufs& t = r.t;
   t = carve(workspace, static_cast<size_t>(M), B, d, e, 0, 0);
-  t.xh = resid_f16(dtb, d, taps);
+  r.xh = tower_xh(dtb, d, taps);
+  lane_in_place(r);
 
   // Packed mode (pooled output only): under the causal mask nothing after a caption's EOT can reach the EOT row that
   // encode_text returns (model.py:366-370), so only the tokens 0..EOT of every caption are embedded and run through the
@@ -502,12 +492,11 @@ static int text_begin(const cmh_text_weights* w, const int64_t* tokens, int32_t 
   // position, the projected tokens go back to their dense [B, L, E] places with zeros behind (text_finish).  Kept rows see the dense
   // path's arithmetic (the mask is still applied to the keys inside the kept prefix): same bits there.
   // (asked for per call - cmh_text_encode_tokens_packed: the caller promises not to read the padded positions - and only then)
-  const bool pack_tokens = pack_tokens_req && tokens_wanted && key_padding_mask && !packed_rows_out && !taps && !amax && text_token_packing() &&
+  const bool pack_tokens = pack_tokens_req && tokens_wanted && key_padding_mask && !packed && !taps && !amax && text_token_packing() &&
                            w->embed_dim % 128 == 0 && d % (dt == CMH_F32 ? 32 : 64) == 0 &&      // the packed projection is a GEMM launch
                            static_cast<size_t>(w->embed_dim) * 4 <= static_cast<size_t>(4) * d * e;   // ... into the MLP scratch
-  if (pack_tokens) packed_rows_out = reinterpret_cast<int32_t*>(1);
   r.packed_tokens = pack_tokens;
-  if (packed_rows_out) {
+  if (packed || pack_tokens) {
     CMH_CHECK_ARG(pack_tokens || (!key_padding_mask && !tokens_wanted && !taps), "text_encode_packed: pooled features only, no mask / taps");
     if ((rc = launch_text_pack_plan(tokens, B, L, t.seq, st, pack_tokens ? key_padding_mask : nullptr, pack_tokens ? t.rows : nullptr))) return rc;
     seq_off = t.seq;
@@ -526,32 +515,31 @@ static int text_begin(const cmh_text_weights* w, const int64_t* tokens, int32_t 
       md = t.seq + B;
       mh = rows_hint_exchange(t.seq + B, B, L, st);
     }
-    if (packed_rows_out != reinterpret_cast<int32_t*>(1) &&
-        hipMemcpyAsync(packed_rows_out, t.seq + B, 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if (packed && rows_out && hipMemcpyAsync(rows_out, t.seq + B, 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "text_encode_packed: copying the row count failed");
   }
 
   // token_embedding gather + positional_embedding[:L]; EOT row = argmax(tokens)  (model.py:360-362,370)
-  r.dtb = dtb; r.d = d; r.B = B; r.T = L; r.M = rows; r.causal = 1; r.seq_off = seq_off; r.md = md; r.mh = mh;
-  return launch_text_embed_packed(tokens, w->token_embedding, w->positional_embedding, t.x, t.xh, t.rows, B, L, d, w->vocab_size, seq_off, st,
+  r.dtb = dtb; r.d = d; r.B = B; r.T = L; r.M = rows; r.causal = 1; r.kpm = key_padding_mask; r.seq_off = seq_off; r.md = md; r.mh = mh;
+  return launch_text_embed_packed(tokens, w->token_embedding, w->positional_embedding, t.x, r.xh, t.rows, B, L, d, w->vocab_size, seq_off, st,
                                   pack_tokens);
 }
 
 // ln_final (+ text_projection) after the last block: on every token (MITH trunk) and / or on the EOT rows
-static int text_finish(const cmh_text_weights* w, const TowerRun& r, void* x_pooled, float* feat, float* tokens_out, int32_t* eot_rows_out,
-                       hipStream_t st) {
+static int text_finish(const cmh_text_weights* w, const TowerRun& r, float* feat, float* tokens_out, int32_t* eot_rows_out, hipStream_t st) {
   const TowerBufs& t = r.t;
+  const void* x_pooled = r.pooled ? r.x_out : nullptr;      // the last block ran its tail on the pooled rows
   const int dt = r.dtb == CMH_FP8 ? CMH_BF16 : r.dtb, d = r.d, B = r.B, M = r.B * r.T;
   int rc;
   if (tokens_out && r.packed_tokens) {
     // the kept rows only (device row count), then back to their dense places; the EOT rows leave as dense indices with them
     float* tmp = static_cast<float*>(t.mlp);      // [rows, E] f32: the MLP scratch is free behind the last block (text_begin checked the sizes)
-    if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w->ln_final_w, w->ln_final_b, t.h, dt == CMH_BF16, r.M, d, st, r.md))) return rc;
+    if ((rc = launch_layernorm_x(t.x, r.xh, nullptr, w->ln_final_w, w->ln_final_b, t.h, dt == CMH_BF16, r.M, d, st, r.md))) return rc;
     if ((rc = launch_gemm(dt, t.h, w->text_projection_t, nullptr, nullptr, tmp, r.M, w->embed_dim, d, 0, st, r.md, r.mh))) return rc;
     if ((rc = launch_unpack_token_rows(tmp, r.seq_off, tokens_out, B, r.T, w->embed_dim, t.rows, eot_rows_out, st))) return rc;
   } else if (tokens_out) {
     // MITH trunk (model/MITH.py:136-139): ln_final and text_projection on EVERY token
-    if ((rc = launch_layernorm_x(t.x, t.xh, nullptr, w->ln_final_w, w->ln_final_b, t.h, dt == CMH_BF16, M, d, st))) return rc;
+    if ((rc = launch_layernorm_x(t.x, r.xh, nullptr, w->ln_final_w, w->ln_final_b, t.h, dt == CMH_BF16, M, d, st))) return rc;
     if ((rc = final_projection(dt, t.h, w->text_projection_t, tokens_out, M, w->embed_dim, d, st))) return rc;
   }
   if (eot_rows_out && !(tokens_out && r.packed_tokens) &&
@@ -559,7 +547,7 @@ static int text_finish(const cmh_text_weights* w, const TowerRun& r, void* x_poo
     return fail(CMH_ERR_LAUNCH, "text_encode: eot row copy failed");
   if (feat) {
     // ln_final (row-wise, so only the pooled rows are normalised), @ text_projection  (:366-370)
-    if ((rc = launch_layernorm_x(x_pooled ? x_pooled : t.x, t.xh, x_pooled ? nullptr : t.rows, w->ln_final_w, w->ln_final_b, t.pool,
+    if ((rc = launch_layernorm_x(x_pooled ? x_pooled : t.x, r.xh, x_pooled ? nullptr : t.rows, w->ln_final_w, w->ln_final_b, t.pool,
                                  dt == CMH_BF16, B, d, st))) return rc;
     if ((rc = final_projection(dt, t.pool, w->text_projection_t, feat, B, w->embed_dim, d, st))) return rc;
   }
@@ -569,27 +557,15 @@ static int text_finish(const cmh_text_weights* w, const TowerRun& r, void* x_poo
 static int text_encode_impl(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
                             const uint8_t* key_padding_mask, float* feat, float* tokens_out, int32_t* eot_rows_out,
                             void* workspace, size_t workspace_bytes, const cmh_taps* taps, void* stream,
-                            int32_t* packed_rows_out = nullptr, float* amax = nullptr, bool pack_tokens_req = false) {
+                            bool packed = false, int32_t* rows_out = nullptr, float* amax = nullptr, bool pack_tokens_req = false) {
   hipStream_t st = as_stream(stream);
   TowerRun r;
   int rc = text_begin(w, tokens, batch, seq_len, key_padding_mask, feat || tokens_out, tokens_out != nullptr, workspace, workspace_bytes,
-                      taps, st, packed_rows_out, amax, r, pack_tokens_req);
+                      taps, st, packed, rows_out, amax, r, pack_tokens_req);
   if (rc) return rc;
-  const TowerBufs& t = r.t;
-  const int dtb = r.dtb, d = r.d, B = r.B, L = r.T, M = B * L, rows = r.M, mh = r.mh;
-  const int32_t* seq_off = r.seq_off;
-  const int32_t* md = r.md;
   const bool tail = feat && !tokens_out && !taps && !amax && !eot_rows_out && w->layers > 0 && pooled_tail_enabled();
-  void* x_pooled = nullptr;
-  for (int i = 0; i < w->layers; ++i) {
-    if (tail && i == w->layers - 1) {
-      if ((rc = run_block_pooled(w->blocks[i], dtb, t, B, L, d, /*causal=*/1, key_padding_mask, st, rows, seq_off, &x_pooled, md, mh))) return rc;
-      break;
-    }
-    if ((rc = run_block(w->blocks[i], dtb, t, B, L, d, /*causal=*/1, key_padding_mask, st, rows, seq_off, amax ? amax + 4 * i : nullptr, md, mh))) return rc;
-    if ((rc = tap(taps, 1 + i, t.x, static_cast<size_t>(M) * d * 4, st))) return rc;
-  }
-  return text_finish(w, r, x_pooled, feat, tokens_out, eot_rows_out, st);
+  if ((rc = run_tower(r, w->blocks, w->layers, tail, amax, taps, st))) return rc;
+  return text_finish(w, r, feat, tokens_out, eot_rows_out, st);
 }
 
 extern "C" int cmh_text_encode(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
@@ -604,11 +580,11 @@ extern "C" int cmh_text_encode_packed(const cmh_text_weights* w, const int64_t* 
                                       int32_t* rows_computed_dev, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(feat, "text_encode_packed: null pointer");
   return text_encode_impl(w, tokens, batch, seq_len, nullptr, feat, nullptr, nullptr, workspace, workspace_bytes, nullptr, stream,
-                          rows_computed_dev ? rows_computed_dev : reinterpret_cast<int32_t*>(1));   // 1: packed, count not wanted
+                          /*packed=*/true, rows_computed_dev);
 }
 
 // encode_image + encode_text of one batch with the two towers in lock-step (reference model/modelbase.py:105-108 runs them back to
-// back; model/base/model.py:340-372): layer i of both towers shares its launches (run_block_pair).  Same features, bit for bit, as
+// back; model/base/model.py:340-372): layer i of both towers shares its launches (block_forward on two lanes).  Same features, bit for bit, as
 // cmh_vit_encode + cmh_text_encode[_packed].
 static int clip_encode_pair_impl(const cmh_vit_weights* vw, const float* image, const float* image_b, int32_t batch_a,
                                  const cmh_text_weights* tw, const int64_t* tokens,
@@ -622,36 +598,29 @@ static int clip_encode_pair_impl(const cmh_vit_weights* vw, const float* image, 
   TowerRun a, b;
   int rc;
   if ((rc = vit_begin(vw, image, batch, true, ws_image, ws_image_bytes, nullptr, st, nullptr, a, image_b, batch_a))) return rc;
-  if ((rc = text_begin(tw, tokens, batch, seq_len, nullptr, true, false, ws_text, ws_text_bytes, nullptr, st,
-                       packed ? (rows_computed_dev ? rows_computed_dev : reinterpret_cast<int32_t*>(1)) : nullptr, nullptr, b))) return rc;
+  if ((rc = text_begin(tw, tokens, batch, seq_len, nullptr, true, false, ws_text, ws_text_bytes, nullptr, st, packed != 0, rows_computed_dev,
+                       nullptr, b))) return rc;
   const bool tail = pooled_tail_enabled();
-  void *xa = nullptr, *xb = nullptr;
   if (tail && vw->layers > 0 && (rc = launch_iota_rows(a.t.rows, a.B, a.T, st))) return rc;
   const int deepest = vw->layers > tw->layers ? vw->layers : tw->layers;
   for (int i = 0; i < deepest; ++i) {
     const bool has_a = i < vw->layers, has_b = i < tw->layers;
     const bool last_a = tail && i == vw->layers - 1, last_b = tail && i == tw->layers - 1;
+    if (has_a) a.w = &vw->blocks[i];
+    if (has_b) b.w = &tw->blocks[i];
+    if (last_a) pool_the_tail(a);
+    if (last_b) pool_the_tail(b);
     // lock-step only when both towers carry the same kind of residual stream (fp16 for widths that are multiples of 256 in the bf16
     // mode, else f32: resid_f16 decides per tower): a grouped launch has ONE set of epilogue flags
-    if (has_a && has_b && last_a == last_b && a.t.xh == b.t.xh) {
-      if ((rc = run_block_pair(vw->blocks[i], tw->blocks[i], a, b, st, last_a))) return rc;
-      if (last_a) {       // the rest of the last block on the pooled rows of each tower (few-row kernels)
-        if ((rc = run_block_pooled(vw->blocks[i], a.dtb, a.t, a.B, a.T, a.d, 0, nullptr, st, a.M, nullptr, &xa, nullptr, -1, true))) return rc;
-        if ((rc = run_block_pooled(tw->blocks[i], b.dtb, b.t, b.B, b.T, b.d, 1, nullptr, st, b.M, b.seq_off, &xb, b.md, b.mh, true))) return rc;
-      }
+    if (has_a && has_b && last_a == last_b && a.xh == b.xh) {
+      if ((rc = block_forward(a, &b, st))) return rc;
       continue;
     }
-    if (has_a) {
-      if (last_a) { if ((rc = run_block_pooled(vw->blocks[i], a.dtb, a.t, a.B, a.T, a.d, 0, nullptr, st, a.M, nullptr, &xa))) return rc; }
-      else if ((rc = run_block(vw->blocks[i], a.dtb, a.t, a.B, a.T, a.d, 0, nullptr, st))) return rc;
-    }
-    if (has_b) {
-      if (last_b) { if ((rc = run_block_pooled(tw->blocks[i], b.dtb, b.t, b.B, b.T, b.d, 1, nullptr, st, b.M, b.seq_off, &xb, b.md, b.mh))) return rc; }
-      else if ((rc = run_block(tw->blocks[i], b.dtb, b.t, b.B, b.T, b.d, 1, nullptr, st, b.M, b.seq_off, nullptr, b.md, b.mh))) return rc;
-    }
+    if (has_a && (rc = block_forward(a, nullptr, st))) return rc;
+    if (has_b && (rc = block_forward(b, nullptr, st))) return rc;
   }
-  if ((rc = vit_finish(vw, a, xa, feat_image, nullptr, st))) return rc;
-  return text_finish(tw, b, xb, feat_text, nullptr, nullptr, st);
+  if ((rc = vit_finish(vw, a, feat_image, nullptr, st))) return rc;
+  return text_finish(tw, b, feat_text, nullptr, nullptr, st);
 }
 
 extern "C" int cmh_clip_encode_pair(const cmh_vit_weights* vw, const float* image, const cmh_text_weights* tw, const int64_t* tokens,
@@ -696,7 +665,7 @@ extern "C" int cmh_text_calibrate_fp8(const cmh_text_weights* w, const int64_t* 
   CMH_CHECK_ARG(feat && amax, "text_calibrate_fp8: null pointer");
   // the packed path: calibrate on the rows the fp8 mode will compute
   return text_encode_impl(w, tokens, batch, seq_len, nullptr, feat, nullptr, nullptr, workspace, workspace_bytes, nullptr, stream,
-                          reinterpret_cast<int32_t*>(1), amax);
+                          /*packed=*/true, nullptr, amax);
 }
 
 extern "C" int cmh_text_encode_tokens(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
@@ -714,7 +683,7 @@ extern "C" int cmh_text_encode_tokens_packed(const cmh_text_weights* w, const in
                                              void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(tokens_out, "text_encode_tokens_packed: null pointer");
   return text_encode_impl(w, tokens, batch, seq_len, key_padding_mask, nullptr, tokens_out, eot_rows_out, workspace,
-                          workspace_bytes, nullptr, stream, nullptr, nullptr, /*pack_tokens_req=*/true);
+                          workspace_bytes, nullptr, stream, false, nullptr, nullptr, /*pack_tokens_req=*/true);
 }
 
 // A stack of ResidualAttentionBlocks on a caller-owned f32 residual stream x [B*T, d] (in place): the 2-layer
@@ -734,11 +703,13 @@ extern "C" int cmh_transformer_blocks(const cmh_block_weights* blocks, int32_t l
   if (workspace_bytes < cmh_blocks_workspace_bytes(dtype, B, T, d)) return fail(CMH_ERR_WORKSPACE, "transformer_blocks: workspace too small");
   hipStream_t st = as_stream(stream);
   const size_t M = static_cast<size_t>(B) * T;
-  TowerBufs t = carve(workspace, M, B, d, dtype == CMH_BF16 ? 2 : 4, 0, 0);
-  if (hipMemcpyAsync(t.x, x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "transformer_blocks: copy failed");
-  for (int i = 0; i < layers; ++i)
-    if ((rc = run_block(blocks[i], dtype, t, B, T, d, causal, key_padding_mask, st))) return rc;
-  if (hipMemcpyAsync(x, t.x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "transformer_blocks: copy failed");
+  TowerRun r;
+  r.t = carve(workspace, M, B, d, dtype == CMH_BF16 ? 2 : 4, 0, 0);
+  r.dtb = dtype; r.d = d; r.B = B; r.T = T; r.M = B * T; r.causal = causal; r.kpm = key_padding_mask;
+  lane_in_place(r);
+  if (hipMemcpyAsync(r.t.x, x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "transformer_blocks: copy failed");
+  if ((rc = run_tower(r, blocks, layers, false, nullptr, nullptr, st))) return rc;
+  if (hipMemcpyAsync(x, r.t.x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "transformer_blocks: copy failed");
   return CMH_OK;
 }
 

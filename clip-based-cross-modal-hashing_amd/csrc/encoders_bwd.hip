@@ -1,9 +1,9 @@
 // Training forward (keeps a tape) and backward of the two CLIP towers (SURVEY §8f "next" #2): kernel sequencing only.
 //
-// Forward with a tape = the forward of encoders.hip with three differences: every block reads its input x_in and writes
-// x_mid / the next block's x_in to fresh tape buffers instead of updating one stream in place (the residual GEMMs already
-// take residual and output separately); c_fc stores the PRE-activation and QuickGELU runs as its own pass; LayerNorm and
-// attention outputs are kept.  Per block the tape holds x_in, h1 = ln_1(x_in), qkv, attn, x_mid, h2 = ln_2(x_mid), pre:
+// Forward with a tape = the forward of encoders.hip (the same block_forward, on lanes that point into the tape: tape_forward) with
+// three differences: every block reads its input x_in and writes x_mid / the next block's x_in to fresh tape buffers instead of
+// updating one stream in place (the residual GEMMs already take residual and output separately); c_fc also stores the
+// PRE-activation (from its epilogue, or with QuickGELU as a pass of its own); LayerNorm and attention outputs are kept.  Per block the tape holds x_in, h1 = ln_1(x_in), qkv, attn, x_mid, h2 = ln_2(x_mid), pre:
 // M*(2*xs*d + 10*e*d) bytes (xs = residual element size, e = GEMM element size): 236 MB per vision block at batch 256, bf16.
 //
 // Backward of one block, given dx = dL/dx_out (f32 gradient stream, updated in place to dL/dx_in).  With Y = X W^T + b:
@@ -24,22 +24,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "cmh_common.h"
+#include "encoder_blocks.h"
 
 namespace cmh {
 
 namespace {
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
-  template <typename T = void> T* take(size_t bytes) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  }
-};
 
 struct LayerTape { void *x_in, *h1, *qkv, *attn, *x_mid, *h2, *pre, *act; };   // act = QuickGELU(pre): c_proj's operand, kept for its wgrad
 
@@ -81,7 +70,7 @@ size_t pad64(size_t m) { return (m + 63) / 64 * 64; }
 // pk: conv1's patch-matrix K (conv1_k); conv1_padded: pk is the padded K, so the padded weight and its gradient get buffers too
 TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t xs, int layers, size_t g2rows, size_t pk,
                       size_t embed, bool conv1_padded = false) {
-  Carver a(ws);
+  Arena a(ws);
   TrainBufs t;
   t.L.resize(layers);
   for (int i = 0; i < layers; ++i) {
@@ -136,7 +125,7 @@ TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t x
   return t;
 }
 
-// the last block's row-wise tail on the pooled rows only (block_forward_train / block_backward): the rule both calls of a step apply,
+// the last block's row-wise tail on the pooled rows only (tape_forward / block_backward): the rule both calls of a step apply,
 // so cmh_set_pooled_tail must not change between a tape's forward and its backward; CMH_TRAIN_POOLED_TAIL=0 keeps the training
 // towers on the full-size path
 bool train_pooled_tail() {
@@ -145,12 +134,6 @@ bool train_pooled_tail() {
 }
 int xkind(int xh) { return xh ? kF16 : kF32; }
 int ekind(int dt) { return dt == CMH_BF16 ? kBF16 : kF32; }
-
-// training runs keep the fp16 residual stream rule of the inference path (bf16 mode, width % 256 == 0, CMH_RESID_F16 != 0)
-int train_xh(int dt, int d) {
-  static const bool off = []() { const char* e = getenv("CMH_RESID_F16"); return e && !strcmp(e, "0"); }();
-  return dt == CMH_BF16 && d % 256 == 0 && !off;
-}
 
 // x [M,d] f32 -> GEMM dtype copy (bf16 mode) or the same pointer (f32 mode)
 int as_gemm_operand(int dt, const float* x, void* scratch, size_t n, hipStream_t st, const void** out) {
@@ -161,42 +144,30 @@ int as_gemm_operand(int dt, const float* x, void* scratch, size_t n, hipStream_t
 
 struct BlockGradPtrs { float *in_w, *in_b, *out_w, *out_b, *ln1_w, *ln1_b, *ln2_w, *ln2_b, *fc_w, *fc_b, *proj_w, *proj_b; };
 
-// pooled_rows (the LAST block of a tower whose only output is the pooled feature, like encoders.hip::run_block_pooled): after the
-// attention the block's row-wise tail - out_proj, ln_2, the MLP - runs on the B pooled rows only.  The tape slots then hold B-row
-// matrices: x_mid, h2, pre, act rows [0, B); the pooled attention rows (out_proj's wgrad operand) sit in h2 rows [B, 2B); x_next
-// receives B rows.  block_backward(..., pooled_rows) reads them back the same way.
-int block_forward_train(const cmh_block_weights& w, int dt, int xh, const LayerTape& L, void* x_next, int B, int T,
-                        int d, int causal, const uint8_t* kpm, hipStream_t st, int rows = -1, const int32_t* seq_off = nullptr,
-                        const int32_t* pooled_rows = nullptr) {
-  const int M = rows >= 0 ? rows : B * T;
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  const int rx = EPI_BIAS | EPI_RESIDUAL | (xh ? EPI_RES_F16 | EPI_OUT_F16 : 0);
-  const size_t esz = dt == CMH_BF16 ? 2 : 4, xsz = xh ? 2 : 4;
-  int rc;
-  if ((rc = launch_layernorm_x(L.x_in, xh, nullptr, w.ln1_w, w.ln1_b, L.h1, dt == CMH_BF16, M, d, st))) return rc;
-  if ((rc = launch_gemm(dt, L.h1, w.in_proj_w, w.in_proj_b, nullptr, L.qkv, M, 3 * d, d, EPI_BIAS | obf, st))) return rc;
-  if ((rc = launch_attention_varlen(L.qkv, L.attn, dt, B, T, d, causal, kpm, seq_off, st))) return rc;
-  const void* attn = L.attn;
-  if (pooled_rows) {
-    void* attn_p = static_cast<char*>(L.h2) + static_cast<size_t>(B) * d * esz;
-    if ((rc = launch_gather_rows2(L.x_in, L.x_mid, static_cast<int>(d * xsz), L.attn, attn_p, static_cast<int>(d * esz), pooled_rows, B, st))) return rc;
-    attn = attn_p;
+// Every block of a tower with its tape: block i reads t.L[i].x_in and writes the next block's x_in (the last one t.x_last); `base`
+// holds what the layers share.  pooled_rows (the LAST block of a tower whose only output is the pooled feature, like the inference
+// towers' pooled tail): after the attention the block's row-wise tail - out_proj, ln_2, the MLP - runs on the B pooled rows only.  The
+// tape slots then hold B-row matrices: x_mid, h2, pre, act rows [0, B); the pooled attention rows (out_proj's wgrad operand) sit in h2
+// rows [B, 2B); x_last receives B rows.  block_backward(..., pooled_rows) reads them back the same way.
+int tape_forward(Lane base, const cmh_block_weights* blocks, int layers, const TrainBufs& t, const int32_t* pooled_rows, hipStream_t st) {
+  for (int i = 0; i < layers; ++i) {
+    const LayerTape& L = t.L[i];
+    Lane l = base;
+    l.w = &blocks[i];
+    l.x_in = L.x_in; l.h1 = L.h1; l.qkv = L.qkv; l.attn = L.attn; l.x_mid = L.x_mid; l.h2 = L.h2; l.pre = L.pre; l.act = L.act;
+    l.x_out = i + 1 < layers ? t.L[i + 1].x_in : t.x_last;
+    if (pooled_rows && i == layers - 1) {
+      l.pooled = pooled_rows;
+      l.attn_p = static_cast<char*>(L.h2) + static_cast<size_t>(l.B) * l.d * (l.dtb == CMH_BF16 ? 2 : 4);
+    }
+    if (int rc = block_forward(l, nullptr, st)) return rc;
   }
-  const int Mt = pooled_rows ? B : M;
-  const void* resid = pooled_rows ? L.x_mid : L.x_in;          // pooled: the gathered residual rows are updated in place
-  if ((rc = launch_gemm(dt, attn, w.out_proj_w, w.out_proj_b, static_cast<const float*>(resid), L.x_mid, Mt, d, d, rx, st))) return rc;
-  if ((rc = launch_layernorm_x(L.x_mid, xh, nullptr, w.ln2_w, w.ln2_b, L.h2, dt == CMH_BF16, Mt, d, st))) return rc;
-  static const bool fuse_act = []() { const char* e = getenv("CMH_FUSE_PRE"); return !(e && e[0] == '0'); }();
-  if (dt == CMH_BF16 && (4 * d) % 256 == 0 && fuse_act) {   // the N % 256 == 0 GEMM kernel has the epilogue
-    // one launch: the activation from the f32 accumulator into L.act, the bf16 pre-activation into L.pre (EPI_SAVE_PRE)
-    if ((rc = launch_gemm(dt, L.h2, w.fc_w, w.fc_b, static_cast<const float*>(L.pre), L.act, Mt, 4 * d, d,
-                          EPI_BIAS | EPI_QUICKGELU | EPI_SAVE_PRE | obf, st))) return rc;
-  } else {
-    if ((rc = launch_gemm(dt, L.h2, w.fc_w, w.fc_b, nullptr, L.pre, Mt, 4 * d, d, EPI_BIAS | obf, st))) return rc;
-    if ((rc = cmh_quick_gelu(L.pre, L.act, static_cast<int64_t>(Mt) * 4 * d, ekind(dt), st))) return rc;
-  }
-  if ((rc = launch_gemm(dt, L.act, w.proj_w, w.proj_b, static_cast<const float*>(L.x_mid), x_next, Mt, d, 4 * d, rx, st))) return rc;
   return CMH_OK;
+}
+Lane train_lane(int dt, int xh, int B, int T, int d, int causal, const uint8_t* kpm, int rows, const int32_t* seq_off) {
+  Lane l;
+  l.dtb = dt; l.xh = xh; l.B = B; l.T = T; l.d = d; l.causal = causal; l.kpm = kpm; l.M = rows; l.seq_off = seq_off;
+  return l;
 }
 
 // dW[O, I] = dY^T X with dY [M, O] (kind ky) and X [M, I] (kind kx); db[O] = column sums of dY
@@ -263,7 +234,7 @@ bool grad_stream16_enabled() {
   return g_grad_stream16 < 0 ? env_on : g_grad_stream16 != 0;
 }
 
-// pooled_rows / dxp (the last block after block_forward_train(..., pooled_rows)): the incoming gradient is dxp [B, d] f32 on the
+// pooled_rows / dxp (the last block after tape_forward(..., pooled_rows)): the incoming gradient is dxp [B, d] f32 on the
 // pooled rows; steps 1-4 run on those B rows, then the two gradients that go on - d(attention output) and the residual stream -
 // are scattered into zeroed full-size buffers for the attention backward and ln_1.
 // keep_f32: the caller reads the f32 gradient stream (t.dx) behind this block (the embeddings' backward after block 0; the
@@ -595,9 +566,7 @@ int tokens_head_forward(int dt, int xh, const TrainBufs& t, const float* ln_w, c
                         int M, int d, int E, hipStream_t st) {
   int rc;
   if ((rc = launch_layernorm_x(t.x_last, xh, nullptr, ln_w, ln_b, t.dxe, dt == CMH_BF16, M, d, st))) return rc;
-  const int bk = dt == CMH_F32 ? 32 : 64;
-  if (E % 128 == 0 && d % bk == 0) return launch_gemm(dt, t.dxe, proj_t, nullptr, nullptr, tokens_out, M, E, d, 0, st);
-  return launch_small_linear(dt, t.dxe, proj_t, nullptr, nullptr, 1.f, CMH_ACT_NONE, tokens_out, M, E, d, st);
+  return final_projection(dt, t.dxe, proj_t, tokens_out, M, E, d, st);
 }
 // backward: dproj (reference layout [d, E]) = (dtok^T h)^T, dh = dtok . proj_t, then LayerNorm backward over every row into t.dx
 // (+ its bf16 operand copy in t.dxe).  Scratch: h in t.dxe, dtok operand in t.tokE, dproj^T in t.projT.
@@ -620,7 +589,7 @@ int tokens_head_backward(int dt, int xh, TrainBufs& t, const float* ln_w, const 
 extern "C" size_t cmh_vit_train_bytes(const cmh_vit_weights* w, int32_t batch) {
   if (!w || batch <= 0 || w->patch <= 0) return 0;
   const size_t g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, d = w->width, B = batch;
-  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = train_xh(w->gemm_dtype, w->width) ? 2 : 4;
+  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = resid_f16(w->gemm_dtype, w->width) ? 2 : 4;
   const int pkp = conv1_k(w->patch, w->gemm_dtype);
   return carve_train(nullptr, B * T, B, d, e, xs, w->layers, B * g2, pkp, w->embed_dim, pkp != 3 * w->patch * w->patch).total;
 }
@@ -637,33 +606,21 @@ static int vit_forward_train_impl(const cmh_vit_weights* w, const float* image, 
   const int pkp = conv1_k(w->patch, dt);      // pkp != pk: the K-padded conv1 (encoders.hip: vit_begin)
   if (tape_bytes < cmh_vit_train_bytes(w, batch)) return fail(CMH_ERR_WORKSPACE, "vit_forward_train: tape too small");
   CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "vit_forward_train: tape must be 256-byte aligned");
-  const int xh = train_xh(dt, d);
+  const int xh = resid_f16(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
   TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, w->embed_dim,
                             pkp != pk);
-  if ((rc = launch_patchify(image, t.patches, dt, B, w->resolution, w->patch, pkp, st))) return rc;
-  const void* conv1_w = w->conv1_w;
-  if (pkp != pk) {
-    if ((rc = launch_copy_cols(w->conv1_w, pk, t.conv1_w, pkp, d, pk, static_cast<int>(e), st))) return rc;
-    conv1_w = t.conv1_w;
-  }
-  if ((rc = launch_gemm(dt, t.patches, conv1_w, nullptr, nullptr, t.patch_out, B * g2, d, pkp, 0, st))) return rc;
+  if ((rc = conv1_stem(w, dt, image, nullptr, 0, B, t.patches, t.conv1_w, t.patch_out, st))) return rc;
   // x_pre = [cls ; patches] + positional (kept for ln_pre's backward), x_0 = ln_pre(x_pre)
   if ((rc = launch_vit_assemble(t.patch_out, w->class_embedding, w->positional_embedding, t.x_pre, B, g2, d, st))) return rc;
   if ((rc = launch_layernorm_any(t.x_pre, kF32, nullptr, w->ln_pre_w, w->ln_pre_b, t.L[0].x_in, xkind(xh), M, d, st))) return rc;
   const bool tail = !tokens_out && train_pooled_tail();      // the same rule in vit_backward_impl
   if ((rc = launch_iota_rows(t.rows, B, T, st))) return rc;
-  for (int i = 0; i < w->layers; ++i) {
-    void* nxt = i + 1 < w->layers ? t.L[i + 1].x_in : t.x_last;
-    if ((rc = block_forward_train(w->blocks[i], dt, xh, t.L[i], nxt, B, T, d, 0, nullptr, st, -1, nullptr,
-                                  tail && i == w->layers - 1 ? t.rows : nullptr))) return rc;
-  }
+  if ((rc = tape_forward(train_lane(dt, xh, B, T, d, 0, nullptr, M, nullptr), w->blocks, w->layers, t, tail ? t.rows : nullptr, st))) return rc;
   if (tokens_out) return tokens_head_forward(dt, xh, t, w->ln_post_w, w->ln_post_b, w->proj_t, tokens_out, M, d, w->embed_dim, st);
   if ((rc = launch_layernorm_x(t.x_last, xh, tail ? nullptr : t.rows, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
-  const int bk = dt == CMH_F32 ? 32 : 64;
-  if (w->embed_dim % 128 == 0 && d % bk == 0) return launch_gemm(dt, t.pool, w->proj_t, nullptr, nullptr, feat, B, w->embed_dim, d, 0, st);
-  return launch_small_linear(dt, t.pool, w->proj_t, nullptr, nullptr, 1.f, CMH_ACT_NONE, feat, B, w->embed_dim, d, st);
+  return final_projection(dt, t.pool, w->proj_t, feat, B, w->embed_dim, d, st);
 }
 
 extern "C" int cmh_vit_forward_train(const cmh_vit_weights* w, const float* image, int32_t batch, float* feat, void* tape,
@@ -696,7 +653,7 @@ static int vit_backward_impl(const cmh_vit_weights* w, int32_t batch, const floa
   const int dt = w->gemm_dtype, d = w->width, B = batch, E = w->embed_dim;
   const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T, pk = 3 * w->patch * w->patch;
   const int pkp = conv1_k(w->patch, dt);
-  const int xh = train_xh(dt, d);
+  const int xh = resid_f16(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
   TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, E, pkp != pk);
@@ -784,7 +741,7 @@ int recall_tape_rows(const void* tape) {
 
 extern "C" size_t cmh_text_train_bytes(const cmh_text_weights* w, int32_t batch, int32_t seq_len) {
   if (!w || batch <= 0 || seq_len <= 0) return 0;
-  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = train_xh(w->gemm_dtype, w->width) ? 2 : 4;
+  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = resid_f16(w->gemm_dtype, w->width) ? 2 : 4;
   return carve_train(nullptr, static_cast<size_t>(batch) * seq_len, batch, w->width, e, xs, w->layers, 0, 0, w->embed_dim).total;
 }
 
@@ -798,7 +755,7 @@ static int text_forward_train_impl(const cmh_text_weights* w, const int64_t* tok
   if (tape_bytes < cmh_text_train_bytes(w, batch, seq_len)) return fail(CMH_ERR_WORKSPACE, "text_forward_train: tape too small");
   CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "text_forward_train: tape must be 256-byte aligned");
   const int dt = w->gemm_dtype, d = w->width, B = batch, L = seq_len, M = B * L;
-  const int xh = train_xh(dt, d);
+  const int xh = resid_f16(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
   TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, 0, 0, w->embed_dim);
@@ -824,11 +781,8 @@ static int text_forward_train_impl(const cmh_text_weights* w, const int64_t* tok
                                      w->vocab_size, seq_off, st, pack_tokens))) return rc;
   // (the gathered attention rows are parked behind the first B rows of the h2 slot: the pooled tail needs 2 B rows of tape there)
   const bool tail = !tokens_out && train_pooled_tail() && rows >= 2 * B;      // the same rule in text_backward_impl
-  for (int i = 0; i < w->layers; ++i) {
-    void* nxt = i + 1 < w->layers ? t.L[i + 1].x_in : t.x_last;
-    if ((rc = block_forward_train(w->blocks[i], dt, xh, t.L[i], nxt, B, L, d, 1, key_padding_mask, st, rows, seq_off,
-                                  tail && i == w->layers - 1 ? t.rows : nullptr))) return rc;
-  }
+  if ((rc = tape_forward(train_lane(dt, xh, B, L, d, 1, key_padding_mask, rows, seq_off), w->blocks, w->layers, t, tail ? t.rows : nullptr,
+                         st))) return rc;
   if (tokens_out && pack_tokens) {
     if ((rc = tokens_head_forward(dt, xh, t, w->ln_final_w, w->ln_final_b, w->text_projection_t, t.tokP, rows, d, w->embed_dim, st))) return rc;
     return launch_unpack_token_rows(t.tokP, t.seq_off, tokens_out, B, L, w->embed_dim, t.rows, eot_rows_out, st);
@@ -840,10 +794,7 @@ static int text_forward_train_impl(const cmh_text_weights* w, const int64_t* tok
     return tokens_head_forward(dt, xh, t, w->ln_final_w, w->ln_final_b, w->text_projection_t, tokens_out, M, d, w->embed_dim, st);
   }
   if ((rc = launch_layernorm_x(t.x_last, xh, tail ? nullptr : t.rows, w->ln_final_w, w->ln_final_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
-  const int bk = dt == CMH_F32 ? 32 : 64;
-  if (w->embed_dim % 128 == 0 && d % bk == 0)
-    return launch_gemm(dt, t.pool, w->text_projection_t, nullptr, nullptr, feat, B, w->embed_dim, d, 0, st);
-  return launch_small_linear(dt, t.pool, w->text_projection_t, nullptr, nullptr, 1.f, CMH_ACT_NONE, feat, B, w->embed_dim, d, st);
+  return final_projection(dt, t.pool, w->text_projection_t, feat, B, w->embed_dim, d, st);
 }
 
 extern "C" int cmh_text_forward_train(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
@@ -880,7 +831,7 @@ static int text_backward_impl(const cmh_text_weights* w, const int64_t* tokens, 
   if ((rc = check_block_grads(gr->blocks, w->layers))) return rc;
   if (tape_bytes < cmh_text_train_bytes(w, batch, seq_len)) return fail(CMH_ERR_WORKSPACE, "text_backward: tape too small");
   const int dt = w->gemm_dtype, d = w->width, B = batch, L = seq_len, M = B * L, E = w->embed_dim;
-  const int xh = train_xh(dt, d);
+  const int xh = resid_f16(dt, d);
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   hipStream_t st = as_stream(stream);
   TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, 0, 0, E);
@@ -983,10 +934,7 @@ extern "C" int cmh_blocks_forward_train(const cmh_block_weights* blocks, int32_t
   hipStream_t st = as_stream(stream);
   TrainBufs t = carve_train(tape, M, B, d, e, 4, layers, 0, 0, 4);
   if (hipMemcpyAsync(t.L[0].x_in, x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
-  for (int i = 0; i < layers; ++i) {
-    void* nxt = i + 1 < layers ? t.L[i + 1].x_in : t.x_last;
-    if ((rc = block_forward_train(blocks[i], dtype, /*xh=*/0, t.L[i], nxt, B, T, d, 0, nullptr, st))) return rc;
-  }
+  if ((rc = tape_forward(train_lane(dtype, /*xh=*/0, B, T, d, 0, nullptr, B * T, nullptr), blocks, layers, t, nullptr, st))) return rc;
   if (hipMemcpyAsync(y, t.x_last, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
   return CMH_OK;
 }

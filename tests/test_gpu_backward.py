@@ -205,7 +205,7 @@ def test_tower_gradients_match_reference_autograd(golden):
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
 def test_pooled_tail_of_the_training_towers_matches_the_full_path(mode):
     """The training forward / backward carry only the pooled rows through the last block's row-wise tail
-    (csrc/encoders_bwd.hip: block_forward_train / block_backward with pooled_rows).  Against the full-size path
+    (csrc/encoders_bwd.hip: tape_forward / block_backward with pooled_rows).  Against the full-size path
     (cmh_set_pooled_tail(0)): identical features, every parameter gradient equal up to the summation order of the weight
     gradients (B rows instead of B*T rows of which all but B are zero).  Ragged captions: the text tower is packed."""
     import sys, os

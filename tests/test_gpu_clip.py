@@ -155,7 +155,7 @@ def test_packed_text_encode_is_bit_identical(mode):
 @pytest.mark.parametrize("mode", ["f32", "bf16", "fp8"])
 def test_pooled_rows_through_the_last_block_are_bit_identical(mode):
     """cmh_set_pooled_tail: only the class-token / EOT rows are carried through the last block's out_proj, ln_2 and MLP
-    (csrc/encoders.hip::run_block_pooled) - the features must equal the full-size path bit for bit, both towers, packed
+    (csrc/encoders.hip: block_forward on a lane with `pooled` rows) - the features must equal the full-size path bit for bit, both towers, packed
     and dense captions."""
     import cmh_native as N
     cfg = recipe.CLIP_VITB32
