@@ -22,6 +22,7 @@ BASE_FLAGS = [
     ("--data-dir", str, "", "directory with index.mat / caption.mat|txt / label.mat (this build; upstream hard-codes it)"),
     ("--synthetic-size", int, 2000, "items of the synthetic dataset (this build)"),
     ("--eval-curves", str2bool, False, "test(): also log P@H<=2 / P@N and store the precision-recall and top-N curves in the .mat (this build)"),
+    ("--eval-graded", str2bool, False, "test(): also log NDCG@N / ACG@N / WAP@N (relevance graded by the number of shared labels) and store them in the .mat (this build)"),
 ]
 
 

@@ -146,6 +146,9 @@ SIGNATURES = {
     "cmh_retrieval_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_hamming_hist": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _sz, _p]),
     "cmh_hamming_topk": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_hamming_topk_graded": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
     "cmh_dchmt_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -703,6 +706,61 @@ def hamming_topk(q_planes, r_planes, bits, k, q_lab=None, r_lab=None, want_count
                                  ptr(idx), ptr(dist), ptr(rel), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)),
           "cmh_hamming_topk")
     return (idx, dist, rel, counts) if want_counts else (idx, dist, rel)
+
+
+GRADE_CLASSES_MAX = 255      # a grade is one byte
+
+
+def _grade_classes(what, classes, LW):
+    """The class count of the graded entry points: the caller's, or what the packed words can hold (at most 255: the kernel
+    saturates a grade there, so the 256th bit of eight words cannot wrap it)."""
+    classes = min(32 * LW, GRADE_CLASSES_MAX) if classes is None else int(classes)
+    if classes < 1 or (classes + 31) // 32 != LW:
+        raise NativeError(f"{what}: classes={classes} does not fit label operands of {LW} words")
+    return classes
+
+
+def hamming_topk_graded(q_planes, r_planes, bits, k, q_lab, r_lab, want_counts=False, classes=None):
+    """hamming_topk with the NUMBER of shared labels where it has the hit flag: -> (idx int32 [Q, k], dist f32 [Q, k],
+    grade uint8 [Q, k]) [+ counts as hamming_hist with want_counts].  idx and dist are hamming_topk's, grade > 0 is its rel.
+    Labels are required, at most 255 classes (`classes`: the count behind pack_labels' words, 32 per word when None)."""
+    if q_lab is None or r_lab is None:
+        raise NativeError("hamming_topk_graded: needs the labels of both sides")
+    qs, qn, rs, rn, Q, N, LW = _retrieval_operands("hamming_topk_graded", q_planes, r_planes, bits, q_lab, r_lab)
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= N:
+        raise NativeError(f"hamming_topk_graded: k={k} outside [1, N={N}]")
+    classes = _grade_classes("hamming_topk_graded", classes, LW)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    grade = torch.empty(Q, k, dtype=torch.uint8, device=dev)
+    counts = torch.empty(Q, 2 * int(bits) + 1, 2, dtype=torch.int32, device=dev) if want_counts else None
+    ws = workspace(lib().cmh_retrieval_workspace_bytes(Q, N, int(bits)), dev, "retrieval")
+    check(lib().cmh_hamming_topk_graded(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), classes, k,
+                                        ptr(idx), ptr(dist), None, ptr(grade), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_hamming_topk_graded")
+    return (idx, dist, grade, counts) if want_counts else (idx, dist, grade)
+
+
+def label_overlap_hist(q_lab, r_lab, classes):
+    """-> int32 [Q, classes+1]: entry [q, g] = database items that share exactly g labels with query q (packed labels of
+    pack_labels, at most 255 classes).  Every row sums to N; N - [:, 0] = the query's relevant items."""
+    if q_lab is None or r_lab is None:
+        raise NativeError("label_overlap_hist: needs the labels of both sides")
+    require_gpu(q_lab, r_lab)
+    classes = int(classes)
+    Q, N, LW = q_lab.shape[0], r_lab.shape[0], (classes + 31) // 32
+    fit("label_overlap_hist", (q_lab, (Q, LW)), (r_lab, (N, LW)))
+    for t in (q_lab, r_lab):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("label_overlap_hist: packed operands are contiguous int32 tensors (pack_labels)")
+    dev = q_lab.device
+    out = torch.empty(Q, classes + 1, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_label_overlap_workspace_bytes(Q, N, classes), dev, "retrieval")
+    check(lib().cmh_label_overlap_hist(ptr(q_lab), ptr(r_lab), Q, N, classes, ptr(out), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_label_overlap_hist")
+    return out
 
 
 # ------------------------------------------------------------------------------------------ losses

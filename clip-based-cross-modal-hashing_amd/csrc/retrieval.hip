@@ -25,6 +25,15 @@
 // LDS per workgroup: (2K+1) * 256 bytes: 33 KiB at 64 bit (4 per CU), 64.25 KiB at 128 bit (2 per CU).  Wider codes (up to 2048 bit:
 // 4097 bins = 1 MiB per tile) keep the columns in the workspace and increment them with global atomics: same code, same results,
 // not fast.
+//
+// Graded relevance (NDCG / ACG / WAP count the labels a pair shares; calc_neighbor only asks whether there are any):
+//   cmh_hamming_topk_graded  the same search; the select pass stores popcount(la & lb) where it stores the hit flag
+//   cmh_label_overlap_hist   grade_counts[q, g] = database items that share exactly g labels with query q.  The mapping of the
+//                            distance histogram with the grade as the bin: 64 queries per workgroup with their label words in
+//                            registers (1 or 3 words) or staged in LDS, database label words wave-uniform, a private column
+//                            [g][lane] of full 32-bit counters (a chunk may hold any number of items), images summed by
+//                            grade_reduce_kernel.  LDS per workgroup: (C+1) * 256 bytes: 6.25 KiB at 24 classes, 20.25 KiB at 80,
+//                            64 KiB at 255 (one byte per grade: C <= 255).
 #include "cmh_common.h"
 
 namespace cmh {
@@ -34,6 +43,7 @@ constexpr int kRetMaxWords = 64;           // bits, classes <= 2048
 constexpr int kRetMaxN = (1 << 19) - 1;    // as the ranking kernel
 constexpr int kLdsBits = 128;              // columns in LDS up to this code length
 constexpr int kChunkMax = 65532;           // items per chunk: two 16-bit counters per word (a multiple of the unroll)
+constexpr int kGradeMax = 255;             // classes of the graded entry points: a grade is one byte
 constexpr size_t kImageCap = size_t(256) << 20;   // bytes of column images per batch of query tiles
 
 struct RetArgs {
@@ -43,7 +53,7 @@ struct RetArgs {
   uint32_t* img;      // [S][tiles][bins][64]
   uint32_t* off;      // [tiles][bins][64]
   int32_t* hstar;     // [tiles * 64]
-  uint32_t* counts;   // [Q][bins][2] or null
+  uint32_t* counts;   // [Q][bins][2] or null ([Q][bins], bins = classes + 1, in the label histogram)
   int32_t* idx;       // [Q][k]
   float* dist;        // [Q][k]
   uint8_t* rel;       // [Q][k] or null
@@ -112,6 +122,17 @@ struct Tile {
       for (int w = 0; w < LW; ++w) any |= st[((WT ? 0 : 2 * W) + w) * 64 + lane] & rl[w];
     }
     return any ? 1u : 0u;
+  }
+  // labels shared with one database item
+  __device__ __forceinline__ uint32_t overlap(const uint32_t* __restrict__ rl) const {
+    uint32_t g = 0;
+    if (LT > 0) {
+#pragma unroll
+      for (int w = 0; w < LR; ++w) g += __popc(l[w] & rl[w]);
+    } else if (LT == LAB_ANY) {
+      for (int w = 0; w < LW; ++w) g += __popc(st[((WT ? 0 : 2 * W) + w) * 64 + lane] & rl[w]);
+    }
+    return g;
   }
 };
 
@@ -245,9 +266,11 @@ __global__ __launch_bounds__(64) void radius_kernel(RetArgs a) {
 }
 
 // ---- pass 2: the stable counting sort of the items at h <= h* ---------------------------------------------------------------------
-template <int WT, int LT, bool GLOB>
+// GRADED: the grade of every placed item as well (grade [Q][k] of the batch, saturated at 255), the hit flag from it.  (A trailing
+// parameter, not a member of RetArgs: the argument layout and so the code of the other kernels stay what they were.)
+template <int WT, int LT, bool GLOB, bool GRADED = false>
 __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
-                                                    const uint32_t* __restrict__ rl) {
+                                                    const uint32_t* __restrict__ rl, uint8_t* __restrict__ grade) {
   extern __shared__ uint32_t smem[];
   const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
   const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
@@ -275,7 +298,13 @@ __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* _
         const size_t o = static_cast<size_t>(q) * k + p;
         a.idx[o] = j;
         a.dist[o] = 0.5f * static_cast<float>(h);
-        if (a.rel) a.rel[o] = static_cast<uint8_t>(t.relevant(rl + static_cast<size_t>(j) * a.LW));
+        if (GRADED) {
+          const uint32_t g = t.overlap(rl + static_cast<size_t>(j) * a.LW);
+          grade[o] = static_cast<uint8_t>(g < 255u ? g : 255u);
+          if (a.rel) a.rel[o] = g ? 1 : 0;
+        } else if (a.rel) {
+          a.rel[o] = static_cast<uint8_t>(t.relevant(rl + static_cast<size_t>(j) * a.LW));
+        }
       }
     }
   };
@@ -307,6 +336,81 @@ __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* _
   for (; j < je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
 }
 
+// ---- the label histogram: per (query tile, chunk) the column image: word [g][lane] = items of the chunk at grade g ----------------
+// The label words of U consecutive database items, as Group holds the code words: one or two wide scalar loads.
+template <int LT>
+struct LabelGroup {
+  static constexpr int U = LT == 1 ? 16 : 4, NL = U * (LT > 0 ? LT : 1);
+  uint32_t l[NL];
+  __device__ __forceinline__ void load(const uint32_t* __restrict__ rl, int j) {
+    const uint32_t* __restrict__ pl = rl + static_cast<size_t>(j) * LT;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) l[i] = pl[i];
+  }
+};
+
+template <int LT>
+__global__ __launch_bounds__(64) void grade_kernel(RetArgs a, const uint32_t* __restrict__ rl) {
+  extern __shared__ uint32_t smem[];
+  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their column
+  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  uint32_t* col = smem;
+  uint32_t* stage = smem + a.bins * 64;
+  Tile<0, LT> t;                                                     // no code words (a.W = 0): the label words only
+  t.load(a, q, lane, stage);
+  // the query's label words are cut to `classes` bits: whatever the words hold behind them, 0 <= g <= classes (g indexes the column)
+  const int classes = a.bins - 1;
+  const uint32_t last = (classes & 31) ? (1u << (classes & 31)) - 1u : 0xffffffffu;
+  if (LT > 0) t.l[(LT > 0 ? LT : 1) - 1] &= last;
+  else stage[(a.LW - 1) * 64 + lane] &= last;
+  for (int g = 0; g < a.bins; ++g) col[g * 64 + lane] = 0u;
+  __syncthreads();
+  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  int j = jb;
+  if (LT > 0) {
+    using G = LabelGroup<LT>;
+    auto work = [&](const G& g, int u0, int u1) {
+#pragma unroll
+      for (int u = u0; u < u1; ++u) atomicAdd(&col[t.overlap(g.l + u * LT) * 64 + lane], 1u);
+    };
+    const int groups = (je - jb) / G::U;
+    G ga, gb;                                                       // two register sets, fetched as in hist_kernel
+    int g = 0;
+    if (groups > 0) ga.load(rl, jb);
+    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
+      work(ga, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      gb.load(rl, j + G::U);
+      __builtin_amdgcn_sched_barrier(0);
+      work(ga, 1, G::U);
+      work(gb, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      ga.load(rl, g + 2 < groups ? j + 2 * G::U : j);
+      __builtin_amdgcn_sched_barrier(0);
+      work(gb, 1, G::U);
+    }
+    if (g < groups) { work(ga, 0, G::U); j += G::U; }
+  }
+  for (; j < je; ++j) atomicAdd(&col[t.overlap(rl + static_cast<size_t>(j) * a.LW) * 64 + lane], 1u);
+  __syncthreads();
+  for (int g = 0; g < a.bins; ++g) image[g * 64 + lane] = col[g * 64 + lane];
+}
+
+// ---- the images of a tile summed over the chunks -> grade_counts[q][g]
+__global__ __launch_bounds__(256) void grade_reduce_kernel(RetArgs a) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= stride) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t gb = t >> 6;
+  const int g = static_cast<int>(gb % a.bins), tile = static_cast<int>(gb / a.bins);
+  uint32_t tot = 0;
+  for (int c = 0; c < a.S; ++c) tot += a.img[c * stride + t];
+  const int q = tile * 64 + lane;
+  if (q < a.Q) a.counts[static_cast<size_t>(q) * a.bins + g] = tot;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 struct Plan {
   int bins, W, tiles, S, chunk, tb;      // tb = query tiles per batch (the images of one batch fit kImageCap)
@@ -328,6 +432,22 @@ int cu_count() {
   return cus;
 }
 
+// The database cut into chunks for `tiles` query tiles whose workgroups hold `lds` bytes of columns (0: none): as many chunks as
+// fill the chip's resident slots once (equal work per workgroup: a second, partly filled round would only wait for its last
+// members), at least smin, at most smax, none below 256 items.  Resident per CU: what the columns leave of the 160 KiB of LDS.
+// -> the number of chunks; *chunk = items per chunk, a multiple of 4.
+int cut_chunks(int n, int tiles, size_t lds, int smin, int smax, int* chunk) {
+  const int per_cu = lds == 0 ? 8 : static_cast<int>((160 * 1024) / lds) < 8 ? static_cast<int>((160 * 1024) / lds) : 8;
+  int s = cu_count() * per_cu / tiles;
+  const int by256 = (n + 255) / 256;
+  s = s < by256 ? s : by256;
+  s = s < smax ? s : smax;
+  s = s > smin ? s : smin;
+  s = s > 1 ? s : 1;
+  *chunk = ((n + s - 1) / s + 3) & ~3;
+  return (n + *chunk - 1) / *chunk;
+}
+
 Plan make_plan(int Q, int64_t N, int bits) {
   Plan p;
   p.bins = 2 * bits + 1;
@@ -336,18 +456,8 @@ Plan make_plan(int Q, int64_t N, int bits) {
   p.tiles = (Q + 63) / 64;
   const int n = static_cast<int>(N);
   const int smin = (n + kChunkMax - 1) / kChunkMax;
-  // one round of workgroups: as many chunks as fill the chip's resident slots once (equal work per workgroup: a second, partly
-  // filled round would only wait for its last members).  Resident per CU: what the columns leave of the 160 KiB of LDS.
   const size_t lds = p.glob ? 0 : static_cast<size_t>(p.bins) * 256;
-  const int per_cu = p.glob ? 8 : static_cast<int>((160 * 1024) / lds) < 8 ? static_cast<int>((160 * 1024) / lds) : 8;
-  int s = cu_count() * per_cu / p.tiles;
-  const int by256 = (n + 255) / 256;
-  s = s < by256 ? s : by256;
-  s = s < (p.glob ? 32 : 256) ? s : (p.glob ? 32 : 256);      // (an image of the wide codes is up to 1 MiB per tile)
-  s = s > smin ? s : smin;
-  s = s > 1 ? s : 1;
-  p.chunk = ((n + s - 1) / s + 3) & ~3;
-  p.S = (n + p.chunk - 1) / p.chunk;
+  p.S = cut_chunks(n, p.tiles, lds, smin, p.glob ? 32 : 256, &p.chunk);      // (an image of the wide codes is up to 1 MiB per tile)
   const size_t per_tile = (static_cast<size_t>(p.S) + 1) * p.tile_words() * 4;
   size_t tb = kImageCap / per_tile;
   tb = tb < 1 ? 1 : tb;
@@ -355,32 +465,39 @@ Plan make_plan(int Q, int64_t N, int bits) {
   return p;
 }
 
+enum Pass { PASS_HIST, PASS_SELECT, PASS_SELECT_GRADED };
+
 template <int WT, int LT, bool GLOB>
-int launch_pass(bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+int launch_pass(Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
   const size_t lds = ((GLOB ? 0 : static_cast<size_t>(a.bins) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
-  const void* fn = select ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB>) : reinterpret_cast<const void*>(hist_kernel<WT, LT, GLOB>);
+  constexpr bool kLabels = LT != LAB_NONE;      // (the graded select exists with labels only)
+  if (pass == PASS_SELECT_GRADED && !kLabels) return fail(CMH_ERR_INVALID, "retrieval: grades asked for without labels");
+  const void* fn = pass == PASS_SELECT_GRADED ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB, kLabels>)
+                   : pass == PASS_SELECT      ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB>)
+                                              : reinterpret_cast<const void*>(hist_kernel<WT, LT, GLOB>);
   if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
     return fail(CMH_ERR_LAUNCH, "retrieval: cannot reserve %zu bytes of LDS", lds);
-  if (select) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl);
+  if (pass == PASS_SELECT_GRADED) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB, kLabels>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, grade);
+  else if (pass == PASS_SELECT) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, grade);
   else hipLaunchKernelGGL((hist_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl);
-  CMH_CHECK_LAUNCH(select ? "hamming_topk select" : "hamming_hist");
+  CMH_CHECK_LAUNCH(pass == PASS_HIST ? "hamming_hist" : "hamming_topk select");
   return CMH_OK;
 }
 
 template <int WT, bool GLOB>
-int launch_labels(bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
-  if (a.LW == 0) return launch_pass<WT, LAB_NONE, GLOB>(select, a, rs, rn, rl, st);
-  if (!GLOB && a.LW == 1) return launch_pass<WT, 1, GLOB>(select, a, rs, rn, rl, st);      // <= 32 classes (MIRFlickr 24, NUS-WIDE 21)
-  if (!GLOB && a.LW == 3) return launch_pass<WT, 3, GLOB>(select, a, rs, rn, rl, st);      // 65..96 classes (MS-COCO 80)
-  return launch_pass<WT, LAB_ANY, GLOB>(select, a, rs, rn, rl, st);
+int launch_labels(Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
+  if (a.LW == 0) return launch_pass<WT, LAB_NONE, GLOB>(pass, a, rs, rn, rl, grade, st);
+  if (!GLOB && a.LW == 1) return launch_pass<WT, 1, GLOB>(pass, a, rs, rn, rl, grade, st);      // <= 32 classes (MIRFlickr 24, NUS-WIDE 21)
+  if (!GLOB && a.LW == 3) return launch_pass<WT, 3, GLOB>(pass, a, rs, rn, rl, grade, st);      // 65..96 classes (MS-COCO 80)
+  return launch_pass<WT, LAB_ANY, GLOB>(pass, a, rs, rn, rl, grade, st);
 }
 
-int launch_any(bool glob, bool select, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
-  if (glob) return launch_labels<0, true>(select, a, rs, rn, rl, st);
-  if (a.W == 1) return launch_labels<1, false>(select, a, rs, rn, rl, st);
-  if (a.W == 2) return launch_labels<2, false>(select, a, rs, rn, rl, st);
-  if (a.W == 3) return launch_labels<3, false>(select, a, rs, rn, rl, st);
-  return launch_labels<4, false>(select, a, rs, rn, rl, st);
+int launch_any(bool glob, Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
+  if (glob) return launch_labels<0, true>(pass, a, rs, rn, rl, grade, st);
+  if (a.W == 1) return launch_labels<1, false>(pass, a, rs, rn, rl, grade, st);
+  if (a.W == 2) return launch_labels<2, false>(pass, a, rs, rn, rl, grade, st);
+  if (a.W == 3) return launch_labels<3, false>(pass, a, rs, rn, rl, grade, st);
+  return launch_labels<4, false>(pass, a, rs, rn, rl, grade, st);
 }
 
 int check_shape(const char* what, int Q, int64_t N, int bits, int classes, bool labels) {
@@ -394,7 +511,7 @@ int check_shape(const char* what, int Q, int64_t N, int bits, int classes, bool 
 // hist (k == 0) or hist + select (k > 0), in batches of query tiles
 int run(const char* what, const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
         const uint32_t* r_nz, const uint32_t* r_label, int Q, int64_t N, int bits, int classes, int k, int32_t* idx, float* dist,
-        uint8_t* rel, uint32_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
+        uint8_t* rel, uint8_t* grade, uint32_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
   const Plan p = make_plan(Q, N, bits);
   if (!workspace || workspace_bytes < p.bytes()) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, p.bytes());
   RetArgs a;
@@ -419,14 +536,15 @@ int run(const char* what, const uint32_t* q_sign, const uint32_t* q_nz, const ui
     a.rel = rel ? rel + static_cast<size_t>(q0) * k : nullptr;
     if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "%s: memset failed", what);
-    int rc = launch_any(p.glob, false, a, r_sign, r_nz, r_label, st);
+    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
     if (rc != CMH_OK) return rc;
     hipLaunchKernelGGL(reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, select ? 1 : 0);
     CMH_CHECK_LAUNCH("retrieval reduce");
     if (select) {
       hipLaunchKernelGGL(radius_kernel, dim3(a.tiles), dim3(64), 0, st, a);
       CMH_CHECK_LAUNCH("retrieval radius");
-      rc = launch_any(p.glob, true, a, r_sign, r_nz, r_label, st);
+      rc = launch_any(p.glob, grade ? PASS_SELECT_GRADED : PASS_SELECT, a, r_sign, r_nz, r_label,
+                      grade ? grade + static_cast<size_t>(q0) * k : nullptr, st);
       if (rc != CMH_OK) return rc;
     }
   }
@@ -450,7 +568,7 @@ extern "C" int cmh_hamming_hist(const uint32_t* q_sign, const uint32_t* q_nz, co
   CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_hist: labels on one side only");
   const int rc = check_shape("hamming_hist", Q, N, bits, classes, q_label != nullptr);
   if (rc != CMH_OK) return rc;
-  return run("hamming_hist", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, 0, nullptr, nullptr, nullptr, counts,
+  return run("hamming_hist", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, 0, nullptr, nullptr, nullptr, nullptr, counts,
              workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -466,5 +584,87 @@ extern "C" int cmh_hamming_topk(const uint32_t* q_sign, const uint32_t* q_nz, co
   if (rc != CMH_OK) return rc;
   CMH_CHECK_ARG(k <= N, "hamming_topk: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
   return run("hamming_topk", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist, rel,
-             counts, workspace, workspace_bytes, as_stream(stream));
+             nullptr, counts, workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                                       const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits,
+                                       int32_t classes, int64_t k, int32_t* idx, float* dist, uint8_t* rel, uint8_t* grade,
+                                       uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && idx && dist && grade, "hamming_topk_graded: null pointer");
+  CMH_CHECK_ARG(q_label && r_label, "hamming_topk_graded: grades need the labels of both sides");
+  CMH_CHECK_ARG(k >= 1 && k <= CMH_TOPK_MAX, "hamming_topk_graded: k=%lld outside [1, %d]", static_cast<long long>(k), CMH_TOPK_MAX);
+  const int rc = check_shape("hamming_topk_graded", Q, N, bits, classes, true);
+  if (rc != CMH_OK) return rc;
+  CMH_CHECK_ARG(classes <= kGradeMax, "hamming_topk_graded: classes=%d exceeds %d (a grade is one byte)", classes, kGradeMax);
+  CMH_CHECK_ARG(k <= N, "hamming_topk_graded: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
+  return run("hamming_topk_graded", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist,
+             rel, grade, counts, workspace, workspace_bytes, as_stream(stream));
+}
+
+namespace cmh {
+namespace {
+
+struct GradePlan {
+  int bins, LW, tiles, S, chunk;
+  size_t lds() const { return (static_cast<size_t>(bins) + (LW == 1 || LW == 3 ? 0 : LW)) * 256; }      // columns + staged query words
+  size_t bytes() const { return static_cast<size_t>(S) * tiles * bins * 256 + 256; }
+};
+
+GradePlan make_grade_plan(int Q, int64_t N, int classes) {
+  GradePlan p;
+  p.bins = classes + 1;
+  p.LW = (classes + 31) / 32;
+  p.tiles = (Q + 63) / 64;
+  p.S = cut_chunks(static_cast<int>(N), p.tiles, p.lds(), 1, 256, &p.chunk);      // 32-bit counters: no limit on a chunk's items
+  return p;
+}
+
+int check_grade_shape(const char* what, int Q, int64_t N, int classes) {
+  CMH_CHECK_ARG(Q > 0 && Q <= 65535 && N > 0, "%s: Q=%d N=%lld", what, Q, static_cast<long long>(N));
+  CMH_CHECK_ARG(N <= kRetMaxN, "%s: N=%lld exceeds %d", what, static_cast<long long>(N), kRetMaxN);
+  CMH_CHECK_ARG(classes > 0, "%s: classes=%d unsupported", what, classes);
+  CMH_CHECK_ARG(classes <= kGradeMax, "%s: classes=%d exceeds %d (a grade is one byte)", what, classes, kGradeMax);
+  return CMH_OK;
+}
+
+template <int LT>
+int launch_grade(const RetArgs& a, const uint32_t* rl, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(grade_kernel<LT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds)) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "label_overlap_hist: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL((grade_kernel<LT>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rl);
+  CMH_CHECK_LAUNCH("label_overlap_hist");
+  return CMH_OK;
+}
+
+}  // namespace
+}  // namespace cmh
+
+extern "C" size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes) {
+  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || classes <= 0 || classes > kGradeMax) return 0;
+  return make_grade_plan(Q, N, classes).bytes();
+}
+
+extern "C" int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r_label, int32_t Q, int64_t N, int32_t classes,
+                                      uint32_t* grade_counts, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_label && r_label && grade_counts, "label_overlap_hist: null pointer");
+  int rc = check_grade_shape("label_overlap_hist", Q, N, classes);
+  if (rc != CMH_OK) return rc;
+  const GradePlan p = make_grade_plan(Q, N, classes);
+  if (!workspace || workspace_bytes < p.bytes())
+    return fail(CMH_ERR_WORKSPACE, "label_overlap_hist: workspace %zu < %zu bytes", workspace_bytes, p.bytes());
+  hipStream_t st = as_stream(stream);
+  RetArgs a = {};
+  a.ql = q_label;
+  a.Q = Q; a.N = static_cast<int>(N); a.bits = 32; a.W = 0; a.LW = p.LW; a.bins = p.bins; a.tiles = p.tiles; a.S = p.S; a.chunk = p.chunk;
+  a.img = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  a.counts = grade_counts;
+  rc = p.LW == 1 ? launch_grade<1>(a, r_label, p.lds(), st) : p.LW == 3 ? launch_grade<3>(a, r_label, p.lds(), st)
+                                                                        : launch_grade<LAB_ANY>(a, r_label, p.lds(), st);
+  if (rc != CMH_OK) return rc;
+  const size_t stride = static_cast<size_t>(p.tiles) * p.bins * 64;
+  hipLaunchKernelGGL(grade_reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a);
+  CMH_CHECK_LAUNCH("label_overlap_hist reduce");
+  return CMH_OK;
 }

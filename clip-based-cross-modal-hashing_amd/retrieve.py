@@ -4,7 +4,8 @@
     python retrieve.py --codes result/DSPH/flickr25k/64/PR_cruve/64-ours-flickr25k-i2t.mat --direction i2t --k 10 --queries 0:5
 
 prints one line per query: its number, then `index:distance` (`index:distance:hit` when the file has labels) for the k nearest
-database items, nearest first, ties by database index."""
+database items, nearest first, ties by database index.  With --graded the third field is the number of labels the neighbour shares
+with the query (0 = no hit) instead of the 0/1 flag."""
 import argparse
 import sys
 
@@ -17,6 +18,7 @@ def parse(argv=None):
     p.add_argument("--direction", choices=sorted(DIRECTIONS), default="i2t", help="query side -> database side")
     p.add_argument("--k", type=int, default=10, help="neighbours per query")
     p.add_argument("--queries", default=":", help="slice a:b of the file's queries (default: all)")
+    p.add_argument("--graded", action="store_true", help="print the shared-label count of each neighbour in place of the hit flag (needs labels in the file)")
     return p.parse_args(argv)
 
 
@@ -40,9 +42,11 @@ def main(argv=None):
     index = CodeIndex.from_mat(args.codes, side=r_key)
     queries = torch.from_numpy(m[q_key][lo:hi]).float()
     labels = torch.from_numpy(m["q_l"][lo:hi]).float() if index.labels is not None and "q_l" in m else None
+    if args.graded and labels is None:
+        raise SystemExit(f"--graded: {args.codes} holds no labels (q_l, r_l)")
     if hi == lo:
         return 0
-    out = [t.cpu().numpy() for t in index.search(queries, args.k, labels)]
+    out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]
     for i in range(hi - lo):
         cols = [f"{out[0][i, j]}:{out[1][i, j]:g}" + (f":{out[2][i, j]}" if len(out) == 3 else "") for j in range(args.k)]
         print(lo + i, " ".join(cols))

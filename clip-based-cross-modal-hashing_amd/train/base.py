@@ -342,6 +342,8 @@ class TrainBase(object):
         self.max_mapt2i = max(self.max_mapt2i, mAPt2i)
         self.logger.info(f">>>>>> MAP(i->t): {mAPi2t}, MAP(t->i): {mAPt2i}, MAP(t->t): {mAPt2t}, MAP(i->i): {mAPi2i}")
         extra = self._eval_curves(query_img, query_txt, retrieval_img, retrieval_txt) if getattr(self.args, "eval_curves", False) else None
+        if getattr(self.args, "eval_graded", False):
+            extra = dict(extra or {}, **self._eval_graded(query_img, query_txt, retrieval_img, retrieval_txt))
         self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
 
@@ -362,6 +364,25 @@ class TrainBase(object):
             at = {n: float(tp[topn.index(n)]) for n in (100, 500, 1000) if n in topn}
             shown = [f"P@H<=2: {float(p[min(4, p.numel() - 1)]):.6f}"] + [f"P@{n}: {v:.6f}" for n, v in at.items()]      # radius 2 = half-distance 4
             self.logger.info(f">>>>>> curves({name}): " + ", ".join(shown))
+        return extra
+
+    def _eval_graded(self, query_img, query_txt, retrieval_img, retrieval_txt):
+        """--eval-graded: NDCG@n, ACG@n and WAP@n for the four directions (utils/retrieval.py), relevance graded by the number of
+        labels a pair shares.  The label histogram behind the ideal DCG depends on the labels only: computed once.  The log shows
+        n = 100 and 1000 where the database holds that many items, else its largest cut-off."""
+        from utils import retrieval as R
+        sides = {"i2t": (query_img, retrieval_txt), "t2i": (query_txt, retrieval_img),
+                 "i2i": (query_img, retrieval_img), "t2t": (query_txt, retrieval_txt)}
+        topn = tuple(n for n in R.DEFAULT_TOPN if n <= retrieval_img.shape[0])
+        grade_counts = R.grade_histogram(self.query_labels, self.retrieval_labels)
+        extra = {"graded_topn": torch.tensor(topn).numpy(), "grade_counts": grade_counts.cpu().numpy()}
+        for name, (q, r) in sides.items():
+            ndcg, acg, wap, _ = R.graded_metrics(q, r, self.query_labels, self.retrieval_labels, topn, grade_counts=grade_counts)
+            extra.update({f"ndcg_{name}": ndcg.numpy(), f"acg_{name}": acg.numpy(), f"wap_{name}": wap.numpy()})
+            at = lambda m, ns: [(n, float(m[topn.index(n)])) for n in ns if n in topn] or [(topn[-1], float(m[-1]))]
+            shown = [f"NDCG@{n}: {v:.6f}" for n, v in at(ndcg, (100, 1000))] + [f"ACG@{n}: {v:.6f}" for n, v in at(acg, (100,))] \
+                + [f"WAP@{n}: {v:.6f}" for n, v in at(wap, (100,))]
+            self.logger.info(f">>>>>> graded({name}): " + ", ".join(shown))
         return extra
 
     def compute_loss(self):

@@ -440,6 +440,24 @@ int cmh_hamming_topk(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_
                      const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
                      int64_t k, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* Graded relevance: the grade of a pair is the NUMBER of labels it shares, popcount(label_q & label_r) = the entry of
+ * label1.matmul(label2.T) that calc_neighbor (:42-45) thresholds; NDCG@n, ACG@n and WAP@n are sums over it.  A grade is one byte:
+ * both entry points take classes <= 255 and refuse more.  Label bits at or above `classes` are zero (cmh_pack_labels writes them so).
+ *
+ * cmh_hamming_topk with grade u8 [Q, k] = the grade of every neighbour (saturated at 255).  Labels and grade are required; idx and
+ * dist are cmh_hamming_topk's bit for bit, rel (optional) == grade > 0, counts (optional) as cmh_hamming_hist.  Workspace:
+ * cmh_retrieval_workspace_bytes. */
+int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                            const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                            int64_t k, int32_t* idx, float* dist, uint8_t* rel, uint8_t* grade, uint32_t* counts,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* grade_counts u32 [Q, classes+1]: grade_counts[i, g] = database items that share exactly g labels with query i (every row sums to
+ * N; N - grade_counts[i, 0] = the query's relevant items).  It depends on the labels only, so one call serves every direction of
+ * an evaluation; the ideal DCG of a query follows from its row without sorting.  Written once, deterministic.  Workspace: its own
+ * query below (cmh_retrieval_workspace_bytes is sized by the code length, which this pass does not have). */
+size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes);
+int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r_label, int32_t Q, int64_t N, int32_t classes,
+                           uint32_t* grade_counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.

@@ -2,9 +2,13 @@
 hamming_map(tie_order=TIE_STABLE, want_perm=True)[2][:, :k], a full sort of N per query and a [Q, N] int32 ranking.
 
 Shapes: 5000 x 15 015 x 64 bit (bench.py's default --map-db) and 5000 x 190 834 x 128 bit (NUS-WIDE).  Packed, resident operands;
-every leg warmed up; legs alternate (ranking, topk k=100, topk k=1000, histogram) x REGIONS in one process; device events around each
-region; a region of the new legs is several calls (a single one is too short to time) and is reported per call.  The outputs of the
-two routes are compared on the timed inputs.  One JSON line per shape (also into --out).
+every leg warmed up; legs alternate (ranking, topk k=100, topk k=1000, histogram, graded topk k=100, graded topk k=1000, label
+histogram) x REGIONS in one process; device events around each region; a region of the new legs is several calls (a single one is
+too short to time) and is reported per call.  The outputs of the two routes are compared on the timed inputs, and the graded
+search's idx / dist with the plain search's.  One JSON line per shape (also into --out).
+
+The graded legs (hamming_topk_graded, label_overlap_hist) are reported against the plain legs of the same run: `graded_over_plain`
+= median over median at the same k, `labelhist_over_hist` = the label histogram over the distance histogram.
 
 Floors of one pass over the database, from the shapes (printed with the line):
   bytes     query tiles x N x (2 W + LW) x 4 B: the database is re-read once per tile of 64 queries, from L2 (34.5 TB/s aggregate);
@@ -63,6 +67,9 @@ def main():
             "topk100": (args.reps, lambda: N.hamming_topk(qp, rp, K, 100, ql, rl)),
             "topk1000": (args.reps, lambda: N.hamming_topk(qp, rp, K, 1000, ql, rl)),
             "hist": (args.reps, lambda: N.hamming_hist(qp, rp, K, ql, rl)),
+            "graded100": (args.reps, lambda: N.hamming_topk_graded(qp, rp, K, 100, ql, rl, classes=C)),
+            "graded1000": (args.reps, lambda: N.hamming_topk_graded(qp, rp, K, 1000, ql, rl, classes=C)),
+            "labelhist": (args.reps, lambda: N.label_overlap_hist(ql, rl, C)),
         }
         # warm-up, and the outputs of the two routes on the timed inputs
         perm = legs["ranking"][1]()
@@ -71,7 +78,11 @@ def main():
         full = N.hamming_dist((qp[0][:64].contiguous(), qp[1][:64].contiguous()), rp, K)
         same = same and bool(torch.equal(i1000[1][:64], full.gather(1, i1000[0][:64].long())))
         same = same and bool((counts.long().sum((1, 2)) == n).all())
-        del perm, full
+        g100, g1000, gcounts = legs["graded100"][1](), legs["graded1000"][1](), legs["labelhist"][1]()
+        graded_same = all(bool(torch.equal(a[j], b[j])) for a, b in ((g100, i100), (g1000, i1000)) for j in (0, 1))
+        graded_same = graded_same and bool(torch.equal((g1000[2] > 0).to(torch.uint8), i1000[2]))
+        graded_same = graded_same and bool(torch.equal(n - gcounts[:, 0], counts[:, :, 1].sum(1).to(gcounts.dtype)))
+        del perm, full, g100, g1000, gcounts
         torch.cuda.synchronize()
         times = {k: [] for k in legs}
         for _ in range(REGIONS):
@@ -85,7 +96,7 @@ def main():
                 del out
                 times[leg].append(e0.elapsed_time(e1) / reps)
         line = {"tool": "retrieval_bench", "shape": name, "Q": Q, "N": n, "bits": K, "classes": C, "regions": REGIONS,
-                "outputs_equal": same, "ms": {}}
+                "outputs_equal": same, "graded_outputs_equal": graded_same, "ms": {}}
         for leg, ts in times.items():
             line["ms"][leg] = {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
         for leg, passes in (("topk100", 2), ("topk1000", 2), ("hist", 1)):
@@ -93,6 +104,9 @@ def main():
             line["ms"][leg]["floor_ms"] = {k: (round(v, 4) if k != "bound" else v) for k, v in fl.items()}
             line["ms"][leg]["share_of_floor"] = round(fl[fl["bound"]] / line["ms"][leg]["median"], 4)
             line["ms"][leg]["ranking_min_over_max"] = round(line["ms"]["ranking"]["min"] / line["ms"][leg]["max"], 2)
+        for leg, base in (("graded100", "topk100"), ("graded1000", "topk1000")):
+            line["ms"][leg]["graded_over_plain"] = round(line["ms"][leg]["median"] / line["ms"][base]["median"], 4)
+        line["ms"]["labelhist"]["labelhist_over_hist"] = round(line["ms"]["labelhist"]["median"] / line["ms"]["hist"]["median"], 4)
         line["new_slowest_beats_ranking_fastest"] = all(line["ms"][leg]["max"] < line["ms"]["ranking"]["min"] for leg in ("topk100", "topk1000"))
         text = json.dumps(line)
         print(text, flush=True)
@@ -102,6 +116,8 @@ def main():
                 f.write(text + "\n")
         if not same:
             raise SystemExit(f"{name}: the two routes disagree")
+        if not graded_same:
+            raise SystemExit(f"{name}: the graded search disagrees with the plain search")
 
 
 if __name__ == "__main__":
