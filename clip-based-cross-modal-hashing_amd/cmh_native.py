@@ -107,6 +107,7 @@ SIGNATURES = {
     "cmh_set_gemm_grouped": (C.c_int, [_i32]),
     "cmh_set_gemm_lc": (C.c_int, [_i32]),
     "cmh_gemm_route": (C.c_int, [_i32] * 8),
+    "cmh_gemm_plan": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "cmh_set_grad_stream16": (C.c_int, [_i32]),
     "cmh_set_text_token_packing": (C.c_int, [_i32]),
     "cmh_linear_gemm_grouped": (C.c_int, [_i32, C.POINTER(GemmProblem), C.POINTER(GemmProblem), _i32, _p]),
@@ -433,9 +434,10 @@ def set_grad_stream16(on: int):
 
 
 def set_gemm_lc(mode: int):
-    """Loader / consumer GEMM kernels (csrc/gemm_lc.hip): -1 environment (CMH_GEMM_LC, unset = 8), 0 the wide kernel only, 1 the 8-wave
-    kernel for every eligible launch, 4 the 12-wave 128-row form, 7 the fp8 QKV form, 8 per-launch cost model over the wide kernel and
-    both 12-wave forms (the default), 9 the 12-wave 160-row form for every eligible launch."""
+    """Loader / consumer GEMM kernels (csrc/gemm_lc.hip): -1 environment (CMH_GEMM_LC, unset = 8), 0 the wide kernel only, 1 / 2 / 3 the
+    8-wave kernel for every eligible launch (2: all but the QuickGELU launches; otherwise alike), 4 the 12-wave 128-row form, 7 the fp8
+    QKV form, 8 per launch the 12-wave 160-row form or the wide kernel, whichever the cost model prices lower (the default; never the
+    128-row form), 9 the 12-wave 160-row form for every eligible launch."""
     check(lib().cmh_set_gemm_lc(int(mode)), "cmh_set_gemm_lc")
 
 
@@ -447,6 +449,19 @@ def gemm_route(a, b=None, epi=0, dt=None):
     if rc < 0:
         raise NativeError(f"cmh_gemm_route: {lib().cmh_last_error()}")
     return rc
+
+
+PLAN_FIELDS = ("family", "rows", "grid", "order", "dge", "res", "grouped")
+
+
+def gemm_plan(a, b=None, epi=0, dt=None):
+    """The plan of a GEMM request under the current switches, without launching it (include/cmh.h: cmh_gemm_plan).  a, b: (M, N, K) or
+    (M, N, K, rows_on_device, hint).  -> (route, [one dict of PLAN_FIELDS per launch])."""
+    def five(s):
+        return (_i32 * 5)(*(tuple(s) + (0, 0))[:5])
+    out = (_i32 * 16)()
+    check(lib().cmh_gemm_plan(BF16 if dt is None else dt, int(epi), five(a), None if b is None else five(b), out), "cmh_gemm_plan")
+    return out[1], [dict(zip(PLAN_FIELDS, out[2 + 7 * i:9 + 7 * i])) for i in range(out[0])]
 
 
 def gemm_tuning(tile_rows: int = -1, order_group: int = -1):

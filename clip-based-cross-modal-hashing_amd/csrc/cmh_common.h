@@ -131,6 +131,35 @@ struct GemmProblem {
   const float* colscale; float alpha, oscale;                 // fp8 operands (launch_gemm_fp8's arguments); unused otherwise
 };
 int launch_gemm_grouped(int dt, const GemmProblem& a, const GemmProblem& b, int epi, hipStream_t st);
+// What one GEMM launch runs.  gemm.hip's plan_gemm decides every field, once per launch and on the host alone; the launchers of
+// the kernel files below take the finished plan and only pick the template instance.
+enum : int { GEMM_WIDE = 0, GEMM_ROWS = 1, GEMM_FALLBACK = 2, GEMM_LC = 3, GEMM_LC2 = 4, GEMM_LC3 = 5, GEMM_LC2Q = 6 };
+struct GemmPlan {
+  int launches;   // 1; 2 = a grouped request that runs as two plain launches, each with a plan of its own (no other field is set)
+  int family;     // GEMM_*: gemm_wide_kernel, gemm_rows_kernel, the 128 x 128 gemm_glds_kernel, gemm_lc / lc2 / lc3 / lc2q_kernel
+  int rows;       // tile rows
+  int grid;       // workgroups
+  int order;      // tile-order group (gemm_order_group; the 128 x 128 kernel: CMH_GEMM_ORDER as it stands)
+  int res;        // residual: 0 none, 1 first, 2 behind the bias (the lc forms' template parameter; the other kernels apply the
+                  // same rule per GEMM on the device)
+  bool dge;       // the wide kernel's deferred-QuickGELU variant
+  bool swap;      // one grouped launch: the second problem has the longer K, so its tiles go first
+};
+int plan_gemm(int dt, const GemmProblem& a, const GemmProblem* b, int epi, GemmPlan* p);   // gemm.hip; b: a grouped request
+int gemm_cus();                    // gemm.hip: the CU count the persistent grids are sized for (whole groups of 8; 256 without a GPU)
+int gemm_order_group(int N);       // gemm.hip: n-panels per group of the wide kernel's tile order
+// the launchers: ev0 / ev1 (optional) are stamped with the dispatch's own begin / end; a / b in the order their tiles run
+int launch_gemm_wide(int dt, const GemmProblem& a, const GemmProblem* b, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0,
+                     hipEvent_t ev1);
+int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int launch_gemm_lc2q(const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int launch_gemm_rows(int dt, const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int launch_gemm_glds(int dt, const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st);
+// pure predicates of the kernel files (gemm_lc.hip reads cmh_set_gemm_lc's mode, gemm_rows.hip cmh_set_gemm_rows' switch)
+bool gemm_wide_supported(int N);                       // N % 256 == 0
+int gemm_lc_mode();
+bool gemm_lc_takes(int dt, int N, int K, int epi);     // a loader / consumer form has this launch's arithmetic
+bool gemm_lc2q_takes(int N, int K, int epi);           // ... the e4m3 form (mode 7)
 bool gemm_rows_takes(int M, int N, int K, int epi);   // gemm_rows.hip: this launch would run on the few-row kernel
 int launch_gemm(int dt, const void* A, const void* W, const float* bias, const float* residual,
                 void* out, int M, int N, int K, int epi, hipStream_t st, const int32_t* m_dev = nullptr, int m_hint = -1);

@@ -169,16 +169,14 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const char* __restrict__
   }
 }
 
-void launch_gemm_glds(int dt, const void* A, const void* W, const float* bias, const float* residual, void* out,
-                      int M, int N, int K, int epi, hipStream_t st) {
-  const int total = (N / gTile) * ((M + gTile - 1) / gTile);
-  static const int order = []() { const char* e = getenv("CMH_GEMM_ORDER"); return e ? atoi(e) : 0; }();
+int launch_gemm_glds(int dt, const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st) {
   if (dt == CMH_F32)
-    hipLaunchKernelGGL(gemm_glds_kernel<true>, dim3(total), dim3(256), 0, st, static_cast<const char*>(A),
-                       static_cast<const char*>(W), bias, residual, out, M, N, K, epi, order);
+    hipLaunchKernelGGL(gemm_glds_kernel<true>, dim3(p.grid), dim3(256), 0, st, static_cast<const char*>(g.A),
+                       static_cast<const char*>(g.W), g.bias, g.residual, g.out, g.M, g.N, g.K, epi, p.order);
   else
-    hipLaunchKernelGGL(gemm_glds_kernel<false>, dim3(total), dim3(256), 0, st, static_cast<const char*>(A),
-                       static_cast<const char*>(W), bias, residual, out, M, N, K, epi, order);
+    hipLaunchKernelGGL(gemm_glds_kernel<false>, dim3(p.grid), dim3(256), 0, st, static_cast<const char*>(g.A),
+                       static_cast<const char*>(g.W), g.bias, g.residual, g.out, g.M, g.N, g.K, epi, p.order);
+  return 0;
 }
 
 }  // namespace cmh

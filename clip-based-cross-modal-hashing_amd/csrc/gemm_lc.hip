@@ -1309,7 +1309,6 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
 #undef L3_REFILL_W
 }
 
-int gemm_lc_mode();
 // ---- "lc2q": the 12-wave form on e4m3 operands (the fp8 mode, BASELINE configs[4]) -------------------------------------------------------
 // A K-step of fp8 operands moves the same 48 KB as a bf16 one for half as many MFMA cycles per k (v_mfma_scale_f32_16x16x128_f8f6f4:
 // one instruction per 16 x 16 x 128), so a K = 768 tile has only SIX K-steps and the wide kernel's fp8 launches are dominated by what
@@ -1541,17 +1540,12 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
 #undef Q_WAIT_ALL
 }
 
-int launch_gemm_lc2q(const GemmProblem& g, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  if (static_cast<size_t>(g.M) * g.K >= (1ull << 32)) return fail(CMH_ERR_INVALID, "gemm (lc2q): operand exceeds the 32-bit offset range");
+int launch_gemm_lc2q(const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   LcProblem P0{static_cast<const char*>(g.A), static_cast<const char*>(g.W), g.bias, g.residual, g.out, g.m_dev, g.M, g.N, g.K};
   P0.colscale = g.colscale; P0.alpha = g.alpha; P0.oscale = g.oscale;
   const LcProblem P1{};
-  const int total = (g.N / lcBN) * ((g.M + lcBM - 1) / lcBM);
-  int cus = 256;
-  { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8) cus = prop.multiProcessorCount & ~7; }
-  const int grid = total < cus ? ((total + 7) & ~7) : cus;
-  if (ev0) hipExtLaunchKernelGGL((gemm_lc2q_kernel<false>), dim3(grid), dim3(768), 0, st, ev0, ev1, 0, P0, P1, epi);
-  else hipLaunchKernelGGL((gemm_lc2q_kernel<false>), dim3(grid), dim3(768), 0, st, P0, P1, epi);
+  if (ev0) hipExtLaunchKernelGGL((gemm_lc2q_kernel<false>), dim3(p.grid), dim3(768), 0, st, ev0, ev1, 0, P0, P1, epi);
+  else hipLaunchKernelGGL((gemm_lc2q_kernel<false>), dim3(p.grid), dim3(768), 0, st, P0, P1, epi);
   CMH_CHECK_LAUNCH("gemm (lc2q)");
   return 0;
 }
@@ -1580,161 +1574,50 @@ bool gemm_lc_takes(int dt, int N, int K, int epi) {
   return true;
 }
 
-// Which kernel takes a bf16 launch (b: the second problem of a grouped launch): 0 the wide kernel, 1 the 8-wave lc kernel, 2 the
-// 12-wave form on 128-row tiles (lc2), 3 on 160-row tiles (lc3).  Mode 8 (the default) prices the wide kernel (`wide_cost`, the units
-// of gemm_wide.hip's tile-height model: the worst workgroup's K-steps + 4 per tile, x rows / 32 x 10 + 6) against the 160-row form
-// in the same units - the kernel's static tile assignment replayed for its tile height - times what a K-step of it costs against
-// the wide kernel's (profiles/r06_a_lc_per_shape.txt), and takes the cheaper.
-static long long lc_cost(const GemmProblem& a, const GemmProblem* b, int rows, int cus) {
-  auto likely = [](const GemmProblem& g) { return g.m_dev && g.m_hint > 0 && g.m_hint <= g.M ? g.m_hint : g.M; };
-  auto tiles_of = [&](int M, int N) { return (N / lcBN) * ((M + rows - 1) / rows); };
-  const int total = tiles_of(a.M, a.N) + (b ? tiles_of(b->M, b->N) : 0);
-  const int per = (total < cus ? ((total + 7) & ~7) : cus) >> 3;
-  const int t0 = tiles_of(likely(a), a.N), t1 = b ? tiles_of(likely(*b), b->N) : 0;
-  const int nk0 = a.K / 64, nk1 = b ? b->K / 64 : 0;
-  long long worst = 0;
-  for (int x = 0; x < 8; ++x) {
-    const int len0 = (t0 >> 3) + (x < (t0 & 7)), len1 = (t1 >> 3) + (x < (t1 & 7));
-    for (int sl = 0; sl < per; ++sl) {
-      const int n0 = sl < len0 ? (len0 - sl + per - 1) / per : 0;
-      const int nall = sl < len0 + len1 ? (len0 + len1 - sl + per - 1) / per : 0;
-      const long long c = static_cast<long long>(n0) * (nk0 + 4) + static_cast<long long>(nall - n0) * (nk1 + 4);
-      worst = c > worst ? c : worst;
-    }
-  }
-  return worst * (10 * (rows / 32) + 6);
-}
-static int lc_cus();
-bool gemm_lc_res_first(int epi, int K);
-int gemm_lc_form(int dt, const GemmProblem& a, const GemmProblem* b, int epi, long long wide_cost) {
-  const int mode = gemm_lc_mode();
-  if (!gemm_lc_takes(dt, a.N, a.K, epi) || (b && (!gemm_lc_takes(dt, b->N, b->K, epi) || gemm_lc_res_first(epi, a.K) != gemm_lc_res_first(epi, b->K))))
-    return 0;
-  if (mode >= 1 && mode <= 3) return 1;
-  if (mode == 4) return 2;
-  if (mode == 9) return 3;
-  if (mode != 8) return 0;
-  // The 160-row form against the wide kernel: its K-step priced at 56/64 of the wide kernel's (83 % MFMA issue against 65-72 %), its
-  // tiles by the same static assignment.  It never takes a residual launch: its residual forms spill 27-28 scratch instructions per
-  // tile in the epilogue (none in the K loop) and measured 1.02-1.5 x the wide kernel on all six (profiles/r06_a_lc_per_shape.txt).
-  // The 128-row form (lc2) is not routed: with its reads compiler-counted it measured 1.08 x on grouped out_proj, the one block launch
-  // where the hand-counted form had won (0.93; profiles/r06_d_route_ab.txt), and it stays an opt-in (mode 4).
-  if (epi & EPI_RESIDUAL) return 0;
-  if (lc_cost(a, b, lc3BM, lc_cus()) * 56 / 64 < wide_cost) return 3;
-  return 0;
-}
-
-// the wide kernel's residual-first rule (gemm_wide.hip, res_first): per GEMM
-bool gemm_lc_res_first(int epi, int K) {
-  return (epi & EPI_RESIDUAL) && !(epi & (EPI_QUICKGELU | EPI_GELU | EPI_RELU)) && K / 64 <= 16;
-}
-
-static int lc_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus < 8) cus = 256;
-    cus &= ~7;
-  }
-  return cus;
-}
-
-// b == nullptr: one problem.  The problem with the longer K goes first (its tiles are the long jobs of the static schedule).
-int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int form) {
-  for (const GemmProblem* g : {&a, b}) {
-    if (!g) continue;
-    if (static_cast<size_t>(g->M) * g->K * 2 >= (1ull << 32) || static_cast<size_t>(lcBN) * g->K * 2 >= (1ull << 32))
-      return fail(CMH_ERR_INVALID, "gemm (lc): operand of %zu bytes exceeds the 32-bit offset range", static_cast<size_t>(g->M) * g->K * 2);
-  }
+// The launch of a finished plan (gemm.hip: plan_gemm has chosen the form - p.family - its grid and the residual form, and has checked
+// that both problems of a grouped launch agree on it).  b == nullptr: one problem.  The problem with the longer K goes first.
+int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   auto prob = [](const GemmProblem& g) {
     return LcProblem{static_cast<const char*>(g.A), static_cast<const char*>(g.W), g.bias, g.residual, g.out, g.m_dev, g.M, g.N, g.K};
   };
-  auto tiles_of = [](const GemmProblem& g) { return (g.N / lcBN) * ((g.M + lcBM - 1) / lcBM); };
-  const int cus = lc_cus();
-  const int total = tiles_of(a) + (b ? tiles_of(*b) : 0);
-  const int grid = total < cus ? ((total + 7) & ~7) : cus;     // sized for the upper bounds: workgroups without a tile exit at once
+  const int grid = p.grid, res = p.res;
+  const bool f16 = (epi & EPI_OUT_F16) != 0;
   const LcProblem P0 = prob(a), P1 = b ? prob(*b) : LcProblem{};
-  if (form == 3) {      // the 160-row 12-wave form
-    const int grid3 = [&]() {
-      const int t = (a.N / lcBN) * ((a.M + lc3BM - 1) / lc3BM) + (b ? (b->N / lcBN) * ((b->M + lc3BM - 1) / lc3BM) : 0);
-      return t < cus ? ((t + 7) & ~7) : cus;
-    }();
-    const int res3 = !(epi & EPI_RESIDUAL) ? 0 : (gemm_lc_res_first(epi, a.K) ? 1 : 2);
-    const bool f16 = (epi & EPI_OUT_F16) != 0;
-#define LC3_GO(G, R, F)                                                                                                       \
+  // per kernel: grouped or not x five forms - no residual -> bf16 or fp16 output; a residual (the fp16 stream, fp16 output) first or
+  // behind the bias
+#define LC_GO(KERNEL, THREADS, ...)                                                                                           \
   do {                                                                                                                       \
-    if (ev0) hipExtLaunchKernelGGL((gemm_lc3_kernel<G, R, F>), dim3(grid3), dim3(768), 0, st, ev0, ev1, 0, P0, P1, epi);     \
-    else hipLaunchKernelGGL((gemm_lc3_kernel<G, R, F>), dim3(grid3), dim3(768), 0, st, P0, P1, epi);                         \
+    if (ev0) hipExtLaunchKernelGGL((KERNEL<__VA_ARGS__>), dim3(grid), dim3(THREADS), 0, st, ev0, ev1, 0, P0, P1, epi);       \
+    else hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), dim3(grid), dim3(THREADS), 0, st, P0, P1, epi);                           \
   } while (0)
-#define LC3_GO_G(G)                                                                                                           \
+#define LC_GO_G(KERNEL, THREADS, G)                                                                                           \
   do {                                                                                                                       \
-    if (res3 == 1) LC3_GO(G, 1, true);                                                                                       \
-    else if (res3 == 2) LC3_GO(G, 2, true);                                                                                  \
-    else if (f16) LC3_GO(G, 0, true);                                                                                        \
-    else LC3_GO(G, 0, false);                                                                                                \
+    if (res == 1) LC_GO(KERNEL, THREADS, G, 1, true);                                                                        \
+    else if (res == 2) LC_GO(KERNEL, THREADS, G, 2, true);                                                                   \
+    else if (f16) LC_GO(KERNEL, THREADS, G, 0, true);                                                                        \
+    else LC_GO(KERNEL, THREADS, G, 0, false);                                                                                \
   } while (0)
-    if (b) LC3_GO_G(true); else LC3_GO_G(false);
-#undef LC3_GO_G
-#undef LC3_GO
-    CMH_CHECK_LAUNCH("gemm (lc3)");
-    return 0;
-  }
-  if (form == 2) {
-    const int res2 = !(epi & EPI_RESIDUAL) ? 0 : (gemm_lc_res_first(epi, a.K) ? 1 : 2);
-    const bool f16 = (epi & EPI_OUT_F16) != 0;
-#define LC2_GO(G, R, F)                                                                                                       \
-  do {                                                                                                                       \
-    if (ev0) hipExtLaunchKernelGGL((gemm_lc2_kernel<G, R, F>), dim3(grid), dim3(768), 0, st, ev0, ev1, 0, P0, P1, epi);      \
-    else hipLaunchKernelGGL((gemm_lc2_kernel<G, R, F>), dim3(grid), dim3(768), 0, st, P0, P1, epi);                          \
-  } while (0)
-#define LC2_GO_G(G)                                                                                                           \
-  do {                                                                                                                       \
-    if (res2 == 1) LC2_GO(G, 1, true);                                                                                       \
-    else if (res2 == 2) LC2_GO(G, 2, true);                                                                                  \
-    else if (f16) LC2_GO(G, 0, true);                                                                                        \
-    else LC2_GO(G, 0, false);                                                                                                \
-  } while (0)
-    if (b) LC2_GO_G(true); else LC2_GO_G(false);
-#undef LC2_GO_G
-#undef LC2_GO
-    CMH_CHECK_LAUNCH("gemm (lc2)");
-    return 0;
-  }
-  const bool rf = gemm_lc_res_first(epi, a.K);      // (the caller has checked that both problems agree)
-  const bool f16o = (epi & EPI_OUT_F16) != 0;
-#define LC_GO2(G, R, F)                                                                                                      \
-  do {                                                                                                                       \
-    if (ev0) hipExtLaunchKernelGGL((gemm_lc_kernel<G, R, F>), dim3(grid), dim3(512), 0, st, ev0, ev1, 0, P0, P1, epi);       \
-    else hipLaunchKernelGGL((gemm_lc_kernel<G, R, F>), dim3(grid), dim3(512), 0, st, P0, P1, epi);                           \
-  } while (0)
-  // five forms: no residual -> bf16 or fp16 output; a residual (the fp16 stream, fp16 output) first or behind the bias
-  const int res = !(epi & EPI_RESIDUAL) ? 0 : (rf ? 1 : 2);
-#define LC_GO(G, R_unused)                                                                                                   \
-  do {                                                                                                                       \
-    if (res == 1) LC_GO2(G, 1, true);                                                                                        \
-    else if (res == 2) LC_GO2(G, 2, true);                                                                                   \
-    else if (f16o) LC_GO2(G, 0, true);                                                                                       \
-    else LC_GO2(G, 0, false);                                                                                                \
-  } while (0)
+#define LC_GO_ALL(KERNEL, THREADS) do { if (b) LC_GO_G(KERNEL, THREADS, true); else LC_GO_G(KERNEL, THREADS, false); } while (0)
   static const int abl = []() { const char* e = getenv("CMH_LC_ABL"); return e ? atoi(e) : 0; }();
-  if (abl && !b && !rf && !(epi & EPI_OUT_F16)) {      // diagnostic builds of the plain, residual-free, bf16-output form only
-#define LC_GO_A(A)                                                                                                            \
-  do {                                                                                                                       \
-    if (ev0) hipExtLaunchKernelGGL((gemm_lc_kernel<false, 0, false, A>), dim3(grid), dim3(512), 0, st, ev0, ev1, 0, P0, P1, epi); \
-    else hipLaunchKernelGGL((gemm_lc_kernel<false, 0, false, A>), dim3(grid), dim3(512), 0, st, P0, P1, epi);                    \
-  } while (0)
-    if (abl == 1) LC_GO_A(1); else if (abl == 2) LC_GO_A(2); else if (abl == 3) LC_GO_A(3); else LC_GO_A(4);
-#undef LC_GO_A
+  if (p.family == GEMM_LC3) {      // the 160-row 12-wave form
+    LC_GO_ALL(gemm_lc3_kernel, 768);
+    CMH_CHECK_LAUNCH("gemm (lc3)");
+  } else if (p.family == GEMM_LC2) {
+    LC_GO_ALL(gemm_lc2_kernel, 768);
+    CMH_CHECK_LAUNCH("gemm (lc2)");
+  } else if (abl && !b && res != 1 && !f16) {      // diagnostic builds of the plain, residual-free, bf16-output form only
+    if (abl == 1) LC_GO(gemm_lc_kernel, 512, false, 0, false, 1);
+    else if (abl == 2) LC_GO(gemm_lc_kernel, 512, false, 0, false, 2);
+    else if (abl == 3) LC_GO(gemm_lc_kernel, 512, false, 0, false, 3);
+    else LC_GO(gemm_lc_kernel, 512, false, 0, false, 4);
     CMH_CHECK_LAUNCH("gemm (lc, diagnostic)");
-    return 0;
+  } else {
+    LC_GO_ALL(gemm_lc_kernel, 512);
+    CMH_CHECK_LAUNCH("gemm (lc)");
   }
-  if (b) { if (rf) LC_GO(true, true); else LC_GO(true, false); }
-  else { if (rf) LC_GO(false, true); else LC_GO(false, false); }
+#undef LC_GO_ALL
+#undef LC_GO_G
 #undef LC_GO
-#undef LC_GO2
-  CMH_CHECK_LAUNCH("gemm (lc)");
   return 0;
 }
 
@@ -1747,7 +1630,7 @@ extern "C" int cmh_debug_lc_stamps(unsigned long long* host_out) {
 #endif
 
 extern "C" int cmh_set_gemm_lc(int32_t mode) {
-  CMH_CHECK_ARG(mode >= -1 && mode <= 9 && mode != 5 && mode != 6, "set_gemm_lc: mode %d (-1 environment, 0 the wide kernel only, 1 every eligible launch, 2 all but QuickGELU launches, 3 by cost model, 4 the 12-wave 128-row form for every block launch, 7 fp8 QKV, 8 per-launch route (default), 9 the 12-wave 160-row form for every block launch)", mode);
+  CMH_CHECK_ARG(mode >= -1 && mode <= 9 && mode != 5 && mode != 6, "set_gemm_lc: mode %d (-1 environment, 0 the wide kernel only, 1 / 2 / 3 the 8-wave kernel for every eligible launch - 2: all but QuickGELU launches, 4 the 12-wave 128-row form for every block launch, 7 fp8 QKV, 8 per launch the 12-wave 160-row form or the wide kernel, by cost (default), 9 the 12-wave 160-row form for every block launch)", mode);
   cmh::gemm_lc_set_mode(mode);
   return CMH_OK;
 }

@@ -246,34 +246,24 @@ bool gemm_rows_takes(int M, int N, int K, int epi) {
   // tiles the same launch fills the chip (configs[0]: validation -10 %, training step -1..3 %; CMH_GEMM_ROWS_MAX_M to compare)
   static const int max_m = []() { const char* e = getenv("CMH_GEMM_ROWS_MAX_M"); return e ? atoi(e) : 2048; }();
   if (off || M > max_m || N % rT != 0) return false;
-  if (epi & (EPI_MUL_DQGELU | EPI_SAVE_PRE | 256 | 512)) return false;   // (EPI_SCALE / EPI_OUT_FP8: the e4m3 instantiation, launch_gemm_rows_fp8)
+  if (epi & (EPI_MUL_DQGELU | EPI_SAVE_PRE | 256 | 512)) return false;   // (EPI_SCALE / EPI_OUT_FP8: the e4m3 instantiation)
   if ((epi & EPI_OUT_F16) && (epi & EPI_OUT_BF16)) return false;
   (void)K;
   return true;
 }
 
-int launch_gemm_rows(int dt, const void* A, const void* W, const float* bias, const float* residual, void* out, int M, int N, int K,
-                     int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  const int grid = (N / rT) * ((M + rT - 1) / rT);
+int launch_gemm_rows(int dt, const GemmProblem& g, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
 #define R_GO(KERNEL)                                                                                                         \
   do {                                                                                                                        \
     if (ev0)                                                                                                                  \
-      hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, st, ev0, ev1, 0, static_cast<const char*>(A),                    \
-                            static_cast<const char*>(W), bias, residual, out, M, N, K, epi, sc);                              \
+      hipExtLaunchKernelGGL(KERNEL, dim3(p.grid), dim3(256), 0, st, ev0, ev1, 0, static_cast<const char*>(g.A),                \
+                            static_cast<const char*>(g.W), g.bias, g.residual, g.out, g.M, g.N, g.K, epi, sc);                \
     else                                                                                                                      \
-      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, st, static_cast<const char*>(A), static_cast<const char*>(W), bias, \
-                         residual, out, M, N, K, epi, sc);                                                                    \
+      hipLaunchKernelGGL(KERNEL, dim3(p.grid), dim3(256), 0, st, static_cast<const char*>(g.A), static_cast<const char*>(g.W), \
+                         g.bias, g.residual, g.out, g.M, g.N, g.K, epi, sc);                                                  \
   } while (0)
-  const RowsScales sc{nullptr, 1.f, 1.f};
-  if (dt == CMH_F32) R_GO(gemm_rows_kernel<0>); else R_GO(gemm_rows_kernel<1>);
-  return 0;
-}
-
-int launch_gemm_rows_fp8(const void* A, const void* W, const float* colscale, float alpha, const float* bias, const float* residual,
-                         void* out, float oscale, int M, int N, int K, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  const int grid = (N / rT) * ((M + rT - 1) / rT);
-  const RowsScales sc{colscale, alpha, oscale};
-  R_GO(gemm_rows_kernel<2>);
+  const RowsScales sc{g.colscale, g.alpha, g.oscale};      // (f32 / bf16 operands: none, 1, 1)
+  if (dt == CMH_F32) R_GO(gemm_rows_kernel<0>); else if (dt == CMH_BF16) R_GO(gemm_rows_kernel<1>); else R_GO(gemm_rows_kernel<2>);
 #undef R_GO
   return 0;
 }

@@ -229,7 +229,7 @@ __device__ __forceinline__ void gemm_wide_body(const char* __restrict__ X, const
   // Infinity Cache once per round (round 1: 4.4x read amplification on the QKV / c_fc shapes).  Order: bands of `band` m-tiles
   // (one band ~ one XCD's share), inside a band groups of G n-panels, inside a group m-tile-major: an XCD's concurrent tiles share
   // G W panels (<= 1.6 MB) and its band's X tiles (~2.5 MB), and the next group re-reads only the X tiles, still in L2.
-  // (ordG = n-panels per group, chosen by the host: wide_order_group(); 0 = the plain n-fastest order, for A/B runs)
+  // (ordG = n-panels per group, chosen by the host: gemm_order_group(); 0 = the plain n-fastest order, for A/B runs)
   const int band = (tiles_m + 7) >> 3;
   auto tile_coords = [&](int logical, int& tm, int& tn) {
     if (ordG == 0) { tm = logical / tiles_n; tn = logical - tm * tiles_n; return; }
@@ -871,7 +871,7 @@ __device__ __forceinline__ void gemm_wide_body(const char* __restrict__ X, const
     };
     int kt_first = 0;
     if constexpr (DGE) {
-      // straight-line: the first 8 K-steps of a tile that follows a deferred one carry its pieces (nk >= 8: wide_dge_applies)
+      // straight-line: the first 8 K-steps of a tile that follows a deferred one carry its pieces (nk >= 8: gemm.hip, dge_applies)
       if (pend_valid) {
         kstep_dge(std::integral_constant<int, 0>{}); kstep_dge(std::integral_constant<int, 1>{});
         kstep_dge(std::integral_constant<int, 2>{}); kstep_dge(std::integral_constant<int, 3>{});
@@ -1096,7 +1096,7 @@ __device__ __forceinline__ void gemm_wide_body(const char* __restrict__ X, const
       }
     }
     if constexpr (DGE) {
-      // ---- deferred QuickGELU: epi = [bias] + QuickGELU [+ the saved pre-activation] + 16-bit output, nothing else (wide_dge_applies).  The pre-activations move to
+      // ---- deferred QuickGELU: epi = [bias] + QuickGELU [+ the saved pre-activation] + 16-bit output, nothing else (gemm.hip: dge_applies).  The pre-activations move to
       // pendf - the accumulators are free for the next tile at once; a workgroup's last tile and partial tiles finish here.
       {
         w_f32x4_t bv[4];
@@ -1389,36 +1389,6 @@ __global__ __launch_bounds__(512) void gemm_wide_tn_multi_kernel(TnMulti tab) {
 
 bool gemm_wide_supported(int N) { return N % wBN == 0; }
 
-// bench.py's roofline leg (cmh_prof_gemm_*): when launch_gemm hands over an event pair, the forward launch goes through
-// hipExtLaunchKernelGGL, which stamps the events with the DISPATCH's own begin / end (what rocprofv3's kernel trace reports),
-// instead of bracketing the launch with two hipEventRecord marker packets (those add the inter-packet gaps to every launch).
-static hipEvent_t g_wide_ev0 = nullptr, g_wide_ev1 = nullptr;
-void gemm_wide_time_next(hipEvent_t start, hipEvent_t stop) { g_wide_ev0 = start; g_wide_ev1 = stop; }
-// gemm_lc.hip: the loader / consumer form of this GEMM (round 5): same bits, other wave roles
-int gemm_lc_mode();
-bool gemm_lc_takes(int dt, int N, int K, int epi);
-bool gemm_lc_res_first(int epi, int K);
-int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int form);
-int gemm_lc_form(int dt, const GemmProblem& a, const GemmProblem* b, int epi, long long wide_cost);
-bool g_force_rows_set();
-int launch_gemm_lc2q(const GemmProblem& g, int epi, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-bool gemm_lc2q_takes(int N, int K, int epi);
-static bool wide_goes_lc(int dt, int epi) {
-  const int mode = gemm_lc_mode();
-  if (mode == 0 || mode == 7 || g_force_rows_set()) return false;
-  if (mode == 2 && (epi & EPI_QUICKGELU)) return false;
-  return dt == CMH_BF16;
-}
-#define W_GO(KERNEL, GRID, ST, ...)                                                                              \
-  do {                                                                                                          \
-    if (g_wide_ev0) {                                                                                           \
-      hipExtLaunchKernelGGL(KERNEL, dim3(GRID), dim3(512), 0, ST, g_wide_ev0, g_wide_ev1, 0, __VA_ARGS__);      \
-      g_wide_ev0 = g_wide_ev1 = nullptr;                                                                        \
-    } else {                                                                                                    \
-      hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(512), 0, ST, __VA_ARGS__);                                    \
-    }                                                                                                           \
-  } while (0)
-
 // out[i] = sum_s partial[s * n + i]
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ partial, int S, size_t n, float* __restrict__ out) {
   const size_t n4 = n / 4;
@@ -1443,55 +1413,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(ReduceJobs J) 
   }
 }
 
-// Tuning overrides (cmh_gemm_tuning; initial values from CMH_GEMM_BM / CMH_GEMM_ORDER): -1 = decided per launch
-static int g_force_rows = []() { const char* e = getenv("CMH_GEMM_BM"); return e ? atoi(e) : -1; }();
-bool g_force_rows_set() { return g_force_rows > 0; }      // a pinned tile height names the wide kernel's own variants
-static int g_force_order = []() { const char* e = getenv("CMH_GEMM_ORDER"); return e ? atoi(e) : -1; }();
-
-// Deferred QuickGELU (template parameter DGE): which launches take it, and what the activation costs a tile switch in the cost
-// models below, in K-steps (tools/gemm_tile_cost.py: switch 1.70 / 1.77 / 2.19 us with a bias epilogue, 3.02 / 3.40 / 5.04 us with
-// QuickGELU at 96 / 128 / 160 rows, K-steps of 0.68 / 0.80 / 0.96 us).  CMH_GEMM_DGE=0 turns the variant off (A/B runs).
-static bool wide_dge_enabled() {
-  static const bool off = []() { const char* e = getenv("CMH_GEMM_DGE"); return e && e[0] == '0'; }();
-  return !off;
-}
-static bool wide_dge_applies(int dt, int epi, int mf, int kmin) {   // kmin: the shortest K of the launch - a tile's 8 pieces need 8 K-steps of the next
-  return wide_dge_enabled() && dt == CMH_BF16 && mf == 4 && kmin >= 8 * 64 && (epi & EPI_QUICKGELU) && (epi & (EPI_OUT_BF16 | EPI_OUT_F16)) &&
-         !(epi & ~(EPI_BIAS | EPI_QUICKGELU | EPI_OUT_BF16 | EPI_OUT_F16 | EPI_SAVE_PRE)) && (!(epi & EPI_SAVE_PRE) || (epi & EPI_OUT_BF16));
-}
-static int wide_gelu_ksteps(int dt, int epi, int mf, int kmin) {
-  if (!(epi & EPI_QUICKGELU) || wide_dge_applies(dt, epi, mf, kmin)) return 0;
-  return mf == 5 ? 3 : 2;
-}
-
-// n-panels per group of the tile order (see tile_coords in the kernel); 0 = the n-fastest order
-static int wide_order_group(int N) {
-  // Round 2 (tools/gemm_bench2.py + bench.py A/B on one box): GROUPS of 3-4 panels inside each XCD's band of m-tiles (ordG 1..64) are
-  // +6 % on a back-to-back chain of a block's four GEMMs but -6 ... -10 % on the QKV / c_fc launches INSIDE the encoder (an X tile
-  // is re-read once per group, after the outputs have passed through the L2): never the default.
-  // Round 4: panel BLOCKS outermost (ordG >= 100, see tile_coords): 2 blocks for 4..11 panels, 3 from 12 on.  Fabric reads per launch
-  // 116 -> 90 MB (QKV, N = 2304) and 185 -> 114 MB (c_fc, N = 3072), L2 hit rate 68-72 -> 76 % - and the SAME launch duration to
-  // +-1 % (profiles/r04_d_gemm_nblocked_order_ab.txt, r04_d_gemm_nblocked_order_traffic.txt): the K loop does not wait on L2 misses.
-  // It is the default for the traffic it saves the other tower's kernels (+0.4 % on the two-stream step, A/B/A/B on one box).
-  const int tn = N / wBN;
-  auto blocked = [&](int nb) { return tn >= 2 * nb ? 100 + (tn + nb - 1) / nb : 0; };
-  if (g_force_order <= -2) return blocked(-g_force_order);     // -NB: the n-blocked order with NB panel blocks
-  if (g_force_order >= 0) return g_force_order;                 // 0: plain n-fastest; 1..64: round 2's panel groups
-  return tn >= 12 ? blocked(3) : (tn >= 4 ? blocked(2) : 0);
-}
-
-static int wide_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus < 8) cus = 256;
-    cus &= ~7;   // whole groups of 8: blockIdx % 8 names the XCD share
-  }
-  return cus;
-}
-
 // Split-K plan for out[M,N] f32 = A.W^T with few tiles and a long K (the wgrad GEMMs): the largest S that divides the K-steps
 // and keeps tiles * S within one round of workgroups.  Returns 1 when splitting does not pay.
 int gemm_wide_splitk_plan(int dt, int M, int N, int K) {
@@ -1499,7 +1420,7 @@ int gemm_wide_splitk_plan(int dt, int M, int N, int K) {
   const int nk = K / (dt == CMH_F32 ? 32 : 64);
   const int tiles = (N / wBN) * ((M + wBM - 1) / wBM);
   int best = 1;
-  for (int s = 2; s <= 64 && tiles * s <= wide_cus(); ++s)
+  for (int s = 2; s <= 64 && tiles * s <= gemm_cus(); ++s)
     if (nk % s == 0 && nk / s >= 8) best = s;
   return best;
 }
@@ -1508,14 +1429,14 @@ int gemm_wide_splitk_plan(int dt, int M, int N, int K) {
 int launch_gemm_wide_splitk(int dt, const void* A, const void* W, float* out, float* partials, int S, int M, int N, int K,
                             hipStream_t st) {
   const int total = (N / wBN) * ((M + wBM - 1) / wBM) * S;
-  const int cus = wide_cus();
+  const int cus = gemm_cus();
   const int grid = total < cus ? ((total + 7) & ~7) : cus;
   if (dt == CMH_F32)
     hipLaunchKernelGGL((gemm_wide_kernel<0, 0, 5>), dim3(grid), dim3(512), 0, st, static_cast<const char*>(A),
-                       static_cast<const char*>(W), nullptr, nullptr, partials, M, N, K, 0, S, wide_order_group(N), WideScales{nullptr, 1.f, 1.f, 0, nullptr, nullptr}, WideProblem{});
+                       static_cast<const char*>(W), nullptr, nullptr, partials, M, N, K, 0, S, gemm_order_group(N), WideScales{nullptr, 1.f, 1.f, 0, nullptr, nullptr}, WideProblem{});
   else
     hipLaunchKernelGGL((gemm_wide_kernel<1, 0, 5>), dim3(grid), dim3(512), 0, st, static_cast<const char*>(A),
-                       static_cast<const char*>(W), nullptr, nullptr, partials, M, N, K, 0, S, wide_order_group(N), WideScales{nullptr, 1.f, 1.f, 0, nullptr, nullptr}, WideProblem{});
+                       static_cast<const char*>(W), nullptr, nullptr, partials, M, N, K, 0, S, gemm_order_group(N), WideScales{nullptr, 1.f, 1.f, 0, nullptr, nullptr}, WideProblem{});
   const size_t n = static_cast<size_t>(M) * N;
   const size_t blocks = (n / 4 + 255) / 256;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(static_cast<unsigned>(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, partials, S, n, out);
@@ -1535,7 +1456,7 @@ bool gemm_wide_tn_supported(int Mm, int Nn, int Kd) {
 int launch_gemm_wide_tn(const void* Xk, const void* Wk, float* out, float* partials, size_t part_bytes, int Mm, int Nn, int Kd,
                         hipStream_t st, float* colsum_partial, int* colsum_slices) {
   if (!gemm_wide_tn_supported(Mm, Nn, Kd)) return fail(CMH_ERR_INVALID, "gemm_tn: unsupported shape Mm=%d Nn=%d Kd=%d", Mm, Nn, Kd);
-  const int cus = wide_cus();
+  const int cus = gemm_cus();
   const int tiles = (Nn / wBN) * (Mm / 128);
   const int nkt = (Kd + 63) / 64;
   int S = cus / tiles;
@@ -1576,11 +1497,11 @@ bool gemm_wide_tn_multi_fits(const TnMultiJob* jobs, int n) {
     if (!gemm_wide_tn_supported(jobs[i].Mm, jobs[i].Nn, jobs[i].Kd) || jobs[i].Kd < 8 * 64) return false;
     tiles += (jobs[i].Nn / wBN) * (jobs[i].Mm / 128);
   }
-  return tiles <= wide_cus();
+  return tiles <= gemm_cus();
 }
 int launch_gemm_wide_tn_multi(const TnMultiJob* jobs, int n, float* partials, size_t part_bytes, hipStream_t st, int* slices) {
   if (n < 1 || n > 4) return fail(CMH_ERR_INVALID, "gemm_tn_multi: %d jobs", n);
-  const int cus = wide_cus();
+  const int cus = gemm_cus();
   int tiles = 0, min_nkt = 1 << 30;
   for (int i = 0; i < n; ++i) {
     if (!gemm_wide_tn_supported(jobs[i].Mm, jobs[i].Nn, jobs[i].Kd))
@@ -1638,258 +1559,55 @@ int launch_gemm_wide_tn_multi(const TnMultiJob* jobs, int n, float* partials, si
   return 0;
 }
 
-static long long wide_plain_cost(int dt, const GemmProblem& g, int epi, int cus);
-static int wide_route(int dt, const GemmProblem& a, const GemmProblem* b, int epi);
-int launch_gemm_wide(int dt, const void* A, const void* W, const float* bias, const float* residual, void* out,
-                     int M, int N, int K, int epi, hipStream_t st, const float* colscale, float alpha, float oscale,
-                     const int32_t* m_dev, int m_hint) {
-  {
-    const GemmProblem g{A, W, bias, residual, out, M, N, K, m_dev, m_hint, nullptr, 1.f, 1.f};
-    const int form = wide_route(dt, g, nullptr, epi);
-    if (form) {
-      const int rc = launch_gemm_lc(g, nullptr, epi, st, g_wide_ev0, g_wide_ev1, form);
-      g_wide_ev0 = g_wide_ev1 = nullptr;
-      return rc;
-    }
-  }
-  if (dt == CMH_FP8 && !g_force_rows_set() && gemm_lc2q_takes(N, K, epi)) {      // the 12-wave form on e4m3 operands (experiment, CMH_GEMM_LC=7)
-    const GemmProblem g{A, W, bias, residual, out, M, N, K, m_dev, m_hint, colscale, alpha, oscale};
-    const int rc = launch_gemm_lc2q(g, epi, st, g_wide_ev0, g_wide_ev1);
-    g_wide_ev0 = g_wide_ev1 = nullptr;
-    return rc;
-  }
-  const WideScales sc{colscale, alpha, oscale, 0, nullptr, m_dev};
-  const size_t esz = dt == CMH_F32 ? 4 : (dt == CMH_FP8 ? 1 : 2);
-  if (static_cast<size_t>(M) * K * esz >= (1ull << 32) || static_cast<size_t>(wBN) * K * esz >= (1ull << 32))
-    return fail(CMH_ERR_INVALID, "gemm: operand of %zu bytes exceeds the 32-bit offset range of the wide kernel",
-                static_cast<size_t>(M) * K * esz);
-  // Tile rows: 160 (MF = 5), 128 (MF = 4) or 96 (MF = 3), whichever needs less time for this M on the chip's CUs: rounds of
-  // workgroups x (K-steps + ~4 K-steps of per-tile overhead) x (rows + a share that does not shrink with the tile).  M = 12 800 /
-  // 19 712 (the dense towers) take 160; the packed text rows (M ~ 10 k) take 128 at N = 1536 / 2048 and 96 at N = 512, where one
-  // round of 220 tiles keeps 86 % of the CUs busy instead of 65 % (166 tiles of 128 rows).  CMH_GEMM_BM=96|128|160 forces one.
-  const int cus = wide_cus();
-  const int nk = K / (dt == CMH_F32 ? 32 : (dt == CMH_FP8 ? 128 : 64));
-  const int Mc = m_dev && m_hint > 0 && m_hint <= M ? m_hint : M;   // the tile height is chosen for the likely row count
-  auto cost = [&](int mf) {   // rounds x (rows + the per-K-step cost that does not shrink with the tile: W fragment reads, barrier) x K-steps
-    const int tiles = (N / wBN) * ((Mc + 32 * mf - 1) / (32 * mf));
-    return static_cast<long long>((tiles + cus - 1) / cus) * (10 * mf + 6) * (nk + 4 + wide_gelu_ksteps(dt, epi, mf, K));
-  };
-  const int forced = g_force_rows;
-  // fp8: 160 rows by default only with e4m3 OUTPUT (the c_fc launches).  The 160-row variant needs 56 fragment registers live across the epilogue
-  // (both 16-byte halves of the next K-step's operands, as aligned 8-register MFMA operands) next to 80 accumulators and the pending
-  // stores; left alone hipcc spills inside the K loop (scratch reloads with vmcnt(0) drain the LDS-DMA pipeline: measured 64 us
-  // against bf16's 46 on QKV).  With the epilogue paths fp8 never takes compiled out, the residual loads in two groups and - for the
-  // 16-bit outputs - only 4 of the 10 stores deferred, the K loops of the e4m3- and 16-bit-output variants are free of scratch
-  // (tools/asm_loop_scratch.py: every variant a launch can select must show no scratch at loop depth 2).
-  // (the f32-output fp8 variant still spills in its K loop; the 16-bit-output one is loop-clean but pays 28 scratch instructions per
-  // tile in its epilogue: serialized GEMM time of an fp8 step -1.3 %, the overlapped step -1.5 % in pairs/s, A/B/A/B on one box - so
-  // it is taken only on request, CMH_GEMM_BM=160 / cmh_gemm_tuning)
-  const bool fp8_160 = epi & (EPI_OUT_FP8 | EPI_OUT_BF16 | EPI_OUT_F16);
-  int mf = dt == CMH_FP8 && !(epi & EPI_OUT_FP8) ? 4 : 5;
-  if (mf == 5 && cost(4) < cost(mf)) mf = 4;
-  if (cost(3) < cost(mf)) mf = 3;
-  if (forced == 96 || forced == 128 || (forced == 160 && (dt != CMH_FP8 || fp8_160))) mf = forced / 32;
-  const int total = (N / wBN) * ((M + 32 * mf - 1) / (32 * mf));
-  int grid = total < cus ? ((total + 7) & ~7) : cus;
-  const int ordg = wide_order_group(N);
-#define W_LAUNCH(DT, OK)                                                                                                  \
-  do {                                                                                                                    \
-    if (mf == 3)                                                                                                          \
-      W_GO((gemm_wide_kernel<DT, OK, 3>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,       \
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});                                                                     \
-    else if (mf == 4)                                                                                                     \
-      W_GO((gemm_wide_kernel<DT, OK, 4>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,       \
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});                                                                     \
-    else                                                                                                                  \
-      W_GO((gemm_wide_kernel<DT, OK, 5>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,       \
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});                                                                     \
+// The forward launch of a finished plan (gemm.hip: plan_gemm has chosen the tile rows, the grid, the tile order and the deferred-
+// QuickGELU variant, and has checked the shapes): one problem, or two in one persistent grid (template parameter GRP; see
+// WideProblem) - `a` the problem with the longer K (its tiles go first), both sharing dt, the output kind and the epilogue flags.
+// With an event pair the launch goes through hipExtLaunchKernelGGL, which stamps the events with the DISPATCH's own begin / end (what
+// rocprofv3's kernel trace reports), instead of bracketing the launch with two hipEventRecord marker packets (those add the
+// inter-packet gaps to every launch).
+int launch_gemm_wide(int dt, const GemmProblem& a, const GemmProblem* b, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0,
+                     hipEvent_t ev1) {
+  const int mf = p.rows / 32;
+  const WideScales sc{a.colscale, a.alpha, a.oscale, 0, nullptr, a.m_dev};
+  const WideProblem p1 = !b ? WideProblem{}
+                            : WideProblem{static_cast<const char*>(b->A), static_cast<const char*>(b->W), b->bias, b->residual, b->out,
+                                          b->colscale, b->m_dev, b->M, b->N, b->K, b->alpha, b->oscale};
+#define W_GO(...)                                                                                                                       \
+  do {                                                                                                                                  \
+    if (ev0)                                                                                                                            \
+      hipExtLaunchKernelGGL((gemm_wide_kernel<__VA_ARGS__>), dim3(p.grid), dim3(512), 0, st, ev0, ev1, 0, static_cast<const char*>(a.A), \
+                            static_cast<const char*>(a.W), a.bias, a.residual, a.out, a.M, a.N, a.K, epi, 1, p.order, sc, p1);          \
+    else                                                                                                                                \
+      hipLaunchKernelGGL((gemm_wide_kernel<__VA_ARGS__>), dim3(p.grid), dim3(512), 0, st, static_cast<const char*>(a.A),                \
+                         static_cast<const char*>(a.W), a.bias, a.residual, a.out, a.M, a.N, a.K, epi, 1, p.order, sc, p1);             \
   } while (0)
+#define W_GO2(DT, OK, GRP) do { if (mf == 3) W_GO(DT, OK, 3, false, GRP); else W_GO(DT, OK, 4, false, GRP); } while (0)
+#define W_GO3(DT, OK, GRP) do { if (mf == 5) W_GO(DT, OK, 5, false, GRP); else W_GO2(DT, OK, GRP); } while (0)
   const bool obf = epi & (EPI_OUT_BF16 | EPI_OUT_F16);   // 16-bit outputs share the packed store path
   const bool o8 = epi & EPI_OUT_FP8;
-  if (dt == CMH_F32) { if (obf) W_LAUNCH(0, 1); else W_LAUNCH(0, 0); }
-  else if (dt == CMH_BF16) {
-    if (obf && wide_dge_applies(dt, epi, mf, K))
-      W_GO((gemm_wide_kernel<1, 1, 4, false, false, true>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});
-    else if (obf) W_LAUNCH(1, 1);
-    else W_LAUNCH(1, 0);
-  }
-  else {
-#undef W_LAUNCH
-#define W_LAUNCH(DT, OK)                                                                                                  \
-  do {                                                                                                                    \
-    if (mf == 3)                                                                                                          \
-      W_GO((gemm_wide_kernel<DT, OK, 3>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,       \
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});                                                                     \
-    else                                                                                                                  \
-      W_GO((gemm_wide_kernel<DT, OK, 4>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias,       \
-           residual, out, M, N, K, epi, 1, ordg, sc, WideProblem{});                                                                     \
-  } while (0)
-    if (o8) {
-      if (mf == 5)
-        W_GO((gemm_wide_kernel<2, 2, 5>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias, residual, out, M, N,
-             K, epi, 1, ordg, sc, WideProblem{});
-      else
-        W_LAUNCH(2, 2);
-    } else if (obf) {
-      if (mf == 5)
-        W_GO((gemm_wide_kernel<2, 1, 5>), grid, st, static_cast<const char*>(A), static_cast<const char*>(W), bias, residual, out, M, N,
-             K, epi, 1, ordg, sc, WideProblem{});
-      else
-        W_LAUNCH(2, 1);
-    } else {
-      W_LAUNCH(2, 0);
+  if (!b) {
+    if (dt == CMH_F32) { if (obf) W_GO3(0, 1, false); else W_GO3(0, 0, false); }
+    else if (dt == CMH_BF16) {
+      if (p.dge) W_GO(1, 1, 4, false, false, true);
+      else if (obf) W_GO3(1, 1, false);
+      else W_GO3(1, 0, false);
     }
+    else if (o8) W_GO3(2, 2, false);
+    else if (obf) W_GO3(2, 1, false);
+    else W_GO2(2, 0, false);
+  } else {      // (plan_gemm groups f32 operands with f32 outputs, bf16 with 16-bit, fp8 with 16-bit or e4m3 outputs only)
+    if (dt == CMH_F32) W_GO3(0, 0, true);
+    else if (dt == CMH_BF16) { if (p.dge) W_GO(1, 1, 4, false, true, true); else W_GO3(1, 1, true); }
+    else if (o8) W_GO3(2, 2, true);
+    else W_GO2(2, 1, true);
   }
-#undef W_LAUNCH
-  return 0;
-}
-
-// Two problems in one persistent grid (template parameter GRP; see WideProblem).  `a` should be the problem with the longer K (its
-// tiles go first); both share dt, the output kind and the epilogue flags.  The tile height is the one whose WORST workgroup - the
-// kernel's own static assignment, replayed here - finishes first.
-// Does ONE grouped launch beat two plain ones?  The same cost units as the tile-height choice (K-steps + 4 per tile, x rows + 6),
-// the worst workgroup of the kernel's static assignment against the two plain launches' rounds, plus a fixed ~8 K-steps per LAUNCH
-// (first stage landing on every CU at once, last epilogue's store drain: profiles/r02_a_gemm_launch_timeline.txt).  Measured at batch
-// 256 (profiles/r04_b_grouped_per_shape.txt): QKV 74.5 -> 68.8 us, out_proj 41.8 -> 36.9, c_fc 104.8 -> 96.4 grouped - but c_proj 92.0
-// -> 98.3: one 48-K-step image tile per workgroup plus a 32-K-step text tile on every second one is a worse packing than two launches;
-// the model reproduces all four.
-static long long wide_plain_cost(int dt, const GemmProblem& g, int epi, int cus) {
-  const int nk = g.K / (dt == CMH_F32 ? 32 : (dt == CMH_FP8 ? 128 : 64));
-  const int M = g.m_dev && g.m_hint > 0 && g.m_hint <= g.M ? g.m_hint : g.M;
-  long long best = -1;
-  for (int mf = (dt == CMH_FP8 && !(epi & EPI_OUT_FP8)) ? 4 : 5; mf >= 3; --mf) {
-    const int tiles = (g.N / wBN) * ((M + 32 * mf - 1) / (32 * mf));
-    const long long c = static_cast<long long>((tiles + cus - 1) / cus) * (10 * mf + 6) * (nk + 4 + wide_gelu_ksteps(dt, epi, mf, g.K));
-    if (best < 0 || c < best) best = c;
-  }
-  return best;
-}
-static long long wide_grouped_cost(int dt, const GemmProblem& a, const GemmProblem& b, int epi, int cus, int* mf_out);
-
-bool gemm_wide_grouping_pays(int dt, const GemmProblem& a, const GemmProblem& b, int epi) {
-  static const bool always = []() { const char* e = getenv("CMH_GEMM_GROUPED"); return e && !strcmp(e, "always"); }();
-  if (always || g_force_rows > 0) return true;            // (a forced tile height: A/B runs and the tests that walk every variant)
-  const int cus = wide_cus();
-  const long long fixed = 8 * 56;
-  return wide_grouped_cost(dt, a, b, epi, cus, nullptr) + fixed <= wide_plain_cost(dt, a, epi, cus) + wide_plain_cost(dt, b, epi, cus) + 2 * fixed;
-}
-
-static long long wide_grouped_cost(int dt, const GemmProblem& a, const GemmProblem& b, int epi, int cus, int* mf_out) {
-  const int bk = dt == CMH_F32 ? 32 : (dt == CMH_FP8 ? 128 : 64);
-  const int nk0 = a.K / bk, nk1 = b.K / bk;
-  auto likely = [](const GemmProblem& g) { return g.m_dev && g.m_hint > 0 && g.m_hint <= g.M ? g.m_hint : g.M; };
-  const int Ma = likely(a), Mb = likely(b);
-  auto tiles_of = [](int M, int N, int mf) { return (N / wBN) * ((M + 32 * mf - 1) / (32 * mf)); };
-  auto cost = [&](int mf) {
-    const int total = tiles_of(a.M, a.N, mf) + tiles_of(b.M, b.N, mf);
-    const int per = (total < cus ? ((total + 7) & ~7) : cus) >> 3;
-    const int t0 = tiles_of(Ma, a.N, mf), t1 = tiles_of(Mb, b.N, mf);
-    long long worst = 0;
-    for (int x = 0; x < 8; ++x) {
-      const int len0 = (t0 >> 3) + (x < (t0 & 7)), len1 = (t1 >> 3) + (x < (t1 & 7));
-      for (int sl = 0; sl < per; ++sl) {
-        const int n0 = sl < len0 ? (len0 - sl + per - 1) / per : 0;
-        const int nall = sl < len0 + len1 ? (len0 + len1 - sl + per - 1) / per : 0;
-        const int ge = wide_gelu_ksteps(dt, epi, mf, a.K < b.K ? a.K : b.K);
-        const long long c = static_cast<long long>(n0) * (nk0 + 4 + ge) + static_cast<long long>(nall - n0) * (nk1 + 4 + ge);
-        worst = c > worst ? c : worst;
-      }
-    }
-    return worst * (10 * mf + 6);
-  };
-  int mf = dt == CMH_FP8 && !(epi & EPI_OUT_FP8) ? 4 : 5;
-  if (mf == 5 && cost(4) < cost(mf)) mf = 4;
-  if (cost(3) < cost(mf)) mf = 3;
-  if (mf_out) *mf_out = mf;
-  return cost(mf);
-}
-
-// Which kernel takes a launch (b: the second problem of a grouped launch): 0 this file's wide kernel, else the gemm_lc.hip form
-// gemm_lc_form names (1 the 8-wave kernel, 2 the 12-wave 128-row form, 3 the 12-wave 160-row form).  Host-only; cmh_gemm_route
-// asks it without launching.
-static int wide_route(int dt, const GemmProblem& a, const GemmProblem* b, int epi) {
-  if (!wide_goes_lc(dt, epi) || !gemm_lc_takes(dt, a.N, a.K, epi)) return 0;
-  if (!b) return gemm_lc_form(dt, a, nullptr, epi, wide_plain_cost(dt, a, epi, wide_cus()));
-  if (!gemm_lc_takes(dt, b->N, b->K, epi) || gemm_lc_res_first(epi, a.K) != gemm_lc_res_first(epi, b->K)) return 0;
-  return gemm_lc_form(dt, a, b, epi, wide_grouped_cost(dt, a, *b, epi, wide_cus(), nullptr));
-}
-
-int launch_gemm_wide_grouped(int dt, const GemmProblem& a, const GemmProblem& b, int epi, hipStream_t st) {
-  {
-    const int form = wide_route(dt, a, &b, epi);
-    if (form) {
-      const int rc = launch_gemm_lc(a, &b, epi, st, g_wide_ev0, g_wide_ev1, form);
-      g_wide_ev0 = g_wide_ev1 = nullptr;
-      return rc;
-    }
-  }
-  const size_t esz = dt == CMH_F32 ? 4 : (dt == CMH_FP8 ? 1 : 2);
-  for (const GemmProblem* g : {&a, &b})
-    if (static_cast<size_t>(g->M) * g->K * esz >= (1ull << 32) || static_cast<size_t>(wBN) * g->K * esz >= (1ull << 32))
-      return fail(CMH_ERR_INVALID, "gemm (grouped): operand of %zu bytes exceeds the 32-bit offset range of the wide kernel",
-                  static_cast<size_t>(g->M) * g->K * esz);
-  const int cus = wide_cus();
-  auto tiles_of = [](int M, int N, int mf) { return (N / wBN) * ((M + 32 * mf - 1) / (32 * mf)); };
-  auto grid_of = [&](int mf) {   // sized for the upper bounds: workgroups beyond the real tile count exit at once
-    const int total = tiles_of(a.M, a.N, mf) + tiles_of(b.M, b.N, mf);
-    return total < cus ? ((total + 7) & ~7) : cus;
-  };
-  const int forced = g_force_rows;
-  const bool fp8_160 = epi & EPI_OUT_FP8;       // (the 16-bit-output 160-row fp8 variant is an opt-in of the plain launches only)
-  int mf = 5;
-  (void)wide_grouped_cost(dt, a, b, epi, cus, &mf);
-  if (forced == 96 || forced == 128 || (forced == 160 && (dt != CMH_FP8 || fp8_160))) mf = forced / 32;
-  const int grid = grid_of(mf);
-  const WideScales sc{a.colscale, a.alpha, a.oscale, 0, nullptr, a.m_dev};
-  const WideProblem p1{static_cast<const char*>(b.A), static_cast<const char*>(b.W), b.bias, b.residual, b.out, b.colscale, b.m_dev,
-                       b.M, b.N, b.K, b.alpha, b.oscale};
-#define W_LAUNCH_G(DT, OK, MFV)                                                                                            \
-  W_GO((gemm_wide_kernel<DT, OK, MFV, false, true>), grid, st, static_cast<const char*>(a.A), static_cast<const char*>(a.W), a.bias, \
-       a.residual, a.out, a.M, a.N, a.K, epi, 1, 0, sc, p1)
-#define W_LAUNCH_G3(DT, OK)                                                                                                \
-  do { if (mf == 3) W_LAUNCH_G(DT, OK, 3); else if (mf == 4) W_LAUNCH_G(DT, OK, 4); else W_LAUNCH_G(DT, OK, 5); } while (0)
-  const bool obf = epi & (EPI_OUT_BF16 | EPI_OUT_F16);
-  if (dt == CMH_F32) {
-    if (obf) return fail(CMH_ERR_INVALID, "gemm (grouped): f32 operands come with f32 outputs");
-    W_LAUNCH_G3(0, 0);
-  } else if (dt == CMH_BF16) {
-    if (!obf) return fail(CMH_ERR_INVALID, "gemm (grouped): bf16 operands come with 16-bit outputs");
-    if (wide_dge_applies(dt, epi, mf, a.K < b.K ? a.K : b.K))
-      W_GO((gemm_wide_kernel<1, 1, 4, false, true, true>), grid, st, static_cast<const char*>(a.A), static_cast<const char*>(a.W), a.bias,
-           a.residual, a.out, a.M, a.N, a.K, epi, 1, 0, sc, p1);
-    else
-      W_LAUNCH_G3(1, 1);
-  } else if (epi & EPI_OUT_FP8) {
-    W_LAUNCH_G3(2, 2);
-  } else {
-    if (!obf) return fail(CMH_ERR_INVALID, "gemm (grouped): fp8 operands come with 16-bit or e4m3 outputs");
-    if (mf == 3) W_LAUNCH_G(2, 1, 3); else W_LAUNCH_G(2, 1, 4);
-  }
-#undef W_LAUNCH_G3
-#undef W_LAUNCH_G
-  CMH_CHECK_LAUNCH("gemm (grouped)");
+#undef W_GO3
+#undef W_GO2
+#undef W_GO
   return 0;
 }
 
 }  // namespace cmh
-
-extern "C" int cmh_gemm_route(int32_t dt, int32_t Ma, int32_t Na, int32_t Ka, int32_t Mb, int32_t Nb, int32_t Kb, int32_t epi) {
-  using namespace cmh;
-  CMH_CHECK_ARG(Ma > 0 && Na > 0 && Ka > 0 && Mb >= 0, "gemm_route: shape %d x %d x %d / %d rows", Ma, Na, Ka, Mb);
-  const GemmProblem a{nullptr, nullptr, nullptr, nullptr, nullptr, Ma, Na, Ka, nullptr, 0, nullptr, 1.f, 1.f};
-  const GemmProblem b{nullptr, nullptr, nullptr, nullptr, nullptr, Mb, Nb, Kb, nullptr, 0, nullptr, 1.f, 1.f};
-  return wide_route(dt, a, Mb > 0 ? &b : nullptr, epi);
-}
-
-extern "C" int cmh_gemm_tuning(int32_t tile_rows, int32_t order_group) {
-  using namespace cmh;
-  CMH_CHECK_ARG(tile_rows == -1 || tile_rows == 96 || tile_rows == 128 || tile_rows == 160, "gemm_tuning: tile_rows %d (-1, 96, 128, 160)", tile_rows);
-  CMH_CHECK_ARG(order_group >= -8 && order_group <= 64, "gemm_tuning: order_group %d (-8..-2: n-blocked, -1: default, 0: n-fastest, > 0: panel groups)", order_group);
-  g_force_rows = tile_rows;
-  g_force_order = order_group;
-  return CMH_OK;
-}
 
 #ifdef W_TIMELINE
 extern "C" int cmh_debug_wide_timeline(unsigned long long* host_out) {

@@ -250,17 +250,28 @@ int cmh_set_gemm_rows(int32_t on);
 /* Round 5: the loader / consumer form of the N % 256 == 0 GEMM (csrc/gemm_lc.hip: four waves of a workgroup only stage operands by
  * LDS-DMA, the other four only multiply; 128 x 256 tiles; bf16 operands with 16-bit outputs and the forward epilogues of a transformer
  * block: bias, + QuickGELU, + fp16 residual; plain and grouped launches).  Same bits per output element as the wide kernel (same MFMA
- * chain over K, same epilogue order).  mode 0: never; 1: every launch it can take; 2: every such launch without QuickGELU;
- * 3: where the host's cost model expects it to be faster; 4: the 12-wave form (4 staging + 8 MFMA waves, stores deferred, 128-row
+ * chain over K, same epilogue order).  mode 0: never; 1, 2, 3: the 8-wave kernel for every launch it can take (the three differ only
+ * in mode 2 leaving the QuickGELU launches to the wide kernel); 4: the 12-wave form (4 staging + 8 MFMA waves, stores deferred, 128-row
  * tiles) for every block launch with K >= 512, the wide kernel elsewhere; 7: the form on e4m3 operands (fp8 QKV launches);
- * 8: per bf16 launch, whichever of the wide kernel, the 12-wave 128-row form and the 12-wave 160-row form the cost model prices lowest;
- * 9: the 12-wave 160-row form for every block launch with K >= 512; -1: the environment's CMH_GEMM_LC (default; unset = 8,
- * CMH_GEMM_LC=0 = the wide kernel only).  Process-wide, not thread-safe. */
+ * 8: per bf16 launch without a residual, the 12-wave 160-row form where the host's cost model prices it below the wide kernel, the
+ * wide kernel elsewhere (the 128-row form is never picked); 9: the 12-wave 160-row form for every block launch with K >= 512;
+ * -1: the environment's CMH_GEMM_LC (default; unset = 8, CMH_GEMM_LC=0 = the wide kernel only).  Process-wide, not thread-safe. */
 int cmh_set_gemm_lc(int32_t mode);
 /* Which kernel the current cmh_set_gemm_lc mode gives a launch of operand type dt (CMH_BF16, ...) and epilogue flags epi:
  * Ma x Na x Ka alone (Mb = 0) or grouped with Mb x Nb x Kb.  0 the wide kernel, 1 the 8-wave loader / consumer kernel, 2 the
  * 12-wave 128-row form, 3 the 12-wave 160-row form.  Host-only: nothing is launched.  Returns -1 on a bad shape. */
 int cmh_gemm_route(int32_t dt, int32_t Ma, int32_t Na, int32_t Ka, int32_t Mb, int32_t Nb, int32_t Kb, int32_t epi);
+/* The whole plan of a GEMM request under the current switches, as the launch path itself computes it (csrc/gemm.hip: plan_gemm).
+ * Host-only: nothing is launched, no GPU is needed (256 CUs are assumed without one).  dt: CMH_F32 / CMH_BF16 / CMH_FP8; epi: the
+ * epilogue flags; a5 / b5: {M, N, K, device-side row count present (0 / 1), its hint (<= 0: none)} of the problem, b5 the second
+ * problem of a grouped request or NULL.  out16: [0] launches - 1, or 2 when the grouped request runs as two plain launches, a then b;
+ * [1] what cmh_gemm_route returns for the same shapes (the loader / consumer form of the route step alone: no row counts, before the
+ * few-row kernel and the grouping decision); then 7 integers per launch ([2..8], and [9..15] for the second of two): kernel family
+ * (0 gemm_wide_kernel, 1 gemm_rows_kernel, 2 the 128 x 128 fallback, 3 the 8-wave loader / consumer kernel, 4 its 12-wave 128-row
+ * form, 5 its 12-wave 160-row form, 6 the 12-wave form on e4m3 operands), tile rows, grid (workgroups), tile-order group, deferred
+ * QuickGELU (0 / 1), residual form (0 none, 1 first, 2 behind the bias), grouped (1: both problems in this launch).  Returns what the
+ * launch would return for a bad shape or flag combination (operand pointers are not part of the plan). */
+int cmh_gemm_plan(int32_t dt, int32_t epi, const int32_t* a5, const int32_t* b5, int32_t* out16);
 
 /* encode_image / encode_text return one pooled row per sample (model/base/model.py:247-250, 366-370), and past the last block's
  * attention every operation is row-wise, so cmh_vit_encode / cmh_text_encode[_packed] carry only those B rows through the last
