@@ -150,6 +150,7 @@ SIGNATURES = {
     "cmh_hamming_topk_graded": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
+    "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
     "cmh_dchmt_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -724,6 +725,8 @@ def hamming_topk(q_planes, r_planes, bits, k, q_lab=None, r_lab=None, want_count
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte
+TOPK_MAX = 524287            # include/cmh.h CMH_TOPK_MAX: the largest N (and k) of the four retrieval entry points
+QUERIES_MAX = 65535          # ... and their largest Q
 
 
 def _grade_classes(what, classes, LW):
@@ -776,6 +779,58 @@ def label_overlap_hist(q_lab, r_lab, classes):
     check(lib().cmh_label_overlap_hist(ptr(q_lab), ptr(r_lab), Q, N, classes, ptr(out), ptr(ws), ws.numel(), stream_ptr(dev)),
           "cmh_label_overlap_hist")
     return out
+
+
+def _topk_list(what, name, lst, Q=None):
+    if not isinstance(lst, (tuple, list)) or len(lst) != 3:
+        raise NativeError(f"{what}: {name} is an (idx, dist, tag or None) tuple")
+    idx, dist, tag = lst
+    if idx is None or dist is None or idx.dim() != 2:
+        raise NativeError(f"{what}: {name} needs idx and dist of shape [Q, k]")
+    require_gpu(idx, dist, tag)
+    rows, width = idx.shape
+    fit(what, (idx, (rows if Q is None else Q, width)), (dist, (idx.shape[0], width)), (tag, (idx.shape[0], width)))
+    for t, dt in ((idx, torch.int32), (dist, torch.float32), (tag, torch.uint8)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise NativeError(f"{what}: {name} holds contiguous int32 idx, float32 dist and uint8 tag tensors")
+    return idx, dist, tag, rows, width
+
+
+def topk_merge(a, b, b_base, k, out=None):
+    """Two top-k lists of the same queries, a = (idx int32 [Q, ka], dist f32 [Q, ka], tag uint8 [Q, ka] or None) and b likewise
+    with its own width kb -> (idx int32 [Q, k], dist f32 [Q, k], tag uint8 [Q, k] or None): the first k entries of their union in
+    the order of hamming_topk.  Rows are ascending by (dist, idx); b's indices are local to a shard that starts at item b_base,
+    behind every item of a, and come out as idx + b_base.  tag = the hit flags or the grades that travel with the entries: on both
+    lists or on neither.  1 <= k <= ka + kb.  out: (idx, dist, tag) of the output's shape to write into in place of
+    fresh ones (what lets a fold over many shards reuse two buffers); their bytes overlap neither a's nor b's nor each other's."""
+    a_idx, a_dist, a_tag, Q, ka = _topk_list("topk_merge", "a", a)
+    b_idx, b_dist, b_tag, _, kb = _topk_list("topk_merge", "b", b, Q)
+    if (a_tag is None) != (b_tag is None):
+        raise NativeError("topk_merge: tags on one list only")
+    k, b_base = int(k), int(b_base)
+    if Q < 1 or ka < 1 or kb < 1 or not 1 <= k <= ka + kb:
+        raise NativeError(f"topk_merge: k={k} outside [1, ka + kb = {ka + kb}] (Q={Q}, ka={ka}, kb={kb})")
+    if not 0 <= b_base <= 2 ** 31 - 1 - kb:
+        raise NativeError(f"topk_merge: b_base={b_base} outside [0, 2^31 - 1 - kb]")
+    dev = a_idx.device
+    if out is None:
+        idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        tag = torch.empty(Q, k, dtype=torch.uint8, device=dev) if a_tag is not None else None
+    else:
+        idx, dist, tag, _, _ = _topk_list("topk_merge", "out", out, Q)
+        fit("topk_merge", (idx, (Q, k)))
+        if (tag is None) != (a_tag is None):
+            raise NativeError("topk_merge: out carries tags exactly when the lists do")
+        span = lambda t: (t.data_ptr(), t.data_ptr() + t.numel() * t.element_size())      # contiguous: the bytes it covers
+        ins = [span(t) for t in (a_idx, a_dist, a_tag, b_idx, b_dist, b_tag) if t is not None]
+        outs = [span(t) for t in (idx, dist, tag) if t is not None]
+        if any(o[0] < i[1] and i[0] < o[1] for o in outs for i in ins) or any(
+                outs[x][0] < outs[y][1] and outs[y][0] < outs[x][1] for x in range(len(outs)) for y in range(x)):
+            raise NativeError("topk_merge: out must not overlap a, b or itself")
+    check(lib().cmh_topk_merge(ptr(a_idx), ptr(a_dist), ptr(a_tag), ka, ptr(b_idx), ptr(b_dist), ptr(b_tag), kb, b_base, Q, k,
+                               ptr(idx), ptr(dist), ptr(tag), stream_ptr(dev)), "cmh_topk_merge")
+    return idx, dist, tag
 
 
 # ------------------------------------------------------------------------------------------ losses

@@ -5,7 +5,13 @@
 
 prints one line per query: its number, then `index:distance` (`index:distance:hit` when the file has labels) for the k nearest
 database items, nearest first, ties by database index.  With --graded the third field is the number of labels the neighbour shares
-with the query (0 = no hit) instead of the 0/1 flag."""
+with the query (0 = no hit) instead of the 0/1 flag.
+
+    python retrieve.py --codes <file>.mat --index db.npz --direction i2t --k 10
+
+searches a saved CodeIndex (CodeIndex.save: any number of items, grown by CodeIndex.add) in place of the .mat's database side; the
+.mat still supplies the queries (the query side of --direction) and their labels.  The database half of --direction is then unused;
+a note on stderr says so when the file holds that side."""
 import argparse
 import sys
 
@@ -18,6 +24,7 @@ def parse(argv=None):
     p.add_argument("--direction", choices=sorted(DIRECTIONS), default="i2t", help="query side -> database side")
     p.add_argument("--k", type=int, default=10, help="neighbours per query")
     p.add_argument("--queries", default=":", help="slice a:b of the file's queries (default: all)")
+    p.add_argument("--index", default="", metavar="FILE", help="a saved CodeIndex (.npz of CodeIndex.save) as the database, in place of the .mat's database side")
     p.add_argument("--graded", action="store_true", help="print the shared-label count of each neighbour in place of the hit flag (needs labels in the file)")
     return p.parse_args(argv)
 
@@ -39,7 +46,12 @@ def main(argv=None):
     q_key, r_key = DIRECTIONS[args.direction]
     m = scio.loadmat(args.codes)
     lo, hi = query_slice(args.queries, m[q_key].shape[0])
-    index = CodeIndex.from_mat(args.codes, side=r_key)
+    index = CodeIndex.load(args.index) if args.index else CodeIndex.from_mat(args.codes, side=r_key)
+    if args.index and r_key in m:
+        print(f"note: --index {args.index} is the database; {r_key} of {args.codes} (--direction {args.direction}) is not searched, "
+              f"only its query side {q_key} is used", file=sys.stderr)
+    if index.bits != m[q_key].shape[1]:
+        raise SystemExit(f"--index {args.index}: {index.bits}-bit codes, the queries of {args.codes} have {m[q_key].shape[1]}")
     queries = torch.from_numpy(m[q_key][lo:hi]).float()
     labels = torch.from_numpy(m["q_l"][lo:hi]).float() if index.labels is not None and "q_l" in m else None
     if args.graded and labels is None:

@@ -23,12 +23,22 @@ calc_neighbor thresholds.  With g_i the grade of the item at position i (1-based
   WAP@n  = (1/R_n) sum_{i<=n, g_i>0} ACG@i,   R_n = #{i <= n : g_i > 0};   WAP@n = 0 if R_n = 0
 Means follow the convention of the curves: over the queries with at least one relevant database item (the others have IDCG = 0).
 graded_topk returns the grades of the neighbours; grade_histogram counts, per query, the database items of every grade (it depends
-on the labels only: one call serves all directions of an evaluation) and is what IDCG is computed from, without sorting anything."""
+on the labels only: one call serves all directions of an evaluation) and is what IDCG is computed from, without sorting anything.
+
+Size.  The native entry points take N <= 524 287 database items and Q <= 65 535 queries per call.  Every function here takes any
+database up to 2^31 - 1 items and any number of queries: the packed planes are row-major, so the database is cut into SHARDS of
+`shard_items` rows (views, packed once), every shard is searched, and the per-shard lists are folded together in ascending shard
+order by cmh_topk_merge (csrc/retrieval_merge.hip), which keeps the order (distance, database index): the result is bit for bit
+what one search over the whole database would give.  Histograms are the int32 sums of the per-shard histograms; queries are cut
+into blocks of QUERIES_MAX rows and the outputs concatenated.  A database and a query set within the limits take exactly the one
+native call they always took.  CodeIndex grows by add() and persists by save() / load()."""
 import torch
 
 import cmh_native as N
 
 DEFAULT_TOPN = (1,) + tuple(range(50, 1001, 50))
+SHARD_ITEMS = N.TOPK_MAX             # database items per shard unless a call says otherwise (tests pass small values)
+ITEMS_MAX = 2 ** 31 - 1              # indices and counts are int32
 
 
 def _dev(*ts):
@@ -50,12 +60,109 @@ def _labels(L, dev):
     return None if L is None else N.pack_labels(L.to(dev).float())
 
 
-def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None):
+def _cuts(n, step):
+    return [(a, min(n, a + step)) for a in range(0, n, step)]
+
+
+def _rows(t, cut, n):
+    """Rows cut[0]:cut[1] of a packed operand of n rows (a tensor, a pair of planes or None): the operand itself when the cut is all
+    of it, else views (a row slice of a contiguous row-major tensor is contiguous: nothing is copied)."""
+    if t is None or cut == (0, n):
+        return t
+    if isinstance(t, tuple):
+        return tuple(x[cut[0]:cut[1]] for x in t)
+    return t[cut[0]:cut[1]]
+
+
+def _plan(what, qp, rp, shard_items):
+    """-> (Q, n, query blocks, database shards) as lists of (begin, end)."""
+    Q, n = qp[0].shape[0], rp[0].shape[0]
+    step = SHARD_ITEMS if shard_items is None else int(shard_items)
+    if not 1 <= step <= N.TOPK_MAX:
+        raise N.NativeError(f"{what}: shard_items={step} outside [1, {N.TOPK_MAX}]")
+    if n > ITEMS_MAX:
+        raise N.NativeError(f"{what}: N={n} exceeds {ITEMS_MAX} (indices and counts are int32)")
+    if Q < 1 or n < 1:
+        raise N.NativeError(f"{what}: Q={Q} N={n}")
+    return Q, n, _cuts(Q, N.QUERIES_MAX), _cuts(n, step)
+
+
+def _search(what, qp, rp, bits, k, ql, rl, shard_items=None, grade_classes=None, want_counts=False):
+    """The k nearest database items of every query over any number of shards and query blocks -> (idx, dist, tag, counts): tag =
+    hit flags (None without labels), or grades with grade_classes; counts = hamming_hist's, None unless want_counts.
+    Per query block: shard 0 is searched with k_0 = min(k, N_0); shard s is searched with min(k, N_s) and folded into the running
+    list, whose width is min(k, items so far), through two output buffers of Q x k entries used in turn: O(Q k) memory however
+    many shards there are."""
+    Q, n, blocks, shards = _plan(what, qp, rp, shard_items)
+    k = int(k)
+    if not 1 <= k <= n:
+        raise N.NativeError(f"{what}: k={k} outside [1, N={n}]")
+
+    def one(qcut, scut, kk):
+        q, r = _rows(qp, qcut, Q), _rows(rp, scut, n)
+        qlab, rlab = _rows(ql, qcut, Q), _rows(rl, scut, n)
+        if grade_classes is not None:
+            out = N.hamming_topk_graded(q, r, bits, kk, qlab, rlab, want_counts=want_counts, classes=grade_classes)
+        else:
+            out = N.hamming_topk(q, r, bits, kk, qlab, rlab, want_counts=want_counts)
+        return out if want_counts else out + (None,)
+
+    parts = []
+    for qcut in blocks:
+        idx, dist, tag, counts = one(qcut, shards[0], min(k, shards[0][1]))
+        flat = [None, None]
+        for s, scut in enumerate(shards[1:]):
+            b_idx, b_dist, b_tag, b_counts = one(qcut, scut, min(k, scut[1] - scut[0]))
+            idx, dist, tag = _fold((idx, dist, tag), (b_idx, b_dist, b_tag), scut, k, flat, s)
+            if want_counts:
+                counts = counts + b_counts
+        parts.append((idx, dist, tag, counts))
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(None if p[0] is None else torch.cat(p) for p in zip(*parts))
+
+
+def _fold(run, b, scut, k, flat, s):
+    """The running list of the shards before scut and the list b of shard scut -> the running list behind it, min(k, scut[1])
+    wide, written into flat[s & 1]: a buffer set of rows x k entries allocated at its first use (two shards never need the second),
+    so that step s reads the set step s - 1 wrote and writes the other."""
+    rows, w = run[0].shape[0], min(k, scut[1])
+    if flat[s & 1] is None:
+        flat[s & 1] = tuple(None if t is None else torch.empty(rows * k, dtype=t.dtype, device=t.device) for t in run)
+    out = tuple(None if t is None else t[:rows * w].view(rows, w) for t in flat[s & 1])
+    return N.topk_merge(run, b, scut[0], w, out=out)
+
+
+def _summed(what, qp, rp, shard_items, one):
+    """one(query cut, shard cut, Q, n) -> an int32 histogram of the block against the shard; summed over the shards (on the GPU),
+    concatenated over the query blocks."""
+    Q, n, blocks, shards = _plan(what, qp, rp, shard_items)
+    parts = []
+    for qcut in blocks:
+        acc = one(qcut, shards[0], Q, n)
+        for scut in shards[1:]:
+            acc = acc + one(qcut, scut, Q, n)
+        parts.append(acc)
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _hist(qp, rp, bits, ql, rl, shard_items=None):
+    return _summed("pr_curve", qp, rp, shard_items, lambda qc, sc, Q, n: N.hamming_hist(
+        _rows(qp, qc, Q), _rows(rp, sc, n), bits, _rows(ql, qc, Q), _rows(rl, sc, n)))
+
+
+def _grade_hist(ql, rl, classes, shard_items=None):
+    return _summed("grade_histogram", (ql,), (rl,), shard_items, lambda qc, sc, Q, n: N.label_overlap_hist(
+        _rows(ql, qc, Q), _rows(rl, sc, n), classes))
+
+
+def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k][, rel uint8 [Q, k] with labels]): the k nearest database codes of every query."""
     if (query_L is None) != (retrieval_L is None):
         raise N.NativeError("hamming_topk: labels on one side only")
     dev = _dev(qB, rB)
-    idx, dist, rel = N.hamming_topk(_codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev), _labels(retrieval_L, dev))
+    idx, dist, rel, _ = _search("hamming_topk", _codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev),
+                                _labels(retrieval_L, dev), shard_items)
     return (idx, dist) if rel is None else (idx, dist, rel)
 
 
@@ -67,20 +174,20 @@ def _classes(what, query_L, retrieval_L):
     return query_L.shape[1]
 
 
-def graded_topk(qB, rB, k, query_L, retrieval_L):
+def graded_topk(qB, rB, k, query_L, retrieval_L, shard_items=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k], grade uint8 [Q, k]): hamming_topk's neighbours with the number of labels each shares
     with its query where hamming_topk has the hit flag (rel == grade > 0).  At most 255 classes."""
     classes = _classes("graded_topk", query_L, retrieval_L)
     dev = _dev(qB, rB)
-    return N.hamming_topk_graded(_codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev), _labels(retrieval_L, dev),
-                                 classes=classes)
+    return _search("graded_topk", _codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev), _labels(retrieval_L, dev),
+                   shard_items, grade_classes=classes)[:3]
 
 
-def grade_histogram(query_L, retrieval_L):
+def grade_histogram(query_L, retrieval_L, shard_items=None):
     """-> int32 [Q, C+1] on the GPU: entry [q, g] = database items that share exactly g labels with query q."""
     classes = _classes("grade_histogram", query_L, retrieval_L)
     dev = _dev(query_L, retrieval_L)
-    return N.label_overlap_hist(_labels(query_L, dev), _labels(retrieval_L, dev), classes)
+    return _grade_hist(_labels(query_L, dev), _labels(retrieval_L, dev), classes, shard_items)
 
 
 def graded_from_grades(grade, grade_counts, topn):
@@ -118,13 +225,13 @@ def graded_from_grades(grade, grade_counts, topn):
     return (dcg / idcg).mean(0), acg[:, cols].mean(0), wap[:, cols].mean(0)
 
 
-def graded_metrics(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN, grade_counts=None):
+def graded_metrics(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN, grade_counts=None, shard_items=None):
     """-> (ndcg [len(topn)], acg [len(topn)], wap [len(topn)], grade uint8 [Q, max(topn)] on the GPU).  grade_counts: a
     grade_histogram of the same labels, to share it among the directions of an evaluation (computed here when None)."""
     topn = [int(n) for n in topn]
-    _, _, grade = graded_topk(qB, rB, max(topn), query_L, retrieval_L)
+    _, _, grade = graded_topk(qB, rB, max(topn), query_L, retrieval_L, shard_items)
     if grade_counts is None:
-        grade_counts = grade_histogram(query_L, retrieval_L)
+        grade_counts = grade_histogram(query_L, retrieval_L, shard_items)
     return graded_from_grades(grade, grade_counts, topn) + (grade,)
 
 
@@ -161,38 +268,119 @@ def topn_from_rel(rel, relevant, topn):
     return (hits / n).mean(0), (hits / relevant[keep].double()[:, None]).mean(0)
 
 
-def pr_curve(qB, rB, query_L, retrieval_L):
+def pr_curve(qB, rB, query_L, retrieval_L, shard_items=None):
     """-> (precision [2K+1], recall [2K+1], counts int32 [Q, 2K+1, 2] on the GPU).  Entry h is the Hamming ball of radius h / 2
     (codes without zeros only reach the even entries; entry 2r is then the usual P@H<=r)."""
     dev = _dev(qB, rB)
-    counts = N.hamming_hist(_codes(qB, dev), _codes(rB, dev), rB.shape[1], _labels(query_L, dev), _labels(retrieval_L, dev))
+    counts = _hist(_codes(qB, dev), _codes(rB, dev), rB.shape[1], _labels(query_L, dev), _labels(retrieval_L, dev), shard_items)
     precision, recall = curves_from_counts(counts)
     return precision, recall, counts
 
 
-def topn_precision(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN):
+def topn_precision(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN, shard_items=None):
     """-> (precision [len(topn)], recall [len(topn)], rel uint8 [Q, max(topn)] on the GPU) of the ranking's first N items."""
     dev = _dev(qB, rB)
     topn = [int(n) for n in topn]
     qp, rp = _codes(qB, dev), _codes(rB, dev)
     ql, rl = _labels(query_L, dev), _labels(retrieval_L, dev)
-    _, _, rel, counts = N.hamming_topk(qp, rp, rB.shape[1], max(topn), ql, rl, want_counts=True)
+    _, _, rel, counts = _search("topn_precision", qp, rp, rB.shape[1], max(topn), ql, rl, shard_items, want_counts=True)
     relevant = counts[:, :, 1].sum(1)
     precision, recall = topn_from_rel(rel, relevant, topn)
     return precision, recall, rel
 
 
 class CodeIndex:
-    """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's)."""
+    """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's).
+    Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
+    plane that add() grows geometrically, so many small add()s never make many small shards.  save() / load() keep the packed
+    planes and labels as one .npz (data only)."""
 
-    def __init__(self, codes, labels=None):
+    def __init__(self, codes, labels=None, shard_items=None):
         dev = _dev(codes)
         self.bits = codes.shape[1]
-        self.size = codes.shape[0]
-        self.planes = _codes(codes, dev)
-        self.labels = _labels(labels, dev)
+        self.size = 0
         self.classes = None if labels is None else labels.shape[1]
         self.device = dev
+        self.shard_items = shard_items
+        self._sign = self._nz = self._lab = None
+        self._append(_codes(codes, dev), _labels(labels, dev))
+
+    @property
+    def planes(self):
+        """(sign, nz) int32 [size, ceil(bits / 32)]: views of the buffers' filled rows."""
+        return self._sign[:self.size], self._nz[:self.size]
+
+    @property
+    def labels(self):
+        return None if self._lab is None else self._lab[:self.size]
+
+    def _append(self, planes, lab):
+        new = planes[0].shape[0]
+        if self.size + new > ITEMS_MAX:
+            raise N.NativeError(f"CodeIndex: {self.size} + {new} items exceed {ITEMS_MAX} (indices are int32)")
+
+        def grown(buf, rows):
+            if buf is not None and self.size + new <= buf.shape[0]:
+                buf[self.size:self.size + new] = rows
+                return buf
+            cap = self.size + new if buf is None else min(ITEMS_MAX, max(self.size + new, 2 * buf.shape[0]))
+            out = torch.empty(cap, rows.shape[1], dtype=rows.dtype, device=rows.device)
+            if self.size:
+                out[:self.size] = buf[:self.size]
+            out[self.size:self.size + new] = rows
+            return out
+
+        self._sign, self._nz = grown(self._sign, planes[0]), grown(self._nz, planes[1])
+        if lab is not None:
+            self._lab = grown(self._lab, lab)
+        self.size += new
+
+    def add(self, codes, labels=None):
+        """Appends items behind the ones the index holds (their indices: size, size + 1, ...); only the new rows are packed."""
+        if codes.dim() < 2:
+            codes = codes.unsqueeze(0)
+        if codes.shape[1] != self.bits:
+            raise N.NativeError(f"CodeIndex.add: {codes.shape[1]}-bit codes for an index of {self.bits} bits")
+        if (labels is None) != (self.classes is None):
+            raise N.NativeError("CodeIndex.add: labels given for an index without them" if self.classes is None
+                                else "CodeIndex.add: the index holds labels, the new items bring none")
+        if labels is not None and (labels.dim() != 2 or labels.shape[1] != self.classes or labels.shape[0] != codes.shape[0]):
+            raise N.NativeError(f"CodeIndex.add: labels of shape {tuple(labels.shape)} for {codes.shape[0]} items of {self.classes} classes")
+        if codes.shape[0]:
+            self._append(_codes(codes, self.device), _labels(labels, self.device))
+        return self
+
+    def save(self, path):
+        """The packed planes, the packed labels (when there are any), bits, classes and size as one .npz: arrays only."""
+        import numpy as np
+        arrays = {"sign": self.planes[0].cpu().numpy(), "nz": self.planes[1].cpu().numpy(), "bits": np.int64(self.bits),
+                  "size": np.int64(self.size), "classes": np.int64(0 if self.classes is None else self.classes)}
+        if self._lab is not None:
+            arrays["labels"] = self.labels.cpu().numpy()
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path, shard_items=None):
+        """An index written by save(); nothing is packed again."""
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            bits, size, classes = int(z["bits"]), int(z["size"]), int(z["classes"])
+            sign, nz = torch.from_numpy(z["sign"]), torch.from_numpy(z["nz"])
+            lab = torch.from_numpy(z["labels"]) if "labels" in z.files else None
+        W = (bits + 31) // 32
+        ok = bits >= 1 and size >= 1 and tuple(sign.shape) == (size, W) and tuple(nz.shape) == (size, W) and sign.dtype == torch.int32 \
+            and nz.dtype == torch.int32 and (classes > 0) == (lab is not None)
+        if ok and lab is not None:
+            ok = tuple(lab.shape) == (size, (classes + 31) // 32) and lab.dtype == torch.int32
+        if not ok:
+            raise N.NativeError(f"CodeIndex.load: {path} is not a file written by CodeIndex.save")
+        self = cls.__new__(cls)
+        self.device = _dev()
+        self.bits, self.size, self.classes, self.shard_items = bits, 0, (classes if classes > 0 else None), shard_items
+        self._sign = self._nz = self._lab = None
+        self._append((sign.to(self.device), nz.to(self.device)), None if lab is None else lab.to(self.device))
+        return self
 
     @classmethod
     def from_mat(cls, path, side="r_img"):
@@ -212,6 +400,8 @@ class CodeIndex:
         if graded:
             if ql is None:
                 raise N.NativeError("CodeIndex.search: graded=True needs query labels and an index with labels")
-            return N.hamming_topk_graded(_codes(query_codes, self.device), self.planes, self.bits, k, ql, rl, classes=self.classes)
-        idx, dist, rel = N.hamming_topk(_codes(query_codes, self.device), self.planes, self.bits, k, ql, rl)
+            return _search("CodeIndex.search", _codes(query_codes, self.device), self.planes, self.bits, k, ql, rl, self.shard_items,
+                           grade_classes=self.classes)[:3]
+        idx, dist, rel, _ = _search("CodeIndex.search", _codes(query_codes, self.device), self.planes, self.bits, k, ql, rl,
+                                    self.shard_items)
         return (idx, dist) if rel is None else (idx, dist, rel)

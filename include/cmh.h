@@ -469,6 +469,20 @@ int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q_nz, const 
 size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes);
 int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r_label, int32_t Q, int64_t N, int32_t classes,
                            uint32_t* grade_counts, void* workspace, size_t workspace_bytes, void* stream);
+/* A database larger than N <= 524287 is searched as shards (utils/retrieval.py: row slices of the packed planes, each within the
+ * limits above) and the per-shard lists are folded together in ascending shard order (csrc/retrieval_merge.hip); the result is bit
+ * for bit the list of one cmh_hamming_topk over the whole database, i.e. of torch.sort(calc_hammingDist(q, r), stable=True).
+ *
+ * Two top-k lists of the same queries -> the first k entries of their union in the order of cmh_hamming_topk.
+ * Every row of a and of b is ascending by (dist, idx).  The caller guarantees that every index of b (after b_base is added)
+ * is larger than every index of a, so "a before b at equal distance" IS ascending database index.
+ * idx[q, :] / dist[q, :] / tag[q, :] = the first k of merge(a[q, :], b[q, :]); b's indices come out as b_idx + b_base.
+ * tag = the hit flag or the grade that travels with an entry: a_tag, b_tag and tag are all given or all null.
+ * 1 <= ka, 1 <= kb, 1 <= k <= ka + kb, 1 <= Q <= 65535 (as the searches that make the lists: more queries go in blocks);
+ * outputs must not alias inputs.  No workspace. */
+int cmh_topk_merge(const int32_t* a_idx, const float* a_dist, const uint8_t* a_tag, int32_t ka,
+                   const int32_t* b_idx, const float* b_dist, const uint8_t* b_tag, int32_t kb, int32_t b_base,
+                   int32_t Q, int32_t k, int32_t* idx, float* dist, uint8_t* tag, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.

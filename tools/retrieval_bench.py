@@ -16,7 +16,18 @@ Floors of one pass over the database, from the shapes (printed with the line):
             256 CUs at 2.4 GHz;
   valu      query tiles x N x (5 W + 8) wave-wide vector instructions of 4 cycles on 1024 SIMDs at 2.4 GHz (and / xor / and / two
             popcounts and their sums per word, the distance, the relevance test, the address).
-The search makes two passes (the second without increments for most items)."""
+The search makes two passes (the second without increments for most items).
+
+--sharded runs the sharded leg instead (utils/retrieval.py: shards of the database searched one by one, the lists folded by
+cmh_topk_merge), synthetic codes, same rules (device events, REGIONS regions of --reps calls, median [min - max], legs alternating):
+  (a) 5000 x 190 834 x 128 bit, k = 100 and 1000, as 1 / 2 / 4 shards.  One shard is the single native call (the baseline: the
+      search as it was before sharding existed); `over_one_shard` = median over median is the price of sharding plus merging.
+      The lists of 2 and 4 shards are compared with the one-shard list on the timed inputs.
+  (b) 5000 x 2 000 000 x 64 bit, k = 1000, at the default shard size (4 shards): no baseline, one call refuses it.  64 rows are
+      compared with torch.sort(stable=True) of the full distance rows.  Reported with the floor of two passes over the same
+      item count.
+`merge` is a leg of its own: the fold of the per-shard lists alone (the merge launches of one search on lists computed before
+the timed regions), and `merge_share` its median over the search's."""
 import argparse
 import json
 import os
@@ -40,16 +51,111 @@ def floors_ms(Q, n, bits, classes, passes):
     return out
 
 
+SHARDED = {"nuswide_190834_128": (5000, 190834, 128, 21, (100, 1000), (1, 2, 4)),
+           "synthetic_2000000_64": (5000, 2000000, 64, 24, (1000,), (None,))}
+
+
+def sharded(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+    for name, (Q, n, K, C, ks, cuts) in SHARDED.items():
+        g = torch.Generator(device=dev).manual_seed(1)
+        rL = (torch.rand(n, C, generator=g, device=dev) < 0.1).float()
+        qL = (torch.rand(Q, C, generator=g, device=dev) < 0.1).float()
+        rL[:, 0] = 1.0
+        qL[:, 0] = 1.0
+        Wm = torch.randn(C, K, generator=g, device=dev)
+        mk = lambda lab: torch.sign(lab @ Wm + 0.5 * torch.randn(lab.shape[0], K, generator=g, device=dev) + 1e-3)
+        rB, qB = mk(rL), mk(qL)
+        rp, qp = N.pack_codes(rB), N.pack_codes(qB)
+        rl, ql = N.pack_labels(rL), N.pack_labels(qL)
+        step = lambda c: N.TOPK_MAX if c is None else (n + c - 1) // c
+        legs, lists = {}, {}
+        for k in ks:
+            for c in cuts:
+                items = step(c)
+                shards = R._cuts(n, items)
+                tag = f"k{k}_s{len(shards)}"
+                legs[tag] = (lambda k=k, items=items: R._search("bench", qp, rp, K, k, ql, rl, items))
+                if len(shards) > 1:
+                    # the per-shard lists of one search, computed once: the merge leg folds them as _search does
+                    per = [N.hamming_topk(qp, R._rows(rp, sc, n), K, min(k, sc[1] - sc[0]), ql, R._rows(rl, sc, n)) for sc in shards]
+                    lists[tag] = (k, shards, per)
+
+                    def fold(tag=tag):
+                        k, shards, per = lists[tag]
+                        run, flat = per[0], [None, None]
+                        for s, (sc, b) in enumerate(zip(shards[1:], per[1:])):
+                            run = R._fold(run, b, sc, k, flat, s)
+                        return run
+                    legs["merge_" + tag] = fold
+        outs = {tag: fn() for tag, fn in legs.items()}                    # warm-up, and the outputs on the timed inputs
+        same = True
+        for tag, out in outs.items():
+            if tag.startswith("merge_"):
+                same = same and all(bool(torch.equal(a, b)) for a, b in zip(out, outs[tag[6:]][:3]))
+            elif f"{tag.split('_')[0]}_s1" in outs:
+                same = same and all(bool(torch.equal(a, b)) for a, b in zip(out[:3], outs[f"{tag.split('_')[0]}_s1"][:3]))
+            else:                                                         # no one-shard list: 64 rows against the full stable sort
+                full = 0.5 * (K - qB[:64] @ rB.T)
+                d, i = torch.sort(full, dim=1, stable=True)
+                k = out[0].shape[1]
+                same = same and bool(torch.equal(out[0][:64].long(), i[:, :k])) and bool(torch.equal(out[1][:64], d[:, :k]))
+                del full, d, i
+        del outs
+        torch.cuda.synchronize()
+        times = {tag: [] for tag in legs}
+        for _ in range(REGIONS):
+            for tag, fn in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.reps):
+                    out = fn()
+                e1.record()
+                e1.synchronize()
+                del out
+                times[tag].append(e0.elapsed_time(e1) / args.reps)
+        line = {"tool": "retrieval_bench", "leg": "sharded", "shape": name, "Q": Q, "N": n, "bits": K, "classes": C, "regions": REGIONS,
+                "outputs_equal": same, "ms": {}}
+        for tag, ts in times.items():
+            line["ms"][tag] = {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
+        for tag in times:
+            if tag.startswith("merge_"):
+                line["ms"][tag[6:]]["merge_share"] = round(line["ms"][tag]["median"] / line["ms"][tag[6:]]["median"], 4)
+            else:
+                one = f"{tag.split('_')[0]}_s1"
+                if one in times:
+                    line["ms"][tag]["over_one_shard"] = round(line["ms"][tag]["median"] / line["ms"][one]["median"], 4)
+                else:
+                    fl = floors_ms(Q, n, K, C, 2)
+                    line["ms"][tag]["floor_ms"] = {k: (round(v, 4) if k != "bound" else v) for k, v in fl.items()}
+                    line["ms"][tag]["share_of_floor"] = round(fl[fl["bound"]] / line["ms"][tag]["median"], 4)
+        text = json.dumps(line)
+        print(text, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(text + "\n")
+        if not same:
+            raise SystemExit(f"{name}: the sharded search disagrees with the search of the whole database")
+        del rB, qB, rp, qp, rl, ql, rL, qL, legs, lists
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--reps", type=int, default=5, help="calls per timed region of the new legs")
     ap.add_argument("--out", default="", help="append the JSON lines to this file")
+    ap.add_argument("--sharded", action="store_true", help="run the sharded leg (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
     if not torch.cuda.is_available():
         raise SystemExit("retrieval_bench needs a GPU: nothing is measured without one")
+    if args.sharded:
+        return sharded(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
