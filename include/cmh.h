@@ -649,7 +649,8 @@ int cmh_layernorm_backward(const void* x, int32_t x_kind, const void* dy, int32_
                            int32_t d, float* dx, int32_t accumulate, float* dgamma, float* dbeta, void* workspace,
                            size_t workspace_bytes, void* stream);
 /* Backward of cmh_attention (same layouts and masks): qkv [B*T,3d], o = the forward output [B*T,d], dout [B*T,d] ->
- * dqkv [B*T,3d]; softmax probabilities are recomputed.  T <= 128. */
+ * dqkv [B*T,3d]; softmax probabilities are recomputed.  T <= 4096 (whole-sequence kernels up to 128, the tiled kernel beyond; the
+ * tiled kernel and the bf16 kernel at T <= 96 do not read o). */
 int cmh_attention_backward(int32_t dtype, const void* qkv, const void* o, const void* dout, void* dqkv, int32_t B, int32_t T,
                            int32_t d, int32_t causal, const uint8_t* key_padding_mask, void* stream);
 /* out = pre * sigmoid(1.702 pre) element-wise from a saved pre-activation (model/base/model.py:162-164). */
