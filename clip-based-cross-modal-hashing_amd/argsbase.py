@@ -21,6 +21,7 @@ BASE_FLAGS = [
     ("--gemm-dtype", str, "f32", "encoder GEMM arithmetic: f32 = reference parity, bf16 = throughput, fp8 = e4m3 block GEMMs, inference only (this build)"),
     ("--data-dir", str, "", "directory with index.mat / caption.mat|txt / label.mat (this build; upstream hard-codes it)"),
     ("--synthetic-size", int, 2000, "items of the synthetic dataset (this build)"),
+    ("--map-tie-order", str, "reference", "mAP ties: reference = the reference's torch.sort order (up to 524 287 database items); stable = by ascending database index, by counting, any database size (this build)"),
     ("--eval-curves", str2bool, False, "test(): also log P@H<=2 / P@N and store the precision-recall and top-N curves in the .mat (this build)"),
     ("--eval-graded", str2bool, False, "test(): also log NDCG@N / ACG@N / WAP@N (relevance graded by the number of shared labels) and store them in the .mat (this build)"),
 ]
@@ -35,6 +36,8 @@ def add_flags(parser, table):
             kw["help"] = doc[0]
         if flag == "--gemm-dtype":
             kw["choices"] = ["f32", "bf16", "fp8"]      # fp8: inference only (--is-train false)
+        if flag == "--map-tie-order":
+            kw["choices"] = ["reference", "stable"]
         parser.add_argument(flag, **kw)
     return parser
 

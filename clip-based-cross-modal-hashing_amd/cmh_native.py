@@ -148,6 +148,9 @@ SIGNATURES = {
     "cmh_hamming_hist": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _sz, _p]),
     "cmh_hamming_topk": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_hamming_topk_graded": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_map_count_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_hamming_ap_partial": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_ap_finish": (C.c_int, [_p, _p, _i32, _i32, _i64, _p, _p, _p]),
     "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
@@ -702,6 +705,53 @@ def hamming_hist(q_planes, r_planes, bits, q_lab=None, r_lab=None):
     check(lib().cmh_hamming_hist(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), 32 * LW,
                                  ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_hist")
     return counts
+
+
+def _counts_operand(what, name, t, Q, bits, dev):
+    if t is None:
+        return None
+    fit(what, (t, (Q, 2 * int(bits) + 1, 2)))
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+        raise NativeError(f"{what}: {name} is a contiguous int32 tensor [Q, 2 * bits + 1, 2] on the operands' device (hamming_hist)")
+    return t
+
+
+def hamming_ap_partial(q_planes, r_planes, bits, q_lab, r_lab, topk=None, total_counts=None, prior_counts=None, want_counts=False):
+    """The AP sums of one database shard by counting (no ranking): -> ap_sum float64 [Q] = the sum, over the shard's relevant items
+    whose rank among the relevant items of the WHOLE database is <= min(k, R), of relrank / rank; ties by ascending database index
+    (torch.sort(stable=True)).  total_counts / prior_counts: hamming_hist's histograms of the whole database and of the shards
+    before this one (None: this call's own / none).  topk=None: k = the whole database.  [+ this shard's counts with want_counts].
+    The sums of the shards add; ap_finish turns them into APs."""
+    if q_lab is None or r_lab is None:
+        raise NativeError("hamming_ap_partial: needs the labels of both sides")
+    qs, qn, rs, rn, Q, N, LW = _retrieval_operands("hamming_ap_partial", q_planes, r_planes, bits, q_lab, r_lab)
+    dev = qs.device
+    total_counts = _counts_operand("hamming_ap_partial", "total_counts", total_counts, Q, bits, dev)
+    prior_counts = _counts_operand("hamming_ap_partial", "prior_counts", prior_counts, Q, bits, dev)
+    ap_sum = torch.empty(Q, dtype=torch.float64, device=dev)
+    counts = torch.empty(Q, 2 * int(bits) + 1, 2, dtype=torch.int32, device=dev) if want_counts else None
+    ws = workspace(lib().cmh_map_count_workspace_bytes(Q, N, int(bits)), dev, "retrieval")
+    check(lib().cmh_hamming_ap_partial(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), 32 * LW,
+                                       0 if topk is None else int(topk), ptr(total_counts), ptr(prior_counts), ptr(counts),
+                                       ptr(ap_sum), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_ap_partial")
+    return (ap_sum, counts) if want_counts else ap_sum
+
+
+def ap_finish(ap_sum, total_counts, bits, topk=None):
+    """ap_sum float64 [Q] (hamming_ap_partial, added over the shards), total_counts int32 [Q, 2 * bits + 1, 2] of the whole database
+    -> (map 0-dim f32, ap f32 [Q]): ap = ap_sum / min(k, R), 0 where R = 0; map = their mean as map_mean forms it."""
+    require_gpu(ap_sum, total_counts)
+    Q = ap_sum.numel()
+    if ap_sum.dtype != torch.float64 or ap_sum.dim() != 1 or not ap_sum.is_contiguous() or Q < 1:
+        raise NativeError("ap_finish: ap_sum is a contiguous float64 tensor [Q]")
+    total_counts = _counts_operand("ap_finish", "total_counts", total_counts, Q, bits, ap_sum.device)
+    if total_counts is None:
+        raise NativeError("ap_finish: needs the histogram of the whole database")
+    ap = torch.empty(Q, dtype=torch.float32, device=ap_sum.device)
+    mp = torch.empty(1, dtype=torch.float32, device=ap_sum.device)
+    check(lib().cmh_ap_finish(ptr(ap_sum), ptr(total_counts), Q, int(bits), 0 if topk is None else int(topk), ptr(ap), ptr(mp),
+                              stream_ptr(ap_sum.device)), "cmh_ap_finish")
+    return mp[0], ap
 
 
 def hamming_topk(q_planes, r_planes, bits, k, q_lab=None, r_lab=None, want_counts=False):

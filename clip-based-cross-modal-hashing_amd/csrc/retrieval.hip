@@ -34,6 +34,12 @@
 //                            [g][lane] of full 32-bit counters (a chunk may hold any number of items), images summed by
 //                            grade_reduce_kernel.  LDS per workgroup: (C+1) * 256 bytes: 6.25 KiB at 24 classes, 20.25 KiB at 80,
 //                            64 KiB at 255 (one byte per grade: C <= 255).
+//
+// mAP by counting (AP needs ranks, not the permutation; any database size, as shards):
+//   cmh_hamming_ap_partial   per query the float64 sum of relrank / rank over the relevant items of one call's database, which may be
+//                            one shard of a larger one: the histogram pass, three small kernels that turn its images into 32-bit
+//                            bases per (chunk, bin, lane), and a second walk whose packed LDS cursor gives both positions of an item.
+//   cmh_ap_finish            ap = sum / min(k, R), map = their f32 mean in query order.
 #include "cmh_common.h"
 
 namespace cmh {
@@ -411,6 +417,221 @@ __global__ __launch_bounds__(256) void grade_reduce_kernel(RetArgs a) {
   if (q < a.Q) a.counts[static_cast<size_t>(q) * a.bins + g] = tot;
 }
 
+// ---- mAP by counting (cmh_hamming_ap_partial / cmh_ap_finish) ---------------------------------------------------------------------
+// AP needs ranks, not the permutation: for a relevant item j at bin h, with ties by ascending database index,
+//   rank(j)    = #{items at h' < h} + #{items at h with index < j} + 1,   relrank(j) = the same over the relevant items,
+//   AP = (1 / total) * sum_{relevant j, relrank(j) <= total} relrank(j) / rank(j),   total = min(k, R).
+// Pass 1 is hist_kernel.  The three kernels below turn its images into the two BASES of every (chunk, bin, lane): items / relevant
+// items at smaller h in the whole database + at h in earlier shards (`prior`) + at h in earlier chunks of this call.  ap_kernel then
+// walks its chunk in index order with the packed cursor of hist_kernel in LDS: the returning add gives both positions inside the chunk.
+// The database may be one shard of a larger one: `total` is then the histogram of all shards and `prior` that of the shards before.
+struct ApArgs {
+  const uint32_t* total;   // [Q][bins][2] of the whole database, or null: this call's own
+  const uint32_t* prior;   // [Q][bins][2] of the shards before this one, or null: none
+  uint32_t* brel;          // [S][tiles][bins][64] bases over the relevant items (those over all items replace the images in a.img)
+  uint32_t* toti;          // [tiles][bins][64] this call's items per bin -> exclusive prefix over the bins of the whole database
+  uint32_t* totr;          // ... the relevant ones
+  uint32_t* kq;            // [tiles * 64] min(k, R) per query
+  double* part;            // [S][tiles][64] a workgroup's sums
+  double* ap_sum;          // [Q]
+  uint32_t k;
+};
+
+// the images of a tile summed over the chunks -> toti, totr (and counts)
+__global__ __launch_bounds__(256) void ap_total_kernel(RetArgs a, ApArgs p) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= stride) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t hb = t >> 6;
+  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
+  uint32_t tot = 0, rel = 0;
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * stride + t];
+    tot += v & 0xffffu;
+    rel += v >> 16;
+  }
+  p.toti[t] = tot;
+  p.totr[t] = rel;
+  const int q = tile * 64 + lane;
+  if (a.counts && q < a.Q) {
+    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
+    o[0] = tot - rel;
+    o[1] = rel;
+  }
+}
+
+// per query: toti / totr become the exclusive prefixes over the bins of the whole database's histogram; kq = min(k, R)
+__global__ __launch_bounds__(64) void ap_scan_kernel(RetArgs a, ApArgs p) {
+  const int lane = threadIdx.x, tile = blockIdx.x;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  const size_t base = static_cast<size_t>(tile) * a.bins * 64 + lane;
+  uint32_t ri = 0, rr = 0;
+  for (int h = 0; h < a.bins; ++h) {
+    const size_t t = base + static_cast<size_t>(h) * 64;
+    uint32_t ni, nr;
+    if (p.total) {
+      const uint32_t* c = p.total + (static_cast<size_t>(q) * a.bins + h) * 2;
+      nr = c[1];
+      ni = c[0] + nr;
+    } else {
+      ni = p.toti[t];
+      nr = p.totr[t];
+    }
+    p.toti[t] = ri;
+    p.totr[t] = rr;
+    ri += ni;
+    rr += nr;
+  }
+  p.kq[tile * 64 + lane] = rr < p.k ? rr : p.k;
+}
+
+// every image becomes the base over all items, brel the base over the relevant ones
+__global__ __launch_bounds__(256) void ap_base_kernel(RetArgs a, ApArgs p) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= stride) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t hb = t >> 6;
+  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  uint32_t bi = p.toti[t], br = p.totr[t];
+  if (p.prior) {
+    const uint32_t* c = p.prior + (static_cast<size_t>(q) * a.bins + h) * 2;
+    bi += c[0] + c[1];
+    br += c[1];
+  }
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * stride + t];
+    a.img[c * stride + t] = bi;
+    p.brel[c * stride + t] = br;
+    bi += v & 0xffffu;
+    br += v >> 16;
+  }
+}
+
+// ---- pass 2 of the mAP: a workgroup's sum of relrank / rank over the relevant items of its chunk ----------------------------------
+// Cursors in LDS (hist_kernel's packed word: the histogram pass's occupancy), the bases read from the workspace for relevant items
+// only; lanes that meet the same bin read one line of [bin][lane].  GLOB: the bases themselves are the cursors, advanced with global
+// atomics (a lane owns its words: the adds of one word come from one lane in index order).
+// (brel, kq and part are trailing parameters, not members of RetArgs: the argument layout of the other kernels stays what it was.)
+template <int WT, int LT, bool GLOB>
+__global__ __launch_bounds__(64) void ap_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
+                                                const uint32_t* __restrict__ rl, uint32_t* brel_all, const uint32_t* __restrict__ kq,
+                                                double* __restrict__ part) {
+  extern __shared__ uint32_t smem[];
+  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their sum
+  const size_t image = (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  uint32_t* bitem = a.img + image;
+  uint32_t* brel = brel_all + image;
+  uint32_t* cur = smem;
+  Tile<WT, LT> t;
+  t.load(a, q, lane, smem + (GLOB ? 0 : a.bins * 64));
+  if (!GLOB)
+    for (int h = 0; h < a.bins; ++h) cur[h * 64 + lane] = 0u;
+  __syncthreads();
+  const uint32_t total = kq[tile * 64 + lane];
+  double acc = 0.0;
+  auto score = [&](int h, uint32_t r) {
+    const int w = h * 64 + lane;
+    if (GLOB) {
+      const uint32_t pi = atomicAdd(&bitem[w], 1u);
+      if (r) {
+        const uint32_t pr = atomicAdd(&brel[w], 1u) + 1u;
+        if (pr <= total) acc += static_cast<double>(__fdiv_rn(static_cast<float>(pr), static_cast<float>(pi + 1u)));
+      }
+    } else {
+      const uint32_t old = atomicAdd(&cur[w], 1u + (r << 16));
+      if (r) {
+        const uint32_t pr = brel[w] + (old >> 16) + 1u;
+        const uint32_t pi = bitem[w] + (old & 0xffffu) + 1u;
+        if (pr <= total) acc += static_cast<double>(__fdiv_rn(static_cast<float>(pr), static_cast<float>(pi)));
+      }
+    }
+  };
+  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  int j = jb;
+  if (WT > 0) {
+    // A workgroup is one wave, and at 4 (2) workgroups per CU a SIMD holds one: nothing hides a wait, so an item at a time (the add's
+    // return, then the bases, then the quotient) costs three round trips per item.  A group is therefore worked on in phases, each
+    // a run of independent instructions: distances and relevance of its U items; the loads of the bases (they need only the bin);
+    // the U returning adds; the quotients.  ONE register set: the next group's fetch is issued behind the wait for the adds'
+    // returns (both count on the same counter: a fetch in flight would be waited for with them) and flies during the quotients.
+    using G = Group<WT, LT>;
+    const int groups = (je - jb) / G::U;
+    G g;
+    if (groups > 0) g.load(rs, rn, rl, jb, true);
+    for (int gi = 0; gi < groups; ++gi, j += G::U) {
+      int w[G::U];
+      uint32_t r[G::U], old[G::U], bi[G::U], br[G::U];
+#pragma unroll
+      for (int u = 0; u < G::U; ++u) {
+        w[u] = t.half(g.s + u * WT, g.n + u * WT) * 64 + lane;
+        r[u] = LT > 0 ? t.relevant(g.l + u * LT) : t.relevant(rl + static_cast<size_t>(j + u) * a.LW);
+      }
+#pragma unroll
+      for (int u = 0; u < G::U; ++u) {
+        bi[u] = br[u] = 0u;
+        if (r[u]) { bi[u] = bitem[w[u]]; br[u] = brel[w[u]]; }
+      }
+#pragma unroll
+      for (int u = 0; u < G::U; ++u) old[u] = atomicAdd(&cur[w[u]], 1u + (r[u] << 16));
+      asm volatile("" : "+v"(old[G::U - 1]));                       // the wait for the adds' returns sits here (they return in order)
+      __builtin_amdgcn_sched_barrier(0);
+      g.load(rs, rn, rl, gi + 1 < groups ? j + G::U : j, true);      // (behind the last group: it once more, no branch)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < G::U; ++u) {
+        const uint32_t pr = br[u] + (old[u] >> 16) + 1u;
+        if (r[u] && pr <= total)
+          acc += static_cast<double>(__fdiv_rn(static_cast<float>(pr), static_cast<float>(bi[u] + (old[u] & 0xffffu) + 1u)));
+      }
+    }
+  }
+  for (; j < je; ++j)
+    score(t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W), t.relevant(rl + static_cast<size_t>(j) * a.LW));
+  part[(static_cast<size_t>(c) * a.tiles + tile) * 64 + lane] = acc;
+}
+
+// the chunks' sums added in chunk order
+__global__ __launch_bounds__(64) void ap_sum_kernel(RetArgs a, ApArgs p) {
+  const int lane = threadIdx.x, tile = blockIdx.x, q = tile * 64 + lane;
+  if (q >= a.Q) return;
+  double s = 0.0;
+  for (int c = 0; c < a.S; ++c) s += p.part[(static_cast<size_t>(c) * a.tiles + tile) * 64 + lane];
+  p.ap_sum[q] = s;
+}
+
+// one wave per query: R from the histogram, ap = ap_sum / min(k, R) in float64, rounded to f32 once
+__global__ __launch_bounds__(64) void ap_finish_kernel(const double* __restrict__ ap_sum, const uint32_t* __restrict__ counts, int bins,
+                                                       uint32_t k, float* __restrict__ ap) {
+  const size_t q = blockIdx.x;
+  uint32_t r = 0;
+  for (int h = threadIdx.x; h < bins; h += 64) r += counts[(q * bins + h) * 2 + 1];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+  if (threadIdx.x == 0) {
+    const uint32_t total = r < k ? r : k;
+    ap[q] = total ? static_cast<float>(ap_sum[q] / static_cast<double>(total)) : 0.f;
+  }
+}
+
+// (((ap[0] + ap[1]) + ...) / Q) in f32 in query order: the mean of the ranking kernel (map_mean_kernel of hamming_map.hip)
+__global__ __launch_bounds__(64) void ap_mean_kernel(const float* __restrict__ ap, int Q, float* __restrict__ out) {
+  __shared__ float buf[1024];
+  float acc = 0.f;
+  for (int q0 = 0; q0 < Q; q0 += 1024) {
+    const int n = Q - q0 < 1024 ? Q - q0 : 1024;
+    for (int i = threadIdx.x; i < n; i += 64) buf[i] = ap[q0 + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < n; ++i) acc += buf[i];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = acc / static_cast<float>(Q);
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 struct Plan {
   int bins, W, tiles, S, chunk, tb;      // tb = query tiles per batch (the images of one batch fit kImageCap)
@@ -551,6 +772,97 @@ int run(const char* what, const uint32_t* q_sign, const uint32_t* q_nz, const ui
   return CMH_OK;
 }
 
+// The mAP's workspace per batch of tb query tiles: images (-> bases over the items) and bases over the relevant items [S] each,
+// toti, totr, kq, the workgroups' float64 sums.  The batch is sized so that all of it fits kImageCap.
+struct ApPlan : Plan {
+  size_t per_tile() const { return (2 * static_cast<size_t>(S) + 2) * tile_words() * 4 + 64 * 4 + static_cast<size_t>(S) * 64 * 8; }
+  size_t ap_bytes() const { return static_cast<size_t>(tb) * per_tile() + 512; }
+};
+
+ApPlan make_ap_plan(int Q, int64_t N, int bits) {
+  ApPlan p;
+  static_cast<Plan&>(p) = make_plan(Q, N, bits);
+  size_t tb = kImageCap / p.per_tile();
+  tb = tb < 1 ? 1 : tb;
+  p.tb = tb < static_cast<size_t>(p.tiles) ? static_cast<int>(tb) : p.tiles;
+  return p;
+}
+
+template <int WT, int LT, bool GLOB>
+int launch_ap(const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(a.bins) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
+  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ap_kernel<WT, LT, GLOB>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "hamming_ap_partial: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL((ap_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, p.brel, p.kq, p.part);
+  CMH_CHECK_LAUNCH("hamming_ap_partial");
+  return CMH_OK;
+}
+
+template <int WT>
+int launch_ap_labels(const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  if (a.LW == 1) return launch_ap<WT, 1, false>(a, p, rs, rn, rl, st);
+  if (a.LW == 3) return launch_ap<WT, 3, false>(a, p, rs, rn, rl, st);
+  return launch_ap<WT, LAB_ANY, false>(a, p, rs, rn, rl, st);
+}
+
+int launch_ap_any(bool glob, const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
+  if (glob) return launch_ap<0, LAB_ANY, true>(a, p, rs, rn, rl, st);
+  if (a.W == 1) return launch_ap_labels<1>(a, p, rs, rn, rl, st);
+  if (a.W == 2) return launch_ap_labels<2>(a, p, rs, rn, rl, st);
+  if (a.W == 3) return launch_ap_labels<3>(a, p, rs, rn, rl, st);
+  return launch_ap_labels<4>(a, p, rs, rn, rl, st);
+}
+
+// hist, the bases, the AP pass and the sum over the chunks, in batches of query tiles
+int run_ap(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign, const uint32_t* r_nz,
+           const uint32_t* r_label, int Q, int64_t N, int bits, int classes, uint32_t k, const uint32_t* total, const uint32_t* prior,
+           uint32_t* counts, double* ap_sum, void* workspace, hipStream_t st) {
+  const ApPlan p = make_ap_plan(Q, N, bits);
+  RetArgs a = {};
+  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = (classes + 31) / 32; a.bins = p.bins;
+  a.S = p.S; a.chunk = p.chunk;
+  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
+    const int q0 = t0 * 64;
+    a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
+    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
+    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
+    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
+    a.ql = q_label + static_cast<size_t>(q0) * a.LW;
+    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
+    const size_t row = static_cast<size_t>(q0) * a.bins * 2;
+    ApArgs b;
+    b.total = total ? total + row : nullptr;
+    b.prior = prior ? prior + row : nullptr;
+    a.img = base;
+    b.brel = base + static_cast<size_t>(a.S) * stride;
+    b.toti = b.brel + static_cast<size_t>(a.S) * stride;
+    b.totr = b.toti + stride;
+    b.kq = b.totr + stride;
+    b.part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(b.kq + static_cast<size_t>(a.tiles) * 64) + 255) & ~static_cast<uintptr_t>(255));
+    b.ap_sum = ap_sum + q0;
+    b.k = k;
+    a.counts = counts ? counts + row : nullptr;
+    if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
+      return fail(CMH_ERR_LAUNCH, "hamming_ap_partial: memset failed");
+    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
+    if (rc != CMH_OK) return rc;
+    const unsigned blocks = static_cast<unsigned>((stride + 255) / 256);
+    hipLaunchKernelGGL(ap_total_kernel, dim3(blocks), dim3(256), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_ap_partial totals");
+    hipLaunchKernelGGL(ap_scan_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_ap_partial scan");
+    hipLaunchKernelGGL(ap_base_kernel, dim3(blocks), dim3(256), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_ap_partial bases");
+    rc = launch_ap_any(p.glob, a, b, r_sign, r_nz, r_label, st);
+    if (rc != CMH_OK) return rc;
+    hipLaunchKernelGGL(ap_sum_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_ap_partial sum");
+  }
+  return CMH_OK;
+}
+
 }  // namespace
 }  // namespace cmh
 
@@ -600,6 +912,40 @@ extern "C" int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q
   CMH_CHECK_ARG(k <= N, "hamming_topk_graded: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
   return run("hamming_topk_graded", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist,
              rel, grade, counts, workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" size_t cmh_map_count_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
+  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
+  return make_ap_plan(Q, N, bits).ap_bytes();
+}
+
+extern "C" int cmh_hamming_ap_partial(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                                      const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits,
+                                      int32_t classes, int64_t topk, const uint32_t* total_counts, const uint32_t* prior_counts,
+                                      uint32_t* counts_out, double* ap_sum, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && ap_sum, "hamming_ap_partial: null pointer");
+  CMH_CHECK_ARG(q_label && r_label, "hamming_ap_partial: AP needs the labels of both sides");
+  const int rc = check_shape("hamming_ap_partial", Q, N, bits, classes, true);
+  if (rc != CMH_OK) return rc;
+  const size_t need = make_ap_plan(Q, N, bits).ap_bytes();
+  CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_ap_partial: workspace %zu < %zu bytes", workspace_bytes, need);
+  const uint32_t k = topk <= 0 || topk > INT32_MAX ? static_cast<uint32_t>(INT32_MAX) : static_cast<uint32_t>(topk);      // (R <= 2^31 - 1)
+  return run_ap(q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, k, total_counts, prior_counts, counts_out, ap_sum,
+                workspace, as_stream(stream));
+}
+
+extern "C" int cmh_ap_finish(const double* ap_sum, const uint32_t* total_counts, int32_t Q, int32_t bits, int64_t topk, float* ap,
+                             float* map, void* stream) {
+  CMH_CHECK_ARG(ap_sum && total_counts && ap && map, "ap_finish: null pointer");
+  CMH_CHECK_ARG(Q > 0, "ap_finish: Q=%d", Q);
+  CMH_CHECK_ARG(bits > 0 && bits <= 32 * kRetMaxWords, "ap_finish: bits=%d unsupported", bits);
+  const uint32_t k = topk <= 0 || topk > INT32_MAX ? static_cast<uint32_t>(INT32_MAX) : static_cast<uint32_t>(topk);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(ap_finish_kernel, dim3(Q), dim3(64), 0, st, ap_sum, total_counts, 2 * bits + 1, k, ap);
+  CMH_CHECK_LAUNCH("ap_finish");
+  hipLaunchKernelGGL(ap_mean_kernel, dim3(1), dim3(64), 0, st, ap, Q, map);
+  CMH_CHECK_LAUNCH("ap_finish mean");
+  return CMH_OK;
 }
 
 namespace cmh {

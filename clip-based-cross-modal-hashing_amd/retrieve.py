@@ -11,7 +11,12 @@ with the query (0 = no hit) instead of the 0/1 flag.
 
 searches a saved CodeIndex (CodeIndex.save: any number of items, grown by CodeIndex.add) in place of the .mat's database side; the
 .mat still supplies the queries (the query side of --direction) and their labels.  The database half of --direction is then unused;
-a note on stderr says so when the file holds that side."""
+a note on stderr says so when the file holds that side.
+
+    python retrieve.py --codes <file>.mat --direction i2t --map [--k K]
+
+prints one line, the mAP (mAP@K with --k) of the chosen direction over the file's queries (--queries) against the database side or
+--index, ties by ascending database index, for a database of any size.  It needs labels (q_l, r_l)."""
 import argparse
 import sys
 
@@ -22,7 +27,8 @@ def parse(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--codes", required=True, help=".mat file written by a trainer (save_mat)")
     p.add_argument("--direction", choices=sorted(DIRECTIONS), default="i2t", help="query side -> database side")
-    p.add_argument("--k", type=int, default=10, help="neighbours per query")
+    p.add_argument("--k", type=int, default=None, help="neighbours per query (default 10); with --map: mAP@K (default: the whole database)")
+    p.add_argument("--map", action="store_true", help="print the mAP of the direction in place of the neighbours (needs labels in the file)")
     p.add_argument("--queries", default=":", help="slice a:b of the file's queries (default: all)")
     p.add_argument("--index", default="", metavar="FILE", help="a saved CodeIndex (.npz of CodeIndex.save) as the database, in place of the .mat's database side")
     p.add_argument("--graded", action="store_true", help="print the shared-label count of each neighbour in place of the hit flag (needs labels in the file)")
@@ -56,6 +62,14 @@ def main(argv=None):
     labels = torch.from_numpy(m["q_l"][lo:hi]).float() if index.labels is not None and "q_l" in m else None
     if args.graded and labels is None:
         raise SystemExit(f"--graded: {args.codes} holds no labels (q_l, r_l)")
+    if args.map:
+        if labels is None:
+            raise SystemExit(f"--map: needs labels (q_l of {args.codes} and the database's)")
+        if hi == lo:
+            raise SystemExit("--map: no queries")
+        print(f"{float(index.map(queries, labels, k=args.k)):.8f}")
+        return 0
+    args.k = 10 if args.k is None else args.k
     if hi == lo:
         return 0
     out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]

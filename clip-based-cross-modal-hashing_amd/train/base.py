@@ -290,14 +290,23 @@ class TrainBase(object):
         """calc_map_k for one direction.  With one process per GPU every rank holds the whole code matrices (_gather_code_shards),
         ranks its own contiguous share of the QUERIES against the whole database, and the per-query APs are gathered in query
         order and summed in f32 exactly like the kernel's own mean (reference utils/calc_utils.py:37-38), so the value is the
-        single-GPU one bit for bit (reference call sites train/base.py:259-262, :299-302)."""
+        single-GPU one bit for bit (reference call sites train/base.py:259-262, :299-302).
+        --map-tie-order stable: ties by ascending database index, by counting (utils.retrieval.mean_average_precision), for a
+        database of any size; the query-sharded path is the same."""
+        if getattr(self.args, "map_tie_order", "reference") == "stable":
+            from utils.retrieval import mean_average_precision
+
+            def calc(qB, rB, qL, rL, k, rank, return_ap=False):
+                return mean_average_precision(qB, rB, qL, rL, k=k, return_ap=return_ap)
+        else:
+            calc = calc_map_k
         if not du.active():
-            return calc_map_k(query_codes, retrieval_codes, self.query_labels, self.retrieval_labels, k, self.rank)
+            return calc(query_codes, retrieval_codes, self.query_labels, self.retrieval_labels, k, self.rank)
         n_query = query_codes.shape[0]
         lo, hi = du.query_shard(n_query)
         if hi > lo:
-            _, ap = calc_map_k(query_codes[lo:hi], retrieval_codes, self.query_labels[lo:hi], self.retrieval_labels, k, self.rank,
-                               return_ap=True)
+            _, ap = calc(query_codes[lo:hi], retrieval_codes, self.query_labels[lo:hi], self.retrieval_labels, k, self.rank,
+                         return_ap=True)
         else:
             ap = torch.empty(0, dtype=torch.float32, device=query_codes.device)
         return du.mean_in_query_order(du.gather_query_sharded_ap(ap, n_query))

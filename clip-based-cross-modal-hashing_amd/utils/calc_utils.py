@@ -37,7 +37,16 @@ def calc_hammingDist(B1, B2):
 
 def calc_map_k_matrix(qB, rB, query_L, retrieval_L, k=None, rank=0, return_ap=False, tie_order="reference"):
     """tie_order="reference": the ranking of the reference's torch.sort on the CPU (libstdc++ introsort tie order, bit-exact);
-    "stable": ties by ascending database index (~4x faster, mAP moves in the 4th digit: not the reference's number)."""
+    "stable": ties by ascending database index (~4x faster, mAP moves in the 4th digit: not the reference's number).
+    A database of more than 524 287 items has the "stable" order only, by counting (utils.retrieval.mean_average_precision)."""
+    if tie_order not in ("reference", "stable"):
+        raise ValueError(f"tie_order {tie_order!r}: reference or stable")
+    if rB.shape[0] > N.TOPK_MAX:
+        if tie_order == "reference":
+            raise N.NativeError(f"calc_map_k_matrix: N={rB.shape[0]} exceeds {N.TOPK_MAX}, the largest ranking; the reference's "
+                                f"introsort tie order does not exist there: pass tie_order=\"stable\" (mAP by counting, any size)")
+        from utils.retrieval import mean_average_precision
+        return mean_average_precision(qB, rB, query_L, retrieval_L, k=k, return_ap=return_ap)
     dev = _dev(qB, rB)
     qB, rB = qB.to(dev).float(), rB.to(dev).float()
     qL, rL = query_L.to(dev).float(), retrieval_L.to(dev).float()

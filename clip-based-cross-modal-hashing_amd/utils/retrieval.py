@@ -31,7 +31,11 @@ database up to 2^31 - 1 items and any number of queries: the packed planes are r
 order by cmh_topk_merge (csrc/retrieval_merge.hip), which keeps the order (distance, database index): the result is bit for bit
 what one search over the whole database would give.  Histograms are the int32 sums of the per-shard histograms; queries are cut
 into blocks of QUERIES_MAX rows and the outputs concatenated.  A database and a query set within the limits take exactly the one
-native call they always took.  CodeIndex grows by add() and persists by save() / load()."""
+native call they always took.  CodeIndex grows by add() and persists by save() / load().
+
+mAP.  mean_average_precision is calc_map_k_matrix's number with ties by ascending database index, computed by counting
+(cmh_hamming_ap_partial): a relevant item's rank is a sum of histogram entries and of a cursor, so nothing is sorted and the
+shards' float64 sums add.  It is the only mAP over more than 524 287 items."""
 import torch
 
 import cmh_native as N
@@ -154,6 +158,46 @@ def _hist(qp, rp, bits, ql, rl, shard_items=None):
 def _grade_hist(ql, rl, classes, shard_items=None):
     return _summed("grade_histogram", (ql,), (rl,), shard_items, lambda qc, sc, Q, n: N.label_overlap_hist(
         _rows(ql, qc, Q), _rows(rl, sc, n), classes))
+
+
+def _map_count(what, qp, rp, bits, ql, rl, k=None, shard_items=None):
+    """mAP by counting over any number of shards and query blocks -> (map 0-dim f32 on the GPU, ap f32 [Q]).  One shard: one
+    hamming_ap_partial.  Several: the histogram of the whole database first (the per-shard ones summed), then one call per shard in
+    ascending order with the histogram of the shards before it; the float64 sums add in shard order."""
+    Q, n, blocks, shards = _plan(what, qp, rp, shard_items)
+    if k is not None and int(k) < 1:
+        raise N.NativeError(f"{what}: k={k} below 1")
+    sums, totals = [], []
+    for qcut in blocks:
+        q, qlab = _rows(qp, qcut, Q), _rows(ql, qcut, Q)
+        if len(shards) == 1:
+            acc, total = N.hamming_ap_partial(q, rp, bits, qlab, rl, topk=k, want_counts=True)
+        else:
+            total = N.hamming_hist(q, _rows(rp, shards[0], n), bits, qlab, _rows(rl, shards[0], n))
+            for scut in shards[1:]:
+                total = total + N.hamming_hist(q, _rows(rp, scut, n), bits, qlab, _rows(rl, scut, n))
+            acc = prior = None
+            for scut in shards:
+                part, own = N.hamming_ap_partial(q, _rows(rp, scut, n), bits, qlab, _rows(rl, scut, n), topk=k,
+                                                 total_counts=total, prior_counts=prior, want_counts=True)
+                acc = part if acc is None else acc + part
+                prior = own if prior is None else prior + own
+        sums.append(acc)
+        totals.append(total)
+    one = len(sums) == 1
+    return N.ap_finish(sums[0] if one else torch.cat(sums), totals[0] if one else torch.cat(totals), bits, topk=k)
+
+
+def mean_average_precision(qB, rB, query_L, retrieval_L, k=None, shard_items=None, return_ap=False):
+    """calc_map_k_matrix with ties by ascending database index (torch.sort(stable=True)), by counting: no ranking, any database up
+    to 2^31 - 1 items.  -> mAP as a 0-dim f32 CPU tensor (return_ap: also the per-query APs, f32 [Q] on the GPU).  AP = 0 for a query
+    without relevant items; the mean runs over ALL queries in query order, in f32, like the reference's."""
+    _classes("mean_average_precision", query_L, retrieval_L)
+    dev = _dev(qB, rB)
+    mp, ap = _map_count("mean_average_precision", _codes(qB, dev), _codes(rB, dev), rB.shape[1], _labels(query_L, dev),
+                        _labels(retrieval_L, dev), k, shard_items)
+    mp = mp.cpu()
+    return (mp, ap) if return_ap else mp
 
 
 def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None):
@@ -391,6 +435,20 @@ class CodeIndex:
         m = scio.loadmat(path)
         labels = torch.from_numpy(m["r_l"]).float() if "r_l" in m else None
         return cls(torch.from_numpy(m[side]).float(), labels)
+
+    def map(self, query_codes, query_labels, k=None, return_ap=False):
+        """mean_average_precision of the queries against the index (which must hold labels)."""
+        if self.labels is None:
+            raise N.NativeError("CodeIndex.map: the index holds no labels")
+        if query_labels is None or query_labels.dim() != 2 or query_labels.shape[1] != self.classes:
+            raise N.NativeError(f"CodeIndex.map: needs query labels of {self.classes} classes")
+        qp = _codes(query_codes, self.device)
+        if query_codes.shape[-1] != self.bits:
+            raise N.NativeError(f"CodeIndex.map: {query_codes.shape[-1]}-bit queries for an index of {self.bits} bits")
+        mp, ap = _map_count("CodeIndex.map", qp, self.planes, self.bits, _labels(query_labels, self.device), self.labels, k,
+                            self.shard_items)
+        mp = mp.cpu()
+        return (mp, ap) if return_ap else mp
 
     def search(self, query_codes, k, query_labels=None, graded=False):
         if query_labels is not None and self.labels is None:

@@ -469,6 +469,27 @@ int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q_nz, const 
 size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes);
 int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r_label, int32_t Q, int64_t N, int32_t classes,
                            uint32_t* grade_counts, void* workspace, size_t workspace_bytes, void* stream);
+/* mAP by counting: cmh_hamming_map's AP with CMH_TIE_STABLE ties, without a ranking.  For a relevant item j at half-distance h,
+ *   rank(j) = #{items at h' < h} + #{items at h with index < j} + 1,  relrank(j) = the same counts over the relevant items + 1,
+ *   AP = (1 / total) * sum over the relevant j with relrank(j) <= total of relrank(j) / rank(j),  total = min(k, R)
+ * (utils/calc_utils.py:26-38 `count / tindex` term by term: every term the f32 quotient of the two f32 numbers, summed in float64).
+ * The database of one call may be ONE SHARD of a larger one whose shards are taken in ascending index order:
+ *   total_counts u32 [Q, 2K+1, 2]  cmh_hamming_hist's histogram of the whole database; null = this call's own (a single shard)
+ *   prior_counts u32 [Q, 2K+1, 2]  the histogram of the shards before this one; null = zeros
+ *   counts_out   u32 [Q, 2K+1, 2]  optional: this shard's histogram
+ *   ap_sum       f64 [Q]           this shard's sum of relrank / rank: written, not accumulated.  The sums of the shards add.
+ * topk <= 0 means k = the size of the whole database.  Labels are required.  Q <= 65535, N <= 524287 per call as above; refused
+ * with -1 before any launch: null operands, sizes outside the limits, a workspace below cmh_map_count_workspace_bytes (0 outside
+ * the limits).  Every output word is written once: two calls give equal bits. */
+size_t cmh_map_count_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_hamming_ap_partial(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                           const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                           int64_t topk, const uint32_t* total_counts, const uint32_t* prior_counts, uint32_t* counts_out,
+                           double* ap_sum, void* workspace, size_t workspace_bytes, void* stream);
+/* ap f32 [Q] = ap_sum / min(k, R) in float64, rounded once (0 where R = 0; R = the relevant items of total_counts);
+ * map f32 [1] = the mean over all Q queries as cmh_map_mean forms it.  Any Q >= 1. */
+int cmh_ap_finish(const double* ap_sum, const uint32_t* total_counts, int32_t Q, int32_t bits, int64_t topk, float* ap, float* map,
+                  void* stream);
 /* A database larger than N <= 524287 is searched as shards (utils/retrieval.py: row slices of the packed planes, each within the
  * limits above) and the per-shard lists are folded together in ascending shard order (csrc/retrieval_merge.hip); the result is bit
  * for bit the list of one cmh_hamming_topk over the whole database, i.e. of torch.sort(calc_hammingDist(q, r), stable=True).

@@ -27,7 +27,13 @@ cmh_topk_merge), synthetic codes, same rules (device events, REGIONS regions of 
       compared with torch.sort(stable=True) of the full distance rows.  Reported with the floor of two passes over the same
       item count.
 `merge` is a leg of its own: the fold of the per-shard lists alone (the merge launches of one search on lists computed before
-the timed regions), and `merge_share` its median over the search's."""
+the timed regions), and `merge_share` its median over the search's.
+
+--map runs the mAP legs instead: the mAP by counting (hamming_ap_partial + ap_finish: no ranking) against the two routes there were,
+hamming_map(TIE_STABLE) (the same tie order: a radix sort of N keys per query) and hamming_map(TIE_REFERENCE), at the two shapes
+above, same rules.  `hist` (the counting route's first pass alone) runs next to them.  Per-query APs of the counting route are
+compared with the stable ranking's on the timed inputs (2e-6).  Then 5000 x 2 000 000 x 64 bit in four shards
+(utils.retrieval._map_count), which no other route takes: 16 of its APs are compared with a float64 AP on torch.sort(stable=True)."""
 import argparse
 import json
 import os
@@ -143,12 +149,117 @@ def sharded(args):
         del rB, qB, rp, qp, rl, ql, rL, qL, legs, lists
 
 
+def _timed(legs, regions):
+    """legs: name -> (reps, fn), alternating, device events around each region -> name -> {median, min, max} in ms per call."""
+    import torch
+    times = {k: [] for k in legs}
+    for _ in range(regions):
+        for leg, (reps, fn) in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                out = fn()
+            e1.record()
+            e1.synchronize()
+            del out
+            times[leg].append(e0.elapsed_time(e1) / reps)
+    return {leg: {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)} for leg, ts in times.items()}
+
+
+def _emit(args, line):
+    text = json.dumps(line)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+
+
+def map_legs(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+
+    def operands(Q, n, K, C):
+        g = torch.Generator(device=dev).manual_seed(1)
+        rL = (torch.rand(n, C, generator=g, device=dev) < 0.1).float()
+        qL = (torch.rand(Q, C, generator=g, device=dev) < 0.1).float()
+        rL[:, 0] = 1.0                                            # every query has relevant items: the ranking skips none
+        qL[:, 0] = 1.0
+        qL[:, 0][::7] = 0.0                                       # ... but not every pair is relevant
+        rL[:, 0][::3] = 0.0
+        Wm = torch.randn(C, K, generator=g, device=dev)
+        mk = lambda lab: torch.sign(lab @ Wm + 0.5 * torch.randn(lab.shape[0], K, generator=g, device=dev) + 1e-3)
+        return mk(qL), mk(rL), qL, rL
+
+    for name in args.shapes:
+        Q, n, K, C = SHAPES[name]
+        qB, rB, qL, rL = operands(Q, n, K, C)
+        qp, rp, ql, rl = N.pack_codes(qB), N.pack_codes(rB), N.pack_labels(qL), N.pack_labels(rL)
+        del qB, rB
+
+        def counting():
+            s, counts = N.hamming_ap_partial(qp, rp, K, ql, rl, want_counts=True)
+            return N.ap_finish(s, counts, K)
+
+        legs = {
+            "counting": (args.reps, counting),
+            "hist": (args.reps, lambda: N.hamming_hist(qp, rp, K, ql, rl)),
+            "stable": (1, lambda: N.hamming_map(qp, ql, rp, rl, K, C, tie_order=N.TIE_STABLE)[:2]),
+            "reference": (1, lambda: N.hamming_map(qp, ql, rp, rl, K, C, tie_order=N.TIE_REFERENCE)[:2]),
+        }
+        outs = {leg: fn() for leg, (_, fn) in legs.items()}        # warm-up, and the outputs on the timed inputs
+        d_ap = float((outs["counting"][1].double() - outs["stable"][1].double()).abs().max())
+        d_map = abs(float(outs["counting"][0]) - float(outs["stable"][0]))
+        relevant_share = float(outs["hist"][:, :, 1].sum().double() / (Q * n))
+        del outs
+        torch.cuda.synchronize()
+        line = {"tool": "retrieval_bench", "leg": "map", "shape": name, "Q": Q, "N": n, "bits": K, "classes": C, "regions": REGIONS,
+                "relevant_share": round(relevant_share, 4), "max_ap_diff_vs_stable": d_ap, "map_diff_vs_stable": d_map,
+                "outputs_equal": d_ap <= 2e-6 and d_map <= 2e-6, "ms": _timed(legs, REGIONS)}
+        for base in ("stable", "reference"):
+            line["ms"]["counting"][f"{base}_over_counting"] = round(line["ms"][base]["median"] / line["ms"]["counting"]["median"], 3)
+        line["ms"]["counting"]["over_hist"] = round(line["ms"]["counting"]["median"] / line["ms"]["hist"]["median"], 3)
+        _emit(args, line)
+        if not line["outputs_equal"]:
+            raise SystemExit(f"{name}: the mAP by counting disagrees with the stable ranking")
+        del qp, rp, ql, rl, legs
+    if args.no_large:
+        return
+    Q, n, K, C = 5000, 2000000, 64, 24
+    qB, rB, qL, rL = operands(Q, n, K, C)
+    qp, rp, ql, rl = N.pack_codes(qB), N.pack_codes(rB), N.pack_labels(qL), N.pack_labels(rL)
+    legs = {"counting": (1, lambda: R._map_count("bench", qp, rp, K, ql, rl)),
+            "search_k1000": (1, lambda: R._search("bench", qp, rp, K, 1000, ql, rl)[:3])}
+    mp, ap = legs["counting"][1]()
+    legs["search_k1000"][1]()
+    rows = 16
+    order = torch.sort((K - qB[:rows] @ rB.T), dim=1, stable=True)[1]
+    hits = ((qL[:rows] @ rL.T) > 0).gather(1, order)
+    del order
+    pos = torch.arange(1, n + 1, device=dev, dtype=torch.float64)
+    want = ((hits.cumsum(1).double() / pos) * hits).sum(1) / hits.sum(1).clamp(min=1)
+    d_ap = float((ap[:rows].double() - want).abs().max())
+    del hits, pos, qB, rB
+    torch.cuda.synchronize()
+    line = {"tool": "retrieval_bench", "leg": "map", "shape": "synthetic_2000000_64", "Q": Q, "N": n, "bits": K, "classes": C,
+            "shards": len(R._cuts(n, R.SHARD_ITEMS)), "regions": REGIONS, "map": float(mp), "max_ap_diff_vs_float64_sort": d_ap,
+            "outputs_equal": d_ap <= 2.4e-7, "ms": _timed(legs, REGIONS)}
+    line["ms"]["counting"]["over_search_k1000"] = round(line["ms"]["counting"]["median"] / line["ms"]["search_k1000"]["median"], 3)
+    _emit(args, line)
+    if not line["outputs_equal"]:
+        raise SystemExit("synthetic_2000000_64: the sharded mAP by counting disagrees with the float64 AP on a stable sort")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--reps", type=int, default=5, help="calls per timed region of the new legs")
     ap.add_argument("--out", default="", help="append the JSON lines to this file")
     ap.add_argument("--sharded", action="store_true", help="run the sharded leg (see above) instead of the others")
+    ap.add_argument("--map", action="store_true", help="run the mAP legs (see above) instead of the others")
+    ap.add_argument("--no-large", action="store_true", help="--map: leave out the 2 000 000-item database")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -156,6 +267,8 @@ def main():
         raise SystemExit("retrieval_bench needs a GPU: nothing is measured without one")
     if args.sharded:
         return sharded(args)
+    if args.map:
+        return map_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
