@@ -38,6 +38,8 @@ def add_flags(parser, table):
             kw["choices"] = ["f32", "bf16", "fp8"]      # fp8: inference only (--is-train false)
         if flag == "--map-tie-order":
             kw["choices"] = ["reference", "stable"]
+        if flag == "--noise-assign":
+            kw["choices"] = ["gpu", "host"]
         parser.add_argument(flag, **kw)
     return parser
 

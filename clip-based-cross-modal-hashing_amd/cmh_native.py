@@ -161,6 +161,8 @@ SIGNATURES = {
     "cmh_twdh_targets": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
     "cmh_twdh_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _sz, _p]),
     "cmh_dnph_loss": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
+    "cmh_assign_rows_workspace_bytes": (_sz, [_i32, _i32]),
+    "cmh_assign_rows": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
     "cmh_vit_encode_tokens": (C.c_int, [C.POINTER(VitWeights), _p, _i32, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens_packed": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
@@ -1051,6 +1053,30 @@ def dnph_loss(hash_img, hash_txt, pre_img, pre_txt, label, proxies, noise_img=No
     check(lib().cmh_dnph_loss(*[ptr(t) for t in ts], ptr(ni), ptr(nt), B, K, Cn, float(margin), float(noise_weight),
                               ptr(out), ptr(ws), ws.numel(), stream_ptr(ts[0].device)), "cmh_dnph_loss")
     return out[0], out[1], out[2]
+
+
+def assign_rows(emb, rows, return_col=False):
+    """gene_noise on the device (train/DNPH_TOMM/b_reg.py): emb f32 [P, B, K] (or [B, K]) and the noise matrix rows f32 [B, K] ->
+    the rows of `rows` assigned to the samples of each problem at minimal total L2 cost, f32 like emb; with return_col also the
+    permutation, int32 [P, B] (row i gets rows[col[p, i]]).  No host synchronisation."""
+    emb, rows = f32c(emb), f32c(rows)
+    require_gpu(emb, rows)
+    single = emb.dim() == 2
+    if single:
+        emb = emb.unsqueeze(0)
+    if emb.dim() != 3 or rows.dim() != 2:
+        raise NativeError(f"assign_rows: emb {tuple(emb.shape)} / rows {tuple(rows.shape)}, expected [P, B, K] and [B, K]")
+    P, B, K = emb.shape
+    fit("assign_rows", (rows, (B, K)))
+    dev = emb.device
+    out = torch.empty(P, B, K, dtype=torch.float32, device=dev)
+    col = torch.empty(P, B, dtype=torch.int32, device=dev) if return_col else None
+    ws = workspace(lib().cmh_assign_rows_workspace_bytes(P, B), dev, f"assign@{stream_ptr(dev)}")
+    check(lib().cmh_assign_rows(ptr(emb), ptr(rows), P, B, K, ptr(out), ptr(col), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_assign_rows")
+    if single:
+        out, col = out[0], (None if col is None else col[0])
+    return (out, col) if return_col else out
 
 
 # ------------------------------------------------------------------------------------------ optimiser

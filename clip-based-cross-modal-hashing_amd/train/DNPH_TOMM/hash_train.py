@@ -1,5 +1,6 @@
 """DNPH (TOMM) trainer (reference train/DNPH_TOMM/hash_train.py:16-89): forward, loss, backward (heads, classifier and both
-towers) and the fused BertAdam step all run on libcmh.  The Hungarian noise assignment stays numpy on the host, like upstream."""
+towers), the Hungarian noise assignment and the fused BertAdam step all run on libcmh (--noise-assign host: the assignment on
+the host with scipy, like upstream)."""
 import os
 import time
 
@@ -8,7 +9,7 @@ import torch
 from model.DNPH_TOMM import MDNPH
 from model.base.optimization import BertAdam
 from train.base import TrainBase
-from .b_reg import gene_noise, rand_unit_rect
+from .b_reg import assign_noise, rand_unit_rect
 from .get_args import get_args
 from .loss import DNPH_out
 
@@ -44,15 +45,14 @@ class DNPHTOMMTrainer(TrainBase):
         self.optimizer_loss = torch.optim.SGD(params=self.DNPH.parameters(), lr=1e-4)
 
     def noise_rows(self, hash_img, hash_text):
-        """The uniform-distribution regulariser's targets (b_reg.py): one random +-1 matrix per step, assigned to the samples of
-        each modality by the Hungarian method on the host (numpy / scipy, as upstream)."""
+        """The uniform-distribution regulariser's targets (b_reg.py): one random +-1 matrix per step (numpy's stream, as
+        upstream), assigned to the samples of each modality by the Hungarian method: on the device in one call for both
+        modalities (--noise-assign gpu), or on the host with scipy as upstream (--noise-assign host)."""
         s_vector = rand_unit_rect(*hash_img.shape)
-        on_host = lambda h: h.cpu().detach().numpy()
-        to_dev = lambda a: torch.from_numpy(a).float().to(self.rank)
-        return to_dev(gene_noise(on_host(hash_img), s_vector)), to_dev(gene_noise(on_host(hash_text), s_vector))
+        return assign_noise(hash_img, hash_text, s_vector, getattr(self.args, "noise_assign", "gpu"))
 
     def compute_loss(self, hash_img, pre_img, hash_text, pre_text, label):
-        i_noises, t_noises = self.noise_rows(hash_img, hash_text)        # Hungarian assignment: host work on the rank's own batch
+        i_noises, t_noises = self.noise_rows(hash_img, hash_text)        # Hungarian assignment on the rank's own batch
         # several ranks: ONE fused all-gather of [B_local, 4K + 3C] (hashes, classifier outputs, labels, assigned noise rows);
         # DNPH_out and the noise term are then evaluated on the global batch
         hash_img, pre_img, hash_text, pre_text, label, i_noises, t_noises = self.loss_inputs(

@@ -557,12 +557,23 @@ int cmh_twdh_loss(const float* p_img, const float* p_txt, const float* target, i
 
 /* DNPH_out.forward + the noise term of the DNPH step (train/DNPH_TOMM/loss.py:14-32,
  * train/DNPH_TOMM/hash_train.py:70-81).  hash_* f32 [B,K], pre_* f32 [B,C], label f32 [B,C], proxies [C,K],
- * noise_* f32 [B,K] (the Hungarian-assigned +-1 rows, host-side as upstream) or both NULL.
+ * noise_* f32 [B,K] (the Hungarian-assigned +-1 rows: cmh_assign_rows, or upstream's host path) or both NULL.
  * out3[0] = p_loss + d_loss - noise_weight*noise, out3[1] = p_loss + d_loss, out3[2] = noise. */
 int cmh_dnph_loss(const float* hash_img, const float* hash_txt, const float* pre_img, const float* pre_txt,
                   const float* label, const float* proxies, const float* noise_img, const float* noise_txt,
                   int32_t B, int32_t K, int32_t C, float margin, float noise_weight, float* out3,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* gene_noise of the DNPH step (train/DNPH_TOMM/b_reg.py:5-40) for P modalities that share one noise matrix, on the device:
+ * cost[p][i][j] = || emb[p][i] - rows[j] ||_2 in f64 (f32 inputs widened, the sum over k in index order), the square linear
+ * assignment problem of each p solved exactly (shortest augmenting paths, f64 duals - scipy's algorithm family), and
+ * out[p][i] = rows[col4row[p][i]].  emb f32 [P,B,K], rows f32 [B,K] (upstream: +-1), out f32 [P,B,K], col_out i32 [P,B] or NULL.
+ * 1 <= B <= 1024, K >= 1, P >= 1.  Where several assignments have exactly the optimal cost, the one returned is fixed by the
+ * solver's tie rule (lowest reduced cost, then an unassigned column, then the lowest column index): the same on every run, not
+ * necessarily scipy's.  Values must be finite.  workspace >= cmh_assign_rows_workspace_bytes(P, B) (0 for sizes out of range). */
+size_t cmh_assign_rows_workspace_bytes(int32_t P, int32_t B);
+int cmh_assign_rows(const float* emb, const float* rows, int32_t P, int32_t B, int32_t K, float* out, int32_t* col_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MITH (BASELINE.json config 3): token-returning trunk, HashingModel pieces, losses.
