@@ -150,6 +150,8 @@ SIGNATURES = {
     "cmh_hamming_topk_graded": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_map_count_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_hamming_ap_partial": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_range_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_hamming_range": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_ap_finish": (C.c_int, [_p, _p, _i32, _i32, _i64, _p, _p, _p]),
     "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
@@ -811,6 +813,42 @@ def hamming_topk_graded(q_planes, r_planes, bits, k, q_lab, r_lab, want_counts=F
                                         ptr(idx), ptr(dist), None, ptr(grade), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)),
           "cmh_hamming_topk_graded")
     return (idx, dist, grade, counts) if want_counts else (idx, dist, grade)
+
+
+def hamming_range(q_planes, r_planes, bits, radius_h, q_lab=None, r_lab=None, total_counts=None, prior_counts=None, row_off=None,
+                  idx_base=0, out=None, want_counts=False):
+    """The fill pass of a radius search: every database item at half-distance h <= radius_h from query q goes into the flat buffers
+    out = (idx int32 [T], dist f32 [T], rel uint8 [T] or None), at row_off[q] (int64 [Q]) + its place in the order (distance, database
+    index); idx = idx_base + its row, dist = 0.5 * h.  The caller sizes the rows from hamming_hist: query q writes exactly
+    [row_off[q], row_off[q] + ball(q)), ball(q) = the items of total_counts (None: of this database) in the bins 0..radius_h, and
+    nothing else of `out`.  total_counts / prior_counts: the histograms of the whole database and of the shards before this one, as
+    hamming_ap_partial takes them.  -> out [+ this database's counts with want_counts]."""
+    qs, qn, rs, rn, Q, N, LW = _retrieval_operands("hamming_range", q_planes, r_planes, bits, q_lab, r_lab)
+    dev = qs.device
+    radius_h, idx_base = int(radius_h), int(idx_base)
+    if not 0 <= radius_h <= 2 * int(bits):
+        raise NativeError(f"hamming_range: radius_h={radius_h} outside [0, {2 * int(bits)}]")
+    if not 0 <= idx_base <= 2 ** 31 - 1 - N:
+        raise NativeError(f"hamming_range: idx_base={idx_base} outside [0, 2^31 - 1 - N]")
+    total_counts = _counts_operand("hamming_range", "total_counts", total_counts, Q, bits, dev)
+    prior_counts = _counts_operand("hamming_range", "prior_counts", prior_counts, Q, bits, dev)
+    if row_off is None or row_off.dtype != torch.int64 or tuple(row_off.shape) != (Q,) or not row_off.is_contiguous() or row_off.device != dev:
+        raise NativeError("hamming_range: row_off is a contiguous int64 tensor [Q] on the operands' device")
+    if not isinstance(out, (tuple, list)) or len(out) != 3 or out[0] is None or out[1] is None:
+        raise NativeError("hamming_range: out is an (idx, dist, rel or None) tuple of flat buffers")
+    idx, dist, rel = out
+    if rel is not None and not LW:
+        raise NativeError("hamming_range: hit flags asked for without labels")
+    for t, dt in ((idx, torch.int32), (dist, torch.float32), (rel, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev or t.numel() != idx.numel()):
+            raise NativeError("hamming_range: out holds contiguous flat int32 idx, float32 dist and uint8 rel buffers of one length "
+                              "on the operands' device")
+    counts = torch.empty(Q, 2 * int(bits) + 1, 2, dtype=torch.int32, device=dev) if want_counts else None
+    ws = workspace(lib().cmh_range_workspace_bytes(Q, N, int(bits)), dev, "retrieval")
+    check(lib().cmh_hamming_range(ptr(qs), ptr(qn), ptr(q_lab), ptr(rs), ptr(rn), ptr(r_lab), Q, N, int(bits), 32 * LW, radius_h,
+                                  ptr(total_counts), ptr(prior_counts), ptr(row_off), idx_base, ptr(idx), ptr(dist), ptr(rel),
+                                  ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_range")
+    return ((idx, dist, rel), counts) if want_counts else (idx, dist, rel)
 
 
 def label_overlap_hist(q_lab, r_lab, classes):

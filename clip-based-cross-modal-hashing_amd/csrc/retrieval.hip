@@ -40,6 +40,11 @@
 //                            one shard of a larger one: the histogram pass, three small kernels that turn its images into 32-bit
 //                            bases per (chunk, bin, lane), and a second walk whose packed LDS cursor gives both positions of an item.
 //   cmh_ap_finish            ap = sum / min(k, R), map = their f32 mean in query order.
+//
+// Radius search (every item within a Hamming radius, as ragged lists; any database size, as shards):
+//   cmh_hamming_range        the select pass without a k: the histogram pass, three small kernels that turn its images into the
+//                            32-bit in-row base of every (chunk, bin <= radius, lane), and a second walk that stores item j at
+//                            row_off[q] + its base's cursor.  The caller sizes the rows from cmh_hamming_hist.
 #include "cmh_common.h"
 
 namespace cmh {
@@ -632,6 +637,151 @@ __global__ __launch_bounds__(64) void ap_mean_kernel(const float* __restrict__ a
   if (threadIdx.x == 0) out[0] = acc / static_cast<float>(Q);
 }
 
+// ---- radius search (cmh_hamming_range) ----------------------------------------------------------------------------------------------
+// Every item at h <= hr, as a ragged list per query in the order (h, database index): the select pass without a k.  An item j of this
+// call at bin h goes to
+//   row_off[q] + #{items of the whole database at h' < h} + #{items at h in earlier shards} + #{items of this call at h, index < j}.
+// Pass 1 is hist_kernel.  The three kernels below follow ap_total / ap_scan / ap_base over the items alone: every image becomes the
+// 32-bit in-row BASE of its (chunk, bin, lane), for the bins up to hr only; range_kernel then walks its chunk in index order with the
+// bases as its private cursors and adds row_off as int64 at the store.  ball[q] = the whole database's items at h <= hr: a position
+// at or behind it is never stored (it cannot arise from consistent histograms; an inconsistent `total` then loses entries and writes
+// nothing outside the query's own rows).
+struct RangeArgs {
+  const uint32_t* total;   // [Q][bins][2] of the whole database, or null: this call's own
+  const uint32_t* prior;   // [Q][bins][2] of the shards before this one, or null: none
+  uint32_t* toti;          // [tiles][bins][64] this call's items per bin -> exclusive prefix over the bins of the whole database
+  uint32_t* ball;          // [tiles * 64] items of the whole database at h <= hr (0 behind the last query)
+  int hr;
+};
+
+// the images of a tile summed over the chunks -> toti (and counts)
+__global__ __launch_bounds__(256) void range_total_kernel(RetArgs a, RangeArgs p) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= stride) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t hb = t >> 6;
+  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
+  uint32_t tot = 0, rel = 0;
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * stride + t];
+    tot += v & 0xffffu;
+    rel += v >> 16;
+  }
+  p.toti[t] = tot;
+  const int q = tile * 64 + lane;
+  if (a.counts && q < a.Q) {
+    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
+    o[0] = tot - rel;
+    o[1] = rel;
+  }
+}
+
+// per query: toti becomes the exclusive prefix over the bins <= hr of the whole database's histogram; ball = its end
+__global__ __launch_bounds__(64) void range_scan_kernel(RetArgs a, RangeArgs p) {
+  const int lane = threadIdx.x, tile = blockIdx.x;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  const size_t base = static_cast<size_t>(tile) * a.bins * 64 + lane;
+  uint32_t run = 0;
+  for (int h = 0; h <= p.hr; ++h) {
+    const size_t t = base + static_cast<size_t>(h) * 64;
+    uint32_t ni;
+    if (p.total) {
+      const uint32_t* c = p.total + (static_cast<size_t>(q) * a.bins + h) * 2;
+      ni = c[0] + c[1];
+    } else {
+      ni = p.toti[t];
+    }
+    p.toti[t] = run;
+    run += ni;
+  }
+  p.ball[tile * 64 + lane] = qa < a.Q ? run : 0u;
+}
+
+// every image of a bin <= hr becomes the in-row base of its (chunk, bin, lane)
+__global__ __launch_bounds__(256) void range_base_kernel(RetArgs a, RangeArgs p) {
+  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
+  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int used = p.hr + 1;
+  if (t >= static_cast<size_t>(a.tiles) * used * 64) return;
+  const int lane = static_cast<int>(t & 63);
+  const size_t hb = t >> 6;
+  const int h = static_cast<int>(hb % used), tile = static_cast<int>(hb / used);
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  const size_t w = (static_cast<size_t>(tile) * a.bins + h) * 64 + lane;
+  uint32_t bi = p.toti[w];
+  if (p.prior) {
+    const uint32_t* c = p.prior + (static_cast<size_t>(q) * a.bins + h) * 2;
+    bi += c[0] + c[1];
+  }
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * stride + w];
+    a.img[c * stride + w] = bi;
+    bi += v & 0xffffu;
+  }
+}
+
+// ---- pass 2 of the radius search: the stable counting sort of the items at h <= hr into the queries' rows -------------------------
+// select_kernel's walk.  The cursors are the bases of the bins 0..hr: (hr + 1) * 256 bytes of LDS (GLOB: the bases themselves,
+// advanced with global atomics; a lane owns its words).  (row_off, ball, hr and idx_base are trailing parameters, not members of
+// RetArgs: the argument layout of the other kernels stays what it was.)
+template <int WT, int LT, bool GLOB>
+__global__ __launch_bounds__(64) void range_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
+                                                   const uint32_t* __restrict__ rl, const int64_t* __restrict__ row_off,
+                                                   const uint32_t* __restrict__ ball, int hr, int idx_base) {
+  extern __shared__ uint32_t smem[];
+  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
+  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
+  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  uint32_t* cur = GLOB ? image : smem;
+  Tile<WT, LT> t;
+  t.load(a, q, lane, smem + (GLOB ? 0 : (hr + 1) * 64));
+  const int hq = qa < a.Q ? hr : -1;               // a lane behind the last query places nothing
+  if (!GLOB)
+    for (int h = 0; h <= hr; ++h) cur[h * 64 + lane] = image[h * 64 + lane];
+  __syncthreads();
+  const int64_t row = row_off[q];
+  const uint32_t end = ball[tile * 64 + lane];
+  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  auto place = [&](int j, int h) {
+    if (h <= hq) {
+      const uint32_t p = atomicAdd(&cur[h * 64 + lane], 1u);
+      if (p < end) {
+        const int64_t o = row + static_cast<int64_t>(p);
+        a.idx[o] = idx_base + j;
+        a.dist[o] = 0.5f * static_cast<float>(h);
+        if (a.rel) a.rel[o] = static_cast<uint8_t>(t.relevant(rl + static_cast<size_t>(j) * a.LW));
+      }
+    }
+  };
+  int j = jb;
+  if (WT > 0) {
+    using G = Group<WT, LT>;
+    auto work = [&](const G& g, int j0, int u0, int u1) {
+#pragma unroll
+      for (int u = u0; u < u1; ++u) place(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
+    };
+    const int groups = (je - jb) / G::U;
+    G ga, gb;                                                       // two register sets, fetched as in select_kernel
+    int g = 0;
+    if (groups > 0) ga.load(rs, rn, rl, jb, false);
+    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
+      work(ga, j, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      gb.load(rs, rn, rl, j + G::U, false);
+      __builtin_amdgcn_sched_barrier(0);
+      work(ga, j, 1, G::U);
+      work(gb, j + G::U, 0, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, false);
+      __builtin_amdgcn_sched_barrier(0);
+      work(gb, j + G::U, 1, G::U);
+    }
+    if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+  }
+  for (; j < je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 struct Plan {
   int bins, W, tiles, S, chunk, tb;      // tb = query tiles per batch (the images of one batch fit kImageCap)
@@ -863,6 +1013,82 @@ int run_ap(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label
   return CMH_OK;
 }
 
+template <int WT, int LT, bool GLOB>
+int launch_range(const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, const int64_t* row_off,
+                 int idx_base, hipStream_t st) {
+  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(p.hr + 1) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
+  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(range_kernel<WT, LT, GLOB>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "hamming_range: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL((range_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, row_off, p.ball, p.hr, idx_base);
+  CMH_CHECK_LAUNCH("hamming_range");
+  return CMH_OK;
+}
+
+template <int WT, bool GLOB>
+int launch_range_labels(const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl,
+                        const int64_t* row_off, int idx_base, hipStream_t st) {
+  if (a.LW == 0) return launch_range<WT, LAB_NONE, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
+  if (!GLOB && a.LW == 1) return launch_range<WT, 1, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
+  if (!GLOB && a.LW == 3) return launch_range<WT, 3, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
+  return launch_range<WT, LAB_ANY, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
+}
+
+int launch_range_any(bool glob, const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl,
+                     const int64_t* row_off, int idx_base, hipStream_t st) {
+  if (glob) return launch_range_labels<0, true>(a, p, rs, rn, rl, row_off, idx_base, st);
+  if (a.W == 1) return launch_range_labels<1, false>(a, p, rs, rn, rl, row_off, idx_base, st);
+  if (a.W == 2) return launch_range_labels<2, false>(a, p, rs, rn, rl, row_off, idx_base, st);
+  if (a.W == 3) return launch_range_labels<3, false>(a, p, rs, rn, rl, row_off, idx_base, st);
+  return launch_range_labels<4, false>(a, p, rs, rn, rl, row_off, idx_base, st);
+}
+
+// hist, the bases and the fill, in batches of query tiles.  The workspace is that of run(): images [S], toti where run() keeps off,
+// ball where it keeps hstar.
+int run_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign, const uint32_t* r_nz,
+              const uint32_t* r_label, int Q, int64_t N, int bits, int classes, int hr, const uint32_t* total, const uint32_t* prior,
+              const int64_t* row_off, int idx_base, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts, void* workspace,
+              hipStream_t st) {
+  const Plan p = make_plan(Q, N, bits);
+  RetArgs a = {};
+  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = q_label ? (classes + 31) / 32 : 0; a.bins = p.bins;
+  a.S = p.S; a.chunk = p.chunk;
+  a.idx = idx; a.dist = dist; a.rel = rel;      // (whole buffers: a query's rows start at its row_off)
+  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
+    const int q0 = t0 * 64;
+    a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
+    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
+    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
+    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
+    a.ql = q_label ? q_label + static_cast<size_t>(q0) * a.LW : nullptr;
+    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
+    const size_t row = static_cast<size_t>(q0) * a.bins * 2;
+    RangeArgs b;
+    b.total = total ? total + row : nullptr;
+    b.prior = prior ? prior + row : nullptr;
+    a.img = base;
+    b.toti = base + static_cast<size_t>(a.S) * stride;
+    b.ball = b.toti + stride;
+    b.hr = hr;
+    a.counts = counts ? counts + row : nullptr;
+    if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
+      return fail(CMH_ERR_LAUNCH, "hamming_range: memset failed");
+    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
+    if (rc != CMH_OK) return rc;
+    hipLaunchKernelGGL(range_total_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_range totals");
+    hipLaunchKernelGGL(range_scan_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_range scan");
+    const size_t used = static_cast<size_t>(a.tiles) * (hr + 1) * 64;
+    hipLaunchKernelGGL(range_base_kernel, dim3(static_cast<unsigned>((used + 255) / 256)), dim3(256), 0, st, a, b);
+    CMH_CHECK_LAUNCH("hamming_range bases");
+    rc = launch_range_any(p.glob, a, b, r_sign, r_nz, r_label, row_off + q0, idx_base, st);
+    if (rc != CMH_OK) return rc;
+  }
+  return CMH_OK;
+}
+
 }  // namespace
 }  // namespace cmh
 
@@ -946,6 +1172,30 @@ extern "C" int cmh_ap_finish(const double* ap_sum, const uint32_t* total_counts,
   hipLaunchKernelGGL(ap_mean_kernel, dim3(1), dim3(64), 0, st, ap, Q, map);
   CMH_CHECK_LAUNCH("ap_finish mean");
   return CMH_OK;
+}
+
+extern "C" size_t cmh_range_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
+  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
+  return make_plan(Q, N, bits).bytes();
+}
+
+extern "C" int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                                 const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                                 int32_t radius_h, const uint32_t* total_counts, const uint32_t* prior_counts, const int64_t* row_off,
+                                 int32_t idx_base, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts_out, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && row_off && idx && dist, "hamming_range: null pointer");
+  CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_range: labels on one side only");
+  CMH_CHECK_ARG(!rel || q_label, "hamming_range: hit flags asked for without labels");
+  const int rc = check_shape("hamming_range", Q, N, bits, classes, q_label != nullptr);
+  if (rc != CMH_OK) return rc;
+  CMH_CHECK_ARG(radius_h >= 0 && radius_h <= 2 * bits, "hamming_range: radius_h=%d outside [0, %d]", radius_h, 2 * bits);
+  CMH_CHECK_ARG(idx_base >= 0 && idx_base <= INT32_MAX - static_cast<int32_t>(N), "hamming_range: idx_base=%d with N=%lld passes 2^31 - 1",
+                idx_base, static_cast<long long>(N));
+  const size_t need = make_plan(Q, N, bits).bytes();
+  CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_range: workspace %zu < %zu bytes", workspace_bytes, need);
+  return run_range(q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, radius_h, total_counts, prior_counts, row_off,
+                   idx_base, idx, dist, rel, counts_out, workspace, as_stream(stream));
 }
 
 namespace cmh {

@@ -16,7 +16,14 @@ a note on stderr says so when the file holds that side.
     python retrieve.py --codes <file>.mat --direction i2t --map [--k K]
 
 prints one line, the mAP (mAP@K with --k) of the chosen direction over the file's queries (--queries) against the database side or
---index, ties by ascending database index, for a database of any size.  It needs labels (q_l, r_l)."""
+--index, ties by ascending database index, for a database of any size.  It needs labels (q_l, r_l).
+
+    python retrieve.py --codes <file>.mat --direction i2t --radius 2 [--max-hits M]
+
+prints one line per query: its number, then `index:distance` (`index:distance:hit` with labels) for EVERY database item within
+Hamming radius R (the units of the distance column; 0.5 steps count for codes with zeros), nearest first, ties by database index.  A
+query whose ball is empty prints its number alone.  --radius excludes --k, --map and --graded; more than --max-hits entries over
+all queries are refused before they are allocated."""
 import argparse
 import sys
 
@@ -32,7 +39,18 @@ def parse(argv=None):
     p.add_argument("--queries", default=":", help="slice a:b of the file's queries (default: all)")
     p.add_argument("--index", default="", metavar="FILE", help="a saved CodeIndex (.npz of CodeIndex.save) as the database, in place of the .mat's database side")
     p.add_argument("--graded", action="store_true", help="print the shared-label count of each neighbour in place of the hit flag (needs labels in the file)")
-    return p.parse_args(argv)
+    p.add_argument("--radius", type=float, default=None, metavar="R", help="print every database item within Hamming radius R of each query in place of the k nearest")
+    p.add_argument("--max-hits", type=int, default=None, metavar="M", help="with --radius: refuse more than M entries in all (default 2^31 - 1)")
+    args = p.parse_args(argv)
+    if args.radius is not None:
+        for flag, given in (("--k", args.k is not None), ("--map", args.map), ("--graded", args.graded)):
+            if given:
+                p.error(f"--radius and {flag} exclude each other")
+        if args.radius != args.radius or args.radius < 0:
+            p.error(f"--radius {args.radius}: a number >= 0")
+    elif args.max_hits is not None:
+        p.error("--max-hits goes with --radius")
+    return args
 
 
 def query_slice(text, n):
@@ -69,9 +87,15 @@ def main(argv=None):
             raise SystemExit("--map: no queries")
         print(f"{float(index.map(queries, labels, k=args.k)):.8f}")
         return 0
-    args.k = 10 if args.k is None else args.k
     if hi == lo:
         return 0
+    if args.radius is not None:
+        out = [t.cpu().numpy() for t in index.range_search(queries, args.radius, labels, max_hits=args.max_hits)]
+        for i in range(hi - lo):
+            cols = [f"{out[1][j]}:{out[2][j]:g}" + (f":{out[3][j]}" if len(out) == 4 else "") for j in range(out[0][i], out[0][i + 1])]
+            print(" ".join([str(lo + i)] + cols))
+        return 0
+    args.k = 10 if args.k is None else args.k
     out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]
     for i in range(hi - lo):
         cols = [f"{out[0][i, j]}:{out[1][i, j]:g}" + (f":{out[2][i, j]}" if len(out) == 3 else "") for j in range(args.k)]

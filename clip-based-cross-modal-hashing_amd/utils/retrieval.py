@@ -35,7 +35,17 @@ native call they always took.  CodeIndex grows by add() and persists by save() /
 
 mAP.  mean_average_precision is calc_map_k_matrix's number with ties by ascending database index, computed by counting
 (cmh_hamming_ap_partial): a relevant item's rank is a sum of histogram entries and of a cursor, so nothing is sorted and the
-shards' float64 sums add.  It is the only mAP over more than 524 287 items."""
+shards' float64 sums add.  It is the only mAP over more than 524 287 items.
+
+Radius search.  hamming_range returns EVERY database item within a Hamming radius of each query (the hash-lookup protocol that
+pr_curve's precision-within-radius numbers describe), as a ragged CSR result: offsets int64 [Q+1], and idx / dist / rel of
+T = offsets[Q] entries in which query q owns offsets[q]:offsets[q+1], ordered by (distance, database index): bit for bit the first
+ball(q) columns of hamming_topk.  `radius` is in calc_hammingDist's units (the dist column); in half-units hr = min(2K,
+floor(2 * radius)), and an item belongs to the ball iff h <= hr.  The histogram sizes the lists (the one device-to-host read per
+query block is T), cmh_hamming_range fills them: memory is the sum of the balls, not Q x the largest one, and a ball may be wider
+than CMH_TOPK_MAX.  Shards fill one allocation in ascending order; empty balls are legal."""
+import math
+
 import torch
 
 import cmh_native as N
@@ -200,6 +210,70 @@ def mean_average_precision(qB, rB, query_L, retrieval_L, k=None, shard_items=Non
     return (mp, ap) if return_ap else mp
 
 
+def radius_half_units(radius, bits):
+    """A radius in calc_hammingDist's units -> hr = min(2K, floor(2 * radius)) half-units; negative or NaN is refused."""
+    r = float(radius)
+    if r != r or r < 0:
+        raise N.NativeError(f"radius={radius}: a Hamming radius is a number >= 0")
+    return 2 * int(bits) if r >= int(bits) else int(math.floor(2 * r))
+
+
+def _range(what, qp, rp, bits, hr, ql, rl, shard_items=None, max_hits=None):
+    """Every item at half-distance <= hr over any number of shards and query blocks -> (offsets int64 [Q+1], idx int32 [T],
+    dist f32 [T], rel uint8 [T] or None without labels).  Per query block: the histogram of the whole database (the per-shard ones
+    summed), its balls' prefix sum = the offsets, T read back (the only device-to-host read) and checked against max_hits before
+    anything is allocated for the block, one allocation, then one fill per shard in ascending order with the histogram of the
+    shards before it.  T = 0 launches no fill."""
+    Q, n, blocks, shards = _plan(what, qp, rp, shard_items)
+    limit = ITEMS_MAX if max_hits is None else int(max_hits)
+    if limit < 0:
+        raise N.NativeError(f"{what}: max_hits={max_hits} below 0")
+    dev = qp[0].device
+    parts, hits = [], 0
+    for qcut in blocks:
+        q, qlab = _rows(qp, qcut, Q), _rows(ql, qcut, Q)
+        total = N.hamming_hist(q, _rows(rp, shards[0], n), bits, qlab, _rows(rl, shards[0], n))
+        for scut in shards[1:]:
+            total = total + N.hamming_hist(q, _rows(rp, scut, n), bits, qlab, _rows(rl, scut, n))
+        off = torch.zeros(qcut[1] - qcut[0] + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(total[:, :hr + 1].sum((1, 2)), 0, out=off[1:])
+        T = int(off[-1])
+        hits += T
+        if hits > limit:
+            raise N.NativeError(f"{what}: T={hits} hits exceed max_hits={limit}")
+        out = (torch.empty(T, dtype=torch.int32, device=dev), torch.empty(T, dtype=torch.float32, device=dev),
+               None if ql is None else torch.empty(T, dtype=torch.uint8, device=dev))
+        if T:
+            row_off, prior = off[:-1], None
+            for s, scut in enumerate(shards):
+                more = s + 1 < len(shards)
+                got = N.hamming_range(q, _rows(rp, scut, n), bits, hr, qlab, _rows(rl, scut, n), total_counts=total, prior_counts=prior,
+                                      row_off=row_off, idx_base=scut[0], out=out, want_counts=more)
+                if more:
+                    prior = got[1] if prior is None else prior + got[1]
+        parts.append((off,) + out)
+    if len(parts) == 1:
+        return parts[0]
+    offs, base = [parts[0][0]], parts[0][0][-1]
+    for p in parts[1:]:
+        offs.append(p[0][1:] + base)
+        base = offs[-1][-1]
+    return (torch.cat(offs),) + tuple(None if ts[0] is None else torch.cat(ts) for ts in zip(*[p[1:] for p in parts]))
+
+
+def hamming_range(qB, rB, radius, query_L=None, retrieval_L=None, shard_items=None, max_hits=None):
+    """-> (offsets int64 [Q+1], idx int32 [T], dist f32 [T][, rel uint8 [T] with labels]) on the GPU: every database code within
+    `radius` (calc_hammingDist's units) of every query; query q's list is idx[offsets[q]:offsets[q+1]], ordered by (distance,
+    database index).  T = offsets[Q]; more than max_hits (default 2^31 - 1) entries are refused before they are allocated."""
+    if (query_L is None) != (retrieval_L is None):
+        raise N.NativeError("hamming_range: labels on one side only")
+    hr = radius_half_units(radius, rB.shape[-1])
+    dev = _dev(qB, rB)
+    off, idx, dist, rel = _range("hamming_range", _codes(qB, dev), _codes(rB, dev), rB.shape[-1], hr, _labels(query_L, dev),
+                                 _labels(retrieval_L, dev), shard_items, max_hits)
+    return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+
 def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k][, rel uint8 [Q, k] with labels]): the k nearest database codes of every query."""
     if (query_L is None) != (retrieval_L is None):
@@ -334,7 +408,8 @@ def topn_precision(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN, shard_items=
 
 
 class CodeIndex:
-    """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's).
+    """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
+    range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
     plane that add() grows geometrically, so many small add()s never make many small shards.  save() / load() keep the packed
     planes and labels as one .npz (data only)."""
@@ -463,3 +538,29 @@ class CodeIndex:
         idx, dist, rel, _ = _search("CodeIndex.search", _codes(query_codes, self.device), self.planes, self.bits, k, ql, rl,
                                     self.shard_items)
         return (idx, dist) if rel is None else (idx, dist, rel)
+
+    def range_search(self, query_codes, radius, query_labels=None, max_hits=None):
+        """hamming_range of the queries against the index: (offsets, idx, dist[, rel with query labels])."""
+        if query_labels is not None and self.labels is None:
+            raise N.NativeError("CodeIndex.range_search: query labels given, but the index has none")
+        if query_codes.shape[-1] != self.bits:
+            raise N.NativeError(f"CodeIndex.range_search: {query_codes.shape[-1]}-bit queries for an index of {self.bits} bits")
+        ql = _labels(query_labels, self.device)
+        off, idx, dist, rel = _range("CodeIndex.range_search", _codes(query_codes, self.device), self.planes, self.bits,
+                                     radius_half_units(radius, self.bits), ql, self.labels if ql is not None else None,
+                                     self.shard_items, max_hits)
+        return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+    def duplicates(self, radius=0, max_hits=None):
+        """The index searched against itself: for every item the OTHER items within `radius`, as hamming_range's CSR tuple (rel when
+        the index holds labels).  An item's own entry is taken out of its list (it is there whenever the item lies within the
+        radius of itself: a code with z zeros is at distance z / 2 from itself).  max_hits bounds the lists before that."""
+        off, idx, dist, rel = _range("CodeIndex.duplicates", self.planes, self.planes, self.bits, radius_half_units(radius, self.bits),
+                                     self.labels, self.labels, self.shard_items, max_hits)
+        ball = off[1:] - off[:-1]
+        item = torch.repeat_interleave(torch.arange(self.size, device=self.device), ball, output_size=idx.numel())
+        keep = idx != item
+        own = torch.zeros(self.size, dtype=torch.int64, device=self.device).index_add_(0, item, (~keep).to(torch.int64))
+        out = torch.zeros_like(off)
+        torch.cumsum(ball - own, 0, out=out[1:])
+        return (out, idx[keep], dist[keep]) + (() if rel is None else (rel[keep],))

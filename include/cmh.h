@@ -490,6 +490,29 @@ int cmh_hamming_ap_partial(const uint32_t* q_sign, const uint32_t* q_nz, const u
  * map f32 [1] = the mean over all Q queries as cmh_map_mean forms it.  Any Q >= 1. */
 int cmh_ap_finish(const double* ap_sum, const uint32_t* total_counts, int32_t Q, int32_t bits, int64_t topk, float* ap, float* map,
                   void* stream);
+/* Radius search: EVERY database item at half-distance h <= radius_h from a query (its Hamming ball), as a ragged list per query in
+ * the order (distance, database index): bit for bit the first ball(q) columns of cmh_hamming_topk.  The caller sizes the lists from
+ * cmh_hamming_hist (ball(q) = the items of its bins 0..radius_h) and passes where each starts:
+ *   row_off      i64 [Q]           start of query q's list in idx / dist / rel (an exclusive prefix sum of the balls, or any other
+ *                                  layout in which the rows [row_off[q], row_off[q] + ball(q)) are disjoint)
+ *   total_counts u32 [Q, 2K+1, 2]  cmh_hamming_hist's histogram of the whole database; null = this call's own (a single shard)
+ *   prior_counts u32 [Q, 2K+1, 2]  the histogram of the shards before this one; null = zeros
+ *   idx_base     added to every index written: the database row at which this call's shard starts (idx_base + N <= 2^31 - 1)
+ *   counts_out   u32 [Q, 2K+1, 2]  optional: this shard's histogram
+ * An item j of this call at h <= radius_h is written, once, at
+ *   row_off[q] + #{items of total at h' < h} + prior[q, h] + #{items of this call at h with index < j}
+ * with idx = idx_base + j, dist = 0.5 * h exactly and rel (optional, needs labels) = the item is relevant.  Shards taken in ascending
+ * index order therefore fill one set of buffers with the list of the whole database.  Nothing outside a query's rows is touched
+ * (a position at or behind the ball of total_counts is dropped), there are no atomics on the outputs, two calls give equal bits.
+ * 0 <= radius_h <= 2 * bits.  Q <= 65535, N <= 524287 per call as above; refused with -1 before any launch: null operands, labels on
+ * one side only, rel without labels, radius_h or sizes outside the limits, a workspace below cmh_range_workspace_bytes (0 outside
+ * the limits). */
+size_t cmh_range_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
+                      const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
+                      int32_t radius_h, const uint32_t* total_counts, const uint32_t* prior_counts, const int64_t* row_off,
+                      int32_t idx_base, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
 /* A database larger than N <= 524287 is searched as shards (utils/retrieval.py: row slices of the packed planes, each within the
  * limits above) and the per-shard lists are folded together in ascending shard order (csrc/retrieval_merge.hip); the result is bit
  * for bit the list of one cmh_hamming_topk over the whole database, i.e. of torch.sort(calc_hammingDist(q, r), stable=True).

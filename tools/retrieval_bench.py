@@ -33,7 +33,16 @@ the timed regions), and `merge_share` its median over the search's.
 hamming_map(TIE_STABLE) (the same tie order: a radix sort of N keys per query) and hamming_map(TIE_REFERENCE), at the two shapes
 above, same rules.  `hist` (the counting route's first pass alone) runs next to them.  Per-query APs of the counting route are
 compared with the stable ranking's on the timed inputs (2e-6).  Then 5000 x 2 000 000 x 64 bit in four shards
-(utils.retrieval._map_count), which no other route takes: 16 of its APs are compared with a float64 AP on torch.sort(stable=True)."""
+(utils.retrieval._map_count), which no other route takes: 16 of its APs are compared with a float64 AP on torch.sort(stable=True).
+
+--range runs the radius-search legs instead: utils.retrieval._range (histogram -> offsets -> T read back -> cmh_hamming_range) against
+the only route to the same lists without it, hamming_topk(k = the largest ball of any query, read off the histogram) and a trim of
+every row, at the two shapes above and, per shape, the two radii at which the mean ball is nearest 100 and 1000 items (read off the
+histogram).  Same rules (warm-up, legs alternating in one process, device events around regions of --reps calls); `fill` (the
+native call alone on offsets made before the timed regions) and `hist` run next to them.  The lists of the two routes are compared
+on the timed inputs.  Reported per radius: both times, the output bytes of both routes (T x 9 against Q x kmax x 9), and the floors
+of the new route's three passes over the database (hist, and hist + fill inside the native call) plus its output bytes over HBM
+bandwidth (8 TB/s).  ONE JSON line for all shapes."""
 import argparse
 import json
 import os
@@ -252,6 +261,70 @@ def map_legs(args):
         raise SystemExit("synthetic_2000000_64: the sharded mAP by counting disagrees with the float64 AP on a stable sort")
 
 
+def range_legs(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+    line = {"tool": "retrieval_bench", "leg": "range", "regions": REGIONS, "reps": args.reps, "outputs_equal": True, "shapes": {}}
+    for name in args.shapes:
+        Q, n, K, C = SHAPES[name]
+        g = torch.Generator(device=dev).manual_seed(1)
+        rL = (torch.rand(n, C, generator=g, device=dev) < 0.1).float()
+        qL = (torch.rand(Q, C, generator=g, device=dev) < 0.1).float()
+        rL[:, 0] = 1.0
+        qL[:, 0] = 1.0
+        Wm = torch.randn(C, K, generator=g, device=dev)
+        mk = lambda lab: torch.sign(lab @ Wm + 0.5 * torch.randn(lab.shape[0], K, generator=g, device=dev) + 1e-3)
+        qp, rp, ql, rl = N.pack_codes(mk(qL)), N.pack_codes(mk(rL)), N.pack_labels(qL), N.pack_labels(rL)
+        balls = N.hamming_hist(qp, rp, K, ql, rl).sum(2).cumsum(1)          # [Q, 2K+1]: ball sizes by half-radius
+        mean = balls.double().mean(0).cpu()
+        shape = {"Q": Q, "N": n, "bits": K, "classes": C, "radii": {}}
+        for target in (100, 1000):
+            hr = int((mean.clamp(min=1e-9).log() - torch.log(torch.tensor(float(target), dtype=torch.float64))).abs().argmin())
+            off = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+            off[1:] = balls[:, hr].cumsum(0)
+            T, kmax = int(off[-1]), int(balls[:, hr].max())
+            row_off = off[:-1].contiguous()
+            bufs = (torch.empty(T, dtype=torch.int32, device=dev), torch.empty(T, dtype=torch.float32, device=dev),
+                    torch.empty(T, dtype=torch.uint8, device=dev))
+
+            def trim():
+                ball = N.hamming_hist(qp, rp, K, ql, rl)[:, :hr + 1].sum((1, 2))
+                k = int(ball.max())
+                rows = N.hamming_topk(qp, rp, K, k, ql, rl)
+                head = torch.arange(k, device=dev)[None, :] < ball[:, None]
+                return tuple(r[head] for r in rows)
+
+            big = Q * kmax > 5e7                                              # the baseline's Q x kmax outputs: one call per region then
+            legs = {"range": (args.reps, lambda: R._range("bench", qp, rp, K, hr, ql, rl)),
+                    "topk_trim": (1 if big else args.reps, trim),
+                    "fill": (args.reps, lambda: N.hamming_range(qp, rp, K, hr, ql, rl, row_off=row_off, out=bufs)),
+                    "hist": (args.reps, lambda: N.hamming_hist(qp, rp, K, ql, rl))}
+            new, old = legs["range"][1](), legs["topk_trim"][1]()           # warm-up, and the outputs on the timed inputs
+            legs["fill"][1](), legs["hist"][1]()
+            same = bool(torch.equal(new[0], off)) and all(bool(torch.equal(a, b)) for a, b in zip(new[1:], old))
+            same = same and all(bool(torch.equal(a, b)) for a, b in zip(new[1:], bufs))
+            del new, old
+            torch.cuda.synchronize()
+            ms = _timed(legs, REGIONS)
+            fl = floors_ms(Q, n, K, C, 3)
+            fl["out_bytes"] = T * 9 / 8e12 * 1e3
+            ms["range"]["floor_ms"] = {k: (round(v, 4) if k != "bound" else v) for k, v in fl.items()}
+            ms["range"]["over_topk_trim"] = round(ms["range"]["median"] / ms["topk_trim"]["median"], 4)
+            ms["range"]["over_hist_plus_fill"] = round(ms["range"]["median"] / (ms["hist"]["median"] + ms["fill"]["median"]), 4)
+            shape["radii"][f"mean_ball_{target}"] = {
+                "radius": hr / 2, "radius_h": hr, "mean_ball": round(float(mean[hr]), 2), "largest_ball": kmax, "T": T,
+                "out_bytes_range": T * 9, "out_bytes_topk_trim": Q * kmax * 9, "outputs_equal": same, "ms": ms}
+            line["outputs_equal"] = line["outputs_equal"] and same
+            del bufs, legs
+        line["shapes"][name] = shape
+        del qp, rp, ql, rl, balls
+    _emit(args, line)
+    if not line["outputs_equal"]:
+        raise SystemExit("the radius search disagrees with hamming_topk(k = largest ball) cut at the balls")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
@@ -260,6 +333,7 @@ def main():
     ap.add_argument("--sharded", action="store_true", help="run the sharded leg (see above) instead of the others")
     ap.add_argument("--map", action="store_true", help="run the mAP legs (see above) instead of the others")
     ap.add_argument("--no-large", action="store_true", help="--map: leave out the 2 000 000-item database")
+    ap.add_argument("--range", action="store_true", help="run the radius-search legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -269,6 +343,8 @@ def main():
         return sharded(args)
     if args.map:
         return map_legs(args)
+    if args.range:
+        return range_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
