@@ -45,6 +45,13 @@
 //   cmh_hamming_range        the select pass without a k: the histogram pass, three small kernels that turn its images into the
 //                            32-bit in-row base of every (chunk, bin <= radius, lane), and a second walk that stores item j at
 //                            row_off[q] + its base's cursor.  The caller sizes the rows from cmh_hamming_hist.
+//
+// Written once, used by every entry point: Block (what a pass kernel starts from), walk2 (the software-pipelined walk over a chunk;
+// select_kernel alone keeps a copy of both, for a measured reason given there),
+// the images -> bases family total / scan / base (REL: with the relevant half, the mAP; without, the radius search), and on the host
+// dispatch + launch_walk (run-time shape -> compile-time kernel form) and for_each_batch (query tiles in batches, the histogram pass).
+#include <type_traits>
+
 #include "cmh_common.h"
 
 namespace cmh {
@@ -68,7 +75,8 @@ struct RetArgs {
   int32_t* idx;       // [Q][k]
   float* dist;        // [Q][k]
   uint8_t* rel;       // [Q][k] or null
-};
+};      // (what one kernel alone needs is a trailing parameter of that kernel: a larger RetArgs moves the argument offsets of every
+        // pass, measured as +1.2 % on the plain search when the grade pointer was a member)
 
 // Label words per item: LT > 0 = that many, in registers; LAB_NONE = no labels; LAB_ANY = any number, the query's staged in LDS.
 enum { LAB_NONE = 0, LAB_ANY = -1 };
@@ -154,8 +162,7 @@ __host__ __device__ inline size_t stage_words(int WT, int LT, int W, int LW) {
 // The words of U consecutive database items, U * WT <= 16 per plane: constant offsets from one wave-uniform address, so each plane
 // arrives in one or two wide scalar loads.  A scalar load can only be waited for together with everything else in flight on its
 // counter, so per-word loads inside the item loop cost a full round trip each (a first version: ~840 cycles per item at 128 bit
-// against ~110 of vector work).  The passes therefore keep two groups in registers and issue the fetch of one right BEHIND the
-// first use of the other (where the wait sits): it is in flight while the rest of that group is worked on.
+// against ~110 of vector work): see walk2.
 template <int WT, int LT>
 struct Group {
   static constexpr int U = WT == 1 ? 16 : WT == 2 ? 8 : 4, NW = U * (WT > 0 ? WT : 1), NL = U * (LT > 0 ? LT : 1);
@@ -174,51 +181,89 @@ struct Group {
   }
 };
 
+// The label words of U consecutive database items, as Group holds the code words: one or two wide scalar loads.
+template <int LT>
+struct LabelGroup {
+  static constexpr int U = LT == 1 ? 16 : 4, NL = U * (LT > 0 ? LT : 1);
+  uint32_t l[NL];
+  __device__ __forceinline__ void load(const uint32_t* __restrict__ rl, int j) {
+    const uint32_t* __restrict__ pl = rl + static_cast<size_t>(j) * LT;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) l[i] = pl[i];
+  }
+};
+
+// What every pass kernel starts from: its lane's query, its chunk [jb, je) of the database, its column image.
+struct Block {
+  int lane, tile, c, q, jb, je;
+  bool valid;      // the lane has a query of its own
+  size_t at;       // the image [bins][64] of (chunk, tile): its first word in a.img and in every array laid out like it
+  __device__ __forceinline__ explicit Block(const RetArgs& a) : lane(threadIdx.x), tile(blockIdx.x), c(blockIdx.y) {
+    const int qa = tile * 64 + lane;
+    valid = qa < a.Q;
+    q = valid ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their column or sum
+    at = (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+    jb = c * a.chunk;
+    je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  }
+};
+
+// The walk over the items [jb, je) in groups of G::U: load(g, j) fetches the group that starts at item j, work(g, j0, u0, u1) handles
+// its members u0 <= u < u1.  Two register sets, and the fetch of one is issued right BEHIND the first use of the other (where the
+// wait for the scalar loads sits): it is in flight while the rest of that group is worked on.  -> the first item left over, for
+// the caller's item-at-a-time tail (fewer than U items).
+template <class G, class Load, class Work>
+__device__ __forceinline__ int walk2(int jb, int je, Load load, Work work) {
+  int j = jb;
+  const int groups = (je - jb) / G::U;
+  G ga, gb;                                                       // two register sets: one is fetched while the other is worked on
+  int g = 0;
+  if (groups > 0) load(ga, jb);
+  for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
+    work(ga, j, 0, 1);                                           // the wait for ga's words (and for everything else in flight) sits here
+    __builtin_amdgcn_sched_barrier(0);
+    load(gb, j + G::U);                                          // ... so gb's fetch is issued behind it and flies during the rest of ga
+    __builtin_amdgcn_sched_barrier(0);
+    work(ga, j, 1, G::U);
+    work(gb, j + G::U, 0, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    load(ga, g + 2 < groups ? j + 2 * G::U : j);                 // (behind the last pair: a group once more, no branch)
+    __builtin_amdgcn_sched_barrier(0);
+    work(gb, j + G::U, 1, G::U);
+  }
+  if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+  return j;
+}
+
 // ---- pass 1: per (query tile, chunk) the column image: word [h][lane] = items at h | relevant items at h << 16 ------------------
 template <int WT, int LT, bool GLOB>
 __global__ __launch_bounds__(64) void hist_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
                                                   const uint32_t* __restrict__ rl) {
   extern __shared__ uint32_t smem[];
-  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their column
-  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  const Block b(a);
+  const int lane = b.lane;
+  uint32_t* image = a.img + b.at;
   uint32_t* col = GLOB ? image : smem;
   Tile<WT, LT> t;
-  t.load(a, q, lane, smem + (GLOB ? 0 : a.bins * 64));
+  t.load(a, b.q, lane, smem + (GLOB ? 0 : a.bins * 64));
   if (!GLOB)
     for (int h = 0; h < a.bins; ++h) col[h * 64 + lane] = 0u;
   __syncthreads();
-  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
-  int j = jb;
+  int j = b.jb;
   if (WT > 0) {
     using G = Group<WT, LT>;
-    auto work = [&](const G& g, int j0, int u0, int u1) {
+    j = walk2<G>(
+        b.jb, b.je, [&](G& g, int j0) { g.load(rs, rn, rl, j0, true); },
+        [&](const G& g, int j0, int u0, int u1) {
 #pragma unroll
-      for (int u = u0; u < u1; ++u) {
-        const int h = t.half(g.s + u * WT, g.n + u * WT);
-        const uint32_t r = LT > 0 ? t.relevant(g.l + u * LT) : t.relevant(rl + static_cast<size_t>(j0 + u) * a.LW);
-        atomicAdd(&col[h * 64 + lane], 1u + (r << 16));
-      }
-    };
-    const int groups = (je - jb) / G::U;
-    G ga, gb;                                                       // two register sets: one is fetched while the other is worked on
-    int g = 0;
-    if (groups > 0) ga.load(rs, rn, rl, jb, true);
-    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
-      work(ga, j, 0, 1);                                           // the wait for ga's words (and for everything else in flight) sits here
-      __builtin_amdgcn_sched_barrier(0);
-      gb.load(rs, rn, rl, j + G::U, true);                                  // ... so gb's fetch is issued behind it and flies during the rest of ga
-      __builtin_amdgcn_sched_barrier(0);
-      work(ga, j, 1, G::U);
-      work(gb, j + G::U, 0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, true);         // (behind the last pair: a group once more, no branch)
-      __builtin_amdgcn_sched_barrier(0);
-      work(gb, j + G::U, 1, G::U);
-    }
-    if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+          for (int u = u0; u < u1; ++u) {
+            const int h = t.half(g.s + u * WT, g.n + u * WT);
+            const uint32_t r = LT > 0 ? t.relevant(g.l + u * LT) : t.relevant(rl + static_cast<size_t>(j0 + u) * a.LW);
+            atomicAdd(&col[h * 64 + lane], 1u + (r << 16));
+          }
+        });
   }
-  for (; j < je; ++j) {
+  for (; j < b.je; ++j) {
     const int h = t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W);
     const uint32_t r = t.relevant(rl + static_cast<size_t>(j) * a.LW);
     atomicAdd(&col[h * 64 + lane], 1u + (r << 16));
@@ -229,29 +274,54 @@ __global__ __launch_bounds__(64) void hist_kernel(RetArgs a, const uint32_t* __r
   }
 }
 
+// ---- images -> counts and bases: one thread per word (tile, bin < used, lane) of a tile's images ------------------------------------
+struct Word {
+  size_t stride, w;      // words of one chunk's images; this thread's word in them
+  int h, q;              // its bin, its query (clamped as in Block)
+  bool live, valid;      // the thread has a word; the word has a query of its own
+  __device__ __forceinline__ Word(const RetArgs& a, int used) : stride(static_cast<size_t>(a.tiles) * a.bins * 64) {
+    const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    live = t < static_cast<size_t>(a.tiles) * used * 64;
+    const int lane = static_cast<int>(t & 63);
+    const size_t hb = t >> 6;
+    h = static_cast<int>(hb % used);
+    const int tile = static_cast<int>(hb / used), qa = tile * 64 + lane;
+    valid = qa < a.Q;
+    q = valid ? qa : a.Q - 1;
+    w = (static_cast<size_t>(tile) * a.bins + h) * 64 + lane;
+  }
+};
+
+// A word summed over the chunks.  packed: hist_kernel's word, items | relevant << 16 (else one full counter); prefix: every chunk's
+// word becomes the items of the chunks before it.
+struct Sum { uint32_t items, rel; };
+__device__ __forceinline__ Sum sum_chunks(const RetArgs& a, const Word& x, bool packed, bool prefix) {
+  Sum s = {0u, 0u};
+  for (int c = 0; c < a.S; ++c) {
+    const uint32_t v = a.img[c * x.stride + x.w];
+    if (prefix) a.img[c * x.stride + x.w] = s.items;
+    s.items += packed ? v & 0xffffu : v;
+    if (packed) s.rel += v >> 16;
+  }
+  return s;
+}
+
+__device__ __forceinline__ void put_counts(const RetArgs& a, const Word& x, Sum s) {
+  if (a.counts && x.valid) {
+    uint32_t* o = a.counts + (static_cast<size_t>(x.q) * a.bins + x.h) * 2;
+    o[0] = s.items - s.rel;
+    o[1] = s.rel;
+  }
+}
+
 // ---- the images of a tile summed over the chunks -> counts; with `select` also: each image becomes the exclusive prefix over the
 //      chunks before it (items only) and off[tile][h][lane] = items at h
 __global__ __launch_bounds__(256) void reduce_kernel(RetArgs a, int select) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= stride) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t hb = t >> 6;
-  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
-  uint32_t tot = 0, rel = 0;
-  for (int c = 0; c < a.S; ++c) {
-    const uint32_t v = a.img[c * stride + t];
-    if (select) a.img[c * stride + t] = tot;
-    tot += v & 0xffffu;
-    rel += v >> 16;
-  }
-  const int q = tile * 64 + lane;
-  if (a.counts && q < a.Q) {
-    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
-    o[0] = tot - rel;
-    o[1] = rel;
-  }
-  if (select) a.off[t] = tot;
+  const Word x(a, a.bins);
+  if (!x.live) return;
+  const Sum s = sum_chunks(a, x, true, select);
+  put_counts(a, x, s);
+  if (select) a.off[x.w] = s.items;
 }
 
 // ---- per query: off becomes the exclusive prefix over the bins up to the radius h* where the cumulative count reaches k ---------
@@ -277,8 +347,9 @@ __global__ __launch_bounds__(64) void radius_kernel(RetArgs a) {
 }
 
 // ---- pass 2: the stable counting sort of the items at h <= h* ---------------------------------------------------------------------
-// GRADED: the grade of every placed item as well (grade [Q][k] of the batch, saturated at 255), the hit flag from it.  (A trailing
-// parameter, not a member of RetArgs: the argument layout and so the code of the other kernels stay what they were.)
+// GRADED: the grade of every placed item as well (grade [Q][k] of the batch, saturated at 255), the hit flag from it.
+// Its own preamble and its own copy of walk2: with Block and walk2 the k = 100 search of 5000 x 190 834 x 128 bit measured 5.660 /
+// 5.667 ms against 5.648 / 5.646 ms of this text (A B A B in one run), past the A-to-A spread; this text compiles to the code it was.
 template <int WT, int LT, bool GLOB, bool GRADED = false>
 __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
                                                     const uint32_t* __restrict__ rl, uint8_t* __restrict__ grade) {
@@ -327,18 +398,18 @@ __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* _
       for (int u = u0; u < u1; ++u) place(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
     };
     const int groups = (je - jb) / G::U;
-    G ga, gb;
+    G ga, gb;                                                       // (walk2, which see)
     int g = 0;
     if (groups > 0) ga.load(rs, rn, rl, jb, false);
     for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
-      work(ga, j, 0, 1);                                           // the wait for ga's words (and for everything else in flight) sits here
+      work(ga, j, 0, 1);
       __builtin_amdgcn_sched_barrier(0);
-      gb.load(rs, rn, rl, j + G::U, false);                                  // ... so gb's fetch is issued behind it and flies during the rest of ga
+      gb.load(rs, rn, rl, j + G::U, false);
       __builtin_amdgcn_sched_barrier(0);
       work(ga, j, 1, G::U);
       work(gb, j + G::U, 0, 1);
       __builtin_amdgcn_sched_barrier(0);
-      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, false);         // (behind the last pair: a group once more, no branch)
+      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, false);
       __builtin_amdgcn_sched_barrier(0);
       work(gb, j + G::U, 1, G::U);
     }
@@ -348,28 +419,16 @@ __global__ __launch_bounds__(64) void select_kernel(RetArgs a, const uint32_t* _
 }
 
 // ---- the label histogram: per (query tile, chunk) the column image: word [g][lane] = items of the chunk at grade g ----------------
-// The label words of U consecutive database items, as Group holds the code words: one or two wide scalar loads.
-template <int LT>
-struct LabelGroup {
-  static constexpr int U = LT == 1 ? 16 : 4, NL = U * (LT > 0 ? LT : 1);
-  uint32_t l[NL];
-  __device__ __forceinline__ void load(const uint32_t* __restrict__ rl, int j) {
-    const uint32_t* __restrict__ pl = rl + static_cast<size_t>(j) * LT;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) l[i] = pl[i];
-  }
-};
-
 template <int LT>
 __global__ __launch_bounds__(64) void grade_kernel(RetArgs a, const uint32_t* __restrict__ rl) {
   extern __shared__ uint32_t smem[];
-  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their column
-  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  const Block b(a);
+  const int lane = b.lane;
+  uint32_t* image = a.img + b.at;
   uint32_t* col = smem;
   uint32_t* stage = smem + a.bins * 64;
   Tile<0, LT> t;                                                     // no code words (a.W = 0): the label words only
-  t.load(a, q, lane, stage);
+  t.load(a, b.q, lane, stage);
   // the query's label words are cut to `classes` bits: whatever the words hold behind them, 0 <= g <= classes (g indexes the column)
   const int classes = a.bins - 1;
   const uint32_t last = (classes & 31) ? (1u << (classes & 31)) - 1u : 0xffffffffu;
@@ -377,139 +436,108 @@ __global__ __launch_bounds__(64) void grade_kernel(RetArgs a, const uint32_t* __
   else stage[(a.LW - 1) * 64 + lane] &= last;
   for (int g = 0; g < a.bins; ++g) col[g * 64 + lane] = 0u;
   __syncthreads();
-  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
-  int j = jb;
+  int j = b.jb;
   if (LT > 0) {
     using G = LabelGroup<LT>;
-    auto work = [&](const G& g, int u0, int u1) {
+    j = walk2<G>(
+        b.jb, b.je, [&](G& g, int j0) { g.load(rl, j0); },
+        [&](const G& g, int, int u0, int u1) {
 #pragma unroll
-      for (int u = u0; u < u1; ++u) atomicAdd(&col[t.overlap(g.l + u * LT) * 64 + lane], 1u);
-    };
-    const int groups = (je - jb) / G::U;
-    G ga, gb;                                                       // two register sets, fetched as in hist_kernel
-    int g = 0;
-    if (groups > 0) ga.load(rl, jb);
-    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
-      work(ga, 0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      gb.load(rl, j + G::U);
-      __builtin_amdgcn_sched_barrier(0);
-      work(ga, 1, G::U);
-      work(gb, 0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      ga.load(rl, g + 2 < groups ? j + 2 * G::U : j);
-      __builtin_amdgcn_sched_barrier(0);
-      work(gb, 1, G::U);
-    }
-    if (g < groups) { work(ga, 0, G::U); j += G::U; }
+          for (int u = u0; u < u1; ++u) atomicAdd(&col[t.overlap(g.l + u * LT) * 64 + lane], 1u);
+        });
   }
-  for (; j < je; ++j) atomicAdd(&col[t.overlap(rl + static_cast<size_t>(j) * a.LW) * 64 + lane], 1u);
+  for (; j < b.je; ++j) atomicAdd(&col[t.overlap(rl + static_cast<size_t>(j) * a.LW) * 64 + lane], 1u);
   __syncthreads();
   for (int g = 0; g < a.bins; ++g) image[g * 64 + lane] = col[g * 64 + lane];
 }
 
 // ---- the images of a tile summed over the chunks -> grade_counts[q][g]
 __global__ __launch_bounds__(256) void grade_reduce_kernel(RetArgs a) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= stride) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t gb = t >> 6;
-  const int g = static_cast<int>(gb % a.bins), tile = static_cast<int>(gb / a.bins);
-  uint32_t tot = 0;
-  for (int c = 0; c < a.S; ++c) tot += a.img[c * stride + t];
-  const int q = tile * 64 + lane;
-  if (q < a.Q) a.counts[static_cast<size_t>(q) * a.bins + g] = tot;
+  const Word x(a, a.bins);
+  if (x.live && x.valid) a.counts[static_cast<size_t>(x.q) * a.bins + x.h] = sum_chunks(a, x, false, false).items;
 }
 
-// ---- mAP by counting (cmh_hamming_ap_partial / cmh_ap_finish) ---------------------------------------------------------------------
-// AP needs ranks, not the permutation: for a relevant item j at bin h, with ties by ascending database index,
+// ---- images -> bases (cmh_hamming_ap_partial / cmh_hamming_range) -----------------------------------------------------------------
+// mAP by counting.  AP needs ranks, not the permutation: for a relevant item j at bin h, with ties by ascending database index,
 //   rank(j)    = #{items at h' < h} + #{items at h with index < j} + 1,   relrank(j) = the same over the relevant items,
 //   AP = (1 / total) * sum_{relevant j, relrank(j) <= total} relrank(j) / rank(j),   total = min(k, R).
-// Pass 1 is hist_kernel.  The three kernels below turn its images into the two BASES of every (chunk, bin, lane): items / relevant
-// items at smaller h in the whole database + at h in earlier shards (`prior`) + at h in earlier chunks of this call.  ap_kernel then
-// walks its chunk in index order with the packed cursor of hist_kernel in LDS: the returning add gives both positions inside the chunk.
-// The database may be one shard of a larger one: `total` is then the histogram of all shards and `prior` that of the shards before.
-struct ApArgs {
+// Pass 1 is hist_kernel.  The three kernels below (REL) turn its images into the two BASES of every (chunk, bin, lane): items /
+// relevant items at smaller h in the whole database + at h in earlier shards (`prior`) + at h in earlier chunks of this call.
+// ap_kernel then walks its chunk in index order with the packed cursor of hist_kernel in LDS: the returning add gives both positions
+// inside the chunk.  The database may be one shard of a larger one: `total` is then the histogram of all shards and `prior` that of
+// the shards before.
+// Radius search.  Every item at h <= hr, as a ragged list per query in the order (h, database index): the select pass without a k.
+// An item j of this call at bin h goes to
+//   row_off[q] + #{items of the whole database at h' < h} + #{items at h in earlier shards} + #{items of this call at h, index < j}.
+// The same three kernels over the items alone (!REL): every image becomes the 32-bit in-row BASE of its (chunk, bin, lane), for the
+// bins up to hr only; range_kernel then walks its chunk in index order with the bases as its private cursors and adds row_off as
+// int64 at the store.  lim[q] = the whole database's items at h <= hr: a position at or behind it is never stored (it cannot arise
+// from consistent histograms; an inconsistent `total` then loses entries and writes nothing outside the query's own rows).
+struct BaseArgs {
   const uint32_t* total;   // [Q][bins][2] of the whole database, or null: this call's own
   const uint32_t* prior;   // [Q][bins][2] of the shards before this one, or null: none
-  uint32_t* brel;          // [S][tiles][bins][64] bases over the relevant items (those over all items replace the images in a.img)
   uint32_t* toti;          // [tiles][bins][64] this call's items per bin -> exclusive prefix over the bins of the whole database
-  uint32_t* totr;          // ... the relevant ones
-  uint32_t* kq;            // [tiles * 64] min(k, R) per query
-  double* part;            // [S][tiles][64] a workgroup's sums
-  double* ap_sum;          // [Q]
-  uint32_t k;
+  uint32_t* totr;          // ... the relevant ones (REL)
+  uint32_t* brel;          // [S][tiles][bins][64] bases over the relevant items (REL; those over all items replace the images in a.img)
+  uint32_t* lim;           // [tiles * 64] REL: min(k, R) per query; else the items of the whole database at h <= hr (0 behind the last query)
+  double* part;            // [S][tiles][64] a workgroup's sums (mAP)
+  double* ap_sum;          // [Q] (mAP)
+  uint32_t k;              // (mAP)
+  int hr;                  // the last bin that gets bases: the radius; bins - 1 in the mAP
 };
 
 // the images of a tile summed over the chunks -> toti, totr (and counts)
-__global__ __launch_bounds__(256) void ap_total_kernel(RetArgs a, ApArgs p) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= stride) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t hb = t >> 6;
-  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
-  uint32_t tot = 0, rel = 0;
-  for (int c = 0; c < a.S; ++c) {
-    const uint32_t v = a.img[c * stride + t];
-    tot += v & 0xffffu;
-    rel += v >> 16;
-  }
-  p.toti[t] = tot;
-  p.totr[t] = rel;
-  const int q = tile * 64 + lane;
-  if (a.counts && q < a.Q) {
-    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
-    o[0] = tot - rel;
-    o[1] = rel;
-  }
+template <bool REL>
+__global__ __launch_bounds__(256) void total_kernel(RetArgs a, BaseArgs p) {
+  const Word x(a, a.bins);
+  if (!x.live) return;
+  const Sum s = sum_chunks(a, x, true, false);
+  p.toti[x.w] = s.items;
+  if (REL) p.totr[x.w] = s.rel;
+  put_counts(a, x, s);
 }
 
-// per query: toti / totr become the exclusive prefixes over the bins of the whole database's histogram; kq = min(k, R)
-__global__ __launch_bounds__(64) void ap_scan_kernel(RetArgs a, ApArgs p) {
+// per query: toti / totr become the exclusive prefixes over the bins <= hr of the whole database's histogram; lim = min(k, R) / the end
+template <bool REL>
+__global__ __launch_bounds__(64) void scan_kernel(RetArgs a, BaseArgs p) {
   const int lane = threadIdx.x, tile = blockIdx.x;
   const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
   const size_t base = static_cast<size_t>(tile) * a.bins * 64 + lane;
   uint32_t ri = 0, rr = 0;
-  for (int h = 0; h < a.bins; ++h) {
+  for (int h = 0; h <= p.hr; ++h) {
     const size_t t = base + static_cast<size_t>(h) * 64;
-    uint32_t ni, nr;
+    uint32_t ni, nr = 0;
     if (p.total) {
       const uint32_t* c = p.total + (static_cast<size_t>(q) * a.bins + h) * 2;
       nr = c[1];
       ni = c[0] + nr;
     } else {
       ni = p.toti[t];
-      nr = p.totr[t];
+      if (REL) nr = p.totr[t];
     }
     p.toti[t] = ri;
-    p.totr[t] = rr;
+    if (REL) p.totr[t] = rr;
     ri += ni;
     rr += nr;
   }
-  p.kq[tile * 64 + lane] = rr < p.k ? rr : p.k;
+  p.lim[tile * 64 + lane] = REL ? (rr < p.k ? rr : p.k) : (qa < a.Q ? ri : 0u);
 }
 
-// every image becomes the base over all items, brel the base over the relevant ones
-__global__ __launch_bounds__(256) void ap_base_kernel(RetArgs a, ApArgs p) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= stride) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t hb = t >> 6;
-  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
-  uint32_t bi = p.toti[t], br = p.totr[t];
+// every image of a bin <= hr becomes the base over all items, brel the base over the relevant ones
+template <bool REL>
+__global__ __launch_bounds__(256) void base_kernel(RetArgs a, BaseArgs p) {
+  const Word x(a, p.hr + 1);
+  if (!x.live) return;
+  uint32_t bi = p.toti[x.w], br = REL ? p.totr[x.w] : 0u;
   if (p.prior) {
-    const uint32_t* c = p.prior + (static_cast<size_t>(q) * a.bins + h) * 2;
+    const uint32_t* c = p.prior + (static_cast<size_t>(x.q) * a.bins + x.h) * 2;
     bi += c[0] + c[1];
     br += c[1];
   }
   for (int c = 0; c < a.S; ++c) {
-    const uint32_t v = a.img[c * stride + t];
-    a.img[c * stride + t] = bi;
-    p.brel[c * stride + t] = br;
+    const uint32_t v = a.img[c * x.stride + x.w];
+    a.img[c * x.stride + x.w] = bi;
+    if (REL) p.brel[c * x.stride + x.w] = br;
     bi += v & 0xffffu;
     br += v >> 16;
   }
@@ -519,24 +547,22 @@ __global__ __launch_bounds__(256) void ap_base_kernel(RetArgs a, ApArgs p) {
 // Cursors in LDS (hist_kernel's packed word: the histogram pass's occupancy), the bases read from the workspace for relevant items
 // only; lanes that meet the same bin read one line of [bin][lane].  GLOB: the bases themselves are the cursors, advanced with global
 // atomics (a lane owns its words: the adds of one word come from one lane in index order).
-// (brel, kq and part are trailing parameters, not members of RetArgs: the argument layout of the other kernels stays what it was.)
 template <int WT, int LT, bool GLOB>
 __global__ __launch_bounds__(64) void ap_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
                                                 const uint32_t* __restrict__ rl, uint32_t* brel_all, const uint32_t* __restrict__ kq,
                                                 double* __restrict__ part) {
   extern __shared__ uint32_t smem[];
-  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;      // lanes behind the last query repeat it; nobody reads their sum
-  const size_t image = (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
-  uint32_t* bitem = a.img + image;
-  uint32_t* brel = brel_all + image;
+  const Block b(a);
+  const int lane = b.lane;
+  uint32_t* bitem = a.img + b.at;
+  uint32_t* brel = brel_all + b.at;
   uint32_t* cur = smem;
   Tile<WT, LT> t;
-  t.load(a, q, lane, smem + (GLOB ? 0 : a.bins * 64));
+  t.load(a, b.q, lane, smem + (GLOB ? 0 : a.bins * 64));
   if (!GLOB)
     for (int h = 0; h < a.bins; ++h) cur[h * 64 + lane] = 0u;
   __syncthreads();
-  const uint32_t total = kq[tile * 64 + lane];
+  const uint32_t total = kq[b.tile * 64 + lane];
   double acc = 0.0;
   auto score = [&](int h, uint32_t r) {
     const int w = h * 64 + lane;
@@ -555,18 +581,18 @@ __global__ __launch_bounds__(64) void ap_kernel(RetArgs a, const uint32_t* __res
       }
     }
   };
-  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
-  int j = jb;
+  int j = b.jb;
   if (WT > 0) {
     // A workgroup is one wave, and at 4 (2) workgroups per CU a SIMD holds one: nothing hides a wait, so an item at a time (the add's
     // return, then the bases, then the quotient) costs three round trips per item.  A group is therefore worked on in phases, each
     // a run of independent instructions: distances and relevance of its U items; the loads of the bases (they need only the bin);
-    // the U returning adds; the quotients.  ONE register set: the next group's fetch is issued behind the wait for the adds'
-    // returns (both count on the same counter: a fetch in flight would be waited for with them) and flies during the quotients.
+    // the U returning adds; the quotients.  ONE register set, not walk2's two: the next group's fetch is issued behind the wait for
+    // the adds' returns (both count on the same counter: a fetch in flight would be waited for with them) and flies during the
+    // quotients.
     using G = Group<WT, LT>;
-    const int groups = (je - jb) / G::U;
+    const int groups = (b.je - b.jb) / G::U;
     G g;
-    if (groups > 0) g.load(rs, rn, rl, jb, true);
+    if (groups > 0) g.load(rs, rn, rl, b.jb, true);
     for (int gi = 0; gi < groups; ++gi, j += G::U) {
       int w[G::U];
       uint32_t r[G::U], old[G::U], bi[G::U], br[G::U];
@@ -594,13 +620,13 @@ __global__ __launch_bounds__(64) void ap_kernel(RetArgs a, const uint32_t* __res
       }
     }
   }
-  for (; j < je; ++j)
+  for (; j < b.je; ++j)
     score(t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W), t.relevant(rl + static_cast<size_t>(j) * a.LW));
-  part[(static_cast<size_t>(c) * a.tiles + tile) * 64 + lane] = acc;
+  part[(static_cast<size_t>(b.c) * a.tiles + b.tile) * 64 + lane] = acc;
 }
 
 // the chunks' sums added in chunk order
-__global__ __launch_bounds__(64) void ap_sum_kernel(RetArgs a, ApArgs p) {
+__global__ __launch_bounds__(64) void ap_sum_kernel(RetArgs a, BaseArgs p) {
   const int lane = threadIdx.x, tile = blockIdx.x, q = tile * 64 + lane;
   if (q >= a.Q) return;
   double s = 0.0;
@@ -622,7 +648,7 @@ __global__ __launch_bounds__(64) void ap_finish_kernel(const double* __restrict_
   }
 }
 
-// (((ap[0] + ap[1]) + ...) / Q) in f32 in query order: the mean of the ranking kernel (map_mean_kernel of hamming_map.hip)
+// (((ap[0] + ap[1]) + ...) / Q) in f32 in query order: the mean of the ranking kernel of hamming_map.hip
 __global__ __launch_bounds__(64) void ap_mean_kernel(const float* __restrict__ ap, int Q, float* __restrict__ out) {
   __shared__ float buf[1024];
   float acc = 0.f;
@@ -637,112 +663,26 @@ __global__ __launch_bounds__(64) void ap_mean_kernel(const float* __restrict__ a
   if (threadIdx.x == 0) out[0] = acc / static_cast<float>(Q);
 }
 
-// ---- radius search (cmh_hamming_range) ----------------------------------------------------------------------------------------------
-// Every item at h <= hr, as a ragged list per query in the order (h, database index): the select pass without a k.  An item j of this
-// call at bin h goes to
-//   row_off[q] + #{items of the whole database at h' < h} + #{items at h in earlier shards} + #{items of this call at h, index < j}.
-// Pass 1 is hist_kernel.  The three kernels below follow ap_total / ap_scan / ap_base over the items alone: every image becomes the
-// 32-bit in-row BASE of its (chunk, bin, lane), for the bins up to hr only; range_kernel then walks its chunk in index order with the
-// bases as its private cursors and adds row_off as int64 at the store.  ball[q] = the whole database's items at h <= hr: a position
-// at or behind it is never stored (it cannot arise from consistent histograms; an inconsistent `total` then loses entries and writes
-// nothing outside the query's own rows).
-struct RangeArgs {
-  const uint32_t* total;   // [Q][bins][2] of the whole database, or null: this call's own
-  const uint32_t* prior;   // [Q][bins][2] of the shards before this one, or null: none
-  uint32_t* toti;          // [tiles][bins][64] this call's items per bin -> exclusive prefix over the bins of the whole database
-  uint32_t* ball;          // [tiles * 64] items of the whole database at h <= hr (0 behind the last query)
-  int hr;
-};
-
-// the images of a tile summed over the chunks -> toti (and counts)
-__global__ __launch_bounds__(256) void range_total_kernel(RetArgs a, RangeArgs p) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= stride) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t hb = t >> 6;
-  const int h = static_cast<int>(hb % a.bins), tile = static_cast<int>(hb / a.bins);
-  uint32_t tot = 0, rel = 0;
-  for (int c = 0; c < a.S; ++c) {
-    const uint32_t v = a.img[c * stride + t];
-    tot += v & 0xffffu;
-    rel += v >> 16;
-  }
-  p.toti[t] = tot;
-  const int q = tile * 64 + lane;
-  if (a.counts && q < a.Q) {
-    uint32_t* o = a.counts + (static_cast<size_t>(q) * a.bins + h) * 2;
-    o[0] = tot - rel;
-    o[1] = rel;
-  }
-}
-
-// per query: toti becomes the exclusive prefix over the bins <= hr of the whole database's histogram; ball = its end
-__global__ __launch_bounds__(64) void range_scan_kernel(RetArgs a, RangeArgs p) {
-  const int lane = threadIdx.x, tile = blockIdx.x;
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
-  const size_t base = static_cast<size_t>(tile) * a.bins * 64 + lane;
-  uint32_t run = 0;
-  for (int h = 0; h <= p.hr; ++h) {
-    const size_t t = base + static_cast<size_t>(h) * 64;
-    uint32_t ni;
-    if (p.total) {
-      const uint32_t* c = p.total + (static_cast<size_t>(q) * a.bins + h) * 2;
-      ni = c[0] + c[1];
-    } else {
-      ni = p.toti[t];
-    }
-    p.toti[t] = run;
-    run += ni;
-  }
-  p.ball[tile * 64 + lane] = qa < a.Q ? run : 0u;
-}
-
-// every image of a bin <= hr becomes the in-row base of its (chunk, bin, lane)
-__global__ __launch_bounds__(256) void range_base_kernel(RetArgs a, RangeArgs p) {
-  const size_t stride = static_cast<size_t>(a.tiles) * a.bins * 64;
-  const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int used = p.hr + 1;
-  if (t >= static_cast<size_t>(a.tiles) * used * 64) return;
-  const int lane = static_cast<int>(t & 63);
-  const size_t hb = t >> 6;
-  const int h = static_cast<int>(hb % used), tile = static_cast<int>(hb / used);
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
-  const size_t w = (static_cast<size_t>(tile) * a.bins + h) * 64 + lane;
-  uint32_t bi = p.toti[w];
-  if (p.prior) {
-    const uint32_t* c = p.prior + (static_cast<size_t>(q) * a.bins + h) * 2;
-    bi += c[0] + c[1];
-  }
-  for (int c = 0; c < a.S; ++c) {
-    const uint32_t v = a.img[c * stride + w];
-    a.img[c * stride + w] = bi;
-    bi += v & 0xffffu;
-  }
-}
-
 // ---- pass 2 of the radius search: the stable counting sort of the items at h <= hr into the queries' rows -------------------------
-// select_kernel's walk.  The cursors are the bases of the bins 0..hr: (hr + 1) * 256 bytes of LDS (GLOB: the bases themselves,
-// advanced with global atomics; a lane owns its words).  (row_off, ball, hr and idx_base are trailing parameters, not members of
-// RetArgs: the argument layout of the other kernels stays what it was.)
+// The cursors are the bases of the bins 0..hr: (hr + 1) * 256 bytes of LDS (GLOB: the bases themselves, advanced with global
+// atomics; a lane owns its words).
 template <int WT, int LT, bool GLOB>
 __global__ __launch_bounds__(64) void range_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
                                                    const uint32_t* __restrict__ rl, const int64_t* __restrict__ row_off,
                                                    const uint32_t* __restrict__ ball, int hr, int idx_base) {
   extern __shared__ uint32_t smem[];
-  const int lane = threadIdx.x, tile = blockIdx.x, c = blockIdx.y;
-  const int qa = tile * 64 + lane, q = qa < a.Q ? qa : a.Q - 1;
-  uint32_t* image = a.img + (static_cast<size_t>(c) * a.tiles + tile) * a.bins * 64;
+  const Block b(a);
+  const int lane = b.lane;
+  uint32_t* image = a.img + b.at;
   uint32_t* cur = GLOB ? image : smem;
   Tile<WT, LT> t;
-  t.load(a, q, lane, smem + (GLOB ? 0 : (hr + 1) * 64));
-  const int hq = qa < a.Q ? hr : -1;               // a lane behind the last query places nothing
+  t.load(a, b.q, lane, smem + (GLOB ? 0 : (hr + 1) * 64));
+  const int hq = b.valid ? hr : -1;                // a lane behind the last query places nothing
   if (!GLOB)
     for (int h = 0; h <= hr; ++h) cur[h * 64 + lane] = image[h * 64 + lane];
   __syncthreads();
-  const int64_t row = row_off[q];
-  const uint32_t end = ball[tile * 64 + lane];
-  const int jb = c * a.chunk, je = jb + a.chunk < a.N ? jb + a.chunk : a.N;
+  const int64_t row = row_off[b.q];
+  const uint32_t end = ball[b.tile * 64 + lane];
   auto place = [&](int j, int h) {
     if (h <= hq) {
       const uint32_t p = atomicAdd(&cur[h * 64 + lane], 1u);
@@ -754,41 +694,37 @@ __global__ __launch_bounds__(64) void range_kernel(RetArgs a, const uint32_t* __
       }
     }
   };
-  int j = jb;
+  int j = b.jb;
   if (WT > 0) {
     using G = Group<WT, LT>;
-    auto work = [&](const G& g, int j0, int u0, int u1) {
+    j = walk2<G>(
+        b.jb, b.je, [&](G& g, int j0) { g.load(rs, rn, rl, j0, false); },
+        [&](const G& g, int j0, int u0, int u1) {
 #pragma unroll
-      for (int u = u0; u < u1; ++u) place(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
-    };
-    const int groups = (je - jb) / G::U;
-    G ga, gb;                                                       // two register sets, fetched as in select_kernel
-    int g = 0;
-    if (groups > 0) ga.load(rs, rn, rl, jb, false);
-    for (; g + 2 <= groups; g += 2, j += 2 * G::U) {
-      work(ga, j, 0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      gb.load(rs, rn, rl, j + G::U, false);
-      __builtin_amdgcn_sched_barrier(0);
-      work(ga, j, 1, G::U);
-      work(gb, j + G::U, 0, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      ga.load(rs, rn, rl, g + 2 < groups ? j + 2 * G::U : j, false);
-      __builtin_amdgcn_sched_barrier(0);
-      work(gb, j + G::U, 1, G::U);
-    }
-    if (g < groups) { work(ga, j, 0, G::U); j += G::U; }
+          for (int u = u0; u < u1; ++u) place(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
+        });
   }
-  for (; j < je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
+  for (; j < b.je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
+// A call's operands as the entry points receive them (ql, rl: null without labels)
+struct Problem {
+  const uint32_t *qs, *qn, *ql, *rs, *rn, *rl;
+  int Q;
+  int64_t N;
+  int bits, classes;
+};
+
 struct Plan {
   int bins, W, tiles, S, chunk, tb;      // tb = query tiles per batch (the images of one batch fit kImageCap)
   bool glob;
   size_t tile_words() const { return static_cast<size_t>(bins) * 64; }
   size_t bytes() const { return ((static_cast<size_t>(S) + 1) * tb * tile_words() + static_cast<size_t>(tb) * 64) * 4 + 256; }
 };
+
+template <class T>
+T* aligned256(void* p) { return reinterpret_cast<T*>((reinterpret_cast<uintptr_t>(p) + 255) & ~static_cast<uintptr_t>(255)); }
 
 // CUs of the current device; 256 (MI355X) where none answers (the workspace query also serves callers without a GPU)
 int cu_count() {
@@ -819,6 +755,13 @@ int cut_chunks(int n, int tiles, size_t lds, int smin, int smax, int* chunk) {
   return (n + *chunk - 1) / *chunk;
 }
 
+// tb = the query tiles whose workspace of per_tile bytes each fits kImageCap
+int batch_tiles(size_t per_tile, int tiles) {
+  size_t tb = kImageCap / per_tile;
+  tb = tb < 1 ? 1 : tb;
+  return tb < static_cast<size_t>(tiles) ? static_cast<int>(tb) : tiles;
+}
+
 Plan make_plan(int Q, int64_t N, int bits) {
   Plan p;
   p.bins = 2 * bits + 1;
@@ -829,101 +772,117 @@ Plan make_plan(int Q, int64_t N, int bits) {
   const int smin = (n + kChunkMax - 1) / kChunkMax;
   const size_t lds = p.glob ? 0 : static_cast<size_t>(p.bins) * 256;
   p.S = cut_chunks(n, p.tiles, lds, smin, p.glob ? 32 : 256, &p.chunk);      // (an image of the wide codes is up to 1 MiB per tile)
-  const size_t per_tile = (static_cast<size_t>(p.S) + 1) * p.tile_words() * 4;
-  size_t tb = kImageCap / per_tile;
-  tb = tb < 1 ? 1 : tb;
-  p.tb = tb < static_cast<size_t>(p.tiles) ? static_cast<int>(tb) : p.tiles;
+  p.tb = batch_tiles((static_cast<size_t>(p.S) + 1) * p.tile_words() * 4, p.tiles);
   return p;
 }
 
-enum Pass { PASS_HIST, PASS_SELECT, PASS_SELECT_GRADED };
+// The run-time shape of a call -> the compile-time form of its pass kernels: f(WT, LT, GLOB) as integral constants.
+//   GLOB (columns in the workspace): any number of code words, labels none or staged
+//   else W in 1..4 code words in registers; label words none (where NONE allows it), 1 (<= 32 classes: MIRFlickr 24, NUS-WIDE 21)
+//   or 3 (65..96 classes: MS-COCO 80) in registers, any other number staged.
+template <int V>
+using Int = std::integral_constant<int, V>;
 
-template <int WT, int LT, bool GLOB>
-int launch_pass(Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
-  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(a.bins) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
-  constexpr bool kLabels = LT != LAB_NONE;      // (the graded select exists with labels only)
-  if (pass == PASS_SELECT_GRADED && !kLabels) return fail(CMH_ERR_INVALID, "retrieval: grades asked for without labels");
-  const void* fn = pass == PASS_SELECT_GRADED ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB, kLabels>)
-                   : pass == PASS_SELECT      ? reinterpret_cast<const void*>(select_kernel<WT, LT, GLOB>)
-                                              : reinterpret_cast<const void*>(hist_kernel<WT, LT, GLOB>);
-  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-    return fail(CMH_ERR_LAUNCH, "retrieval: cannot reserve %zu bytes of LDS", lds);
-  if (pass == PASS_SELECT_GRADED) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB, kLabels>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, grade);
-  else if (pass == PASS_SELECT) hipLaunchKernelGGL((select_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, grade);
-  else hipLaunchKernelGGL((hist_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl);
-  CMH_CHECK_LAUNCH(pass == PASS_HIST ? "hamming_hist" : "hamming_topk select");
+template <bool NONE, class F>
+int dispatch(bool glob, int W, int LW, std::bool_constant<NONE>, F f) {
+  auto labels = [&](auto wt, auto gl) {
+    if constexpr (NONE)
+      if (LW == 0) return f(wt, Int<LAB_NONE>{}, gl);
+    if constexpr (!decltype(gl)::value) {
+      if (LW == 1) return f(wt, Int<1>{}, gl);
+      if (LW == 3) return f(wt, Int<3>{}, gl);
+    }
+    return f(wt, Int<LAB_ANY>{}, gl);
+  };
+  if (glob) return labels(Int<0>{}, std::true_type{});
+  if (W == 1) return labels(Int<1>{}, std::false_type{});
+  if (W == 2) return labels(Int<2>{}, std::false_type{});
+  if (W == 3) return labels(Int<3>{}, std::false_type{});
+  return labels(Int<4>{}, std::false_type{});
+}
+
+// One pass kernel over (query tiles x chunks): lds_bins columns [bin][lane] in LDS plus the form's staged query words.
+template <int WT, int LT, class... P, class... A>
+int launch_walk(void (*kernel)(RetArgs, P...), int lds_bins, const char* what, const RetArgs& a, hipStream_t st, A... args) {
+  const size_t lds = (static_cast<size_t>(lds_bins) * 64 + stage_words(WT, LT, a.W, a.LW)) * 4;
+  if (lds > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "%s: cannot reserve %zu bytes of LDS", what, lds);
+  hipLaunchKernelGGL(kernel, dim3(a.tiles, a.S), dim3(64), lds, st, a, args...);
+  CMH_CHECK_LAUNCH(what);
   return CMH_OK;
 }
 
-template <int WT, bool GLOB>
-int launch_labels(Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
-  if (a.LW == 0) return launch_pass<WT, LAB_NONE, GLOB>(pass, a, rs, rn, rl, grade, st);
-  if (!GLOB && a.LW == 1) return launch_pass<WT, 1, GLOB>(pass, a, rs, rn, rl, grade, st);      // <= 32 classes (MIRFlickr 24, NUS-WIDE 21)
-  if (!GLOB && a.LW == 3) return launch_pass<WT, 3, GLOB>(pass, a, rs, rn, rl, grade, st);      // 65..96 classes (MS-COCO 80)
-  return launch_pass<WT, LAB_ANY, GLOB>(pass, a, rs, rn, rl, grade, st);
-}
-
-int launch_any(bool glob, Pass pass, const RetArgs& a, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, uint8_t* grade, hipStream_t st) {
-  if (glob) return launch_labels<0, true>(pass, a, rs, rn, rl, grade, st);
-  if (a.W == 1) return launch_labels<1, false>(pass, a, rs, rn, rl, grade, st);
-  if (a.W == 2) return launch_labels<2, false>(pass, a, rs, rn, rl, grade, st);
-  if (a.W == 3) return launch_labels<3, false>(pass, a, rs, rn, rl, grade, st);
-  return launch_labels<4, false>(pass, a, rs, rn, rl, grade, st);
-}
-
-int check_shape(const char* what, int Q, int64_t N, int bits, int classes, bool labels) {
-  CMH_CHECK_ARG(Q > 0 && Q <= 65535 && N > 0, "%s: Q=%d N=%lld", what, Q, static_cast<long long>(N));
-  CMH_CHECK_ARG(N <= kRetMaxN, "%s: N=%lld exceeds %d", what, static_cast<long long>(N), kRetMaxN);
-  CMH_CHECK_ARG(bits > 0 && bits <= 32 * kRetMaxWords, "%s: bits=%d unsupported", what, bits);
-  CMH_CHECK_ARG(!labels || (classes > 0 && classes <= 32 * kRetMaxWords), "%s: classes=%d unsupported", what, classes);
+// The limits all entry points share: bits where `codes`, 0 < classes <= cmax where `labels`.  what = null: only the answer (the
+// workspace queries leave no message).
+int check_shape(const char* what, int Q, int64_t N, int bits, bool codes, int classes, bool labels, int cmax = 32 * kRetMaxWords) {
+  auto bad = [&](const char* fmt, auto... v) -> int { return what ? fail(CMH_ERR_INVALID, fmt, what, v...) : CMH_ERR_INVALID; };
+  if (Q <= 0 || Q > 65535 || N <= 0) return bad("%s: Q=%d N=%lld", Q, static_cast<long long>(N));
+  if (N > kRetMaxN) return bad("%s: N=%lld exceeds %d", static_cast<long long>(N), kRetMaxN);
+  if (codes && (bits <= 0 || bits > 32 * kRetMaxWords)) return bad("%s: bits=%d unsupported", bits);
+  if (labels && (classes <= 0 || (classes > cmax && cmax != kGradeMax))) return bad("%s: classes=%d unsupported", classes);
+  if (labels && classes > cmax) return bad("%s: classes=%d exceeds %d (a grade is one byte)", classes, cmax);
   return CMH_OK;
 }
 
-// hist (k == 0) or hist + select (k > 0), in batches of query tiles
-int run(const char* what, const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
-        const uint32_t* r_nz, const uint32_t* r_label, int Q, int64_t N, int bits, int classes, int k, int32_t* idx, float* dist,
-        uint8_t* rel, uint8_t* grade, uint32_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  const Plan p = make_plan(Q, N, bits);
-  if (!workspace || workspace_bytes < p.bytes()) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, p.bytes());
-  RetArgs a;
-  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = q_label ? (classes + 31) / 32 : 0; a.bins = p.bins;
-  a.S = p.S; a.chunk = p.chunk; a.k = k;
-  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  const bool select = k > 0;
+// The query tiles in batches of p.tb.  Per batch: the RetArgs of its queries (operands, images at the head of the workspace, counts),
+// the zeroed images of the wide codes, the histogram pass; then body(a, q0, stride) with q0 = the batch's first query and stride =
+// the words of one chunk's images, for what the caller makes of the images.
+template <class Body>
+int for_each_batch(const char* what, const Plan& p, const Problem& pb, uint32_t* counts, void* workspace, hipStream_t st, Body body) {
+  RetArgs a = {};
+  a.N = static_cast<int>(pb.N); a.bits = pb.bits; a.W = p.W; a.LW = pb.ql ? (pb.classes + 31) / 32 : 0; a.bins = p.bins;
+  a.S = p.S; a.chunk = p.chunk;
+  a.img = aligned256<uint32_t>(workspace);
   for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
     const int q0 = t0 * 64;
     a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
-    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
-    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
-    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
-    a.ql = q_label ? q_label + static_cast<size_t>(q0) * a.LW : nullptr;
-    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
-    a.img = base;
-    a.off = base + static_cast<size_t>(a.S) * stride;
-    a.hstar = reinterpret_cast<int32_t*>(a.off + stride);
+    a.Q = pb.Q - q0 < a.tiles * 64 ? pb.Q - q0 : a.tiles * 64;
+    a.qs = pb.qs + static_cast<size_t>(q0) * a.W;
+    a.qn = pb.qn + static_cast<size_t>(q0) * a.W;
+    a.ql = pb.ql ? pb.ql + static_cast<size_t>(q0) * a.LW : nullptr;
     a.counts = counts ? counts + static_cast<size_t>(q0) * a.bins * 2 : nullptr;
-    a.idx = idx ? idx + static_cast<size_t>(q0) * k : nullptr;
-    a.dist = dist ? dist + static_cast<size_t>(q0) * k : nullptr;
-    a.rel = rel ? rel + static_cast<size_t>(q0) * k : nullptr;
+    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
     if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "%s: memset failed", what);
-    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
+    int rc = dispatch(p.glob, a.W, a.LW, std::true_type{}, [&](auto WT, auto LT, auto GLOB) {
+      return launch_walk<WT, LT>(hist_kernel<WT, LT, GLOB>, GLOB ? 0 : a.bins, "hamming_hist", a, st, pb.rs, pb.rn, pb.rl);
+    });
+    if (rc == CMH_OK) rc = body(a, q0, stride);
     if (rc != CMH_OK) return rc;
-    hipLaunchKernelGGL(reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, select ? 1 : 0);
-    CMH_CHECK_LAUNCH("retrieval reduce");
-    if (select) {
-      hipLaunchKernelGGL(radius_kernel, dim3(a.tiles), dim3(64), 0, st, a);
-      CMH_CHECK_LAUNCH("retrieval radius");
-      rc = launch_any(p.glob, grade ? PASS_SELECT_GRADED : PASS_SELECT, a, r_sign, r_nz, r_label,
-                      grade ? grade + static_cast<size_t>(q0) * k : nullptr, st);
-      if (rc != CMH_OK) return rc;
-    }
   }
   return CMH_OK;
 }
 
+// hist (k == 0) or hist + select (k > 0)
+int run(const char* what, const Problem& pb, int k, int32_t* idx, float* dist, uint8_t* rel, uint8_t* grade, uint32_t* counts,
+        void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const Plan p = make_plan(pb.Q, pb.N, pb.bits);
+  if (!workspace || workspace_bytes < p.bytes()) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, p.bytes());
+  return for_each_batch(what, p, pb, counts, workspace, st, [&](RetArgs& a, int q0, size_t stride) -> int {
+    a.k = k;
+    a.off = a.img + static_cast<size_t>(a.S) * stride;
+    a.hstar = reinterpret_cast<int32_t*>(a.off + stride);
+    a.idx = idx ? idx + static_cast<size_t>(q0) * k : nullptr;
+    a.dist = dist ? dist + static_cast<size_t>(q0) * k : nullptr;
+    a.rel = rel ? rel + static_cast<size_t>(q0) * k : nullptr;
+    hipLaunchKernelGGL(reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, k > 0 ? 1 : 0);
+    CMH_CHECK_LAUNCH("retrieval reduce");
+    if (k <= 0) return CMH_OK;
+    hipLaunchKernelGGL(radius_kernel, dim3(a.tiles), dim3(64), 0, st, a);
+    CMH_CHECK_LAUNCH("retrieval radius");
+    uint8_t* g = grade ? grade + static_cast<size_t>(q0) * k : nullptr;
+    return dispatch(p.glob, a.W, a.LW, std::true_type{}, [&](auto WT, auto LT, auto GLOB) {
+      constexpr bool kLabels = LT != LAB_NONE;      // (the graded select exists with labels only)
+      if (g && !kLabels) return fail(CMH_ERR_INVALID, "retrieval: grades asked for without labels");
+      return launch_walk<WT, LT>(g ? select_kernel<WT, LT, GLOB, kLabels> : select_kernel<WT, LT, GLOB>, GLOB ? 0 : a.bins,
+                                 "hamming_topk select", a, st, pb.rs, pb.rn, pb.rl, g);
+    });
+  });
+}
+
 // The mAP's workspace per batch of tb query tiles: images (-> bases over the items) and bases over the relevant items [S] each,
-// toti, totr, kq, the workgroups' float64 sums.  The batch is sized so that all of it fits kImageCap.
+// toti, totr, lim, the workgroups' float64 sums.  The batch is sized so that all of it fits kImageCap.
 struct ApPlan : Plan {
   size_t per_tile() const { return (2 * static_cast<size_t>(S) + 2) * tile_words() * 4 + 64 * 4 + static_cast<size_t>(S) * 64 * 8; }
   size_t ap_bytes() const { return static_cast<size_t>(tb) * per_tile() + 512; }
@@ -932,161 +891,86 @@ struct ApPlan : Plan {
 ApPlan make_ap_plan(int Q, int64_t N, int bits) {
   ApPlan p;
   static_cast<Plan&>(p) = make_plan(Q, N, bits);
-  size_t tb = kImageCap / p.per_tile();
-  tb = tb < 1 ? 1 : tb;
-  p.tb = tb < static_cast<size_t>(p.tiles) ? static_cast<int>(tb) : p.tiles;
+  p.tb = batch_tiles(p.per_tile(), p.tiles);
   return p;
 }
 
-template <int WT, int LT, bool GLOB>
-int launch_ap(const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
-  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(a.bins) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ap_kernel<WT, LT, GLOB>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-    return fail(CMH_ERR_LAUNCH, "hamming_ap_partial: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL((ap_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, p.brel, p.kq, p.part);
-  CMH_CHECK_LAUNCH("hamming_ap_partial");
+// total, scan and base over the bins 0..b.hr of a batch: the images become bases
+template <bool REL>
+int launch_bases(const RetArgs& a, const BaseArgs& b, size_t stride, const char* what, hipStream_t st) {
+  hipLaunchKernelGGL(total_kernel<REL>, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, b);
+  hipLaunchKernelGGL(scan_kernel<REL>, dim3(a.tiles), dim3(64), 0, st, a, b);
+  const size_t used = static_cast<size_t>(a.tiles) * (b.hr + 1) * 64;
+  hipLaunchKernelGGL(base_kernel<REL>, dim3(static_cast<unsigned>((used + 255) / 256)), dim3(256), 0, st, a, b);
+  CMH_CHECK_LAUNCH(what);
   return CMH_OK;
 }
 
-template <int WT>
-int launch_ap_labels(const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
-  if (a.LW == 1) return launch_ap<WT, 1, false>(a, p, rs, rn, rl, st);
-  if (a.LW == 3) return launch_ap<WT, 3, false>(a, p, rs, rn, rl, st);
-  return launch_ap<WT, LAB_ANY, false>(a, p, rs, rn, rl, st);
-}
-
-int launch_ap_any(bool glob, const RetArgs& a, const ApArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, hipStream_t st) {
-  if (glob) return launch_ap<0, LAB_ANY, true>(a, p, rs, rn, rl, st);
-  if (a.W == 1) return launch_ap_labels<1>(a, p, rs, rn, rl, st);
-  if (a.W == 2) return launch_ap_labels<2>(a, p, rs, rn, rl, st);
-  if (a.W == 3) return launch_ap_labels<3>(a, p, rs, rn, rl, st);
-  return launch_ap_labels<4>(a, p, rs, rn, rl, st);
-}
-
-// hist, the bases, the AP pass and the sum over the chunks, in batches of query tiles
-int run_ap(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign, const uint32_t* r_nz,
-           const uint32_t* r_label, int Q, int64_t N, int bits, int classes, uint32_t k, const uint32_t* total, const uint32_t* prior,
-           uint32_t* counts, double* ap_sum, void* workspace, hipStream_t st) {
-  const ApPlan p = make_ap_plan(Q, N, bits);
-  RetArgs a = {};
-  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = (classes + 31) / 32; a.bins = p.bins;
-  a.S = p.S; a.chunk = p.chunk;
-  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
-    const int q0 = t0 * 64;
-    a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
-    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
-    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
-    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
-    a.ql = q_label + static_cast<size_t>(q0) * a.LW;
-    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
+// hist, the bases, the AP pass and the sum over the chunks
+int run_ap(const Problem& pb, uint32_t k, const uint32_t* total, const uint32_t* prior, uint32_t* counts, double* ap_sum, void* workspace,
+           hipStream_t st) {
+  const ApPlan p = make_ap_plan(pb.Q, pb.N, pb.bits);
+  return for_each_batch("hamming_ap_partial", p, pb, counts, workspace, st, [&](RetArgs& a, int q0, size_t stride) -> int {
     const size_t row = static_cast<size_t>(q0) * a.bins * 2;
-    ApArgs b;
+    BaseArgs b = {};
     b.total = total ? total + row : nullptr;
     b.prior = prior ? prior + row : nullptr;
-    a.img = base;
-    b.brel = base + static_cast<size_t>(a.S) * stride;
+    b.brel = a.img + static_cast<size_t>(a.S) * stride;
     b.toti = b.brel + static_cast<size_t>(a.S) * stride;
     b.totr = b.toti + stride;
-    b.kq = b.totr + stride;
-    b.part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(b.kq + static_cast<size_t>(a.tiles) * 64) + 255) & ~static_cast<uintptr_t>(255));
+    b.lim = b.totr + stride;
+    b.part = aligned256<double>(b.lim + static_cast<size_t>(a.tiles) * 64);
     b.ap_sum = ap_sum + q0;
     b.k = k;
-    a.counts = counts ? counts + row : nullptr;
-    if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
-      return fail(CMH_ERR_LAUNCH, "hamming_ap_partial: memset failed");
-    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
+    b.hr = a.bins - 1;
+    int rc = launch_bases<true>(a, b, stride, "hamming_ap_partial bases", st);
     if (rc != CMH_OK) return rc;
-    const unsigned blocks = static_cast<unsigned>((stride + 255) / 256);
-    hipLaunchKernelGGL(ap_total_kernel, dim3(blocks), dim3(256), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_ap_partial totals");
-    hipLaunchKernelGGL(ap_scan_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_ap_partial scan");
-    hipLaunchKernelGGL(ap_base_kernel, dim3(blocks), dim3(256), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_ap_partial bases");
-    rc = launch_ap_any(p.glob, a, b, r_sign, r_nz, r_label, st);
+    rc = dispatch(p.glob, a.W, a.LW, std::false_type{}, [&](auto WT, auto LT, auto GLOB) {
+      return launch_walk<WT, LT>(ap_kernel<WT, LT, GLOB>, GLOB ? 0 : a.bins, "hamming_ap_partial", a, st, pb.rs, pb.rn, pb.rl, b.brel,
+                                 b.lim, b.part);
+    });
     if (rc != CMH_OK) return rc;
     hipLaunchKernelGGL(ap_sum_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
     CMH_CHECK_LAUNCH("hamming_ap_partial sum");
-  }
-  return CMH_OK;
+    return CMH_OK;
+  });
 }
 
-template <int WT, int LT, bool GLOB>
-int launch_range(const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl, const int64_t* row_off,
-                 int idx_base, hipStream_t st) {
-  const size_t lds = ((GLOB ? 0 : static_cast<size_t>(p.hr + 1) * 64) + stage_words(WT, LT, a.W, a.LW)) * 4;
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(range_kernel<WT, LT, GLOB>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
-    return fail(CMH_ERR_LAUNCH, "hamming_range: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL((range_kernel<WT, LT, GLOB>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rs, rn, rl, row_off, p.ball, p.hr, idx_base);
-  CMH_CHECK_LAUNCH("hamming_range");
-  return CMH_OK;
-}
-
-template <int WT, bool GLOB>
-int launch_range_labels(const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl,
-                        const int64_t* row_off, int idx_base, hipStream_t st) {
-  if (a.LW == 0) return launch_range<WT, LAB_NONE, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
-  if (!GLOB && a.LW == 1) return launch_range<WT, 1, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
-  if (!GLOB && a.LW == 3) return launch_range<WT, 3, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
-  return launch_range<WT, LAB_ANY, GLOB>(a, p, rs, rn, rl, row_off, idx_base, st);
-}
-
-int launch_range_any(bool glob, const RetArgs& a, const RangeArgs& p, const uint32_t* rs, const uint32_t* rn, const uint32_t* rl,
-                     const int64_t* row_off, int idx_base, hipStream_t st) {
-  if (glob) return launch_range_labels<0, true>(a, p, rs, rn, rl, row_off, idx_base, st);
-  if (a.W == 1) return launch_range_labels<1, false>(a, p, rs, rn, rl, row_off, idx_base, st);
-  if (a.W == 2) return launch_range_labels<2, false>(a, p, rs, rn, rl, row_off, idx_base, st);
-  if (a.W == 3) return launch_range_labels<3, false>(a, p, rs, rn, rl, row_off, idx_base, st);
-  return launch_range_labels<4, false>(a, p, rs, rn, rl, row_off, idx_base, st);
-}
-
-// hist, the bases and the fill, in batches of query tiles.  The workspace is that of run(): images [S], toti where run() keeps off,
-// ball where it keeps hstar.
-int run_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign, const uint32_t* r_nz,
-              const uint32_t* r_label, int Q, int64_t N, int bits, int classes, int hr, const uint32_t* total, const uint32_t* prior,
-              const int64_t* row_off, int idx_base, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts, void* workspace,
-              hipStream_t st) {
-  const Plan p = make_plan(Q, N, bits);
-  RetArgs a = {};
-  a.N = static_cast<int>(N); a.bits = bits; a.W = p.W; a.LW = q_label ? (classes + 31) / 32 : 0; a.bins = p.bins;
-  a.S = p.S; a.chunk = p.chunk;
-  a.idx = idx; a.dist = dist; a.rel = rel;      // (whole buffers: a query's rows start at its row_off)
-  uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  for (int t0 = 0; t0 < p.tiles; t0 += p.tb) {
-    const int q0 = t0 * 64;
-    a.tiles = p.tiles - t0 < p.tb ? p.tiles - t0 : p.tb;
-    a.Q = Q - q0 < a.tiles * 64 ? Q - q0 : a.tiles * 64;
-    a.qs = q_sign + static_cast<size_t>(q0) * a.W;
-    a.qn = q_nz + static_cast<size_t>(q0) * a.W;
-    a.ql = q_label ? q_label + static_cast<size_t>(q0) * a.LW : nullptr;
-    const size_t stride = static_cast<size_t>(a.tiles) * p.tile_words();
+// hist, the bases and the fill.  The workspace is that of run(): images [S], toti where run() keeps off, lim where it keeps hstar.
+int run_range(const Problem& pb, int hr, const uint32_t* total, const uint32_t* prior, const int64_t* row_off, int idx_base, int32_t* idx,
+              float* dist, uint8_t* rel, uint32_t* counts, void* workspace, hipStream_t st) {
+  const Plan p = make_plan(pb.Q, pb.N, pb.bits);
+  return for_each_batch("hamming_range", p, pb, counts, workspace, st, [&](RetArgs& a, int q0, size_t stride) -> int {
+    a.idx = idx; a.dist = dist; a.rel = rel;      // (whole buffers: a query's rows start at its row_off)
     const size_t row = static_cast<size_t>(q0) * a.bins * 2;
-    RangeArgs b;
+    BaseArgs b = {};
     b.total = total ? total + row : nullptr;
     b.prior = prior ? prior + row : nullptr;
-    a.img = base;
-    b.toti = base + static_cast<size_t>(a.S) * stride;
-    b.ball = b.toti + stride;
+    b.toti = a.img + static_cast<size_t>(a.S) * stride;
+    b.lim = b.toti + stride;
     b.hr = hr;
-    a.counts = counts ? counts + row : nullptr;
-    if (p.glob && hipMemsetAsync(a.img, 0, static_cast<size_t>(a.S) * stride * 4, st) != hipSuccess)
-      return fail(CMH_ERR_LAUNCH, "hamming_range: memset failed");
-    int rc = launch_any(p.glob, PASS_HIST, a, r_sign, r_nz, r_label, nullptr, st);
+    const int rc = launch_bases<false>(a, b, stride, "hamming_range bases", st);
     if (rc != CMH_OK) return rc;
-    hipLaunchKernelGGL(range_total_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_range totals");
-    hipLaunchKernelGGL(range_scan_kernel, dim3(a.tiles), dim3(64), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_range scan");
-    const size_t used = static_cast<size_t>(a.tiles) * (hr + 1) * 64;
-    hipLaunchKernelGGL(range_base_kernel, dim3(static_cast<unsigned>((used + 255) / 256)), dim3(256), 0, st, a, b);
-    CMH_CHECK_LAUNCH("hamming_range bases");
-    rc = launch_range_any(p.glob, a, b, r_sign, r_nz, r_label, row_off + q0, idx_base, st);
-    if (rc != CMH_OK) return rc;
-  }
-  return CMH_OK;
+    return dispatch(p.glob, a.W, a.LW, std::true_type{}, [&](auto WT, auto LT, auto GLOB) {
+      return launch_walk<WT, LT>(range_kernel<WT, LT, GLOB>, GLOB ? 0 : hr + 1, "hamming_range", a, st, pb.rs, pb.rn, pb.rl, row_off + q0,
+                                 b.lim, hr, idx_base);
+    });
+  });
+}
+
+struct GradePlan {
+  int bins, LW, tiles, S, chunk;
+  size_t lds() const { return (static_cast<size_t>(bins) + (LW == 1 || LW == 3 ? 0 : LW)) * 256; }      // columns + staged query words
+  size_t bytes() const { return static_cast<size_t>(S) * tiles * bins * 256 + 256; }
+};
+
+GradePlan make_grade_plan(int Q, int64_t N, int classes) {
+  GradePlan p;
+  p.bins = classes + 1;
+  p.LW = (classes + 31) / 32;
+  p.tiles = (Q + 63) / 64;
+  p.S = cut_chunks(static_cast<int>(N), p.tiles, p.lds(), 1, 256, &p.chunk);      // 32-bit counters: no limit on a chunk's items
+  return p;
 }
 
 }  // namespace
@@ -1095,8 +979,7 @@ int run_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_la
 using namespace cmh;
 
 extern "C" size_t cmh_retrieval_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
-  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
-  return make_plan(Q, N, bits).bytes();
+  return check_shape(nullptr, Q, N, bits, true, 0, false) == CMH_OK ? make_plan(Q, N, bits).bytes() : 0;
 }
 
 extern "C" int cmh_hamming_hist(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
@@ -1104,9 +987,9 @@ extern "C" int cmh_hamming_hist(const uint32_t* q_sign, const uint32_t* q_nz, co
                                 uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && counts, "hamming_hist: null pointer");
   CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_hist: labels on one side only");
-  const int rc = check_shape("hamming_hist", Q, N, bits, classes, q_label != nullptr);
+  const int rc = check_shape("hamming_hist", Q, N, bits, true, classes, q_label != nullptr);
   if (rc != CMH_OK) return rc;
-  return run("hamming_hist", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, 0, nullptr, nullptr, nullptr, nullptr, counts,
+  return run("hamming_hist", {q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, 0, nullptr, nullptr, nullptr, nullptr, counts,
              workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -1118,10 +1001,10 @@ extern "C" int cmh_hamming_topk(const uint32_t* q_sign, const uint32_t* q_nz, co
   CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_topk: labels on one side only");
   CMH_CHECK_ARG(!rel || q_label, "hamming_topk: hit flags asked for without labels");
   CMH_CHECK_ARG(k >= 1 && k <= CMH_TOPK_MAX, "hamming_topk: k=%lld outside [1, %d]", static_cast<long long>(k), CMH_TOPK_MAX);
-  const int rc = check_shape("hamming_topk", Q, N, bits, classes, q_label != nullptr);
+  const int rc = check_shape("hamming_topk", Q, N, bits, true, classes, q_label != nullptr);
   if (rc != CMH_OK) return rc;
   CMH_CHECK_ARG(k <= N, "hamming_topk: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
-  return run("hamming_topk", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist, rel,
+  return run("hamming_topk", {q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, static_cast<int>(k), idx, dist, rel,
              nullptr, counts, workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -1132,17 +1015,15 @@ extern "C" int cmh_hamming_topk_graded(const uint32_t* q_sign, const uint32_t* q
   CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && idx && dist && grade, "hamming_topk_graded: null pointer");
   CMH_CHECK_ARG(q_label && r_label, "hamming_topk_graded: grades need the labels of both sides");
   CMH_CHECK_ARG(k >= 1 && k <= CMH_TOPK_MAX, "hamming_topk_graded: k=%lld outside [1, %d]", static_cast<long long>(k), CMH_TOPK_MAX);
-  const int rc = check_shape("hamming_topk_graded", Q, N, bits, classes, true);
+  const int rc = check_shape("hamming_topk_graded", Q, N, bits, true, classes, true, kGradeMax);
   if (rc != CMH_OK) return rc;
-  CMH_CHECK_ARG(classes <= kGradeMax, "hamming_topk_graded: classes=%d exceeds %d (a grade is one byte)", classes, kGradeMax);
   CMH_CHECK_ARG(k <= N, "hamming_topk_graded: k=%lld exceeds N=%lld", static_cast<long long>(k), static_cast<long long>(N));
-  return run("hamming_topk_graded", q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, static_cast<int>(k), idx, dist,
+  return run("hamming_topk_graded", {q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, static_cast<int>(k), idx, dist,
              rel, grade, counts, workspace, workspace_bytes, as_stream(stream));
 }
 
 extern "C" size_t cmh_map_count_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
-  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
-  return make_ap_plan(Q, N, bits).ap_bytes();
+  return check_shape(nullptr, Q, N, bits, true, 0, false) == CMH_OK ? make_ap_plan(Q, N, bits).ap_bytes() : 0;
 }
 
 extern "C" int cmh_hamming_ap_partial(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
@@ -1151,12 +1032,12 @@ extern "C" int cmh_hamming_ap_partial(const uint32_t* q_sign, const uint32_t* q_
                                       uint32_t* counts_out, double* ap_sum, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && ap_sum, "hamming_ap_partial: null pointer");
   CMH_CHECK_ARG(q_label && r_label, "hamming_ap_partial: AP needs the labels of both sides");
-  const int rc = check_shape("hamming_ap_partial", Q, N, bits, classes, true);
+  const int rc = check_shape("hamming_ap_partial", Q, N, bits, true, classes, true);
   if (rc != CMH_OK) return rc;
   const size_t need = make_ap_plan(Q, N, bits).ap_bytes();
   CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_ap_partial: workspace %zu < %zu bytes", workspace_bytes, need);
   const uint32_t k = topk <= 0 || topk > INT32_MAX ? static_cast<uint32_t>(INT32_MAX) : static_cast<uint32_t>(topk);      // (R <= 2^31 - 1)
-  return run_ap(q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, k, total_counts, prior_counts, counts_out, ap_sum,
+  return run_ap({q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, k, total_counts, prior_counts, counts_out, ap_sum,
                 workspace, as_stream(stream));
 }
 
@@ -1174,10 +1055,7 @@ extern "C" int cmh_ap_finish(const double* ap_sum, const uint32_t* total_counts,
   return CMH_OK;
 }
 
-extern "C" size_t cmh_range_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
-  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || bits <= 0 || bits > 32 * kRetMaxWords) return 0;
-  return make_plan(Q, N, bits).bytes();
-}
+extern "C" size_t cmh_range_workspace_bytes(int32_t Q, int64_t N, int32_t bits) { return cmh_retrieval_workspace_bytes(Q, N, bits); }
 
 extern "C" int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* q_label, const uint32_t* r_sign,
                                  const uint32_t* r_nz, const uint32_t* r_label, int32_t Q, int64_t N, int32_t bits, int32_t classes,
@@ -1187,65 +1065,25 @@ extern "C" int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, c
   CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && row_off && idx && dist, "hamming_range: null pointer");
   CMH_CHECK_ARG((q_label == nullptr) == (r_label == nullptr), "hamming_range: labels on one side only");
   CMH_CHECK_ARG(!rel || q_label, "hamming_range: hit flags asked for without labels");
-  const int rc = check_shape("hamming_range", Q, N, bits, classes, q_label != nullptr);
+  const int rc = check_shape("hamming_range", Q, N, bits, true, classes, q_label != nullptr);
   if (rc != CMH_OK) return rc;
   CMH_CHECK_ARG(radius_h >= 0 && radius_h <= 2 * bits, "hamming_range: radius_h=%d outside [0, %d]", radius_h, 2 * bits);
   CMH_CHECK_ARG(idx_base >= 0 && idx_base <= INT32_MAX - static_cast<int32_t>(N), "hamming_range: idx_base=%d with N=%lld passes 2^31 - 1",
                 idx_base, static_cast<long long>(N));
   const size_t need = make_plan(Q, N, bits).bytes();
   CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_range: workspace %zu < %zu bytes", workspace_bytes, need);
-  return run_range(q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes, radius_h, total_counts, prior_counts, row_off,
+  return run_range({q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, radius_h, total_counts, prior_counts, row_off,
                    idx_base, idx, dist, rel, counts_out, workspace, as_stream(stream));
 }
 
-namespace cmh {
-namespace {
-
-struct GradePlan {
-  int bins, LW, tiles, S, chunk;
-  size_t lds() const { return (static_cast<size_t>(bins) + (LW == 1 || LW == 3 ? 0 : LW)) * 256; }      // columns + staged query words
-  size_t bytes() const { return static_cast<size_t>(S) * tiles * bins * 256 + 256; }
-};
-
-GradePlan make_grade_plan(int Q, int64_t N, int classes) {
-  GradePlan p;
-  p.bins = classes + 1;
-  p.LW = (classes + 31) / 32;
-  p.tiles = (Q + 63) / 64;
-  p.S = cut_chunks(static_cast<int>(N), p.tiles, p.lds(), 1, 256, &p.chunk);      // 32-bit counters: no limit on a chunk's items
-  return p;
-}
-
-int check_grade_shape(const char* what, int Q, int64_t N, int classes) {
-  CMH_CHECK_ARG(Q > 0 && Q <= 65535 && N > 0, "%s: Q=%d N=%lld", what, Q, static_cast<long long>(N));
-  CMH_CHECK_ARG(N <= kRetMaxN, "%s: N=%lld exceeds %d", what, static_cast<long long>(N), kRetMaxN);
-  CMH_CHECK_ARG(classes > 0, "%s: classes=%d unsupported", what, classes);
-  CMH_CHECK_ARG(classes <= kGradeMax, "%s: classes=%d exceeds %d (a grade is one byte)", what, classes, kGradeMax);
-  return CMH_OK;
-}
-
-template <int LT>
-int launch_grade(const RetArgs& a, const uint32_t* rl, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(grade_kernel<LT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds)) != hipSuccess)
-    return fail(CMH_ERR_LAUNCH, "label_overlap_hist: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL((grade_kernel<LT>), dim3(a.tiles, a.S), dim3(64), lds, st, a, rl);
-  CMH_CHECK_LAUNCH("label_overlap_hist");
-  return CMH_OK;
-}
-
-}  // namespace
-}  // namespace cmh
-
 extern "C" size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes) {
-  if (Q <= 0 || Q > 65535 || N <= 0 || N > kRetMaxN || classes <= 0 || classes > kGradeMax) return 0;
-  return make_grade_plan(Q, N, classes).bytes();
+  return check_shape(nullptr, Q, N, 0, false, classes, true, kGradeMax) == CMH_OK ? make_grade_plan(Q, N, classes).bytes() : 0;
 }
 
 extern "C" int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r_label, int32_t Q, int64_t N, int32_t classes,
                                       uint32_t* grade_counts, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(q_label && r_label && grade_counts, "label_overlap_hist: null pointer");
-  int rc = check_grade_shape("label_overlap_hist", Q, N, classes);
+  int rc = check_shape("label_overlap_hist", Q, N, 0, false, classes, true, kGradeMax);
   if (rc != CMH_OK) return rc;
   const GradePlan p = make_grade_plan(Q, N, classes);
   if (!workspace || workspace_bytes < p.bytes())
@@ -1254,10 +1092,12 @@ extern "C" int cmh_label_overlap_hist(const uint32_t* q_label, const uint32_t* r
   RetArgs a = {};
   a.ql = q_label;
   a.Q = Q; a.N = static_cast<int>(N); a.bits = 32; a.W = 0; a.LW = p.LW; a.bins = p.bins; a.tiles = p.tiles; a.S = p.S; a.chunk = p.chunk;
-  a.img = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  a.img = aligned256<uint32_t>(workspace);
   a.counts = grade_counts;
-  rc = p.LW == 1 ? launch_grade<1>(a, r_label, p.lds(), st) : p.LW == 3 ? launch_grade<3>(a, r_label, p.lds(), st)
-                                                                        : launch_grade<LAB_ANY>(a, r_label, p.lds(), st);
+  const char* what = "label_overlap_hist";
+  rc = p.LW == 1   ? launch_walk<0, 1>(grade_kernel<1>, a.bins, what, a, st, r_label)
+       : p.LW == 3 ? launch_walk<0, 3>(grade_kernel<3>, a.bins, what, a, st, r_label)
+                   : launch_walk<0, LAB_ANY>(grade_kernel<LAB_ANY>, a.bins, what, a, st, r_label);
   if (rc != CMH_OK) return rc;
   const size_t stride = static_cast<size_t>(p.tiles) * p.bins * 64;
   hipLaunchKernelGGL(grade_reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a);
