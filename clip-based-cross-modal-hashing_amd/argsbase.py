@@ -23,6 +23,7 @@ BASE_FLAGS = [
     ("--synthetic-size", int, 2000, "items of the synthetic dataset (this build)"),
     ("--map-tie-order", str, "reference", "mAP ties: reference = the reference's torch.sort order (up to 524 287 database items); stable = by ascending database index, by counting, any database size (this build)"),
     ("--eval-curves", str2bool, False, "test(): also log P@H<=2 / P@N and store the precision-recall and top-N curves in the .mat (this build)"),
+    ("--eval-recall", str2bool, False, "test(): also log Recall@1/5/10 and MedR of the paired query items (image i <-> caption i) and store the rank counts in the .mat (this build)"),
     ("--eval-graded", str2bool, False, "test(): also log NDCG@N / ACG@N / WAP@N (relevance graded by the number of shared labels) and store them in the .mat (this build)"),
 ]
 

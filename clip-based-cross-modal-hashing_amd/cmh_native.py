@@ -153,6 +153,8 @@ SIGNATURES = {
     "cmh_range_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_hamming_range": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_ap_finish": (C.c_int, [_p, _p, _i32, _i32, _i64, _p, _p, _p]),
+    "cmh_rank_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "cmh_hamming_rank": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _i32, _p, _p, _sz, _p]),
     "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
@@ -849,6 +851,39 @@ def hamming_range(q_planes, r_planes, bits, radius_h, q_lab=None, r_lab=None, to
                                   ptr(total_counts), ptr(prior_counts), ptr(row_off), idx_base, ptr(idx), ptr(dist), ptr(rel),
                                   ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_range")
     return ((idx, dist, rel), counts) if want_counts else (idx, dist, rel)
+
+
+RANK_TARGETS_MAX = 8         # target slots per query of one cmh_hamming_rank
+
+
+def hamming_rank(q_planes, r_planes, bits, t_planes, bound):
+    """The three counts behind the rank of given targets, by one walk over the database (no list, no sort):
+    -> int32 [Q, G, 3] = (less, ties_before, ties).  t_planes: the packed planes of the targets, a pair of int32 [Q, G, W] (or
+    [Q * G, W]) tensors; bound int32 [Q, G] (or [Q * G]), 1 <= G <= 8: database items with index < bound count as before the target
+    among its ties (the target's own row in this database; clamp(t - a, 0, b - a) for the shard [a, b) of a larger one), -1 = the
+    slot has no target and gives three zeros.  less + ties_before is the target's column in hamming_topk's row; the counts of the
+    shards of a database add."""
+    qs, qn, rs, rn, Q, N, _ = _retrieval_operands("hamming_rank", q_planes, r_planes, bits, None, None)
+    ts, tn = t_planes
+    require_gpu(ts, tn, bound)
+    dev, W = qs.device, (int(bits) + 31) // 32
+    if Q < 1 or bound.dim() not in (1, 2) or bound.numel() % Q:
+        raise NativeError(f"hamming_rank: bound of shape {tuple(bound.shape)} for {Q} queries")
+    G = bound.numel() // Q
+    if not 1 <= G <= RANK_TARGETS_MAX:
+        raise NativeError(f"hamming_rank: G={G} targets per query outside [1, {RANK_TARGETS_MAX}]")
+    if bound.dim() == 2:
+        fit("hamming_rank", (bound, (Q, G)))
+    for t in (ts, tn):
+        fit("hamming_rank", (t, (Q, G, W) if t.dim() == 3 else (Q * G, W)))
+    for t in (ts, tn, bound):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise NativeError("hamming_rank: target planes and bound are contiguous int32 tensors on the operands' device")
+    out = torch.empty(Q, G, 3, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_rank_workspace_bytes(Q, N, int(bits), G), dev, "retrieval")
+    check(lib().cmh_hamming_rank(ptr(qs), ptr(qn), ptr(rs), ptr(rn), Q, N, int(bits), ptr(ts), ptr(tn), ptr(bound), G, ptr(out),
+                                 ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_rank")
+    return out
 
 
 def label_overlap_hist(q_lab, r_lab, classes):

@@ -46,6 +46,10 @@
 //                            32-bit in-row base of every (chunk, bin <= radius, lane), and a second walk that stores item j at
 //                            row_off[q] + its base's cursor.  The caller sizes the rows from cmh_hamming_hist.
 //
+// Ranks of given targets (instance-level recall: where does the item that belongs to this query rank?; any database size, as shards):
+//   cmh_hamming_rank         per (query, target) the three counts less / ties_before / ties of one walk over the database: no
+//                            columns, a lane keeps its targets' distances and counters in registers; the counts of shards add.
+//
 // Written once, used by every entry point: Block (what a pass kernel starts from), walk2 (the software-pipelined walk over a chunk;
 // select_kernel alone keeps a copy of both, for a measured reason given there),
 // the images -> bases family total / scan / base (REL: with the relevant half, the mAP; without, the radius search), and on the host
@@ -707,6 +711,81 @@ __global__ __launch_bounds__(64) void range_kernel(RetArgs a, const uint32_t* __
   for (; j < b.je; ++j) place(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
 }
 
+// ---- ranks of given targets by counting (cmh_hamming_rank) ------------------------------------------------------------------------
+// The 0-based position of target t in the stable ranking of query q is #{j : h(q, j) < h(q, t)} + #{j < t : h(q, j) = h(q, t)}: a
+// count, so one walk over the database answers it, without columns, sort or list.  A lane holds, for each of its up to GT targets,
+// the target's half-distance h_t (rank_target_kernel; -1 = the slot has no target: no distance is below or at it), its bound and
+// three full 32-bit counters (a chunk may hold any number of items):
+//   less += h < h_t,   ties += h == h_t,   ties_before += (h == h_t) & (j < bound).
+// Every (chunk, tile) workgroup leaves its counters [g][3][lane] where the other passes leave their column image (a.bins = 3 * G);
+// grade_reduce_kernel adds the chunks in ascending order and writes out[q][g][3] once.
+
+// one thread per (q, g): h_t = Tile::half of query q against its g-th target (same arithmetic, same cut of the last word)
+__global__ __launch_bounds__(256) void rank_target_kernel(RetArgs a, const uint32_t* __restrict__ ts, const uint32_t* __restrict__ tn,
+                                                          const int32_t* __restrict__ bound, int G, int32_t* __restrict__ ht) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= static_cast<size_t>(a.Q) * G) return;
+  if (bound[i] < 0) { ht[i] = -1; return; }
+  const size_t q = i / G;
+  const uint32_t last = (a.bits & 31) ? (1u << (a.bits & 31)) - 1u : 0xffffffffu;
+  int both = 0, diff = 0;
+  for (int w = 0; w < a.W; ++w) {
+    const uint32_t nz = a.qn[q * a.W + w] & (w == a.W - 1 ? last : 0xffffffffu) & tn[i * a.W + w];
+    both += __popc(nz);
+    diff += __popc((a.qs[q * a.W + w] ^ ts[i * a.W + w]) & nz);
+  }
+  ht[i] = a.bits - both + 2 * diff;
+}
+
+template <int WT, int GT>
+__global__ __launch_bounds__(64) void rank_kernel(RetArgs a, const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
+                                                  const int32_t* __restrict__ ht, const int32_t* __restrict__ bound, int G) {
+  extern __shared__ uint32_t smem[];
+  const Block b(a);
+  const int lane = b.lane;
+  Tile<WT, LAB_NONE> t;
+  t.load(a, b.q, lane, smem);
+  __syncthreads();
+  int hq[GT], bd[GT];
+  uint32_t less[GT], before[GT], ties[GT];
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {                 // (G < GT: the slots behind the call's targets are empty ones)
+    const bool live = g < G;
+    hq[g] = live ? ht[static_cast<size_t>(b.q) * G + g] : -1;
+    bd[g] = live ? bound[static_cast<size_t>(b.q) * G + g] : -1;
+    less[g] = before[g] = ties[g] = 0u;
+  }
+  auto count = [&](int j, int h) {
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+      const uint32_t eq = h == hq[g] ? 1u : 0u;
+      less[g] += h < hq[g] ? 1u : 0u;
+      ties[g] += eq;
+      before[g] += eq & (j < bd[g] ? 1u : 0u);
+    }
+  };
+  int j = b.jb;
+  if (WT > 0) {
+    using Gr = Group<WT, LAB_NONE>;
+    j = walk2<Gr>(
+        b.jb, b.je, [&](Gr& g, int j0) { g.load(rs, rn, nullptr, j0, false); },
+        [&](const Gr& g, int j0, int u0, int u1) {
+#pragma unroll
+          for (int u = u0; u < u1; ++u) count(j0 + u, t.half(g.s + u * WT, g.n + u * WT));
+        });
+  }
+  for (; j < b.je; ++j) count(j, t.half(rs + static_cast<size_t>(j) * a.W, rn + static_cast<size_t>(j) * a.W));
+  uint32_t* image = a.img + b.at;
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+    if (g < G) {
+      image[(g * 3 + 0) * 64 + lane] = less[g];
+      image[(g * 3 + 1) * 64 + lane] = before[g];
+      image[(g * 3 + 2) * 64 + lane] = ties[g];
+    }
+  }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 // A call's operands as the entry points receive them (ql, rl: null without labels)
 struct Problem {
@@ -973,6 +1052,60 @@ GradePlan make_grade_plan(int Q, int64_t N, int classes) {
   return p;
 }
 
+constexpr int kRankTargets = 8;            // targets per query and call: the widest form of rank_kernel
+
+// The rank pass keeps no columns, so a workgroup's LDS is the staged query words alone (none with 1..4 code words) and its image is
+// the 3 * G counter rows: the chunks only have to fill the chip (32-bit counters: no limit on a chunk's items).
+struct RankPlan {
+  int W, tiles, S, chunk, G;
+  bool staged() const { return W > 4; }
+  size_t targets_bytes() const { return align_up(static_cast<size_t>(tiles) * 64 * G * 4, 256); }      // h_t [Q][G]
+  size_t bytes() const { return 256 + targets_bytes() + static_cast<size_t>(S) * tiles * 3 * G * 256; }
+};
+
+RankPlan make_rank_plan(int Q, int64_t N, int bits, int G) {
+  RankPlan p;
+  p.W = (bits + 31) / 32;
+  p.tiles = (Q + 63) / 64;
+  p.G = G;
+  p.S = cut_chunks(static_cast<int>(N), p.tiles, p.staged() ? static_cast<size_t>(2 * p.W) * 256 : 0, 1, 1024, &p.chunk);
+  return p;
+}
+
+int check_rank_shape(const char* what, int Q, int64_t N, int bits, int G) {
+  const int rc = check_shape(what, Q, N, bits, true, 0, false);
+  if (rc != CMH_OK) return rc;
+  if (G < 1 || G > kRankTargets) return what ? fail(CMH_ERR_INVALID, "%s: G=%d outside [1, %d]", what, G, kRankTargets) : CMH_ERR_INVALID;
+  return CMH_OK;
+}
+
+// the preamble, the walk (WT: 1..4 words in registers, else staged; GT: one target, else eight slots) and the sum over the chunks
+int run_rank(const Problem& pb, const uint32_t* ts, const uint32_t* tn, const int32_t* bound, int G, int32_t* out, void* workspace,
+             hipStream_t st) {
+  const RankPlan p = make_rank_plan(pb.Q, pb.N, pb.bits, G);
+  RetArgs a = {};
+  a.qs = pb.qs; a.qn = pb.qn;
+  a.Q = pb.Q; a.N = static_cast<int>(pb.N); a.bits = pb.bits; a.W = p.W; a.bins = 3 * G; a.tiles = p.tiles; a.S = p.S; a.chunk = p.chunk;
+  int32_t* ht = aligned256<int32_t>(workspace);
+  a.img = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ht) + p.targets_bytes());
+  a.counts = reinterpret_cast<uint32_t*>(out);
+  const size_t pairs = static_cast<size_t>(pb.Q) * G;
+  hipLaunchKernelGGL(rank_target_kernel, dim3(static_cast<unsigned>((pairs + 255) / 256)), dim3(256), 0, st, a, ts, tn, bound, G, ht);
+  CMH_CHECK_LAUNCH("hamming_rank targets");
+  const int32_t* hc = ht;
+  auto walk = [&](auto WT, auto GT) {
+    return launch_walk<WT, LAB_NONE>(rank_kernel<WT, GT>, 0, "hamming_rank", a, st, pb.rs, pb.rn, hc, bound, G);
+  };
+  auto targets = [&](auto WT) { return G == 1 ? walk(WT, Int<1>{}) : walk(WT, Int<kRankTargets>{}); };
+  const int rc = p.staged() ? targets(Int<0>{}) : p.W == 1 ? targets(Int<1>{}) : p.W == 2 ? targets(Int<2>{}) : p.W == 3 ? targets(Int<3>{})
+                                                                                                              : targets(Int<4>{});
+  if (rc != CMH_OK) return rc;
+  const size_t stride = static_cast<size_t>(p.tiles) * a.bins * 64;
+  hipLaunchKernelGGL(grade_reduce_kernel, dim3(static_cast<unsigned>((stride + 255) / 256)), dim3(256), 0, st, a);
+  CMH_CHECK_LAUNCH("hamming_rank reduce");
+  return CMH_OK;
+}
+
 }  // namespace
 }  // namespace cmh
 
@@ -1074,6 +1207,21 @@ extern "C" int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, c
   CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_range: workspace %zu < %zu bytes", workspace_bytes, need);
   return run_range({q_sign, q_nz, q_label, r_sign, r_nz, r_label, Q, N, bits, classes}, radius_h, total_counts, prior_counts, row_off,
                    idx_base, idx, dist, rel, counts_out, workspace, as_stream(stream));
+}
+
+extern "C" size_t cmh_rank_workspace_bytes(int32_t Q, int64_t N, int32_t bits, int32_t G) {
+  return check_rank_shape(nullptr, Q, N, bits, G) == CMH_OK ? make_rank_plan(Q, N, bits, G).bytes() : 0;
+}
+
+extern "C" int cmh_hamming_rank(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q,
+                                int64_t N, int32_t bits, const uint32_t* t_sign, const uint32_t* t_nz, const int32_t* bound, int32_t G,
+                                int32_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && t_sign && t_nz && bound && out, "hamming_rank: null pointer");
+  const int rc = check_rank_shape("hamming_rank", Q, N, bits, G);
+  if (rc != CMH_OK) return rc;
+  const size_t need = make_rank_plan(Q, N, bits, G).bytes();
+  CMH_CHECK_ARG(workspace && workspace_bytes >= need, "hamming_rank: workspace %zu < %zu bytes", workspace_bytes, need);
+  return run_rank({q_sign, q_nz, nullptr, r_sign, r_nz, nullptr, Q, N, bits, 0}, t_sign, t_nz, bound, G, out, workspace, as_stream(stream));
 }
 
 extern "C" size_t cmh_label_overlap_workspace_bytes(int32_t Q, int64_t N, int32_t classes) {

@@ -23,11 +23,22 @@ prints one line, the mAP (mAP@K with --k) of the chosen direction over the file'
 prints one line per query: its number, then `index:distance` (`index:distance:hit` with labels) for EVERY database item within
 Hamming radius R (the units of the distance column; 0.5 steps count for codes with zeros), nearest first, ties by database index.  A
 query whose ball is empty prints its number alone.  --radius excludes --k, --map and --graded; more than --max-hits entries over
-all queries are refused before they are allocated."""
+all queries are refused before they are allocated.
+
+    python retrieve.py --codes <file>.mat --direction i2t --recall [--ks 1,5,10] [--ties index|optimistic|pessimistic|expected]
+
+prints one line, `R@1: ... R@5: ... R@10: ... MedR: ... MeanR: ... MRR: ...`: where the item that BELONGS to each query ranks
+(instance-level recall, by counting: any database size).  The database is the QUERY side of the direction's other modality (i2t:
+q_img against q_txt, the paired test-set protocol) and query i belongs to item i; --queries slices the queries and their targets
+with them.  With --index the database is the saved index and --targets FILE names the pairing: one line per query of the file
+(before --queries), holding the space-separated database indices that belong to it; an empty line = no target.  --ties picks the
+order inside a group of equal distances (index: by database index, as every other mode here; expected: the mean over random
+orders, without MRR).  --recall excludes --radius, --map, --graded and --k."""
 import argparse
 import sys
 
 DIRECTIONS = {"i2t": ("q_img", "r_txt"), "t2i": ("q_txt", "r_img"), "i2i": ("q_img", "r_img"), "t2t": ("q_txt", "r_txt")}
+TIES = ("index", "optimistic", "pessimistic", "expected")
 
 
 def parse(argv=None):
@@ -41,7 +52,28 @@ def parse(argv=None):
     p.add_argument("--graded", action="store_true", help="print the shared-label count of each neighbour in place of the hit flag (needs labels in the file)")
     p.add_argument("--radius", type=float, default=None, metavar="R", help="print every database item within Hamming radius R of each query in place of the k nearest")
     p.add_argument("--max-hits", type=int, default=None, metavar="M", help="with --radius: refuse more than M entries in all (default 2^31 - 1)")
+    p.add_argument("--recall", action="store_true", help="print Recall@K, MedR, mean rank and MRR of the item that belongs to each query in place of the neighbours")
+    p.add_argument("--ks", default=None, metavar="K1,K2,...", help="with --recall: the cut-offs (default 1,5,10)")
+    p.add_argument("--ties", choices=TIES, default=None, help="with --recall: the order inside a group of equal distances (default index)")
+    p.add_argument("--targets", default=None, metavar="FILE", help="with --recall --index: one line per query, the database indices that belong to it")
     args = p.parse_args(argv)
+    if args.recall:
+        for flag, given in (("--radius", args.radius is not None), ("--map", args.map), ("--graded", args.graded), ("--k", args.k is not None)):
+            if given:
+                p.error(f"--recall and {flag} exclude each other")
+        if bool(args.index) != (args.targets is not None):
+            p.error("--recall: --index and --targets go together (without them the pairing is the identity over the file's query sides)")
+        try:
+            args.ks = [int(k) for k in ("1,5,10" if args.ks is None else args.ks).split(",")]
+        except ValueError:
+            args.ks = []
+        if not args.ks or min(args.ks) < 1:
+            p.error("--ks: comma-separated integers >= 1")
+        args.ties = args.ties or "index"
+    else:
+        for flag, given in (("--ks", args.ks is not None), ("--ties", args.ties is not None), ("--targets", args.targets is not None)):
+            if given:
+                p.error(f"{flag} goes with --recall")
     if args.radius is not None:
         for flag, given in (("--k", args.k is not None), ("--map", args.map), ("--graded", args.graded)):
             if given:
@@ -61,6 +93,42 @@ def query_slice(text, n):
     return lo, hi
 
 
+def read_targets(path, queries, items):
+    """One line per query: the space-separated database indices that belong to it -> int64 [queries, G], -1 = padding."""
+    import torch
+    with open(path) as f:
+        rows = [[int(x) for x in line.split()] for line in f.read().splitlines()]
+    if len(rows) != queries:
+        raise SystemExit(f"--targets {path}: {len(rows)} lines for {queries} queries")
+    if any(not 0 <= t < items for r in rows for t in r):
+        raise SystemExit(f"--targets {path}: an index outside 0..{items - 1}")
+    G = max(1, max(len(r) for r in rows))
+    return torch.tensor([r + [-1] * (G - len(r)) for r in rows], dtype=torch.int64).reshape(queries, G)
+
+
+def recall(args, m, q_key, r_key, lo, hi):
+    import torch
+
+    from utils.retrieval import CodeIndex
+    if hi == lo:
+        raise SystemExit("--recall: no queries")
+    queries = torch.from_numpy(m[q_key][lo:hi]).float()
+    if args.index:
+        index = CodeIndex.load(args.index)
+        targets = read_targets(args.targets, m[q_key].shape[0], index.size)[lo:hi]
+    else:
+        side = "q_" + r_key[2:]                                    # the query side of the other modality: the paired items
+        index = CodeIndex(torch.from_numpy(m[side]).float())
+        targets = torch.arange(lo, hi)
+    if index.bits != queries.shape[1]:
+        raise SystemExit(f"--recall: {index.bits}-bit database codes, the queries of {args.codes} have {queries.shape[1]}")
+    out = index.recall(queries, targets, ks=args.ks, ties=args.ties)
+    cols = [f"R@{k}: {float(v):.6f}" for k, v in zip(args.ks, out["recall"])]
+    cols += [f"MedR: {out['median_rank']:g}", f"MeanR: {out['mean_rank']:.6f}"] + ([f"MRR: {out['mrr']:.6f}"] if "mrr" in out else [])
+    print(" ".join(cols))
+    return 0
+
+
 def main(argv=None):
     args = parse(argv)
     import scipy.io as scio
@@ -70,6 +138,8 @@ def main(argv=None):
     q_key, r_key = DIRECTIONS[args.direction]
     m = scio.loadmat(args.codes)
     lo, hi = query_slice(args.queries, m[q_key].shape[0])
+    if args.recall:
+        return recall(args, m, q_key, r_key, lo, hi)
     index = CodeIndex.load(args.index) if args.index else CodeIndex.from_mat(args.codes, side=r_key)
     if args.index and r_key in m:
         print(f"note: --index {args.index} is the database; {r_key} of {args.codes} (--direction {args.direction}) is not searched, "

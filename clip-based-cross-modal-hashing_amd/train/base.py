@@ -353,6 +353,8 @@ class TrainBase(object):
         extra = self._eval_curves(query_img, query_txt, retrieval_img, retrieval_txt) if getattr(self.args, "eval_curves", False) else None
         if getattr(self.args, "eval_graded", False):
             extra = dict(extra or {}, **self._eval_graded(query_img, query_txt, retrieval_img, retrieval_txt))
+        if getattr(self.args, "eval_recall", False):
+            extra = dict(extra or {}, **self._eval_recall(query_img, query_txt))
         self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
 
@@ -392,6 +394,28 @@ class TrainBase(object):
             shown = [f"NDCG@{n}: {v:.6f}" for n, v in at(ndcg, (100, 1000))] + [f"ACG@{n}: {v:.6f}" for n, v in at(acg, (100,))] \
                 + [f"WAP@{n}: {v:.6f}" for n, v in at(wap, (100,))]
             self.logger.info(f">>>>>> graded({name}): " + ", ".join(shown))
+        return extra
+
+    def _eval_recall(self, query_img, query_txt):
+        """--eval-recall: instance-level recall over the query set, image i <-> caption i (utils/retrieval.py): i2t ranks q_txt for
+        every q_img, t2i the reverse.  The log shows R@1/5/10 and MedR with ties by database index and as the mean over random tie
+        orders; the .mat gets the [Q, 1, 3] counts (less, ties_before, ties), from which every convention follows, and the metric
+        vectors of both.  Every rank holds all codes (like _map); only the main one writes."""
+        from utils import retrieval as R
+        ks = R.RECALL_KS
+        extra = {"recall_ks": torch.tensor(ks).numpy()}
+        for name, (q, r) in {"i2t": (query_img, query_txt), "t2i": (query_txt, query_img)}.items():
+            counts = R.target_counts(q, r, torch.arange(q.shape[0]))
+            extra[f"recall_counts_{name}"] = counts.cpu().numpy()
+            shown = []
+            for ties in ("index", "expected"):
+                m = R.recall_from_counts(counts, ks, ties)
+                extra.update({f"recall_{ties}_{name}": m["recall"].numpy(), f"recall_medr_{ties}_{name}": m["median_rank"],
+                              f"recall_meanr_{ties}_{name}": m["mean_rank"]})
+                if "mrr" in m:
+                    extra[f"recall_mrr_{ties}_{name}"] = m["mrr"]
+                shown.append(f"{ties}: " + ", ".join([f"R@{k}: {float(v):.6f}" for k, v in zip(ks, m["recall"])] + [f"MedR: {m['median_rank']:g}"]))
+            self.logger.info(f">>>>>> recall({name}): " + "; ".join(shown))
         return extra
 
     def compute_loss(self):

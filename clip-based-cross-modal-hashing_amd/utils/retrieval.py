@@ -43,7 +43,27 @@ T = offsets[Q] entries in which query q owns offsets[q]:offsets[q+1], ordered by
 ball(q) columns of hamming_topk.  `radius` is in calc_hammingDist's units (the dist column); in half-units hr = min(2K,
 floor(2 * radius)), and an item belongs to the ball iff h <= hr.  The histogram sizes the lists (the one device-to-host read per
 query block is T), cmh_hamming_range fills them: memory is the sum of the balls, not Q x the largest one, and a ball may be wider
-than CMH_TOPK_MAX.  Shards fill one allocation in ascending order; empty balls are legal."""
+than CMH_TOPK_MAX.  Shards fill one allocation in ascending order; empty balls are legal.
+
+Instance-level recall (Recall@K, MedR, mean rank, MRR over PAIRED items: where does the caption of this image rank?).  A rank is a
+count: the 0-based position of database item t in the stable ranking of query q is
+  #{j : h(q, j) < h(q, t)} + #{j < t : h(q, j) = h(q, t)},
+so target_counts makes one walk over the database (cmh_hamming_rank: no list, no sort, any database size, the counts of shards add)
+and returns, per (query, target), counts[q, g] = (less, ties_before, ties): items nearer than the target, items as near with a
+smaller index, items as near (the target included).  The tie convention is the caller's choice, applied by ranks_from_counts:
+  "index"        less + ties_before        the target's column in hamming_topk's row: the module's convention
+  "optimistic"   less                      the target first among its ties
+  "pessimistic"  less + ties - 1           ... last
+  "expected"     less + (ties - 1) / 2     the mean over a uniformly random order of the ties (float64)
+recall_from_counts: a query's best rank is the minimum over its targets (-1 in `targets` pads a row), R@K = the share of queries
+whose best 1-based rank is <= K, median_rank / mean_rank / mrr over the 1-based best ranks, all over the queries that have a
+target.  Under "expected" R@K of a target is clamp((K - less) / ties, 0, 1), the probability that a random tie order puts it in the
+first K: exact for one target per query; with several the per-query maximum is taken, a LOWER BOUND of the probability that any
+lands there.  MRR has no such closed form and is not defined under "expected".
+Bias note: Hamming ties are massive, and under identity pairing t(q) = q the "index" convention favours small q, whose targets
+precede most of their ties.  A NumPy check (2000 random 16-bit codes, each query its item with 10 % of the bits flipped: 10 items
+on average share the target's distance) gives R@1 = 0.546 over the first half of the queries and 0.399 over the second.  Report
+"expected", or both bounds, for paired data."""
 import math
 
 import torch
@@ -407,9 +427,151 @@ def topn_precision(qB, rB, query_L, retrieval_L, topn=DEFAULT_TOPN, shard_items=
     return precision, recall, rel
 
 
+RANK_TIES = ("index", "optimistic", "pessimistic", "expected")
+RECALL_KS = (1, 5, 10)
+
+
+def _targets(what, targets, Q, n, dev):
+    """targets: integers [Q] or [Q, G], database indices, -1 = padding -> int64 [Q, G] on dev; anything else is refused."""
+    t = torch.as_tensor(targets)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise N.NativeError(f"{what}: targets are integer database indices, not {t.dtype}")
+    if t.dim() == 1:
+        t = t[:, None]
+    if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < 1:
+        raise N.NativeError(f"{what}: targets of shape {tuple(t.shape)} for {Q} queries ([Q] or [Q, G])")
+    t = t.to(dev).long()
+    if bool(((t < -1) | (t >= n)).any()):
+        raise N.NativeError(f"{what}: a target outside 0..{n - 1} (-1 pads a row)")
+    return t
+
+
+def _target_counts(what, qp, rp, bits, targets, shard_items=None):
+    """(less, ties_before, ties) of every (query, target) over any number of shards, query blocks and blocks of RANK_TARGETS_MAX
+    targets -> int64 [Q, G, 3].  The targets' planes are rows of the packed database (index_select); for the shard [a, b) the bound
+    is clamp(t - a, 0, b - a): all of a shard behind the target, none of one before it; the shards' counts add."""
+    Q, n, blocks, shards = _plan(what, qp, rp, shard_items)
+    t = _targets(what, targets, Q, n, qp[0].device)
+    parts = []
+    for qcut in blocks:
+        q, cols = _rows(qp, qcut, Q), []
+        for g0 in range(0, t.shape[1], N.RANK_TARGETS_MAX):
+            tt = t[qcut[0]:qcut[1], g0:g0 + N.RANK_TARGETS_MAX]
+            rows = tt.clamp(min=0).reshape(-1)
+            tp = tuple(x.index_select(0, rows) for x in rp)
+            acc = None
+            for a, b in shards:
+                bound = torch.where(tt >= 0, (tt - a).clamp(0, b - a), tt).to(torch.int32).contiguous()
+                c = N.hamming_rank(q, _rows(rp, (a, b), n), bits, tp, bound).long()
+                acc = c if acc is None else acc + c
+            cols.append(acc)
+        parts.append(cols[0] if len(cols) == 1 else torch.cat(cols, 1))
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def target_counts(qB, rB, targets, shard_items=None):
+    """-> int64 [Q, G, 3] on the GPU: (less, ties_before, ties) of database item targets[q, g] in the ranking of query q (see the
+    module docstring); a padding slot (-1) gives three zeros.  targets: integers [Q] or [Q, G]."""
+    dev = _dev(qB, rB)
+    return _target_counts("target_counts", _codes(qB, dev), _codes(rB, dev), rB.shape[-1], targets, shard_items)
+
+
+def _counts3(counts):
+    c = counts.detach().cpu().to(torch.int64)
+    if c.dim() != 3 or c.shape[2] != 3:
+        raise ValueError(f"counts of shape {tuple(c.shape)}: [Q, G, 3] of target_counts")
+    return c[:, :, 0], c[:, :, 1], c[:, :, 2]
+
+
+def _tie_rule(ties):
+    if ties not in RANK_TIES:
+        raise ValueError(f"ties={ties!r}: one of {RANK_TIES}")
+    return ties
+
+
+def ranks_from_counts(counts, ties="index"):
+    """counts [Q, G, 3] (target_counts) -> the 0-based rank of every target under the tie convention: int64 [Q, G] on the CPU, -1
+    for padding ("expected": float64, NaN for padding)."""
+    less, before, tied = _counts3(counts)
+    ties = _tie_rule(ties)
+    pad = tied == 0                                                    # a target is one of its own ties
+    if ties == "expected":
+        r = less.double() + (tied - 1).double() / 2
+        return torch.where(pad, torch.full_like(r, float("nan")), r)
+    r = less + before if ties == "index" else less if ties == "optimistic" else less + tied - 1
+    return torch.where(pad, torch.full_like(r, -1), r)
+
+
+class _Metrics(dict):
+    """recall_from_counts' result; under ties="expected" it has no "mrr", and asking for it says why."""
+
+    def __missing__(self, key):
+        if key == "mrr":
+            raise N.NativeError('recall_from_counts: mrr is not defined under ties="expected" (no closed form over random tie orders)')
+        raise KeyError(key)
+
+
+def recall_from_counts(counts, ks=RECALL_KS, ties="index"):
+    """counts [Q, G, 3] (target_counts, on any device) -> {"recall": float64 [len(ks)], "median_rank", "mean_rank", "mrr": floats
+    over the 1-based best ranks, "best_rank": [Q] 1-based, -1 without a target ("expected": float64, NaN)}; float64 arithmetic on
+    the CPU.  Means run over the queries with at least one target (all zeros when there is none).  "expected": see the module
+    docstring; no "mrr"."""
+    less, _, tied = _counts3(counts)
+    ties = _tie_rule(ties)
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 1:
+        raise ValueError(f"ks {ks}: cut-offs >= 1")
+    r = ranks_from_counts(counts, ties)
+    pad = tied == 0
+    has = ~pad.all(1)
+    expected = ties == "expected"
+    if expected:
+        best = torch.where(pad, torch.full_like(r, float("inf")), r).min(1).values + 1.0
+        best = torch.where(has, best, torch.full_like(best, float("nan")))
+        hit = [((k - less).double() / tied.clamp(min=1).double()).clamp(0, 1).masked_fill(pad, 0.0).max(1).values for k in ks]
+    else:
+        best = torch.where(pad, torch.full_like(r, torch.iinfo(torch.int64).max - 1), r).min(1).values + 1
+        best = torch.where(has, best, torch.full_like(best, -1))
+        hit = [(best <= k).double() for k in ks]
+    out = _Metrics(best_rank=best)
+    if not bool(has.any()):
+        out.update(recall=torch.zeros(len(ks), dtype=torch.float64), median_rank=0.0, mean_rank=0.0)
+        if not expected:
+            out["mrr"] = 0.0
+        return out
+    b = best[has].double()
+    s = b.sort().values
+    out.update(recall=torch.stack([h[has].mean() for h in hit]), median_rank=float((s[(s.numel() - 1) // 2] + s[s.numel() // 2]) / 2),
+               mean_rank=float(b.mean()))
+    if not expected:
+        out["mrr"] = float((1.0 / b).mean())
+    return out
+
+
+def _identity(what, Q, n):
+    if Q > n:
+        raise N.NativeError(f"{what}: identity pairing needs Q={Q} <= N={n} (pass targets)")
+    return torch.arange(Q)
+
+
+def recall_at_k(qB, rB, targets=None, ks=RECALL_KS, ties="index", shard_items=None):
+    """Recall@K, MedR, mean rank and MRR of paired items: recall_from_counts of target_counts, plus "counts" (int64 [Q, G, 3] on
+    the GPU) for any other convention.  targets=None: identity pairing t(q) = q, the paired test-set protocol (Q <= N)."""
+    _tie_rule(ties)
+    dev = _dev(qB, rB)
+    qp, rp = _codes(qB, dev), _codes(rB, dev)
+    if targets is None:
+        targets = _identity("recall_at_k", qp[0].shape[0], rp[0].shape[0])
+    counts = _target_counts("recall_at_k", qp, rp, rB.shape[-1], targets, shard_items)
+    out = recall_from_counts(counts, ks, ties)
+    out["counts"] = counts
+    return out
+
+
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
-    range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists.
+    range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
+    rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
     plane that add() grows geometrically, so many small add()s never make many small shards.  save() / load() keep the packed
     planes and labels as one .npz (data only)."""
@@ -550,6 +712,22 @@ class CodeIndex:
                                      radius_half_units(radius, self.bits), ql, self.labels if ql is not None else None,
                                      self.shard_items, max_hits)
         return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+    def rank_of(self, query_codes, targets):
+        """target_counts of the queries against the index: int64 [Q, G, 3] = (less, ties_before, ties) of item targets[q, g]."""
+        if query_codes.shape[-1] != self.bits:
+            raise N.NativeError(f"CodeIndex.rank_of: {query_codes.shape[-1]}-bit queries for an index of {self.bits} bits")
+        return _target_counts("CodeIndex.rank_of", _codes(query_codes, self.device), self.planes, self.bits, targets, self.shard_items)
+
+    def recall(self, query_codes, targets=None, ks=RECALL_KS, ties="index"):
+        """recall_at_k of the queries against the index (targets=None: query q belongs to item q)."""
+        _tie_rule(ties)
+        if targets is None:
+            targets = _identity("CodeIndex.recall", query_codes.shape[0] if query_codes.dim() > 1 else 1, self.size)
+        counts = self.rank_of(query_codes, targets)
+        out = recall_from_counts(counts, ks, ties)
+        out["counts"] = counts
+        return out
 
     def duplicates(self, radius=0, max_hits=None):
         """The index searched against itself: for every item the OTHER items within `radius`, as hamming_range's CSR tuple (rel when

@@ -513,6 +513,25 @@ int cmh_hamming_range(const uint32_t* q_sign, const uint32_t* q_nz, const uint32
                       int32_t radius_h, const uint32_t* total_counts, const uint32_t* prior_counts, const int64_t* row_off,
                       int32_t idx_base, int32_t* idx, float* dist, uint8_t* rel, uint32_t* counts_out, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* Ranks of given targets by counting (instance-level recall: Recall@K, MedR, MRR over paired items).  The 0-based position of
+ * database item t in the stable ranking of query q (its column in cmh_hamming_topk's row) is
+ *   #{j : h(q, j) < h(q, t)} + #{j < t : h(q, j) = h(q, t)},
+ * so one walk over the database gives it: no list, no sort.  It replaces cmh_hamming_topk with k = N followed by a search of the
+ * [Q, N] index matrix for the target (8 bytes per pair, k <= CMH_TOPK_MAX, no sum over shards).  Every query has G target slots:
+ *   t_sign, t_nz u32 [Q*G, W]  the packed planes of the targets (W = ceil(bits / 32)): slot g of query q is row q * G + g
+ *   bound        i32 [Q*G]     0..N: database items with index < bound count as "before" among the ties (the target's own index
+ *                              in this call's database; for one shard [a, b) of a larger database clamp(t - a, 0, b - a));
+ *                              -1: the slot has no target, its planes are not read and its three outputs are 0
+ *   out          i32 [Q, G, 3] (less, ties_before, ties): items at a smaller half-distance than the target, items at the target's
+ *                              half-distance with index < bound, items at the target's half-distance (the target itself included
+ *                              when it lies in this call's database).  The counts of the shards of a database add.
+ * 1 <= G <= 8; Q <= 65535, N <= 524287, bits <= 2048 per call as above.  Refused with a negative status before any launch: null
+ * operands, sizes outside the limits, a workspace below cmh_rank_workspace_bytes (0 outside the limits).  Every output word is
+ * written once, without atomics: two calls give equal bits. */
+size_t cmh_rank_workspace_bytes(int32_t Q, int64_t N, int32_t bits, int32_t G);
+int cmh_hamming_rank(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q, int64_t N,
+                     int32_t bits, const uint32_t* t_sign, const uint32_t* t_nz, const int32_t* bound, int32_t G, int32_t* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
 /* A database larger than N <= 524287 is searched as shards (utils/retrieval.py: row slices of the packed planes, each within the
  * limits above) and the per-shard lists are folded together in ascending shard order (csrc/retrieval_merge.hip); the result is bit
  * for bit the list of one cmh_hamming_topk over the whole database, i.e. of torch.sort(calc_hammingDist(q, r), stable=True).

@@ -42,7 +42,15 @@ histogram).  Same rules (warm-up, legs alternating in one process, device events
 native call alone on offsets made before the timed regions) and `hist` run next to them.  The lists of the two routes are compared
 on the timed inputs.  Reported per radius: both times, the output bytes of both routes (T x 9 against Q x kmax x 9), and the floors
 of the new route's three passes over the database (hist, and hist + fill inside the native call) plus its output bytes over HBM
-bandwidth (8 TB/s).  ONE JSON line for all shapes."""
+bandwidth (8 TB/s).  ONE JSON line for all shapes.
+
+--rank runs the target-rank legs instead: the ranks of paired items by counting (utils.retrieval._target_counts: the gather of the
+targets' planes and ONE cmh_hamming_rank; `native` is the call alone on planes gathered before the timed regions) against the only
+route there was, hamming_topk(k = N) and a search of the [Q, N] index matrix for the target (`topk_lookup`), at 5000 x 5000 x 64 bit
+(identity pairing) and 5000 x 190 834 x 128 bit (one random target per query).  Same rules (warm-up, legs alternating in one
+process, device events around regions of --reps calls; the baseline runs once per region); both routes' positions are compared on
+the timed inputs.  A baseline that cannot be allocated is recorded as such.  Then 5000 x 2 000 000 x 64 bit in four shards, which no
+other route takes: 16 of its rows are compared with counts made from the full distance rows.  One JSON line per shape."""
 import argparse
 import json
 import os
@@ -325,6 +333,79 @@ def range_legs(args):
         raise SystemExit("the radius search disagrees with hamming_topk(k = largest ball) cut at the balls")
 
 
+RANK = {"paired_5000_64": (5000, 5000, 64, True), "nuswide_190834_128": (5000, 190834, 128, False)}
+
+
+def rank_legs(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+
+    def operands(Q, n, K, identity):
+        g = torch.Generator(device=dev).manual_seed(1)
+        rB = torch.sign(torch.randn(n, K, generator=g, device=dev) + 1e-3)
+        t = torch.arange(Q, device=dev) if identity else torch.randint(0, n, (Q,), generator=g, device=dev)
+        flip = torch.rand(Q, K, generator=g, device=dev) < 0.1                     # a query = its item with a tenth of the bits flipped
+        return torch.where(flip, -rB[t], rB[t]), rB, t
+
+    def row_counts(qB, rB, t, rows):
+        h = (qB.shape[1] - qB[:rows] @ rB.T).long()
+        ht = h.gather(1, t[:rows, None])
+        before = (h == ht) & (torch.arange(rB.shape[0], device=dev)[None, :] < t[:rows, None])
+        return torch.stack([(h < ht).sum(1), before.sum(1), (h == ht).sum(1)], 1)
+
+    for name, (Q, n, K, identity) in RANK.items():
+        qB, rB, t = operands(Q, n, K, identity)
+        qp, rp = N.pack_codes(qB), N.pack_codes(rB)
+        tp = tuple(x.index_select(0, t) for x in rp)
+        bound = t.to(torch.int32)[:, None].contiguous()
+
+        def lookup():
+            idx = N.hamming_topk(qp, rp, K, n)[0]
+            return (idx == t[:, None]).to(torch.uint8).argmax(1)
+
+        legs = {"counting": (args.reps, lambda: R._target_counts("bench", qp, rp, K, t)),
+                "native": (args.reps, lambda: N.hamming_rank(qp, rp, K, tp, bound))}
+        counts = legs["counting"][1]()                                            # warm-up, and the outputs on the timed inputs
+        same = bool(torch.equal(counts, legs["native"][1]().long())) and bool(torch.equal(counts[:64, 0], row_counts(qB, rB, t, 64)))
+        line = {"tool": "retrieval_bench", "leg": "rank", "shape": name, "Q": Q, "N": n, "bits": K, "pairing": "identity" if identity else "random",
+                "regions": REGIONS, "reps": args.reps, "mean_ties": round(float(counts[:, 0, 2].double().mean()), 2)}
+        try:
+            pos = lookup()
+            same = same and bool(torch.equal(pos, counts[:, 0, 0] + counts[:, 0, 1]))
+            del pos
+            legs["topk_lookup"] = (1, lookup)
+            line["topk_lookup_bytes"] = Q * n * 8
+        except torch.cuda.OutOfMemoryError:
+            line["topk_lookup"] = f"cannot allocate the [Q, N] lists of k = N ({Q * n * 8} bytes)"
+        torch.cuda.synchronize()
+        line.update(outputs_equal=same, ms=_timed(legs, REGIONS))
+        fl = {k: v for k, v in floors_ms(Q, n, K, 0, 1).items() if k in ("bytes", "valu")}      # (no columns: no LDS increments)
+        line["ms"]["native"]["floor_ms"] = dict({k: round(v, 4) for k, v in fl.items()}, bound=max(fl, key=fl.get))
+        if "topk_lookup" in legs:
+            line["ms"]["counting"]["over_topk_lookup"] = round(line["ms"]["counting"]["median"] / line["ms"]["topk_lookup"]["median"], 4)
+        _emit(args, line)
+        if not same:
+            raise SystemExit(f"{name}: the ranks by counting disagree with the target's column in hamming_topk(k = N)")
+        del qB, rB, t, qp, rp, tp, bound, legs, counts
+    if args.no_large:
+        return
+    Q, n, K = 5000, 2000000, 64
+    qB, rB, t = operands(Q, n, K, False)
+    qp, rp = N.pack_codes(qB), N.pack_codes(rB)
+    legs = {"counting": (1, lambda: R._target_counts("bench", qp, rp, K, t))}
+    counts = legs["counting"][1]()
+    same = bool(torch.equal(counts[:16, 0], row_counts(qB, rB, t, 16)))
+    torch.cuda.synchronize()
+    line = {"tool": "retrieval_bench", "leg": "rank", "shape": "synthetic_2000000_64", "Q": Q, "N": n, "bits": K, "pairing": "random",
+            "shards": len(R._cuts(n, R.SHARD_ITEMS)), "regions": REGIONS, "outputs_equal": same, "topk_lookup": "no such route: k <= 524 287",
+            "ms": _timed(legs, REGIONS)}
+    _emit(args, line)
+    if not same:
+        raise SystemExit("synthetic_2000000_64: the sharded ranks by counting disagree with counts made from the distance rows")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
@@ -332,8 +413,9 @@ def main():
     ap.add_argument("--out", default="", help="append the JSON lines to this file")
     ap.add_argument("--sharded", action="store_true", help="run the sharded leg (see above) instead of the others")
     ap.add_argument("--map", action="store_true", help="run the mAP legs (see above) instead of the others")
-    ap.add_argument("--no-large", action="store_true", help="--map: leave out the 2 000 000-item database")
+    ap.add_argument("--no-large", action="store_true", help="--map, --rank: leave out the 2 000 000-item database")
     ap.add_argument("--range", action="store_true", help="run the radius-search legs (see above) instead of the others")
+    ap.add_argument("--rank", action="store_true", help="run the target-rank legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -345,6 +427,8 @@ def main():
         return map_legs(args)
     if args.range:
         return range_legs(args)
+    if args.rank:
+        return rank_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
