@@ -157,6 +157,8 @@ SIGNATURES = {
     "cmh_hamming_rank": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _i32, _p, _p, _sz, _p]),
     "cmh_label_overlap_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
+    "cmh_topk_few_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_hamming_topk_few": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -701,6 +703,9 @@ def _retrieval_operands(what, q_planes, r_planes, bits, q_lab, r_lab):
     return qs, qn, rs, rn, Q, N, LW
 
 
+check_retrieval_operands = _retrieval_operands      # for callers that use labels beside a native call that takes none (utils/retrieval.py)
+
+
 def hamming_hist(q_planes, r_planes, bits, q_lab=None, r_lab=None):
     """-> counts int32 [Q, 2*bits+1, 2]: counts[i, h, 1] = database items at calc_hammingDist == h/2 from query i that share a
     label with it, counts[i, h, 0] = the others (everything without labels)."""
@@ -778,6 +783,31 @@ def hamming_topk(q_planes, r_planes, bits, k, q_lab=None, r_lab=None, want_count
                                  ptr(idx), ptr(dist), ptr(rel), ptr(counts), ptr(ws), ws.numel(), stream_ptr(dev)),
           "cmh_hamming_topk")
     return (idx, dist, rel, counts) if want_counts else (idx, dist, rel)
+
+
+FEW_Q_MAX = 64               # include/cmh.h CMH_FEW_Q_MAX, CMH_FEW_K_MAX, CMH_FEW_BITS_MAX: the limits of cmh_hamming_topk_few
+FEW_K_MAX = 4096
+FEW_BITS_MAX = 128
+
+
+def hamming_topk_few(q_planes, r_planes, bits, k):
+    """hamming_topk for few queries against a database of any size up to 2^31 - 1 items in ONE native call (csrc/retrieval_few.hip:
+    lanes own items): -> (idx int32 [Q, k], dist f32 [Q, k]), row q = the first k columns of torch.sort(hamming_dist[q], stable=True).
+    1 <= Q <= FEW_Q_MAX, bits <= FEW_BITS_MAX, 1 <= k <= min(N, FEW_K_MAX); no labels (gather the k results' label words)."""
+    qs, qn, rs, rn, Q, N, _ = _retrieval_operands("hamming_topk_few", q_planes, r_planes, bits, None, None)
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= FEW_K_MAX:                                     # (before anything of Q x k entries is allocated)
+        raise NativeError(f"hamming_topk_few: k={k} outside [1, {FEW_K_MAX}]")
+    if k > N:
+        raise NativeError(f"hamming_topk_few: k={k} exceeds N={N}")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    need = lib().cmh_topk_few_workspace_bytes(Q, N, int(bits))      # 0 outside the limits: the call below refuses with the reason
+    ws = workspace(need, dev, "retrieval_few")
+    check(lib().cmh_hamming_topk_few(ptr(qs), ptr(qn), ptr(rs), ptr(rn), Q, N, int(bits), k, ptr(idx), ptr(dist),
+                                     ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_topk_few")
+    return idx, dist
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte

@@ -1,0 +1,31 @@
+"""What turns a method model's output into its hash code in {-1, 0, +1}: stated once, for the trainers' evaluation loops
+(train/base.py::get_code*, reference train/base.py:130-223) and for the query front end (query.py)."""
+import torch
+
+import cmh_native as N
+
+
+def sign_code(out) -> torch.Tensor:
+    """sign() of the tanh head's output (DSPH, DNpH, DMsH_LN, DHaPH; reference train/base.py:130-148)."""
+    return N.sign_codes(out)
+
+
+def pair_argmax_code(out) -> torch.Tensor:
+    """argmax over each pair of probabilities; index 0 -> -1, 1 -> +1 (DCHMT; reference train/base.py:150-158).  `out`: the head's
+    list of [B, 2] pairs, or their concatenation [B, 2K]."""
+    p = torch.cat(out, dim=-1) if isinstance(out, (list, tuple)) else out
+    return N.pair_argmax_codes(p)
+
+
+def first_sign_code(out) -> torch.Tensor:
+    """sign() of the first output; the second is the class logits (DNPH; reference train/base.py:206-223)."""
+    return N.sign_codes(out[0])
+
+
+CODE_RULES = {"DSPH": sign_code, "DNpH": sign_code, "DMsH_LN": sign_code, "DHaPH": sign_code, "DCHMT": pair_argmax_code,
+              "DNPH": first_sign_code}
+
+
+def code_rule(method):
+    """The rule TrainBase._codes_for_eval applies for `method` (sign_code for every method without a rule of its own)."""
+    return CODE_RULES.get(method, sign_code)

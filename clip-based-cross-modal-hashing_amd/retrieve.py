@@ -33,7 +33,15 @@ q_img against q_txt, the paired test-set protocol) and query i belongs to item i
 with them.  With --index the database is the saved index and --targets FILE names the pairing: one line per query of the file
 (before --queries), holding the space-separated database indices that belong to it; an empty line = no target.  --ties picks the
 order inside a group of equal distances (index: by database index, as every other mode here; expected: the mean over random
-orders, without MRR).  --recall excludes --radius, --map, --graded and --k."""
+orders, without MRR).  --recall excludes --radius, --map, --graded and --k.
+
+    python retrieve.py --text "a dog on a beach" --index db.npz --method DSPH --pretrained model.pth -clip-path ViT-B-32.pt --output-dim 64 --k 10
+
+asks the index a question: every --text CAPTION and --image PATH (both repeatable, in any mix; answered in the order given) is
+encoded by the trained model (query.py::QueryEncoder: the tokenizer or the image transform, the towers, the method's heads and its
+code rule) and searched in the saved CodeIndex.  No --codes file is needed.  Per query one block: a line `query <number> <text|image>:
+<what was asked>`, then k lines `<rank> <database index> <distance>`, nearest first, ties by database index.  --max-words,
+--resolution, --gemm-dtype and --bpe-path are the trainer's options of those names.  MITH and TwDH are not supported here."""
 import argparse
 import sys
 
@@ -41,9 +49,26 @@ DIRECTIONS = {"i2t": ("q_img", "r_txt"), "t2i": ("q_txt", "r_img"), "i2i": ("q_i
 TIES = ("index", "optimistic", "pessimistic", "expected")
 
 
+class _Ask(argparse.Action):
+    """--text / --image append (kind, value) to one list, so that the questions keep the order of the command line."""
+
+    def __call__(self, parser, namespace, value, option_string=None):
+        namespace.ask = (getattr(namespace, "ask", None) or []) + [(option_string.lstrip("-"), value)]
+
+
 def parse(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--codes", required=True, help=".mat file written by a trainer (save_mat)")
+    p.add_argument("--codes", default=None, help=".mat file written by a trainer (save_mat); required unless --text / --image ask the questions")
+    p.add_argument("--text", action=_Ask, metavar="CAPTION", help="search the --index for this caption (repeatable; needs --method, --pretrained, -clip-path, --output-dim)")
+    p.add_argument("--image", action=_Ask, metavar="PATH", help="search the --index for this picture (repeatable, mixes with --text)")
+    p.add_argument("--method", default=None, help="with --text / --image: the method the checkpoint was trained with")
+    p.add_argument("--pretrained", default=None, metavar="FILE", help="with --text / --image: the trained model (model-<epoch>.pth)")
+    p.add_argument("-clip-path", "--clip-path", dest="clip_path", default=None, metavar="FILE", help="with --text / --image: the CLIP checkpoint the model was built on")
+    p.add_argument("--output-dim", type=int, default=None, help="with --text / --image: the code length in bits")
+    p.add_argument("--max-words", type=int, default=32)
+    p.add_argument("--resolution", type=int, default=224)
+    p.add_argument("--gemm-dtype", default="f32")
+    p.add_argument("--bpe-path", default=None, metavar="FILE", help="the CLIP BPE merges file (default: next to the tokenizer)")
     p.add_argument("--direction", choices=sorted(DIRECTIONS), default="i2t", help="query side -> database side")
     p.add_argument("--k", type=int, default=None, help="neighbours per query (default 10); with --map: mAP@K (default: the whole database)")
     p.add_argument("--map", action="store_true", help="print the mAP of the direction in place of the neighbours (needs labels in the file)")
@@ -57,6 +82,22 @@ def parse(argv=None):
     p.add_argument("--ties", choices=TIES, default=None, help="with --recall: the order inside a group of equal distances (default index)")
     p.add_argument("--targets", default=None, metavar="FILE", help="with --recall --index: one line per query, the database indices that belong to it")
     args = p.parse_args(argv)
+    args.ask = getattr(args, "ask", None) or []
+    if args.ask:
+        if not args.index:
+            p.error("--text / --image search a saved CodeIndex: --index FILE is required")
+        for flag, given in (("--codes", args.codes is not None), ("--map", args.map), ("--graded", args.graded), ("--recall", args.recall),
+                            ("--radius", args.radius is not None), ("--queries", args.queries != ":")):
+            if given:
+                p.error(f"--text / --image and {flag} exclude each other")
+        missing = [flag for flag, v in (("--method", args.method), ("--pretrained", args.pretrained), ("-clip-path", args.clip_path),
+                                        ("--output-dim", args.output_dim)) if v is None]
+        if missing:
+            p.error(f"--text / --image need the model: {', '.join(missing)} missing")
+        if args.k is not None and args.k < 1:
+            p.error("--k: at least 1")
+    elif args.codes is None:
+        p.error("the following arguments are required: --codes")
     if args.recall:
         for flag, given in (("--radius", args.radius is not None), ("--map", args.map), ("--graded", args.graded), ("--k", args.k is not None)):
             if given:
@@ -129,8 +170,42 @@ def recall(args, m, q_key, r_key, lo, hi):
     return 0
 
 
+def ask(args):
+    """--text / --image: encode the questions, search the index, print one block per question."""
+    from query import QueryEncoder, check_method
+    try:
+        check_method(args.method)                                  # by name, before the index or the checkpoint is read
+    except (NotImplementedError, ValueError) as e:
+        raise SystemExit(str(e))
+    import torch
+
+    from utils.retrieval import CodeIndex
+    index = CodeIndex.load(args.index)
+    if index.bits != args.output_dim:
+        raise SystemExit(f"--index {args.index}: {index.bits}-bit codes, the model of --output-dim {args.output_dim} writes {args.output_dim}-bit ones")
+    enc = QueryEncoder(args.method, args.pretrained, args.clip_path, args.output_dim, max_words=args.max_words,
+                       resolution=args.resolution, gemm_dtype=args.gemm_dtype, bpe_path=args.bpe_path)
+    k = min(10 if args.k is None else args.k, index.size)
+    texts = [v for kind, v in args.ask if kind == "text"]
+    images = [v for kind, v in args.ask if kind == "image"]
+    codes = {"text": enc.encode_text(texts) if texts else None, "image": enc.encode_image(images) if images else None}
+    at = {"text": 0, "image": 0}
+    rows = []
+    for kind, _ in args.ask:                                       # back into the order of the command line
+        rows.append(codes[kind][at[kind]])
+        at[kind] += 1
+    idx, dist = (t.cpu().numpy() for t in index.search(torch.stack(rows), k))
+    for i, (kind, value) in enumerate(args.ask):
+        print(f"query {i} {kind}: {value}")
+        for j in range(k):
+            print(f"{j + 1} {idx[i, j]} {dist[i, j]:g}")
+    return 0
+
+
 def main(argv=None):
     args = parse(argv)
+    if args.ask:
+        return ask(args)
     import scipy.io as scio
     import torch
 

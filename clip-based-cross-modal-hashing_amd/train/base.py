@@ -18,6 +18,7 @@ from torch.utils.data import DataLoader
 
 import cmh_native as N
 import dist_utils as du
+from code_rules import first_sign_code, pair_argmax_code, sign_code
 from streams import AlternatingStreams
 from utils import get_logger, get_summary_writer
 from utils.calc_utils import calc_map_k_matrix as calc_map_k
@@ -227,12 +228,11 @@ class TrainBase(object):
 
     def get_code(self, data_loader, length: int):
         return self._code_loop(data_loader, length, lambda i, t, b: (
-            N.sign_codes(self.model.encode_image(i)), N.sign_codes(self.model.encode_text(t))))
+            sign_code(self.model.encode_image(i)), sign_code(self.model.encode_text(t))))
 
     def make_hash_code_DCHMT(self, code) -> torch.Tensor:
         """argmax over each pair; index 0 -> -1, 1 -> +1 (train/base.py:150-158)."""
-        p = torch.cat(code, dim=-1) if isinstance(code, (list, tuple)) else code
-        return N.pair_argmax_codes(p)
+        return pair_argmax_code(code)
 
     def get_code_DCHMT(self, data_loader, length: int):
         return self._code_loop(data_loader, length, lambda i, t, b: (
@@ -240,7 +240,7 @@ class TrainBase(object):
 
     def get_code_DNPH(self, data_loader, length: int):
         return self._code_loop(data_loader, length, lambda i, t, b: (
-            N.sign_codes(self.model.encode_image(i)[0]), N.sign_codes(self.model.encode_text(t)[0])))
+            first_sign_code(self.model.encode_image(i)), first_sign_code(self.model.encode_text(t))))
 
     def backward(self, loss, *loss_modules):
         """loss.backward(); with one process per GPU also the gradient means over the ranks, each tower's all-reduce queued from

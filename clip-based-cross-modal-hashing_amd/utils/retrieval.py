@@ -25,13 +25,16 @@ Means follow the convention of the curves: over the queries with at least one re
 graded_topk returns the grades of the neighbours; grade_histogram counts, per query, the database items of every grade (it depends
 on the labels only: one call serves all directions of an evaluation) and is what IDCG is computed from, without sorting anything.
 
-Size.  The native entry points take N <= 524 287 database items and Q <= 65 535 queries per call.  Every function here takes any
+Few queries (Q <= QUERIES_FEW, k <= 4096, codes up to 128 bit, no shard size stated) take ONE cmh_hamming_topk_few over the whole
+database, whatever its size (csrc/retrieval_few.hip: lanes own items; _few_route): the same bytes as the route below.
+
+Size.  The other native entry points take N <= 524 287 database items and Q <= 65 535 queries per call.  Every function here takes any
 database up to 2^31 - 1 items and any number of queries: the packed planes are row-major, so the database is cut into SHARDS of
 `shard_items` rows (views, packed once), every shard is searched, and the per-shard lists are folded together in ascending shard
 order by cmh_topk_merge (csrc/retrieval_merge.hip), which keeps the order (distance, database index): the result is bit for bit
 what one search over the whole database would give.  Histograms are the int32 sums of the per-shard histograms; queries are cut
-into blocks of QUERIES_MAX rows and the outputs concatenated.  A database and a query set within the limits take exactly the one
-native call they always took.  CodeIndex grows by add() and persists by save() / load().
+into blocks of QUERIES_MAX rows and the outputs concatenated.  A database and a query set within the limits take exactly one
+native call.  CodeIndex grows by add() and persists by save() / load().
 
 mAP.  mean_average_precision is calc_map_k_matrix's number with ties by ascending database index, computed by counting
 (cmh_hamming_ap_partial): a relevant item's rank is a sum of histogram entries and of a cursor, so nothing is sorted and the
@@ -73,6 +76,8 @@ import cmh_native as N
 DEFAULT_TOPN = (1,) + tuple(range(50, 1001, 50))
 SHARD_ITEMS = N.TOPK_MAX             # database items per shard unless a call says otherwise (tests pass small values)
 ITEMS_MAX = 2 ** 31 - 1              # indices and counts are int32
+QUERIES_FEW = 64                     # up to this many queries a plain search is ONE cmh_hamming_topk_few over the whole database (_few_route);
+                                     # set from the measurement of DESIGN.md 9.6, 0 = nothing routes there
 
 
 def _dev(*ts):
@@ -121,6 +126,15 @@ def _plan(what, qp, rp, shard_items):
     return Q, n, _cuts(Q, N.QUERIES_MAX), _cuts(n, step)
 
 
+def _few_route(Q, k, bits, shard_items, graded, want_counts):
+    """Does a search go to the few-query kernel (lanes own items, the whole database in one call) in place of the tiles kernels
+    (lanes own queries, shards)?  Decided from what the call shows, never by an option: few queries, a result page of neighbours, a
+    code the kernel takes, nothing it does not compute (grades, histograms), and no shard size: a caller who states one is asking
+    for shards."""
+    return (Q <= min(QUERIES_FEW, N.FEW_Q_MAX) and k <= N.FEW_K_MAX and bits <= N.FEW_BITS_MAX and not graded and not want_counts
+            and shard_items is None)
+
+
 def _search(what, qp, rp, bits, k, ql, rl, shard_items=None, grade_classes=None, want_counts=False):
     """The k nearest database items of every query over any number of shards and query blocks -> (idx, dist, tag, counts): tag =
     hit flags (None without labels), or grades with grade_classes; counts = hamming_hist's, None unless want_counts.
@@ -131,6 +145,13 @@ def _search(what, qp, rp, bits, k, ql, rl, shard_items=None, grade_classes=None,
     k = int(k)
     if not 1 <= k <= n:
         raise N.NativeError(f"{what}: k={k} outside [1, N={n}]")
+    if _few_route(Q, k, bits, shard_items, grade_classes is not None, want_counts):
+        # the hit flags from the label words of the k results: Q x k x LW integers of glue, equal to the tiles route's flags.  The
+        # native call takes no labels, so they are checked here as the tiles route's binding checks them, before anything is gathered
+        N.check_retrieval_operands(what, qp, rp, bits, ql, rl)
+        idx, dist = N.hamming_topk_few(qp, rp, bits, k)
+        rel = None if ql is None else ((rl[idx.long()] & ql[:, None, :]) != 0).any(-1).to(torch.uint8)
+        return idx, dist, rel, None
 
     def one(qcut, scut, kk):
         q, r = _rows(qp, qcut, Q), _rows(rp, scut, n)

@@ -547,6 +547,25 @@ int cmh_topk_merge(const int32_t* a_idx, const float* a_dist, const uint8_t* a_t
                    const int32_t* b_idx, const float* b_dist, const uint8_t* b_tag, int32_t kb, int32_t b_base,
                    int32_t Q, int32_t k, int32_t* idx, float* dist, uint8_t* tag, void* stream);
 
+/* Few queries against a database of any size (csrc/retrieval_few.hip): the interactive case, one caption or one image against an
+ * index.  The entry points above let lanes own queries (64 per wave: with one query 63 lanes repeat it); here lanes own items, the
+ * query words are wave-uniform, and one call takes any database up to 2^31 - 1 items: no shards, no merge.
+ *   idx i32 [Q, k], dist f32 [Q, k] = 0.5 * h exactly: row q holds the first k columns of torch.sort(calc_hammingDist(q, r),
+ *   stable=True), ordered by (distance, ascending database index): for N <= 524287 bit for bit what cmh_hamming_topk writes, beyond
+ *   that what the fold of its per-shard lists through cmh_topk_merge gives.
+ * 1 <= Q <= CMH_FEW_Q_MAX (one tile of the entry points above: beyond it their lanes are full), 1 <= N <= 2^31 - 1,
+ * 1 <= bits <= CMH_FEW_BITS_MAX, 1 <= k <= min(N, CMH_FEW_K_MAX) (a result page, not a ranking).  No labels: the caller gathers
+ * the k results' label words.  Database planes of 2 (4) words per row are read as 8 (16) bytes: aligned so (rows of a 256-byte
+ * aligned buffer are).  Refused with -1 before any launch: null operands, sizes outside the limits, misaligned planes; -2: a
+ * workspace below cmh_topk_few_workspace_bytes (0 outside the limits).  No atomics on idx / dist, every element is written once: two
+ * calls give equal bits, on any stream. */
+#define CMH_FEW_Q_MAX 64
+#define CMH_FEW_K_MAX 4096
+#define CMH_FEW_BITS_MAX 128
+size_t cmh_topk_few_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_hamming_topk_few(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q, int64_t N,
+                         int32_t bits, int32_t k, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */

@@ -50,7 +50,20 @@ route there was, hamming_topk(k = N) and a search of the [Q, N] index matrix for
 (identity pairing) and 5000 x 190 834 x 128 bit (one random target per query).  Same rules (warm-up, legs alternating in one
 process, device events around regions of --reps calls; the baseline runs once per region); both routes' positions are compared on
 the timed inputs.  A baseline that cannot be allocated is recorded as such.  Then 5000 x 2 000 000 x 64 bit in four shards, which no
-other route takes: 16 of its rows are compared with counts made from the full distance rows.  One JSON line per shape."""
+other route takes: 16 of its rows are compared with counts made from the full distance rows.  One JSON line per shape.
+
+--few runs the few-query legs instead: ONE cmh_hamming_topk_few over the whole database (csrc/retrieval_few.hip: lanes own items)
+against the route such a search took before it existed, the tiles kernels (lanes own queries) as utils.retrieval._search runs them
+at the default shard size: one cmh_hamming_topk at 190 834 x 128 bit, four shards and three merges at 2 000 000 x 64 bit.
+Q = 1, 2, 4, 8, 16, 32, 64 and k = 10, 1000 on both databases; a query is a database item with a tenth of its bits flipped.  Same
+rules (warm-up, legs alternating in one process, device events around regions of --reps calls, median [min - max], packed resident
+operands); both routes' lists are compared on the timed inputs.  `queries_few` is the largest Q of that list at which the new
+call's maximum lies below the tiles route's minimum on both databases at k = 1000 (utils.retrieval.QUERIES_FEW is set from it);
+`bar_q1` says whether the ranges are apart at Q = 1 on both databases at both k.  Floor per shape: two passes over N x 2 W x 4 bytes
+at the HBM rate (8 TB/s) plus Q x N / 64 wave-wide item groups x (5 W + 8) vector instructions of 4 cycles on 1024 SIMDs at 2.4 GHz
+per pass.  Then, without a bar, the wall time of one interactive query against the 2 000 000-item index: caption -> tokens -> codes
+(query.py::QueryEncoder on a ViT-B/32-sized DSPH model with random weights) -> 10 neighbours, warm, median of 20, split into
+tokenise / encode / search (host clock around a device synchronise).  ONE JSON line."""
 import argparse
 import json
 import os
@@ -406,6 +419,97 @@ def rank_legs(args):
         raise SystemExit("synthetic_2000000_64: the sharded ranks by counting disagree with counts made from the distance rows")
 
 
+FEW = {"nuswide_190834_128": (190834, 128), "synthetic_2000000_64": (2000000, 64)}
+FEW_QS = (1, 2, 4, 8, 16, 32, 64)
+FEW_KS = (10, 1000)
+
+
+def few_floor_ms(Q, n, bits):
+    W = (bits + 31) // 32
+    by = 2 * n * 2 * W * 4 / 8e12
+    valu = 2 * (Q * n / 64) * (5 * W + 8) * 4 / (1024 * 2.4e9)
+    return {"bytes": round(by * 1e3, 5), "valu": round(valu * 1e3, 5), "sum": round((by + valu) * 1e3, 5)}
+
+
+def few_legs(args):
+    import tempfile
+    import time
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+    line = {"tool": "retrieval_bench", "leg": "few", "regions": REGIONS, "reps": args.reps, "outputs_equal": True, "shapes": {}}
+    apart = {}                                                     # (shape, Q, k) -> the new call's max < the tiles route's min
+    for name, (n, K) in FEW.items():
+        g = torch.Generator(device=dev).manual_seed(1)
+        rB = torch.sign(torch.randn(n, K, generator=g, device=dev) + 1e-3)
+        t = torch.randint(0, n, (max(FEW_QS),), generator=g, device=dev)
+        flip = torch.rand(max(FEW_QS), K, generator=g, device=dev) < 0.1
+        qp_all, rp = N.pack_codes(torch.where(flip, -rB[t], rB[t])), N.pack_codes(rB)
+        del rB, flip
+        shape = {"N": n, "bits": K, "shards_of_the_tiles_route": len(R._cuts(n, R.SHARD_ITEMS)), "ms": {}}
+        for Q in FEW_QS:
+            qp = tuple(x[:Q].contiguous() for x in qp_all)
+            legs = {}
+            for k in FEW_KS:
+                legs[f"few_k{k}"] = (args.reps, lambda k=k: N.hamming_topk_few(qp, rp, K, k))
+                legs[f"tiles_k{k}"] = (args.reps, lambda k=k: R._search("bench", qp, rp, K, k, None, None, shard_items=R.SHARD_ITEMS)[:2])
+            outs = {leg: fn() for leg, (_, fn) in legs.items()}    # warm-up, and the outputs of both routes on the timed inputs
+            same = all(bool(torch.equal(a, b)) for k in FEW_KS for a, b in zip(outs[f"few_k{k}"], outs[f"tiles_k{k}"]))
+            line["outputs_equal"] = line["outputs_equal"] and same
+            del outs
+            torch.cuda.synchronize()
+            ms = _timed(legs, REGIONS)
+            for k in FEW_KS:
+                apart[(name, Q, k)] = ms[f"few_k{k}"]["max"] < ms[f"tiles_k{k}"]["min"]
+                ms[f"few_k{k}"]["tiles_over_few"] = round(ms[f"tiles_k{k}"]["median"] / ms[f"few_k{k}"]["median"], 2)
+                ms[f"few_k{k}"]["apart"] = apart[(name, Q, k)]
+            ms["floor_ms"] = few_floor_ms(Q, n, K)
+            ms["outputs_equal"] = same
+            shape["ms"][f"Q{Q}"] = ms
+        line["shapes"][name] = shape
+        if name != "synthetic_2000000_64":
+            del qp_all, rp
+    holds = [Q for Q in FEW_QS if all(apart[(name, Q, 1000)] for name in FEW)]
+    line["queries_few"] = max(holds) if holds else 0
+    line["queries_few_holds_at"] = holds
+    line["bar_q1"] = all(apart[(name, 1, k)] for name in FEW for k in FEW_KS)
+    line["queries_few_committed"] = R.QUERIES_FEW
+
+    # one interactive query against the 2 000 000-item index (rp, of the last shape): caption -> tokens -> codes -> 10 neighbours
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import recipe
+    from model.DSPH import MDSPH
+    from query import QueryEncoder
+    n, K = FEW["synthetic_2000000_64"]
+    sd = {k: torch.from_numpy(v) for k, v in recipe.clip_state_dict(recipe.CLIP_VITB32, 7).items()}
+    state = MDSPH(outputDim=K, clipPath=sd, saveDir=tempfile.mkdtemp(prefix="cmh_few_")).state_dict()
+    enc = QueryEncoder("DSPH", state, sd, K, bpe_path=os.path.join(ROOT, "tests", "golden", "clip_bpe_merges_48894.txt.gz"))
+    caption = ["a dog on a beach"]
+    parts = {"tokenise": [], "encode": [], "search": [], "total": []}
+    for i in range(5 + 20):                                        # five warm-up rounds, then the 20 that count
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tokens = enc.tokenize(caption)
+        t1 = time.perf_counter()
+        codes = enc.encode_tokens(tokens)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        idx, dist, _, _ = R._search("bench", R._codes(codes, dev), rp, K, 10, None, None)      # (CodeIndex.search on resident planes)
+        first = idx[0].tolist()                                    # (the answer on the host: what retrieve.py prints)
+        t3 = time.perf_counter()
+        if i >= 5:
+            for key, v in (("tokenise", t1 - t0), ("encode", t2 - t1), ("search", t3 - t2), ("total", t3 - t0)):
+                parts[key].append(v * 1e3)
+    line["one_query_ms"] = {key: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+                            for key, v in parts.items()}
+    line["one_query_ms"]["model"] = "DSPH on ViT-B/32 (random weights), f32 GEMMs, 64 bit; index 2 000 000 x 64 bit; k = 10"
+    line["one_query_ms"]["neighbours"] = len(first)
+    _emit(args, line)
+    if not line["outputs_equal"]:
+        raise SystemExit("the few-query search disagrees with the tiles route")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
@@ -416,6 +520,7 @@ def main():
     ap.add_argument("--no-large", action="store_true", help="--map, --rank: leave out the 2 000 000-item database")
     ap.add_argument("--range", action="store_true", help="run the radius-search legs (see above) instead of the others")
     ap.add_argument("--rank", action="store_true", help="run the target-rank legs (see above) instead of the others")
+    ap.add_argument("--few", action="store_true", help="run the few-query legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -429,6 +534,8 @@ def main():
         return range_legs(args)
     if args.rank:
         return rank_legs(args)
+    if args.few:
+        return few_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
