@@ -288,8 +288,8 @@ def test_tower_backward_in_parts_equals_one_call(mode):
 @pytest.mark.parametrize("B,K,C,alpha", [(8, 16, 5, 0.8), (64, 64, 24, 0.8), (256, 64, 80, 0.8), (32, 128, 10, 0.0)])
 def test_hyp_loss_backward(B, K, C, alpha):
     """d HyP / d(x, y, proxies) against torch autograd (fp64) of the reference formula (train/DSPH/loss.py:22-72)."""
-    import torch.nn.functional as F
     from backward_ops import HypLoss
+    from lossutil import hyp_loss
     g = torch.Generator().manual_seed(B + K + C)
     x = torch.tanh(torch.randn(B, K, generator=g))
     y = torch.tanh(torch.randn(B, K, generator=g))
@@ -299,22 +299,7 @@ def test_hyp_loss_backward(B, K, C, alpha):
     prox = torch.randn(C, K, generator=g)
     thr = 0.05
 
-    def ref(x, y, p):
-        cos = F.normalize(x, dim=1) @ F.normalize(p, dim=1).T
-        cos_t = F.normalize(y, dim=1) @ F.normalize(p, dim=1).T
-        lab = label.double()
-        P, Nn = (lab != 0).sum(), (lab == 0).sum()
-        tot = ((1 - cos)[lab == 1].sum() + (1 - cos_t)[lab == 1].sum()) / P + (F.relu(cos - thr)[lab == 0].sum() + F.relu(cos_t - thr)[lab == 0].sum()) / Nn
-        if alpha > 0:
-            idx = lab.sum(1) > 1
-            l_ = lab[idx]
-            cs = l_ @ l_.T
-            if (cs == 0).sum() > 0:
-                xn, tn = F.normalize(x[idx], dim=1), F.normalize(y[idx], dim=1)
-                Z = (cs == 0).sum()
-                for s in (xn @ xn.T, tn @ tn.T, xn @ tn.T):
-                    tot = tot + (alpha * F.relu(s - thr))[cs == 0].sum() / Z
-        return tot
+    ref = lambda x, y, p: hyp_loss(x, y, p, label, thr, alpha)
     xr, yr, pr = (t.double().requires_grad_(True) for t in (x, y, prox))
     (ref(xr, yr, pr) * 1.7).backward()
     xd, yd, pd = (t.to(DEV).requires_grad_(True) for t in (x, y, prox))
