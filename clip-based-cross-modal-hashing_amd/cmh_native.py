@@ -159,6 +159,9 @@ SIGNATURES = {
     "cmh_label_overlap_hist": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _sz, _p]),
     "cmh_topk_few_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_hamming_topk_few": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "cmh_soft_query_planes": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "cmh_soft_topk_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_soft_topk": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -808,6 +811,68 @@ def hamming_topk_few(q_planes, r_planes, bits, k):
     check(lib().cmh_hamming_topk_few(ptr(qs), ptr(qn), ptr(rs), ptr(rn), Q, N, int(bits), k, ptr(idx), ptr(dist),
                                      ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_topk_few")
     return idx, dist
+
+
+SOFT_LEVELS = 15             # include/cmh.h CMH_SOFT_LEVELS: a soft query's weights are integers in [-15, 15]
+SOFT_Q_MAX = 64              # ... CMH_SOFT_Q_MAX, CMH_SOFT_K_MAX, CMH_SOFT_BITS_MAX: the limits of cmh_soft_topk
+SOFT_K_MAX = 4096
+SOFT_BITS_MAX = 128
+SOFT_ROWS_MAX = 65535        # rows of one cmh_soft_query_planes
+
+
+def soft_query_planes(u):
+    """The head's real-valued output u f32 [Q, bits] (any Q, bits <= SOFT_BITS_MAX) -> (q_sign int32 [Q, W], q_mag int32 [Q, 4, W],
+    wsum int32 [Q], scale f32 [Q]): per row s = max |u_i| and the weights w_i = rint((u_i / s) * 15) in [-15, 15] (all 0 when s == 0)
+    as a sign plane (bit set: w_i > 0) and the four bit planes of |w_i|; wsum = sum |w_i|, scale = s.  A non-finite entry raises
+    (one host sync reads the flag back)."""
+    u = f32c(u)
+    require_gpu(u)
+    if u.dim() != 2 or u.shape[0] < 1:
+        raise NativeError(f"soft_query_planes: u of shape {tuple(u.shape)}, expected [Q >= 1, bits]")
+    Q, bits = u.shape
+    if not 1 <= bits <= SOFT_BITS_MAX:
+        raise NativeError(f"soft_query_planes: bits={bits} outside [1, {SOFT_BITS_MAX}]")
+    dev, W = u.device, (bits + 31) // 32
+    q_sign = torch.empty(Q, W, dtype=torch.int32, device=dev)
+    q_mag = torch.empty(Q, 4, W, dtype=torch.int32, device=dev)
+    wsum = torch.empty(Q, dtype=torch.int32, device=dev)
+    scale = torch.empty(Q, dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    for a in range(0, Q, SOFT_ROWS_MAX):
+        b = min(Q, a + SOFT_ROWS_MAX)
+        check(lib().cmh_soft_query_planes(ptr(u[a:b]), b - a, bits, ptr(q_sign[a:b]), ptr(q_mag[a:b]), ptr(wsum[a:b]), ptr(scale[a:b]),
+                                          ptr(bad), stream_ptr(dev)), "cmh_soft_query_planes")
+    if int(bad.item()):
+        raise NativeError("soft_query_planes: a soft query must be finite (NaN or Inf in the head's output)")
+    return q_sign, q_mag, wsum, scale
+
+
+def soft_topk(q, r_planes, bits, k):
+    """The first k database items of every soft query in ascending (wdist, database index), one native call over a database of
+    any size up to 2^31 - 1 items (csrc/retrieval_soft.hip): q = (q_sign, q_mag[, wsum, scale]) of soft_query_planes, r_planes =
+    pack_codes' -> (idx int32 [Q, k], wdist int32 [Q, k]), wdist = sum |w_i| - sum w_i r_i.  1 <= Q <= SOFT_Q_MAX, bits <=
+    SOFT_BITS_MAX, 1 <= k <= min(N, SOFT_K_MAX)."""
+    (qs, qm), (rs, rn) = q[:2], r_planes
+    require_gpu(qs, qm, rs, rn)
+    Q, N = qs.shape[0], rs.shape[0]
+    W = (int(bits) + 31) // 32
+    fit("soft_topk", (qs, (Q, W)), (qm, (Q, 4, W)), (rs, (N, W)), (rn, (N, W)))
+    for t in (qs, qm, rs, rn):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("soft_topk: packed operands are contiguous int32 tensors (soft_query_planes / pack_codes)")
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= SOFT_K_MAX:                                    # (before anything of Q x k entries is allocated)
+        raise NativeError(f"soft_topk: k={k} outside [1, {SOFT_K_MAX}]")
+    if k > N:
+        raise NativeError(f"soft_topk: k={k} exceeds N={N}")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    wdist = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    need = lib().cmh_soft_topk_workspace_bytes(Q, N, int(bits))     # 0 outside the limits: the call below refuses with the reason
+    ws = workspace(need, dev, "retrieval_soft")
+    check(lib().cmh_soft_topk(ptr(qs), ptr(qm), ptr(rs), ptr(rn), Q, N, int(bits), k, ptr(idx), ptr(wdist), ptr(ws), ws.numel(),
+                              stream_ptr(dev)), "cmh_soft_topk")
+    return idx, wdist
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte

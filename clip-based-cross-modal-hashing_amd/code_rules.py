@@ -26,6 +26,35 @@ CODE_RULES = {"DSPH": sign_code, "DNpH": sign_code, "DMsH_LN": sign_code, "DHaPH
               "DNPH": first_sign_code}
 
 
+def soft_output(out) -> torch.Tensor:
+    """The tanh head's output itself: sign_code writes its sign."""
+    return out.float()
+
+
+def pair_margin(out) -> torch.Tensor:
+    """p[..., 1] - p[..., 0] of each probability pair: positive exactly where pair_argmax_code picks index 1 (+1), negative where
+    it picks index 0 (-1); 0 on a tie, which the argmax gives to index 0."""
+    p = torch.cat(out, dim=-1) if isinstance(out, (list, tuple)) else out
+    p = p.float().reshape(p.shape[0], -1, 2)
+    return p[..., 1] - p[..., 0]
+
+
+def first_soft_output(out) -> torch.Tensor:
+    """The first output itself; the second is the class logits (DNPH)."""
+    return out[0].float()
+
+
+# The real-valued output behind each rule of CODE_RULES, for soft queries (utils/retrieval.py::soft_topk): wherever it is
+# non-zero, its sign is the code the method's rule writes.
+SOFT_RULES = {"DSPH": soft_output, "DNpH": soft_output, "DMsH_LN": soft_output, "DHaPH": soft_output, "DCHMT": pair_margin,
+              "DNPH": first_soft_output}
+
+
 def code_rule(method):
     """The rule TrainBase._codes_for_eval applies for `method` (sign_code for every method without a rule of its own)."""
     return CODE_RULES.get(method, sign_code)
+
+
+def soft_rule(method):
+    """The soft output that goes with code_rule(method)."""
+    return SOFT_RULES.get(method, soft_output)

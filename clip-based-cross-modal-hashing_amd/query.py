@@ -4,12 +4,15 @@
     enc = QueryEncoder("DSPH", "result/DSPH/flickr25k/64/model-99.pth", "ViT-B-32.pt", 64)
     codes = enc.encode_text(["a dog on a beach"])                 # f32 [1, 64] in {-1, 0, +1}
     idx, dist = CodeIndex.load("db.npz").search(codes, 10)
+    soft = enc.encode_text(["a dog on a beach"], soft=True)      # f32 [1, 64]: the head's output before the code rule
+    idx, dist, wdist = CodeIndex.load("db.npz").search_soft(soft, 10)
 
 The model is built as its trainer's _init_model builds it (construct, load_state_dict, float(), set_gemm_dtype, eval()), with
 clip.assume_frozen = True: the weights never change here, so the towers skip their per-call parameter scan.  Text goes through the
 native BPE tokenizer (dataset.base.shared_tokenizer), images through the GPU transform of the evaluation sets
 (dataset.gpu_transform.preprocess, train=False), the output through the method's code rule (code_rules.py): what the trainer's
-get_code* writes for the same caption or picture."""
+get_code* writes for the same caption or picture; with soft=True through the method's soft rule instead: the real-valued output
+whose sign that code is."""
 import importlib
 
 MODELS = {"DSPH": ("model.DSPH", "MDSPH"), "DCHMT": ("model.DCHMT", "MDCMHT"), "DNPH": ("model.DNPH_TOMM", "MDNPH"),
@@ -35,11 +38,11 @@ class QueryEncoder:
 
         import torch
 
-        from code_rules import code_rule
+        from code_rules import code_rule, soft_rule
         self.method, self.bits = method, int(output_dim)
         self.max_words, self.resolution, self.bpe_path = int(max_words), int(resolution), bpe_path
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.rule = code_rule(method)
+        self.rule, self.soft_rule = code_rule(method), soft_rule(method)
         state = pretrained if isinstance(pretrained, dict) else torch.load(pretrained, map_location="cpu")
         module, name = MODELS[method]
         kw = dict(outputDim=self.bits, clipPath=clip_path, saveDir=tempfile.mkdtemp(prefix="cmh_query_"), is_train=False)   # (the model's log)
@@ -59,17 +62,17 @@ class QueryEncoder:
             captions = [captions]
         return shared_tokenizer(self.bpe_path).encode_captions(list(captions), self.max_words)
 
-    def encode_tokens(self, tokens):
+    def encode_tokens(self, tokens, soft=False):
         import torch
         with torch.no_grad():
-            return self.rule(self.model.encode_text(tokens.to(self.device)))
+            return (self.soft_rule if soft else self.rule)(self.model.encode_text(tokens.to(self.device)))
 
-    def encode_text(self, captions):
-        """list of str -> f32 [n, K] codes in {-1, 0, +1} on the GPU."""
-        return self.encode_tokens(self.tokenize(captions))
+    def encode_text(self, captions, soft=False):
+        """list of str -> f32 [n, K] codes in {-1, 0, +1} on the GPU; soft=True: the real-valued output behind them."""
+        return self.encode_tokens(self.tokenize(captions), soft)
 
-    def encode_image(self, images):
-        """paths or uint8 [H, W, 3] arrays -> f32 [n, K] codes in {-1, 0, +1} on the GPU."""
+    def encode_image(self, images, soft=False):
+        """paths or uint8 [H, W, 3] arrays -> f32 [n, K] codes in {-1, 0, +1} on the GPU; soft=True: the real-valued output."""
         import numpy as np
         import torch
 
@@ -84,4 +87,4 @@ class QueryEncoder:
             arrays.append(im)
         with torch.no_grad():
             batch = RaggedImages.from_arrays(arrays).to(self.device)
-            return self.rule(self.model.encode_image(preprocess(batch, self.resolution, train=False)))
+            return (self.soft_rule if soft else self.rule)(self.model.encode_image(preprocess(batch, self.resolution, train=False)))

@@ -41,7 +41,13 @@ asks the index a question: every --text CAPTION and --image PATH (both repeatabl
 encoded by the trained model (query.py::QueryEncoder: the tokenizer or the image transform, the towers, the method's heads and its
 code rule) and searched in the saved CodeIndex.  No --codes file is needed.  Per query one block: a line `query <number> <text|image>:
 <what was asked>`, then k lines `<rank> <database index> <distance>`, nearest first, ties by database index.  --max-words,
---resolution, --gemm-dtype and --bpe-path are the trainer's options of those names.  MITH and TwDH are not supported here."""
+--resolution, --gemm-dtype and --bpe-path are the trainer's options of those names.  MITH and TwDH are not supported here.
+
+    python retrieve.py --text "a dog on a beach" --soft --index db.npz --method DSPH --pretrained model.pth -clip-path ViT-B-32.pt --output-dim 64
+
+ranks by the model's real-valued output instead of its sign (CodeIndex.search_soft: the asymmetric distance, which orders the items
+a Hamming ranking leaves tied); the same blocks, the distance column in the soft distance's units.  --soft goes with --text /
+--image only."""
 import argparse
 import sys
 
@@ -61,6 +67,7 @@ def parse(argv=None):
     p.add_argument("--codes", default=None, help=".mat file written by a trainer (save_mat); required unless --text / --image ask the questions")
     p.add_argument("--text", action=_Ask, metavar="CAPTION", help="search the --index for this caption (repeatable; needs --method, --pretrained, -clip-path, --output-dim)")
     p.add_argument("--image", action=_Ask, metavar="PATH", help="search the --index for this picture (repeatable, mixes with --text)")
+    p.add_argument("--soft", action="store_true", help="with --text / --image: rank by the model's real-valued output (soft queries) instead of its sign")
     p.add_argument("--method", default=None, help="with --text / --image: the method the checkpoint was trained with")
     p.add_argument("--pretrained", default=None, metavar="FILE", help="with --text / --image: the trained model (model-<epoch>.pth)")
     p.add_argument("-clip-path", "--clip-path", dest="clip_path", default=None, metavar="FILE", help="with --text / --image: the CLIP checkpoint the model was built on")
@@ -96,6 +103,8 @@ def parse(argv=None):
             p.error(f"--text / --image need the model: {', '.join(missing)} missing")
         if args.k is not None and args.k < 1:
             p.error("--k: at least 1")
+    elif args.soft:
+        p.error("--soft goes with --text / --image: a soft query is the model's output, a --codes file holds only signs")
     elif args.codes is None:
         p.error("the following arguments are required: --codes")
     if args.recall:
@@ -188,13 +197,15 @@ def ask(args):
     k = min(10 if args.k is None else args.k, index.size)
     texts = [v for kind, v in args.ask if kind == "text"]
     images = [v for kind, v in args.ask if kind == "image"]
-    codes = {"text": enc.encode_text(texts) if texts else None, "image": enc.encode_image(images) if images else None}
+    codes = {"text": enc.encode_text(texts, soft=args.soft) if texts else None,
+             "image": enc.encode_image(images, soft=args.soft) if images else None}
     at = {"text": 0, "image": 0}
     rows = []
     for kind, _ in args.ask:                                       # back into the order of the command line
         rows.append(codes[kind][at[kind]])
         at[kind] += 1
-    idx, dist = (t.cpu().numpy() for t in index.search(torch.stack(rows), k))
+    found = index.search_soft(torch.stack(rows), k)[:2] if args.soft else index.search(torch.stack(rows), k)
+    idx, dist = (t.cpu().numpy() for t in found)
     for i, (kind, value) in enumerate(args.ask):
         print(f"query {i} {kind}: {value}")
         for j in range(k):

@@ -28,6 +28,13 @@ on the labels only: one call serves all directions of an evaluation) and is what
 Few queries (Q <= QUERIES_FEW, k <= 4096, codes up to 128 bit, no shard size stated) take ONE cmh_hamming_topk_few over the whole
 database, whatever its size (csrc/retrieval_few.hip: lanes own items; _few_route): the same bytes as the route below.
 
+Soft queries.  soft_topk / CodeIndex.search_soft rank the database by the head's REAL-VALUED output u (query.py: encode_*(...,
+soft=True); code_rules.SOFT_RULES) in place of its sign: calc_hammingDist on u, the asymmetric distance, which orders the items a
+Hamming ranking leaves tied.  u is quantised per row to integer weights w_i = rint((u_i / max|u|) * 15) and the database stays the
+packed planes: wdist = sum |w_i| - sum w_i r_i (an exact integer), dist = wdist * (max|u| / 30) = 0.5 (sum |u~_i| - u~ . r) for
+the quantised query u~, ties by ascending database index.  One cmh_soft_topk (csrc/retrieval_soft.hip) per block of 64 queries
+over the whole database, whatever its size; codes up to 128 bit and k <= 4096, and no other route computes this distance.
+
 Size.  The other native entry points take N <= 524 287 database items and Q <= 65 535 queries per call.  Every function here takes any
 database up to 2^31 - 1 items and any number of queries: the packed planes are row-major, so the database is cut into SHARDS of
 `shard_items` rows (views, packed once), every shard is searched, and the per-shard lists are folded together in ascending shard
@@ -325,6 +332,36 @@ def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None):
     return (idx, dist) if rel is None else (idx, dist, rel)
 
 
+def _soft_search(what, u, rp, bits, k):
+    """-> (idx int32 [Q, k], dist f32 [Q, k], wdist int32 [Q, k]) of soft queries u f32 [Q, bits] against packed planes: blocks of
+    SOFT_Q_MAX queries, one cmh_soft_topk each over the whole database."""
+    if u.dim() < 2:
+        u = u.unsqueeze(0)
+    n, k = rp[0].shape[0], int(k)
+    if u.shape[1] != bits:
+        raise N.NativeError(f"{what}: {u.shape[1]}-entry soft queries for codes of {bits} bits")
+    if bits > N.SOFT_BITS_MAX:
+        raise N.NativeError(f"{what}: bits={bits} exceeds {N.SOFT_BITS_MAX}, the limit of the soft search (no other route computes its distance)")
+    if k > N.SOFT_K_MAX:
+        raise N.NativeError(f"{what}: k={k} exceeds {N.SOFT_K_MAX}, the limit of the soft search (no other route computes its distance)")
+    if not 1 <= k <= n:
+        raise N.NativeError(f"{what}: k={k} outside [1, N={n}]")
+    if u.shape[0] < 1 or n > ITEMS_MAX:
+        raise N.NativeError(f"{what}: Q={u.shape[0]} N={n}")
+    qs, qm, _, scale = N.soft_query_planes(u.to(rp[0].device).float())
+    parts = [N.soft_topk((qs[a:b], qm[a:b]), rp, bits, k) for a, b in _cuts(u.shape[0], N.SOFT_Q_MAX)]
+    idx, wdist = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+    unit = scale / torch.full_like(scale, 30.0)      # (tensor / tensor: one IEEE division; by a Python number the GPU multiplies by 1 / 30)
+    return idx, wdist.float() * unit[:, None], wdist
+
+
+def soft_topk(u, rB, k):
+    """-> (idx int32 [Q, k], dist f32 [Q, k], wdist int32 [Q, k]): the k nearest database codes rB (f32 in {-1, 0, +1}) of every
+    soft query u (f32 [Q, K], the head's output before its code rule), by (wdist, database index); dist = wdist * (max|u| / 30)."""
+    dev = _dev(u, rB)
+    return _soft_search("soft_topk", u, _codes(rB, dev), rB.shape[-1], k)
+
+
 def _classes(what, query_L, retrieval_L):
     if query_L is None or retrieval_L is None:
         raise N.NativeError(f"{what}: needs the labels of both sides")
@@ -591,6 +628,7 @@ def recall_at_k(qB, rB, targets=None, ks=RECALL_KS, ties="index", shard_items=No
 
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
+    search_soft(u, k) -> soft_topk's;
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
@@ -721,6 +759,13 @@ class CodeIndex:
         idx, dist, rel, _ = _search("CodeIndex.search", _codes(query_codes, self.device), self.planes, self.bits, k, ql, rl,
                                     self.shard_items)
         return (idx, dist) if rel is None else (idx, dist, rel)
+
+    def search_soft(self, u, k):
+        """soft_topk of the soft queries u (f32 [Q, bits], QueryEncoder.encode_*(..., soft=True)) against the index: (idx, dist,
+        wdist).  Any number of queries; bits <= 128 and k <= 4096."""
+        if u.shape[-1] != self.bits:
+            raise N.NativeError(f"CodeIndex.search_soft: {u.shape[-1]}-entry soft queries for an index of {self.bits} bits")
+        return _soft_search("CodeIndex.search_soft", u, self.planes, self.bits, k)
 
     def range_search(self, query_codes, radius, query_labels=None, max_hits=None):
         """hamming_range of the queries against the index: (offsets, idx, dist[, rel with query labels])."""

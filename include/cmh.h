@@ -566,6 +566,38 @@ size_t cmh_topk_few_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
 int cmh_hamming_topk_few(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q, int64_t N,
                          int32_t bits, int32_t k, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Soft-query search (csrc/retrieval_soft.hip): few queries given as the head's REAL-VALUED output u (before sign() / the pair
+ * argmax) against the packed database.  calc_hammingDist = 0.5 (K - q . r) evaluated on u instead of its sign: an unsure bit costs
+ * little when it disagrees, a confident one a lot, which orders the items a Hamming ranking leaves tied.  Nothing is stored per
+ * item: the database is cmh_pack_codes' planes.
+ * cmh_soft_query_planes quantises: per row s = max_i |u_i|; s == 0: every weight 0; else w_i = rint((u_i / s) * 15), three f32
+ * operations, each rounded once (IEEE division, IEEE multiplication, round half to even), so w_i in [-CMH_SOFT_LEVELS,
+ * CMH_SOFT_LEVELS].
+ *   u f32 [Q, bits] -> q_sign u32 [Q, W] (bit i set: w_i > 0), q_mag u32 [Q, 4, W] (plane b = bit b of |w_i|; zero at and behind
+ *   `bits`), wsum i32 [Q] = sum |w_i|, scale f32 [Q] = s; W = ceil(bits / 32).  *bad (i32, the caller zeroes it) is set when an entry
+ *   is not finite; that row's weights, wsum and scale are then 0.  1 <= Q <= 65535, 1 <= bits <= CMH_SOFT_BITS_MAX.
+ * cmh_soft_topk ranks: for an item r in {-1, 0, +1}^bits
+ *   wdist(u, r) = sum |w_i| - sum w_i r_i = sum_{r_i = 0} |w_i| + 2 sum_{r_i != 0, sign differs} |w_i|,
+ *   an integer in [0, 2 wsum]; (scale / 30) * wdist = 0.5 (sum |u~_i| - u~ . r) for the quantised query u~ = (s / 15) w: the
+ *   reference's distance on u~ minus the per-query constant 0.5 (bits - sum |u~_i|).  A query with every |w_i| = 15 gives
+ *   wdist = 15 h, h the half-units of cmh_hamming_topk_few; a zero weight takes its bit out of the distance.
+ *   idx i32 [Q, k], wdist i32 [Q, k]: row q holds the first k database items in ascending (wdist, database index).  The q_mag
+ *   words are cut to `bits` bits in the kernel: what the database planes hold behind `bits` is never counted.
+ * Limits and refusals as cmh_hamming_topk_few: 1 <= Q <= CMH_SOFT_Q_MAX, 1 <= N <= 2^31 - 1 in one call, 1 <= bits <=
+ * CMH_SOFT_BITS_MAX, 1 <= k <= min(N, CMH_SOFT_K_MAX); database rows of 2 (4) words are read as 8 (16) bytes: aligned so.  -1 before
+ * any launch: null operands, sizes outside the limits, misaligned planes; -2: a workspace below cmh_soft_topk_workspace_bytes
+ * (0 outside the limits).  The stable counting sort of cmh_hamming_topk_few over 30 bits + 1 bins: exact, no atomics on idx /
+ * wdist, every element written once: two calls give equal bits, on any stream. */
+#define CMH_SOFT_LEVELS 15
+#define CMH_SOFT_Q_MAX 64
+#define CMH_SOFT_K_MAX 4096
+#define CMH_SOFT_BITS_MAX 128
+int cmh_soft_query_planes(const float* u, int32_t Q, int32_t bits, uint32_t* q_sign, uint32_t* q_mag, int32_t* wsum, float* scale,
+                          int32_t* bad, void* stream);
+size_t cmh_soft_topk_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_soft_topk(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q, int64_t N,
+                  int32_t bits, int32_t k, int32_t* idx, int32_t* wdist, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */

@@ -63,7 +63,16 @@ call's maximum lies below the tiles route's minimum on both databases at k = 100
 at the HBM rate (8 TB/s) plus Q x N / 64 wave-wide item groups x (5 W + 8) vector instructions of 4 cycles on 1024 SIMDs at 2.4 GHz
 per pass.  Then, without a bar, the wall time of one interactive query against the 2 000 000-item index: caption -> tokens -> codes
 (query.py::QueryEncoder on a ViT-B/32-sized DSPH model with random weights) -> 10 neighbours, warm, median of 20, split into
-tokenise / encode / search (host clock around a device synchronise).  ONE JSON line."""
+tokenise / encode / search (host clock around a device synchronise).  ONE JSON line.
+
+--soft runs the soft-query legs instead: cmh_soft_topk (csrc/retrieval_soft.hip: the weighted distance of a real-valued query, 30 bits
++ 1 bins) against cmh_hamming_topk_few (2 bits + 1 bins) on the same database planes in the same process, at Q = 1, 64 and k = 10,
+1000 on both databases of --few; a soft query is tanh of a normal draw scaled towards a database item, the Hamming query its sign.
+Same rules (warm-up, legs alternating, device events around regions of --reps calls, median [min - max], packed resident operands;
+`soft_planes` times the quantiser with its flag read back).  Where soft and Hamming must agree (all |w| = 15) the lists are compared on the timed
+database.  Reported per (shape, Q, k): both times and soft / few, and both workspaces.  CMH_SOFT_GROUP=g in the environment
+pins g queries per workgroup, CMH_SOFT_MIN_CHUNK=c the fewest items of a chunk, in place of the plan's choices, for an A/B of the
+same line.  ONE JSON line."""
 import argparse
 import json
 import os
@@ -510,6 +519,50 @@ def few_legs(args):
         raise SystemExit("the few-query search disagrees with the tiles route")
 
 
+SOFT_QS = (1, 64)
+
+
+def soft_legs(args):
+    import torch
+    import cmh_native as N
+    dev = torch.device("cuda:0")
+    line = {"tool": "retrieval_bench", "leg": "soft", "regions": REGIONS, "reps": args.reps, "agree_where_they_must": True,
+            "soft_group_pinned": os.environ.get("CMH_SOFT_GROUP", ""), "soft_min_chunk_pinned": os.environ.get("CMH_SOFT_MIN_CHUNK", ""),
+            "shapes": {}}
+    for name, (n, K) in FEW.items():
+        g = torch.Generator(device=dev).manual_seed(1)
+        rB = torch.sign(torch.randn(n, K, generator=g, device=dev) + 1e-3)
+        t = torch.randint(0, n, (max(SOFT_QS),), generator=g, device=dev)
+        u_all = torch.tanh(torch.randn(max(SOFT_QS), K, generator=g, device=dev) + 0.8 * rB[t])
+        rp = N.pack_codes(rB)
+        shape = {"N": n, "bits": K, "bins_soft": 30 * K + 1, "bins_few": 2 * K + 1, "ms": {}}
+        for Q in SOFT_QS:
+            u = u_all[:Q].contiguous()
+            sq, hq = N.soft_query_planes(u), N.pack_codes(torch.sign(u))
+            hard = N.soft_query_planes(torch.sign(u))              # every |w| = 15: the Hamming order, wdist = 15 h
+            for k in FEW_KS:
+                (si, sw), (fi, fd) = N.soft_topk(hard, rp, K, k), N.hamming_topk_few(hq, rp, K, k)
+                line["agree_where_they_must"] &= bool(torch.equal(si, fi)) and bool(torch.equal(sw, (30 * fd).to(torch.int32)))
+            legs = {"soft_planes": (args.reps, lambda: N.soft_query_planes(u))}
+            for k in FEW_KS:
+                legs[f"soft_k{k}"] = (args.reps, lambda k=k: N.soft_topk(sq, rp, K, k))
+                legs[f"few_k{k}"] = (args.reps, lambda k=k: N.hamming_topk_few(hq, rp, K, k))
+            for _, fn in legs.values():                            # warm-up
+                fn()
+            torch.cuda.synchronize()
+            ms = _timed(legs, REGIONS)
+            for k in FEW_KS:
+                ms[f"soft_k{k}"]["soft_over_few"] = round(ms[f"soft_k{k}"]["median"] / ms[f"few_k{k}"]["median"], 2)
+            ms["workspace_mib"] = {"soft": round(N.lib().cmh_soft_topk_workspace_bytes(Q, n, K) / 2 ** 20, 2),
+                                   "few": round(N.lib().cmh_topk_few_workspace_bytes(Q, n, K) / 2 ** 20, 2)}
+            shape["ms"][f"Q{Q}"] = ms
+        line["shapes"][name] = shape
+        del rB, rp, u_all
+    _emit(args, line)
+    if not line["agree_where_they_must"]:
+        raise SystemExit("the soft search disagrees with the few-query search on queries whose weights are all 15")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
@@ -521,6 +574,7 @@ def main():
     ap.add_argument("--range", action="store_true", help="run the radius-search legs (see above) instead of the others")
     ap.add_argument("--rank", action="store_true", help="run the target-rank legs (see above) instead of the others")
     ap.add_argument("--few", action="store_true", help="run the few-query legs (see above) instead of the others")
+    ap.add_argument("--soft", action="store_true", help="run the soft-query legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -536,6 +590,8 @@ def main():
         return rank_legs(args)
     if args.few:
         return few_legs(args)
+    if args.soft:
+        return soft_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
