@@ -101,6 +101,7 @@ SIGNATURES = {
     "cmh_linear_gemm": (C.c_int, [_i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "cmh_layernorm": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
     "cmh_attention": (C.c_int, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "cmh_attention_pair": (C.c_int, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cmh_gemm_tuning": (C.c_int, [_i32, _i32]),
     "cmh_set_pooled_tail": (C.c_int, [_i32]),
     "cmh_set_gemm_rows": (C.c_int, [_i32]),
@@ -557,6 +558,27 @@ def attention(qkv, B, T, causal, key_padding_mask=None):
     check(lib().cmh_attention(dt, ptr(qkv), ptr(o), B, T, d, int(bool(causal)), ptr(kpm), stream_ptr(qkv.device)),
           "cmh_attention")
     return o
+
+
+def attention_pair(qkv0, B0, T0, causal0, qkv1, B1, T1, causal1, key_padding_mask0=None, key_padding_mask1=None, out=None):
+    """Both attentions in one launch -> (o0, o1), or None when the library has no pair kernel for these two problems (nothing was
+    launched; call `attention` twice).  out: optional (o0, o1) buffers to write into."""
+    require_gpu(qkv0, qkv1, key_padding_mask0, key_padding_mask1)
+    if qkv0.dtype != qkv1.dtype:
+        raise NativeError("attention_pair: the two problems differ in dtype")
+    qkv0, qkv1 = qkv0.contiguous(), qkv1.contiguous()
+    dt = BF16 if qkv0.dtype == torch.bfloat16 else F32
+    d0, d1 = qkv0.shape[1] // 3, qkv1.shape[1] // 3
+    o0, o1 = out if out is not None else (torch.empty(B0 * T0, d0, dtype=qkv0.dtype, device=qkv0.device),
+                                          torch.empty(B1 * T1, d1, dtype=qkv1.dtype, device=qkv1.device))
+    k0 = None if key_padding_mask0 is None else key_padding_mask0.to(torch.uint8).contiguous()
+    k1 = None if key_padding_mask1 is None else key_padding_mask1.to(torch.uint8).contiguous()
+    rc = lib().cmh_attention_pair(dt, ptr(qkv0), ptr(o0), B0, T0, d0, int(bool(causal0)), ptr(k0),
+                                  ptr(qkv1), ptr(o1), B1, T1, d1, int(bool(causal1)), ptr(k1), stream_ptr(qkv0.device))
+    if rc == 1:
+        return None
+    check(rc, "cmh_attention_pair")
+    return o0, o1
 
 
 # ------------------------------------------------------------------------------------------ heads

@@ -11,6 +11,7 @@
 // rescale per key tile.  Sequence lengths here are 50 / <=77, so the whole kernel is ~1 % of the
 // encoder FLOPs; exactness (plain fp32 FMA order, accurate expf) matters more.
 #include "cmh_common.h"
+#include "attention_pair.h"
 
 namespace cmh {
 
@@ -185,7 +186,7 @@ template <int NKT>
 __device__ __forceinline__ void attention_mfma_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, int Tmax, int d, int causal,
                                                     const uint8_t* __restrict__ kpm, const int32_t* __restrict__ seq_off,
                                                     float o8_inv_scale, int block, bf16_t* sV) {
-  constexpr int NKS = NKT / 2;
+  constexpr int NKS = (NKT + 1) / 2;   // PV steps of 32 keys; NKT odd: the upper 16 keys of the last step are zero on both operands
   constexpr int TP = NKT * 16;
   constexpr int VST = kAttnVST;
 
@@ -286,15 +287,21 @@ __device__ __forceinline__ void attention_mfma_body(const bf16_t* __restrict__ q
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-          asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
-                       : "=v"(raw[s][dt][hh])
-                       : "v"(a0), "i"((32 * s + 16 * hh) * VST * 2 + 32 * dt));
+        for (int hh = 0; hh < 2; ++hh) {
+          if (2 * s + hh < NKT)
+            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+                         : "=v"(raw[s][dt][hh])
+                         : "v"(a0), "i"((32 * s + 16 * hh) * VST * 2 + 32 * dt));
+          else raw[s][dt][hh] = uint2{0u, 0u};      // (no such key tile)
+        }
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(raw[s][0][0]), "+v"(raw[s][0][1]), "+v"(raw[s][1][0]), "+v"(raw[s][1][1]), "+v"(raw[s][2][0]),
-                     "+v"(raw[s][2][1]), "+v"(raw[s][3][0]), "+v"(raw[s][3][1]));
+      if (2 * s + 1 < NKT)
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(raw[s][0][0]), "+v"(raw[s][0][1]), "+v"(raw[s][1][0]), "+v"(raw[s][1][1]), "+v"(raw[s][2][0]),
+                       "+v"(raw[s][2][1]), "+v"(raw[s][3][0]), "+v"(raw[s][3][1]));
+      else      // (the upper halves are constants, not reads)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(raw[s][0][0]), "+v"(raw[s][1][0]), "+v"(raw[s][2][0]), "+v"(raw[s][3][0]));
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
         vf[s][dt] = __builtin_bit_cast(abf16x8_t, uint4{raw[s][dt][0].x, raw[s][dt][0].y, raw[s][dt][1].x, raw[s][dt][1].y});
@@ -333,17 +340,22 @@ __device__ __forceinline__ void attention_mfma_body(const bf16_t* __restrict__ q
     // raw scores (the 1/sqrt(64) scale is folded into the exponent below): the softmax costs one add + one max, then sub, mul,
     // v_exp, add per score - it is VALU issue, not the matrix pipe, that three waves per SIMD queue for in this kernel
     af32x4_t sc[NKT];
+    // the causal tests see the tile index through qd.  Five tiles: opaque to the compiler, which otherwise peels the first five
+    // query tiles off this loop (the tests fold per copy) and across the copies holds 185 registers - 17 of them spilled at three
+    // waves per SIMD; rolled, the kernel needs 153
+    int qd = qt;
+    if constexpr (NKT == 5) asm volatile("" : "+s"(qd));
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      if ((causal && kt > qt) || ((tile_none >> kt) & 1u)) {
+      if ((causal && kt > qd) || ((tile_none >> kt) & 1u)) {
         sc[kt] = af32x4_t{-1e30f, -1e30f, -1e30f, -1e30f};
       } else {
         sc[kt] = af32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 2; ++s) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][s], qf[s], sc[kt], 0, 0, 0);
         uint32_t okb = (keyok >> (kt * 4)) & 15u;
-        if (causal && kt == qt) okb &= diagok;
-        if (!((tile_all >> kt) & 1u) || (causal && kt == qt)) {
+        if (causal && kt == qd) okb &= diagok;
+        if (!((tile_all >> kt) & 1u) || (causal && kt == qd)) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) sc[kt][r] = ((okb >> r) & 1u) ? sc[kt][r] : -1e30f;
         }
@@ -381,7 +393,11 @@ __device__ __forceinline__ void attention_mfma_body(const bf16_t* __restrict__ q
     for (int s = 0; s < NKS; ++s) {
       abf16x8_t pb;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pb[j] = static_cast<__bf16>(sc[2 * s + (j >> 2)][j & 3]);
+      for (int j = 0; j < 8; ++j) {
+        constexpr int kLast = NKT - 1;
+        const int kt = 2 * s + (j >> 2);
+        pb[j] = kt < NKT ? static_cast<__bf16>(sc[kt < NKT ? kt : kLast][j & 3]) : static_cast<__bf16>(0.f);
+      }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) oc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s][dt], pb, oc[dt], 0, 0, 0);
     }
@@ -445,6 +461,65 @@ static void launch_attention_mfma(const void* qkv, void* o, int B, int T, int d,
                                   const int32_t* seq_off, hipStream_t st, float o8_inv_scale) {
   hipLaunchKernelGGL(attention_mfma_kernel<NKT>, dim3(B * (d / HD)), dim3(64), 0, st, static_cast<const bf16_t*>(qkv),
                      static_cast<bf16_t*>(o), B, T, d, causal, kpm, seq_off, o8_inv_scale);
+}
+
+// The attentions of BOTH towers in one launch (the lock-step pair path of encoders.hip): blocks [0, blocks0) run the first problem,
+// the rest the second, each through attention_mfma_body compiled for its own key-tile count: identical bits.  A kernel has one
+// register budget, so a pair is only instantiated where both bodies fit three waves per SIMD (NKT <= 5).
+struct AttnSide {
+  const bf16_t* qkv; bf16_t* o; int Tmax, d, causal; const uint8_t* kpm; const int32_t* seq_off; float o8_inv_scale;
+};
+template <int N0, int N1>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void attention_mfma_pair_kernel(AttnSide a0, AttnSide a1, int blocks0, int shift) {
+  __shared__ __attribute__((aligned(16))) bf16_t sV[(N0 > N1 ? N0 : N1) * 16 * kAttnVST];
+  int blk = static_cast<int>(blockIdx.x) + shift;          // shift = 0: the first problem's blocks lead; = blocks0 - grid: they trail
+  if (blk < 0) blk += gridDim.x;
+  if (blk < blocks0) attention_mfma_body<N0>(a0.qkv, a0.o, a0.Tmax, a0.d, a0.causal, a0.kpm, a0.seq_off, a0.o8_inv_scale, blk, sV);
+  else attention_mfma_body<N1>(a1.qkv, a1.o, a1.Tmax, a1.d, a1.causal, a1.kpm, a1.seq_off, a1.o8_inv_scale, blk - blocks0, sV);
+}
+
+static int attn_pair_tiles(int T) { return T <= 32 ? 2 : T <= 64 ? 4 : T <= 80 ? 5 : 0; }
+
+// does block_forward try the pair launch?  CMH_ATTN_PAIR=0 / 1 overrides the default (the A/B switch of
+// profiles/r08_a_attention_pair_ab.txt); CMH_PAIR_KERNELS=0 turns every pair kernel off
+constexpr bool kAttnPairDefault = true;
+bool attention_pair_routed() {
+  static const bool on = []() { const char* e = getenv("CMH_ATTN_PAIR"); return e && e[0] ? e[0] != '0' : kAttnPairDefault; }();
+  return on;
+}
+
+// 1 = not a pair this file has a kernel for (or CMH_PAIR_KERNELS=0): launch the two singly; < 0 = the launch itself failed
+int launch_attention_pair(const AttnProblem& p0, const AttnProblem& p1, hipStream_t st) {
+  static const bool off = []() { const char* e = getenv("CMH_PAIR_KERNELS"); return e && e[0] == '0'; }();
+  if (off) return 1;
+  const AttnProblem* P[2] = {&p0, &p1};
+  int nk[2];
+  for (int i = 0; i < 2; ++i) {
+    const AttnProblem& p = *P[i];
+    if (p.dt != CMH_BF16 || p.B <= 0 || p.T <= 0 || p.d <= 0 || p.d % HD != 0) return 1;
+    if (!(nk[i] = attn_pair_tiles(p.T))) return 1;
+  }
+  // the longer-running side's blocks come first (profiles/r08_a_attention_pair_ab.txt; -DATT_PAIR_SHORT_FIRST: the other order)
+  const int first = nk[1] > nk[0] ? 1 : 0;
+  const AttnProblem &f = *P[first], &s = *P[1 - first];
+  const int nf = nk[first], ns = nk[1 - first];
+  auto side = [](const AttnProblem& p) {
+    return AttnSide{static_cast<const bf16_t*>(p.qkv), static_cast<bf16_t*>(p.o), p.T, p.d, p.causal, p.kpm, p.seq_off, p.o8_inv_scale};
+  };
+  const int bf = f.B * (f.d / HD), bs = s.B * (s.d / HD);
+  const dim3 grid(bf + bs), block(64);
+#ifdef ATT_PAIR_SHORT_FIRST
+  const int shift = -bs;
+#else
+  const int shift = 0;
+#endif
+  if (nf == 5 && ns == 4) hipLaunchKernelGGL((attention_mfma_pair_kernel<5, 4>), grid, block, 0, st, side(f), side(s), bf, shift);
+  else if (nf == 4 && ns == 4) hipLaunchKernelGGL((attention_mfma_pair_kernel<4, 4>), grid, block, 0, st, side(f), side(s), bf, shift);
+  else if (nf == 4 && ns == 2) hipLaunchKernelGGL((attention_mfma_pair_kernel<4, 2>), grid, block, 0, st, side(f), side(s), bf, shift);
+  else return 1;
+  CMH_CHECK_LAUNCH("attention_mfma (pair)");
+  return CMH_OK;
 }
 
 int launch_attention(const void* qkv, void* o, int dt, int B, int T, int d, int causal,

@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "encoder_blocks.h"
+#include "attention_pair.h"
 
 namespace cmh {
 
@@ -204,14 +205,20 @@ int block_forward(const Lane& a, const Lane* b, hipStream_t st) {
                 "block_forward: the towers' residual streams differ in kind (the caller runs such towers one by one)");
   if ((rc = ln_stage(L, n, OP_LN1, st))) return rc;
   if ((rc = gemm_stage(L, n, G_IN_PROJ, st))) return rc;
-  // (the two attentions stay two launches: one launch for both - each side's body compiled for its own key-tile count - runs every
-  // wave at the wider side's register budget, 2 waves per SIMD instead of 3 for the image side: 36.3 us against 16.6 + 16.1,
-  // profiles/r04_j_bench_kernel_stats.csv; removed again)
+  // Both attentions as one launch where attention.hip has a pair kernel (bf16 forms, both T <= 80), else one launch per tower.  A
+  // kernel has one register budget: round 4's pair ran the text side on six key tiles and with it every wave at 2 per SIMD (36.3 us
+  // against 16.6 + 16.1, removed again); with the five-tile body both sides keep 3.  ViT-B/32 at batch 256, packed captions,
+  // per layer in the serialized trace: 26.6 us against 33.6 for the two launches (profiles/r08_a_attention_pair_ab.txt)
+  auto attn_problem = [](const Lane& l) {
+    const bool q = l.dtb == CMH_FP8;
+    return AttnProblem{l.qkv, l.attn, q ? CMH_BF16 : l.dtb, l.B, l.T, l.d, l.causal, l.kpm, l.seq_off, q ? 1.0f / scale(l, OP_ATTN) : 0.f};
+  };
+  int singly = 1;
+  if (n == 2 && attention_pair_routed() && (singly = launch_attention_pair(attn_problem(a), attn_problem(*b), st)) < 0) return singly;
   for (int i = 0; i < n; ++i) {
     const Lane& l = *L[i];
-    const bool q = l.dtb == CMH_FP8;
-    if ((rc = launch_attention_varlen(l.qkv, l.attn, q ? CMH_BF16 : l.dtb, l.B, l.T, l.d, l.causal, l.kpm, l.seq_off, st,
-                                      q ? 1.0f / scale(l, OP_ATTN) : 0.f))) return rc;
+    const AttnProblem p = attn_problem(l);
+    if (singly && (rc = launch_attention_varlen(p.qkv, p.o, p.dt, p.B, p.T, p.d, p.causal, p.kpm, p.seq_off, st, p.o8_inv_scale))) return rc;
     if ((rc = amax_stage(l, OP_ATTN, l.attn, static_cast<size_t>(l.M) * l.d, st))) return rc;
   }
   if (n == 2 && (a.pooled || b->pooled)) {      // the rest of the last block on the pooled rows of each tower (few-row kernels)
@@ -730,4 +737,16 @@ extern "C" int cmh_attention(int32_t dtype, const void* qkv, void* o, int32_t B,
   CMH_CHECK_ARG(qkv && o, "attention: null pointer");
   CMH_CHECK_ARG(dtype == CMH_F32 || dtype == CMH_BF16, "attention: bad dtype");
   return launch_attention(qkv, o, dtype, B, T, d, causal, key_padding_mask, as_stream(stream));
+}
+
+extern "C" int cmh_attention_pair(int32_t dtype, const void* qkv0, void* o0, int32_t B0, int32_t T0, int32_t d0, int32_t causal0,
+                                  const uint8_t* key_padding_mask0, const void* qkv1, void* o1, int32_t B1, int32_t T1, int32_t d1,
+                                  int32_t causal1, const uint8_t* key_padding_mask1, void* stream) {
+  CMH_CHECK_ARG(qkv0 && o0 && qkv1 && o1, "attention (pair): null pointer");
+  CMH_CHECK_ARG(dtype == CMH_F32 || dtype == CMH_BF16, "attention (pair): bad dtype");
+  CMH_CHECK_ARG(B0 > 0 && T0 > 0 && B1 > 0 && T1 > 0, "attention (pair): empty batch");
+  CMH_CHECK_ARG(d0 > 0 && d0 % 64 == 0 && d1 > 0 && d1 % 64 == 0, "attention (pair): widths %d, %d are not multiples of 64", d0, d1);
+  const AttnProblem p0{qkv0, o0, dtype, B0, T0, d0, causal0, key_padding_mask0, nullptr, 0.f};
+  const AttnProblem p1{qkv1, o1, dtype, B1, T1, d1, causal1, key_padding_mask1, nullptr, 0.f};
+  return launch_attention_pair(p0, p1, as_stream(stream));
 }

@@ -223,6 +223,13 @@ int cmh_set_gemm_grouped(int32_t on);
 /* softmax(q k^T / 8 [+causal] [+key padding]) v per head (head dim 64) on packed qkv [B*T, 3d] -> o [B*T, d]. */
 int cmh_attention(int32_t dtype, const void* qkv, void* o, int32_t B, int32_t T, int32_t d, int32_t causal,
                   const uint8_t* key_padding_mask, void* stream);
+/* Two attention problems (arguments as cmh_attention, each with its own B, T, d, causal flag and mask) as ONE launch: the lock-step
+ * pair path's kernel, here for tests and benchmarks.  bf16, both T <= 80.  Returns CMH_OK when launched, 1 when there is no such
+ * kernel for the pair (f32, T > 80, key-tile counts not instantiated, CMH_PAIR_KERNELS=0): nothing was launched and the caller
+ * calls cmh_attention twice; < 0 on error.  Every output element has cmh_attention's bits. */
+int cmh_attention_pair(int32_t dtype, const void* qkv0, void* o0, int32_t B0, int32_t T0, int32_t d0, int32_t causal0,
+                       const uint8_t* key_padding_mask0, const void* qkv1, void* o1, int32_t B1, int32_t T1, int32_t d1,
+                       int32_t causal1, const uint8_t* key_padding_mask1, void* stream);
 
 /* Measurement hook (bench.py `roofline`): while enabled, every GEMM launch of the library is timed with a pair of HIP events
  * on the launch stream.  The two hand-written GEMM kernels launch through hipExtLaunchKernelGGL, which stamps the pair with the
