@@ -19,9 +19,10 @@
 //   6. dh1  = dqkv W_in                                                       dW_in = dqkv^T h1,        db_in = sum dqkv
 //   7. dx  += LayerNorm_bwd(x_in, dh1) (+ dln_1)
 // Gradients are WRITTEN (not accumulated) into caller-owned f32 buffers shaped like the reference's parameters.
+// Host structure: TrainDims (a call's sizes) -> carve_train / open_tape / open_backward (the shared checks, the tape's slots); BlockRun (one
+// tower's walk) -> tape_forward, blocks_backward (the per-layer rules) -> block_backward (its four Linears: one table; its scratch: BlockRed).
 #include <cstring>
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "encoder_blocks.h"
@@ -46,8 +47,7 @@ struct TrainBufs {
   float* dx2;          // [M,d] f32
   void* dxe;           // [M,d] e
   void* dpre;          // [M,4d] e
-  float* part;         // split-K partial planes of the wgrad GEMMs
-  size_t part_bytes;
+  float* part;         // split-K partial planes of the wgrad GEMMs (kPartBytes)
   void* dh;            // [M,d] e
   void* dqkv;          // [M,3d] e
   void* tA;            // [rmax, Mpad] e   dY^T
@@ -66,14 +66,46 @@ struct TrainBufs {
 };
 
 size_t pad64(size_t m) { return (m + 63) / 64 * 64; }
+constexpr size_t kPartBytes = static_cast<size_t>(256 + 64) * 160 * 256 * 4;      // split-K planes: <= one round of 160x256 f32 tiles
+float* aligned_f32(void* p) {      // where a reduction's f32 partials start in a workspace: its first 256-byte boundary
+  return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 255) & ~static_cast<uintptr_t>(255));
+}
 
-// pk: conv1's patch-matrix K (conv1_k); conv1_padded: pk is the padded K, so the padded weight and its gradient get buffers too
-TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t xs, int layers, size_t g2rows, size_t pk,
-                      size_t embed, bool conv1_padded = false) {
+// The sizes of one training call: every entry point (forward, backward, *_train_bytes) derives them here and opens its tape with them.
+// e / xs: bytes of a GEMM operand / of a residual-stream element (xh: the fp16 stream); M = B * T rows; E: the head's width.
+struct TrainDims {
+  int dt, xh, B, T, M, d, E, layers;
+  size_t e, xs, g2rows = 0;      // g2rows (vision): rows of the patch matrix
+  int pk = 0, pkp = 0;           // vision: conv1's K = 3 p^2 and the K it runs with (conv1_k); pkp != pk: the K-padded conv1
+  // a bare stack of blocks: f32 stream, no head (E = 4 keeps the head's slots at their smallest)
+  TrainDims(int dtype, int B_, int T_, int d_, int layers_, int E_ = 4, int xh_ = 0)
+      : dt(dtype), xh(xh_), B(B_), T(T_), M(B_ * T_), d(d_), E(E_), layers(layers_), e(dtype == CMH_BF16 ? 2 : 4), xs(xh_ ? 2 : 4) {}
+  TrainDims(const cmh_text_weights* w, int batch, int seq_len)
+      : TrainDims(w->gemm_dtype, batch, seq_len, w->width, w->layers, w->embed_dim, resid_f16(w->gemm_dtype, w->width)) {}
+  TrainDims(const cmh_vit_weights* w, int batch)
+      : TrainDims(w->gemm_dtype, batch, 1, w->width, w->layers, w->embed_dim, resid_f16(w->gemm_dtype, w->width)) {
+    const int g = w->patch > 0 ? w->resolution / w->patch : 0;      // T = the patch grid + the class token
+    T = g * g + 1, M = B * T, g2rows = static_cast<size_t>(B) * g * g, pk = 3 * w->patch * w->patch, pkp = conv1_k(w->patch, dt);
+  }
+};
+
+// A block's six deferred reductions keep their partial sums side by side in t.red: 9 slices of a [M, d] bias gradient's partials
+// (proj 1, fc 4, out 1, in 3), then the two LayerNorm workspaces.  carve_train sizes t.red for bytes(); block_backward reads the offsets.
+struct BlockRed {
+  size_t db_slice, ln_ws, proj, fc, out, in, ln2, ln1;
+  BlockRed(int M, int d)
+      : db_slice(align_up(static_cast<size_t>((M + 63) / 64) * d * 4 + 256, 256)), ln_ws(align_up(cmh_layernorm_backward_workspace_bytes(M, d), 256)),
+        proj(0), fc(db_slice), out(5 * db_slice), in(6 * db_slice), ln2(9 * db_slice), ln1(ln2 + ln_ws) {}
+  size_t bytes() const { return ln1 + ln_ws; }
+};
+
+TrainBufs carve_train(void* ws, const TrainDims& D) {
+  const size_t M = static_cast<size_t>(D.B) * D.T, B = D.B, d = D.d, e = D.e, xs = D.xs, g2rows = D.g2rows, pk = D.pkp, embed = D.E;
+  const bool conv1_padded = D.pkp != D.pk;
   Arena a(ws);
   TrainBufs t;
-  t.L.resize(layers);
-  for (int i = 0; i < layers; ++i) {
+  t.L.resize(D.layers);
+  for (int i = 0; i < D.layers; ++i) {
     t.L[i].x_in = a.take(M * d * xs);
     t.L[i].h1 = a.take(M * d * e);
     t.L[i].qkv = a.take(M * 3 * d * e);
@@ -94,8 +126,7 @@ TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t x
   t.dx2 = a.take<float>(M * d * 4);
   t.dxe = a.take(M * d * e);
   t.dpre = a.take(M * 4 * d * e);
-  t.part_bytes = static_cast<size_t>(256 + 64) * 160 * 256 * 4;      // <= one round of 160x256 f32 tiles (kPartBytes)
-  t.part = a.take<float>(t.part_bytes);
+  t.part = a.take<float>(kPartBytes);
   t.dh = a.take(M * d * e);
   t.dqkv = a.take(M * 3 * d * e);
   size_t rmax = 4 * d > pk ? 4 * d : pk;
@@ -114,8 +145,7 @@ TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t x
   const size_t cands[] = {cmh_colsum_workspace_bytes(static_cast<int>(M), static_cast<int>(4 * d)),
                           cmh_colsum_workspace_bytes(static_cast<int>(B), static_cast<int>((M / B) * d))};
   for (size_t c : cands) rb = c > rb ? c : rb;
-  // a block's six deferred reductions keep their partials side by side: 9 [M, d]-bias slices (proj 1, fc 4, out 1, in 3) + 2 LayerNorms
-  const size_t batched = 9 * align_up(((M + 63) / 64) * d * 4 + 256, 256) + 2 * align_up(cmh_layernorm_backward_workspace_bytes(static_cast<int>(M), static_cast<int>(d)), 256);
+  const size_t batched = BlockRed(static_cast<int>(M), static_cast<int>(d)).bytes();
   rb = batched > rb ? batched : rb;
   t.red_bytes = rb;
   t.red = a.take(rb);
@@ -123,6 +153,21 @@ TrainBufs carve_train(void* ws, size_t M, size_t B, size_t d, size_t e, size_t x
   t.conv1_dw = a.take<float>(conv1_padded ? d * pk * 4 : 0);
   t.total = a.off;
   return t;
+}
+
+int check_train_tower(const TrainDims& D, const cmh_block_weights* blocks) {
+  CMH_CHECK_ARG(D.dt == CMH_F32 || D.dt == CMH_BF16, "bad gemm_dtype %d", D.dt);
+  CMH_CHECK_ARG(D.d > 0 && D.d % 128 == 0 && D.d <= 1024, "width %d must be a multiple of 128, <= 1024", D.d);
+  CMH_CHECK_ARG(D.layers >= 0 && D.E > 0 && D.E % 4 == 0, "bad layers/embed_dim");
+  CMH_CHECK_ARG(D.layers == 0 || blocks, "blocks is null");
+  return CMH_OK;
+}
+// Entry point `what` opens its tape: it holds carve_train's total and, where the call fills it (need_aligned), is 256-byte aligned.
+int open_tape(const char* what, const TrainDims& D, void* tape, size_t tape_bytes, bool need_aligned, TrainBufs* t) {
+  if (tape_bytes < carve_train(nullptr, D).total) return fail(CMH_ERR_WORKSPACE, "%s: tape too small", what);
+  CMH_CHECK_ARG(!need_aligned || (reinterpret_cast<uintptr_t>(tape) & 255) == 0, "%s: tape must be 256-byte aligned", what);
+  *t = carve_train(tape, D);
+  return CMH_OK;
 }
 
 // the last block's row-wise tail on the pooled rows only (tape_forward / block_backward): the rule both calls of a step apply,
@@ -135,39 +180,37 @@ bool train_pooled_tail() {
 int xkind(int xh) { return xh ? kF16 : kF32; }
 int ekind(int dt) { return dt == CMH_BF16 ? kBF16 : kF32; }
 
-// x [M,d] f32 -> GEMM dtype copy (bf16 mode) or the same pointer (f32 mode)
-int as_gemm_operand(int dt, const float* x, void* scratch, size_t n, hipStream_t st, const void** out) {
-  if (dt == CMH_F32) { *out = x; return CMH_OK; }
-  *out = scratch;
-  return cmh_cast_f32_to_bf16(x, scratch, static_cast<int64_t>(n), st);
-}
+// One tower's walk over its blocks, forward with a tape or backward: what no layer changes (the role Lane plays for block_forward).
+struct BlockRun {
+  const TrainDims& D; const cmh_block_weights* blocks; TrainBufs& t; hipStream_t st;
+  int M;                                                                       // rows of the stream (a packed text tape: its packed row count)
+  int causal = 0; const uint8_t* kpm = nullptr; const int32_t* seq_off = nullptr;      // text: the mask; packed rows: per-caption row offsets
+  bool tail = false;                                                           // the last block's row-wise tail runs on the pooled rows t.rows only
+};
 
-struct BlockGradPtrs { float *in_w, *in_b, *out_w, *out_b, *ln1_w, *ln1_b, *ln2_w, *ln2_b, *fc_w, *fc_b, *proj_w, *proj_b; };
-
-// Every block of a tower with its tape: block i reads t.L[i].x_in and writes the next block's x_in (the last one t.x_last); `base`
-// holds what the layers share.  pooled_rows (the LAST block of a tower whose only output is the pooled feature, like the inference
-// towers' pooled tail): after the attention the block's row-wise tail - out_proj, ln_2, the MLP - runs on the B pooled rows only.  The
-// tape slots then hold B-row matrices: x_mid, h2, pre, act rows [0, B); the pooled attention rows (out_proj's wgrad operand) sit in h2
-// rows [B, 2B); x_last receives B rows.  block_backward(..., pooled_rows) reads them back the same way.
-int tape_forward(Lane base, const cmh_block_weights* blocks, int layers, const TrainBufs& t, const int32_t* pooled_rows, hipStream_t st) {
-  for (int i = 0; i < layers; ++i) {
-    const LayerTape& L = t.L[i];
+// Every block of a tower with its tape: block i reads t.L[i].x_in and writes the next block's x_in (the last one t.x_last).
+// r.tail (the LAST block of a tower whose only output is the pooled feature, like the inference towers' pooled tail): after the
+// attention the block's row-wise tail - out_proj, ln_2, the MLP - runs on the B pooled rows only.  The tape slots then hold B-row
+// matrices: x_mid, h2, pre, act rows [0, B); the pooled attention rows (out_proj's wgrad operand) sit in h2 rows [B, 2B); x_last
+// receives B rows.  block_backward(..., pooled) reads them back the same way.
+int tape_forward(const BlockRun& r) {
+  const TrainDims& D = r.D;
+  Lane base;
+  base.dtb = D.dt; base.xh = D.xh; base.B = D.B; base.T = D.T; base.d = D.d;
+  base.causal = r.causal; base.kpm = r.kpm; base.M = r.M; base.seq_off = r.seq_off;
+  for (int i = 0; i < D.layers; ++i) {
+    const LayerTape& L = r.t.L[i];
     Lane l = base;
-    l.w = &blocks[i];
+    l.w = &r.blocks[i];
     l.x_in = L.x_in; l.h1 = L.h1; l.qkv = L.qkv; l.attn = L.attn; l.x_mid = L.x_mid; l.h2 = L.h2; l.pre = L.pre; l.act = L.act;
-    l.x_out = i + 1 < layers ? t.L[i + 1].x_in : t.x_last;
-    if (pooled_rows && i == layers - 1) {
-      l.pooled = pooled_rows;
-      l.attn_p = static_cast<char*>(L.h2) + static_cast<size_t>(l.B) * l.d * (l.dtb == CMH_BF16 ? 2 : 4);
+    l.x_out = i + 1 < D.layers ? r.t.L[i + 1].x_in : r.t.x_last;
+    if (r.tail && i == D.layers - 1) {
+      l.pooled = r.t.rows;
+      l.attn_p = static_cast<char*>(L.h2) + static_cast<size_t>(D.B) * D.d * D.e;
     }
-    if (int rc = block_forward(l, nullptr, st)) return rc;
+    if (int rc = block_forward(l, nullptr, r.st)) return rc;
   }
   return CMH_OK;
-}
-Lane train_lane(int dt, int xh, int B, int T, int d, int causal, const uint8_t* kpm, int rows, const int32_t* seq_off) {
-  Lane l;
-  l.dtb = dt; l.xh = xh; l.B = B; l.T = T; l.d = d; l.causal = causal; l.kpm = kpm; l.M = rows; l.seq_off = seq_off;
-  return l;
 }
 
 // dW[O, I] = dY^T X with dY [M, O] (kind ky) and X [M, I] (kind kx); db[O] = column sums of dY
@@ -182,7 +225,7 @@ int wgrad_core(int dt, const void* dY, int ky, int O, const void* X, int kx, int
   const void* dYb = ky == kBF16 ? dY : dYe;
   if (dt == CMH_BF16 && kx == kBF16 && dYb && gemm_wide_tn_supported(O, I, M)) {
     // the bias gradient's first stage (column sums of dY per K split) is a by-product of the same launch
-    float* dbp = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(w.red) + 255) & ~static_cast<uintptr_t>(255));
+    float* dbp = aligned_f32(w.red);
     const bool cs = db && w.red_bytes >= static_cast<size_t>(64) * O * 4 + 256;
     int slices = 0;
     if ((rc = launch_gemm_wide_tn(dYb, X, dW, w.part, w.part_bytes, O, I, M, st, cs ? dbp : nullptr, &slices))) return rc;
@@ -194,7 +237,7 @@ int wgrad_core(int dt, const void* dY, int ky, int O, const void* X, int kx, int
   }
   // db = column sums of dY: their first stage rides on the transpose of dY when that takes the tiled path
   const bool fuse_db = db && transpose_is_vectorised(dY, w.tA, M, O, mp) && w.red_bytes >= static_cast<size_t>((M + 63) / 64) * O * 4 + 256;
-  float* dbp = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(w.red) + 255) & ~static_cast<uintptr_t>(255));
+  float* dbp = aligned_f32(w.red);
   if ((rc = launch_transpose(dY, ky, w.tA, ekind(dt), M, O, mp, st, fuse_db ? dbp : nullptr))) return rc;
   if (fuse_db && w.defer && w.defer->n < FinalJobs::kMax) w.defer->add(dbp, (M + 63) / 64, O, db);     // final stage queued
   else if (fuse_db && (rc = launch_colsum_final(dbp, (M + 63) / 64, O, db, st))) return rc;
@@ -211,22 +254,16 @@ int wgrad_core(int dt, const void* dY, int ky, int O, const void* X, int kx, int
 int wgrad(int dt, const void* dY, int ky, int O, const void* X, int kx, int I, int M, float* dW, float* db, TrainBufs& t,
           hipStream_t st, FinalJobs* defer = nullptr, size_t red_off = 0, const void* dYe = nullptr) {
   return wgrad_core(dt, dY, ky, O, X, kx, I, M, dW, db,
-                    WgradScratch{t.tA, t.tB, t.part, t.part_bytes, static_cast<char*>(t.red) + red_off, t.red_bytes - red_off, defer}, st,
+                    WgradScratch{t.tA, t.tB, t.part, kPartBytes, static_cast<char*>(t.red) + red_off, t.red_bytes - red_off, defer}, st,
                     dYe);
 }
 
-// dX[M, I] = dY[M, O] . W[O, I]  (W in the GEMM dtype, row-major [O, I]); out typed by `epi`
-int dgrad(int dt, const void* dYe, const void* W, int O, int I, int M, const void* aux, void* dX, int epi, TrainBufs& t,
-          hipStream_t st, const void* Wt = nullptr) {      // Wt: W^T [I, O] when the caller has it already
-  int rc;
-  if (!Wt) {
-    if ((rc = launch_transpose(W, ekind(dt), t.wT, ekind(dt), O, I, O, st))) return rc;      // W^T [I, O]
-    Wt = t.wT;
-  }
-  return launch_gemm(dt, dYe, Wt, nullptr, static_cast<const float*>(aux), dX, M, I, O, epi, st);
+int zero_pad_buffers(TrainBufs& t, size_t M, hipStream_t st) {
+  if (pad64(M) == M) return CMH_OK;     // no padding columns: nothing to clear
+  if (hipMemsetAsync(t.tA, 0, t.tAB_bytes, st) != hipSuccess || hipMemsetAsync(t.tB, 0, t.tAB_bytes, st) != hipSuccess)
+    return fail(CMH_ERR_LAUNCH, "backward: memset failed");
+  return CMH_OK;
 }
-
-int zero_pad_buffers(TrainBufs& t, size_t M, hipStream_t st);
 
 static int g_grad_stream16 = -1;      // cmh_set_grad_stream16: -1 = from the environment (CMH_GRAD_STREAM16=0 switches it off)
 bool grad_stream16_enabled() {
@@ -234,53 +271,74 @@ bool grad_stream16_enabled() {
   return g_grad_stream16 < 0 ? env_on : g_grad_stream16 != 0;
 }
 
-// pooled_rows / dxp (the last block after tape_forward(..., pooled_rows)): the incoming gradient is dxp [B, d] f32 on the
-// pooled rows; steps 1-4 run on those B rows, then the two gradients that go on - d(attention output) and the residual stream -
-// are scattered into zeroed full-size buffers for the attention backward and ln_1.
+// One of a block's four Linears, Y = X W^T + b over `rows` rows, as its backward needs it.  dY (kind ky) is what the bias gradient
+// sums; dYe is the same gradient as a bf16 GEMM operand where dY itself is f32 (the residual stream keeps both).
+struct BlockLinear {
+  const void* W; int O, I;
+  const void* dY; int ky; const void* dYe; const void* X; int rows;
+  float *dW, *db;
+  size_t red;                    // its bias partials in t.red (BlockRed)
+  void* Wt;                      // W^T [I, O] in t.wT
+  const void* operand() const { return dYe ? dYe : dY; }
+};
+
+// Block `layer`: t.dx holds dL/dx_out and leaves as dL/dx_in.  dxe_ready: the block before (or the all-token head) left its bf16 copy in t.dxe.
+// pooled (the last block of a run with r.tail): the incoming gradient is t.dx2 [B, d] f32 on the pooled rows t.rows;
+// steps 1-4 run on those B rows, then the two gradients that go on - d(attention output) and the residual stream - are scattered into
+// zeroed full-size buffers for the attention backward and ln_1.
 // keep_f32: the caller reads the f32 gradient stream (t.dx) behind this block (the embeddings' backward after block 0; the
 // caller-visible dx of cmh_blocks_backward) - see the 16-bit stream below.
-int block_backward(const cmh_block_weights& w, const BlockGradPtrs& g, int dt, int xh, const LayerTape& L, TrainBufs& t, int B,
-                   int T, int d, int causal, const uint8_t* kpm, hipStream_t st, bool dxe_ready, int rows = -1,
-                   const int32_t* seq_off = nullptr, const int32_t* pooled_rows = nullptr, float* dxp = nullptr,
-                   bool keep_f32 = true) {
-  const int M = rows >= 0 ? rows : B * T;
-  const int Mt = pooled_rows ? B : M;                  // rows of the row-wise tail (steps 1-4)
-  float* dxt = pooled_rows ? dxp : t.dx;               // its gradient stream
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  const int ek = ekind(dt), xk = xkind(xh);
-  const size_t md = static_cast<size_t>(M) * d;
-  const void* dxe = nullptr;
+int block_backward(const BlockRun& r, int layer, const cmh_block_grads& g, bool dxe_ready, bool pooled, bool keep_f32) {
+  const cmh_block_weights& w = r.blocks[layer];
+  TrainBufs& t = r.t;
+  const LayerTape& L = t.L[layer];
+  hipStream_t st = r.st;
+  const int dt = r.D.dt, B = r.D.B, d = r.D.d, M = r.M;
+  const int Mt = pooled ? B : M;                       // rows of the row-wise tail (steps 1-4)
+  float* dxt = pooled ? t.dx2 : t.dx;                  // its gradient stream
+  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0, ek = ekind(dt), xk = xkind(r.D.xh);
+  const size_t esz = r.D.e, md = static_cast<size_t>(M) * d, mtd = static_cast<size_t>(Mt) * d;
   // bf16 mode: the LayerNorm backward kernels also leave the new dx as the bf16 GEMM operand (t.dxe)
   void* dx_copy = dt == CMH_BF16 ? t.dxe : nullptr;
   int rc;
   // The final stage of the block's six small reductions (four bias gradients, two LayerNorm parameter pairs) is queued and
-  // launched once at the end of the block; their partial sums live side by side in t.red (sized for that by carve_train).
+  // launched once at the end of the block; their partial sums live side by side in t.red (BlockRed).
   FinalJobs jobs;
-  const size_t db_slice = align_up(static_cast<size_t>((M + 63) / 64) * d * 4 + 256, 256);       // partials of a [M, d] bias gradient
-  const size_t ln_ws = align_up(cmh_layernorm_backward_workspace_bytes(M, d), 256);
-  const size_t off_proj = 0, off_fc = db_slice, off_out = 5 * db_slice, off_in = 6 * db_slice, off_ln2 = 9 * db_slice,
-               off_ln1 = off_ln2 + ln_ws;
-  const bool batched = off_ln1 + ln_ws <= t.red_bytes;
+  const BlockRed R(M, d);
+  const bool batched = R.bytes() <= t.red_bytes;
   FinalJobs* dj = batched ? &jobs : nullptr;
   char* red = static_cast<char*>(t.red);
-  // W^T of the four weight matrices, one launch: proj [d, 4d], fc [4d, d], out_proj [d, d], in_proj [3d, d]
-  const size_t esz = dt == CMH_BF16 ? 2 : 4, dd = static_cast<size_t>(d) * d;
+  // The four Linears in the order the backward meets them; what concerns all four - the W^T launch, the one-launch wgrad and its fit
+  // test, the per-layer wgrads, the bias jobs - is derived from this table.  (pooled: out_proj's X, the gathered attention rows, is
+  // parked behind the first B rows of the h2 slot.  out_proj's dYe is filled in once ln_2's copy has its place.)
+  const void* attn_rows = pooled ? static_cast<const char*>(L.h2) + static_cast<size_t>(B) * d * esz : L.attn;
+  enum { kProj, kFc, kOut, kIn };
+  BlockLinear lin[4] = {{w.proj_w, d, 4 * d, dxt, kF32, dx_copy, L.act, Mt, g.proj_w, g.proj_b, R.proj},
+                        {w.fc_w, 4 * d, d, t.dpre, ek, nullptr, L.h2, Mt, g.fc_w, g.fc_b, R.fc},
+                        {w.out_proj_w, d, d, dxt, kF32, nullptr, attn_rows, Mt, g.out_proj_w, g.out_proj_b, R.out},
+                        {w.in_proj_w, 3 * d, d, t.dqkv, ek, nullptr, L.h1, M, g.in_proj_w, g.in_proj_b, R.in}};
+  const void* wsrc[4];      // W^T of the four weight matrices side by side in t.wT, one launch
+  void* wdst[4];
+  int wR[4], wC[4];
+  TnMultiJob probe[4];      // the one-launch wgrad's shapes
   char* wt = static_cast<char*>(t.wT);
-  const void* wsrc[4] = {w.proj_w, w.fc_w, w.out_proj_w, w.in_proj_w};
-  void* wdst[4] = {wt, wt + 4 * dd * esz, wt + 8 * dd * esz, wt + 9 * dd * esz};
-  const int wR[4] = {d, 4 * d, d, 3 * d}, wC[4] = {4 * d, d, d, d};
+  for (int j = 0; j < 4; ++j) {
+    lin[j].Wt = wt;
+    wt += static_cast<size_t>(lin[j].O) * lin[j].I * esz;
+    wsrc[j] = lin[j].W; wdst[j] = lin[j].Wt; wR[j] = lin[j].O; wC[j] = lin[j].I;
+    probe[j] = TnMultiJob{nullptr, nullptr, nullptr, nullptr, lin[j].O, lin[j].I, lin[j].rows};
+  }
   if ((rc = launch_transpose_multi(wsrc, wdst, wR, wC, 4, ek, st))) return rc;
-  if (pooled_rows && (rc = zero_pad_buffers(t, static_cast<size_t>(B), st))) return rc;      // the tail's transposes are B rows wide
+  if (pooled && (rc = zero_pad_buffers(t, static_cast<size_t>(B), st))) return rc;      // the tail's transposes are B rows wide
   // Round 4: the block's four weight gradients as ONE launch (gemm_wide.hip: gemm_wide_tn_multi_kernel), issued after the last dgrad
   // and before ln_1's backward: together they are one round of the chip with little or no K split, no partial planes, one launch's
   // fixed cost instead of four.  Their operands must all still be there at that point: the residual gradient as a GEMM operand exists
   // in two versions per block (at the block's entry: c_proj's dY; after ln_2: out_proj's), so ln_2's backward writes its copy to a
   // second buffer (t.dx2, otherwise only the pooled tail's) and ln_1's, as before, to t.dxe - the next block's entry.
-  const TnMultiJob probe[4] = {{nullptr, nullptr, nullptr, nullptr, d, 4 * d, M}, {nullptr, nullptr, nullptr, nullptr, 4 * d, d, M},
-                               {nullptr, nullptr, nullptr, nullptr, d, d, M}, {nullptr, nullptr, nullptr, nullptr, 3 * d, d, M}};
-  const bool multi = dt == CMH_BF16 && !pooled_rows && batched && dx_copy && gemm_wide_tn_multi_enabled() && gemm_wide_tn_multi_fits(probe, 4) &&
-                     db_slice >= static_cast<size_t>(64) * d * 4 + 256;
+  const bool multi = dt == CMH_BF16 && !pooled && batched && dx_copy && gemm_wide_tn_multi_enabled() && gemm_wide_tn_multi_fits(probe, 4) &&
+                     R.db_slice >= static_cast<size_t>(64) * d * 4 + 256;
   void* dx_copy2 = multi ? static_cast<void*>(t.dx2) : dx_copy;      // where ln_2's backward leaves the bf16 copy of the new dx
+  lin[kOut].dYe = dx_copy2;
   // Round 5: the 16-bit gradient stream.  The residual gradient is needed twice per block as a bf16 GEMM operand (c_proj's and
   // out_proj's dY) and twice as the sum a LayerNorm backward adds to; kept in f32 the two LayerNorm launches read AND write it
   // beside the bf16 copy they leave anyway (14 bytes per element: x 2, dy 2, dx 4 + 4, copy 2).  In the bf16 mode's multi-launch
@@ -289,71 +347,76 @@ int block_backward(const cmh_block_weights& w, const BlockGradPtrs& g, int dt, i
   // each 2^-9 relative: below what the bf16 GEMM operands already cost, tests/test_gpu_backward.py).  t.dx is written only where
   // somebody reads it (keep_f32).  The f32 mode, the pooled last block and CMH_GRAD_STREAM16=0 keep the f32 stream.
   const bool s16 = multi && grad_stream16_enabled();
-  // 1. MLP projection (dxe_ready: the previous block's ln_1 backward already wrote t.dxe)
-  const size_t mtd = static_cast<size_t>(Mt) * d;
-  if (dxe_ready && dx_copy) dxe = t.dxe;
-  else if ((rc = as_gemm_operand(dt, dxt, t.dxe, mtd, st, &dxe))) return rc;
-  const void* dxe_entry = dxe;
-  if ((rc = dgrad(dt, dxe, w.proj_w, d, 4 * d, Mt, L.pre, t.dpre, EPI_MUL_DQGELU | obf, t, st, wdst[0]))) return rc;
-  if (!multi && (rc = wgrad(dt, dxt, kF32, d, L.act, ek, 4 * d, Mt, g.proj_w, g.proj_b, t, st, dj, batched ? off_proj : 0,
-                            dt == CMH_BF16 ? dxe : nullptr))) return rc;
+  // one Linear's stage: dX [rows, I] = dY . W on (dY, W^T), through `epi` and typed like the GEMM operands; then - unless the one
+  // launch takes all four - dW and db
+  auto stage = [&](const BlockLinear& l, const void* aux, void* dX, int epi) {
+    int rc = launch_gemm(dt, l.operand(), l.Wt, nullptr, static_cast<const float*>(aux), dX, l.rows, l.I, l.O, epi | obf, st);
+    if (rc || multi) return rc;
+    return wgrad(dt, l.dY, l.ky, l.O, l.X, ek, l.I, l.rows, l.dW, l.db, t, st, dj, batched ? l.red : 0, l.dYe);
+  };
+  // 1. MLP projection: the incoming gradient as a GEMM operand first (f32 mode: the stream itself)
+  if (dx_copy && !dxe_ready && (rc = cmh_cast_f32_to_bf16(dxt, t.dxe, static_cast<int64_t>(mtd), st))) return rc;
+  if ((rc = stage(lin[kProj], L.pre, t.dpre, EPI_MUL_DQGELU))) return rc;
   // 2. c_fc
-  if ((rc = dgrad(dt, t.dpre, w.fc_w, 4 * d, d, Mt, nullptr, t.dh, obf, t, st, wdst[1]))) return rc;
-  if (!multi && (rc = wgrad(dt, t.dpre, ek, 4 * d, L.h2, ek, d, Mt, g.fc_w, g.fc_b, t, st, dj, batched ? off_fc : 0))) return rc;
+  if ((rc = stage(lin[kFc], nullptr, t.dh, 0))) return rc;
   // 3. ln_2
   if ((rc = launch_layernorm_backward(L.x_mid, xk, t.dh, ek, w.ln2_w, nullptr, Mt, d, dxt, s16 ? 0 : 1, g.ln2_w, g.ln2_b,
-                                      batched ? red + off_ln2 : red, batched ? ln_ws : t.red_bytes, st, dx_copy2, dj,
-                                      s16 ? dxe_entry : nullptr, !s16))) return rc;
+                                      batched ? red + R.ln2 : red, batched ? R.ln_ws : t.red_bytes, st, dx_copy2, dj,
+                                      s16 ? dx_copy : nullptr, !s16))) return rc;
   // 4. out_proj
-  if (dx_copy2) dxe = dx_copy2;
-  else if ((rc = as_gemm_operand(dt, dxt, t.dxe, mtd, st, &dxe))) return rc;
-  const void* dxe_mid = dxe;
-  const void* attn_rows = pooled_rows ? static_cast<const char*>(L.h2) + static_cast<size_t>(B) * d * esz : L.attn;
-  if ((rc = dgrad(dt, dxe, w.out_proj_w, d, d, Mt, nullptr, t.dh, obf, t, st, wdst[2]))) return rc;
-  if (!multi && (rc = wgrad(dt, dxt, kF32, d, attn_rows, ek, d, Mt, g.out_w, g.out_b, t, st, dj, batched ? off_out : 0,
-                            dt == CMH_BF16 ? dxe : nullptr))) return rc;
+  if ((rc = stage(lin[kOut], nullptr, t.dh, 0))) return rc;
   const void* dattn = t.dh;
-  if (pooled_rows) {
+  if (pooled) {
     // back to full size: d(attention output) is zero off the pooled rows (t.dxe is free now), the residual gradient likewise
     if (hipMemsetAsync(t.dxe, 0, md * esz, st) != hipSuccess || hipMemsetAsync(t.dx, 0, md * 4, st) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "backward: memset failed");
-    if ((rc = launch_scatter_rows(t.dh, pooled_rows, t.dxe, B, static_cast<int>(d * esz), st))) return rc;
-    if ((rc = launch_scatter_rows(dxp, pooled_rows, t.dx, B, d * 4, st))) return rc;
+    if ((rc = launch_scatter_rows(t.dh, t.rows, t.dxe, B, static_cast<int>(d * esz), st))) return rc;
+    if ((rc = launch_scatter_rows(t.dx2, t.rows, t.dx, B, d * 4, st))) return rc;
     dattn = t.dxe;
     if ((rc = zero_pad_buffers(t, static_cast<size_t>(M), st))) return rc;       // the B-row transposes left their rows in the padding
   }
   // 5. attention
-  if ((rc = launch_attention_backward(dt, L.qkv, L.attn, dattn, t.dqkv, B, T, d, causal, kpm, seq_off, st))) return rc;
+  if ((rc = launch_attention_backward(dt, L.qkv, L.attn, dattn, t.dqkv, B, r.D.T, d, r.causal, r.kpm, r.seq_off, st))) return rc;
   // 6. in_proj
-  if ((rc = dgrad(dt, t.dqkv, w.in_proj_w, 3 * d, d, M, nullptr, t.dh, obf, t, st, wdst[3]))) return rc;
-  if (!multi && (rc = wgrad(dt, t.dqkv, ek, 3 * d, L.h1, ek, d, M, g.in_w, g.in_b, t, st, dj, batched ? off_in : 0))) return rc;
+  if ((rc = stage(lin[kIn], nullptr, t.dh, 0))) return rc;
   if (multi) {
-    auto dbp = [&](size_t off) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(red + off) + 255) & ~static_cast<uintptr_t>(255)); };
-    const TnMultiJob jobs4[4] = {{dxe_entry, L.act, g.proj_w, dbp(off_proj), d, 4 * d, M},
-                                 {t.dpre, L.h2, g.fc_w, dbp(off_fc), 4 * d, d, M},
-                                 {dxe_mid, L.attn, g.out_w, dbp(off_out), d, d, M},
-                                 {t.dqkv, L.h1, g.in_w, dbp(off_in), 3 * d, d, M}};
-    float* const dbs[4] = {g.proj_b, g.fc_b, g.out_b, g.in_b};
+    TnMultiJob jobs4[4];
+    for (int j = 0; j < 4; ++j)
+      jobs4[j] = TnMultiJob{lin[j].operand(), lin[j].X, lin[j].dW, aligned_f32(red + lin[j].red), lin[j].O, lin[j].I, lin[j].rows};
     int slices[4] = {0, 0, 0, 0};
-    if ((rc = launch_gemm_wide_tn_multi(jobs4, 4, t.part, t.part_bytes, st, slices))) return rc;
-    for (int i = 0; i < 4; ++i) jobs.add(jobs4[i].colsum, slices[i], jobs4[i].Mm, dbs[i]);
+    if ((rc = launch_gemm_wide_tn_multi(jobs4, 4, t.part, kPartBytes, st, slices))) return rc;
+    for (int j = 0; j < 4; ++j) jobs.add(jobs4[j].colsum, slices[j], lin[j].O, lin[j].db);
   }
   // 7. ln_1
   if ((rc = launch_layernorm_backward(L.x_in, xk, t.dh, ek, w.ln1_w, nullptr, M, d, t.dx, s16 ? 0 : 1, g.ln1_w, g.ln1_b,
-                                      batched ? red + off_ln1 : red, batched ? ln_ws : t.red_bytes, st, dx_copy, dj,
-                                      s16 ? dxe_mid : nullptr, !s16 || keep_f32))) return rc;
+                                      batched ? red + R.ln1 : red, batched ? R.ln_ws : t.red_bytes, st, dx_copy, dj,
+                                      s16 ? dx_copy2 : nullptr, !s16 || keep_f32))) return rc;
   return launch_final_jobs(jobs, st);
 }
 
-BlockGradPtrs grads_of(const cmh_block_grads& g) {
-  return BlockGradPtrs{g.in_proj_w, g.in_proj_b, g.out_proj_w, g.out_proj_b, g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b,
-                       g.fc_w, g.fc_b, g.proj_w, g.proj_b};
+// What every backward entry point `what` checks after its own arguments, in this order, then its tape: the layer range [lo, *hi)
+// (*hi < 0: every layer), the tower, the head's gradient pointers (head_grads: the caller's null test of its own struct), the blocks'.
+int open_backward(const char* what, const TrainDims& D, const cmh_block_weights* blocks, bool head_grads, const cmh_block_grads* grads,
+                  void* tape, size_t tape_bytes, int* hi, int lo, TrainBufs* t) {
+  if (*hi < 0) *hi = D.layers;
+  CMH_CHECK_ARG(0 <= lo && lo <= *hi && *hi <= D.layers, "%s: layers [%d, %d) of %d", what, lo, *hi, D.layers);
+  int rc = check_train_tower(D, blocks);
+  if (rc) return rc;
+  CMH_CHECK_ARG(head_grads && grads, "%s: null gradient pointer", what);
+  for (int i = 0; i < D.layers; ++i) {
+    const cmh_block_grads& p = grads[i];
+    CMH_CHECK_ARG(p.in_proj_w && p.in_proj_b && p.out_proj_w && p.out_proj_b && p.ln1_w && p.ln1_b && p.ln2_w && p.ln2_b && p.fc_w &&
+                  p.fc_b && p.proj_w && p.proj_b, "backward: block %d has a null gradient pointer", i);
+  }
+  return open_tape(what, D, tape, tape_bytes, /*need_aligned=*/false, t);
 }
-int check_block_grads(const cmh_block_grads* g, int layers) {
-  for (int i = 0; i < layers; ++i) {
-    const BlockGradPtrs p = grads_of(g[i]);
-    CMH_CHECK_ARG(p.in_w && p.in_b && p.out_w && p.out_b && p.ln1_w && p.ln1_b && p.ln2_w && p.ln2_b && p.fc_w && p.fc_b &&
-                  p.proj_w && p.proj_b, "backward: block %d has a null gradient pointer", i);
+
+// Blocks hi-1 .. lo of a tower, last first, with the rules that depend on the layer: the LAST block finds a bf16 copy of its incoming
+// gradient only behind the all-token head, and it alone runs the pooled tail; block 0 leaves the f32 stream for whoever comes after.
+int blocks_backward(const BlockRun& r, const cmh_block_grads* grads, int hi, int lo, bool dtokens_head) {
+  for (int i = hi - 1; i >= lo; --i) {
+    const bool last = i == r.D.layers - 1;
+    if (int rc = block_backward(r, i, grads[i], /*dxe_ready=*/!last || dtokens_head, /*pooled=*/r.tail && last, /*keep_f32=*/i == 0)) return rc;
   }
   return CMH_OK;
 }
@@ -434,12 +497,15 @@ __global__ __launch_bounds__(256) void pool_wgrad_kernel(const T* __restrict__ p
   }
 }
 
+// A tower's head: its parameters (out = LN(rows of x_last) . proj) and, for the backward, where their gradients go
+struct Head { const float *ln_w, *ln_b; const void* proj_t; float *dproj = nullptr, *dln_w = nullptr, *dln_b = nullptr; };
+
 // compact = the forward carried only the pooled rows through the last block (x_last holds B rows): the gradient stays compact too,
-// B rows of t.dx2, for block_backward(..., pooled_rows, dxp)
-int pooled_backward(int dt, int xh, const void* x_last, const int32_t* rows, const void* pool, const void* proj_t,
-                    const float* ln_w, const float* dfeat, float* dproj, float* dln_w, float* dln_b, TrainBufs& t, int B, int M,
-                    int d, int E, hipStream_t st, bool compact = false) {
-  float* dpool = t.small;
+// B rows of t.dx2, for block_backward(..., pooled).  M: rows of the gradient stream otherwise.
+int pooled_backward(const TrainDims& D, TrainBufs& t, const Head& h, const float* dfeat, int M, bool compact, hipStream_t st) {
+  const int dt = D.dt, B = D.B, d = D.d, E = D.E;
+  const void *pool = t.pool, *proj_t = h.proj_t;
+  float *dpool = t.small, *dproj = h.dproj;
   if (dt == CMH_F32) {
     hipLaunchKernelGGL(pool_dgrad_kernel<float>, dim3(B), dim3(256), 0, st, dfeat, static_cast<const float*>(proj_t), dpool, B, d, E);
     hipLaunchKernelGGL(pool_wgrad_kernel<float>, dim3(d), dim3(256), 0, st, static_cast<const float*>(pool), dfeat, dproj, B, d, E);
@@ -451,10 +517,9 @@ int pooled_backward(int dt, int xh, const void* x_last, const int32_t* rows, con
     hipLaunchKernelGGL(pool_wgrad_kernel<bf16_t>, dim3(d), dim3(256), 0, st, static_cast<const bf16_t*>(pool), dfeat, dproj, B, d, E);
   }
   CMH_CHECK_LAUNCH("pooled projection backward");
-  if (compact)
-    return launch_layernorm_backward(x_last, xkind(xh), dpool, kF32, ln_w, nullptr, B, d, t.dx2, 0, dln_w, dln_b, t.red, t.red_bytes, st);
-  if (hipMemsetAsync(t.dx, 0, static_cast<size_t>(M) * d * 4, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "backward: memset failed");
-  return launch_layernorm_backward(x_last, xkind(xh), dpool, kF32, ln_w, rows, B, d, t.dx, 0, dln_w, dln_b, t.red, t.red_bytes, st);
+  if (!compact && hipMemsetAsync(t.dx, 0, static_cast<size_t>(M) * d * 4, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "backward: memset failed");
+  return launch_layernorm_backward(t.x_last, xkind(D.xh), dpool, kF32, h.ln_w, compact ? nullptr : t.rows, B, d, compact ? t.dx2 : t.dx, 0,
+                                   h.dln_w, h.dln_b, t.red, t.red_bytes, st);
 }
 
 // token embedding: dE[token[r], :] += dx[r, :]
@@ -511,29 +576,12 @@ __global__ __launch_bounds__(256) void packed_embed_scatter_kernel(const int64_t
   for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dE + static_cast<size_t>(id) * d + c, dx[r * d + c]);
 }
 
-int zero_pad_buffers(TrainBufs& t, size_t M, hipStream_t st) {
-  if (pad64(M) == M) return CMH_OK;     // no padding columns: nothing to clear
-  if (hipMemsetAsync(t.tA, 0, t.tAB_bytes, st) != hipSuccess || hipMemsetAsync(t.tB, 0, t.tAB_bytes, st) != hipSuccess)
-    return fail(CMH_ERR_LAUNCH, "backward: memset failed");
-  return CMH_OK;
-}
-
-int check_train_tower(int dt, int width, int layers, int embed, const cmh_block_weights* blocks) {
-  CMH_CHECK_ARG(dt == CMH_F32 || dt == CMH_BF16, "bad gemm_dtype %d", dt);
-  CMH_CHECK_ARG(width > 0 && width % 128 == 0 && width <= 1024, "width %d must be a multiple of 128, <= 1024", width);
-  CMH_CHECK_ARG(layers >= 0 && embed > 0 && embed % 4 == 0, "bad layers/embed_dim");
-  CMH_CHECK_ARG(layers == 0 || blocks, "blocks is null");
-  return CMH_OK;
-}
-
 }  // namespace
 }  // namespace cmh
 
 using namespace cmh;
 
 // ================================================================================================================ wgrad
-static constexpr size_t kPartBytes = static_cast<size_t>(256 + 64) * 160 * 256 * 4;      // <= one round of 160x256 f32 tiles
-
 extern "C" size_t cmh_linear_wgrad_workspace_bytes(int32_t dtype, int32_t M, int32_t O, int32_t I) {
   if (M <= 0 || O <= 0 || I <= 0) return 0;
   const size_t e = dtype == CMH_BF16 ? 2 : 4, mp = pad64(static_cast<size_t>(M));
@@ -560,67 +608,63 @@ extern "C" int cmh_linear_wgrad(int32_t dtype, const void* dy, int32_t dy_kind, 
   return wgrad_core(dtype, dy, dy_kind, O, x, x_kind, I, M, dw, db, w, st);
 }
 
-// ---- all-token head (MITH trunk, model/MITH.py:70-80,136-139): tokens = LN(x_last, every row) . proj ---------------------------
-// forward: the normalised rows go through t.dxe (free during the forward pass)
-int tokens_head_forward(int dt, int xh, const TrainBufs& t, const float* ln_w, const float* ln_b, const void* proj_t, float* tokens_out,
-                        int M, int d, int E, hipStream_t st) {
+// ================================================================================================================ heads
+// forward of either head over `rows` rows: out = LN(x_last, rows gathered by `gather` if given) . proj, the normalised rows through
+// `normed`.  All-token head (MITH trunk, model/MITH.py:70-80,136-139): every row, through t.dxe (free during the forward pass);
+// pooled head: the B pooled rows (tail: the last block left only those in x_last), through t.pool, which the backward reads.
+static int head_forward(const TrainDims& D, const TrainBufs& t, const Head& h, const int32_t* gather, void* normed, float* out, int rows,
+                        hipStream_t st) {
   int rc;
-  if ((rc = launch_layernorm_x(t.x_last, xh, nullptr, ln_w, ln_b, t.dxe, dt == CMH_BF16, M, d, st))) return rc;
-  return final_projection(dt, t.dxe, proj_t, tokens_out, M, E, d, st);
+  if ((rc = launch_layernorm_x(t.x_last, D.xh, gather, h.ln_w, h.ln_b, normed, D.dt == CMH_BF16, rows, D.d, st))) return rc;
+  return final_projection(D.dt, normed, h.proj_t, out, rows, D.E, D.d, st);
 }
-// backward: dproj (reference layout [d, E]) = (dtok^T h)^T, dh = dtok . proj_t, then LayerNorm backward over every row into t.dx
+// all-token head, backward: dproj (reference layout [d, E]) = (dtok^T h)^T, dh = dtok . proj_t, then LayerNorm backward over every row into t.dx
 // (+ its bf16 operand copy in t.dxe).  Scratch: h in t.dxe, dtok operand in t.tokE, dproj^T in t.projT.
-int tokens_head_backward(int dt, int xh, TrainBufs& t, const float* ln_w, const float* ln_b, const void* proj_t, const float* dtok,
-                         float* dproj, float* dln_w, float* dln_b, int M, int d, int E, hipStream_t st) {
+static int tokens_head_backward(const TrainDims& D, TrainBufs& t, const Head& h, const float* dtok, int M, hipStream_t st) {
+  const int dt = D.dt, d = D.d, E = D.E;
   int rc;
-  if ((rc = launch_layernorm_x(t.x_last, xh, nullptr, ln_w, ln_b, t.dxe, dt == CMH_BF16, M, d, st))) return rc;     // h again
-  float* dprojT = t.projT;
-  if ((rc = wgrad(dt, dtok, kF32, E, t.dxe, ekind(dt), d, M, dprojT, nullptr, t, st))) return rc;                     // [E, d]
-  if ((rc = launch_transpose(dprojT, kF32, dproj, kF32, E, d, E, st))) return rc;                                      // -> [d, E]
-  const void* dtok_e = nullptr;
-  if ((rc = as_gemm_operand(dt, dtok, t.tokE, static_cast<size_t>(M) * E, st, &dtok_e))) return rc;
-  const int obf = dt == CMH_BF16 ? EPI_OUT_BF16 : 0;
-  if ((rc = dgrad(dt, dtok_e, proj_t, E, d, M, nullptr, t.dh, obf, t, st))) return rc;
-  return launch_layernorm_backward(t.x_last, xkind(xh), t.dh, ekind(dt), ln_w, nullptr, M, d, t.dx, 0, dln_w, dln_b, t.red, t.red_bytes,
-                                   st, dt == CMH_BF16 ? t.dxe : nullptr);
+  if ((rc = launch_layernorm_x(t.x_last, D.xh, nullptr, h.ln_w, h.ln_b, t.dxe, dt == CMH_BF16, M, d, st))) return rc;   // h again
+  if ((rc = wgrad(dt, dtok, kF32, E, t.dxe, ekind(dt), d, M, t.projT, nullptr, t, st))) return rc;                    // [E, d]
+  if ((rc = launch_transpose(t.projT, kF32, h.dproj, kF32, E, d, E, st))) return rc;                                   // -> [d, E]
+  const void* dtok_e = dt == CMH_BF16 ? t.tokE : static_cast<const void*>(dtok);      // dtok as a GEMM operand (f32 mode: itself)
+  if (dt == CMH_BF16 && (rc = cmh_cast_f32_to_bf16(dtok, t.tokE, static_cast<int64_t>(M) * E, st))) return rc;
+  if ((rc = launch_transpose(h.proj_t, ekind(dt), t.wT, ekind(dt), E, d, E, st))) return rc;                           // proj [d, E]
+  if ((rc = launch_gemm(dt, dtok_e, t.wT, nullptr, nullptr, t.dh, M, d, E, dt == CMH_BF16 ? EPI_OUT_BF16 : 0, st))) return rc;
+  return launch_layernorm_backward(t.x_last, xkind(D.xh), t.dh, ekind(dt), h.ln_w, nullptr, M, d, t.dx, 0, h.dln_w, h.dln_b, t.red,
+                                   t.red_bytes, st, dt == CMH_BF16 ? t.dxe : nullptr);
+}
+// either head's backward over a gradient stream of M rows: dtokens [M, E] (all-token) or dfeat [B, E] (pooled; tail: pooled_backward)
+static int head_backward(const TrainDims& D, TrainBufs& t, const Head& h, const float* dfeat, const float* dtokens, int M, bool tail, hipStream_t st) {
+  return dtokens ? tokens_head_backward(D, t, h, dtokens, M, st) : pooled_backward(D, t, h, dfeat, M, tail, st);
 }
 
 // ================================================================================================================ vision
 extern "C" size_t cmh_vit_train_bytes(const cmh_vit_weights* w, int32_t batch) {
-  if (!w || batch <= 0 || w->patch <= 0) return 0;
-  const size_t g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, d = w->width, B = batch;
-  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = resid_f16(w->gemm_dtype, w->width) ? 2 : 4;
-  const int pkp = conv1_k(w->patch, w->gemm_dtype);
-  return carve_train(nullptr, B * T, B, d, e, xs, w->layers, B * g2, pkp, w->embed_dim, pkp != 3 * w->patch * w->patch).total;
+  return !w || batch <= 0 || w->patch <= 0 ? 0 : carve_train(nullptr, TrainDims(w, batch)).total;
 }
 
 static int vit_forward_train_impl(const cmh_vit_weights* w, const float* image, int32_t batch, float* feat, float* tokens_out,
                                   void* tape, size_t tape_bytes, void* stream) {
   CMH_CHECK_ARG(w && image && (feat || tokens_out) && tape && batch > 0, "vit_forward_train: bad arguments");
-  int rc = check_train_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
+  const TrainDims D(w, batch);      // D.pkp != D.pk: the K-padded conv1 (encoders.hip: vit_begin)
+  int rc = check_train_tower(D, w->blocks);
   if (rc) return rc;
   CMH_CHECK_ARG(w->layers > 0, "vit_forward_train: no layers");
   CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0, "vit_forward_train: resolution / patch");
-  const int dt = w->gemm_dtype, d = w->width, B = batch;
-  const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T, pk = 3 * w->patch * w->patch;
-  const int pkp = conv1_k(w->patch, dt);      // pkp != pk: the K-padded conv1 (encoders.hip: vit_begin)
-  if (tape_bytes < cmh_vit_train_bytes(w, batch)) return fail(CMH_ERR_WORKSPACE, "vit_forward_train: tape too small");
-  CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "vit_forward_train: tape must be 256-byte aligned");
-  const int xh = resid_f16(dt, d);
-  const size_t e = dt == CMH_BF16 ? 2 : 4;
+  TrainBufs t;
+  if ((rc = open_tape("vit_forward_train", D, tape, tape_bytes, /*need_aligned=*/true, &t))) return rc;
+  const int B = D.B, T = D.T, M = D.M, d = D.d;
+  const Head head{w->ln_post_w, w->ln_post_b, w->proj_t};
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, w->embed_dim,
-                            pkp != pk);
-  if ((rc = conv1_stem(w, dt, image, nullptr, 0, B, t.patches, t.conv1_w, t.patch_out, st))) return rc;
+  if ((rc = conv1_stem(w, D.dt, image, nullptr, 0, B, t.patches, t.conv1_w, t.patch_out, st))) return rc;
   // x_pre = [cls ; patches] + positional (kept for ln_pre's backward), x_0 = ln_pre(x_pre)
-  if ((rc = launch_vit_assemble(t.patch_out, w->class_embedding, w->positional_embedding, t.x_pre, B, g2, d, st))) return rc;
-  if ((rc = launch_layernorm_any(t.x_pre, kF32, nullptr, w->ln_pre_w, w->ln_pre_b, t.L[0].x_in, xkind(xh), M, d, st))) return rc;
+  if ((rc = launch_vit_assemble(t.patch_out, w->class_embedding, w->positional_embedding, t.x_pre, B, T - 1, d, st))) return rc;
+  if ((rc = launch_layernorm_any(t.x_pre, kF32, nullptr, w->ln_pre_w, w->ln_pre_b, t.L[0].x_in, xkind(D.xh), M, d, st))) return rc;
   const bool tail = !tokens_out && train_pooled_tail();      // the same rule in vit_backward_impl
   if ((rc = launch_iota_rows(t.rows, B, T, st))) return rc;
-  if ((rc = tape_forward(train_lane(dt, xh, B, T, d, 0, nullptr, M, nullptr), w->blocks, w->layers, t, tail ? t.rows : nullptr, st))) return rc;
-  if (tokens_out) return tokens_head_forward(dt, xh, t, w->ln_post_w, w->ln_post_b, w->proj_t, tokens_out, M, d, w->embed_dim, st);
-  if ((rc = launch_layernorm_x(t.x_last, xh, tail ? nullptr : t.rows, w->ln_post_w, w->ln_post_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
-  return final_projection(dt, t.pool, w->proj_t, feat, B, w->embed_dim, d, st);
+  if ((rc = tape_forward(BlockRun{D, w->blocks, t, st, M, /*causal=*/0, nullptr, nullptr, tail}))) return rc;
+  if (tokens_out) return head_forward(D, t, head, nullptr, t.dxe, tokens_out, M, st);
+  return head_forward(D, t, head, tail ? nullptr : t.rows, t.pool, feat, B, st);
 }
 
 extern "C" int cmh_vit_forward_train(const cmh_vit_weights* w, const float* image, int32_t batch, float* feat, void* tape,
@@ -642,36 +686,22 @@ extern "C" int cmh_vit_forward_train_tokens(const cmh_vit_weights* w, const floa
 static int vit_backward_impl(const cmh_vit_weights* w, int32_t batch, const float* dfeat, const float* dtokens, const cmh_vit_grads* gr,
                              void* tape, size_t tape_bytes, void* stream, int layer_hi = -1, int layer_lo = 0) {
   CMH_CHECK_ARG(w && (dfeat || dtokens) && gr && tape && batch > 0, "vit_backward: bad arguments");
-  if (layer_hi < 0) layer_hi = w->layers;
-  CMH_CHECK_ARG(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= w->layers, "vit_backward: layers [%d, %d) of %d", layer_lo, layer_hi, w->layers);
-  int rc = check_train_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
+  const TrainDims D(w, batch);
+  const bool head_grads = gr->conv1_w && gr->class_embedding && gr->positional_embedding && gr->ln_pre_w && gr->ln_pre_b && gr->ln_post_w &&
+                          gr->ln_post_b && gr->proj;
+  TrainBufs t;
+  int rc = open_backward("vit_backward", D, w->blocks, head_grads, gr->blocks, tape, tape_bytes, &layer_hi, layer_lo, &t);
   if (rc) return rc;
-  CMH_CHECK_ARG(gr->conv1_w && gr->class_embedding && gr->positional_embedding && gr->ln_pre_w && gr->ln_pre_b && gr->ln_post_w &&
-                gr->ln_post_b && gr->proj && gr->blocks, "vit_backward: null gradient pointer");
-  if ((rc = check_block_grads(gr->blocks, w->layers))) return rc;
-  if (tape_bytes < cmh_vit_train_bytes(w, batch)) return fail(CMH_ERR_WORKSPACE, "vit_backward: tape too small");
-  const int dt = w->gemm_dtype, d = w->width, B = batch, E = w->embed_dim;
-  const int g = w->resolution / w->patch, g2 = g * g, T = g2 + 1, M = B * T, pk = 3 * w->patch * w->patch;
-  const int pkp = conv1_k(w->patch, dt);
-  const int xh = resid_f16(dt, d);
-  const size_t e = dt == CMH_BF16 ? 2 : 4;
+  const int dt = D.dt, B = D.B, T = D.T, M = D.M, d = D.d, g2 = T - 1, pk = D.pk, pkp = D.pkp;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, static_cast<size_t>(B) * g2, pkp, E, pkp != pk);
-  const bool tail = !dtokens && train_pooled_tail();
+  BlockRun run{D, w->blocks, t, st, M};
+  run.tail = !dtokens && train_pooled_tail();
   if (layer_hi == w->layers) {
     if ((rc = zero_pad_buffers(t, static_cast<size_t>(M), st))) return rc;
-    if (dtokens) {
-      if ((rc = tokens_head_backward(dt, xh, t, w->ln_post_w, w->ln_post_b, w->proj_t, dtokens, gr->proj, gr->ln_post_w, gr->ln_post_b, M, d,
-                                     E, st))) return rc;
-    } else if ((rc = pooled_backward(dt, xh, t.x_last, t.rows, t.pool, w->proj_t, w->ln_post_w, dfeat, gr->proj, gr->ln_post_w,
-                                     gr->ln_post_b, t, B, M, d, E, st, tail))) return rc;
+    if ((rc = head_backward(D, t, Head{w->ln_post_w, w->ln_post_b, w->proj_t, gr->proj, gr->ln_post_w, gr->ln_post_b}, dfeat, dtokens, M,
+                            run.tail, st))) return rc;
   }
-  for (int i = layer_hi - 1; i >= layer_lo; --i) {
-    const bool last = i == w->layers - 1;
-    if ((rc = block_backward(w->blocks[i], grads_of(gr->blocks[i]), dt, xh, t.L[i], t, B, T, d, 0, nullptr, st,
-                             !last || dtokens != nullptr, -1, nullptr, tail && last ? t.rows : nullptr, tail && last ? t.dx2 : nullptr,
-                             /*keep_f32=*/i == 0))) return rc;
-  }
+  if ((rc = blocks_backward(run, gr->blocks, layer_hi, layer_lo, dtokens != nullptr))) return rc;
   if (layer_lo > 0) return CMH_OK;
   // ln_pre, then the embeddings: x_pre[b,0] = cls + pos[0], x_pre[b,1+i] = patch_out[b*g2+i] + pos[1+i]
   if ((rc = launch_layernorm_backward(t.x_pre, kF32, t.dx, kF32, w->ln_pre_w, nullptr, M, d, t.dx2, 0, gr->ln_pre_w, gr->ln_pre_b,
@@ -719,49 +749,52 @@ extern "C" int cmh_vit_backward_tokens(const cmh_vit_weights* w, int32_t batch, 
 // it here, keyed by the tape's address, so that the backward call(s) on the same tape need no stream synchronisation of their own.
 namespace {
 std::mutex g_tape_rows_mu;
-std::unordered_map<const void*, int> g_tape_rows;
-std::vector<const void*> g_tape_order;                    // insertion order: the OLDEST entry goes when the table is full
+struct { const void* tape; int rows; } g_tape_rows[64];      // a ring: the OLDEST entry goes when a new tape comes - tapes of long-gone
+size_t g_tape_next = 0;                                       // steps; a forward's entry outlives the 63 forwards after it
 void remember_tape_rows(const void* tape, int rows) {
   std::lock_guard<std::mutex> lk(g_tape_rows_mu);
-  if (g_tape_rows.find(tape) == g_tape_rows.end()) {
-    if (g_tape_order.size() >= 64) {                      // tapes of long-gone steps; a forward's entry outlives the 63 forwards after it
-      g_tape_rows.erase(g_tape_order.front());
-      g_tape_order.erase(g_tape_order.begin());
-    }
-    g_tape_order.push_back(tape);
-  }
-  g_tape_rows[tape] = rows;
+  for (auto& e : g_tape_rows)
+    if (e.tape == tape) { e.rows = rows; return; }
+  g_tape_rows[g_tape_next++ % 64] = {tape, rows};
 }
 int recall_tape_rows(const void* tape) {
   std::lock_guard<std::mutex> lk(g_tape_rows_mu);
-  const auto it = g_tape_rows.find(tape);
-  return it == g_tape_rows.end() ? -1 : it->second;
+  for (const auto& e : g_tape_rows)
+    if (e.tape == tape) return e.rows;
+  return -1;
+}
+// The packed row count of a tape for the call `what`: the count the forward call remembered (no synchronisation here); for a tape this
+// process did not fill (or tape == nullptr: the forward call itself) a synchronous read-back of the plan's seq_off[B]; then the range
+// check.  dense_ok: 0 is an answer too - an all-token tape filled densely (its forward remembered 0 and zeroed seq_off).
+int tape_packed_rows(const char* what, const void* tape, const TrainBufs& t, const TrainDims& D, bool dense_ok, hipStream_t st, int* rows) {
+  int32_t total = tape ? recall_tape_rows(tape) : -1;
+  if (total < 0 && (hipMemcpyAsync(&total, t.seq_off + D.B, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+    return fail(CMH_ERR_LAUNCH, "%s: reading the packed row count failed", what);
+  CMH_CHECK_ARG(total >= (dense_ok ? 0 : 1) && total <= D.M, "%s: the tape holds a bad packed row count %d (of %d rows)", what, total, D.M);
+  *rows = total;
+  return CMH_OK;
 }
 }  // namespace
 
 extern "C" size_t cmh_text_train_bytes(const cmh_text_weights* w, int32_t batch, int32_t seq_len) {
-  if (!w || batch <= 0 || seq_len <= 0) return 0;
-  const size_t e = w->gemm_dtype == CMH_BF16 ? 2 : 4, xs = resid_f16(w->gemm_dtype, w->width) ? 2 : 4;
-  return carve_train(nullptr, static_cast<size_t>(batch) * seq_len, batch, w->width, e, xs, w->layers, 0, 0, w->embed_dim).total;
+  return !w || batch <= 0 || seq_len <= 0 ? 0 : carve_train(nullptr, TrainDims(w, batch, seq_len)).total;
 }
 
 static int text_forward_train_impl(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
                                    const uint8_t* key_padding_mask, float* feat, float* tokens_out, int32_t* eot_rows_out, void* tape,
                                    size_t tape_bytes, void* stream, bool pack_tokens_req = false) {
   CMH_CHECK_ARG(w && tokens && (feat || tokens_out) && tape && batch > 0 && seq_len > 0, "text_forward_train: bad arguments");
-  int rc = check_train_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
+  const TrainDims D(w, batch, seq_len);
+  int rc = check_train_tower(D, w->blocks);
   if (rc) return rc;
   CMH_CHECK_ARG(w->layers > 0 && seq_len <= w->context_length, "text_forward_train: layers / seq_len");
-  if (tape_bytes < cmh_text_train_bytes(w, batch, seq_len)) return fail(CMH_ERR_WORKSPACE, "text_forward_train: tape too small");
-  CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "text_forward_train: tape must be 256-byte aligned");
-  const int dt = w->gemm_dtype, d = w->width, B = batch, L = seq_len, M = B * L;
-  const int xh = resid_f16(dt, d);
-  const size_t e = dt == CMH_BF16 ? 2 : 4;
+  TrainBufs t;
+  if ((rc = open_tape("text_forward_train", D, tape, tape_bytes, /*need_aligned=*/true, &t))) return rc;
+  const int dt = D.dt, xh = D.xh, B = D.B, L = D.T, M = D.M, d = D.d;
+  const Head head{w->ln_final_w, w->ln_final_b, w->text_projection_t};
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, 0, 0, w->embed_dim);
-  // packed like encode_text (encoders.hip): only the tokens 0..EOT of every caption are run through the blocks
-  const int32_t* seq_off = nullptr;
-  int rows = M;
+  // packed like encode_text (encoders.hip): only the tokens 0..EOT of every caption are run through the blocks (run.M of them)
+  BlockRun run{D, w->blocks, t, st, M, /*causal=*/1, key_padding_mask};
   // the all-token trunk (MITH): packed only on the caller's word that the padded positions of tokens_out are read by nobody
   // (cmh_text_forward_train_tokens_packed; encoders.hip text_begin has the reasoning) - their gradient is then exactly zero as well
   const int bk0 = dt == CMH_F32 ? 32 : 64;
@@ -769,32 +802,27 @@ static int text_forward_train_impl(const cmh_text_weights* w, const int64_t* tok
   if (tokens_out && !pack_tokens) remember_tape_rows(tape, 0);      // 0: this tape's all-token head is dense (text_backward_impl)
   if ((!tokens_out && text_packing(key_padding_mask)) || pack_tokens) {
     if ((rc = launch_text_pack_plan(tokens, B, L, t.seq_off, st, pack_tokens ? key_padding_mask : nullptr, pack_tokens ? t.rows : nullptr))) return rc;
-    int32_t total = 0;
-    if (hipMemcpyAsync(&total, t.seq_off + B, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return fail(CMH_ERR_LAUNCH, "text_forward_train: reading the packed row count failed");
-    CMH_CHECK_ARG(total > 0 && total <= M, "text_forward_train: bad packed row count %d", total);
-    seq_off = t.seq_off;
-    rows = total;
-    remember_tape_rows(tape, rows);
+    // the producer of the count: its own read (tape = nullptr: nothing to recall), through the check every reader applies
+    if ((rc = tape_packed_rows("text_forward_train", nullptr, t, D, /*dense_ok=*/false, st, &run.M))) return rc;
+    run.seq_off = t.seq_off;
+    remember_tape_rows(tape, run.M);
   }
   if ((rc = launch_text_embed_packed(tokens, w->token_embedding, w->positional_embedding, t.L[0].x_in, xh, t.rows, B, L, d,
-                                     w->vocab_size, seq_off, st, pack_tokens))) return rc;
+                                     w->vocab_size, run.seq_off, st, pack_tokens))) return rc;
   // (the gathered attention rows are parked behind the first B rows of the h2 slot: the pooled tail needs 2 B rows of tape there)
-  const bool tail = !tokens_out && train_pooled_tail() && rows >= 2 * B;      // the same rule in text_backward_impl
-  if ((rc = tape_forward(train_lane(dt, xh, B, L, d, 1, key_padding_mask, rows, seq_off), w->blocks, w->layers, t, tail ? t.rows : nullptr,
-                         st))) return rc;
+  run.tail = !tokens_out && train_pooled_tail() && run.M >= 2 * B;      // the same rule in text_backward_impl
+  if ((rc = tape_forward(run))) return rc;
   if (tokens_out && pack_tokens) {
-    if ((rc = tokens_head_forward(dt, xh, t, w->ln_final_w, w->ln_final_b, w->text_projection_t, t.tokP, rows, d, w->embed_dim, st))) return rc;
+    if ((rc = head_forward(D, t, head, nullptr, t.dxe, t.tokP, run.M, st))) return rc;
     return launch_unpack_token_rows(t.tokP, t.seq_off, tokens_out, B, L, w->embed_dim, t.rows, eot_rows_out, st);
   }
   if (tokens_out) {
     if (eot_rows_out && hipMemcpyAsync(eot_rows_out, t.rows, static_cast<size_t>(B) * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "text_forward_train_tokens: eot row copy failed");
     if (hipMemsetAsync(t.seq_off, 0, static_cast<size_t>(B + 1) * 4, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "text_forward_train_tokens: memset failed");
-    return tokens_head_forward(dt, xh, t, w->ln_final_w, w->ln_final_b, w->text_projection_t, tokens_out, M, d, w->embed_dim, st);
+    return head_forward(D, t, head, nullptr, t.dxe, tokens_out, M, st);
   }
-  if ((rc = launch_layernorm_x(t.x_last, xh, tail ? nullptr : t.rows, w->ln_final_w, w->ln_final_b, t.pool, dt == CMH_BF16, B, d, st))) return rc;
-  return final_projection(dt, t.pool, w->text_projection_t, feat, B, w->embed_dim, d, st);
+  return head_forward(D, t, head, run.tail ? nullptr : t.rows, t.pool, feat, B, st);
 }
 
 extern "C" int cmh_text_forward_train(const cmh_text_weights* w, const int64_t* tokens, int32_t batch, int32_t seq_len,
@@ -822,67 +850,42 @@ static int text_backward_impl(const cmh_text_weights* w, const int64_t* tokens, 
                               const uint8_t* key_padding_mask, const float* dfeat, const float* dtokens, const cmh_text_grads* gr,
                               void* tape, size_t tape_bytes, void* stream, int layer_hi = -1, int layer_lo = 0) {   // parts: see vit_backward_impl
   CMH_CHECK_ARG(w && tokens && (dfeat || dtokens) && gr && tape && batch > 0 && seq_len > 0, "text_backward: bad arguments");
-  if (layer_hi < 0) layer_hi = w->layers;
-  CMH_CHECK_ARG(0 <= layer_lo && layer_lo <= layer_hi && layer_hi <= w->layers, "text_backward: layers [%d, %d) of %d", layer_lo, layer_hi, w->layers);
-  int rc = check_train_tower(w->gemm_dtype, w->width, w->layers, w->embed_dim, w->blocks);
+  const TrainDims D(w, batch, seq_len);
+  const bool head_grads = gr->token_embedding && gr->positional_embedding && gr->ln_final_w && gr->ln_final_b && gr->text_projection;
+  TrainBufs t;
+  int rc = open_backward("text_backward", D, w->blocks, head_grads, gr->blocks, tape, tape_bytes, &layer_hi, layer_lo, &t);
   if (rc) return rc;
-  CMH_CHECK_ARG(gr->token_embedding && gr->positional_embedding && gr->ln_final_w && gr->ln_final_b && gr->text_projection &&
-                gr->blocks, "text_backward: null gradient pointer");
-  if ((rc = check_block_grads(gr->blocks, w->layers))) return rc;
-  if (tape_bytes < cmh_text_train_bytes(w, batch, seq_len)) return fail(CMH_ERR_WORKSPACE, "text_backward: tape too small");
-  const int dt = w->gemm_dtype, d = w->width, B = batch, L = seq_len, M = B * L, E = w->embed_dim;
-  const int xh = resid_f16(dt, d);
-  const size_t e = dt == CMH_BF16 ? 2 : 4;
+  const int B = D.B, L = D.T, M = D.M, d = D.d, E = D.E;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, static_cast<size_t>(M), B, d, e, xh ? 2 : 4, w->layers, 0, 0, E);
-  const int32_t* seq_off = nullptr;
-  int rows = M;
-  if (!dtokens && text_packing(key_padding_mask)) {       // same rule as the forward call that filled this tape
-    int32_t total = recall_tape_rows(tape);                // remembered by the forward call (no synchronisation here)
-    if (total < 0) {                                       // a tape this process did not fill: read the count back
-      if (hipMemcpyAsync(&total, t.seq_off + B, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(CMH_ERR_LAUNCH, "text_backward: reading the packed row count failed");
-    }
-    CMH_CHECK_ARG(total > 0 && total <= M, "text_backward: the tape holds no packed plan (row count %d)", total);
-    seq_off = t.seq_off;
-    rows = total;
+  BlockRun run{D, w->blocks, t, st, M, /*causal=*/1, key_padding_mask};
+  // Is the tape packed?  Pooled head: by the forward call's own rule.  All-token head: a tape that
+  // cmh_text_forward_train_tokens_packed filled holds a packed plan, a dense one the count 0.
+  if (dtokens || text_packing(key_padding_mask)) {
+    int total = 0;
+    if ((rc = tape_packed_rows(dtokens ? "text_backward_tokens" : "text_backward", tape, t, D, /*dense_ok=*/dtokens != nullptr, st, &total)))
+      return rc;
+    if (total > 0) { run.seq_off = t.seq_off; run.M = total; }
   }
-  if (dtokens) {       // a tape that cmh_text_forward_train_tokens_packed filled holds a packed plan: the forward call remembered its row
-                       // count (0 for a dense tape, whose forward also zeroed seq_off); a tape this process does not remember is asked
-    int32_t total = recall_tape_rows(tape);
-    if (total < 0 && (hipMemcpyAsync(&total, t.seq_off + B, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-      return fail(CMH_ERR_LAUNCH, "text_backward_tokens: reading the packed row count failed");
-    CMH_CHECK_ARG(total >= 0 && total <= M, "text_backward_tokens: the tape holds a bad packed row count %d", total);
-    if (total > 0) { seq_off = t.seq_off; rows = total; }
-  }
-  const bool tail = !dtokens && train_pooled_tail() && rows >= 2 * B;
+  run.tail = !dtokens && train_pooled_tail() && run.M >= 2 * B;
   if (layer_hi == w->layers) {
-    if ((rc = zero_pad_buffers(t, static_cast<size_t>(rows), st))) return rc;
-    if (dtokens) {
-      const float* dtok = dtokens;
-      if (seq_off) {   // the kept rows of the dense [B, L, E] gradient (the padded rows' gradient is zero by the caller's promise)
-        if ((rc = launch_pack_token_rows(dtokens, seq_off, t.tokP, B, L, E, st))) return rc;
-        dtok = t.tokP;
-      }
-      if ((rc = tokens_head_backward(dt, xh, t, w->ln_final_w, w->ln_final_b, w->text_projection_t, dtok, gr->text_projection,
-                                     gr->ln_final_w, gr->ln_final_b, rows, d, E, st))) return rc;
-    } else if ((rc = pooled_backward(dt, xh, t.x_last, t.rows, t.pool, w->text_projection_t, w->ln_final_w, dfeat, gr->text_projection,
-                                     gr->ln_final_w, gr->ln_final_b, t, B, rows, d, E, st, tail))) return rc;
+    if ((rc = zero_pad_buffers(t, static_cast<size_t>(run.M), st))) return rc;
+    const float* dtok = dtokens;
+    if (dtokens && run.seq_off) {   // the kept rows of the dense [B, L, E] gradient (the padded rows' gradient is zero by the caller's promise)
+      if ((rc = launch_pack_token_rows(dtokens, run.seq_off, t.tokP, B, L, E, st))) return rc;
+      dtok = t.tokP;
+    }
+    if ((rc = head_backward(D, t, Head{w->ln_final_w, w->ln_final_b, w->text_projection_t, gr->text_projection, gr->ln_final_w, gr->ln_final_b},
+                            dfeat, dtok, run.M, run.tail, st))) return rc;
   }
-  for (int i = layer_hi - 1; i >= layer_lo; --i) {
-    const bool last = i == w->layers - 1;
-    if ((rc = block_backward(w->blocks[i], grads_of(gr->blocks[i]), dt, xh, t.L[i], t, B, L, d, 1, key_padding_mask, st,
-                             !last || dtokens != nullptr, rows, seq_off, tail && last ? t.rows : nullptr, tail && last ? t.dx2 : nullptr,
-                             /*keep_f32=*/i == 0))) return rc;
-  }
+  if ((rc = blocks_backward(run, gr->blocks, layer_hi, layer_lo, dtokens != nullptr))) return rc;
   if (layer_lo > 0) return CMH_OK;
   // x_0[b, t] = token_embedding[tokens[b, t]] + positional_embedding[t]
   if (hipMemsetAsync(gr->positional_embedding, 0, static_cast<size_t>(w->context_length) * d * 4, st) != hipSuccess ||
       hipMemsetAsync(gr->token_embedding, 0, static_cast<size_t>(w->vocab_size) * d * 4, st) != hipSuccess)
     return fail(CMH_ERR_LAUNCH, "text_backward: memset failed");
-  if (seq_off) {
-    hipLaunchKernelGGL(packed_dpos_kernel, dim3(L, (d + 255) / 256), dim3(256), 0, st, t.dx, seq_off, B, d, gr->positional_embedding);
-    hipLaunchKernelGGL(packed_embed_scatter_kernel, dim3(M), dim3(256), 0, st, tokens, t.dx, seq_off, gr->token_embedding, B, L, d,
+  if (run.seq_off) {
+    hipLaunchKernelGGL(packed_dpos_kernel, dim3(L, (d + 255) / 256), dim3(256), 0, st, t.dx, run.seq_off, B, d, gr->positional_embedding);
+    hipLaunchKernelGGL(packed_embed_scatter_kernel, dim3(M), dim3(256), 0, st, tokens, t.dx, run.seq_off, gr->token_embedding, B, L, d,
                        w->vocab_size);
   } else {
     if ((rc = cmh_colsum(t.dx, kF32, B, L * d, gr->positional_embedding, t.red, t.red_bytes, st))) return rc;
@@ -913,29 +916,26 @@ extern "C" int cmh_text_backward_tokens(const cmh_text_weights* w, const int64_t
   return text_backward_impl(w, tokens, batch, seq_len, key_padding_mask, nullptr, dtokens, gr, tape, tape_bytes, stream);
 }
 
-
 // ================================================================================================ a bare stack of blocks
 // MITH's concept transformer (model/MITH.py:379-396: 2 ResidualAttentionBlocks over the K "concept tokens" of every sample, no
 // mask) under training: f32 residual stream in and out, GEMM operands in `dtype`.
 extern "C" size_t cmh_blocks_train_bytes(int32_t dtype, int32_t B, int32_t T, int32_t d, int32_t layers) {
-  if (B <= 0 || T <= 0 || d <= 0 || layers <= 0) return 0;
-  const size_t e = dtype == CMH_BF16 ? 2 : 4;
-  return carve_train(nullptr, static_cast<size_t>(B) * T, B, d, e, 4, layers, 0, 0, 4).total;
+  return B <= 0 || T <= 0 || d <= 0 || layers <= 0 ? 0 : carve_train(nullptr, TrainDims(dtype, B, T, d, layers)).total;
 }
 
 extern "C" int cmh_blocks_forward_train(const cmh_block_weights* blocks, int32_t layers, int32_t dtype, const float* x, float* y,
                                         int32_t B, int32_t T, int32_t d, void* tape, size_t tape_bytes, void* stream) {
   CMH_CHECK_ARG(blocks && x && y && tape && layers > 0 && B > 0 && T > 0, "blocks_forward_train: bad arguments");
-  int rc = check_train_tower(dtype, d, layers, 4, blocks);
+  const TrainDims D(dtype, B, T, d, layers);
+  int rc = check_train_tower(D, blocks);
   if (rc) return rc;
-  if (tape_bytes < cmh_blocks_train_bytes(dtype, B, T, d, layers)) return fail(CMH_ERR_WORKSPACE, "blocks_forward_train: tape too small");
-  CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(tape) & 255) == 0, "blocks_forward_train: tape must be 256-byte aligned");
-  const size_t M = static_cast<size_t>(B) * T, e = dtype == CMH_BF16 ? 2 : 4;
+  TrainBufs t;
+  if ((rc = open_tape("blocks_forward_train", D, tape, tape_bytes, /*need_aligned=*/true, &t))) return rc;
+  const size_t bytes = static_cast<size_t>(D.M) * d * 4;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, M, B, d, e, 4, layers, 0, 0, 4);
-  if (hipMemcpyAsync(t.L[0].x_in, x, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
-  if ((rc = tape_forward(train_lane(dtype, /*xh=*/0, B, T, d, 0, nullptr, B * T, nullptr), blocks, layers, t, nullptr, st))) return rc;
-  if (hipMemcpyAsync(y, t.x_last, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
+  if (hipMemcpyAsync(t.L[0].x_in, x, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
+  if ((rc = tape_forward(BlockRun{D, blocks, t, st, D.M}))) return rc;
+  if (hipMemcpyAsync(y, t.x_last, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_forward_train: copy failed");
   return CMH_OK;
 }
 
@@ -943,18 +943,15 @@ extern "C" int cmh_blocks_backward(const cmh_block_weights* blocks, const cmh_bl
                                    const float* dy, float* dx, int32_t B, int32_t T, int32_t d, void* tape, size_t tape_bytes,
                                    void* stream) {
   CMH_CHECK_ARG(blocks && grads && dy && dx && tape && layers > 0 && B > 0 && T > 0, "blocks_backward: bad arguments");
-  int rc = check_train_tower(dtype, d, layers, 4, blocks);
+  const TrainDims D(dtype, B, T, d, layers);
+  TrainBufs t;
+  int hi = layers, rc = open_backward("blocks_backward", D, blocks, /*head_grads=*/true, grads, tape, tape_bytes, &hi, 0, &t);
   if (rc) return rc;
-  if ((rc = check_block_grads(grads, layers))) return rc;
-  if (tape_bytes < cmh_blocks_train_bytes(dtype, B, T, d, layers)) return fail(CMH_ERR_WORKSPACE, "blocks_backward: tape too small");
-  const size_t M = static_cast<size_t>(B) * T, e = dtype == CMH_BF16 ? 2 : 4;
+  const size_t bytes = static_cast<size_t>(D.M) * d * 4;
   hipStream_t st = as_stream(stream);
-  TrainBufs t = carve_train(tape, M, B, d, e, 4, layers, 0, 0, 4);
-  if ((rc = zero_pad_buffers(t, M, st))) return rc;
-  if (hipMemcpyAsync(t.dx, dy, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_backward: copy failed");
-  for (int i = layers - 1; i >= 0; --i)
-    if ((rc = block_backward(blocks[i], grads_of(grads[i]), dtype, /*xh=*/0, t.L[i], t, B, T, d, 0, nullptr, st, i != layers - 1, -1, nullptr,
-                             nullptr, nullptr, /*keep_f32=*/i == 0))) return rc;
-  if (hipMemcpyAsync(dx, t.dx, M * d * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_backward: copy failed");
+  if ((rc = zero_pad_buffers(t, static_cast<size_t>(D.M), st))) return rc;
+  if (hipMemcpyAsync(t.dx, dy, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_backward: copy failed");
+  if ((rc = blocks_backward(BlockRun{D, blocks, t, st, D.M}, grads, layers, 0, /*dtokens_head=*/false))) return rc;
+  if (hipMemcpyAsync(dx, t.dx, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "blocks_backward: copy failed");
   return CMH_OK;
 }

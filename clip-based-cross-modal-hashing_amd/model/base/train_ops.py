@@ -94,6 +94,14 @@ def _block_grads(grads, nhead):
     return arr
 
 
+def _grad_call(params, nhead, struct, order=None):
+    """What every backward bridge sets up: the flat buffer and its views, the block array (returned to be kept alive) and the
+    tower's gradient struct over them -> (grads, flat, blocks, struct)"""
+    grads, flat = _grad_buffers(params, order)
+    blocks = _block_grads(grads, nhead)
+    return grads, flat, blocks, struct(*[t.data_ptr() for t in grads[:nhead]], C.cast(blocks, C.POINTER(N.BlockGrads)))
+
+
 class VitTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, clip, image, *params):
@@ -112,9 +120,7 @@ class VitTrain(torch.autograd.Function):
         s, params = ctx.struct, ctx.params
         ranges = _layer_parts(s.layers)
         order, bounds = _part_order(8, (5, 6, 7), s.layers, ranges)       # ln_post.weight / bias, proj come with the first part
-        grads, flat = _grad_buffers(params, order)
-        blocks = _block_grads(grads, 8)
-        g = N.VitGrads(*[t.data_ptr() for t in grads[:8]], C.cast(blocks, C.POINTER(N.BlockGrads)))
+        grads, flat, _blocks, g = _grad_call(params, 8, N.VitGrads, order)
         dfeat = N.f32c(dfeat)
         for k, (hi, lo) in enumerate(ranges):
             N.check(N.lib().cmh_vit_backward_part(C.byref(s), ctx.B, N.ptr(dfeat), C.byref(g), N.ptr(ctx.tape), ctx.tape.numel(), hi, lo,
@@ -141,9 +147,7 @@ class TextTrain(torch.autograd.Function):
         s, params, text = ctx.struct, ctx.params, ctx.text
         ranges = _layer_parts(s.layers)
         order, bounds = _part_order(5, (2, 3, 4), s.layers, ranges)       # ln_final.weight / bias, text_projection: first part
-        grads, flat = _grad_buffers(params, order)
-        blocks = _block_grads(grads, 5)
-        g = N.TextGrads(*[t.data_ptr() for t in grads[:5]], C.cast(blocks, C.POINTER(N.BlockGrads)))
+        grads, flat, _blocks, g = _grad_call(params, 5, N.TextGrads, order)
         dfeat = N.f32c(dfeat)
         B, L = text.shape
         for k, (hi, lo) in enumerate(ranges):
@@ -172,9 +176,7 @@ class VitTrainTokens(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dtok):
         s, params = ctx.struct, ctx.params
-        grads, flat = _grad_buffers(params)
-        blocks = _block_grads(grads, 8)
-        g = N.VitGrads(*[t.data_ptr() for t in grads[:8]], C.cast(blocks, C.POINTER(N.BlockGrads)))
+        grads, flat, _blocks, g = _grad_call(params, 8, N.VitGrads)
         dtok = N.f32c(dtok)
         N.check(N.lib().cmh_vit_backward_tokens(C.byref(s), ctx.B, N.ptr(dtok), C.byref(g), N.ptr(ctx.tape), ctx.tape.numel(),
                                                 N.stream_ptr(dtok.device)), "cmh_vit_backward_tokens")
@@ -206,9 +208,7 @@ class TextTrainTokens(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dtok, _drows):
         s, params, text = ctx.struct, ctx.params, ctx.text
-        grads, flat = _grad_buffers(params)
-        blocks = _block_grads(grads, 5)
-        g = N.TextGrads(*[t.data_ptr() for t in grads[:5]], C.cast(blocks, C.POINTER(N.BlockGrads)))
+        grads, flat, _blocks, g = _grad_call(params, 5, N.TextGrads)
         dtok = N.f32c(dtok)
         B, L = text.shape
         N.check(N.lib().cmh_text_backward_tokens(C.byref(s), N.ptr(text), B, L, N.ptr(ctx.kpm), N.ptr(dtok), C.byref(g),

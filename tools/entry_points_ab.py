@@ -10,7 +10,12 @@
 
 `run` records the sha256 of every output's bytes (features, token matrices, amax arrays, every gradient).  The device is synchronised
 between entry-point calls, so that the packed text path's tile-height hint (the previous call's row count, taken only when its event
-has completed) is the same in every run."""
+has completed) is the same in every run.
+
+Training legs: every tower's forward + backward with the pooled tail on and off (the bridges' three backward parts), the backward
+again as two parts (cmh_*_backward_part over layers .. a, a .. 0), and - at the `tiny` and `vitb32` bf16 configs - once with each of
+the block backward's two switches off: the 16-bit gradient stream (cmh_set_grad_stream16(0)) and the one-launch wgrad
+(CMH_WGRAD_MULTI=0, which the library reads at every call: `run` sets it for that leg and takes it away again, in one process)."""
 import csv
 import glob
 import hashlib
@@ -113,22 +118,37 @@ def run(out_path):
             keep(f"{key}/grad{i}", p.grad)
             p.grad = None
 
-    def training(tag, m, img, txt, kpm, modes, full):
+    def training(tag, m, img, txt, kpm, modes, full, switches=False):
         m.assume_frozen = False
         gen = torch.Generator(dev).manual_seed(3)
         vp, tp = T.vit_params(m.visual), T.text_params(m)
+        calls = (("vit", vp, lambda: m.encode_image(img)), ("text", tp, lambda: m.encode_text(txt)),
+                 ("text_mask", tp, lambda: m.encode_text(txt, key_padding_mask=kpm)))
+
+        def towers(k, some):
+            for name, params, call in some:
+                f = call()
+                keep(f"{k}/{name}_forward_train", f)
+                f.backward(torch.randn(f.shape, device=dev, generator=gen))
+                grads_of(f"{k}/{name}_backward", params)
+
         for mode in modes:
             m.set_gemm_dtype(mode)
             for tail in (True, False):
                 N.set_pooled_tail(tail)
                 k = f"{tag}/{mode}/tail{int(tail)}"
-                for name, params, call in (("vit", vp, lambda: m.encode_image(img)), ("text", tp, lambda: m.encode_text(txt)),
-                                           ("text_mask", tp, lambda: m.encode_text(txt, key_padding_mask=kpm))):
-                    f = call()
-                    keep(f"{k}/{name}_forward_train", f)
-                    f.backward(torch.randn(f.shape, device=dev, generator=gen))
-                    grads_of(f"{k}/{name}_backward", params)
+                towers(k, calls)
             N.set_pooled_tail(True)
+            T.PARTS = 2                             # the backward as (layers .. a, a .. 0)
+            towers(f"{tag}/{mode}/parts2", calls[:2])
+            T.PARTS = 3
+            if mode == "bf16" and switches:
+                N.set_grad_stream16(0)
+                towers(f"{tag}/bf16/stream16_off", calls[:2])
+                N.set_grad_stream16(-1)
+                os.environ["CMH_WGRAD_MULTI"] = "0"
+                towers(f"{tag}/bf16/wgrad_multi_off", calls[:2])
+                del os.environ["CMH_WGRAD_MULTI"]
             if not full:
                 continue
             tok = T.VitTrainTokens.apply(m, img, *vp)
@@ -159,7 +179,7 @@ def run(out_path):
         m = model(cfg, 1)
         img, txt, kpm = inputs(cfg, 32, 77, 1)
         inference("vitb32", m, img, txt, kpm, ("f32", "bf16", "fp8"), True)
-        training("vitb32", m, img, txt, kpm, ("f32", "bf16"), True)
+        training("vitb32", m, img, txt, kpm, ("f32", "bf16"), True, switches=True)
         del m
         m = model(VITL14_CUT, 2)
         img, txt, kpm = inputs(VITL14_CUT, 8, 77, 2)
@@ -174,9 +194,12 @@ def run(out_path):
         m = model(cfg, 4)
         img, txt, kpm = inputs(cfg, 32, 16, 4)
         inference("tiny", m, img, txt, kpm, ("f32", "bf16"), True)
-        training("tiny", m, img, txt, kpm, ("f32", "bf16"), True)
+        training("tiny", m, img, txt, kpm, ("f32", "bf16"), True, switches=True)
     finally:
         N.set_pooled_tail(True)
+        N.set_grad_stream16(-1)
+        T.PARTS = 3
+        os.environ.pop("CMH_WGRAD_MULTI", None)
     with open(out_path, "w") as f:
         json.dump({"lib": N.LIB_PATH, "outputs": digests}, f, indent=0)
     print(f"{len(digests)} outputs of {N.LIB_PATH} -> {out_path}")
