@@ -56,7 +56,7 @@ worst e32 of the family printed by tests/test_loss_edges_host.py:
   LinearHash y 1.9e-07 (1.1e-06)          dx 2.8e-07 (3.5e-07)   dW 1.1e-07 (4.3e-07)   db 2.3e-07 (7.3e-07)
   BatchNorm  y 1.5e-07 (2.8e-07)          running statistics 6.8e-08 (9.3e-08)   dx 1.5e-07 (1.7e-07)   dw 1.1e-07 (2.0e-07)   db 8.4e-08 (1.6e-07)
 No case is above 8 x e32 (64 x would need explaining); every case takes under a second.
-Out of scope: the DMsH-LN multi-similarity loss (its mining thresholds are relative to each row's own extrema), twdh_* (elementwise),
+Elsewhere: the DMsH-LN multi-similarity loss and csrc/mith.hip (tests/test_gpu_mith_edges.py).  Out of scope: twdh_* (elementwise),
 the forward small-linear kernels (test_linear_act_many_rows_has_the_one_row_kernels_bits)."""
 import pytest
 import torch
