@@ -5,15 +5,10 @@
 //   sign / argmax   train/base.py:141-158      codes in {-1,0,+1}
 // small_linear also serves the towers' final projection when embed_dim is not a multiple of the GEMM
 // tile (tiny test configs).
-#include "cmh_common.h"
+// Host structure: no entry point of this file takes a workspace; the small-linear kernels share head_common.h's wave_sum.
+#include "head_common.h"
 
 namespace cmh {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 ld4(const bf16_t* p) {
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const T* __restrict__
     float t = 0.f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float v = wsum(s[u]);
+      const float v = wave_sum(s[u]);
       if (lane == u) t = v;
     }
     const int n = n0 + lane;
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void small_linear_rows_kernel(const T* __re
     for (int r = 0; r < R; ++r)
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const float v = wsum(s[r][u]);
+        const float v = wave_sum(s[r][u]);
         if (lane == r * 4 + u) t = v;
       }
     const int n = n0 + (lane & 3), m = m0 + (lane >> 2);

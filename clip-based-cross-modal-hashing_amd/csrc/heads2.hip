@@ -5,25 +5,10 @@
 //   TwDH targets + loss   train/TwDH/hash_train.py:77-163 (hash_center_multilables, hash_convert, BCELoss, soft-argmax term)
 //   DNPH_out + noise term train/DNPH_TOMM/loss.py:14-32, train/DNPH_TOMM/hash_train.py:65-81
 // All operands are [batch, <= 4096] matrices: launch/latency-bound, so each op is ONE launch (+ a 1-thread finalize).
-#include "cmh_common.h"
+// Host structure: cmh_twdh_loss and cmh_dnph_loss open a workspace of kAccBytes (their f64 accumulators: nothing to carve); no shared launcher.
+#include "head_common.h"
 
 namespace cmh {
-
-__device__ __forceinline__ float h2_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double h2_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float h2_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // BatchNorm1d, training mode: per-feature batch mean and BIASED variance (what nn.BatchNorm1d normalises with).
 // One wave per feature column, lanes stride the batch.
@@ -35,13 +20,13 @@ __global__ __launch_bounds__(256) void batchnorm_train_kernel(const float* __res
   if (col >= d) return;
   float s = 0.f;
   for (int r = lane; r < B; r += 64) s += x[static_cast<size_t>(r) * d + col];
-  const float mean = h2_wave_sum(s) / static_cast<float>(B);
+  const float mean = wave_sum(s) / static_cast<float>(B);
   float ss = 0.f;
   for (int r = lane; r < B; r += 64) {
     const float c = x[static_cast<size_t>(r) * d + col] - mean;
     ss = fmaf(c, c, ss);
   }
-  const float rstd = 1.0f / sqrtf(h2_wave_sum(ss) / static_cast<float>(B) + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum(ss) / static_cast<float>(B) + eps);
   const float g = w[col], bb = b[col];
   for (int r = lane; r < B; r += 64)
     y[static_cast<size_t>(r) * d + col] = (x[static_cast<size_t>(r) * d + col] - mean) * rstd * g + bb;
@@ -58,13 +43,13 @@ __global__ __launch_bounds__(256) void batchnorm_running_kernel(const float* __r
   if (col >= d) return;
   float s = 0.f;
   for (int r = lane; r < B; r += 64) s += x[static_cast<size_t>(r) * d + col];
-  const float mean = h2_wave_sum(s) / static_cast<float>(B);
+  const float mean = wave_sum(s) / static_cast<float>(B);
   float ss = 0.f;
   for (int r = lane; r < B; r += 64) {
     const float c = x[static_cast<size_t>(r) * d + col] - mean;
     ss = fmaf(c, c, ss);
   }
-  ss = h2_wave_sum(ss);
+  ss = wave_sum(ss);
   if (lane == 0) {
     const float unbiased = B > 1 ? ss / static_cast<float>(B - 1) : ss;
     running_mean[col] = (1.f - momentum) * running_mean[col] + momentum * mean;
@@ -81,20 +66,20 @@ __global__ __launch_bounds__(256) void batchnorm_bwd_kernel(const float* __restr
   if (col >= d) return;
   float s = 0.f;
   for (int r = lane; r < B; r += 64) s += x[static_cast<size_t>(r) * d + col];
-  const float mean = h2_wave_sum(s) / static_cast<float>(B);
+  const float mean = wave_sum(s) / static_cast<float>(B);
   float ss = 0.f;
   for (int r = lane; r < B; r += 64) {
     const float c = x[static_cast<size_t>(r) * d + col] - mean;
     ss = fmaf(c, c, ss);
   }
-  const float rstd = 1.0f / sqrtf(h2_wave_sum(ss) / static_cast<float>(B) + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum(ss) / static_cast<float>(B) + eps);
   float sg = 0.f, sb = 0.f;
   for (int r = lane; r < B; r += 64) {
     const float g = dy[static_cast<size_t>(r) * d + col];
     sg = fmaf(g, (x[static_cast<size_t>(r) * d + col] - mean) * rstd, sg);
     sb += g;
   }
-  sg = h2_wave_sum(sg); sb = h2_wave_sum(sb);
+  sg = wave_sum(sg); sb = wave_sum(sb);
   if (lane == 0) { dw[col] = sg; db[col] = sb; }
   const float k = w[col] * rstd, inv = 1.0f / static_cast<float>(B);
   for (int r = lane; r < B; r += 64) {
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(256) void twdh_loss_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const double s = h2_wave_sum(v[j]);
+    const double s = wave_sum(v[j]);
     if (lane == 0) sh[j][wid] = s;
   }
   __syncthreads();
@@ -200,7 +185,7 @@ __global__ __launch_bounds__(256) void dnph_row_kernel(const float* __restrict__
     ss = fmaf(v, v, ss);
     if (nz) dotn = fmaf(v, nz[static_cast<size_t>(b) * K + k], dotn);
   }
-  const float inv = 1.0f / fmaxf(sqrtf(h2_wave_sum(ss)), 1e-12f);
+  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
   for (int k = lane; k < K; k += 64) row[k] = f[k] * inv;
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(256) void dnph_row_kernel(const float* __restrict__
     const float lg = -(d2 + (label[static_cast<size_t>(b) * C + c] == 1.f ? mrg : 0.f));
     mx = fmaxf(mx, lg);
   }
-  mx = h2_wave_max(mx);
+  mx = wave_max(mx);
   float se = 0.f, lab_lg = 0.f, lab_n = 0.f;
   for (int c = lane; c < C; c += 64) {
     const float* p = prox + static_cast<size_t>(c) * K;
@@ -237,9 +222,9 @@ __global__ __launch_bounds__(256) void dnph_row_kernel(const float* __restrict__
     lab_lg = fmaf(l, lg, lab_lg);
     lab_n += l;
   }
-  se = h2_wave_sum(se);
-  lab_lg = h2_wave_sum(lab_lg);
-  lab_n = h2_wave_sum(lab_n);
+  se = wave_sum(se);
+  lab_lg = wave_sum(lab_lg);
+  lab_n = wave_sum(lab_n);
   const float lse = mx + logf(se);
   const double ploss = -(static_cast<double>(lab_lg) - static_cast<double>(lab_n) * lse);   // sum_c -l*(lg - lse)
   // CrossEntropy(pre, argmax(label)) : first maximum, like torch.argmax
@@ -257,12 +242,12 @@ __global__ __launch_bounds__(256) void dnph_row_kernel(const float* __restrict__
     const int oi = __shfl_xor(besti, o, 64);
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
   }
-  pmx = h2_wave_max(pmx);
+  pmx = wave_max(pmx);
   float pse = 0.f;
   for (int c = lane; c < C; c += 64) pse += expf(pre[c] - pmx);
-  pse = h2_wave_sum(pse);
+  pse = wave_sum(pse);
   const double ce = -(static_cast<double>(pre[besti]) - (pmx + logf(pse)));
-  const float dn = h2_wave_sum(dotn);
+  const float dn = wave_sum(dotn);
   if (lane == 0) {
     atomicAdd(&acc[0], ploss);
     atomicAdd(&acc[r < B ? 1 : 2], ce);
@@ -330,7 +315,7 @@ extern "C" int cmh_twdh_targets(const float* label, const float* center, const f
 extern "C" int cmh_twdh_loss(const float* p_img, const float* p_txt, const float* target, int32_t B, int32_t K,
                              float* out2, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(p_img && p_txt && target && out2 && workspace && B > 0 && K > 0, "twdh_loss: bad arguments");
-  if (workspace_bytes < 256) return fail(CMH_ERR_WORKSPACE, "twdh_loss: workspace must be >= 256 bytes");
+  if (int rc = open_ws("twdh_loss", workspace, workspace_bytes, kAccBytes)) return rc;
   hipStream_t st = as_stream(stream);
   double* acc = static_cast<double*>(workspace);
   if (hipMemsetAsync(acc, 0, 64, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "twdh_loss: memset failed");
@@ -349,7 +334,7 @@ extern "C" int cmh_dnph_loss(const float* hash_img, const float* hash_txt, const
   CMH_CHECK_ARG(hash_img && hash_txt && pre_img && pre_txt && label && proxies && out3 && workspace, "dnph_loss: null pointer");
   CMH_CHECK_ARG(B > 0 && K > 0 && K <= 4096 && C > 0, "dnph_loss: bad shape");
   CMH_CHECK_ARG((noise_img == nullptr) == (noise_txt == nullptr), "dnph_loss: give both noise matrices or neither");
-  if (workspace_bytes < 256) return fail(CMH_ERR_WORKSPACE, "dnph_loss: workspace must be >= 256 bytes");
+  if (int rc = open_ws("dnph_loss", workspace, workspace_bytes, kAccBytes)) return rc;
   hipStream_t st = as_stream(stream);
   double* acc = static_cast<double*>(workspace);
   if (hipMemsetAsync(acc, 0, 64, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "dnph_loss: memset failed");

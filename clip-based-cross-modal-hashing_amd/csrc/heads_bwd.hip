@@ -2,16 +2,12 @@
 //   cmh_linear_act_backward    LinearHash: y = act((x W^T + b) * mask * keep_scale)            (model/modelbase.py:25-35)
 //   cmh_dsph_hyp_loss_backward HyP.forward (train/DSPH/loss.py:22-72): d loss / d(x, y, proxies)
 // All f32, launch-latency bound (B = 256, K = 64, C <= ~100): a handful of launches, one wave per row.
-#include "cmh_common.h"
+// Host structure: cmh_dsph_hyp_loss_backward carves HypBwdWs, cmh_dchmt_loss_backward DchmtBwdWs (both under cmh_head_backward_workspace_bytes),
+// cmh_dnph_loss_backward DnphBwdWs, cmh_linear_act_backward LinearActBwdWs; every row normalisation is launch_normalize_rows (losses.hip).
+#include "head_common.h"
 
 namespace cmh {
 namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---- LinearHash ----------------------------------------------------------------------------------------------------------
 // dz[m,n] = dy[m,n] * act'(.) * (mask ? mask*keep_scale : 1);   act' from the OUTPUT y: tanh -> 1 - y^2, relu -> y > 0
@@ -56,25 +52,12 @@ __global__ __launch_bounds__(256) void la_dw_kernel(const float* __restrict__ dz
   if (blockIdx.y == 0 && threadIdx.x < 64) {     // db[n]: one wave, lanes stride over m, butterfly
     float a = 0.f;
     for (int m = threadIdx.x; m < M; m += 64) a += dz[static_cast<size_t>(m) * N + n];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if (threadIdx.x == 0) db[n] = a;
   }
 }
 
 // ---- HyP ---------------------------------------------------------------------------------------------------------------------
-// rows -> unit vectors (F.normalize, eps 1e-12) + the divisor used
-__global__ __launch_bounds__(256) void hyp_normalize_kernel(const float* __restrict__ a, float* __restrict__ an, float* __restrict__ nrm,
-                                                            int R, int K) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= R) return;
-  float ss = 0.f;
-  for (int k = lane; k < K; k += 64) { const float v = a[static_cast<size_t>(row) * K + k]; ss = fmaf(v, v, ss); }
-  const float n = fmaxf(sqrtf(wsum(ss)), 1e-12f);
-  for (int k = lane; k < K; k += 64) an[static_cast<size_t>(row) * K + k] = a[static_cast<size_t>(row) * K + k] / n;
-  if (lane == 0) nrm[row] = n;
-}
-
 // cnt[0] = #(label != 0) (P_num), cnt[1] = #(label == 0) (N_num); multi[b] = label[b].sum() > 1.  One workgroup.
 __global__ __launch_bounds__(256) void hyp_counts_kernel(const float* __restrict__ label, int B, int C, int* __restrict__ multi,
                                                          float* __restrict__ cnt) {
@@ -87,7 +70,7 @@ __global__ __launch_bounds__(256) void hyp_counts_kernel(const float* __restrict
     for (int c = 0; c < C; ++c) s += label[static_cast<size_t>(b) * C + c];
     multi[b] = s > 1.f;
   }
-  p = wsum(p); n = wsum(n);
+  p = wave_sum(p); n = wave_sum(n);
   if (lane == 0) { sh[0][wid] = p; sh[1][wid] = n; }
   __syncthreads();
   if (threadIdx.x < 2) cnt[threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(64) void hyp_pairs_kernel(const float* __restrict__
     for (int c = 0; c < C; ++c) ll = fmaf(label[static_cast<size_t>(i) * C + c], label[static_cast<size_t>(j) * C + c], ll);
     if (ll == 0.f) z += 1.f;
   }
-  z = wsum(z);
+  z = wave_sum(z);
   if (lane == 0 && z != 0.f) atomicAdd(cnt + 2, z);
 }
 
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(64) void hyp_rows_kernel(const float* __restrict__ 
       px[v] = k < K ? pn[static_cast<size_t>(c) * K + k] : 0.f;
       cx = fmaf(xi[v], px[v], cx); ct = fmaf(yi[v], px[v], ct);
     }
-    cx = wsum(cx); ct = wsum(ct);
+    cx = wave_sum(cx); ct = wave_sum(ct);
     const float l = label[static_cast<size_t>(b) * C + c];
     float wx = 0.f, wt = 0.f;
     if (l == 1.f) { wx = -invP; wt = -invP; }
@@ -171,7 +154,7 @@ __global__ __launch_bounds__(64) void hyp_rows_kernel(const float* __restrict__ 
         yj[v] = k < K ? yn[static_cast<size_t>(j) * K + k] : 0.f;
         sx = fmaf(xi[v], xj[v], sx); st = fmaf(yi[v], yj[v], st); sxt = fmaf(xi[v], yj[v], sxt); stx = fmaf(xj[v], yi[v], stx);
       }
-      sx = wsum(sx); st = wsum(st); sxt = wsum(sxt); stx = wsum(stx);
+      sx = wave_sum(sx); st = wave_sum(st); sxt = wave_sum(sxt); stx = wave_sum(stx);
       const float a = sx > thr ? 2.f * w : 0.f, bq = st > thr ? 2.f * w : 0.f, cq = sxt > thr ? w : 0.f, dq = stx > thr ? w : 0.f;
 #pragma unroll
       for (int v = 0; v < KV; ++v) {
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(64) void hyp_rows_kernel(const float* __restrict__ 
   float dxg = 0.f, dyg = 0.f;
 #pragma unroll
   for (int v = 0; v < KV; ++v) { dxg = fmaf(xi[v], gx[v], dxg); dyg = fmaf(yi[v], gy[v], dyg); }
-  dxg = wsum(dxg); dyg = wsum(dyg);
+  dxg = wave_sum(dxg); dyg = wave_sum(dyg);
   const float rx = up / nx[b], ry = up / ny[b];
 #pragma unroll
   for (int v = 0; v < KV; ++v) {
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(256) void hyp_proxy_kernel(const float* __restrict_
       yb[v] = k < K ? yn[static_cast<size_t>(b) * K + k] : 0.f;
       cx = fmaf(xb[v], pc[v], cx); ct = fmaf(yb[v], pc[v], ct);
     }
-    cx = wsum(cx); ct = wsum(ct);
+    cx = wave_sum(cx); ct = wave_sum(ct);
     const float l = label[static_cast<size_t>(b) * C + c];
     float wx = 0.f, wt = 0.f;
     if (l == 1.f) { wx = -invP; wt = -invP; }
@@ -239,7 +222,7 @@ __global__ __launch_bounds__(256) void hyp_proxy_kernel(const float* __restrict_
   float pg = 0.f;
 #pragma unroll
   for (int v = 0; v < KV; ++v) pg = fmaf(pc[v], g[v], pg);
-  pg = wsum(pg);
+  pg = wave_sum(pg);
   const float r = up / np_[c];
 #pragma unroll
   for (int v = 0; v < KV; ++v) { const int k = lane + 64 * v; if (k < K) dp[static_cast<size_t>(c) * K + k] = (g[v] - pc[v] * pg) * r; }
@@ -294,7 +277,7 @@ __global__ __launch_bounds__(64) void dchmt_rows_kernel(const float* __restrict_
   for (int j = 0; j < B; ++j) {
     float ll = 0.f;
     for (int c = lane; c < C; c += 64) ll = fmaf(label[static_cast<size_t>(i) * C + c], label[static_cast<size_t>(j) * C + c], ll);
-    const bool same = wsum(ll) > 0.f;                    // calc_neighbor
+    const bool same = wave_sum(ll) > 0.f;                    // calc_neighbor
     float aj[DV], tj[DV], s_it = 0.f, s_ti = 0.f, s_ii = 0.f, s_tt = 0.f;
 #pragma unroll
     for (int v = 0; v < DV; ++v) {
@@ -308,7 +291,7 @@ __global__ __launch_bounds__(64) void dchmt_rows_kernel(const float* __restrict_
         s_it = fmaf(d1, d1, s_it); s_ti = fmaf(d2, d2, s_ti); s_ii = fmaf(d3, d3, s_ii); s_tt = fmaf(d4, d4, s_tt);
       }
     }
-    s_it = wsum(s_it); s_ti = wsum(s_ti); s_ii = wsum(s_ii); s_tt = wsum(s_tt);
+    s_it = wave_sum(s_it); s_ti = wave_sum(s_ti); s_ii = wave_sum(s_ii); s_tt = wave_sum(s_tt);
     if (cosine) { s_it = 1.f - s_it; s_ti = 1.f - s_ti; s_ii = 1.f - s_ii; s_tt = 1.f - s_tt; }
     else { s_it = sqrtf(s_it); s_ti = sqrtf(s_ti); s_ii = sqrtf(s_ii); s_tt = sqrtf(s_tt); }
     const float w_it = dchmt_dsim(s_it, same, cosine, l2, thr, maxv, inv_n), w_ti = dchmt_dsim(s_ti, same, cosine, l2, thr, maxv, inv_n);
@@ -333,7 +316,7 @@ __global__ __launch_bounds__(64) void dchmt_rows_kernel(const float* __restrict_
   if (cosine) {                                          // through a / |a| (no eps: utils/utils.py:61-62)
 #pragma unroll
     for (int v = 0; v < DV; ++v) { pa = fmaf(ai[v], ga[v], pa); pt = fmaf(ti[v], gt[v], pt); }
-    pa = wsum(pa); pt = wsum(pt);
+    pa = wave_sum(pa); pt = wave_sum(pt);
   }
 #pragma unroll
   for (int v = 0; v < DV; ++v) {
@@ -368,13 +351,13 @@ __global__ __launch_bounds__(64) void dnph_rows_bwd_kernel(const float* __restri
   for (int v = 0; v < KV; ++v) { const int k = lane + 64 * v; fi[v] = k < K ? fn[static_cast<size_t>(r) * K + k] : 0.f; g[v] = 0.f; }
   float lsum = 0.f;
   for (int c = lane; c < C; c += 64) lsum += label[static_cast<size_t>(lb) * C + c];
-  lsum = wsum(lsum);
+  lsum = wave_sum(lsum);
   float m = -1e30f;
   for (int c = 0; c < C; ++c) {
     float dd = 0.f;
 #pragma unroll
     for (int v = 0; v < KV; ++v) { const int k = lane + 64 * v; const float d = k < K ? fi[v] - pn[static_cast<size_t>(c) * K + k] : 0.f; dd = fmaf(d, d, dd); }
-    dd = wsum(dd);
+    dd = wave_sum(dd);
     const float z = -(dd + (label[static_cast<size_t>(lb) * C + c] == 1.f ? mrg : 0.f));
     if (lane == 0) zs[c] = z;
     m = fmaxf(m, z);
@@ -382,7 +365,7 @@ __global__ __launch_bounds__(64) void dnph_rows_bwd_kernel(const float* __restri
   __syncthreads();
   float se = 0.f;
   for (int c = lane; c < C; c += 64) se += expf(zs[c] - m);
-  se = wsum(se);
+  se = wave_sum(se);
   const float inv2b = 1.f / (2.f * static_cast<float>(B));
   for (int c = 0; c < C; ++c) {
     const float sm = expf(zs[c] - m) / se;
@@ -398,7 +381,7 @@ __global__ __launch_bounds__(64) void dnph_rows_bwd_kernel(const float* __restri
   float pg = 0.f;
 #pragma unroll
   for (int v = 0; v < KV; ++v) pg = fmaf(fi[v], g[v], pg);
-  pg = wsum(pg);
+  pg = wave_sum(pg);
   const float rn = 1.f / nf[r];
   const float* noise = r < B ? noise_img : noise_txt;
   float* out = r < B ? dimg : dtxt;
@@ -431,7 +414,7 @@ __global__ __launch_bounds__(64) void dnph_proxy_bwd_kernel(const float* __restr
   float pg = 0.f;
 #pragma unroll
   for (int v = 0; v < KV; ++v) pg = fmaf(pc[v], g[v], pg);
-  pg = wsum(pg);
+  pg = wave_sum(pg);
   const float rn = up / np_[c];
 #pragma unroll
   for (int v = 0; v < KV; ++v) { const int k = lane + 64 * v; if (k < K) dp[static_cast<size_t>(c) * K + k] = (g[v] - pc[v] * pg) * rn; }
@@ -458,21 +441,9 @@ __global__ __launch_bounds__(64) void ce_argmax_bwd_kernel(const float* __restri
   }
   float se = 0.f;
   for (int c = lane; c < C; c += 64) se += expf(pre[static_cast<size_t>(r) * C + c] - m);
-  se = wsum(se);
+  se = wave_sum(se);
   for (int c = lane; c < C; c += 64)
     dpre[static_cast<size_t>(r) * C + c] = (expf(pre[static_cast<size_t>(r) * C + c] - m) / se - (c == li ? 1.f : 0.f)) * up / static_cast<float>(B);
-}
-
-// rows / |row| (no eps) and the norms
-__global__ __launch_bounds__(256) void plain_normalize_kernel(const float* __restrict__ a, float* __restrict__ an, float* __restrict__ nrm,
-                                                              int R, int K) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= R) return;
-  float ss = 0.f;
-  for (int k = lane; k < K; k += 64) { const float v = a[static_cast<size_t>(row) * K + k]; ss = fmaf(v, v, ss); }
-  const float n = sqrtf(wsum(ss));
-  for (int k = lane; k < K; k += 64) an[static_cast<size_t>(row) * K + k] = a[static_cast<size_t>(row) * K + k] / n;
-  if (lane == 0) nrm[row] = n;
 }
 
 }  // namespace
@@ -480,11 +451,29 @@ __global__ __launch_bounds__(256) void plain_normalize_kernel(const float* __res
 
 using namespace cmh;
 
+// cmh_head_backward_workspace_bytes serves two layouts, each from the first 256-byte boundary of the caller's workspace.  HypBwdWs is
+// the larger (it fills the query exactly), DchmtBwdWs ends 2 bk + 2 v bytes behind the boundary.
+struct HypBwdWs { float *xn, *yn, *pn, *nx, *ny, *np_; int* multi; float* cnt; size_t total; };
+static HypBwdWs carve_hyp_bwd(void* ws, size_t B, size_t K, size_t C) {
+  Carver c(ws, true);
+  const size_t bk = B * K * 4, v = (B > C ? B : C) * 4;
+  return {c.f32(bk), c.f32(bk), c.f32(C * K * 4), c.f32(v), c.f32(v), c.f32(v), c.take<int>(B * 4), c.f32(3 * 4), c.total()};
+}
+struct DchmtBwdWs { float *an, *tn, *na, *nt; size_t total; };
+static DchmtBwdWs carve_dchmt_bwd(void* ws, size_t B, size_t D, size_t C) {
+  Carver c(ws, true);
+  return {c.f32(B * D * 4), c.f32(B * D * 4), c.f32((B > C ? B : C) * 4), c.f32((B > C ? B : C) * 4), c.total()};
+}
+struct DnphBwdWs { float *fn, *pn, *nf, *np_, *G; size_t total; };     // f = cat(img, txt): 2 B rows
+static DnphBwdWs carve_dnph_bwd(void* ws, size_t B, size_t K, size_t C) {
+  Carver c(ws, true);
+  return {c.f32(2 * B * K * 4), c.f32(C * K * 4), c.f32(2 * B * 4), c.f32(C * 4), c.f32(2 * B * C * 4), c.total(256)};
+}
+struct LinearActBwdWs { float* dz; size_t total; };                    // [M, N]
+static LinearActBwdWs carve_linear_act_bwd(void* ws, size_t M, size_t N) { Carver c(ws, true); return {c.f32(M * N * 4, 4), c.total()}; }
+
 extern "C" size_t cmh_dnph_backward_workspace_bytes(int32_t B, int32_t K, int32_t C) {
-  if (B <= 0 || K <= 0 || C <= 0) return 0;
-  return align_up(static_cast<size_t>(2) * B * K * 4, 256) + align_up(static_cast<size_t>(C) * K * 4, 256) +
-         align_up(static_cast<size_t>(2) * B * 4, 256) + align_up(static_cast<size_t>(C) * 4, 256) +
-         align_up(static_cast<size_t>(2) * B * C * 4, 256) + 512;
+  return B <= 0 || K <= 0 || C <= 0 ? 0 : carve_dnph_bwd(nullptr, B, K, C).total;
 }
 
 extern "C" int cmh_dnph_loss_backward(const float* hash_img, const float* hash_txt, const float* pre_img, const float* pre_txt,
@@ -496,20 +485,15 @@ extern "C" int cmh_dnph_loss_backward(const float* hash_img, const float* hash_t
                 dproxies && workspace, "dnph_loss_backward: null pointer");
   CMH_CHECK_ARG((noise_img == nullptr) == (noise_txt == nullptr), "dnph_loss_backward: give both noise matrices or none");
   CMH_CHECK_ARG(B > 0 && K > 0 && K <= 512 && C > 0 && C <= 4096, "dnph_loss_backward: bad shape B=%d K=%d C=%d", B, K, C);
-  if (workspace_bytes < cmh_dnph_backward_workspace_bytes(B, K, C)) return fail(CMH_ERR_WORKSPACE, "dnph_loss_backward: workspace too small");
-  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  float* fn = reinterpret_cast<float*>(ws); ws += align_up(static_cast<size_t>(2) * B * K * 4, 256);
-  float* pn = reinterpret_cast<float*>(ws); ws += align_up(static_cast<size_t>(C) * K * 4, 256);
-  float* nf = reinterpret_cast<float*>(ws); ws += align_up(static_cast<size_t>(2) * B * 4, 256);
-  float* np_ = reinterpret_cast<float*>(ws); ws += align_up(static_cast<size_t>(C) * 4, 256);
-  float* G = reinterpret_cast<float*>(ws);
+  if (int rc = open_ws("dnph_loss_backward", workspace, workspace_bytes, carve_dnph_bwd(nullptr, B, K, C).total)) return rc;
+  const DnphBwdWs w = carve_dnph_bwd(workspace, B, K, C);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, hash_img, fn, nf, B, K);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, hash_txt, fn + static_cast<size_t>(B) * K, nf + B, B, K);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, proxies, pn, np_, C, K);
-  hipLaunchKernelGGL(dnph_rows_bwd_kernel, dim3(2 * B), dim3(64), static_cast<size_t>(C) * 4, st, fn, nf, pn, label, noise_img, noise_txt, B, K,
-                     C, margin, noise_img ? noise_weight : 0.f, dloss, G, dhash_img, dhash_txt);
-  hipLaunchKernelGGL(dnph_proxy_bwd_kernel, dim3(C), dim3(64), 0, st, fn, pn, np_, G, 2 * B, K, C, dloss, dproxies);
+  launch_normalize_rows(hash_img, w.fn, w.nf, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(hash_txt, w.fn + static_cast<size_t>(B) * K, w.nf + B, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(proxies, w.pn, w.np_, C, K, 1e-12f, nullptr, st);
+  hipLaunchKernelGGL(dnph_rows_bwd_kernel, dim3(2 * B), dim3(64), static_cast<size_t>(C) * 4, st, w.fn, w.nf, w.pn, label, noise_img, noise_txt,
+                     B, K, C, margin, noise_img ? noise_weight : 0.f, dloss, w.G, dhash_img, dhash_txt);
+  hipLaunchKernelGGL(dnph_proxy_bwd_kernel, dim3(C), dim3(64), 0, st, w.fn, w.pn, w.np_, w.G, 2 * B, K, C, dloss, dproxies);
   hipLaunchKernelGGL(ce_argmax_bwd_kernel, dim3(B), dim3(64), 0, st, pre_img, label, B, C, dloss, dpre_img);
   hipLaunchKernelGGL(ce_argmax_bwd_kernel, dim3(B), dim3(64), 0, st, pre_txt, label, B, C, dloss, dpre_txt);
   CMH_CHECK_LAUNCH("dnph_loss_backward");
@@ -531,24 +515,20 @@ extern "C" int cmh_dchmt_loss_backward(const float* img, const float* txt, const
   CMH_CHECK_ARG(img && txt && label && dimg && dtxt && workspace, "dchmt_loss_backward: null pointer");
   CMH_CHECK_ARG(B > 0 && D > 0 && D <= 512 && C > 0 && B <= 32768, "dchmt_loss_backward: bad shape");
   CMH_CHECK_ARG((similarity == 0 || similarity == 1) && (loss_type == 1 || loss_type == 2), "dchmt_loss_backward: bad similarity / loss_type");
-  if (workspace_bytes < cmh_head_backward_workspace_bytes(B, D, C)) return fail(CMH_ERR_WORKSPACE, "dchmt_loss_backward: workspace too small");
-  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  const size_t bk = align_up(static_cast<size_t>(B) * D * 4, 256), v = align_up(static_cast<size_t>(B > C ? B : C) * 4, 256);
-  float* an = reinterpret_cast<float*>(ws);
-  float* tn = reinterpret_cast<float*>(ws + bk);
-  float* na = reinterpret_cast<float*>(ws + 2 * bk);
-  float* nt = reinterpret_cast<float*>(ws + 2 * bk + v);
+  if (int rc = open_ws("dchmt_loss_backward", workspace, workspace_bytes, cmh_head_backward_workspace_bytes(B, D, C))) return rc;
+  const DchmtBwdWs w = carve_dchmt_bwd(workspace, B, D, C);
+  assert(w.total <= cmh_head_backward_workspace_bytes(B, D, C));
   hipStream_t st = as_stream(stream);
   const float* A = img;
   const float* T = txt;
   if (similarity == 1) {   // the forward normalises unless a matrix is identically zero (pair probabilities never are)
-    hipLaunchKernelGGL(plain_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, img, an, na, B, D);
-    hipLaunchKernelGGL(plain_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, txt, tn, nt, B, D);
-    A = an; T = tn;
+    launch_normalize_rows(img, w.an, w.na, B, D, 0.f, nullptr, st);
+    launch_normalize_rows(txt, w.tn, w.nt, B, D, 0.f, nullptr, st);
+    A = w.an; T = w.tn;
   }
   const float thr = sim_threshold != 0.f ? sim_threshold : 0.05f;
   const float maxv = sqrtf(static_cast<float>(output_dim) * 2.f * vartheta);
-  hipLaunchKernelGGL(dchmt_rows_kernel, dim3(B), dim3(64), 0, st, A, T, na, nt, label, B, D, C, similarity, loss_type == 2, thr, maxv,
+  hipLaunchKernelGGL(dchmt_rows_kernel, dim3(B), dim3(64), 0, st, A, T, w.na, w.nt, label, B, D, C, similarity, loss_type == 2, thr, maxv,
                      dloss, dimg, dtxt);
   CMH_CHECK_LAUNCH("dchmt_loss_backward");
   return CMH_OK;
@@ -565,8 +545,8 @@ extern "C" int cmh_linear_act_backward(const float* x, const float* w, const flo
                                        int32_t K, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(x && w && y && dy && dx && dw && db && workspace && M > 0 && N > 0 && K > 0, "linear_act_backward: bad arguments");
   CMH_CHECK_ARG(act == CMH_ACT_NONE || act == CMH_ACT_TANH || act == CMH_ACT_RELU, "linear_act_backward: bad act %d", act);
-  if (workspace_bytes < static_cast<size_t>(M) * N * 4 + 256) return fail(CMH_ERR_WORKSPACE, "linear_act_backward: workspace too small");
-  float* dz = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  if (int rc = open_ws("linear_act_backward", workspace, workspace_bytes, carve_linear_act_bwd(nullptr, M, N).total)) return rc;
+  float* dz = carve_linear_act_bwd(workspace, M, N).dz;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(la_dz_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, y, dy, drop_mask, keep_scale, act, dz, M * N);
   hipLaunchKernelGGL(la_dx_kernel, dim3(M), dim3(256), 0, st, dz, w, dx, M, N, K);
@@ -580,29 +560,20 @@ extern "C" int cmh_dsph_hyp_loss_backward(const float* x, const float* y, const 
                                           float* dy, float* dproxies, void* workspace, size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(x && y && label && proxies && dx && dy && dproxies && workspace, "dsph_hyp_loss_backward: null pointer");
   CMH_CHECK_ARG(B > 0 && K > 0 && K <= 512 && C > 0 && B <= 32768, "dsph_hyp_loss_backward: bad shape B=%d K=%d C=%d", B, K, C);
-  if (workspace_bytes < cmh_head_backward_workspace_bytes(B, K, C)) return fail(CMH_ERR_WORKSPACE, "dsph_hyp_loss_backward: workspace too small");
-  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  const size_t bk = align_up(static_cast<size_t>(B) * K * 4, 256), ck = align_up(static_cast<size_t>(C) * K * 4, 256);
-  const size_t v = align_up(static_cast<size_t>(B > C ? B : C) * 4, 256);
-  float* xn = reinterpret_cast<float*>(ws);
-  float* yn = reinterpret_cast<float*>(ws + bk);
-  float* pn = reinterpret_cast<float*>(ws + 2 * bk);
-  float* nx = reinterpret_cast<float*>(ws + 2 * bk + ck);
-  float* ny = reinterpret_cast<float*>(ws + 2 * bk + ck + v);
-  float* np_ = reinterpret_cast<float*>(ws + 2 * bk + ck + 2 * v);
-  int* multi = reinterpret_cast<int*>(ws + 2 * bk + ck + 3 * v);
-  float* cnt = reinterpret_cast<float*>(ws + 2 * bk + ck + 3 * v + align_up(static_cast<size_t>(B) * 4, 256));
+  if (int rc = open_ws("dsph_hyp_loss_backward", workspace, workspace_bytes, cmh_head_backward_workspace_bytes(B, K, C))) return rc;
+  const HypBwdWs w = carve_hyp_bwd(workspace, B, K, C);
+  assert(w.total <= cmh_head_backward_workspace_bytes(B, K, C));
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, x, xn, nx, B, K);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, y, yn, ny, B, K);
-  hipLaunchKernelGGL(hyp_normalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, proxies, pn, np_, C, K);
-  hipLaunchKernelGGL(hyp_counts_kernel, dim3(1), dim3(256), 0, st, label, B, C, multi, cnt);
-  if (alpha > 0.f) hipLaunchKernelGGL(hyp_pairs_kernel, dim3(B), dim3(64), 0, st, label, multi, B, C, cnt);
+  launch_normalize_rows(x, w.xn, w.nx, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(y, w.yn, w.ny, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(proxies, w.pn, w.np_, C, K, 1e-12f, nullptr, st);
+  hipLaunchKernelGGL(hyp_counts_kernel, dim3(1), dim3(256), 0, st, label, B, C, w.multi, w.cnt);
+  if (alpha > 0.f) hipLaunchKernelGGL(hyp_pairs_kernel, dim3(B), dim3(64), 0, st, label, w.multi, B, C, w.cnt);
 #define HYP_BWD(KV)                                                                                                               \
   do {                                                                                                                          \
-    hipLaunchKernelGGL(hyp_rows_kernel<KV>, dim3(B), dim3(64), 0, st, xn, yn, pn, nx, ny, label, multi, cnt, B, K, C, threshold, alpha, \
+    hipLaunchKernelGGL(hyp_rows_kernel<KV>, dim3(B), dim3(64), 0, st, w.xn, w.yn, w.pn, w.nx, w.ny, label, w.multi, w.cnt, B, K, C, threshold, alpha, \
                        dloss, dx, dy);                                                                                          \
-    hipLaunchKernelGGL(hyp_proxy_kernel<KV>, dim3(C), dim3(256), 0, st, xn, yn, pn, np_, label, cnt, B, K, C, threshold, dloss,    \
+    hipLaunchKernelGGL(hyp_proxy_kernel<KV>, dim3(C), dim3(256), 0, st, w.xn, w.yn, w.pn, w.np_, label, w.cnt, B, K, C, threshold, dloss, \
                        dproxies);                                                                                               \
   } while (0)
   if (K <= 64) HYP_BWD(1);

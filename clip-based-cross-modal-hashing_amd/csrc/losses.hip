@@ -5,26 +5,15 @@
 // that live in L2: these kernels are launch/latency-bound, not HBM- or MFMA-bound, so the
 // design goal is FEW launches (the reference issues ~20-40 tiny ATen kernels per loss): one thread per
 // (i,j) pair, block reduction, one double atomic per block per accumulator, then a 1-thread finalize.
-#include "cmh_common.h"
+// Host structure: cmh_dsph_hyp_loss carves HypFwdWs, cmh_dchmt_loss DchmtFwdWs (both under cmh_loss_workspace_bytes); both normalise through
+// launch_normalize_rows, which with launch_row_norms2 is defined here for every head / loss file (head_common.h).
+#include "head_common.h"
 
 namespace cmh {
 
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) t += sh[w];
-  return t;
-}
-
-// rows of a [R,K] -> unit L2 norm (F.normalize: x / max(||x||, 1e-12)) or plain division (eps = 0,
-// utils/utils.py:61-62); also flags[0] |= any element non-zero.  One wave per row.
-__global__ __launch_bounds__(256) void row_normalize_kernel(const float* __restrict__ a, float* __restrict__ out, int R,
-                                                            int K, float eps, int* __restrict__ anynz) {
+// The one row normaliser (launch_normalize_rows).  mith.hip's l2norm_rows_kernel multiplies by a reciprocal - another rounding - and stays.
+__global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __restrict__ a, float* __restrict__ out, float* __restrict__ divisor,
+                                                             int R, int K, float eps, int* __restrict__ anynz) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
@@ -35,12 +24,30 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(const float* __restr
     ss = fmaf(v, v, ss);
     nz |= v != 0.f;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  float nrm = sqrtf(ss);
+  float nrm = sqrtf(wave_sum(ss));
   if (eps > 0.f) nrm = fmaxf(nrm, eps);
   for (int k = lane; k < K; k += 64) out[static_cast<size_t>(row) * K + k] = a[static_cast<size_t>(row) * K + k] / nrm;
+  if (divisor && lane == 0) divisor[row] = nrm;
   if (anynz && __ballot(nz) && lane == 0) atomicOr(anynz, 1);
+}
+
+// The one norms kernel (launch_row_norms2): rows of a, then rows of b
+__global__ __launch_bounds__(256) void row_norms2_kernel(const float* __restrict__ a, const float* __restrict__ b, int B, int K,
+                                                         float floor, float* __restrict__ norms) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= 2 * B) return;
+  const float* src = row < B ? a + static_cast<size_t>(row) * K : b + static_cast<size_t>(row - B) * K;
+  float s = 0.f;
+  for (int k = lane; k < K; k += 64) s = fmaf(src[k], src[k], s);
+  s = sqrtf(wave_sum(s));
+  if (lane == 0) norms[row] = floor > 0.f ? fmaxf(s, floor) : s;
+}
+
+void launch_normalize_rows(const float* a, float* out, float* divisor, int R, int K, float eps, int* anynz, hipStream_t st) {
+  hipLaunchKernelGGL(normalize_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, st, a, out, divisor, R, K, eps, anynz);
+}
+void launch_row_norms2(const float* a, const float* b, int B, int K, float floor, float* norms, hipStream_t st) {
+  hipLaunchKernelGGL(row_norms2_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, st, a, b, B, K, floor, norms);
 }
 
 // ---- DSPH ------------------------------------------------------------------------------------------------
@@ -66,7 +73,7 @@ __global__ __launch_bounds__(256) void dsph_proxy_kernel(const float* __restrict
   }
 #pragma unroll
   for (int t = 0; t < 6; ++t) {
-    const double s = block_sum(v[t], sh);
+    const double s = block_sum_ltr(v[t], sh);
     if (threadIdx.x == 0 && s != 0.0) atomicAdd(&acc[t], s);
   }
 }
@@ -161,7 +168,7 @@ __global__ __launch_bounds__(256) void dsph_pair_kernel(const float* __restrict_
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    const double s = block_sum(v[t], sh);
+    const double s = block_sum_ltr(v[t], sh);
     if (threadIdx.x == 0 && s != 0.0) atomicAdd(&acc[6 + t], s);
   }
 }
@@ -210,7 +217,7 @@ __global__ __launch_bounds__(256) void dchmt_pair_kernel(const float* __restrict
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const double s = block_sum(v[t], sh);
+    const double s = block_sum_ltr(v[t], sh);
     if (threadIdx.x == 0 && s != 0.0) atomicAdd(&acc[t], s);
   }
 }
@@ -231,11 +238,24 @@ __global__ __launch_bounds__(256) void select_rows_kernel(const float* __restric
 
 using namespace cmh;
 
+// Both forwards open a workspace of cmh_loss_workspace_bytes.  HypFwdWs is the larger layout (it fills the query exactly; the two rows
+// after yn are DchmtFwdWs' ia / ta and stay unused here), DchmtFwdWs ends 512 + 4 bk bytes in.
+struct HypFwdWs { double* acc; int* flags_unused; float *xn, *yn, *ia_unused, *ta_unused, *pn; int* multi; size_t total; };
+static HypFwdWs carve_hyp_fwd(void* ws, size_t B, size_t K, size_t C) {
+  Carver c(ws);
+  return {c.take<double>(kAccBytes), c.take<int>(kFlagBytes), c.f32(B * K * 4), c.f32(B * K * 4), c.f32(B * K * 4), c.f32(B * K * 4),
+          c.f32(C * K * 4), c.take<int>(B * 4), c.total()};
+}
+struct DchmtFwdWs { double* acc; int* flags; float *in_, *tn_, *ia, *ta; size_t total; };
+static DchmtFwdWs carve_dchmt_fwd(void* ws, size_t B, size_t D) {
+  Carver c(ws);
+  return {c.take<double>(kAccBytes), c.take<int>(kFlagBytes), c.f32(B * D * 4), c.f32(B * D * 4), c.f32(B * D * 4), c.f32(B * D * 4), c.total()};
+}
+
 extern "C" size_t cmh_loss_workspace_bytes(int32_t B, int32_t K, int32_t C) {
   if (B <= 0 || K <= 0 || C <= 0) return 0;
   const size_t bk = align_up(static_cast<size_t>(B) * K * 4, 256);
-  return 256 /*acc*/ + 256 /*flags*/ + 4 * bk + align_up(static_cast<size_t>(C) * K * 4, 256) +
-         align_up(static_cast<size_t>(B) * 4, 256);
+  return kAccBytes + kFlagBytes + 4 * bk + align_up(static_cast<size_t>(C) * K * 4, 256) + align_up(static_cast<size_t>(B) * 4, 256);
 }
 
 extern "C" int cmh_dsph_hyp_loss(const float* x, const float* y, const float* label, const float* proxies, int32_t B,
@@ -243,28 +263,23 @@ extern "C" int cmh_dsph_hyp_loss(const float* x, const float* y, const float* la
                                  size_t workspace_bytes, void* stream) {
   CMH_CHECK_ARG(x && y && label && proxies && loss && workspace, "dsph_hyp_loss: null pointer");
   CMH_CHECK_ARG(B > 0 && K > 0 && C > 0 && B <= 32768, "dsph_hyp_loss: bad shape B=%d K=%d C=%d", B, K, C);
-  if (workspace_bytes < cmh_loss_workspace_bytes(B, K, C)) return fail(CMH_ERR_WORKSPACE, "dsph_hyp_loss: workspace too small");
+  if (int rc = open_ws("dsph_hyp_loss", workspace, workspace_bytes, cmh_loss_workspace_bytes(B, K, C))) return rc;
+  const HypFwdWs w = carve_hyp_fwd(workspace, B, K, C);
+  assert(w.total <= cmh_loss_workspace_bytes(B, K, C));
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  double* acc = reinterpret_cast<double*>(ws);
-  const size_t bk = align_up(static_cast<size_t>(B) * K * 4, 256);
-  float* xn = reinterpret_cast<float*>(ws + 512);
-  float* yn = reinterpret_cast<float*>(ws + 512 + bk);
-  float* pn = reinterpret_cast<float*>(ws + 512 + 4 * bk);
-  int* multi = reinterpret_cast<int*>(ws + 512 + 4 * bk + align_up(static_cast<size_t>(C) * K * 4, 256));
-  if (hipMemsetAsync(acc, 0, 256, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "dsph_hyp_loss: memset failed");
-  hipLaunchKernelGGL(row_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, x, xn, B, K, 1e-12f, nullptr);
-  hipLaunchKernelGGL(row_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, y, yn, B, K, 1e-12f, nullptr);
-  hipLaunchKernelGGL(row_normalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, proxies, pn, C, K, 1e-12f, nullptr);
-  hipLaunchKernelGGL(dsph_proxy_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, xn, yn, pn, label, B, K, C, threshold, acc);
+  if (hipMemsetAsync(w.acc, 0, kAccBytes, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "dsph_hyp_loss: memset failed");
+  launch_normalize_rows(x, w.xn, nullptr, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(y, w.yn, nullptr, B, K, 1e-12f, nullptr, st);
+  launch_normalize_rows(proxies, w.pn, nullptr, C, K, 1e-12f, nullptr, st);
+  hipLaunchKernelGGL(dsph_proxy_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, w.xn, w.yn, w.pn, label, B, K, C, threshold, w.acc);
   if (alpha > 0.f) {
-    hipLaunchKernelGGL(dsph_multi_kernel, dim3((B + 255) / 256), dim3(256), 0, st, label, B, C, multi);
+    hipLaunchKernelGGL(dsph_multi_kernel, dim3((B + 255) / 256), dim3(256), 0, st, label, B, C, w.multi);
     if (B > 1024)
-      hipLaunchKernelGGL(dsph_pair_kernel<4>, dim3((B + 63) / 64, (B + 63) / 64), dim3(256), 0, st, xn, yn, label, multi, B, K, C, threshold, acc);
+      hipLaunchKernelGGL(dsph_pair_kernel<4>, dim3((B + 63) / 64, (B + 63) / 64), dim3(256), 0, st, w.xn, w.yn, label, w.multi, B, K, C, threshold, w.acc);
     else
-      hipLaunchKernelGGL(dsph_pair_kernel<2>, dim3((B + 31) / 32, (B + 31) / 32), dim3(256), 0, st, xn, yn, label, multi, B, K, C, threshold, acc);
+      hipLaunchKernelGGL(dsph_pair_kernel<2>, dim3((B + 31) / 32, (B + 31) / 32), dim3(256), 0, st, w.xn, w.yn, label, w.multi, B, K, C, threshold, w.acc);
   }
-  hipLaunchKernelGGL(dsph_finalize_kernel, dim3(1), dim3(1), 0, st, acc, alpha, loss);
+  hipLaunchKernelGGL(dsph_finalize_kernel, dim3(1), dim3(1), 0, st, w.acc, alpha, loss);
   CMH_CHECK_LAUNCH("dsph_hyp_loss");
   return CMH_OK;
 }
@@ -276,36 +291,29 @@ extern "C" int cmh_dchmt_loss(const float* img, const float* txt, const float* l
   CMH_CHECK_ARG(B > 0 && D > 0 && C > 0 && B <= 32768, "dchmt_loss: bad shape");
   CMH_CHECK_ARG(similarity == 0 || similarity == 1, "dchmt_loss: similarity must be 0 (euclidean) or 1 (cosine)");
   CMH_CHECK_ARG(loss_type == 1 || loss_type == 2, "dchmt_loss: loss_type must be 1 (l1) or 2 (l2)");
-  if (workspace_bytes < cmh_loss_workspace_bytes(B, D, C)) return fail(CMH_ERR_WORKSPACE, "dchmt_loss: workspace too small");
+  if (int rc = open_ws("dchmt_loss", workspace, workspace_bytes, cmh_loss_workspace_bytes(B, D, C))) return rc;
+  const DchmtFwdWs w = carve_dchmt_fwd(workspace, B, D);
+  assert(w.total <= cmh_loss_workspace_bytes(B, D, C));
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  double* acc = reinterpret_cast<double*>(ws);
-  int* flags = reinterpret_cast<int*>(ws + 256);
-  const size_t bk = align_up(static_cast<size_t>(B) * D * 4, 256);
-  float* in_ = reinterpret_cast<float*>(ws + 512);
-  float* tn_ = reinterpret_cast<float*>(ws + 512 + bk);
-  float* ia = reinterpret_cast<float*>(ws + 512 + 2 * bk);
-  float* ta = reinterpret_cast<float*>(ws + 512 + 3 * bk);
-  if (hipMemsetAsync(ws, 0, 512, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "dchmt_loss: memset failed");
+  if (hipMemsetAsync(w.acc, 0, kAccBytes + kFlagBytes, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "dchmt_loss: memset failed");
   const float* A = img;
   const float* T = txt;
   const float thr = sim_threshold != 0.f ? sim_threshold : 0.05f;   // hash_train.py:82,86-87
   if (similarity == 1) {
     const int64_t n = static_cast<int64_t>(B) * D;
-    hipLaunchKernelGGL(row_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, img, in_, B, D, 0.f, flags);
-    hipLaunchKernelGGL(row_normalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, txt, tn_, B, D, 0.f, flags + 1);
-    hipLaunchKernelGGL(select_rows_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, img, in_, flags, ia, n);
-    hipLaunchKernelGGL(select_rows_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, txt, tn_, flags + 1, ta, n);
-    A = ia;
-    T = ta;
+    launch_normalize_rows(img, w.in_, nullptr, B, D, 0.f, w.flags, st);
+    launch_normalize_rows(txt, w.tn_, nullptr, B, D, 0.f, w.flags + 1, st);
+    hipLaunchKernelGGL(select_rows_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, img, w.in_, w.flags, w.ia, n);
+    hipLaunchKernelGGL(select_rows_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, txt, w.tn_, w.flags + 1, w.ta, n);
+    A = w.ia; T = w.ta;
   }
   const float maxv = sqrtf(static_cast<float>(output_dim) * 2.f * vartheta);   // :101
   const dim3 grid((B * B + 255) / 256);
   const int l2 = loss_type == 2;
-  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, A, T, label, B, D, C, similarity, l2, thr, maxv, acc);
-  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, A, A, label, B, D, C, similarity, l2, thr, maxv, acc);
-  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, T, T, label, B, D, C, similarity, l2, thr, maxv, acc);
-  hipLaunchKernelGGL(dchmt_finalize_kernel, dim3(1), dim3(1), 0, st, acc, B, loss);
+  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, A, T, label, B, D, C, similarity, l2, thr, maxv, w.acc);
+  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, A, A, label, B, D, C, similarity, l2, thr, maxv, w.acc);
+  hipLaunchKernelGGL(dchmt_pair_kernel, grid, dim3(256), 0, st, T, T, label, B, D, C, similarity, l2, thr, maxv, w.acc);
+  hipLaunchKernelGGL(dchmt_finalize_kernel, dim3(1), dim3(1), 0, st, w.acc, B, loss);
   CMH_CHECK_LAUNCH("dchmt_loss");
   return CMH_OK;
 }

@@ -6,35 +6,11 @@
 //   losses                      train/MITH/hash_train.py:80-83,103-147,168-201 (bayesian vs memory bank, InfoNCE,
 //                               token-level InfoNCE, quantisation / distillation squared errors, B = sign(mix))
 // Activations are batch-major ([N, K, D] where the reference holds [K, N, D]); values are identical.
-#include "cmh_common.h"
+// Host structure: cmh_info_nce and cmh_info_nce_backward carve NceWs (its matrix-pipe or its row layout), cmh_mith_bayesian_loss_backward
+// BayesBwdWs; cmh_sq_diff_sum and cmh_mith_bayesian_loss open a workspace of kAccBytes.  Reductions: head_common.h.
+#include "head_common.h"
 
 namespace cmh {
-
-__device__ __forceinline__ float m_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double m_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float m_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double m_block_sum(double v, double* sh) {
-  v = m_wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) t += sh[w];
-  return t;
-}
 
 constexpr int kLtaMaxL = 80;     // tokens per sample (49 patches / <= 77 words)
 constexpr int kLtaMaxK = 128;    // concepts (= hash bits)
@@ -156,17 +132,18 @@ __global__ __launch_bounds__(256) void bitwise_hash_kernel(const float* __restri
     const float4 c = *reinterpret_cast<const float4*>(wr + d);
     s = fmaf(a.x, c.x, s); s = fmaf(a.y, c.y, s); s = fmaf(a.z, c.z, s); s = fmaf(a.w, c.w, s);
   }
-  s = m_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) out[i] = tanhf(s + bias[k]);
 }
 
+// (x * (1 / n), not x / n as launch_normalize_rows: another rounding, so this stays a kernel of its own)
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int R, int D) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   float ss = 0.f;
   for (int d = lane; d < D; d += 64) { const float v = x[static_cast<size_t>(r) * D + d]; ss = fmaf(v, v, ss); }
-  const float inv = 1.0f / fmaxf(sqrtf(m_wave_sum(ss)), 1e-12f);
+  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
   for (int d = lane; d < D; d += 64) y[static_cast<size_t>(r) * D + d] = x[static_cast<size_t>(r) * D + d] * inv;
 }
 
@@ -193,7 +170,7 @@ __global__ __launch_bounds__(256) void sq_diff_kernel(const float* __restrict__ 
     const double d = static_cast<double>(a[i]) - static_cast<double>(b[i]);
     v += d * d;
   }
-  const double s = m_block_sum(v, sh);
+  const double s = block_sum_ltr(v, sh);
   if (threadIdx.x == 0 && s != 0.0) atomicAdd(acc, s);
 }
 
@@ -230,7 +207,7 @@ __global__ __launch_bounds__(256) void bayes_kernel(const float* __restrict__ ba
       v += static_cast<double>((l > 0.f ? s : 0.f) - logf(1.f + expf(s)));
     }
   }
-  const double t = m_block_sum(v, sh);
+  const double t = block_sum_ltr(v, sh);
   if (threadIdx.x == 0 && t != 0.0) atomicAdd(acc, t);
 }
 
@@ -292,7 +269,7 @@ __global__ __launch_bounds__(256) void bayes_mfma_kernel(const float* __restrict
         v += static_cast<double>((l[r] > 0.f ? sv : 0.f) - logf(1.f + expf(sv)));
       }
   }
-  const double t = m_block_sum(v, sh);
+  const double t = block_sum_ltr(v, sh);
   if (threadIdx.x == 0 && t != 0.0) atomicAdd(acc, t);
 }
 
@@ -319,7 +296,7 @@ __global__ __launch_bounds__(256) void row_ce_kernel(const float* __restrict__ a
     mx = fmaxf(mx, s);
     if (g0 + j == i) diag = s;
   }
-  mx = m_wave_max(mx);
+  mx = wave_max(mx);
   float se = 0.f;
   for (int j = lane; j < G; j += 64) {
     const float* br = b + static_cast<size_t>(g0 + j) * D;
@@ -327,8 +304,8 @@ __global__ __launch_bounds__(256) void row_ce_kernel(const float* __restrict__ a
     for (int d = 0; d < D; ++d) s = fmaf(ar[d], br[d], s);
     se += expf(s * inv_temp - mx);
   }
-  se = m_wave_sum(se);
-  diag = m_wave_sum(diag);
+  se = wave_sum(se);
+  diag = wave_sum(diag);
   if (lane == 0) atomicAdd(acc, static_cast<double>(mx + logf(se) - diag));
 }
 
@@ -493,7 +470,7 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
     for (int d = 0; d < D; ++d) s = fmaf(ar[d], br[d], s);
     mx = fmaxf(mx, s * inv_temp);
   }
-  mx = m_wave_max(mx);
+  mx = wave_max(mx);
   float se = 0.f;
   for (int j = lane; j < G; j += 64) {
     const float* br = b + static_cast<size_t>(g0 + j) * D;
@@ -501,7 +478,7 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
     for (int d = 0; d < D; ++d) s = fmaf(ar[d], br[d], s);
     se += expf(s * inv_temp - mx);
   }
-  se = m_wave_sum(se);
+  se = wave_sum(se);
   if (lane == 0) lse[i] = mx + logf(se);
 }
 // d/dx_i of 0.5/R [sum_i CE(x_i . y / T) + sum_i CE(y_i . x / T)] (diagonal targets inside the group):
@@ -588,10 +565,10 @@ __global__ __launch_bounds__(256) void nce_lse_kernel(const float* __restrict__ 
     const float* row = Sg + static_cast<size_t>(i) * G;
     float mx = -1e30f;
     for (int j = lane; j < G; j += 64) mx = fmaxf(mx, row[j]);
-    mx = m_wave_max(mx);
+    mx = wave_max(mx);
     float se = 0.f;
     for (int j = lane; j < G; j += 64) se += expf(row[j] - mx);
-    se = m_wave_sum(se);
+    se = wave_sum(se);
     const float l = mx + logf(se);
     if (lane == 0) {
       if (lse_row) lse_row[static_cast<size_t>(grp) * G + i] = l;
@@ -618,7 +595,7 @@ __global__ __launch_bounds__(256) void nce_lse_kernel(const float* __restrict__ 
     if (lse_col) lse_col[static_cast<size_t>(grp) * G + j] = l;
     v += static_cast<double>(l - Sg[static_cast<size_t>(j) * G + j]);
   }
-  const double t = m_block_sum(v, sh);
+  const double t = block_sum_ltr(v, sh);
   if (acc && threadIdx.x == 0 && t != 0.0) atomicAdd(acc, t);
 }
 
@@ -731,7 +708,7 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
   const float* gr = dy + static_cast<size_t>(row) * D;
   float ss = 0.f, sg = 0.f;
   for (int d = lane; d < D; d += 64) { ss = fmaf(xr[d], xr[d], ss); sg = fmaf(xr[d], gr[d], sg); }
-  ss = m_wave_sum(ss); sg = m_wave_sum(sg);
+  ss = wave_sum(ss); sg = wave_sum(sg);
   const float nrm = sqrtf(ss);
   const float inv = 1.0f / fmaxf(nrm, 1e-12f);
   // below the eps clamp y = x / eps is linear: dx = dy / eps
@@ -778,7 +755,7 @@ __global__ __launch_bounds__(256) void bithash_dw_kernel(const float* __restrict
   if (blockIdx.y == 0) {                       // db[k]: lanes across the wave's samples, wave sums in wave order
     float sb = 0.f;
     for (int n = n0 + lane; n < n1; n += 64) { const size_t i = static_cast<size_t>(n) * K + k; sb += dy[i] * (1.0f - y[i] * y[i]); }
-    sb = m_wave_sum(sb);
+    sb = wave_sum(sb);
     if (lane == 0) redb[wid] = sb;
   }
   __syncthreads();
@@ -842,7 +819,8 @@ static bool bayes_mfma_off() {   // CMH_BAYES_MFMA=0: the butterfly kernels (A/B
 
 extern "C" int cmh_sq_diff_sum(const float* a, const float* b, int64_t n, float* out, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  CMH_CHECK_ARG(a && b && out && workspace && n > 0 && workspace_bytes >= 256, "sq_diff_sum: bad arguments");
+  CMH_CHECK_ARG(a && b && out && workspace && n > 0, "sq_diff_sum: bad arguments");
+  if (int rc = open_ws("sq_diff_sum", workspace, workspace_bytes, kAccBytes, CMH_ERR_INVALID)) return rc;
   hipStream_t st = as_stream(stream);
   double* acc = static_cast<double*>(workspace);
   if (hipMemsetAsync(acc, 0, 8, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "sq_diff_sum: memset failed");
@@ -856,7 +834,8 @@ extern "C" int cmh_sq_diff_sum(const float* a, const float* b, int64_t n, float*
 extern "C" int cmh_mith_bayesian_loss(const float* bank, const float* batch, const float* bank_label, const float* label,
                                       int32_t Mb, int32_t B, int32_t K, int32_t C, float* out, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(bank && batch && bank_label && label && out && workspace && workspace_bytes >= 256, "mith_bayesian_loss: bad arguments");
+  CMH_CHECK_ARG(bank && batch && bank_label && label && out && workspace, "mith_bayesian_loss: bad arguments");
+  if (int rc = open_ws("mith_bayesian_loss", workspace, workspace_bytes, kAccBytes, CMH_ERR_INVALID)) return rc;
   CMH_CHECK_ARG(Mb > 0 && B > 0 && K > 0 && C > 0, "mith_bayesian_loss: bad shape");
   hipStream_t st = as_stream(stream);
   double* acc = static_cast<double*>(workspace);
@@ -871,20 +850,27 @@ extern "C" int cmh_mith_bayesian_loss(const float* bank, const float* batch, con
   return CMH_OK;
 }
 
-// workspace of the matrix-pipe path of cmh_info_nce / cmh_info_nce_backward: 256 bytes of accumulators, the R x G scores, two R-vectors
-extern "C" size_t cmh_info_nce_workspace_bytes(int32_t R, int32_t G) {
-  return R > 0 && G > 0 ? 256 + (static_cast<size_t>(R) * G + 2 * static_cast<size_t>(R)) * 4 + 256 : 0;
+// InfoNCE's two layouts.  Matrix pipe (what cmh_info_nce_workspace_bytes asks for; from the workspace's own base): the accumulators, the R x G
+// scores and both directions' log-sum-exps, packed.  Rows (the backward on a smaller workspace; from its first 256-byte boundary): the latter.
+struct NceWs { double* acc; float *S, *lse_row, *lse_col; size_t total; };
+static NceWs carve_nce(void* ws, size_t R, size_t G, bool mfma) {
+  Carver c(ws, !mfma);
+  if (mfma) return {c.take<double>(kAccBytes), c.f32(R * G * 4, 4), c.f32(R * 4, 4), c.f32(R * 4, 4), c.total(256)};
+  return {nullptr, nullptr, c.f32(R * 4, 4), c.f32(R * 4, 4), c.total()};
 }
+
+extern "C" size_t cmh_info_nce_workspace_bytes(int32_t R, int32_t G) { return R > 0 && G > 0 ? carve_nce(nullptr, R, G, true).total : 0; }
 
 extern "C" int cmh_info_nce(const float* a, const float* b, int32_t R, int32_t G, int32_t D, float temperature, float* out,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(a && b && out && workspace && workspace_bytes >= 256, "info_nce: bad arguments");
+  CMH_CHECK_ARG(a && b && out && workspace, "info_nce: bad arguments");
+  if (int rc = open_ws("info_nce", workspace, workspace_bytes, kAccBytes, CMH_ERR_INVALID)) return rc;
   CMH_CHECK_ARG(R > 0 && G > 0 && R % G == 0 && D > 0 && D <= 4096 && temperature > 0.f, "info_nce: bad shape");
   hipStream_t st = as_stream(stream);
   double* acc = static_cast<double*>(workspace);
   if (hipMemsetAsync(acc, 0, 8, st) != hipSuccess) return fail(CMH_ERR_LAUNCH, "info_nce: memset failed");
-  if (D % 64 == 0 && workspace_bytes >= cmh_info_nce_workspace_bytes(R, G) && !bayes_mfma_off()) {
-    float* S = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
+  if (D % 64 == 0 && workspace_bytes >= carve_nce(nullptr, R, G, true).total && !bayes_mfma_off()) {
+    float* S = carve_nce(workspace, R, G, true).S;
     const long tiles = static_cast<long>(R / G) * ((G + 15) / 16) * ((G + 15) / 16);
     hipLaunchKernelGGL(nce_scores_kernel, dim3(static_cast<unsigned>((tiles + 3) / 4)), dim3(256), 0, st, a, b, R, G, D, 1.0f / temperature, S);
     hipLaunchKernelGGL(nce_lse_kernel, dim3(R / G, (G + 63) / 64), dim3(256), 0, st, S, G, static_cast<float*>(nullptr),
@@ -945,8 +931,11 @@ extern "C" int cmh_bitwise_hash_backward(const float* x, const float* w, const f
   return CMH_OK;
 }
 
+struct BayesBwdWs { float* partial; size_t total; };      // [kBayesSlices, B, K] partial gradients
+static BayesBwdWs carve_bayes_bwd(void* ws, size_t B, size_t K) { Carver c(ws, true); return {c.f32(kBayesSlices * B * K * 4, 4), c.total()}; }
+
 extern "C" size_t cmh_mith_bayesian_backward_workspace_bytes(int32_t B, int32_t K) {
-  return B > 0 && K > 0 ? static_cast<size_t>(kBayesSlices) * B * K * 4 + 256 : 0;
+  return B > 0 && K > 0 ? carve_bayes_bwd(nullptr, B, K).total : 0;
 }
 
 extern "C" int cmh_mith_bayesian_loss_backward(const float* bank, const float* batch, const float* bank_label, const float* label,
@@ -955,8 +944,8 @@ extern "C" int cmh_mith_bayesian_loss_backward(const float* bank, const float* b
   CMH_CHECK_ARG(bank && batch && bank_label && label && dbatch && workspace, "mith_bayesian_loss_backward: null pointer");
   CMH_CHECK_ARG(Mb > 0 && B > 0 && K > 0 && K <= 128 && C > 0, "mith_bayesian_loss_backward: bad shape (K <= 128)");
   CMH_CHECK_ARG((Mb + kBayesSlices - 1) / kBayesSlices <= kBayesMaxRows, "mith_bayesian_loss_backward: bank of %d rows is too large", Mb);
-  if (workspace_bytes < cmh_mith_bayesian_backward_workspace_bytes(B, K)) return fail(CMH_ERR_WORKSPACE, "mith_bayesian_loss_backward: workspace too small");
-  float* partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
+  if (int rc = open_ws("mith_bayesian_loss_backward", workspace, workspace_bytes, carve_bayes_bwd(nullptr, B, K).total)) return rc;
+  float* partial = carve_bayes_bwd(workspace, B, K).partial;
   hipStream_t st = as_stream(stream);
   if (K % 16 == 0 && C <= 128 && !bayes_mfma_off())
     hipLaunchKernelGGL(bayes_bwd_mfma_kernel, dim3((B + 15) / 16, kBayesSlices), dim3(256), 0, st, bank, batch, bank_label, label, Mb, B, K, C, dloss, partial);
@@ -972,15 +961,12 @@ extern "C" int cmh_info_nce_backward(const float* a, const float* b, int32_t R, 
   CMH_CHECK_ARG(a && b && da && db && workspace, "info_nce_backward: null pointer");
   CMH_CHECK_ARG(R > 0 && G > 0 && R % G == 0 && D > 0 && temperature > 0.f, "info_nce_backward: bad shape R=%d G=%d D=%d", R, G, D);
   CMH_CHECK_ARG(static_cast<size_t>(4) * (D + G) * 4 <= 64 * 1024, "info_nce_backward: D + G = %d too large for the LDS rows", D + G);
-  if (workspace_bytes < static_cast<size_t>(2) * R * 4 + 256) return fail(CMH_ERR_WORKSPACE, "info_nce_backward: workspace must hold 2 R floats");
-  float* lse_a = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-  float* lse_b = lse_a + R;
+  if (int rc = open_ws("info_nce_backward", workspace, workspace_bytes, carve_nce(nullptr, R, G, false).total)) return rc;
   hipStream_t st = as_stream(stream);
   const float it = 1.0f / temperature;
-  if (D % 64 == 0 && workspace_bytes >= cmh_info_nce_workspace_bytes(R, G) && !bayes_mfma_off()) {
-    float* S = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-    float* lr = S + static_cast<size_t>(R) * G;
-    float* lc = lr + R;
+  if (D % 64 == 0 && workspace_bytes >= carve_nce(nullptr, R, G, true).total && !bayes_mfma_off()) {
+    const NceWs w = carve_nce(workspace, R, G, true);
+    float *S = w.S, *lr = w.lse_row, *lc = w.lse_col;
     const int tg = (G + 15) / 16;
     const long tiles = static_cast<long>(R / G) * tg * tg, gw = static_cast<long>(R / G) * tg * (D / 64);
     const size_t n = static_cast<size_t>(R) * G;
@@ -993,6 +979,8 @@ extern "C" int cmh_info_nce_backward(const float* a, const float* b, int32_t R, 
     CMH_CHECK_LAUNCH("info_nce_backward");
     return CMH_OK;
   }
+  const NceWs w = carve_nce(workspace, R, G, false);
+  float *lse_a = w.lse_row, *lse_b = w.lse_col;
   const dim3 grid((R + 3) / 4);
   hipLaunchKernelGGL(row_lse_kernel, grid, dim3(256), static_cast<size_t>(4) * D * 4, st, a, b, R, G, D, it, lse_a);
   hipLaunchKernelGGL(row_lse_kernel, grid, dim3(256), static_cast<size_t>(4) * D * 4, st, b, a, R, G, D, it, lse_b);

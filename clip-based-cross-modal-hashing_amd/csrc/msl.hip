@@ -14,7 +14,9 @@
 //   d loss / d sim_ij = (1/B) * [ -exp(-2 (s - 0.5)) / (1 + sum_pos) | +exp(40 (s - 0.5)) / (1 + sum_neg) ]  on the mined entries,
 // then through the row normalisation, dS_i = (g_i - sim_i (sim_i . g_i)) / |S_i|, and dfeats = dS . feat2, dfeat2 = dS^T . feats
 // (feat2 = feats: the two are added).  B = 256, K = 64: 4 MFLOP per call - launch-latency-bound like every loss kernel of the path.
-#include "cmh_common.h"
+// Host structure: the two MSL entries carve MslWs, the two SPL entries SplWs (MslWs and the row norms behind it, from launch_row_norms2 of
+// losses.hip with F.normalize's floor 1e-12); msl_check / spl_check are their shared argument and workspace checks.
+#include "head_common.h"
 
 namespace cmh {
 
@@ -28,26 +30,12 @@ struct MslWs {
   float* row;       // [B, 8]  |S_i| clamped, min(pos_), max(neg_), sum_pos, sum_neg, valid, loss_i, unused
   size_t total;
 };
-static MslWs msl_carve(void* ws, size_t B) {
-  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~static_cast<uintptr_t>(255));
-  MslWs w;
-  size_t off = 0;
-  w.S = reinterpret_cast<float*>(p + off); off += align_up(B * B * 4, 256);
-  w.G = reinterpret_cast<float*>(p + off); off += align_up(B * B * 4, 256);
-  w.same = reinterpret_cast<uint8_t*>(p + off); off += align_up(B * B, 256);
-  w.row = reinterpret_cast<float*>(p + off); off += align_up(B * 8 * 4, 256);
-  w.total = off + 256;
-  return w;
-}
-
-template <typename T, typename Op>
-__device__ __forceinline__ T msl_block_reduce(T v, T* red, Op op) {      // over the 256 threads of a workgroup
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return op(op(red[0], red[1]), op(red[2], red[3]));
+static MslWs carve_msl(Carver& c, size_t B) { return {c.f32(B * B * 4), c.f32(B * B * 4), c.take<uint8_t>(B * B), c.f32(B * 8 * 4), c.total()}; }
+static MslWs carve_msl(void* ws, size_t B) { Carver c(ws, true); return carve_msl(c, B); }
+struct SplWs { MslWs m; float* norms; size_t total; };     // norms: |a_i| then |b_i|, each >= 1e-12
+static SplWs carve_spl(void* ws, size_t B) {
+  Carver c(ws, true);
+  return {carve_msl(c, B), c.f32(B * 8), c.total()};
 }
 
 // row statistics of the forward (also the first half of the backward)
@@ -76,7 +64,7 @@ __global__ __launch_bounds__(256) void msl_rows_kernel(const float* __restrict__
   }
   auto addf = [](float a, float b) { return a + b; };
   auto addi = [](int a, int b) { return a + b; };
-  const float norm = sqrtf(msl_block_reduce(sumsq, redf, addf));
+  const float norm = sqrtf(block_reduce_pairwise(sumsq, redf, addf));
   const float denom = fmaxf(norm, 1e-12f);
   float mn = 3.0e38f, mx = -3.0e38f;
   int cp = 0, cn = 0;
@@ -85,10 +73,10 @@ __global__ __launch_bounds__(256) void msl_rows_kernel(const float* __restrict__
     if (Li[j]) { if (s < 1.0f - kMslEps) { mn = fminf(mn, s); ++cp; } }
     else { mx = fmaxf(mx, s); ++cn; }
   }
-  mn = msl_block_reduce(mn, redf, [](float a, float b) { return fminf(a, b); });
-  mx = msl_block_reduce(mx, redf, [](float a, float b) { return fmaxf(a, b); });
-  cp = msl_block_reduce(cp, redi, addi);
-  cn = msl_block_reduce(cn, redi, addi);
+  mn = block_reduce_pairwise(mn, redf, [](float a, float b) { return fminf(a, b); });
+  mx = block_reduce_pairwise(mx, redf, [](float a, float b) { return fmaxf(a, b); });
+  cp = block_reduce_pairwise(cp, redi, addi);
+  cn = block_reduce_pairwise(cn, redi, addi);
   float sp = 0.f, sn = 0.f;
   int np_ = 0, nn = 0;
   if (cp > 0 && cn > 0) {
@@ -99,10 +87,10 @@ __global__ __launch_bounds__(256) void msl_rows_kernel(const float* __restrict__
       } else if (s + kMslMargin > mn) { sn += expf(kMslScaleNeg * (s - kMslThresh)); ++nn; }
     }
   }
-  sp = msl_block_reduce(sp, redf, addf);
-  sn = msl_block_reduce(sn, redf, addf);
-  np_ = msl_block_reduce(np_, redi, addi);
-  nn = msl_block_reduce(nn, redi, addi);
+  sp = block_reduce_pairwise(sp, redf, addf);
+  sn = block_reduce_pairwise(sn, redf, addf);
+  np_ = block_reduce_pairwise(np_, redi, addi);
+  nn = block_reduce_pairwise(nn, redi, addi);
   if (tid == 0) {
     const bool valid = cp > 0 && cn > 0 && np_ > 0 && nn > 0;
     float* r = w.row + static_cast<size_t>(i) * 8;
@@ -143,7 +131,7 @@ __global__ __launch_bounds__(256) void msl_bwd_rows_kernel(const float* __restri
     grow[j] = g;
     dot = fmaf(s, g, dot);
   }
-  dot = msl_block_reduce(dot, redf, [](float a, float b) { return a + b; });
+  dot = block_reduce_pairwise(dot, redf, [](float a, float b) { return a + b; });
   const bool clamped = r[7] < 1e-12f;                 // F.normalize divided by eps: no projection term
   float* Gi = w.G + static_cast<size_t>(i) * B;
   for (int j = tid; j < B; j += 256) {
@@ -198,18 +186,6 @@ __global__ __launch_bounds__(256) void msl_bwd_cols_kernel(const float* __restri
 // Backward (weights are constants): d loss / d s_ij = (1 / (B tau)) [ e w (1 / (P_i + N_i)) - same_ij e w+ / P_i ], then through both
 // normalisations; a = b (the image-image / text-text calls): the two roles' gradients are added.
 // Workspace use: S = the cosines, same bits, row[i] = {P_i, N_i, loss_i}, G = d loss / d s, norms after row.
-__global__ __launch_bounds__(256) void spl_norms_kernel(const float* __restrict__ a, const float* __restrict__ b, int B, int K,
-                                                        float* __restrict__ norms) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= 2 * B) return;
-  const float* src = row < B ? a + static_cast<size_t>(row) * K : b + static_cast<size_t>(row - B) * K;
-  float s = 0.f;
-  for (int k = lane; k < K; k += 64) s = fmaf(src[k], src[k], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) norms[row] = fmaxf(sqrtf(s), 1e-12f);
-}
-
 __global__ __launch_bounds__(256) void spl_rows_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ lab, const float* __restrict__ norms, int B, int K,
                                                        int C, float inv_tau, float delta, MslWs w) {
@@ -239,8 +215,8 @@ __global__ __launch_bounds__(256) void spl_rows_kernel(const float* __restrict__
     else Nn += e * expf((-1.f + s) * delta);
   }
   auto addf = [](float x, float y) { return x + y; };
-  P = msl_block_reduce(P, redf, addf);
-  Nn = msl_block_reduce(Nn, redf, addf);
+  P = block_reduce_pairwise(P, redf, addf);
+  Nn = block_reduce_pairwise(Nn, redf, addf);
   if (tid == 0) {
     float* r = w.row + static_cast<size_t>(i) * 8;
     r[0] = P; r[1] = Nn; r[6] = -logf(P / (Nn + P));
@@ -289,7 +265,7 @@ __global__ __launch_bounds__(256) void spl_bwd_rows_kernel(const float* __restri
       dot = fmaf(dv[q], a[static_cast<size_t>(i) * K + k] / na, dot);
     }
   }
-  dot = msl_block_reduce(dot, redf, [](float x, float y) { return x + y; });
+  dot = block_reduce_pairwise(dot, redf, [](float x, float y) { return x + y; });
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int k = tid + 256 * q;
@@ -325,7 +301,7 @@ __global__ __launch_bounds__(256) void spl_bwd_cols_kernel(const float* __restri
       dot = fmaf(dv[q], b[static_cast<size_t>(j) * K + k] / nb, dot);
     }
   }
-  dot = msl_block_reduce(dot, redf, [](float x, float y) { return x + y; });
+  dot = block_reduce_pairwise(dot, redf, [](float x, float y) { return x + y; });
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int k = tid + 256 * q;
@@ -348,15 +324,14 @@ static constexpr int kMslMaxB = 8192;
 
 extern "C" size_t cmh_spl_workspace_bytes(int32_t B) {
   if (B <= 0) return 0;
-  return msl_carve(nullptr, static_cast<size_t>(B)).total + align_up(static_cast<size_t>(B) * 8, 256);
+  return carve_spl(nullptr, B).total;
 }
 
 static int spl_check(const float* a, const float* labels, int B, int K, int C, float tau, float delta, void* ws, size_t ws_bytes, const char* what) {
   CMH_CHECK_ARG(a && labels && ws, "%s: null pointer", what);
   CMH_CHECK_ARG(B > 0 && B <= kMslMaxB && K > 0 && K <= kMslMaxK && C > 0 && C <= kMslMaxK, "%s: bad shape B=%d K=%d C=%d", what, B, K, C);
   CMH_CHECK_ARG(tau > 0.f && delta >= 0.f && delta <= 1.f, "%s: temperature %g, delta %g", what, tau, delta);
-  if (ws_bytes < cmh_spl_workspace_bytes(B)) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, cmh_spl_workspace_bytes(B));
-  return CMH_OK;
+  return open_ws(what, ws, ws_bytes, carve_spl(nullptr, B).total);
 }
 
 extern "C" int cmh_spl_loss(const float* a, const float* b, const float* labels, int32_t B, int32_t K, int32_t C, float temperature,
@@ -364,12 +339,12 @@ extern "C" int cmh_spl_loss(const float* a, const float* b, const float* labels,
   int rc = spl_check(a, labels, B, K, C, temperature, delta, workspace, workspace_bytes, "spl_loss");
   if (rc) return rc;
   CMH_CHECK_ARG(loss, "spl_loss: null pointer");
-  const MslWs w = msl_carve(workspace, static_cast<size_t>(B));
-  float* norms = reinterpret_cast<float*>(reinterpret_cast<char*>(w.row) + align_up(static_cast<size_t>(B) * 32, 256));
+  const SplWs sw = carve_spl(workspace, B);
+  const MslWs& w = sw.m;
   hipStream_t st = as_stream(stream);
   const float* bb = b ? b : a;
-  hipLaunchKernelGGL(spl_norms_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, st, a, bb, B, K, norms);
-  hipLaunchKernelGGL(spl_rows_kernel, dim3(B), dim3(256), 0, st, a, bb, labels, norms, B, K, C, 1.0f / temperature, delta, w);
+  launch_row_norms2(a, bb, B, K, 1e-12f, sw.norms, st);
+  hipLaunchKernelGGL(spl_rows_kernel, dim3(B), dim3(256), 0, st, a, bb, labels, sw.norms, B, K, C, 1.0f / temperature, delta, w);
   hipLaunchKernelGGL(msl_sum_kernel, dim3(1), dim3(64), 0, st, w.row, B, loss);
   CMH_CHECK_LAUNCH("spl_loss");
   return CMH_OK;
@@ -381,29 +356,28 @@ extern "C" int cmh_spl_loss_backward(const float* a, const float* b, const float
   int rc = spl_check(a, labels, B, K, C, temperature, delta, workspace, workspace_bytes, "spl_loss_backward");
   if (rc) return rc;
   CMH_CHECK_ARG(da && (!b || db), "spl_loss_backward: null gradient pointer");
-  const MslWs w = msl_carve(workspace, static_cast<size_t>(B));
-  float* norms = reinterpret_cast<float*>(reinterpret_cast<char*>(w.row) + align_up(static_cast<size_t>(B) * 32, 256));
+  const SplWs sw = carve_spl(workspace, B);
+  const MslWs& w = sw.m;
   hipStream_t st = as_stream(stream);
   const float* bb = b ? b : a;
   const size_t lds = static_cast<size_t>(B) * 4;
-  hipLaunchKernelGGL(spl_norms_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, st, a, bb, B, K, norms);
-  hipLaunchKernelGGL(spl_rows_kernel, dim3(B), dim3(256), 0, st, a, bb, labels, norms, B, K, C, 1.0f / temperature, delta, w);
-  hipLaunchKernelGGL(spl_bwd_rows_kernel, dim3(B), dim3(256), lds, st, a, bb, norms, B, K, 1.0f / temperature, delta, w, dloss, da);
-  hipLaunchKernelGGL(spl_bwd_cols_kernel, dim3(B), dim3(256), lds, st, a, bb, norms, B, K, w, b ? 0 : 1, b ? db : da);
+  launch_row_norms2(a, bb, B, K, 1e-12f, sw.norms, st);
+  hipLaunchKernelGGL(spl_rows_kernel, dim3(B), dim3(256), 0, st, a, bb, labels, sw.norms, B, K, C, 1.0f / temperature, delta, w);
+  hipLaunchKernelGGL(spl_bwd_rows_kernel, dim3(B), dim3(256), lds, st, a, bb, sw.norms, B, K, 1.0f / temperature, delta, w, dloss, da);
+  hipLaunchKernelGGL(spl_bwd_cols_kernel, dim3(B), dim3(256), lds, st, a, bb, sw.norms, B, K, w, b ? 0 : 1, b ? db : da);
   CMH_CHECK_LAUNCH("spl_loss_backward");
   return CMH_OK;
 }
 
 extern "C" size_t cmh_msl_workspace_bytes(int32_t B) {
   if (B <= 0) return 0;
-  return msl_carve(nullptr, static_cast<size_t>(B)).total;
+  return carve_msl(nullptr, B).total;
 }
 
 static int msl_check(const float* x, const float* labels, int B, int K, int Kl, void* workspace, size_t workspace_bytes, const char* what) {
   CMH_CHECK_ARG(x && labels && workspace, "%s: null pointer", what);
   CMH_CHECK_ARG(B > 0 && B <= kMslMaxB && K > 0 && K <= kMslMaxK && Kl > 0 && Kl <= kMslMaxK, "%s: bad shape B=%d K=%d Kl=%d", what, B, K, Kl);
-  if (workspace_bytes < cmh_msl_workspace_bytes(B)) return fail(CMH_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, cmh_msl_workspace_bytes(B));
-  return CMH_OK;
+  return open_ws(what, workspace, workspace_bytes, carve_msl(nullptr, B).total);
 }
 
 extern "C" int cmh_msl_loss(const float* feats, const float* feat2, const float* labels, int32_t B, int32_t K, int32_t Kl, float* loss,
@@ -411,7 +385,7 @@ extern "C" int cmh_msl_loss(const float* feats, const float* feat2, const float*
   int rc = msl_check(feats, labels, B, K, Kl, workspace, workspace_bytes, "msl_loss");
   if (rc) return rc;
   CMH_CHECK_ARG(loss, "msl_loss: null pointer");
-  const MslWs w = msl_carve(workspace, static_cast<size_t>(B));
+  const MslWs w = carve_msl(workspace, B);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(msl_rows_kernel, dim3(B), dim3(256), 0, st, feats, feat2 ? feat2 : feats, labels, B, K, Kl, w);
   hipLaunchKernelGGL(msl_sum_kernel, dim3(1), dim3(64), 0, st, w.row, B, loss);
@@ -425,7 +399,7 @@ extern "C" int cmh_msl_loss_backward(const float* feats, const float* feat2, con
   int rc = msl_check(feats, labels, B, K, Kl, workspace, workspace_bytes, "msl_loss_backward");
   if (rc) return rc;
   CMH_CHECK_ARG(dfeats && (!feat2 || dfeat2), "msl_loss_backward: null gradient pointer");
-  const MslWs w = msl_carve(workspace, static_cast<size_t>(B));
+  const MslWs w = carve_msl(workspace, B);
   hipStream_t st = as_stream(stream);
   const float* y = feat2 ? feat2 : feats;
   const size_t lds = static_cast<size_t>(B) * 4;

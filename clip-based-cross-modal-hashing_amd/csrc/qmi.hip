@@ -10,33 +10,12 @@
 // column i: YT_ji), its 256 threads stride over j, every pair costs four K-long dot products out of LDS / L2.  The forward leaves
 // per-row partial sums (in f64) that a one-wave kernel adds in row order, so the value does not depend on scheduling; the backward
 // reuses sum(D) from the forward.  B = 256, K = 64: 17 MFLOP - launch-latency-bound, like every loss kernel of the path.
-#include "cmh_common.h"
+// Host structure: cmh_qmi_loss and cmh_qmi_loss_backward carve QmiWs; the norms come from launch_row_norms2 (losses.hip), floor 0.
+#include "head_common.h"
 
 namespace cmh {
 
 constexpr int kQmiMaxK = 1024;
-
-__device__ __forceinline__ float qmi_block_sum(float v, float* red) {   // sum over the 256 threads of a workgroup
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-// norms[0][i] = |x_i|, norms[1][i] = |t_i|
-__global__ __launch_bounds__(256) void qmi_norms_kernel(const float* __restrict__ x, const float* __restrict__ t, int B, int K,
-                                                        float* __restrict__ norms) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= 2 * B) return;
-  const float* src = row < B ? x + static_cast<size_t>(row) * K : t + static_cast<size_t>(row - B) * K;
-  float s = 0.f;
-  for (int k = lane; k < K; k += 64) s = fmaf(src[k], src[k], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) norms[row] = sqrtf(s);
-}
 
 // BWD = false: part[i] = {sum_j in-terms, sum_j S^2 terms, sum_j D_ij}  (f64 x 3 per row)
 // BWD = true : dx[i], dt[i] = gradient rows (scaled by gscale[0]); inv_m = sum(D) / B^2 from the forward
@@ -117,7 +96,7 @@ __global__ __launch_bounds__(256) void qmi_rows_kernel(const float* __restrict__
     }
   }
   if (!BWD) {
-    const float a = qmi_block_sum(in_sum, red), b = qmi_block_sum(sq_sum, red), c = qmi_block_sum(d_sum, red);
+    const float a = block_sum_ltr(in_sum, red), b = block_sum_ltr(sq_sum, red), c = block_sum_ltr(d_sum, red);
     if (tid == 0) { part[3 * i] = a; part[3 * i + 1] = b; part[3 * i + 2] = c; }
     return;
   }
@@ -133,7 +112,7 @@ __global__ __launch_bounds__(256) void qmi_rows_kernel(const float* __restrict__
     px = fmaf(x[static_cast<size_t>(i) * K + k], gx[k], px);
     pt = fmaf(t[static_cast<size_t>(i) * K + k], gt[k], pt);
   }
-  const float dotx = qmi_block_sum(px, red), dott = qmi_block_sum(pt, red);
+  const float dotx = block_sum_ltr(px, red), dott = block_sum_ltr(pt, red);
   const float gs = gscale[0];
   const float cx = nx > 0.f ? dotx / (nx * (nx + eps) * (nx + eps)) : 0.f;
   const float ct = nt > 0.f ? dott / (nt * (nt + eps) * (nt + eps)) : 0.f;
@@ -158,9 +137,10 @@ __global__ __launch_bounds__(64) void qmi_finalize_kernel(const double* __restri
 
 using namespace cmh;
 
-extern "C" size_t cmh_qmi_workspace_bytes(int32_t B) {
-  return B > 0 ? align_up(static_cast<size_t>(B) * 3 * sizeof(double), 256) + align_up(static_cast<size_t>(B) * 2 * sizeof(float), 256) : 0;
-}
+struct QmiWs { double* part; float* norms; size_t total; };     // [B, 3] row partials (forward), norms[0][i] = |x_i|, norms[1][i] = |t_i|
+static QmiWs carve_qmi(void* ws, size_t B) { Carver c(ws); return {c.take<double>(B * 3 * sizeof(double)), c.f32(B * 2 * sizeof(float)), c.total()}; }
+
+extern "C" size_t cmh_qmi_workspace_bytes(int32_t B) { return B > 0 ? carve_qmi(nullptr, B).total : 0; }
 
 static int qmi_check(const void* a, const void* b, const void* c, int B, int K, int C) {
   CMH_CHECK_ARG(a && b && c, "qmi_loss: null pointer");
@@ -172,14 +152,14 @@ extern "C" int cmh_qmi_loss(const float* img, const float* txt, const uint32_t* 
                             float eps, float* loss, float* sum_d, void* workspace, size_t workspace_bytes, void* stream) {
   int rc = qmi_check(img, txt, labels_packed, B, K, C);
   if (rc) return rc;
-  CMH_CHECK_ARG(loss && sum_d && workspace && workspace_bytes >= cmh_qmi_workspace_bytes(B), "qmi_loss: outputs / workspace");
+  CMH_CHECK_ARG(loss && sum_d, "qmi_loss: outputs");
+  if ((rc = open_ws("qmi_loss", workspace, workspace_bytes, carve_qmi(nullptr, B).total, CMH_ERR_INVALID))) return rc;
+  const QmiWs w = carve_qmi(workspace, B);
   hipStream_t st = as_stream(stream);
-  double* part = static_cast<double*>(workspace);
-  float* norms = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(static_cast<size_t>(B) * 3 * sizeof(double), 256));
-  hipLaunchKernelGGL(qmi_norms_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, st, img, txt, B, K, norms);
-  hipLaunchKernelGGL(qmi_rows_kernel<false>, dim3(B), dim3(256), 0, st, img, txt, labels_packed, norms, B, K, (C + 31) / 32, eps, part,
+  launch_row_norms2(img, txt, B, K, 0.f, w.norms, st);
+  hipLaunchKernelGGL(qmi_rows_kernel<false>, dim3(B), dim3(256), 0, st, img, txt, labels_packed, w.norms, B, K, (C + 31) / 32, eps, w.part,
                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(qmi_finalize_kernel, dim3(1), dim3(64), 0, st, part, B, loss, sum_d);
+  hipLaunchKernelGGL(qmi_finalize_kernel, dim3(1), dim3(64), 0, st, w.part, B, loss, sum_d);
   CMH_CHECK_LAUNCH("qmi_loss");
   return CMH_OK;
 }
@@ -189,10 +169,11 @@ extern "C" int cmh_qmi_loss_backward(const float* img, const float* txt, const u
                                      size_t workspace_bytes, void* stream) {
   int rc = qmi_check(img, txt, labels_packed, B, K, C);
   if (rc) return rc;
-  CMH_CHECK_ARG(sum_d && dloss && dimg && dtxt && workspace && workspace_bytes >= cmh_qmi_workspace_bytes(B), "qmi_loss_backward: arguments");
+  CMH_CHECK_ARG(sum_d && dloss && dimg && dtxt, "qmi_loss_backward: arguments");
+  if ((rc = open_ws("qmi_loss_backward", workspace, workspace_bytes, carve_qmi(nullptr, B).total, CMH_ERR_INVALID))) return rc;
+  float* norms = carve_qmi(workspace, B).norms;
   hipStream_t st = as_stream(stream);
-  float* norms = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(static_cast<size_t>(B) * 3 * sizeof(double), 256));
-  hipLaunchKernelGGL(qmi_norms_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, st, img, txt, B, K, norms);
+  launch_row_norms2(img, txt, B, K, 0.f, norms, st);
   hipLaunchKernelGGL(qmi_rows_kernel<true>, dim3(B), dim3(256), 0, st, img, txt, labels_packed, norms, B, K, (C + 31) / 32, eps, nullptr,
                      sum_d, dloss, dimg, dtxt);
   CMH_CHECK_LAUNCH("qmi_loss_backward");
