@@ -148,6 +148,22 @@ struct GemmPlan {
 int plan_gemm(int dt, const GemmProblem& a, const GemmProblem* b, int epi, GemmPlan* p);   // gemm.hip; b: a grouped request
 int gemm_cus();                    // gemm.hip: the CU count the persistent grids are sized for (whole groups of 8; 256 without a GPU)
 int gemm_order_group(int N);       // gemm.hip: n-panels per group of the wide kernel's tile order
+// The persistent grids' static tile assignment ("the deal"), stated once for the wide kernel (gemm_wide.hip), the loader / consumer
+// kernels (gemm_lc.hip) and the host's replay of it (gemm.hip, tile_cost).  XCD x = blockIdx % 8 owns a
+// contiguous eighth of a problem's `total` tiles; workgroup `slot` = blockIdx / 8 of the XCD's `per` = grid / 8 takes positions
+// slot, slot + per, ... of its XCD's share - in a grouped launch of the first problem's share followed by the second's.
+struct DealShare { int lo, len; };
+__host__ __device__ __forceinline__ DealShare deal_share(int total, int xcd) {
+  const int q = total >> 3, r = total & 7;
+  return {xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, xcd < r ? q + 1 : q};
+}
+// positions slot, slot + per, ... below len: the tiles a workgroup takes from a share (or a concatenation) of `len` tiles
+__host__ __device__ __forceinline__ int deal_count(int len, int slot, int per) { return slot < len ? (len - slot + per - 1) / per : 0; }
+// position j of the concatenation [first share | second share] as a tile of its own problem; a workgroup's first
+// deal_count(first.len, slot, per) positions are the first problem's (`second` false)
+__host__ __device__ __forceinline__ int deal_tile(int j, bool second, DealShare first, DealShare other) {
+  return second ? other.lo + (j - first.len) : first.lo + j;
+}
 // the launchers: ev0 / ev1 (optional) are stamped with the dispatch's own begin / end; a / b in the order their tiles run
 int launch_gemm_wide(int dt, const GemmProblem& a, const GemmProblem* b, int epi, const GemmPlan& p, hipStream_t st, hipEvent_t ev0,
                      hipEvent_t ev1);

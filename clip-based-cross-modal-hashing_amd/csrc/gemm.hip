@@ -107,10 +107,9 @@ static long long tile_cost(int dt, const GemmProblem& a, const GemmProblem* b, i
   const int c0 = a.K / k_step(dt) + 4 + ge, c1 = b ? b->K / k_step(dt) + 4 + ge : 0;
   long long worst = 0;
   for (int x = 0; x < 8; ++x) {
-    const int len0 = (t0 >> 3) + (x < (t0 & 7)), len1 = (t1 >> 3) + (x < (t1 & 7));
+    const int len0 = deal_share(t0, x).len, len1 = deal_share(t1, x).len;
     for (int sl = 0; sl < (b ? per : 1); ++sl) {
-      const int n0 = sl < len0 ? (len0 - sl + per - 1) / per : 0;
-      const int nall = sl < len0 + len1 ? (len0 + len1 - sl + per - 1) / per : 0;
+      const int n0 = deal_count(len0, sl, per), nall = deal_count(len0 + len1, sl, per);
       const long long c = static_cast<long long>(n0) * c0 + static_cast<long long>(nall - n0) * c1;
       worst = c > worst ? c : worst;
     }

@@ -75,6 +75,249 @@ __device__ unsigned long long g_lc_stamps[256 * 8];
 #define LC_T() __builtin_amdgcn_s_memtime()
 #endif
 
+// ---- what the four kernels share: the tile schedule, the loader waves, the 12-wave forms' epilogue pieces --------------------------------
+
+// One workgroup's tiles: the static assignment of cmh_common.h (deal_share / deal_count / deal_tile) on BM-row tiles, K-steps of BK
+// elements; GRP: the second problem's share follows the first's.  Scalars built from the two by-value problems (selecting between the
+// structs themselves at run time would put them on the stack).  lc2q is the plain case with BK = 128.
+template <int BM, bool GRP, int BK = 64>
+struct LcSchedule {
+  int M0, M1;                      // the row counts, clamped from the device
+  int tiles_n0, tiles_n1, slot, per;
+  DealShare sh0, sh1;              // this XCD's share of each problem's n-fastest tile order
+  int n_first, my_tiles;           // tiles of the first problem / of both that this workgroup runs
+  int nk0, nk1, S;                 // K-steps per tile; K-steps of this workgroup = barriers after the prologue's
+  // the deal.  my_tiles == 0: no tile for this workgroup (the grid is sized for the row counts' upper bounds) - the kernel returns
+  __device__ __forceinline__ LcSchedule(const LcProblem& p0, const LcProblem& p1) {
+    M0 = p0.Mub;
+    if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
+    M0 = __builtin_amdgcn_readfirstlane(M0);        // (a loaded value: the compiler cannot know that it is uniform)
+    M1 = 0;
+    if constexpr (GRP) {
+      M1 = p1.Mub;
+      if (p1.m_dev) { const int md = *p1.m_dev; M1 = md < M1 ? md : M1; }
+      M1 = __builtin_amdgcn_readfirstlane(M1);
+    }
+    tiles_n0 = p0.N / lcBN; tiles_n1 = GRP ? p1.N / lcBN : 1;
+    const int total0 = tiles_n0 * ((M0 + BM - 1) / BM);
+    const int total1 = GRP ? tiles_n1 * ((M1 + BM - 1) / BM) : 0;
+    const int xcd = blockIdx.x & 7;
+    slot = blockIdx.x >> 3; per = gridDim.x >> 3;
+    sh0 = deal_share(total0, xcd); sh1 = deal_share(total1, xcd);
+    n_first = deal_count(sh0.len, slot, per);
+    my_tiles = deal_count(sh0.len + sh1.len, slot, per);
+  }
+  // ... and what it comes to in K-steps: a statement of its own, so that a workgroup without tiles returns in front of it
+  __device__ __forceinline__ void count_ksteps(const LcProblem& p0, const LcProblem& p1) {
+    nk0 = p0.K / BK; nk1 = GRP ? p1.K / BK : 0;
+    S = n_first * nk0 + (my_tiles - n_first) * nk1;
+  }
+  // tile ti -> (second problem?, m0, n0)
+  __device__ void tile_of(int ti, bool& second, int& m0, int& n0) const {
+    second = GRP && ti >= n_first;
+    const int logical = deal_tile(slot + ti * per, second, sh0, sh1);
+    const int tn_cnt = second ? tiles_n1 : tiles_n0;
+    const int tm = logical / tn_cnt;
+    m0 = tm * BM;
+    n0 = (logical - tm * tn_cnt) * lcBN;
+  }
+};
+
+// The loader waves (0..3, one per SIMD) of the bf16 kernels: they stage operands and nothing else.  A stage = W 256 rows | X BM rows of
+// 128 bytes (one K-step of a row) at lds + (stage % 3) * STG; two bias rows (tile parity) behind the ring.
+// Piece = 1 KiB = 8 rows x 128 B: lane i fills (row 8 piece + i / 8, physical chunk i % 8) and fetches logical chunk (i % 8) ^ (row & 7).
+// Wave l stages W pieces 8 l .. 8 l + 7 and X pieces XP l .. XP l + XP - 1 of every stage.  Source = uniform base + 32-bit lane offset.
+// ABL: the 8-wave kernel's diagnostic bits (2: nothing staged after the prologue, 4: one stage in flight instead of two).
+// The counted waits: one stage in flight is lc_pieces(BM) entries of a loader wave's vmcnt queue (8 W pieces + BM / 32 X pieces; the
+// bias piece rides in front of its stage), so `stage s has landed, n younger stages may fly` is vmcnt(n * lc_pieces(BM)).
+constexpr int lc_pieces(int bm) { return 8 + bm / 32; }
+#define LC_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+template <int BM, bool GRP, int ABL = 0, int LDS_BYTES>
+__device__ __forceinline__ void lc_loader_wave(const LcSchedule<BM, GRP>& sc, char (&lds)[LDS_BYTES], int wid, int lane, int epi,
+                                               const char* X0, const char* W0, const float* B0, int K0, const char* X1, const char* W1,
+                                               const float* B1, int K1) {
+  constexpr int XP = BM / 32;                       // X pieces per wave and stage
+  constexpr int PIECES = lc_pieces(BM);
+  static_assert(2 * PIECES < 64, "the counted waits must fit gfx950's 6-bit vmcnt field");
+  constexpr int STG = lcWBytes + BM * lcRowBytes;
+  static_assert(LDS_BYTES == 3 * STG + 2 * 1024, "the ring of three stages, then the two bias rows");
+  const int sub = lane >> 3, ch = lane & 7;
+  uint32_t offW[8], offX[XP];
+  const char* Wt = nullptr;
+  const char* Xt = nullptr;
+  const char* Bt = nullptr;      // &bias[n0] of the tile being staged
+  int i_nk = 0;
+  int w_prob = -1;               // the problem offW was computed for
+  auto set_tile = [&](int ti) {
+    bool second; int m0, n0;
+    sc.tile_of(ti, second, m0, n0);
+    const uint32_t rs = static_cast<uint32_t>(second ? K1 : K0) * 2;
+    if (w_prob != static_cast<int>(second)) {      // once per problem: the W offsets follow its row stride
+      w_prob = static_cast<int>(second);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int row = (wid * 8 + i) * 8 + sub;
+        offW[i] = static_cast<uint32_t>(row) * rs + ((ch ^ (row & 7)) << 4);
+      }
+    }
+    i_nk = second ? sc.nk1 : sc.nk0;
+    const int Mp = second ? sc.M1 : sc.M0;
+    Wt = (second ? W1 : W0) + static_cast<size_t>(n0) * rs;
+    Xt = second ? X1 : X0;
+    Bt = reinterpret_cast<const char*>((second ? B1 : B0) + n0);
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+      const int row = (wid * XP + i) * 8 + sub;
+      int xr = m0 + row;
+      xr = xr < Mp ? xr : Mp - 1;               // rows past M are computed on duplicated data and never stored
+      offX[i] = static_cast<uint32_t>(xr) * rs + ((ch ^ (row & 7)) << 4);      // < 4 GiB: checked on the host
+    }
+  };
+  int i_tile = 0, i_kt = 0, ibuf = 0;
+  set_tile(0);
+  const bool bias_wave = wid == 0 && (epi & EPI_BIAS);
+  auto issue_stage = [&]() {
+    char* base = lds + ibuf * STG;
+    const uint32_t koff = static_cast<uint32_t>(i_kt) * lcRowBytes;
+    // The tile's 256 bias values (1 KiB) go to LDS with its first stage: OLDER than that stage's pieces in this wave's queue, so
+    // every counted wait that retires the stage retires them too.  Slot = tile parity: tile t - 2's epilogue is over before the
+    // loaders reach tile t (three stages ahead of the MFMA waves at most, and a tile has >= 4 K-steps).
+    if (i_kt == 0 && bias_wave)
+      __builtin_amdgcn_global_load_lds((lc_gptr_t)(Bt + lane * 16), (lc_lptr_t)(lds + 3 * STG + (i_tile & 1) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      __builtin_amdgcn_global_load_lds((lc_gptr_t)(Wt + koff + offW[i]), (lc_lptr_t)(base + (wid * 8 + i) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < XP; ++i)
+      __builtin_amdgcn_global_load_lds((lc_gptr_t)(Xt + koff + offX[i]), (lc_lptr_t)(base + lcWBytes + (wid * XP + i) * 1024), 16, 0, 0);
+    ibuf = ibuf == 2 ? 0 : ibuf + 1;
+    if (++i_kt == i_nk) {
+      i_kt = 0;
+      if (++i_tile < sc.my_tiles) set_tile(i_tile);
+    }
+  };
+  const int S = sc.S;
+  issue_stage();
+  if (S > 1) issue_stage();
+  if (S > 2) issue_stage();
+  if (S > 2) LC_VMCNT(2 * PIECES);                  // stage 0 landed; two younger stages may fly
+  else if (S > 1) LC_VMCNT(PIECES);
+  else LC_VMCNT(0);
+  __builtin_amdgcn_s_barrier();
+  for (int s = 0; s < S; ++s) {
+    // in front of barrier s: stage s + 1 has landed (stage s + 2 may fly)
+    if (s + 2 < S && !(ABL & 4)) LC_VMCNT(PIECES);
+    else LC_VMCNT(0);
+    __builtin_amdgcn_s_barrier();
+    // behind it nobody reads buffer s % 3 any more
+    if (s + 3 < S && !(ABL & 2)) issue_stage();
+  }
+}
+
+// ---- the MFMA waves of the 12-wave forms (lc2, lc3, lc2q): 2 (m) x 4 (n) waves, MF 16-row m-fragments x 4 n-fragments each -------------
+__device__ __forceinline__ lc_f32x4_t lc_mfma_bf16(const lc_u32x4_t& w, const lc_u32x4_t& x, const lc_f32x4_t& cin) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lc_bf16x8_t, w), __builtin_bit_cast(lc_bf16x8_t, x), cin, 0, 0, 0);
+}
+// parked piece idx (wave-uniform: a jump, not a select) of NP goes to its place in the previous tile: row block ROW0 + idx / 2, half idx % 2
+template <int NP, int ROW0 = 0>
+__device__ __forceinline__ void lc_store_parked(const lc_u32x4_t (&pend)[NP], int idx, char* base, uint32_t off0, uint32_t ldn) {
+  static_assert(NP == 4 || NP == 8, "four or eight parked pieces");
+  char* p = base + (off0 + static_cast<uint32_t>(ROW0 + (idx >> 1)) * 16u * ldn + static_cast<uint32_t>(idx & 1) * 64u);
+  switch (idx) {
+    case 0: *reinterpret_cast<lc_u32x4_t*>(p) = pend[0]; break;
+    case 1: *reinterpret_cast<lc_u32x4_t*>(p) = pend[1]; break;
+    case 2: *reinterpret_cast<lc_u32x4_t*>(p) = pend[2]; break;
+    case 3: *reinterpret_cast<lc_u32x4_t*>(p) = pend[3]; break;
+    case 4: *reinterpret_cast<lc_u32x4_t*>(p) = pend[NP > 4 ? 4 : 3]; break;
+    case 5: *reinterpret_cast<lc_u32x4_t*>(p) = pend[NP > 4 ? 5 : 3]; break;
+    case 6: *reinterpret_cast<lc_u32x4_t*>(p) = pend[NP > 4 ? 6 : 3]; break;
+    default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[NP - 1]; break;
+  }
+}
+// residual tile `ti` as MFMA wave (wm, wn) sees it: a uniform base (&residual[m0 + wm * BM / 2][n0 + wn * 64]), the row stride
+// (elements) and the rows that exist from there
+template <int BM, bool GRP>
+__device__ __forceinline__ void lc_residual_of(const LcSchedule<BM, GRP>& sc, int ti, int wm, int wn, const void* R0, int N0,
+                                               const void* R1, int N1, const uint16_t*& base, int& ld, int& rows) {
+  bool second; int m0, n0;
+  sc.tile_of(ti, second, m0, n0);
+  ld = second ? N1 : N0;
+  rows = (second ? sc.M1 : sc.M0) - (m0 + wm * (BM / 2));
+  base = reinterpret_cast<const uint16_t*>(second ? R1 : R0) + static_cast<size_t>(m0 + wm * (BM / 2)) * ld + n0 + wn * 64;
+}
+// piece (b, pr) of a residual tile: this lane's row of row block b (clamped to the last real row: rows past M are never stored) x 8
+// consecutive n, in the packed 16-byte layout of the output.  base = &residual[tile row 0 of the wave][its first n], ld in elements
+__device__ __forceinline__ lc_u32x4_t lc_res_piece(const uint16_t* base, int ld, int rows, int frow, int fq, int b, int pr) {
+  int r = b * 16 + frow;
+  r = r < rows ? r : rows - 1;
+  return *reinterpret_cast<const lc_u32x4_t*>(base + static_cast<size_t>(r) * ld + (fq & 1) * 16 + (fq & 2) * 4 + 32 * pr);
+}
+// piece (b, pr) of a fetched residual, brought to the accumulator layout (v_permlane16_swap) and ADDED to the two n-fragments it covers
+template <int MF>
+__device__ __forceinline__ void lc_add_piece(lc_f32x4_t (&acc)[4][MF], int b, int pr, const lc_u32x4_t& qv) {
+  const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(qv[0], qv[2], false, false);
+  const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(qv[1], qv[3], false, false);
+  acc[2 * pr][b][0] += f16lo_to_f32(s0[0]); acc[2 * pr][b][1] += f16hi_to_f32(s0[0]);
+  acc[2 * pr][b][2] += f16lo_to_f32(s1[0]); acc[2 * pr][b][3] += f16hi_to_f32(s1[0]);
+  acc[2 * pr + 1][b][0] += f16lo_to_f32(s0[1]); acc[2 * pr + 1][b][1] += f16hi_to_f32(s0[1]);
+  acc[2 * pr + 1][b][2] += f16lo_to_f32(s1[1]); acc[2 * pr + 1][b][3] += f16hi_to_f32(s1[1]);
+}
+template <int MF>
+__device__ __forceinline__ void lc_zero(lc_f32x4_t (&acc)[4][MF]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < MF; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+}
+// + bias: the wave's 64 values of the LDS bias row at `ab` (staged by the loaders with the tile's first stage)
+template <int MF>
+__device__ __forceinline__ void lc_add_bias(lc_f32x4_t (&acc)[4][MF], uint32_t ab) {
+  lc_f32x4_t bv[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) bv[a] = __builtin_bit_cast(lc_f32x4_t, lc_lds_read(ab + a * 64));
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < MF; ++b) acc[a][b] += bv[a];
+}
+// QuickGELU, two values at a time: the wide kernel's instruction sequence (packed-f32 multiply / add, v_exp_f32 / v_rcp_f32 per value)
+template <int MF>
+__device__ __forceinline__ void lc_quickgelu(lc_f32x4_t (&acc)[4][MF]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < MF; ++b)
+#pragma unroll
+      for (int j = 0; j < 4; j += 2) {
+        const lc_f32x2_t v = {acc[a][b][j], acc[a][b][j + 1]};
+        const lc_f32x2_t t = v * lc_f32x2_t{-2.4554669595930157f, -2.4554669595930157f};
+        const lc_f32x2_t d = lc_f32x2_t{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + lc_f32x2_t{1.0f, 1.0f};
+        const lc_f32x2_t o = v * lc_f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+        acc[a][b][j] = o[0];
+        acc[a][b][j + 1] = o[1];
+      }
+}
+// output piece (b, pr): 16 x 32 values of n-fragments 2 pr and 2 pr + 1, packed to 16 bits.  v_permlane16_swap exchanges, between the lane
+// pairs (l, l + 16), the packed words of the two fragments: an even lane-row then owns 8 consecutive n of fragment 2 pr and an odd
+// lane-row 8 consecutive n of fragment 2 pr + 1 -> one 16-byte store per lane
+template <bool F16O, int MF>
+__device__ __forceinline__ lc_u32x4_t lc_pack_piece(const lc_f32x4_t (&acc)[4][MF], int b, int pr) {
+  uint32_t lo[2], hi[2];
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    if constexpr (F16O) {
+      lo[w] = pack_f16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
+      hi[w] = pack_f16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
+    } else {
+      lo[w] = pack_bf16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
+      hi[w] = pack_bf16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
+    }
+  }
+  const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(lo[0], hi[0], false, false);
+  const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(lo[1], hi[1], false, false);
+  return lc_u32x4_t{s0[0], s1[0], s0[1], s1[1]};
+}
+
 // RF: the residual-first rule applies to this launch (short K with a residual: the accumulators start as the residual tile); a template
 // parameter so that a tile's first K-step is one straight path - C = 0 inside the first MFMAs, or the loaded residual
 // ABL (diagnostic instantiations only, CMH_LC_ABL): 1 the MFMA waves skip their MFMAs (what the feed alone sustains), 2 the loaders stage
@@ -98,115 +341,13 @@ __global__ __launch_bounds__(512) void gemm_lc_kernel(LcProblem p0, LcProblem p1
   const char* const X1 = p1.X; const char* const W1 = p1.W; const float* const B1 = p1.bias;
   const void* const R1 = p1.residual; void* const O1 = p1.out;
   const int N1 = p1.N, K1 = p1.K;
-  int M0 = p0.Mub;
-  if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
-  M0 = __builtin_amdgcn_readfirstlane(M0);        // (a loaded value: the compiler cannot know that it is uniform)
-  int M1 = 0;
-  if constexpr (GRP) {
-    M1 = p1.Mub;
-    if (p1.m_dev) { const int md = *p1.m_dev; M1 = md < M1 ? md : M1; }
-    M1 = __builtin_amdgcn_readfirstlane(M1);
-  }
-  // ---- this workgroup's tiles: the wide kernel's static assignment.  XCD x = blockIdx % 8 owns a contiguous eighth of each problem's
-  // n-fastest tile order; workgroup `slot` of the XCD takes positions slot, slot + per, ... of the concatenation of the two eighths.
-  const int tiles_n0 = N0 / lcBN, tiles_n1 = GRP ? N1 / lcBN : 1;
-  const int total0 = tiles_n0 * ((M0 + lcBM - 1) / lcBM);
-  const int total1 = GRP ? tiles_n1 * ((M1 + lcBM - 1) / lcBM) : 0;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
-  const int q0 = total0 >> 3, r0 = total0 & 7, q1 = total1 >> 3, r1 = total1 & 7;
-  const int lo0 = xcd < r0 ? xcd * (q0 + 1) : r0 * (q0 + 1) + (xcd - r0) * q0, len0 = xcd < r0 ? q0 + 1 : q0;
-  const int lo1 = xcd < r1 ? xcd * (q1 + 1) : r1 * (q1 + 1) + (xcd - r1) * q1, len1 = xcd < r1 ? q1 + 1 : q1;
-  const int n_first = slot < len0 ? (len0 - slot + per - 1) / per : 0;
-  const int span = len0 + len1;
-  const int my_tiles = slot < span ? (span - slot + per - 1) / per : 0;
-  if (my_tiles == 0) return;
-  const int nk0 = K0 / 64, nk1 = GRP ? K1 / 64 : 0;
-  const int S = n_first * nk0 + (my_tiles - n_first) * nk1;      // K-steps of this workgroup = barriers after the prologue's
-  // tile ti -> (second problem?, m0, n0)
-  auto tile_of = [&](int ti, bool& second, int& m0, int& n0) {
-    const int j = slot + ti * per;
-    second = GRP && ti >= n_first;
-    const int logical = second ? lo1 + (j - len0) : lo0 + j;
-    const int tn_cnt = second ? tiles_n1 : tiles_n0;
-    const int tm = logical / tn_cnt;
-    m0 = tm * lcBM;
-    n0 = (logical - tm * tn_cnt) * lcBN;
-  };
+  LcSchedule<lcBM, GRP> sc(p0, p1);
+  if (sc.my_tiles == 0) return;
+  sc.count_ksteps(p0, p1);
+  const int n_first = sc.n_first, my_tiles = sc.my_tiles;
 
   if (wid < 4) {
-    // =================================================== loader waves ===============================================================
-    // Piece = 1 KiB = 8 rows x 128 B: lane i fills (row 8 piece + i / 8, physical chunk i % 8) and fetches logical chunk (i % 8) ^ (row & 7).
-    // Wave l stages W pieces 8 l .. 8 l + 7 and X pieces 4 l .. 4 l + 3 of every stage.  Source = uniform base + 32-bit lane offset.
-    const int sub = lane >> 3, ch = lane & 7;
-    uint32_t offW[8], offX[4];
-    const char* Wt = nullptr;
-    const char* Xt = nullptr;
-    const char* Bt = nullptr;      // &bias[n0] of the tile being staged
-    int i_nk = 0;
-    int w_prob = -1;               // the problem offW was computed for
-    auto set_tile = [&](int ti) {
-      bool second; int m0, n0;
-      tile_of(ti, second, m0, n0);
-      const uint32_t rs = static_cast<uint32_t>(second ? K1 : K0) * 2;
-      if (w_prob != static_cast<int>(second)) {      // once per problem: the W offsets follow its row stride
-        w_prob = static_cast<int>(second);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int row = (wid * 8 + i) * 8 + sub;
-          offW[i] = static_cast<uint32_t>(row) * rs + ((ch ^ (row & 7)) << 4);
-        }
-      }
-      i_nk = second ? nk1 : nk0;
-      const int Mp = second ? M1 : M0;
-      Wt = (second ? W1 : W0) + static_cast<size_t>(n0) * rs;
-      Xt = second ? X1 : X0;
-      Bt = reinterpret_cast<const char*>((second ? B1 : B0) + n0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = (wid * 4 + i) * 8 + sub;
-        int xr = m0 + row;
-        xr = xr < Mp ? xr : Mp - 1;               // rows past M are computed on duplicated data and never stored
-        offX[i] = static_cast<uint32_t>(xr) * rs + ((ch ^ (row & 7)) << 4);      // < 4 GiB: checked on the host
-      }
-    };
-    int i_tile = 0, i_kt = 0, ibuf = 0;
-    set_tile(0);
-    const bool bias_wave = wid == 0 && (epi & EPI_BIAS);
-    auto issue_stage = [&]() {
-      char* base = lds + ibuf * lcSTG;
-      const uint32_t koff = static_cast<uint32_t>(i_kt) * lcRowBytes;
-      // The tile's 256 bias values (1 KiB) go to LDS with its first stage: OLDER than that stage's pieces in this wave's queue, so
-      // every counted wait that retires the stage retires them too.  Slot = tile parity: tile t - 2's epilogue is over before the
-      // loaders reach tile t (three stages ahead of the MFMA waves at most, and a tile has >= 4 K-steps).
-      if (i_kt == 0 && bias_wave)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Bt + lane * 16), (lc_lptr_t)(lds + 3 * lcSTG + (i_tile & 1) * 1024), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Wt + koff + offW[i]), (lc_lptr_t)(base + (wid * 8 + i) * 1024), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Xt + koff + offX[i]), (lc_lptr_t)(base + lcWBytes + (wid * 4 + i) * 1024), 16, 0, 0);
-      ibuf = ibuf == 2 ? 0 : ibuf + 1;
-      if (++i_kt == i_nk) {
-        i_kt = 0;
-        if (++i_tile < my_tiles) set_tile(i_tile);
-      }
-    };
-    issue_stage();
-    if (S > 1) issue_stage();
-    if (S > 2) issue_stage();
-    if (S > 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");        // stage 0 landed; two younger stages may fly
-    else if (S > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    for (int s = 0; s < S; ++s) {
-      // in front of barrier s: stage s + 1 has landed (stage s + 2 may fly)
-      if (s + 2 < S && !(ABL & 4)) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      // behind it nobody reads buffer s % 3 any more
-      if (s + 3 < S && !(ABL & 2)) issue_stage();
-    }
+    lc_loader_wave<lcBM, GRP, ABL>(sc, lds, wid, lane, epi, X0, W0, B0, K0, X1, W1, B1, K1);
     return;
   }
 
@@ -224,9 +365,9 @@ __global__ __launch_bounds__(512) void gemm_lc_kernel(LcProblem p0, LcProblem p1
   // the compute side's view of its problem
   const void* residual = R0;
   void* out = O0;
-  int N = N0, M = M0, nk = nk0;
+  int N = N0, M = sc.M0, nk = sc.nk0;
   [[maybe_unused]] auto to_problem1 = [&]() {
-    residual = R1; out = O1; N = N1; M = M1; nk = nk1;
+    residual = R1; out = O1; N = N1; M = sc.M1; nk = sc.nk1;
   };
   if constexpr (GRP) { if (n_first == 0) to_problem1(); }
   // the wide kernel's residual-first rule: short K -> the accumulators START as the residual tile ((residual + sum) + bias), long K ->
@@ -311,7 +452,7 @@ __global__ __launch_bounds__(512) void gemm_lc_kernel(LcProblem p0, LcProblem p1
   int cur = 0;
   {
     bool second; int m0, n0;
-    tile_of(0, second, m0, n0);
+    sc.tile_of(0, second, m0, n0);
     if constexpr (RF) { zero_acc(); add_residual(m0, n0); }
   }
   __builtin_amdgcn_s_barrier();                    // stage 0 has landed
@@ -405,7 +546,7 @@ __global__ __launch_bounds__(512) void gemm_lc_kernel(LcProblem p0, LcProblem p1
 
   for (int ti = 0; ti < my_tiles; ++ti) {
     bool second; int m0, n0;
-    tile_of(ti, second, m0, n0);
+    sc.tile_of(ti, second, m0, n0);
     if constexpr (GRP) { if (ti == n_first && ti > 0) to_problem1(); }
     // (zeroed with 128 v_mov here rather than by C = 0 in a peeled first K-step: a second copy of the K-step body leaves the allocator
     // two register assignments to reconcile at every tile boundary, and it does so through scratch)
@@ -488,7 +629,7 @@ __global__ __launch_bounds__(512) void gemm_lc_kernel(LcProblem p0, LcProblem p1
   if (c == 0 && lane == 0 && blockIdx.x < 256) {
     unsigned long long* o = g_lc_stamps + blockIdx.x * 8;
     o[0] = LC_T() - st_t0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0; o[2] = st_first; o[3] = st_k; o[4] = st_e;
-    o[5] = static_cast<unsigned long long>(S); o[6] = static_cast<unsigned long long>(my_tiles); o[7] = static_cast<unsigned long long>(my_tiles);
+    o[5] = static_cast<unsigned long long>(sc.S); o[6] = static_cast<unsigned long long>(my_tiles); o[7] = static_cast<unsigned long long>(my_tiles);
   }
 #endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads issued past the last stage
@@ -518,105 +659,13 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
   const char* const X1 = p1.X; const char* const W1 = p1.W; const float* const B1 = p1.bias; void* const O1 = p1.out;
   const void* const R1 = p1.residual;
   const int N1 = p1.N, K1 = p1.K;
-  int M0 = p0.Mub;
-  if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
-  M0 = __builtin_amdgcn_readfirstlane(M0);
-  int M1 = 0;
-  if constexpr (GRP) {
-    M1 = p1.Mub;
-    if (p1.m_dev) { const int md = *p1.m_dev; M1 = md < M1 ? md : M1; }
-    M1 = __builtin_amdgcn_readfirstlane(M1);
-  }
-  const int tiles_n0 = N0 / lcBN, tiles_n1 = GRP ? N1 / lcBN : 1;
-  const int total0 = tiles_n0 * ((M0 + lcBM - 1) / lcBM);
-  const int total1 = GRP ? tiles_n1 * ((M1 + lcBM - 1) / lcBM) : 0;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
-  const int q0 = total0 >> 3, r0 = total0 & 7, q1 = total1 >> 3, r1 = total1 & 7;
-  const int lo0 = xcd < r0 ? xcd * (q0 + 1) : r0 * (q0 + 1) + (xcd - r0) * q0, len0 = xcd < r0 ? q0 + 1 : q0;
-  const int lo1 = xcd < r1 ? xcd * (q1 + 1) : r1 * (q1 + 1) + (xcd - r1) * q1, len1 = xcd < r1 ? q1 + 1 : q1;
-  const int n_first = slot < len0 ? (len0 - slot + per - 1) / per : 0;
-  const int span = len0 + len1;
-  const int my_tiles = slot < span ? (span - slot + per - 1) / per : 0;
-  if (my_tiles == 0) return;
-  const int nk0 = K0 / 64, nk1 = GRP ? K1 / 64 : 0;
-  const int S = n_first * nk0 + (my_tiles - n_first) * nk1;
-  auto tile_of = [&](int ti, bool& second, int& m0, int& n0) {
-    const int j = slot + ti * per;
-    second = GRP && ti >= n_first;
-    const int logical = second ? lo1 + (j - len0) : lo0 + j;
-    const int tn_cnt = second ? tiles_n1 : tiles_n0;
-    const int tm = logical / tn_cnt;
-    m0 = tm * lcBM;
-    n0 = (logical - tm * tn_cnt) * lcBN;
-  };
+  LcSchedule<lcBM, GRP> sc(p0, p1);
+  if (sc.my_tiles == 0) return;
+  sc.count_ksteps(p0, p1);
+  const int n_first = sc.n_first, my_tiles = sc.my_tiles;
 
   if (wid < 4) {
-    // ---- loader waves: the lc kernel's, piece for piece ----
-    const int sub = lane >> 3, ch = lane & 7;
-    uint32_t offW[8], offX[4];
-    const char* Wt = nullptr;
-    const char* Xt = nullptr;
-    const char* Bt = nullptr;
-    int i_nk = 0;
-    int w_prob = -1;
-    auto set_tile = [&](int ti) {
-      bool second; int m0, n0;
-      tile_of(ti, second, m0, n0);
-      const uint32_t rs = static_cast<uint32_t>(second ? K1 : K0) * 2;
-      if (w_prob != static_cast<int>(second)) {
-        w_prob = static_cast<int>(second);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int row = (wid * 8 + i) * 8 + sub;
-          offW[i] = static_cast<uint32_t>(row) * rs + ((ch ^ (row & 7)) << 4);
-        }
-      }
-      i_nk = second ? nk1 : nk0;
-      const int Mp = second ? M1 : M0;
-      Wt = (second ? W1 : W0) + static_cast<size_t>(n0) * rs;
-      Xt = second ? X1 : X0;
-      Bt = reinterpret_cast<const char*>((second ? B1 : B0) + n0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = (wid * 4 + i) * 8 + sub;
-        int xr = m0 + row;
-        xr = xr < Mp ? xr : Mp - 1;
-        offX[i] = static_cast<uint32_t>(xr) * rs + ((ch ^ (row & 7)) << 4);
-      }
-    };
-    int i_tile = 0, i_kt = 0, ibuf = 0;
-    set_tile(0);
-    const bool bias_wave = wid == 0 && (epi & EPI_BIAS);
-    auto issue_stage = [&]() {
-      char* base = lds + ibuf * lcSTG;
-      const uint32_t koff = static_cast<uint32_t>(i_kt) * lcRowBytes;
-      if (i_kt == 0 && bias_wave)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Bt + lane * 16), (lc_lptr_t)(lds + 3 * lcSTG + (i_tile & 1) * 1024), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Wt + koff + offW[i]), (lc_lptr_t)(base + (wid * 8 + i) * 1024), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((lc_gptr_t)(Xt + koff + offX[i]), (lc_lptr_t)(base + lcWBytes + (wid * 4 + i) * 1024), 16, 0, 0);
-      ibuf = ibuf == 2 ? 0 : ibuf + 1;
-      if (++i_kt == i_nk) {
-        i_kt = 0;
-        if (++i_tile < my_tiles) set_tile(i_tile);
-      }
-    };
-    issue_stage();
-    if (S > 1) issue_stage();
-    if (S > 2) issue_stage();
-    if (S > 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (S > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    for (int s = 0; s < S; ++s) {
-      if (s + 2 < S) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (s + 3 < S) issue_stage();
-    }
+    lc_loader_wave<lcBM, GRP>(sc, lds, wid, lane, epi, X0, W0, B0, K0, X1, W1, B1, K1);
     return;
   }
 
@@ -637,57 +686,23 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
   [[maybe_unused]] int res_kt = -1;                     // RES != 0: at K-step res_kt (-1: never) the residual rows (residual_of) are fetched into pend
 
   void* out = O0;
-  int N = N0, M = M0, nk = nk0;
-  [[maybe_unused]] auto to_problem1 = [&]() { out = O1; N = N1; M = M1; nk = nk1; };
+  int N = N0, M = sc.M0, nk = sc.nk0;
+  [[maybe_unused]] auto to_problem1 = [&]() { out = O1; N = N1; M = sc.M1; nk = sc.nk1; };
   if constexpr (GRP) { if (n_first == 0) to_problem1(); }
 
-  auto mfma = [&](const lc_u32x4_t& w, const lc_u32x4_t& x, const lc_f32x4_t& cin) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lc_bf16x8_t, w), __builtin_bit_cast(lc_bf16x8_t, x), cin, 0, 0, 0);
-  };
-  auto store_pending = [&](int idx) __attribute__((always_inline)) {      // idx is wave-uniform: a jump, not a select
-    char* p = pend_base + (pend_off0 + static_cast<uint32_t>(idx >> 1) * 16u * pend_ldn + static_cast<uint32_t>(idx & 1) * 64u);
-    switch (idx) {
-      case 0: *reinterpret_cast<lc_u32x4_t*>(p) = pend[0]; break;
-      case 1: *reinterpret_cast<lc_u32x4_t*>(p) = pend[1]; break;
-      case 2: *reinterpret_cast<lc_u32x4_t*>(p) = pend[2]; break;
-      case 3: *reinterpret_cast<lc_u32x4_t*>(p) = pend[3]; break;
-      case 4: *reinterpret_cast<lc_u32x4_t*>(p) = pend[4]; break;
-      case 5: *reinterpret_cast<lc_u32x4_t*>(p) = pend[5]; break;
-      case 6: *reinterpret_cast<lc_u32x4_t*>(p) = pend[6]; break;
-      default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[7]; break;
-    }
-  };
-  // the residual rows the K loop fetches (RES 1: the next tile's, RES 2: this tile's): a uniform base (&residual[m0 + wm * 64][n0 + wn * 64]),
-  // the row stride and the rows that exist from there, formed at the tile's start - the K loop only loads
+  // the residual rows the K loop fetches (RES 1: the next tile's, RES 2: this tile's): lc_residual_of's base, row stride and row count,
+  // formed at the tile's start - the K loop only loads
   [[maybe_unused]] const uint16_t* rq_base = nullptr;
   [[maybe_unused]] int rq_ld = 0, rq_rows = 0;
   [[maybe_unused]] auto residual_of = [&](int ti) __attribute__((always_inline)) {
-    bool second; int m0, n0;
-    tile_of(ti, second, m0, n0);
-    rq_ld = second ? N1 : N0;
-    rq_rows = (second ? M1 : M0) - (m0 + wm * 64);
-    rq_base = reinterpret_cast<const uint16_t*>(second ? R1 : R0) + static_cast<size_t>(m0 + wm * 64) * rq_ld + n0 + wn * 64;
+    lc_residual_of(sc, ti, wm, wn, R0, N0, R1, N1, rq_base, rq_ld, rq_rows);
   };
-  // the fetch: this lane's row of each row block (clamped to the last real row: rows past M are never stored) x 8 consecutive n, into
-  // the (free) parked-piece registers, in the packed 16-byte layout of the output
+  // the fetch: every piece into the (free) parked-piece registers
   [[maybe_unused]] auto fetch_residual = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      int r = b * 16 + frow;
-      r = r < rq_rows ? r : rq_rows - 1;
+    for (int b = 0; b < 4; ++b)
 #pragma unroll
-      for (int pr = 0; pr < 2; ++pr)
-        pend[2 * b + pr] = *reinterpret_cast<const lc_u32x4_t*>(rq_base + static_cast<size_t>(r) * rq_ld + (fq & 1) * 16 + (fq & 2) * 4 + 32 * pr);
-    }
-  };
-  // piece (b, pr) of a fetched residual, brought to the accumulator layout (v_permlane16_swap) and ADDED to the two n-fragments it covers
-  [[maybe_unused]] auto add_piece = [&](int b, int pr, const lc_u32x4_t& qv) __attribute__((always_inline)) {
-    const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(qv[0], qv[2], false, false);
-    const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(qv[1], qv[3], false, false);
-    acc[2 * pr][b][0] += f16lo_to_f32(s0[0]); acc[2 * pr][b][1] += f16hi_to_f32(s0[0]);
-    acc[2 * pr][b][2] += f16lo_to_f32(s1[0]); acc[2 * pr][b][3] += f16hi_to_f32(s1[0]);
-    acc[2 * pr + 1][b][0] += f16lo_to_f32(s0[1]); acc[2 * pr + 1][b][1] += f16hi_to_f32(s0[1]);
-    acc[2 * pr + 1][b][2] += f16lo_to_f32(s1[1]); acc[2 * pr + 1][b][3] += f16hi_to_f32(s1[1]);
+      for (int pr = 0; pr < 2; ++pr) pend[2 * b + pr] = lc_res_piece(rq_base, rq_ld, rq_rows, frow, fq, b, pr);
   };
 // The fragment reads are plain LDS loads: the compiler counts their returns and waits in front of each first use, so no copy, spill or
 // reuse of a fragment register can come between a read and its wait.  The one wait the protocol itself needs - every read of this
@@ -700,14 +715,11 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
   if constexpr (RES == 1) {                        // the first tile's accumulators start as its residual rows (0 + r: the wide kernel's bits)
     residual_of(0);
     fetch_residual();
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    lc_zero(acc);
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
-      for (int pr = 0; pr < 2; ++pr) add_piece(b, pr, pend[2 * b + pr]);
+      for (int pr = 0; pr < 2; ++pr) lc_add_piece(acc, b, pr, pend[2 * b + pr]);
   }
   __builtin_amdgcn_s_barrier();                    // stage 0 has landed
   asm volatile("" ::: "memory");
@@ -721,7 +733,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     const uint32_t bo = static_cast<uint32_t>(cur) * lcSTG;
     const uint32_t w1 = (aW + bo) ^ 64u, x1 = (aX + bo) ^ 64u;
     __builtin_amdgcn_sched_barrier(0);
-#define L2_MFMA0(a, b) acc[a][b] = mfma(fw[a], fxa[b], acc[a][b])
+#define L2_MFMA0(a, b) acc[a][b] = lc_mfma_bf16(fw[a], fxa[b], acc[a][b])
 #define L2_GROUP0(a)                                                                                   \
   do {                                                                                                 \
     if constexpr ((a) == 0) L2_READ_X(fxb, 0, x1);                                                     \
@@ -740,7 +752,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     // (pend_idx / the K-step counter are kept OPAQUE to the optimizer: knowing "kt < 4" it peels four copies of this body, hoists
     // the residual addresses across them through scratch and - measured - gets the first row block's address wrong)
     if (pend_idx < 8) {                               // two 16-byte pieces of the previous tile per K-step: gone after four
-      store_pending(pend_idx); store_pending(pend_idx + 1);
+      lc_store_parked(pend, pend_idx, pend_base, pend_off0, pend_ldn); lc_store_parked(pend, pend_idx + 1, pend_base, pend_off0, pend_ldn);
       pend_idx += 2;
       asm volatile("" : "+s"(pend_idx));
       __builtin_amdgcn_sched_barrier(0);
@@ -754,7 +766,7 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     const int nxt = cur == 2 ? 0 : cur + 1;
     const uint32_t bn = static_cast<uint32_t>(nxt) * lcSTG;
     const uint32_t w0 = aW + bn, x0 = aX + bn;
-#define L2_MFMA1(a, b) acc[a][b] = mfma(fw[a], fxb[b], acc[a][b])
+#define L2_MFMA1(a, b) acc[a][b] = lc_mfma_bf16(fw[a], fxb[b], acc[a][b])
     __builtin_amdgcn_sched_barrier(0);
     L2_MFMA1(0, 0); L2_MFMA1(0, 1); L2_MFMA1(0, 2); L2_MFMA1(0, 3);
     __builtin_amdgcn_sched_barrier(0);
@@ -787,14 +799,9 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
 
   for (int ti = 0; ti < my_tiles; ++ti) {
     bool second; int m0, n0;
-    tile_of(ti, second, m0, n0);
+    sc.tile_of(ti, second, m0, n0);
     if constexpr (GRP) { if (ti == n_first && ti > 0) to_problem1(); }
-    if constexpr (RES != 1) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
+    if constexpr (RES != 1) lc_zero(acc);
     if constexpr (RES == 1) { res_kt = ti + 1 < my_tiles ? 4 : -1; if (ti + 1 < my_tiles) residual_of(ti + 1); }      // the NEXT tile's rows, once the parked pieces are out
     // this tile's own rows, at the same K-step: the registers are free from there on.  (A build that fetched at K-step nk - 3 once
     // returned garbage in some lanes' first row block - the symptom of the peeled build above, whose residual addresses went through
@@ -808,37 +815,14 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
     }
     // nk >= 8 (host): every parked piece has left after four K-steps
 
-    if (epi & EPI_BIAS) {
-      const uint32_t ab = lds_base + 3 * lcSTG + (ti & 1) * 1024 + (wn * 64 + fq * 4) * 4;
-      lc_f32x4_t bv[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) bv[a] = __builtin_bit_cast(lc_f32x4_t, lc_lds_read(ab + a * 64));
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] += bv[a];
-    }
-    if (epi & EPI_QUICKGELU) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int j = 0; j < 4; j += 2) {
-            const lc_f32x2_t v = {acc[a][b][j], acc[a][b][j + 1]};
-            const lc_f32x2_t t = v * lc_f32x2_t{-2.4554669595930157f, -2.4554669595930157f};
-            const lc_f32x2_t d = lc_f32x2_t{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + lc_f32x2_t{1.0f, 1.0f};
-            const lc_f32x2_t o = v * lc_f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-            acc[a][b][j] = o[0];
-            acc[a][b][j + 1] = o[1];
-          }
-    }
+    if (epi & EPI_BIAS) lc_add_bias(acc, lds_base + 3 * lcSTG + (ti & 1) * 1024 + (wn * 64 + fq * 4) * 4);
+    if (epi & EPI_QUICKGELU) lc_quickgelu(acc);
     if constexpr (RES == 2) {                        // long K: the residual behind the bias (fetched three K-steps ago)
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(pend[0]), "+v"(pend[1]), "+v"(pend[2]), "+v"(pend[3]), "+v"(pend[4]), "+v"(pend[5]), "+v"(pend[6]), "+v"(pend[7])::"memory");
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
-        for (int pr = 0; pr < 2; ++pr) add_piece(b, pr, pend[2 * b + pr]);
+        for (int pr = 0; pr < 2; ++pr) lc_add_piece(acc, b, pr, pend[2 * b + pr]);
     }
     if constexpr (RES == 1) {
       if (res_kt >= 0)
@@ -853,26 +837,14 @@ __global__ __launch_bounds__(768) void gemm_lc2_kernel(LcProblem p0, LcProblem p
       for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
-          uint32_t lo[2], hi[2];
-#pragma unroll
-          for (int w = 0; w < 2; ++w) {
-            if constexpr (F16O) {
-              lo[w] = pack_f16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
-              hi[w] = pack_f16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
-            } else {
-              lo[w] = pack_bf16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
-              hi[w] = pack_bf16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
-            }
-          }
-          const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(lo[0], hi[0], false, false);
-          const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(lo[1], hi[1], false, false);
+          const lc_u32x4_t val = lc_pack_piece<F16O>(acc, b, pr);
           if constexpr (RES == 1) {                  // the rotation: this piece's accumulators restart as the next tile's residual piece
             const lc_u32x4_t nextres = pend[2 * b + pr];
             acc[2 * pr][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
             acc[2 * pr + 1][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (res_kt >= 0) add_piece(b, pr, nextres);
+            if (res_kt >= 0) lc_add_piece(acc, b, pr, nextres);
           }
-          pend[2 * b + pr] = lc_u32x4_t{s0[0], s1[0], s0[1], s1[1]};
+          pend[2 * b + pr] = val;
         }
       pend_base = obase; pend_off0 = off0; pend_ldn = ldn;
       const bool full = m0 + lcBM <= M;
@@ -924,6 +896,10 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   const char* const X1 = p1.X; const char* const W1 = p1.W; const float* const B1 = p1.bias; void* const O1 = p1.out;
   const void* const R1 = p1.residual;
   const int N1 = p1.N, K1 = p1.K;
+  // This kernel is the routed one, and its instruction stream is pinned (tools/isa_pin.py): LcSchedule<lc3BM, GRP> and
+  // lc_loader_wave<lc3BM, GRP> state exactly what follows, down to `return` of the loader waves, but through them hipcc orders
+  // the scalar arithmetic differently and merges n_first with my_tiles in a plain launch - another stream.  So the statement
+  // stays written out here, word for word what those two say, until a change to this kernel re-records the pins anyway.
   int M0 = p0.Mub;
   if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
   M0 = __builtin_amdgcn_readfirstlane(M0);
@@ -957,7 +933,7 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   };
 
   if (wid < 4) {
-    // ---- loader waves: lc2's, with 20 X pieces per stage (5 per wave): 13 pieces per wave and stage ----
+    // ---- loader waves: lc_loader_wave's text with 20 X pieces per stage (5 per wave): 13 pieces per wave and stage ----
     const int sub = lane >> 3, ch = lane & 7;
     uint32_t offW[8], offX[5];
     const char* Wt = nullptr;
@@ -1013,13 +989,13 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
     issue_stage();
     if (S > 1) issue_stage();
     if (S > 2) issue_stage();
-    if (S > 2) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");        // stage 0 landed; two younger stages may fly
-    else if (S > 1) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (S > 2) LC_VMCNT(2 * lc_pieces(lc3BM));        // stage 0 landed; two younger stages may fly
+    else if (S > 1) LC_VMCNT(lc_pieces(lc3BM));
+    else LC_VMCNT(0);
     __builtin_amdgcn_s_barrier();
     for (int s = 0; s < S; ++s) {
-      if (s + 2 < S) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (s + 2 < S) LC_VMCNT(lc_pieces(lc3BM));
+      else LC_VMCNT(0);
       __builtin_amdgcn_s_barrier();
       if (s + 3 < S) issue_stage();
     }
@@ -1050,21 +1026,10 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   [[maybe_unused]] auto to_problem1 = [&]() { out = O1; N = N1; M = M1; nk = nk1; };
   if constexpr (GRP) { if (n_first == 0) to_problem1(); }
 
-  auto mfma = [&](const lc_u32x4_t& w, const lc_u32x4_t& x, const lc_f32x4_t& cin) __attribute__((always_inline)) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lc_bf16x8_t, w), __builtin_bit_cast(lc_bf16x8_t, x), cin, 0, 0, 0);
-  };
+  // (the shared pieces are reached through these lambdas, and the zeroing and the bias add below stay written out - lc_add_bias's
+  // text - because that is the form in which the pinned instantiations keep their instruction stream)
   auto store_pending = [&](int idx) __attribute__((always_inline)) {
-    char* p = pend_base + (pend_off0 + static_cast<uint32_t>(idx >> 1) * 16u * pend_ldn + static_cast<uint32_t>(idx & 1) * 64u);
-    switch (idx) {
-      case 0: *reinterpret_cast<lc_u32x4_t*>(p) = pend[0]; break;
-      case 1: *reinterpret_cast<lc_u32x4_t*>(p) = pend[1]; break;
-      case 2: *reinterpret_cast<lc_u32x4_t*>(p) = pend[2]; break;
-      case 3: *reinterpret_cast<lc_u32x4_t*>(p) = pend[3]; break;
-      case 4: *reinterpret_cast<lc_u32x4_t*>(p) = pend[4]; break;
-      case 5: *reinterpret_cast<lc_u32x4_t*>(p) = pend[5]; break;
-      case 6: *reinterpret_cast<lc_u32x4_t*>(p) = pend[6]; break;
-      default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[7]; break;
-    }
+    lc_store_parked(pend, idx, pend_base, pend_off0, pend_ldn);
   };
   // residual tile `ti`: uniform base (&residual[m0 + wm * 80][n0 + wn * 64]), row stride, rows that exist from there
   [[maybe_unused]] auto residual_of = [&](int ti, const uint16_t*& base, int& ld, int& rows) __attribute__((always_inline)) {
@@ -1076,18 +1041,9 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   };
   // piece (b, pr) of a residual: this lane's row (clamped to the last real row: rows past M are never stored) x 8 consecutive n
   [[maybe_unused]] auto res_piece = [&](const uint16_t* base, int ld, int rows, int b, int pr) __attribute__((always_inline)) {
-    int r = b * 16 + frow;
-    r = r < rows ? r : rows - 1;
-    return *reinterpret_cast<const lc_u32x4_t*>(base + static_cast<size_t>(r) * ld + (fq & 1) * 16 + (fq & 2) * 4 + 32 * pr);
+    return lc_res_piece(base, ld, rows, frow, fq, b, pr);
   };
-  [[maybe_unused]] auto add_piece = [&](int b, int pr, const lc_u32x4_t& qv) __attribute__((always_inline)) {
-    const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(qv[0], qv[2], false, false);
-    const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(qv[1], qv[3], false, false);
-    acc[2 * pr][b][0] += f16lo_to_f32(s0[0]); acc[2 * pr][b][1] += f16hi_to_f32(s0[0]);
-    acc[2 * pr][b][2] += f16lo_to_f32(s1[0]); acc[2 * pr][b][3] += f16hi_to_f32(s1[0]);
-    acc[2 * pr + 1][b][0] += f16lo_to_f32(s0[1]); acc[2 * pr + 1][b][1] += f16hi_to_f32(s0[1]);
-    acc[2 * pr + 1][b][2] += f16lo_to_f32(s1[1]); acc[2 * pr + 1][b][3] += f16hi_to_f32(s1[1]);
-  };
+  [[maybe_unused]] auto add_piece = [&](int b, int pr, const lc_u32x4_t& qv) __attribute__((always_inline)) { lc_add_piece(acc, b, pr, qv); };
 
   int cur = 0;
   if constexpr (RES == 1) {                        // the first tile's accumulators start as its residual rows (0 + r: the wide kernel's bits)
@@ -1114,32 +1070,32 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   // stage has landed in every wave - the barrier - before the first read of the next stage)
 #define L3_GROUP(a)                                                                                    \
   do {                                                                                                 \
-    acc[a][0] = mfma(fw[a], fx[0], acc[a][0]);                                                         \
-    acc[a][1] = mfma(fw[a], fx[1], acc[a][1]);                                                         \
-    acc[a][2] = mfma(fw[a], fx[2], acc[a][2]);                                                         \
-    acc[a][3] = mfma(fw[a], fx[3], acc[a][3]);                                                         \
-    acc[a][4] = mfma(fw[a], fx[4], acc[a][4]);                                                         \
+    acc[a][0] = lc_mfma_bf16(fw[a], fx[0], acc[a][0]);                                                 \
+    acc[a][1] = lc_mfma_bf16(fw[a], fx[1], acc[a][1]);                                                 \
+    acc[a][2] = lc_mfma_bf16(fw[a], fx[2], acc[a][2]);                                                 \
+    acc[a][3] = lc_mfma_bf16(fw[a], fx[3], acc[a][3]);                                                 \
+    acc[a][4] = lc_mfma_bf16(fw[a], fx[4], acc[a][4]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
   } while (0)
 #define L3_LAST(wsrc, xsrc)                                                                            \
   do {                                                                                                 \
-    acc[3][0] = mfma(fw[3], fx[0], acc[3][0]);                                                         \
+    acc[3][0] = lc_mfma_bf16(fw[3], fx[0], acc[3][0]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     fx[0] = lc_lds_read((xsrc));                                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    acc[3][1] = mfma(fw[3], fx[1], acc[3][1]);                                                         \
+    acc[3][1] = lc_mfma_bf16(fw[3], fx[1], acc[3][1]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     fx[1] = lc_lds_read((xsrc) + 2048);                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    acc[3][2] = mfma(fw[3], fx[2], acc[3][2]);                                                         \
+    acc[3][2] = lc_mfma_bf16(fw[3], fx[2], acc[3][2]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     fx[2] = lc_lds_read((xsrc) + 4096);                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    acc[3][3] = mfma(fw[3], fx[3], acc[3][3]);                                                         \
+    acc[3][3] = lc_mfma_bf16(fw[3], fx[3], acc[3][3]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     fx[3] = lc_lds_read((xsrc) + 6144);                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
-    acc[3][4] = mfma(fw[3], fx[4], acc[3][4]);                                                         \
+    acc[3][4] = lc_mfma_bf16(fw[3], fx[4], acc[3][4]);                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                 \
     fx[4] = lc_lds_read((xsrc) + 8192);                                                                \
     fw[3] = lc_lds_read((wsrc) + 6144);                                                                \
@@ -1225,21 +1181,7 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
 #pragma unroll
         for (int b = 0; b < 5; ++b) acc[a][b] += bv[a];
     }
-    if (epi & EPI_QUICKGELU) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 5; ++b)
-#pragma unroll
-          for (int j = 0; j < 4; j += 2) {
-            const lc_f32x2_t v = {acc[a][b][j], acc[a][b][j + 1]};
-            const lc_f32x2_t t = v * lc_f32x2_t{-2.4554669595930157f, -2.4554669595930157f};
-            const lc_f32x2_t d = lc_f32x2_t{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + lc_f32x2_t{1.0f, 1.0f};
-            const lc_f32x2_t o = v * lc_f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-            acc[a][b][j] = o[0];
-            acc[a][b][j + 1] = o[1];
-          }
-    }
+    if (epi & EPI_QUICKGELU) lc_quickgelu(acc);
     if constexpr (RES == 2) {                        // long K: the residual behind the bias
 #pragma unroll
       for (int b = 0; b < 4; ++b)
@@ -1258,26 +1200,13 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
       for (int b = 0; b < 5; ++b)
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
-          uint32_t lo[2], hi[2];
-#pragma unroll
-          for (int w = 0; w < 2; ++w) {
-            if constexpr (F16O) {
-              lo[w] = pack_f16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
-              hi[w] = pack_f16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
-            } else {
-              lo[w] = pack_bf16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
-              hi[w] = pack_bf16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
-            }
-          }
-          const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(lo[0], hi[0], false, false);
-          const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(lo[1], hi[1], false, false);
+          const lc_u32x4_t val = lc_pack_piece<F16O>(acc, b, pr);
           if constexpr (RES == 1) {                  // the rotation: this piece's accumulators restart as the next tile's residual piece
             const lc_u32x4_t nextres = b < 4 ? pend[2 * b + pr] : r4[pr];
             acc[2 * pr][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
             acc[2 * pr + 1][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
             if (res_kt >= 0) add_piece(b, pr, nextres);
           }
-          const lc_u32x4_t val = {s0[0], s1[0], s0[1], s1[1]};
           if (b < 4) pend[2 * b + pr] = val;
           else own4[pr] = val;
         }
@@ -1326,26 +1255,14 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
   const char* const X0 = p0.X; const char* const W0 = p0.W; const float* const B0 = p0.bias; void* const O0 = p0.out;
   const float* const CS0 = p0.colscale; const float alpha0 = p0.alpha;
   const int N0 = p0.N, K0 = p0.K;
-  int M0 = p0.Mub;
-  if (p0.m_dev) { const int md = *p0.m_dev; M0 = md < M0 ? md : M0; }
-  M0 = __builtin_amdgcn_readfirstlane(M0);
-  const int tiles_n0 = N0 / lcBN;
-  const int total0 = tiles_n0 * ((M0 + lcBM - 1) / lcBM);
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
-  const int q0 = total0 >> 3, r0 = total0 & 7;
-  const int lo0 = xcd < r0 ? xcd * (q0 + 1) : r0 * (q0 + 1) + (xcd - r0) * q0, len0 = xcd < r0 ? q0 + 1 : q0;
-  const int my_tiles = slot < len0 ? (len0 - slot + per - 1) / per : 0;
-  if (my_tiles == 0) return;
-  const int nk0 = K0 / 128;                        // 128 k per K-step (rows of 128 bytes)
-  const int S = my_tiles * nk0;
-  auto tile_of = [&](int ti, int& m0, int& n0) {
-    const int logical = lo0 + slot + ti * per;
-    const int tm = logical / tiles_n0;
-    m0 = tm * lcBM;
-    n0 = (logical - tm * tiles_n0) * lcBN;
-  };
+  LcSchedule<lcBM, false, 128> sc(p0, p1);
+  if (sc.my_tiles == 0) return;
+  sc.count_ksteps(p0, p1);
+  const int M0 = sc.M0, nk0 = sc.nk0, my_tiles = sc.my_tiles;
   if (wid < 4) {
-    // ---- loader waves: the lc kernel's (a row of either operand is 128 bytes per K-step, whatever the element type) ----
+    // ---- loader waves: lc_loader_wave's protocol for one problem with rows of K bytes and no bias row, written out: through the
+    // routine itself the MFMA waves of this kernel, which sit at their register limit, spill one register more ----
+    const int S = sc.S;
     const int sub = lane >> 3, ch = lane & 7;
     uint32_t offW[8], offX[4];
     const char* Wt = nullptr;
@@ -1356,8 +1273,8 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
       offW[i] = static_cast<uint32_t>(row) * rs + ((ch ^ (row & 7)) << 4);
     }
     auto set_tile = [&](int ti) {
-      int m0, n0;
-      tile_of(ti, m0, n0);
+      bool second; int m0, n0;
+      sc.tile_of(ti, second, m0, n0);
       Wt = W0 + static_cast<size_t>(n0) * rs;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1387,13 +1304,13 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
     issue_stage();
     if (S > 1) issue_stage();
     if (S > 2) issue_stage();
-    if (S > 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (S > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (S > 2) LC_VMCNT(2 * lc_pieces(lcBM));
+    else if (S > 1) LC_VMCNT(lc_pieces(lcBM));
+    else LC_VMCNT(0);
     __builtin_amdgcn_s_barrier();
     for (int s = 0; s < S; ++s) {
-      if (s + 2 < S) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (s + 2 < S) LC_VMCNT(lc_pieces(lcBM));
+      else LC_VMCNT(0);
       __builtin_amdgcn_s_barrier();
       if (s + 3 < S) issue_stage();
     }
@@ -1415,14 +1332,8 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
   int pend_idx = 4;
   char* pend_base = nullptr;
   uint32_t pend_off0 = 0, pend_ldn = 0;
-  auto store_pending = [&](int idx) __attribute__((always_inline)) {
-    char* p = pend_base + (pend_off0 + static_cast<uint32_t>(2 + (idx >> 1)) * 16u * pend_ldn + static_cast<uint32_t>(idx & 1) * 64u);
-    switch (idx) {
-      case 0: *reinterpret_cast<lc_u32x4_t*>(p) = pend[0]; break;
-      case 1: *reinterpret_cast<lc_u32x4_t*>(p) = pend[1]; break;
-      case 2: *reinterpret_cast<lc_u32x4_t*>(p) = pend[2]; break;
-      default: *reinterpret_cast<lc_u32x4_t*>(p) = pend[3]; break;
-    }
+  auto store_pending = [&](int idx) __attribute__((always_inline)) {      // pend[idx] = piece (2 + idx / 2, idx % 2)
+    lc_store_parked<4, 2>(pend, idx, pend_base, pend_off0, pend_ldn);
   };
   auto mfma8 = [&](int a, int b) __attribute__((always_inline)) {
     lc_i32x8_t va, vb;
@@ -1493,12 +1404,9 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
     cur = nxt;
   };
   for (int ti = 0; ti < my_tiles; ++ti) {
-    int m0, n0;
-    tile_of(ti, m0, n0);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    bool second; int m0, n0;
+    sc.tile_of(ti, second, m0, n0);
+    lc_zero(acc);
     for (int kt = 0; kt < nk0; ++kt) kstep();
     // dequantisation fused with the bias: acc * (alpha * colscale[n]) + bias[n]  (the wide kernel's expression)
 #pragma unroll
@@ -1516,15 +1424,7 @@ __global__ __launch_bounds__(768) void gemm_lc2q_kernel(LcProblem p0, LcProblem 
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
-        uint32_t lo[2], hi[2];
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-          lo[w] = pack_bf16x2(acc[2 * pr][b][2 * w], acc[2 * pr][b][2 * w + 1]);
-          hi[w] = pack_bf16x2(acc[2 * pr + 1][b][2 * w], acc[2 * pr + 1][b][2 * w + 1]);
-        }
-        const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(lo[0], hi[0], false, false);
-        const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(lo[1], hi[1], false, false);
-        const lc_u32x4_t val = {s0[0], s1[0], s0[1], s1[1]};
+        const lc_u32x4_t val = lc_pack_piece<false>(acc, b, pr);
         if (b >= 2) pend[(b - 2) * 2 + pr] = val;
         if ((b < 2 || !park) && m0 + wm * 64 + b * 16 + frow < M0 && !(epi & 256))
           *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + static_cast<uint32_t>(b * 16) * ldn + pr * 64)) = val;

@@ -204,22 +204,22 @@ __device__ __forceinline__ void gemm_wide_body(const char* __restrict__ X, const
   const int base_total = tiles_n * tiles_m;
   const int total = base_total * ksplit;
   const int xcd = blockIdx.x & 7, slot = ONE ? 0 : blockIdx.x >> 3, per_xcd_blocks = ONE ? 1 : gridDim.x >> 3;
-  const int q = total >> 3, r = total & 7;
-  const int range_lo = ONE ? one_tile : (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q);
-  const int range_len = ONE ? 1 : (xcd < r ? q + 1 : q);
+  const DealShare share = deal_share(total, xcd);      // (cmh_common.h: the deal, as gemm.hip's tile_cost replays it)
+  const int range_lo = ONE ? one_tile : share.lo;
+  const int range_len = ONE ? 1 : share.len;
   // GRP: this XCD's contiguous range of the SECOND problem's tiles follows its range of the first in the workgroups' stride:
   // position j = slot + ti * per_xcd_blocks of the concatenation, so a workgroup's first n_first tiles are the first problem's
   int tiles_n1 = 0, range_lo1 = 0, range_len1 = 0, n_first = 0;
   if constexpr (GRP) {
     tiles_n1 = p1.N / wBN;
     const int total1 = tiles_n1 * ((M1 + BMt - 1) / BMt);
-    const int q1 = total1 >> 3, r1 = total1 & 7;
-    range_lo1 = xcd < r1 ? xcd * (q1 + 1) : r1 * (q1 + 1) + (xcd - r1) * q1;
-    range_len1 = xcd < r1 ? q1 + 1 : q1;
-    n_first = slot < range_len ? (range_len - slot + per_xcd_blocks - 1) / per_xcd_blocks : 0;
+    const DealShare share1 = deal_share(total1, xcd);
+    range_lo1 = share1.lo;
+    range_len1 = share1.len;
+    n_first = deal_count(range_len, slot, per_xcd_blocks);
   }
   const int span = GRP ? range_len + range_len1 : range_len;
-  const int my_tiles = slot < span ? (span - slot + per_xcd_blocks - 1) / per_xcd_blocks : 0;
+  const int my_tiles = deal_count(span, slot, per_xcd_blocks);
   if (my_tiles == 0) return;
 
   int nk = K / BK / ksplit;   // K-steps per (virtual) tile

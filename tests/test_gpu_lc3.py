@@ -96,6 +96,97 @@ def test_lc3_grouped_launch_gives_the_wide_kernels_bits(case, mode):
     assert torch.equal(got_md[0], ref[0]) and torch.equal(got_md[1][:Mb - 37], ref[1][:Mb - 37])
 
 
+# ---- the edges of the tile deal the loader / consumer kernels share (csrc/cmh_common.h: deal_share / deal_count / deal_tile; gemm_lc.hip:
+# LcSchedule), under every form that deals with it: the 8-wave kernel (mode 1), the 12-wave forms on 128 rows (4) and 160 rows (9), the
+# e4m3 form (7).  Small shapes, each against the wide kernel's bits.
+FORM = {1: 1, 4: 2, 9: 3}                  # mode -> gemm_route's answer
+FAMILY = {1: 3, 4: 4, 9: 5, 7: 6}          # mode -> cmh_gemm_plan's family (GEMM_LC, GEMM_LC2, GEMM_LC3, GEMM_LC2Q)
+# (M, N, K, kind):
+#  161 x 256: two tiles on a grid of 8 - six workgroups return at once, the second tile is a one-row tail
+#  4641 x 2304: 30 x 9 = 270 tiles of 160 rows (37 x 9 of 128) on 256 workgroups - total % 8 != 0, some workgroups take two tiles and
+#  park stores, the last m-tile is partial
+#  kind 1 at K = 512 / 1088: the residual first / behind the bias
+EDGE_PLAIN = [(161, 256, 512, 0), (4641, 2304, 512, 0), (161, 256, 512, 1), (161, 256, 1088, 1)]
+# grouped, residual-free (the two K take different residual forms).  The longer K runs first.  First case: every XCD that has a tile of
+# the second problem has one of the first, each workgroup runs one and then the other.  Second case: the first problem is one tile
+# of 160 rows (two of 128) against four of the second, so the workgroups of the next XCDs start in the second problem (n_first == 0)
+EDGE_GROUPED = [((161, 256, 512), (130, 512, 1024)), ((161, 512, 512), (130, 256, 1024))]
+
+
+def _reached(N, mode, a, b, epi, dt=None):
+    if mode in FORM:
+        assert N.gemm_route(a, b, epi) == FORM[mode]
+    plan = N.gemm_plan(a, b, epi, dt)[1]      # (the e4m3 form is not one of gemm_route's answers: the plan's family says it)
+    assert [p["family"] for p in plan] == [FAMILY[mode]]
+
+
+@pytest.mark.parametrize("mode", [1, 4, 9])
+@pytest.mark.parametrize("case", range(len(EDGE_PLAIN)))
+def test_deal_edges_plain_launch_gives_the_wide_kernels_bits(case, mode):
+    import cmh_native as N
+    M, Nn, K, kind = EDGE_PLAIN[case]
+    g = torch.Generator().manual_seed(1200 + case)
+    p = _problem(M, Nn, K, kind, g)
+    try:
+        if M <= 2048:
+            N.set_gemm_rows(0)
+        N.set_gemm_lc(0)
+        ref = _plain(N, p, kind)
+        N.set_gemm_lc(mode)
+        _reached(N, mode, (M, Nn, K), None, _epi(N, kind))
+        got = _plain(N, p, kind)
+    finally:
+        N.set_gemm_lc(-1)
+        N.set_gemm_rows(-1)
+    assert torch.equal(ref, got)
+
+
+@pytest.mark.parametrize("case", [0, 1])
+def test_deal_edges_plain_e4m3_launch_gives_the_wide_kernels_bits(case):
+    import cmh_native as N
+    M, Nn, K, _ = EDGE_PLAIN[case]
+    g = torch.Generator().manual_seed(1300 + case)
+    e4m3 = lambda shape, sc: (torch.randn(*shape, generator=g) * sc).to(torch.float8_e4m3fn).view(torch.uint8).to(DEV)
+    x, w = e4m3((M, K), 1.0), e4m3((Nn, K), 8 * K ** -0.5)
+    cs, b = (torch.rand(Nn, generator=g) * 0.1 + 0.05).to(DEV), torch.randn(Nn, generator=g).to(DEV)
+    try:
+        if M <= 2048:
+            N.set_gemm_rows(0)
+        N.set_gemm_lc(0)
+        ref = N.linear_gemm_fp8(x, w, cs, 0.37, bias=b, out="bf16")
+        N.set_gemm_lc(7)
+        _reached(N, 7, (M, Nn, K), None, N.EPI_BIAS | N.EPI_OUT_BF16, N.FP8)
+        got = N.linear_gemm_fp8(x, w, cs, 0.37, bias=b, out="bf16")
+    finally:
+        N.set_gemm_lc(-1)
+        N.set_gemm_rows(-1)
+    assert torch.equal(ref, got)
+
+
+@pytest.mark.parametrize("mode", [1, 4, 9])
+@pytest.mark.parametrize("case", range(len(EDGE_GROUPED)))
+def test_deal_edges_grouped_launch_gives_the_wide_kernels_bits(case, mode):
+    import cmh_native as N
+    (Ma, Na, Ka), (Mb, Nb, Kb) = EDGE_GROUPED[case]
+    g = torch.Generator().manual_seed(1400 + case)
+    probs = [_problem(Ma, Na, Ka, 0, g), _problem(Mb, Nb, Kb, 0, g)]
+    md = torch.tensor([Mb - 37], dtype=torch.int32, device=DEV)      # once more with a device-side row count on the second problem
+    try:
+        N.set_gemm_rows(0)
+        N.set_gemm_lc(0)
+        ref = [_plain(N, p, 0) for p in probs]
+        N.set_gemm_lc(mode)
+        _reached(N, mode, (Ma, Na, Ka), (Mb, Nb, Kb), _epi(N, 0))
+        got = N.linear_gemm_grouped(probs, out="bf16")
+        got_md = N.linear_gemm_grouped(probs, out="bf16", m_dev=(None, md))
+    finally:
+        N.set_gemm_lc(-1)
+        N.set_gemm_rows(-1)
+    for r, o in zip(ref, got):
+        assert torch.equal(r, o)
+    assert torch.equal(got_md[0], ref[0]) and torch.equal(got_md[1][:Mb - 37], ref[1][:Mb - 37])
+
+
 def test_lc3_never_writes_rows_past_the_device_side_count():
     import ctypes as C
     import cmh_native as N
