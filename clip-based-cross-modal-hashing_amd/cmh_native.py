@@ -163,6 +163,12 @@ SIGNATURES = {
     "cmh_soft_query_planes": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "cmh_soft_topk_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_soft_topk": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "cmh_topk_few_masked_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_hamming_topk_few_masked": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
+    "cmh_soft_topk_masked_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "cmh_soft_topk_masked": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
+    "cmh_mask_from_labels": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p]),
+    "cmh_mask_from_ids": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -895,6 +901,102 @@ def soft_topk(q, r_planes, bits, k):
     check(lib().cmh_soft_topk(ptr(qs), ptr(qm), ptr(rs), ptr(rn), Q, N, int(bits), k, ptr(idx), ptr(wdist), ptr(ws), ws.numel(),
                               stream_ptr(dev)), "cmh_soft_topk")
     return idx, wdist
+
+
+MASK_ANY, MASK_ALL, MASK_NONE = 0, 1, 2      # include/cmh.h CMH_MASK_*: the modes of cmh_mask_from_labels
+
+
+def mask_words(n):
+    """Words of an allow-mask over n items: int64 [ceil(n / 64)], bit j % 64 of word j / 64 = item j is admitted."""
+    return (int(n) + 63) // 64
+
+
+def _mask_operand(what, allow, N):
+    require_gpu(allow)
+    if allow.dtype != torch.int64 or allow.dim() != 1 or not allow.is_contiguous() or allow.numel() != mask_words(N):
+        raise NativeError(f"{what}: the allow-mask is a contiguous int64 tensor [{mask_words(N)}] for {N} items, "
+                          f"not {allow.dtype} {tuple(allow.shape)}")
+    return allow
+
+
+def hamming_topk_few_masked(q_planes, r_planes, allow, bits, k):
+    """hamming_topk_few over only the items the allow-mask admits (int64 [ceil(N / 64)] on the GPU): -> (idx int32 [Q, k], dist f32
+    [Q, k], found int32 [Q]).  Row q holds the first found[q] = min(k, admitted) admitted items in ascending (distance, DATABASE
+    index); the columns behind hold idx = -1, dist = +inf.  k is checked against N; nothing synchronises."""
+    qs, qn, rs, rn, Q, N, _ = _retrieval_operands("hamming_topk_few_masked", q_planes, r_planes, bits, None, None)
+    allow = _mask_operand("hamming_topk_few_masked", allow, N)
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= FEW_K_MAX:
+        raise NativeError(f"hamming_topk_few_masked: k={k} outside [1, {FEW_K_MAX}]")
+    if k > N:
+        raise NativeError(f"hamming_topk_few_masked: k={k} exceeds N={N}")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    found = torch.empty(Q, dtype=torch.int32, device=dev)
+    need = lib().cmh_topk_few_masked_workspace_bytes(Q, N, int(bits))
+    ws = workspace(need, dev, "retrieval_few")
+    check(lib().cmh_hamming_topk_few_masked(ptr(qs), ptr(qn), ptr(rs), ptr(rn), ptr(allow), Q, N, int(bits), k, ptr(idx), ptr(dist),
+                                            ptr(found), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_hamming_topk_few_masked")
+    return idx, dist, found
+
+
+def soft_topk_masked(q, r_planes, allow, bits, k):
+    """soft_topk over only the items the allow-mask admits: -> (idx int32 [Q, k], wdist int32 [Q, k], found int32 [Q]); the columns
+    at and behind found[q] hold idx = -1, wdist = 2^31 - 1."""
+    (qs, qm), (rs, rn) = q[:2], r_planes
+    require_gpu(qs, qm, rs, rn)
+    Q, N = qs.shape[0], rs.shape[0]
+    W = (int(bits) + 31) // 32
+    fit("soft_topk_masked", (qs, (Q, W)), (qm, (Q, 4, W)), (rs, (N, W)), (rn, (N, W)))
+    for t in (qs, qm, rs, rn):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("soft_topk_masked: packed operands are contiguous int32 tensors (soft_query_planes / pack_codes)")
+    allow = _mask_operand("soft_topk_masked", allow, N)
+    dev = qs.device
+    k = int(k)
+    if not 1 <= k <= SOFT_K_MAX:
+        raise NativeError(f"soft_topk_masked: k={k} outside [1, {SOFT_K_MAX}]")
+    if k > N:
+        raise NativeError(f"soft_topk_masked: k={k} exceeds N={N}")
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    wdist = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    found = torch.empty(Q, dtype=torch.int32, device=dev)
+    need = lib().cmh_soft_topk_masked_workspace_bytes(Q, N, int(bits))
+    ws = workspace(need, dev, "retrieval_soft")
+    check(lib().cmh_soft_topk_masked(ptr(qs), ptr(qm), ptr(rs), ptr(rn), ptr(allow), Q, N, int(bits), k, ptr(idx), ptr(wdist),
+                                     ptr(found), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_soft_topk_masked")
+    return idx, wdist, found
+
+
+def mask_from_labels(r_lab, need, mode, classes):
+    """-> an allow-mask int64 [ceil(N / 64)] from packed labels r_lab int32 [N, LW] and the packed class set need int32 [LW]:
+    MASK_ANY (label & need) != 0, MASK_ALL (label & need) == need, MASK_NONE (label & need) == 0; tail bits zero."""
+    require_gpu(r_lab, need)
+    N_, LW = r_lab.shape[0], (int(classes) + 31) // 32
+    fit("mask_from_labels", (r_lab, (N_, LW)), (need, (LW,)))
+    for t in (r_lab, need):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("mask_from_labels: packed labels are contiguous int32 tensors (pack_labels)")
+    allow = torch.empty(mask_words(N_), dtype=torch.int64, device=r_lab.device)
+    check(lib().cmh_mask_from_labels(ptr(r_lab), ptr(need), int(mode), N_, int(classes), ptr(allow), stream_ptr(r_lab.device)),
+          "cmh_mask_from_labels")
+    return allow
+
+
+def mask_from_ids(allow, ids, n, value):
+    """Sets (value 1) or clears (value 0) the bits of the items `ids` (int32 [M] on the GPU, duplicates are legal) in the allow-mask
+    over n items, in place.  An id outside [0, n) changes nothing and raises after the call (one host sync reads the flag back)."""
+    allow = _mask_operand("mask_from_ids", allow, n)
+    require_gpu(ids)
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise NativeError("mask_from_ids: ids is a contiguous int32 tensor [M]")
+    bad = torch.zeros(1, dtype=torch.int32, device=allow.device)
+    check(lib().cmh_mask_from_ids(ptr(ids), ids.numel(), int(n), int(value), ptr(allow), ptr(bad), stream_ptr(allow.device)),
+          "cmh_mask_from_ids")
+    if int(bad.item()):
+        raise NativeError(f"mask_from_ids: an id outside [0, {int(n)})")
+    return allow
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte

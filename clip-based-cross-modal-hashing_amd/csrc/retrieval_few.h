@@ -5,6 +5,7 @@
 //     template <int W> struct Query { int hs; load(qa, qb, hstar, q, last); };      a query's wave-uniform words and its radius
 //     template <int W> static int bin(const Item<W>&, const Query<W>&, int bits);   the integer distance, 0 <= bin < FewArgs::bins
 //     static Out out(int bin);                             what the distance column holds for that bin
+//     static Out pad();                                    ... and for a column behind a masked search's last admitted item
 //   };
 // and the pipeline is the stable counting sort over that integer:
 //   few_pass<.., false>  per (chunk, group of <= FewArgs::group queries) the histogram of the bins, left in the workspace as
@@ -19,6 +20,8 @@
 // on shared words.  Queries beyond a group go to further workgroups (grid.y) that read the same chunk again (from L2 / the
 // Infinity Cache: the groups of a chunk are dispatched together).
 // No atomics on the outputs: every (query, column < k) is written exactly once, so two calls give equal bytes.
+// The FILTERED search (MASKED = true) is the same pipeline over the items an allow-mask admits: one 64-bit word per slab in the
+// walk's `valid`, and a radius kernel that takes "fewer than k admitted" (found < k; it writes found and the pad columns).
 #pragma once
 
 #include "cmh_common.h"
@@ -65,10 +68,14 @@ struct Item {
 };
 
 // ---- the walk of both passes: SELECT = false the histogram, true the stable counting sort of the items at bin <= h* ---------------
-template <class Rule, int W, bool SELECT>
+// MASKED: only the items an allow-mask admits are counted and placed.  allow u64 [ceil(N / 64)], bit j % 64 of word j / 64 = item j
+// is admitted; a slab of 64 items starts at a multiple of 64 (chunks are multiples of 64 items, a step is 64 kFewSlabs), so its
+// 64 bits are ONE wave-uniform word, requested with the slab's rows and ANDed into `valid`.  Bits at and behind N are cut by
+// j < je as the lanes behind the last item are; a slab that starts at or behind je reads no word.
+template <class Rule, int W, bool SELECT, bool MASKED>
 __global__ __launch_bounds__(64) void few_pass_kernel(FewArgs a, const uint32_t* __restrict__ qa, const uint32_t* __restrict__ qb,
                                                       const uint32_t* __restrict__ rs, const uint32_t* __restrict__ rn,
-                                                      const int32_t* __restrict__ hstar) {
+                                                      const int32_t* __restrict__ hstar, const uint64_t* __restrict__ allow) {
   using Query = typename Rule::template Query<W>;
   using Out = typename Rule::Out;
   extern __shared__ uint32_t col[];      // [nq][bins]: counters (histogram) or cursors (select)
@@ -92,17 +99,20 @@ __global__ __launch_bounds__(64) void few_pass_kernel(FewArgs a, const uint32_t*
   Out* dist = static_cast<Out*>(a.dist);
   // kFewSlabs x 64 items at a time: that many independent row loads per plane are in flight per lane (one wave per workgroup and two
   // workgroups per SIMD: nothing else hides the latency), and the next set is requested before this one is worked on.
+  constexpr int kWords = MASKED ? kFewSlabs : 1;                             // (unmasked: never touched)
   Item<W> cur[kFewSlabs], nxt[kFewSlabs];
-  auto fetch = [&](Item<W>(&it)[kFewSlabs], int64_t base) {
+  uint64_t cura[kWords], nxta[kWords];
+  auto fetch = [&](Item<W>(&it)[kFewSlabs], uint64_t(&aw)[kWords], int64_t base) {
 #pragma unroll
     for (int u = 0; u < kFewSlabs; ++u) {
       const int64_t j = base + u * 64 + lane;
       it[u].load(rs, rn, j < je ? j : je - 1);                               // (lanes behind the last item read it once more)
+      if constexpr (MASKED) aw[u] = base + u * 64 < je ? allow[(base + u * 64) >> 6] : uint64_t(0);
     }
   };
-  fetch(cur, jb);
+  fetch(cur, cura, jb);
   for (int64_t base = jb; base < je; base += 64 * kFewSlabs) {
-    fetch(nxt, base + 64 * kFewSlabs);
+    fetch(nxt, nxta, base + 64 * kFewSlabs);
     Query qc, qx;
     qc.load(qa, qb, hstar, q0, last);
     for (int qi = 0; qi < nq; ++qi) {
@@ -110,7 +120,8 @@ __global__ __launch_bounds__(64) void few_pass_kernel(FewArgs a, const uint32_t*
 #pragma unroll
       for (int u = 0; u < kFewSlabs; ++u) {                                   // in index order: slab u lies before slab u + 1
         const int64_t j = base + u * 64 + lane;
-        const bool valid = j < je;                                            // lanes behind item N - 1 count and place nothing
+        bool valid = j < je;                                                  // lanes behind item N - 1 count and place nothing
+        if constexpr (MASKED) valid = valid && ((cura[u] >> lane) & 1u);      // ... and items the mask does not admit
         const int h = Rule::template bin<W>(cur[u], qc, a.bits);
         if (!SELECT) {
           if (valid) atomicAdd(&col[qi * a.bins + h], 1u);
@@ -139,6 +150,10 @@ __global__ __launch_bounds__(64) void few_pass_kernel(FewArgs a, const uint32_t*
     }
 #pragma unroll
     for (int u = 0; u < kFewSlabs; ++u) cur[u] = nxt[u];
+    if constexpr (MASKED) {
+#pragma unroll
+      for (int u = 0; u < kFewSlabs; ++u) cura[u] = nxta[u];
+    }
   }
   if (!SELECT) {
     __syncthreads();
@@ -170,8 +185,8 @@ __global__ __launch_bounds__(kFewParts * kFewBinTile) void few_total_kernel(FewA
 }
 
 // ---- one wave per query: tot becomes off (the exclusive prefix over the bins), hstar = the first bin whose cumulative count >= k ----
-__global__ __launch_bounds__(64) void few_radius_kernel(FewArgs a) {
-  const int lane = threadIdx.x, q = blockIdx.x;
+// -> h* of the wave's query, -1 when the query's bins hold fewer than k items (a masked search only); total = the sum of its bins
+__device__ __forceinline__ int few_radius(const FewArgs& a, int lane, int q, uint32_t& total) {
   uint32_t* tot = a.tot + static_cast<size_t>(q) * a.bins;
   uint32_t carry = 0;
   int hs = -1;
@@ -189,7 +204,34 @@ __global__ __launch_bounds__(64) void few_radius_kernel(FewArgs a) {
     if (hs < 0 && m) hs = h0 + __ffsll(static_cast<unsigned long long>(m)) - 1;
     carry += __shfl(x, 63, 64);
   }
-  if (lane == 0) a.hstar[q] = hs;      // (k <= N = the sum of a query's bins: always found)
+  total = carry;
+  return hs;
+}
+
+__global__ __launch_bounds__(64) void few_radius_kernel(FewArgs a) {
+  uint32_t total;
+  const int hs = few_radius(a, threadIdx.x, blockIdx.x, total);
+  if (threadIdx.x == 0) a.hstar[blockIdx.x] = hs;      // (k <= N = the sum of a query's bins: always found)
+}
+
+// The masked search's: the bins hold the A admitted items, and A < k is legal.  Then h* = the last bin (everything admitted is
+// placed, in columns 0..A-1), found = A, and the columns at and behind found are written HERE, once: idx = -1, dist = pad.
+template <class Out>
+__global__ __launch_bounds__(64) void few_radius_masked_kernel(FewArgs a, int32_t* __restrict__ found, Out pad) {
+  const int lane = threadIdx.x, q = blockIdx.x;
+  uint32_t total;
+  const int hs = few_radius(a, lane, q, total);
+  const int got = hs < 0 ? static_cast<int>(total) : a.k;
+  if (lane == 0) {
+    a.hstar[q] = hs < 0 ? a.bins - 1 : hs;
+    found[q] = got;
+  }
+  Out* dist = static_cast<Out*>(a.dist);
+  for (int c = got + lane; c < a.k; c += 64) {
+    const size_t o = static_cast<size_t>(q) * a.k + c;
+    a.idx[o] = -1;
+    dist[o] = pad;
+  }
 }
 
 // ---- one thread per (bin <= h*, part) of a query: every image of its part becomes the cursor base of its (chunk, bin) ---------------
@@ -274,9 +316,10 @@ FewArgs few_args(const FewPlan& p, int Q, int64_t N, int bits, int k, int32_t* i
 // a lane fetches its item's row with one load of W words: rows of 2 and 4 words are read as 8 and 16 bytes
 int few_row_bytes(int W) { return W == 2 ? 8 : W == 4 ? 16 : 4; }
 
-template <class Rule, int W>
+// allow / found: null = the plain search; both given = the masked one (the masked walk, the radius kernel that writes found and pads)
+template <class Rule, int W, bool MASKED>
 int run_few_w(const char* what, const FewArgs& a, const FewPlan& p, const uint32_t* qa, const uint32_t* qb, const uint32_t* rs,
-              const uint32_t* rn, hipStream_t st) {
+              const uint32_t* rn, const uint64_t* allow, int32_t* found, hipStream_t st) {
   const int nq = a.Q < a.group ? a.Q : a.group;
   const size_t lds = static_cast<size_t>(nq) * a.bins * 4;
   const dim3 walk(p.S, p.groups), bins((a.bins + kFewBinTile - 1) / kFewBinTile, a.Q);
@@ -287,23 +330,44 @@ int run_few_w(const char* what, const FewArgs& a, const FewPlan& p, const uint32
     return CMH_OK;
   };
   int rc;
-  hipLaunchKernelGGL((few_pass_kernel<Rule, W, false>), walk, dim3(64), lds, st, a, qa, qb, rs, rn, static_cast<const int32_t*>(nullptr));
+  hipLaunchKernelGGL((few_pass_kernel<Rule, W, false, MASKED>), walk, dim3(64), lds, st, a, qa, qb, rs, rn,
+                     static_cast<const int32_t*>(nullptr), allow);
   if ((rc = launched("histogram")) != CMH_OK) return rc;
   hipLaunchKernelGGL(few_total_kernel, bins, dim3(kFewParts * kFewBinTile), 0, st, a);
   if ((rc = launched("totals")) != CMH_OK) return rc;
-  hipLaunchKernelGGL(few_radius_kernel, dim3(a.Q), dim3(64), 0, st, a);
+  if constexpr (MASKED)
+    hipLaunchKernelGGL((few_radius_masked_kernel<typename Rule::Out>), dim3(a.Q), dim3(64), 0, st, a, found, Rule::pad());
+  else
+    hipLaunchKernelGGL(few_radius_kernel, dim3(a.Q), dim3(64), 0, st, a);
   if ((rc = launched("radius")) != CMH_OK) return rc;
   hipLaunchKernelGGL(few_base_kernel, bins, dim3(kFewParts * kFewBinTile), 0, st, a);
   if ((rc = launched("bases")) != CMH_OK) return rc;
-  hipLaunchKernelGGL((few_pass_kernel<Rule, W, true>), walk, dim3(64), lds, st, a, qa, qb, rs, rn, static_cast<const int32_t*>(a.hstar));
+  hipLaunchKernelGGL((few_pass_kernel<Rule, W, true, MASKED>), walk, dim3(64), lds, st, a, qa, qb, rs, rn,
+                     static_cast<const int32_t*>(a.hstar), allow);
   return launched("select");
+}
+
+template <class Rule, bool MASKED>
+int run_few_m(const char* what, const FewArgs& a, const FewPlan& p, const uint32_t* qa, const uint32_t* qb, const uint32_t* rs,
+              const uint32_t* rn, const uint64_t* allow, int32_t* found, hipStream_t st) {
+  return p.W == 1   ? run_few_w<Rule, 1, MASKED>(what, a, p, qa, qb, rs, rn, allow, found, st)
+         : p.W == 2 ? run_few_w<Rule, 2, MASKED>(what, a, p, qa, qb, rs, rn, allow, found, st)
+         : p.W == 3 ? run_few_w<Rule, 3, MASKED>(what, a, p, qa, qb, rs, rn, allow, found, st)
+                    : run_few_w<Rule, 4, MASKED>(what, a, p, qa, qb, rs, rn, allow, found, st);
 }
 
 template <class Rule>
 int run_few(const char* what, const FewArgs& a, const FewPlan& p, const uint32_t* qa, const uint32_t* qb, const uint32_t* rs,
-            const uint32_t* rn, hipStream_t st) {
-  return p.W == 1 ? run_few_w<Rule, 1>(what, a, p, qa, qb, rs, rn, st) : p.W == 2 ? run_few_w<Rule, 2>(what, a, p, qa, qb, rs, rn, st)
-         : p.W == 3 ? run_few_w<Rule, 3>(what, a, p, qa, qb, rs, rn, st) : run_few_w<Rule, 4>(what, a, p, qa, qb, rs, rn, st);
+            const uint32_t* rn, hipStream_t st, const uint64_t* allow = nullptr, int32_t* found = nullptr) {
+  return allow ? run_few_m<Rule, true>(what, a, p, qa, qb, rs, rn, allow, found, st)
+               : run_few_m<Rule, false>(what, a, p, qa, qb, rs, rn, nullptr, nullptr, st);
+}
+
+// What a masked call refuses beyond the plain one's checks
+int check_few_mask(const char* what, const void* allow, const void* found) {
+  if (!allow || !found) return fail(CMH_ERR_INVALID, "%s: null pointer (allow, found)", what);
+  if (reinterpret_cast<uintptr_t>(allow) % 8) return fail(CMH_ERR_INVALID, "%s: the allow-mask holds 64-bit words: aligned to 8 bytes", what);
+  return CMH_OK;
 }
 
 }  // namespace

@@ -25,6 +25,7 @@
 // Queries beyond 16 go to further workgroups (grid.y) that read the same chunk again (from L2 / the Infinity Cache: the groups of a
 // chunk are dispatched together): the database is read once per 16 queries and pass, not once per query.
 // No atomics on the outputs: every (query, column < k) is written exactly once, so two calls give equal bytes.
+// cmh_hamming_topk_few_masked is the same search over the items an allow-mask admits (retrieval_few.h: MASKED).
 #include "retrieval_few.h"
 
 namespace cmh {
@@ -64,6 +65,7 @@ struct HammingRule {
     return bits - both + 2 * diff;
   }
   static __device__ __forceinline__ float out(int h) { return 0.5f * static_cast<float>(h); }
+  static float pad() { return __builtin_inff(); }
 };
 
 // As many chunks as fill the chip's wave slots once, none below 256 items (a small database is cut as cut_chunks of retrieval.hip
@@ -96,4 +98,27 @@ extern "C" int cmh_hamming_topk_few(const uint32_t* q_sign, const uint32_t* q_nz
     return fail(CMH_ERR_WORKSPACE, "hamming_topk_few: workspace %zu < %zu bytes", workspace_bytes, p.bytes(Q));
   const FewArgs a = few_args(p, Q, N, bits, k, idx, dist, workspace);
   return run_few<HammingRule>("hamming_topk_few", a, p, q_sign, q_nz, r_sign, r_nz, as_stream(stream));
+}
+
+extern "C" size_t cmh_topk_few_masked_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
+  return cmh_topk_few_workspace_bytes(Q, N, bits);      // (the filter adds nothing to the workspace: one plan for both)
+}
+
+extern "C" int cmh_hamming_topk_few_masked(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz,
+                                           const uint64_t* allow, int32_t Q, int64_t N, int32_t bits, int32_t k, int32_t* idx, float* dist,
+                                           int32_t* found, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_nz && r_sign && r_nz && idx && dist, "hamming_topk_few_masked: null pointer");
+  int rc = check_few_mask("hamming_topk_few_masked", allow, found);
+  if (rc != CMH_OK) return rc;
+  if ((rc = check_few_shape("hamming_topk_few_masked", Q, N, bits)) != CMH_OK) return rc;
+  CMH_CHECK_ARG(k >= 1 && k <= CMH_FEW_K_MAX, "hamming_topk_few_masked: k=%d outside [1, %d]", k, CMH_FEW_K_MAX);
+  CMH_CHECK_ARG(k <= N, "hamming_topk_few_masked: k=%d exceeds N=%lld", k, static_cast<long long>(N));
+  const FewPlan p = hamming_plan(Q, N, bits);
+  const uintptr_t row = few_row_bytes(p.W);
+  CMH_CHECK_ARG(reinterpret_cast<uintptr_t>(r_sign) % row == 0 && reinterpret_cast<uintptr_t>(r_nz) % row == 0,
+                "hamming_topk_few_masked: database planes of %d words per row must be aligned to %d bytes", p.W, static_cast<int>(row));
+  if (!workspace || workspace_bytes < p.bytes(Q))
+    return fail(CMH_ERR_WORKSPACE, "hamming_topk_few_masked: workspace %zu < %zu bytes", workspace_bytes, p.bytes(Q));
+  const FewArgs a = few_args(p, Q, N, bits, k, idx, dist, workspace);
+  return run_few<HammingRule>("hamming_topk_few_masked", a, p, q_sign, q_nz, r_sign, r_nz, as_stream(stream), allow, found);
 }

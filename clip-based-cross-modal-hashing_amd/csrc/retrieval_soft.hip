@@ -91,6 +91,7 @@ struct SoftRule {
     return d;
   }
   static __device__ __forceinline__ int32_t out(int d) { return d; }
+  static int32_t pad() { return INT32_MAX; }
 };
 
 // ---- the quantiser: one wave per query row, lane l holds entries l and l + 64 ---------------------------------------------------------
@@ -181,4 +182,27 @@ extern "C" int cmh_soft_topk(const uint32_t* q_sign, const uint32_t* q_mag, cons
     return fail(CMH_ERR_WORKSPACE, "soft_topk: workspace %zu < %zu bytes", workspace_bytes, p.bytes(Q));
   const FewArgs a = few_args(p, Q, N, bits, k, idx, wdist, workspace);
   return run_few<SoftRule>("soft_topk", a, p, q_sign, q_mag, r_sign, r_nz, as_stream(stream));
+}
+
+extern "C" size_t cmh_soft_topk_masked_workspace_bytes(int32_t Q, int64_t N, int32_t bits) {
+  return cmh_soft_topk_workspace_bytes(Q, N, bits);      // (the filter adds nothing to the workspace: one plan for both)
+}
+
+extern "C" int cmh_soft_topk_masked(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz,
+                                    const uint64_t* allow, int32_t Q, int64_t N, int32_t bits, int32_t k, int32_t* idx, int32_t* wdist,
+                                    int32_t* found, void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(q_sign && q_mag && r_sign && r_nz && idx && wdist, "soft_topk_masked: null pointer");
+  int rc = check_few_mask("soft_topk_masked", allow, found);
+  if (rc != CMH_OK) return rc;
+  if ((rc = check_soft_topk("soft_topk_masked", Q, N, bits)) != CMH_OK) return rc;
+  CMH_CHECK_ARG(k >= 1 && k <= CMH_SOFT_K_MAX, "soft_topk_masked: k=%d outside [1, %d]", k, CMH_SOFT_K_MAX);
+  CMH_CHECK_ARG(k <= N, "soft_topk_masked: k=%d exceeds N=%lld", k, static_cast<long long>(N));
+  const FewPlan p = soft_plan(Q, N, bits);
+  const uintptr_t row = few_row_bytes(p.W);
+  CMH_CHECK_ARG(reinterpret_cast<uintptr_t>(r_sign) % row == 0 && reinterpret_cast<uintptr_t>(r_nz) % row == 0,
+                "soft_topk_masked: database planes of %d words per row must be aligned to %d bytes", p.W, static_cast<int>(row));
+  if (!workspace || workspace_bytes < p.bytes(Q))
+    return fail(CMH_ERR_WORKSPACE, "soft_topk_masked: workspace %zu < %zu bytes", workspace_bytes, p.bytes(Q));
+  const FewArgs a = few_args(p, Q, N, bits, k, idx, wdist, workspace);
+  return run_few<SoftRule>("soft_topk_masked", a, p, q_sign, q_mag, r_sign, r_nz, as_stream(stream), allow, found);
 }

@@ -47,12 +47,22 @@ code rule) and searched in the saved CodeIndex.  No --codes file is needed.  Per
 
 ranks by the model's real-valued output instead of its sign (CodeIndex.search_soft: the asymmetric distance, which orders the items
 a Hamming ranking leaves tied); the same blocks, the distance column in the soft distance's units.  --soft goes with --text /
---image only."""
+--image only.
+
+    python retrieve.py --text "a dog on a beach" --index db.npz ... --any-label 3,7 --no-label 2 --exclude-ids seen.txt
+
+filters the search: only the items of the index that carry at least one of the classes of --any-label, all of --all-labels and none
+of --no-label (class numbers, comma-separated; the index must hold labels), that are listed in --only-ids FILE and not listed in
+--exclude-ids FILE (one database index per line) are searched; the conditions given combine by AND.  The filters go with --index in
+the neighbour modes (--text / --image, also with --soft, and --codes --index), not with --map, --graded, --radius or --recall.  The
+indices printed are the index's own.  A query with fewer than --k admitted items prints only those it found."""
 import argparse
 import sys
 
 DIRECTIONS = {"i2t": ("q_img", "r_txt"), "t2i": ("q_txt", "r_img"), "i2i": ("q_img", "r_img"), "t2t": ("q_txt", "r_txt")}
 TIES = ("index", "optimistic", "pessimistic", "expected")
+LABEL_FILTERS = ("--any-label", "--all-labels", "--no-label")
+FILTERS = LABEL_FILTERS + ("--only-ids", "--exclude-ids")
 
 
 class _Ask(argparse.Action):
@@ -88,8 +98,32 @@ def parse(argv=None):
     p.add_argument("--ks", default=None, metavar="K1,K2,...", help="with --recall: the cut-offs (default 1,5,10)")
     p.add_argument("--ties", choices=TIES, default=None, help="with --recall: the order inside a group of equal distances (default index)")
     p.add_argument("--targets", default=None, metavar="FILE", help="with --recall --index: one line per query, the database indices that belong to it")
+    p.add_argument("--any-label", default=None, metavar="C1,C2,...", help="with --index: only items that carry at least one of these classes")
+    p.add_argument("--all-labels", default=None, metavar="C1,C2,...", help="with --index: only items that carry all of these classes")
+    p.add_argument("--no-label", default=None, metavar="C1,C2,...", help="with --index: only items that carry none of these classes")
+    p.add_argument("--only-ids", default=None, metavar="FILE", help="with --index: only the database indices listed in FILE, one per line")
+    p.add_argument("--exclude-ids", default=None, metavar="FILE", help="with --index: not the database indices listed in FILE, one per line")
     args = p.parse_args(argv)
     args.ask = getattr(args, "ask", None) or []
+    args.filtered = False
+    for flag in FILTERS:
+        value = getattr(args, flag[2:].replace("-", "_"))
+        if value is None:
+            continue
+        args.filtered = True
+        if not args.index:
+            p.error(f"{flag} filters a saved CodeIndex: --index FILE is required")
+        for other, given in (("--map", args.map), ("--graded", args.graded), ("--recall", args.recall), ("--radius", args.radius is not None)):
+            if given:
+                p.error(f"{flag} and {other} exclude each other (a filter goes with the neighbour modes)")
+        if flag in LABEL_FILTERS:
+            try:
+                classes = [int(c) for c in value.split(",")]
+            except ValueError:
+                classes = [-1]
+            if min(classes) < 0:
+                p.error(f"{flag}: comma-separated class numbers >= 0")
+            setattr(args, flag[2:].replace("-", "_"), classes)
     if args.ask:
         if not args.index:
             p.error("--text / --image search a saved CodeIndex: --index FILE is required")
@@ -156,6 +190,32 @@ def read_targets(path, queries, items):
     return torch.tensor([r + [-1] * (G - len(r)) for r in rows], dtype=torch.int64).reshape(queries, G)
 
 
+def read_ids(flag, path, items):
+    """One database index per line (blank lines are skipped) -> a list of integers inside the index."""
+    try:
+        with open(path) as f:
+            ids = [int(line) for line in f.read().split()]
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"{flag} {path}: {e}")
+    if any(not 0 <= i < items for i in ids):
+        raise SystemExit(f"{flag} {path}: an index outside 0..{items - 1}")
+    return ids
+
+
+def item_mask(args, index):
+    """The ItemMask of the filter options over the index; None when none is given."""
+    if not args.filtered:
+        return None
+    if index.labels is None and (args.any_label is not None or args.all_labels is not None or args.no_label is not None):
+        raise SystemExit(f"--index {args.index} holds no labels: --any-label / --all-labels / --no-label cannot filter it")
+    for flag, classes in (("--any-label", args.any_label), ("--all-labels", args.all_labels), ("--no-label", args.no_label)):
+        if classes is not None and max(classes) >= index.classes:
+            raise SystemExit(f"{flag}: the index holds classes 0..{index.classes - 1}")
+    return index.mask(any_of=args.any_label, all_of=args.all_labels, none_of=args.no_label,
+                      ids=None if args.only_ids is None else read_ids("--only-ids", args.only_ids, index.size),
+                      exclude_ids=None if args.exclude_ids is None else read_ids("--exclude-ids", args.exclude_ids, index.size))
+
+
 def recall(args, m, q_key, r_key, lo, hi):
     import torch
 
@@ -204,11 +264,13 @@ def ask(args):
     for kind, _ in args.ask:                                       # back into the order of the command line
         rows.append(codes[kind][at[kind]])
         at[kind] += 1
-    found = index.search_soft(torch.stack(rows), k)[:2] if args.soft else index.search(torch.stack(rows), k)
-    idx, dist = (t.cpu().numpy() for t in found)
+    mask = item_mask(args, index)
+    got = index.search_soft(torch.stack(rows), k, mask=mask) if args.soft else index.search(torch.stack(rows), k, mask=mask)
+    idx, dist = (t.cpu().numpy() for t in got[:2])
+    count = [k] * len(rows) if mask is None else got[3].cpu().tolist()      # a filtered row holds only what the filter admits
     for i, (kind, value) in enumerate(args.ask):
         print(f"query {i} {kind}: {value}")
-        for j in range(k):
+        for j in range(count[i]):
             print(f"{j + 1} {idx[i, j]} {dist[i, j]:g}")
     return 0
 
@@ -252,9 +314,16 @@ def main(argv=None):
             print(" ".join([str(lo + i)] + cols))
         return 0
     args.k = 10 if args.k is None else args.k
-    out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]
+    mask = item_mask(args, index)
+    count = [args.k] * (hi - lo)
+    if mask is None:
+        out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]
+    else:
+        idx, dist, rel, found = index.search(queries, args.k, labels, mask=mask)
+        out = [t.cpu().numpy() for t in (idx, dist) + (() if rel is None else (rel,))]
+        count = found.cpu().tolist()                               # a filtered row holds only what the filter admits
     for i in range(hi - lo):
-        cols = [f"{out[0][i, j]}:{out[1][i, j]:g}" + (f":{out[2][i, j]}" if len(out) == 3 else "") for j in range(args.k)]
+        cols = [f"{out[0][i, j]}:{out[1][i, j]:g}" + (f":{out[2][i, j]}" if len(out) == 3 else "") for j in range(count[i])]
         print(lo + i, " ".join(cols))
     return 0
 

@@ -35,6 +35,16 @@ packed planes: wdist = sum |w_i| - sum w_i r_i (an exact integer), dist = wdist 
 the quantised query u~, ties by ascending database index.  One cmh_soft_topk (csrc/retrieval_soft.hip) per block of 64 queries
 over the whole database, whatever its size; codes up to 128 bit and k <= 4096, and no other route computes this distance.
 
+Filtered search.  hamming_topk / soft_topk / CodeIndex.search / CodeIndex.search_soft take mask=ItemMask: the nearest items AMONG
+THOSE the mask admits (items that carry a label, that are not in a deny list, an id range ...), with database indices, and without
+a packed copy of the admitted rows.  An ItemMask is one bit per database item (int64 words, bit j % 64 of word j / 64); it is made
+from booleans, id lists or label conditions (ItemMask.from_*, CodeIndex.mask) and combined with & | ~.  A masked search always
+takes the few-query kernels (cmh_hamming_topk_few_masked / cmh_soft_topk_masked: one 64-bit word per 64 items in the walk), in
+blocks of 64 queries, and returns one more element, found int32 [Q] = min(k, admitted items): the columns at and behind found[q]
+are pads (idx = -1, dist = +inf, rel = 0, wdist = 2^31 - 1).  k is checked against the database, not against the admitted count
+(that lives on the GPU; nothing synchronises).  Codes up to 128 bit and k <= 4096; the tiles route (shards, grades, histograms)
+takes no mask.
+
 Size.  The other native entry points take N <= 524 287 database items and Q <= 65 535 queries per call.  Every function here takes any
 database up to 2^31 - 1 items and any number of queries: the packed planes are row-major, so the database is cut into SHARDS of
 `shard_items` rows (views, packed once), every shard is searched, and the per-shard lists are folded together in ascending shard
@@ -131,6 +141,149 @@ def _plan(what, qp, rp, shard_items):
     if Q < 1 or n < 1:
         raise N.NativeError(f"{what}: Q={Q} N={n}")
     return Q, n, _cuts(Q, N.QUERIES_MAX), _cuts(n, step)
+
+
+def _tail(n):
+    """The bits of the last mask word that belong to items: all 64 when n is a multiple of 64."""
+    r = int(n) % 64
+    return -1 if r == 0 else (1 << r) - 1
+
+
+class ItemMask:
+    """One bit per database item: words int64 [ceil(n / 64)], bit j % 64 of word j / 64 set = item j is admitted; n = the items.
+    What the constructors and the operators return has zero bits behind n.  from_bool, to_bool, count and & | ~ are plain torch on
+    whatever device the words live; from_ids and from_labels run on the GPU (cmh_mask_from_ids / cmh_mask_from_labels)."""
+
+    def __init__(self, words, n):
+        n = int(n)
+        if n < 1 or n > ITEMS_MAX:
+            raise N.NativeError(f"ItemMask: n={n} outside [1, {ITEMS_MAX}]")
+        if words.dtype != torch.int64 or words.dim() != 1 or words.numel() != N.mask_words(n):
+            raise N.NativeError(f"ItemMask: words are int64 [{N.mask_words(n)}] for n={n}, not {words.dtype} {tuple(words.shape)}")
+        self.words, self.n = words.contiguous(), n
+
+    @classmethod
+    def all(cls, n, device=None):
+        """Every item admitted."""
+        words = torch.full((N.mask_words(n),), -1, dtype=torch.int64, device=device)
+        words[-1] &= _tail(n)
+        return cls(words, n)
+
+    @classmethod
+    def from_bool(cls, t):
+        """t: [n] booleans (anything whose nonzero entries mean admitted), on any device."""
+        t = torch.as_tensor(t)
+        if t.dim() != 1 or t.numel() < 1:
+            raise N.NativeError(f"ItemMask.from_bool: a tensor [n >= 1], not {tuple(t.shape)}")
+        n = t.numel()
+        bits = torch.zeros(N.mask_words(n) * 64, dtype=torch.int64, device=t.device)
+        bits[:n] = (t != 0).to(torch.int64)
+        shifts = torch.arange(64, dtype=torch.int64, device=t.device)
+        return cls((bits.view(-1, 64) << shifts).sum(1), n)      # (distinct bits: the sum is their OR; bit 63 is the sign bit)
+
+    @classmethod
+    def from_ids(cls, n, ids, keep=True, device=None):
+        """keep=True: an allow list (only `ids` admitted); keep=False: a deny list (everything but `ids`).  Duplicates are legal; an
+        id outside [0, n) raises."""
+        ids = torch.as_tensor(ids)
+        if ids.numel() == 0:
+            ids = ids.to(torch.int64)                              # (an empty list arrives as float32)
+        if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() > 1:
+            raise N.NativeError(f"ItemMask.from_ids: ids are integers [M], not {ids.dtype} {tuple(ids.shape)}")
+        dev = _dev(ids) if device is None else torch.device(device)
+        ids = ids.reshape(-1).to(dev)
+        ids = torch.where((ids < 0) | (ids >= int(n)), torch.full_like(ids, -1), ids)      # (the cast to int32 must not fold a large id into range)
+        mask = cls.all(n, dev) if not keep else cls(torch.zeros(N.mask_words(n), dtype=torch.int64, device=dev), n)
+        N.mask_from_ids(mask.words, ids.to(torch.int32).contiguous(), n, 1 if keep else 0)      # raises on an id outside [0, n)
+        return mask
+
+    @classmethod
+    def from_labels(cls, labels, any_of=None, all_of=None, none_of=None, classes=None):
+        """labels: multi-hot [n, C] (any dtype but int32) or packed int32 [n, ceil(classes / 32)] (pack_labels; classes = 32 per word
+        unless given).  any_of / all_of / none_of: class indices; the item carries at least one of / all of / none of them.  The
+        conditions given are ANDed; none given admits everything."""
+        if labels is None or labels.dim() != 2 or labels.shape[0] < 1:
+            raise N.NativeError("ItemMask.from_labels: labels [n >= 1, C] (multi-hot) or packed int32 [n, LW]")
+        dev = _dev(labels)
+        if labels.dtype == torch.int32:
+            lab = labels.to(dev).contiguous()
+            classes = 32 * lab.shape[1] if classes is None else int(classes)
+        else:
+            lab, classes = _labels(labels, dev), labels.shape[1]
+        n, mask = lab.shape[0], None
+        for mode, wanted in ((N.MASK_ANY, any_of), (N.MASK_ALL, all_of), (N.MASK_NONE, none_of)):
+            if wanted is None:
+                continue
+            c = torch.as_tensor(wanted, dtype=torch.int64).reshape(-1)
+            if c.numel() and (int(c.min()) < 0 or int(c.max()) >= classes):
+                raise N.NativeError(f"ItemMask.from_labels: a class outside [0, {classes})")
+            hot = torch.zeros(1, classes, dtype=torch.float32)
+            hot[0, c] = 1.0
+            one = cls(N.mask_from_labels(lab, _labels(hot, dev)[0].contiguous(), mode, classes), n)
+            mask = one if mask is None else mask & one
+        return cls.all(n, dev) if mask is None else mask
+
+    def to(self, device):
+        return ItemMask(self.words.to(device), self.n)
+
+    def to_bool(self):
+        """-> bool [n] on the words' device."""
+        shifts = torch.arange(64, dtype=torch.int64, device=self.words.device)
+        return (((self.words[:, None] >> shifts) & 1) != 0).reshape(-1)[:self.n]
+
+    def count(self):
+        """The number of admitted items (a Python int: one read from the device)."""
+        return int(self.to_bool().sum())
+
+    def _same(self, other):
+        if not isinstance(other, ItemMask) or other.n != self.n:
+            raise N.NativeError(f"ItemMask: the operands cover {self.n} and {getattr(other, 'n', other)!r} items")
+        return other.words.to(self.words.device)
+
+    def __and__(self, other):
+        return ItemMask(self.words & self._same(other), self.n)
+
+    def __or__(self, other):
+        return ItemMask(self.words | self._same(other), self.n)
+
+    def __invert__(self):
+        words = ~self.words
+        words[-1] &= _tail(self.n)
+        return ItemMask(words, self.n)
+
+
+def _check_mask(what, mask, n, bits, k, shard_items=None, graded=False, want_counts=False):
+    """What a masked search refuses, by name, before anything touches the GPU: the routes that take no mask and the limits of the
+    kernels that do."""
+    if not isinstance(mask, ItemMask):
+        raise N.NativeError(f"{what}: mask= takes an ItemMask, not {type(mask).__name__}")
+    for name, given in (("graded=True", graded), ("want_counts", want_counts), ("shard_items", shard_items is not None)):
+        if given:
+            raise N.NativeError(f"{what}: {name} and mask= exclude each other (the tiles route takes no mask)")
+    if mask.n != n:
+        raise N.NativeError(f"{what}: the mask covers {mask.n} items, the database holds {n}")
+    if bits > N.FEW_BITS_MAX:
+        raise N.NativeError(f"{what}: bits={bits} exceeds {N.FEW_BITS_MAX}, the limit of a masked search")
+    if int(k) > N.FEW_K_MAX:
+        raise N.NativeError(f"{what}: k={int(k)} exceeds {N.FEW_K_MAX}, the limit of a masked search")
+    if not 1 <= int(k) <= n:
+        raise N.NativeError(f"{what}: k={int(k)} outside [1, N={n}]")
+
+
+def _masked_search(what, qp, rp, bits, k, ql, rl, mask):
+    """The masked few-query kernel over blocks of FEW_Q_MAX queries -> (idx, dist, rel, found); rel = the hit flags from the gathered
+    label words as on the unmasked few route (None without labels), 0 in the pad columns."""
+    Q, n = qp[0].shape[0], rp[0].shape[0]
+    _check_mask(what, mask, n, bits, k)
+    N.check_retrieval_operands(what, qp, rp, bits, ql, rl)
+    allow = mask.words.to(rp[0].device)
+    parts = [N.hamming_topk_few_masked(_rows(qp, cut, Q), rp, allow, bits, int(k)) for cut in _cuts(Q, N.FEW_Q_MAX)]
+    idx, dist, found = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+    rel = None
+    if ql is not None:
+        hit = ((rl[idx.clamp(min=0).long()] & ql[:, None, :]) != 0).any(-1)
+        rel = (hit & (idx >= 0)).to(torch.uint8)
+    return idx, dist, rel, found
 
 
 def _few_route(Q, k, bits, shard_items, graded, want_counts):
@@ -322,22 +475,31 @@ def hamming_range(qB, rB, radius, query_L=None, retrieval_L=None, shard_items=No
     return (off, idx, dist) if rel is None else (off, idx, dist, rel)
 
 
-def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None):
-    """-> (idx int32 [Q, k], dist f32 [Q, k][, rel uint8 [Q, k] with labels]): the k nearest database codes of every query."""
+def hamming_topk(qB, rB, k, query_L=None, retrieval_L=None, shard_items=None, mask=None):
+    """-> (idx int32 [Q, k], dist f32 [Q, k][, rel uint8 [Q, k] with labels]): the k nearest database codes of every query.
+    mask=ItemMask: among the items it admits -> (idx, dist, rel or None, found int32 [Q]); pads idx = -1, dist = +inf, rel = 0."""
     if (query_L is None) != (retrieval_L is None):
         raise N.NativeError("hamming_topk: labels on one side only")
+    if mask is not None:
+        _check_mask("hamming_topk", mask, rB.shape[0], rB.shape[1], k, shard_items)
+        dev = _dev(qB, rB)
+        return _masked_search("hamming_topk", _codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev),
+                              _labels(retrieval_L, dev), mask)
     dev = _dev(qB, rB)
     idx, dist, rel, _ = _search("hamming_topk", _codes(qB, dev), _codes(rB, dev), rB.shape[1], k, _labels(query_L, dev),
                                 _labels(retrieval_L, dev), shard_items)
     return (idx, dist) if rel is None else (idx, dist, rel)
 
 
-def _soft_search(what, u, rp, bits, k):
+def _soft_search(what, u, rp, bits, k, mask=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k], wdist int32 [Q, k]) of soft queries u f32 [Q, bits] against packed planes: blocks of
-    SOFT_Q_MAX queries, one cmh_soft_topk each over the whole database."""
+    SOFT_Q_MAX queries, one cmh_soft_topk each over the whole database.  mask=ItemMask: cmh_soft_topk_masked, and found int32 [Q]
+    as a fourth element; the pad columns hold idx = -1, dist = +inf, wdist = 2^31 - 1."""
     if u.dim() < 2:
         u = u.unsqueeze(0)
     n, k = rp[0].shape[0], int(k)
+    if mask is not None:
+        _check_mask(what, mask, n, bits, k)
     if u.shape[1] != bits:
         raise N.NativeError(f"{what}: {u.shape[1]}-entry soft queries for codes of {bits} bits")
     if bits > N.SOFT_BITS_MAX:
@@ -349,17 +511,26 @@ def _soft_search(what, u, rp, bits, k):
     if u.shape[0] < 1 or n > ITEMS_MAX:
         raise N.NativeError(f"{what}: Q={u.shape[0]} N={n}")
     qs, qm, _, scale = N.soft_query_planes(u.to(rp[0].device).float())
+    unit = scale / torch.full_like(scale, 30.0)      # (tensor / tensor: one IEEE division; by a Python number the GPU multiplies by 1 / 30)
+    if mask is not None:
+        allow = mask.words.to(rp[0].device)
+        parts = [N.soft_topk_masked((qs[a:b], qm[a:b]), rp, allow, bits, k) for a, b in _cuts(u.shape[0], N.SOFT_Q_MAX)]
+        idx, wdist, found = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+        dist = wdist.float() * unit[:, None]
+        return idx, torch.where(idx >= 0, dist, torch.full_like(dist, float("inf"))), wdist, found
     parts = [N.soft_topk((qs[a:b], qm[a:b]), rp, bits, k) for a, b in _cuts(u.shape[0], N.SOFT_Q_MAX)]
     idx, wdist = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
-    unit = scale / torch.full_like(scale, 30.0)      # (tensor / tensor: one IEEE division; by a Python number the GPU multiplies by 1 / 30)
     return idx, wdist.float() * unit[:, None], wdist
 
 
-def soft_topk(u, rB, k):
+def soft_topk(u, rB, k, mask=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k], wdist int32 [Q, k]): the k nearest database codes rB (f32 in {-1, 0, +1}) of every
-    soft query u (f32 [Q, K], the head's output before its code rule), by (wdist, database index); dist = wdist * (max|u| / 30)."""
+    soft query u (f32 [Q, K], the head's output before its code rule), by (wdist, database index); dist = wdist * (max|u| / 30).
+    mask=ItemMask: among the items it admits -> (idx, dist, wdist, found int32 [Q])."""
+    if mask is not None:
+        _check_mask("soft_topk", mask, rB.shape[0], rB.shape[-1], k)
     dev = _dev(u, rB)
-    return _soft_search("soft_topk", u, _codes(rB, dev), rB.shape[-1], k)
+    return _soft_search("soft_topk", u, _codes(rB, dev), rB.shape[-1], k, mask)
 
 
 def _classes(what, query_L, retrieval_L):
@@ -628,7 +799,7 @@ def recall_at_k(qB, rB, targets=None, ks=RECALL_KS, ties="index", shard_items=No
 
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
-    search_soft(u, k) -> soft_topk's;
+    search_soft(u, k) -> soft_topk's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
@@ -746,11 +917,30 @@ class CodeIndex:
         mp = mp.cpu()
         return (mp, ap) if return_ap else mp
 
-    def search(self, query_codes, k, query_labels=None, graded=False):
+    def mask(self, any_of=None, all_of=None, none_of=None, ids=None, exclude_ids=None):
+        """An ItemMask over the index's items as they are NOW (after add() it no longer fits and is refused): the items that carry at
+        least one class of any_of, all of all_of and none of none_of (the index must hold labels), that are among `ids` and not
+        among `exclude_ids`.  The conditions given are ANDed; none given admits everything."""
+        if (any_of is not None or all_of is not None or none_of is not None) and self.labels is None:
+            raise N.NativeError("CodeIndex.mask: a label condition (any_of / all_of / none_of) on an index without labels")
+        m = ItemMask.all(self.size, self.device) if self.labels is None else \
+            ItemMask.from_labels(self.labels, any_of, all_of, none_of, classes=self.classes)
+        if ids is not None:
+            m = m & ItemMask.from_ids(self.size, ids, keep=True, device=self.device)
+        if exclude_ids is not None:
+            m = m & ItemMask.from_ids(self.size, exclude_ids, keep=False, device=self.device)
+        return m
+
+    def search(self, query_codes, k, query_labels=None, graded=False, mask=None):
+        """mask=ItemMask (CodeIndex.mask): among the items it admits -> (idx, dist, rel or None, found)."""
         if query_labels is not None and self.labels is None:
             raise N.NativeError("CodeIndex.search: query labels given, but the index has none")
+        if mask is not None:
+            _check_mask("CodeIndex.search", mask, self.size, self.bits, k, self.shard_items, graded)
         ql = _labels(query_labels, self.device)
         rl = self.labels if ql is not None else None
+        if mask is not None:
+            return _masked_search("CodeIndex.search", _codes(query_codes, self.device), self.planes, self.bits, k, ql, rl, mask)
         if graded:
             if ql is None:
                 raise N.NativeError("CodeIndex.search: graded=True needs query labels and an index with labels")
@@ -760,12 +950,12 @@ class CodeIndex:
                                     self.shard_items)
         return (idx, dist) if rel is None else (idx, dist, rel)
 
-    def search_soft(self, u, k):
+    def search_soft(self, u, k, mask=None):
         """soft_topk of the soft queries u (f32 [Q, bits], QueryEncoder.encode_*(..., soft=True)) against the index: (idx, dist,
-        wdist).  Any number of queries; bits <= 128 and k <= 4096."""
+        wdist).  Any number of queries; bits <= 128 and k <= 4096.  mask=ItemMask: (idx, dist, wdist, found)."""
         if u.shape[-1] != self.bits:
             raise N.NativeError(f"CodeIndex.search_soft: {u.shape[-1]}-entry soft queries for an index of {self.bits} bits")
-        return _soft_search("CodeIndex.search_soft", u, self.planes, self.bits, k)
+        return _soft_search("CodeIndex.search_soft", u, self.planes, self.bits, k, mask)
 
     def range_search(self, query_codes, radius, query_labels=None, max_hits=None):
         """hamming_range of the queries against the index: (offsets, idx, dist[, rel with query labels])."""

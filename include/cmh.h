@@ -605,6 +605,44 @@ size_t cmh_soft_topk_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
 int cmh_soft_topk(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz, int32_t Q, int64_t N,
                   int32_t bits, int32_t k, int32_t* idx, int32_t* wdist, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Filtered search: the two searches above over only the items an ALLOW-MASK admits (the nearest items among those that carry a
+ * label, are not in a deny list, lie in an id range ...), without a packed copy of the admitted rows.
+ *   allow u64 [ceil(N / 64)], 8-byte aligned, on the GPU: bit j % 64 of word j / 64 set = database item j is admitted.  Bits at
+ *   and behind N in the last word may hold anything: they are never read as admitted.
+ * cmh_hamming_topk_few_masked / cmh_soft_topk_masked: operands, limits and refusals of cmh_hamming_topk_few / cmh_soft_topk.  k is
+ * checked against N, not against the number A of admitted items (it lives on the device; the call does not synchronise):
+ *   row q of idx / dist (wdist) holds the first min(k, A) ADMITTED items in ascending (distance, database index); the indices are
+ *   database indices, not positions in the subset: bit for bit what the unmasked call gives on a database of the admitted rows
+ *   alone, mapped back.  found i32 [Q] = min(k, A).  The columns at and behind found[q] hold idx = -1 and dist = +inf (wdist =
+ *   INT32_MAX).
+ * Every element of idx, dist and found is written exactly once by some kernel of the call, without atomics: two calls give equal
+ * bytes, on any stream.  -1 before any launch: a null or misaligned allow, a null found, and everything the unmasked call refuses;
+ * -2: a workspace below cmh_topk_few_masked_workspace_bytes / cmh_soft_topk_masked_workspace_bytes (0 outside the limits; the
+ * unmasked calls' sizes). */
+size_t cmh_topk_few_masked_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_hamming_topk_few_masked(const uint32_t* q_sign, const uint32_t* q_nz, const uint32_t* r_sign, const uint32_t* r_nz,
+                                const uint64_t* allow, int32_t Q, int64_t N, int32_t bits, int32_t k, int32_t* idx, float* dist,
+                                int32_t* found, void* workspace, size_t workspace_bytes, void* stream);
+size_t cmh_soft_topk_masked_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
+int cmh_soft_topk_masked(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz,
+                         const uint64_t* allow, int32_t Q, int64_t N, int32_t bits, int32_t k, int32_t* idx, int32_t* wdist,
+                         int32_t* found, void* workspace, size_t workspace_bytes, void* stream);
+/* Allow-masks made on the GPU (csrc/retrieval_mask.hip).
+ * cmh_mask_from_labels: r_label u32 [N, LW] (cmh_pack_labels, LW = ceil(classes / 32)), need u32 [LW] on the GPU -> allow.  Item j is
+ * admitted under mode CMH_MASK_ANY iff (label & need) != 0, CMH_MASK_ALL iff (label & need) == need, CMH_MASK_NONE iff (label &
+ * need) == 0 (an empty need: any admits nothing, all and none admit everything).  Every word of allow is written once, the bits at
+ * and behind N zero; no atomics.  1 <= N <= 2^31 - 1, classes >= 1.
+ * cmh_mask_from_ids: sets (value 1) or clears (value 0) the bits of the items ids i32 [M] in an EXISTING mask; duplicates are
+ * legal, M = 0 does nothing.  An id outside [0, N) changes nothing and sets *bad (i32 on the GPU, the caller zeroes it).  The bits
+ * go in by atomic OR / AND on the mask words: the result does not depend on the order.
+ * -1 before any launch: null operands, a misaligned allow, a mode or value that is none of the above, sizes outside the limits. */
+#define CMH_MASK_ANY 0
+#define CMH_MASK_ALL 1
+#define CMH_MASK_NONE 2
+int cmh_mask_from_labels(const uint32_t* r_label, const uint32_t* need, int32_t mode, int64_t N, int32_t classes, uint64_t* allow,
+                         void* stream);
+int cmh_mask_from_ids(const int32_t* ids, int64_t M, int64_t N, int32_t value, uint64_t* allow, int32_t* bad, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */

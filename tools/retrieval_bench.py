@@ -72,7 +72,16 @@ Same rules (warm-up, legs alternating, device events around regions of --reps ca
 `soft_planes` times the quantiser with its flag read back).  Where soft and Hamming must agree (all |w| = 15) the lists are compared on the timed
 database.  Reported per (shape, Q, k): both times and soft / few, and both workspaces.  CMH_SOFT_GROUP=g in the environment
 pins g queries per workgroup, CMH_SOFT_MIN_CHUNK=c the fewest items of a chunk, in place of the plan's choices, for an A/B of the
-same line.  ONE JSON line."""
+same line.  ONE JSON line.
+
+--masked runs the filtered-search legs instead: cmh_hamming_topk_few_masked (the allow-mask in the walk: one 64-bit word per 64
+items) on both databases of --few at Q = 1, 64 and k = 10, 1000 under random masks that admit a share 1.0 / 0.5 / 0.1 / 0.01 of the
+items, against (b) `few`, the unmasked cmh_hamming_topk_few on the same operands (at share 1.0 the difference is the price of the
+filter), (c) `gather`, the only route there was: the admitted rows gathered into a second packed database (mask -> booleans ->
+nonzero, which reads the count back; two row gathers), the unmasked search of that with k' = min(k, admitted), and the indices
+mapped back, with its allocations; and `gather_cached`, (c) on a subset gathered BEFORE the timed regions: what (c) costs while the
+filter does not change.  Same rules (warm-up, legs alternating, device events around regions of --reps calls, median [min - max],
+packed resident operands); the lists of (a) and (c) are compared on the timed inputs.  ONE JSON line."""
 import argparse
 import json
 import os
@@ -563,6 +572,72 @@ def soft_legs(args):
         raise SystemExit("the soft search disagrees with the few-query search on queries whose weights are all 15")
 
 
+MASKED_SHARES = (1.0, 0.5, 0.1, 0.01)
+
+
+def masked_legs(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+    line = {"tool": "retrieval_bench", "leg": "masked", "regions": REGIONS, "reps": args.reps, "outputs_equal": True, "shapes": {}}
+    for name, (n, K) in FEW.items():
+        g = torch.Generator(device=dev).manual_seed(1)
+        rB = torch.sign(torch.randn(n, K, generator=g, device=dev) + 1e-3)
+        t = torch.randint(0, n, (max(SOFT_QS),), generator=g, device=dev)
+        flip = torch.rand(max(SOFT_QS), K, generator=g, device=dev) < 0.1
+        qp_all, rp = N.pack_codes(torch.where(flip, -rB[t], rB[t])), N.pack_codes(rB)
+        draw = torch.rand(n, generator=g, device=dev)
+        del rB, flip
+        shape = {"N": n, "bits": K, "ms": {}}
+        for Q in SOFT_QS:
+            qp = tuple(x[:Q].contiguous() for x in qp_all)
+            for k in FEW_KS:
+                cell = {}
+                for share in MASKED_SHARES:
+                    mask = R.ItemMask.from_bool(draw < share)
+                    allow = mask.words
+
+                    def gathered(sub=None):
+                        keep, rows = sub if sub is not None else (None, None)
+                        if sub is None:
+                            keep = mask.to_bool().nonzero().flatten()
+                            rows = tuple(x.index_select(0, keep) for x in rp)
+                        kk = min(k, keep.numel())
+                        idx, dist = N.hamming_topk_few(qp, rows, K, kk)
+                        return keep[idx.long()].to(torch.int32), dist
+
+                    keep = mask.to_bool().nonzero().flatten()
+                    cached = (keep, tuple(x.index_select(0, keep) for x in rp))
+                    legs = {"masked": (args.reps, lambda: N.hamming_topk_few_masked(qp, rp, allow, K, k)),
+                            "few": (args.reps, lambda: N.hamming_topk_few(qp, rp, K, k)),
+                            "gather": (args.reps, gathered),
+                            "gather_cached": (args.reps, lambda: gathered(cached))}
+                    outs = {leg: fn() for leg, (_, fn) in legs.items()}      # warm-up, and the outputs of both routes on the timed inputs
+                    w = outs["gather"][0].shape[1]
+                    same = bool(torch.equal(outs["masked"][0][:, :w], outs["gather"][0])) and bool(torch.equal(outs["masked"][1][:, :w], outs["gather"][1])) \
+                        and outs["masked"][2].tolist() == [w] * Q and bool((outs["masked"][0][:, w:] == -1).all())
+                    if share == 1.0:
+                        same = same and bool(torch.equal(outs["masked"][0], outs["few"][0])) and bool(torch.equal(outs["masked"][1], outs["few"][1]))
+                    line["outputs_equal"] = line["outputs_equal"] and same
+                    del outs
+                    torch.cuda.synchronize()
+                    ms = _timed(legs, REGIONS)
+                    ms["admitted"] = int(keep.numel())
+                    ms["masked_over_few"] = round(ms["masked"]["median"] / ms["few"]["median"], 3)
+                    ms["gather_over_masked"] = round(ms["gather"]["median"] / ms["masked"]["median"], 2)
+                    ms["gather_cached_over_masked"] = round(ms["gather_cached"]["median"] / ms["masked"]["median"], 2)
+                    ms["outputs_equal"] = same
+                    cell[f"share{share}"] = ms
+                    del cached, keep
+                shape["ms"][f"Q{Q}_k{k}"] = cell
+        line["shapes"][name] = shape
+        del qp_all, rp, draw
+    _emit(args, line)
+    if not line["outputs_equal"]:
+        raise SystemExit("the masked search disagrees with the search of the gathered rows")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
@@ -575,6 +650,7 @@ def main():
     ap.add_argument("--rank", action="store_true", help="run the target-rank legs (see above) instead of the others")
     ap.add_argument("--few", action="store_true", help="run the few-query legs (see above) instead of the others")
     ap.add_argument("--soft", action="store_true", help="run the soft-query legs (see above) instead of the others")
+    ap.add_argument("--masked", action="store_true", help="run the filtered-search legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
     import cmh_native as N
@@ -592,6 +668,8 @@ def main():
         return few_legs(args)
     if args.soft:
         return soft_legs(args)
+    if args.masked:
+        return masked_legs(args)
     dev = torch.device("cuda:0")
     for name in args.shapes:
         Q, n, K, C = SHAPES[name]
