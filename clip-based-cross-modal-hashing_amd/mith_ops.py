@@ -4,21 +4,15 @@ import ctypes as C
 import torch
 
 import cmh_native as N
+from model.base.model import _gemm_w
 
 EPI_BIAS, EPI_QUICKGELU, EPI_RESIDUAL, EPI_OUT_BF16, EPI_GELU, EPI_RELU = 1, 2, 4, 8, 16, 32
 
 
-_bf16_weights = {}
-
-
 def weight_bf16(w):
-    """bf16 copy of a GEMM weight, re-cast when the parameter changes (data_ptr / _version)"""
-    key = id(w)
-    hit = _bf16_weights.get(key)
-    if hit is None or hit[0] != (w.data_ptr(), w._version):
-        hit = ((w.data_ptr(), w._version), N.cast_bf16(w.detach()))
-        _bf16_weights[key] = hit
-    return hit[1]
+    """bf16 copy of a GEMM weight: the one the towers use, kept on the parameter itself (model/base/model.py::_gemm_w) - re-cast
+    when the parameter changes, rewritten in place by the fused BertAdam step, gone with the parameter"""
+    return _gemm_w(w, N.BF16, [])
 
 
 def gemm(x, w, bias=None, residual=None, act=None, dtype=N.F32, out_bf16=False):
@@ -49,33 +43,22 @@ def gemm(x, w, bias=None, residual=None, act=None, dtype=N.F32, out_bf16=False):
 
 
 def vit_encode_tokens(clip, image):
-    image = N.f32c(image)
-    N.require_gpu(image)
-    s = clip._vit_struct()
-    B = image.shape[0]
-    T = (s.resolution // s.patch) ** 2 + 1
-    out = torch.empty(B * T, s.embed_dim, dtype=torch.float32, device=image.device)
-    ws = N.workspace(N.lib().cmh_vit_workspace_bytes(C.byref(s), B), image.device, f"vit@{N.stream_ptr(image.device)}")      # one scratch per stream: the eval loops run batches on alternating streams
-    N.check(N.lib().cmh_vit_encode_tokens(C.byref(s), N.ptr(image), B, N.ptr(out), N.ptr(ws), ws.numel(),
-                                          N.stream_ptr(image.device)), "cmh_vit_encode_tokens")
-    return out.view(B, T, s.embed_dim)
+    c, = clip._open("vit_encode_tokens", images=[image], tokens=True)
+    N.check(N.lib().cmh_vit_encode_tokens(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(c.out), N.ptr(c.ws), c.ws.numel(), c.stream),
+            "cmh_vit_encode_tokens")
+    return c.out.view(c.dims[0], -1, c.s.embed_dim)
 
 
 def text_encode_tokens(clip, text, key_padding_mask, padded_unused=False):
     """padded_unused: the caller reads no padded position of the result (MITH: HashingModel masks them) - they are then not computed
     and come back as zeros (cmh_text_encode_tokens_packed)"""
-    N.require_gpu(text)
-    text = text.to(torch.int64).contiguous()
-    s = clip._text_struct()
-    B, L = text.shape
-    out = torch.empty(B * L, s.embed_dim, dtype=torch.float32, device=text.device)
-    rows = torch.empty(B, dtype=torch.int32, device=text.device)
+    c, = clip._open("text_encode_tokens", texts=[text], tokens=True)
+    rows = torch.empty(c.dims[0], dtype=torch.int32, device=c.out.device)
     kpm = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()
-    ws = N.workspace(N.lib().cmh_text_workspace_bytes(C.byref(s), B, L), text.device, f"text@{N.stream_ptr(text.device)}")
-    fn = N.lib().cmh_text_encode_tokens_packed if padded_unused and kpm is not None else N.lib().cmh_text_encode_tokens
-    N.check(fn(C.byref(s), N.ptr(text), B, L, N.ptr(kpm), N.ptr(out), N.ptr(rows), N.ptr(ws), ws.numel(), N.stream_ptr(text.device)),
-            "cmh_text_encode_tokens")
-    return out.view(B, L, s.embed_dim), rows
+    fn = "cmh_text_encode_tokens" + ("_packed" if padded_unused and kpm is not None else "")
+    N.check(getattr(N.lib(), fn)(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(kpm), N.ptr(c.out), N.ptr(rows), N.ptr(c.ws), c.ws.numel(),
+                                 c.stream), fn)
+    return c.out.view(*c.dims, c.s.embed_dim), rows
 
 
 def transformer_blocks(block_array, layers, x, B, T, dtype=N.F32):

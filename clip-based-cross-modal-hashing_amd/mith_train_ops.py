@@ -8,7 +8,7 @@ import torch
 import backward_ops as B
 import cmh_native as N
 import mith_ops as M
-from model.base.train_ops import _BLOCK_FIELDS, block_params
+from model.base.train_ops import _block_grads, blocks_params  # noqa: F401  (blocks_params: the callers' parameter list)
 
 
 class GemmLinear(torch.autograd.Function):
@@ -147,20 +147,13 @@ class BlocksTrain(torch.autograd.Function):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise N.NativeError("training needs contiguous float32 parameters (model.float())")
         grads = [torch.empty_like(p) for p in ctx.params]
-        arr = (N.BlockGrads * layers)()
-        for i in range(layers):
-            for j, f in enumerate(_BLOCK_FIELDS):
-                setattr(arr[i], f, grads[12 * i + j].data_ptr())
+        arr = _block_grads(grads)
         dx = torch.empty_like(dy)
         N.check(N.lib().cmh_blocks_backward(C.cast(ctx.blocks, C.POINTER(N.BlockWeights)), C.cast(arr, C.POINTER(N.BlockGrads)), layers,
                                             dtype, N.ptr(dy), N.ptr(dx), Bn, T, d, N.ptr(ctx.tape), ctx.tape.numel(),
                                             N.stream_ptr(dy.device)), "cmh_blocks_backward")
         ctx.tape = ctx.keep = None
         return (dx, None, None, None, None, None) + tuple(grads)
-
-
-def blocks_params(resblocks):
-    return [p for blk in resblocks for p in block_params(blk)]
 
 
 # ---- loss terms (train/MITH/hash_train.py:103-147) ----------------------------------------------------------------------------

@@ -18,7 +18,9 @@ from torch import nn
 
 import cmh_native as N
 import mith_ops as M
-from model.base.model import CLIP, Transformer, VisionTransformer, _fill_blocks, convert_weights, no_backward  # noqa: F401
+from model.base import train_ops
+from model.base.model import CLIP, Transformer, VisionTransformer, _fill_blocks
+from model.base.model import build_model as build_clip
 from streams import overlapped
 
 MITH_MAX_PATCH_TOKENS = 80     # kLtaMaxL of csrc/mith.hip: the token aggregation keeps a sample's tokens in LDS
@@ -30,24 +32,20 @@ class ViT(VisionTransformer):
 
 class CLIP1(CLIP):
     def encode_image(self, image):
-        from model.base import train_ops as T
-        params = T.vit_params(self.visual)
-        if not self.assume_frozen and T.wants_grad(params):                 # training: tape-keeping forward, token gradients back
-            image = N.f32c(image)
-            s = self._vit_struct()
-            tok = T.VitTrainTokens.apply(self, image, *params).view(image.shape[0], -1, s.embed_dim)
+        if self._wants_tape(train_ops.VIT):                                      # training: tape-keeping forward, token gradients back
+            (image,), _ = self._operands("encode_image", images=[image])
+            tok = train_ops.VitTrainTokens.apply(self, image, *train_ops.VIT.params(self))
+            tok = tok.view(image.shape[0], -1, tok.shape[-1])
         else:
             tok = M.vit_encode_tokens(self, image)                       # [B, T, E]
         return tok[:, 1:].permute(1, 0, 2), None, tok[:, 0]
 
     def encode_text(self, text, key_padding_mask):
-        from model.base import train_ops as T
-        params = T.text_params(self)
-        if not self.assume_frozen and T.wants_grad(params):
-            text = text.to(torch.int64).contiguous()
+        if self._wants_tape(train_ops.TEXT):
+            _, (text,) = self._operands("encode_text", texts=[text])
             kpm = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()
-            tok, rows = T.TextTrainTokens.apply(self, text, kpm, *params)
-            tok = tok.view(text.shape[0], text.shape[1], -1)
+            tok, rows = train_ops.TextTrainTokens.apply(self, text, kpm, *train_ops.TEXT.params(self))
+            tok = tok.view(*text.shape, -1)
         else:
             tok, rows = M.text_encode_tokens(self, text, key_padding_mask,   # [B, L, E]
                                              padded_unused=bool(getattr(self, "padded_tokens_unused", False)))
@@ -58,26 +56,13 @@ class CLIP1(CLIP):
 
 
 def build_model(state_dict: dict):
-    """model/MITH.py:163-204 (same shape inference as model/base/model.py::build_model, CLIP1 instead of CLIP)."""
-    vision_width = state_dict["visual.conv1.weight"].shape[0]
-    vision_layers = len([k for k in state_dict if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
-    vision_patch_size = state_dict["visual.conv1.weight"].shape[-1]
-    grid_size = round((state_dict["visual.positional_embedding"].shape[0] - 1) ** 0.5)
-    if grid_size * grid_size > MITH_MAX_PATCH_TOKENS:
-        raise NotImplementedError(f"MITH's token aggregation (mith_lta) is built for at most {MITH_MAX_PATCH_TOKENS} tokens per sample; "
-                                  f"this checkpoint has {grid_size * grid_size} image patches (ViT-B/32 has 49)")
-    embed_dim = state_dict["text_projection"].shape[1]
-    tw = state_dict["ln_final.weight"].shape[0]
-    layers = len(set(k.split(".")[2] for k in state_dict if k.startswith("transformer.resblocks")))
-    model = CLIP1(embed_dim, vision_patch_size * grid_size, vision_layers, vision_width, vision_patch_size,
-                  state_dict["positional_embedding"].shape[0], state_dict["token_embedding.weight"].shape[0], tw, tw // 64,
-                  layers)
-    for key in ["input_resolution", "context_length", "vocab_size"]:
-        if key in state_dict:
-            del state_dict[key]
-    convert_weights(model)
-    model.load_state_dict(state_dict)
-    return model
+    """model/MITH.py:163-204: model/base/model.py::build_model with CLIP1 and the token aggregation's limit."""
+    def accept(shapes):
+        patches = (shapes["image_resolution"] // shapes["vision_patch_size"]) ** 2
+        if patches > MITH_MAX_PATCH_TOKENS:
+            raise NotImplementedError(f"MITH's token aggregation (mith_lta) is built for at most {MITH_MAX_PATCH_TOKENS} tokens per sample; "
+                                      f"this checkpoint has {patches} image patches (ViT-B/32 has 49)")
+    return build_clip(state_dict, CLIP1, accept)
 
 
 def load_download_clip(clip_path) -> nn.Module:

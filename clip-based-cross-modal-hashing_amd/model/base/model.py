@@ -15,20 +15,23 @@ never touches ATen math: encode_image / encode_text call cmh_vit_encode / cmh_te
 Arithmetic mode (`CLIP.set_gemm_dtype`): "f32" = exact fp32 MFMA, the parity mode for the
 reference's `model.float()` trainers; "bf16" = bf16 MFMA operands with fp32 accumulation,
 LayerNorm/softmax/residual in fp32 (the throughput mode, BASELINE.json configs[1]).
-Backward through the towers is not implemented yet (SURVEY §8f "next" #2): outputs carry a grad_fn
-that raises, so `loss.backward()` fails loudly instead of silently training nothing.
+Training: when gradients are enabled and a tower parameter asks for them, encode_image / encode_text run
+the tape-keeping forward and the native backward (model/base/train_ops.py, which also holds the tables of
+which parameter goes to which struct field).  Outputs of the inference-only calls carry a grad_fn that
+raises, so `loss.backward()` fails loudly instead of silently training nothing.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 from torch import nn
 
 import cmh_native as N
+from model.base import train_ops as T
 
 
 class LayerNorm(nn.LayerNorm):
@@ -98,14 +101,12 @@ def no_backward(out: torch.Tensor, anchor: torch.Tensor) -> torch.Tensor:
 
 
 class _TowerCache:
-    """Device-resident weights in the layout libcmh wants + the ctypes structs that point at them.
-    Rebuilt when any parameter changed (data_ptr/_version) or the arithmetic mode changed."""
+    """Device-resident weights in the layout libcmh wants + the ctypes structs that point at them.  A new entry is made when any
+    parameter changed (data_ptr/_version) or the arithmetic mode changed; a training tape keeps the entry it ran with."""
 
-    def __init__(self):
-        self.key = None
-        self.keep = []          # tensors that must outlive the structs
-        self.struct = None
-        self.blocks = None
+    def __init__(self, key=None, struct=None, blocks=None, keep=()):
+        self.key, self.struct, self.blocks = key, struct, blocks
+        self.keep = keep        # tensors that must outlive the structs
 
 
 def _prep(p: torch.Tensor, keep: list) -> torch.Tensor:
@@ -146,39 +147,30 @@ FP8_HEADROOM = 2.0     # act_scale = FP8_HEADROOM * amax(calibration batch) / 44
 
 
 def _fill_blocks(resblocks, dt: int, keep: list, act_amax=None):
+    """cmh_block_weights array from train_ops.BLOCK_TABLE.  The fp8 mode differs only in how the four GEMM weights are lowered (e4m3
+    bytes + per-channel scales in the `*_cs` field next to each `*_w`) and in the activation scales."""
+    if dt == N.FP8 and act_amax is None and len(resblocks):
+        raise N.NativeError("fp8 mode needs activation scales: call clip.calibrate_fp8(images, texts) first")
     arr = (N.BlockWeights * len(resblocks))()
     for i, blk in enumerate(resblocks):
         b = arr[i]
+        for field, get, is_gemm in T.BLOCK_TABLE:
+            if is_gemm and dt == N.FP8:
+                w, cs = _fp8_w(get(blk), keep)
+                setattr(b, field, w), setattr(b, field[:-1] + "cs", cs)
+            else:
+                setattr(b, field, (_gemm_w(get(blk), dt, keep) if is_gemm else _prep(get(blk), keep)).data_ptr())
         if dt == N.FP8:
-            if act_amax is None:
-                raise N.NativeError("fp8 mode needs activation scales: call clip.calibrate_fp8(images, texts) first")
-            b.in_proj_w, b.in_proj_cs = _fp8_w(blk.attn.in_proj_weight, keep)
-            b.out_proj_w, b.out_proj_cs = _fp8_w(blk.attn.out_proj.weight, keep)
-            b.fc_w, b.fc_cs = _fp8_w(blk.mlp.c_fc.weight, keep)
-            b.proj_w, b.proj_cs = _fp8_w(blk.mlp.c_proj.weight, keep)
             for j in range(4):
                 b.act_scale[j] = max(float(act_amax[i][j]), 1e-6) * FP8_HEADROOM / 448.0
-            for name, src in (("in_proj_b", blk.attn.in_proj_bias), ("out_proj_b", blk.attn.out_proj.bias), ("ln1_w", blk.ln_1.weight),
-                              ("ln1_b", blk.ln_1.bias), ("ln2_w", blk.ln_2.weight), ("ln2_b", blk.ln_2.bias),
-                              ("fc_b", blk.mlp.c_fc.bias), ("proj_b", blk.mlp.c_proj.bias)):
-                setattr(b, name, _prep(src, keep).data_ptr())
-            continue
-        b.in_proj_w = _gemm_w(blk.attn.in_proj_weight, dt, keep).data_ptr()
-        b.in_proj_b = _prep(blk.attn.in_proj_bias, keep).data_ptr()
-        b.out_proj_w = _gemm_w(blk.attn.out_proj.weight, dt, keep).data_ptr()
-        b.out_proj_b = _prep(blk.attn.out_proj.bias, keep).data_ptr()
-        b.ln1_w = _prep(blk.ln_1.weight, keep).data_ptr()
-        b.ln1_b = _prep(blk.ln_1.bias, keep).data_ptr()
-        b.ln2_w = _prep(blk.ln_2.weight, keep).data_ptr()
-        b.ln2_b = _prep(blk.ln_2.bias, keep).data_ptr()
-        b.fc_w = _gemm_w(blk.mlp.c_fc.weight, dt, keep).data_ptr()
-        b.fc_b = _prep(blk.mlp.c_fc.bias, keep).data_ptr()
-        b.proj_w = _gemm_w(blk.mlp.c_proj.weight, dt, keep).data_ptr()
-        b.proj_b = _prep(blk.mlp.c_proj.bias, keep).data_ptr()
     return arr
 
 
-FP8_MAX_IMAGE_TOKENS = 128   # the fp8 mode's e4m3-output attention (csrc/attention.hip) is built for T <= 128 (ViT-B/32: 50)
+# one tower's share of an inference call (CLIP._open): struct, operand (`more`: the further image batches of a two-batch call),
+# (B,) / (B, L), result buffer, scratch, the packed row count's device word or None, stream
+_Call = namedtuple("_Call", "tower s x more dims out ws rows stream")
+
+FP8_MAX_IMAGE_TOKENS = 128  # the fp8 mode's e4m3-output attention (csrc/attention.hip) is built for T <= 128 (ViT-B/32: 50)
 
 _DT = {"f32": N.F32, "fp32": N.F32, "float32": N.F32, "bf16": N.BF16, "bfloat16": N.BF16, "fp8": N.FP8, "e4m3": N.FP8}
 
@@ -206,8 +198,7 @@ class CLIP(nn.Module):
         self.initialize_parameters()
         self._gemm_dtype = _DT[os.environ.get("CMH_GEMM_DTYPE", "f32").lower()]
         self._check_fp8_tokens(self._gemm_dtype)
-        self._vit_cache = _TowerCache()
-        self._txt_cache = _TowerCache()
+        self._tower_cache = {"vit": _TowerCache(), "text": _TowerCache()}
         self.assume_frozen = False     # True: skip the per-call parameter-version scan (pure inference)
         self._fp8_amax = {"vit": None, "text": None}     # [layers, 4] calibration maxima of the four GEMM inputs per block
         self._fp8_amax_key = {"vit": None, "text": None}  # the parameter versions those maxima were measured with
@@ -260,45 +251,37 @@ class CLIP(nn.Module):
             raise N.NativeError(f"the fp8 mode is built for at most {FP8_MAX_IMAGE_TOKENS} image tokens; this checkpoint has {tokens} "
                                 "(ViT-B/16 and larger): use set_gemm_dtype('bf16' | 'f32')")
 
-    def calibrate_fp8(self, image=None, text=None, reset=True):
+    def calibrate_fp8(self, image=None, text=None, reset=True, _versions=None):
         """Calibration pass of the fp8 mode: runs the batch(es) in bf16 mode and records, per block, the largest magnitude of the
         four GEMM inputs (ln_1 output, attention output, ln_2 output, QuickGELU(c_fc) output).  The per-tensor quantisation
         scales are FP8_HEADROOM * amax / 448.  Call again with reset=False to widen the maxima with more batches.
-        Returns the bf16-mode features of the batches it was given."""
+        Returns the bf16-mode features of the batches it was given.  (_versions: the scans an entry point that calibrates on its
+        first batch has made already.)"""
         mode, self._gemm_dtype = self._gemm_dtype, N.BF16
         out = []
         try:
             with torch.no_grad():
-                for tower, x in (("vit", image), ("text", text)):
+                for tower, x in ((T.VIT, image), (T.TEXT, text)):
                     if x is None:
                         continue
-                    s = self._vit_struct() if tower == "vit" else self._text_struct()
-                    dev = x.device
-                    N.require_gpu(x)
-                    prev = self._fp8_amax[tower]
-                    amax = torch.zeros(s.layers * 4, dtype=torch.float32, device=dev)
-                    if prev is not None and not reset:
-                        amax.copy_(torch.as_tensor(prev, dtype=torch.float32).reshape(-1))
-                    B = x.shape[0]
-                    feat = torch.empty(B, s.embed_dim, dtype=torch.float32, device=dev)
-                    if tower == "vit":
-                        x = N.f32c(x)
-                        ws = N.workspace(N.lib().cmh_vit_workspace_bytes(C.byref(s), B), dev, f"vit@{N.stream_ptr(dev)}")
-                        N.check(N.lib().cmh_vit_calibrate_fp8(C.byref(s), N.ptr(x), B, N.ptr(feat), N.ptr(amax), N.ptr(ws), ws.numel(),
-                                                              N.stream_ptr(dev)), "cmh_vit_calibrate_fp8")
-                    else:
-                        x = x.to(torch.int64).contiguous()
-                        L = x.shape[1]
-                        ws = N.workspace(N.lib().cmh_text_workspace_bytes(C.byref(s), B, L), dev, f"text@{N.stream_ptr(dev)}")
-                        N.check(N.lib().cmh_text_calibrate_fp8(C.byref(s), N.ptr(x), B, L, N.ptr(feat), N.ptr(amax), N.ptr(ws), ws.numel(),
-                                                               N.stream_ptr(dev)), "cmh_text_calibrate_fp8")
-                    vals = amax.cpu().reshape(s.layers, 4)
+                    name, scan = tower.name, (_versions or {}).get(tower.name)
+                    if scan is None or scan == "frozen":
+                        scan = self._scan(tower)                 # the maxima belong to these very weights, frozen or not
+                    c, = self._open("calibrate_fp8", **{"texts" if tower.text else "images": [x]},
+                                    versions={name: "frozen" if self.assume_frozen else scan})
+                    amax = torch.zeros(c.s.layers * 4, dtype=torch.float32, device=x.device)
+                    if self._fp8_amax[name] is not None and not reset:
+                        amax.copy_(torch.as_tensor(self._fp8_amax[name], dtype=torch.float32).reshape(-1))
+                    fn = f"cmh_{name}_calibrate_fp8"
+                    N.check(getattr(N.lib(), fn)(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(c.out), N.ptr(amax), N.ptr(c.ws), c.ws.numel(),
+                                                 c.stream), fn)
+                    vals = amax.cpu().reshape(c.s.layers, 4)
                     if not bool(torch.isfinite(vals).all()):
                         raise N.NativeError("calibrate_fp8: non-finite activations in the calibration batch")
-                    self._fp8_amax[tower] = vals.tolist()
-                    self._fp8_amax_key[tower] = self._fp8_param_key(tower)
-                    (self._vit_cache if tower == "vit" else self._txt_cache).key = None       # scales changed: rebuild the fp8 structs
-                    out.append(feat)
+                    self._fp8_amax[name] = vals.tolist()
+                    self._fp8_amax_key[name] = scan[len(tower.head):]          # the blocks' versions
+                    self._tower_cache[name].key = None                        # scales changed: rebuild the fp8 structs
+                    out.append(c.out)
         finally:
             self._gemm_dtype = mode
         return tuple(out)
@@ -321,74 +304,51 @@ class CLIP(nn.Module):
     def gemm_dtype(self) -> str:
         return {N.BF16: "bf16", N.FP8: "fp8"}.get(self._gemm_dtype, "f32")
 
-    def _fp8_param_key(self, tower):
-        blocks = self.visual.transformer if tower == "vit" else self.transformer
-        return tuple((p.data_ptr(), p._version) for p in blocks.parameters())
-
-    def _fp8_scales_current(self, tower):
+    def _fp8_scales_current(self, tower, versions):
         """Activation scales belong to the weights they were calibrated with: after load_state_dict or a training step the blocks
         produce other magnitudes, and stale per-tensor scales saturate at +-448 or waste range.  A change of any block parameter
         since the calibration drops the maxima, so that the next fp8 batch calibrates itself (assume_frozen skips the check)."""
-        if self._fp8_amax[tower] is not None and not self.assume_frozen and self._fp8_amax_key[tower] != self._fp8_param_key(tower):
+        name = tower.name
+        if self._fp8_amax[name] is not None and versions != "frozen" and self._fp8_amax_key[name] != versions[len(tower.head):]:
             import warnings
-            warnings.warn(f"fp8 mode: the {tower} tower's weights changed since calibrate_fp8; re-calibrating on this batch")
-            self._fp8_amax[tower] = None
-        return self._fp8_amax[tower] is not None
+            warnings.warn(f"fp8 mode: the {name} tower's weights changed since calibrate_fp8; re-calibrating on this batch")
+            self._fp8_amax[name] = None
+        return self._fp8_amax[name] is not None
 
     # -- native weight structs -------------------------------------------------------------------
-    def _key(self, params):
-        if self.assume_frozen:
-            return (self._gemm_dtype, str(self.device), "frozen")
-        return (self._gemm_dtype, str(self.device)) + tuple((p.data_ptr(), p._version) for p in params)
+    def _scan(self, tower):
+        """(data_ptr, _version) of every parameter of a tower (train_ops.VIT / TEXT), in the order of its table: the one walk over
+        the parameters that every key is made of.  A public call makes it at most once per tower and hands the result down."""
+        return tuple((p.data_ptr(), p._version) for p in tower.params(self))
+
+    def _versions(self, tower):
+        return "frozen" if self.assume_frozen else self._scan(tower)      # assume_frozen: no scan at all
+
+    def _key(self, tower, versions=None):
+        """what a tower's structs and features depend on besides the input: the arithmetic mode, the device, the weights' versions"""
+        return (self._gemm_dtype, str(self.device), self._versions(tower) if versions is None else versions)
+
+    def _tower_entry(self, tower, versions=None):
+        key = self._key(tower, versions)
+        if self._tower_cache[tower.name].key != key:
+            root, keep, dt = tower.root(self), [], self._gemm_dtype
+            s = tower.weights(gemm_dtype=dt, layers=len(root.transformer.resblocks), **tower.geometry(root))
+            for field, grad_field, get, is_gemm in tower.head:
+                t = _gemm_w(get(root), dt, keep, transpose=field != grad_field) if is_gemm else _prep(get(root), keep)
+                setattr(s, field, t.data_ptr())
+            blocks = _fill_blocks(root.transformer.resblocks, dt, keep, self._fp8_amax[tower.name])
+            s.blocks = C.cast(blocks, C.POINTER(N.BlockWeights))
+            self._tower_cache[tower.name] = _TowerCache(key, s, blocks, keep)
+        return self._tower_cache[tower.name]
+
+    def _tower_struct(self, tower, versions=None):
+        return self._tower_entry(tower, versions).struct
 
     def _vit_struct(self):
-        v, c = self.visual, self._vit_cache
-        key = self._key(list(v.parameters()))
-        if c.key != key:
-            keep, dt = [], self._gemm_dtype
-            s = N.VitWeights()
-            s.gemm_dtype = dt
-            s.resolution = v.input_resolution
-            s.patch = v.conv1.weight.shape[-1]
-            s.width = v.conv1.weight.shape[0]
-            s.layers = len(v.transformer.resblocks)
-            s.embed_dim = v.proj.shape[1]
-            s.conv1_w = _gemm_w(v.conv1.weight, dt, keep).data_ptr()
-            s.class_embedding = _prep(v.class_embedding, keep).data_ptr()
-            s.positional_embedding = _prep(v.positional_embedding, keep).data_ptr()
-            s.ln_pre_w = _prep(v.ln_pre.weight, keep).data_ptr()
-            s.ln_pre_b = _prep(v.ln_pre.bias, keep).data_ptr()
-            s.ln_post_w = _prep(v.ln_post.weight, keep).data_ptr()
-            s.ln_post_b = _prep(v.ln_post.bias, keep).data_ptr()
-            s.proj_t = _gemm_w(v.proj, dt, keep, transpose=True).data_ptr()
-            c.blocks = _fill_blocks(v.transformer.resblocks, dt, keep, self._fp8_amax["vit"])
-            s.blocks = C.cast(c.blocks, C.POINTER(N.BlockWeights))
-            c.struct, c.keep, c.key = s, keep, key
-        return c.struct
+        return self._tower_struct(T.VIT)
 
     def _text_struct(self):
-        c = self._txt_cache
-        params = [self.token_embedding.weight, self.positional_embedding, self.ln_final.weight, self.ln_final.bias,
-                  self.text_projection] + list(self.transformer.parameters())
-        key = self._key(params)
-        if c.key != key:
-            keep, dt = [], self._gemm_dtype
-            s = N.TextWeights()
-            s.gemm_dtype = dt
-            s.context_length = self.positional_embedding.shape[0]
-            s.vocab_size = self.token_embedding.weight.shape[0]
-            s.width = self.ln_final.weight.shape[0]
-            s.layers = len(self.transformer.resblocks)
-            s.embed_dim = self.text_projection.shape[1]
-            s.token_embedding = _prep(self.token_embedding.weight, keep).data_ptr()
-            s.positional_embedding = _prep(self.positional_embedding, keep).data_ptr()
-            s.ln_final_w = _prep(self.ln_final.weight, keep).data_ptr()
-            s.ln_final_b = _prep(self.ln_final.bias, keep).data_ptr()
-            s.text_projection_t = _gemm_w(self.text_projection, dt, keep, transpose=True).data_ptr()
-            c.blocks = _fill_blocks(self.transformer.resblocks, dt, keep, self._fp8_amax["text"])
-            s.blocks = C.cast(c.blocks, C.POINTER(N.BlockWeights))
-            c.struct, c.keep, c.key = s, keep, key
-        return c.struct
+        return self._tower_struct(T.TEXT)
 
     @staticmethod
     def _taps(tap_list):
@@ -399,84 +359,102 @@ class CLIP(nn.Module):
         return taps, arr
 
     # -- the two hot-path entry points -----------------------------------------------------------
+    def _wants_tape(self, *towers):
+        """the one tape-or-encode decision: a training forward when gradients are enabled and a tower parameter asks for them"""
+        if self.assume_frozen or not torch.is_grad_enabled() or not any(p.requires_grad for t in towers for p in t.params(self)):
+            return False
+        if self._gemm_dtype == N.FP8:
+            raise N.NativeError("the fp8 mode is inference-only: use torch.no_grad() or set_gemm_dtype('bf16' | 'f32') to train")
+        return True
+
+    def _operands(self, who, images=(), texts=()):
+        """Batches in the kernels' types (f32 / i64, contiguous), on the GPU like the weights, every image batch [n,3,R,R] with n its
+        caption batch's where there is one -> (images, texts)"""
+        images, texts = [N.f32c(i) for i in images], [t.to(torch.int64).contiguous() for t in texts]
+        N.require_gpu(*images, *texts, *([self.visual.proj] if images else []), *([self.text_projection] if texts else []))
+        R = self.visual.input_resolution
+        for k, im in enumerate(images):
+            want = ((texts[k] if texts else im).shape[0], 3, R, R)
+            if tuple(im.shape) != want:
+                raise N.NativeError(f"{who}: expected images {list(want)}, got {tuple(im.shape)}")
+        return images, texts
+
+    def _open(self, who, images=(), texts=(), versions=None, tokens=False, packed=False):
+        """What every inference entry point does before its native call, for each tower it has batches for: the operands
+        (_operands), fp8 activation scales calibrated on the first batch, the struct under one scan of the parameters (`versions`:
+        scans the caller made already), the result buffer ([B, E] pooled, [B*T, E] tokens), the tower's scratch of the current
+        stream, the device word that receives a packed text call's row count -> [_Call per tower, image first]"""
+        images, texts = self._operands(who, images, texts)
+        ops = [(T.VIT, images)] * bool(images) + [(T.TEXT, texts)] * bool(texts)
+        given = versions or {}
+        ver = {t.name: given[t.name] if t.name in given else self._versions(t) for t, _ in ops}
+        if self._gemm_dtype == N.FP8 and not all(self._fp8_scales_current(t, ver[t.name]) for t, _ in ops):
+            # the first batch (or the first after a weight change) calibrates the activation scales
+            self.calibrate_fp8(image=images[0] if images else None, text=texts[0] if texts else None, _versions=ver)
+        dev = (images or texts)[0].device
+        stream, calls = N.stream_ptr(dev), []
+        for tower, xs in ops:
+            s = self._tower_struct(tower, ver[tower.name])
+            B = sum(x.shape[0] for x in xs)
+            dims = (B, xs[0].shape[1]) if tower.text else (B,)
+            per = 1 if not tokens else dims[1] if tower.text else (s.resolution // s.patch) ** 2 + 1
+            out = torch.empty(B * per, s.embed_dim, dtype=torch.float32, device=dev)
+            need = getattr(N.lib(), f"cmh_{tower.name}_workspace_bytes")(C.byref(s), *dims)
+            ws = N.workspace(need, dev, f"{tower.name}@{stream}")         # one scratch per stream: sub-batches may overlap
+            rows = torch.empty(1, dtype=torch.int32, device=dev) if packed and tower.text else None    # stays on the device
+            x = torch.cat(xs, 0) if tower.text and len(xs) > 1 else xs[0]
+            calls.append(_Call(tower, s, x, xs[1:], dims, out, ws, rows, stream))
+        return calls
+
+    def _finish(self, *calls):
+        """... and after it: a packed call's row count is kept for `last_text_rows`; the features refuse a backward pass"""
+        for c in calls:
+            if c.rows is not None:
+                self._last_text_rows = (c.rows, c.dims[0] * c.dims[1])
+        return tuple(no_backward(c.out, c.tower.projection(self)) for c in calls)
+
     def encode_image(self, image, taps=None):
         """image f32 [B,3,R,R] -> [B, embed_dim] f32  (reference model/base/model.py:356-357,228-252)."""
-        if taps is None:
-            hit = self._stashed("image", image)
-            if hit is not None:
-                return hit
-        image = N.f32c(image)
-        N.require_gpu(image, self.visual.proj)
-        if self._gemm_dtype == N.FP8 and not self._fp8_scales_current("vit"):
-            self.calibrate_fp8(image=image)              # first batch (or first after a weight change) calibrates the activation scales
-        s = self._vit_struct()
-        B = image.shape[0]
-        if tuple(image.shape[1:]) != (3, s.resolution, s.resolution):
-            raise N.NativeError(f"encode_image: expected [B,3,{s.resolution},{s.resolution}], got {tuple(image.shape)}")
-        if taps is None and not self.assume_frozen:
-            from model.base import train_ops as T            # training: tape-keeping forward with a real backward
-            params = T.vit_params(self.visual)
-            if T.wants_grad(params):
-                if self._gemm_dtype == N.FP8:
-                    raise N.NativeError("the fp8 mode is inference-only: use torch.no_grad() or set_gemm_dtype('bf16' | 'f32') to train")
-                return T.VitTrain.apply(self, image, *params)
-        s = self._vit_struct()
-        feat = torch.empty(B, s.embed_dim, dtype=torch.float32, device=image.device)
-        need = N.lib().cmh_vit_workspace_bytes(C.byref(s), B)
-        ws = N.workspace(need, image.device, f"vit@{N.stream_ptr(image.device)}")   # one scratch per stream: sub-batches may overlap
+        if taps is None and self._wants_tape(T.VIT):         # training: tape-keeping forward with a real backward
+            (image,), _ = self._operands("encode_image", images=[image])
+            return T.VitTrain.apply(self, image, *T.VIT.params(self))
+        versions = self._versions(T.VIT)
+        hit = self._stashed("image", image, self._key(T.VIT, versions)) if taps is None else None
+        if hit is not None:
+            return hit
+        c, = self._open("encode_image", images=[image], versions={"vit": versions})
         tp, _arr = self._taps(taps)
-        N.check(N.lib().cmh_vit_encode(C.byref(s), N.ptr(image), B, N.ptr(feat), N.ptr(ws), ws.numel(),
-                                       None if tp is None else C.byref(tp), N.stream_ptr(image.device)),
-                "cmh_vit_encode")
-        return no_backward(feat, self.visual.proj)
+        N.check(N.lib().cmh_vit_encode(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(c.out), N.ptr(c.ws), c.ws.numel(),
+                                       None if tp is None else C.byref(tp), c.stream), "cmh_vit_encode")
+        return self._finish(c)[0]
 
     def encode_text(self, text, key_padding_mask=None, taps=None):
         """text i64 [B,L] -> [B, embed_dim] f32  (reference model/base/model.py:359-372)."""
-        if taps is None and key_padding_mask is None:
-            hit = self._stashed("text", text)
-            if hit is not None:
-                return hit
-        N.require_gpu(text, self.text_projection)
-        text = text.to(torch.int64).contiguous()
-        if self._gemm_dtype == N.FP8 and not self._fp8_scales_current("text"):
-            self.calibrate_fp8(text=text)
-        s = self._text_struct()
-        B, L = text.shape
         kpm = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()
-        if taps is None and not self.assume_frozen:
-            from model.base import train_ops as T
-            params = T.text_params(self)
-            if T.wants_grad(params):
-                if self._gemm_dtype == N.FP8:
-                    raise N.NativeError("the fp8 mode is inference-only: use torch.no_grad() or set_gemm_dtype('bf16' | 'f32') to train")
-                return T.TextTrain.apply(self, text, kpm, *params)
-        s = self._text_struct()
-        feat = torch.empty(B, s.embed_dim, dtype=torch.float32, device=text.device)
-        need = N.lib().cmh_text_workspace_bytes(C.byref(s), B, L)
-        ws = N.workspace(need, text.device, f"text@{N.stream_ptr(text.device)}")
-        if kpm is None and taps is None and self.pack_text:
-            # only the tokens up to each caption's EOT can reach the pooled row under the causal mask: skip the padding
-            rows = torch.empty(1, dtype=torch.int32, device=text.device)       # the count stays on the device: nothing waits for it
-            N.check(N.lib().cmh_text_encode_packed(C.byref(s), N.ptr(text), B, L, N.ptr(feat), N.ptr(rows), N.ptr(ws), ws.numel(),
-                                                   N.stream_ptr(text.device)), "cmh_text_encode_packed")
-            self._last_text_rows = (rows, B * L)
-            return no_backward(feat, self.text_projection)
-        tp, _arr = self._taps(taps)
-        N.check(N.lib().cmh_text_encode(C.byref(s), N.ptr(text), B, L, N.ptr(kpm), N.ptr(feat), N.ptr(ws), ws.numel(),
-                                        None if tp is None else C.byref(tp), N.stream_ptr(text.device)),
-                "cmh_text_encode")
-        return no_backward(feat, self.text_projection)
+        if taps is None and self._wants_tape(T.TEXT):
+            _, (text,) = self._operands("encode_text", texts=[text])
+            return T.TextTrain.apply(self, text, kpm, *T.TEXT.params(self))
+        versions, plain = self._versions(T.TEXT), taps is None and kpm is None
+        hit = self._stashed("text", text, (self.pack_text, self._key(T.TEXT, versions))) if plain else None
+        if hit is not None:
+            return hit
+        # only the tokens up to each caption's EOT can reach the pooled row under the causal mask: the packed call skips the padding
+        c, = self._open("encode_text", texts=[text], versions={"text": versions}, packed=plain and self.pack_text)
+        if c.rows is not None:
+            N.check(N.lib().cmh_text_encode_packed(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(c.out), N.ptr(c.rows), N.ptr(c.ws),
+                                                   c.ws.numel(), c.stream), "cmh_text_encode_packed")
+        else:
+            tp, _arr = self._taps(taps)
+            N.check(N.lib().cmh_text_encode(C.byref(c.s), N.ptr(c.x), *c.dims, N.ptr(kpm), N.ptr(c.out), N.ptr(c.ws), c.ws.numel(),
+                                            None if tp is None else C.byref(tp), c.stream), "cmh_text_encode")
+        return self._finish(c)[0]
 
     def prefetch_pair(self, image, text):
         """Inference helper for code that calls encode_image(image) and encode_text(text) back to back (every method model's
         encode_* does, model/modelbase.py:88-92): run both towers NOW in lock-step (encode_pair) and hand the two features out to
         the next encode_image / encode_text call on these very tensors.  Bit-identical to the separate calls; a no-op when a
         gradient is wanted."""
-        if torch.is_grad_enabled() and not self.assume_frozen:
-            return
-        fi, ft = self.encode_pair(image, text)
-        key = self._stash_key()
-        self._pair_stash = {"image": [(image, fi, key)], "text": [(text, ft, key)]}
+        self.prefetch_pairs([(image, text)])
 
     def prefetch_pairs(self, batches):
         """prefetch_pair for TWO loader batches [(image_a, text_a), (image_b, text_b)] in one native call (cmh_clip_encode_pair2: the
@@ -484,28 +462,26 @@ class CLIP(nn.Module):
         out to its own encode_image / encode_text calls; bit-identical to two prefetch_pair calls."""
         if torch.is_grad_enabled() and not self.assume_frozen:
             return
-        (ia, ta), (ib, tb) = batches
-        fi, ft = self.encode_pair2(ia, ta, ib, tb)
-        key, Ba = self._stash_key(), ia.shape[0]
-        self._pair_stash = {"image": [(ia, fi[:Ba], key), (ib, fi[Ba:], key)], "text": [(ta, ft[:Ba], key), (tb, ft[Ba:], key)]}
+        # what a stashed feature depends on besides its input tensor: the arithmetic mode and its tower's weights (and the packing)
+        versions = {t.name: self._versions(t) for t in (T.VIT, T.TEXT)}
+        fi, ft = self._encode_pairs(batches, versions)
+        keys = (self._key(T.VIT, versions["vit"]), (self.pack_text, self._key(T.TEXT, versions["text"])))
+        self._pair_stash, lo = {"image": [], "text": []}, 0
+        for image, text in batches:
+            hi = lo + image.shape[0]
+            self._pair_stash["image"].append((image, fi[lo:hi], keys[0]))
+            self._pair_stash["text"].append((text, ft[lo:hi], keys[1]))
+            lo = hi
 
-    def _stashed(self, side, x):
+    def _stashed(self, side, x, key):
         st = getattr(self, "_pair_stash", None)
-        if not st or not st.get(side):
-            return None
-        for i, (src, feat, key) in enumerate(st[side]):
-            if src is x and key == self._stash_key():
+        for i, (src, feat, its_key) in enumerate(st.get(side, ()) if st else ()):
+            if src is x and its_key == key:
                 del st[side][i]
                 if not st[side]:
                     del st[side]
                 return feat
         return None
-
-    def _stash_key(self):
-        """what a stashed feature depends on besides its input tensor: the arithmetic mode and the weights' versions"""
-        text = [self.token_embedding.weight, self.positional_embedding, self.ln_final.weight, self.ln_final.bias,
-                self.text_projection] + list(self.transformer.parameters())
-        return (self.pack_text, self._key(list(self.visual.parameters())), self._key(text))
 
     def drop_pair_stash(self):
         """Forget features prefetch_pair computed and nobody picked up; counts them (`pair_stash_misses`) so that a model whose
@@ -519,58 +495,26 @@ class CLIP(nn.Module):
         """(encode_image(image), encode_text(text)) with the two towers in lock-step: layer i of both shares its GEMM launches
         (cmh_clip_encode_pair; reference model/modelbase.py:105-108 calls the two encoders back to back).  Bit-identical to the two
         separate calls.  Inference (no tape); training, taps and masks take the single-tower entry points."""
-        if not self.assume_frozen and torch.is_grad_enabled():
-            from model.base import train_ops as T
-            if T.wants_grad(T.vit_params(self.visual)) or T.wants_grad(T.text_params(self)):
-                return self.encode_image(image), self.encode_text(text)
-        image = N.f32c(image)
-        N.require_gpu(image, text, self.visual.proj, self.text_projection)
-        text = text.to(torch.int64).contiguous()
-        if self._gemm_dtype == N.FP8 and not (self._fp8_scales_current("vit") and self._fp8_scales_current("text")):
-            self.calibrate_fp8(image=image, text=text)
-        sv, st = self._vit_struct(), self._text_struct()
-        B, L = text.shape
-        if tuple(image.shape) != (B, 3, sv.resolution, sv.resolution):
-            raise N.NativeError(f"encode_pair: expected image [{B},3,{sv.resolution},{sv.resolution}], got {tuple(image.shape)}")
-        fi = torch.empty(B, sv.embed_dim, dtype=torch.float32, device=image.device)
-        ft = torch.empty(B, st.embed_dim, dtype=torch.float32, device=image.device)
-        tag = N.stream_ptr(image.device)
-        wv = N.workspace(N.lib().cmh_vit_workspace_bytes(C.byref(sv), B), image.device, f"vit@{tag}")
-        wt = N.workspace(N.lib().cmh_text_workspace_bytes(C.byref(st), B, L), image.device, f"text@{tag}")
-        rows = torch.empty(1, dtype=torch.int32, device=image.device) if self.pack_text else None
-        N.check(N.lib().cmh_clip_encode_pair(C.byref(sv), N.ptr(image), C.byref(st), N.ptr(text), B, L, 1 if self.pack_text else 0,
-                                             N.ptr(fi), N.ptr(ft), N.ptr(rows), N.ptr(wv), wv.numel(), N.ptr(wt), wt.numel(), tag),
-                "cmh_clip_encode_pair")
-        if rows is not None:
-            self._last_text_rows = (rows, B * L)
-        return no_backward(fi, self.visual.proj), no_backward(ft, self.text_projection)
+        if self._wants_tape(T.VIT, T.TEXT):
+            return self.encode_image(image), self.encode_text(text)
+        return self._encode_pairs([(image, text)])
 
     def encode_pair2(self, image_a, text_a, image_b, text_b):
         """encode_pair of two batches in one native call: (features of [a; b] images, of [a; b] captions).  The images stay two
         tensors (cmh_clip_encode_pair2 patchifies them into one matrix), the captions are concatenated (157 KB).  Inference only."""
-        image_a, image_b = N.f32c(image_a), N.f32c(image_b)
-        N.require_gpu(image_a, image_b, text_a, text_b, self.visual.proj, self.text_projection)
-        text = torch.cat([text_a.to(torch.int64), text_b.to(torch.int64)], 0).contiguous()
-        if self._gemm_dtype == N.FP8 and not (self._fp8_scales_current("vit") and self._fp8_scales_current("text")):
-            self.calibrate_fp8(image=image_a, text=text_a.to(torch.int64).contiguous())
-        sv, st = self._vit_struct(), self._text_struct()
-        Ba, Bb, L = image_a.shape[0], image_b.shape[0], text.shape[1]
-        B = Ba + Bb
-        for im, n in ((image_a, text_a.shape[0]), (image_b, text_b.shape[0])):
-            if tuple(im.shape) != (n, 3, sv.resolution, sv.resolution):
-                raise N.NativeError(f"encode_pair2: expected images [{n},3,{sv.resolution},{sv.resolution}], got {tuple(im.shape)}")
-        fi = torch.empty(B, sv.embed_dim, dtype=torch.float32, device=image_a.device)
-        ft = torch.empty(B, st.embed_dim, dtype=torch.float32, device=image_a.device)
-        tag = N.stream_ptr(image_a.device)
-        wv = N.workspace(N.lib().cmh_vit_workspace_bytes(C.byref(sv), B), image_a.device, f"vit@{tag}")
-        wt = N.workspace(N.lib().cmh_text_workspace_bytes(C.byref(st), B, L), image_a.device, f"text@{tag}")
-        rows = torch.empty(1, dtype=torch.int32, device=image_a.device) if self.pack_text else None
-        N.check(N.lib().cmh_clip_encode_pair2(C.byref(sv), N.ptr(image_a), Ba, N.ptr(image_b), Bb, C.byref(st), N.ptr(text), L,
-                                              1 if self.pack_text else 0, N.ptr(fi), N.ptr(ft), N.ptr(rows), N.ptr(wv), wv.numel(),
-                                              N.ptr(wt), wt.numel(), tag), "cmh_clip_encode_pair2")
-        if rows is not None:
-            self._last_text_rows = (rows, B * L)
-        return no_backward(fi, self.visual.proj), no_backward(ft, self.text_projection)
+        return self._encode_pairs([(image_a, text_a), (image_b, text_b)])
+
+    def _encode_pairs(self, batches, versions=None):
+        v, t = self._open("encode_pair" if len(batches) == 1 else "encode_pair2", *zip(*batches), versions=versions, packed=self.pack_text)
+        pack, (B, L) = 1 if self.pack_text else 0, t.dims
+        tail = (N.ptr(v.out), N.ptr(t.out), N.ptr(t.rows), N.ptr(v.ws), v.ws.numel(), N.ptr(t.ws), t.ws.numel(), v.stream)
+        if len(batches) == 1:
+            N.check(N.lib().cmh_clip_encode_pair(C.byref(v.s), N.ptr(v.x), C.byref(t.s), N.ptr(t.x), B, L, pack, *tail),
+                    "cmh_clip_encode_pair")
+        else:
+            N.check(N.lib().cmh_clip_encode_pair2(C.byref(v.s), N.ptr(v.x), v.x.shape[0], N.ptr(v.more[0]), v.more[0].shape[0],
+                                                  C.byref(t.s), N.ptr(t.x), L, pack, *tail), "cmh_clip_encode_pair2")
+        return self._finish(v, t)
 
     def forward(self, image, text):
         """Cosine-similarity logits (reference :374-388); assembled from the two native encodes."""
@@ -605,26 +549,31 @@ def convert_weights(model: nn.Module):
     model.apply(_convert)
 
 
-def build_model(state_dict: dict):
-    """Reference :415-455: infer the architecture from tensor shapes, fp16-convert, load strict."""
+def infer_shapes(state_dict: dict) -> dict:
+    """Reference :415-437: the constructor's arguments from the checkpoint's tensor shapes."""
     if "visual.proj" not in state_dict:
         raise NotImplementedError("only ViT CLIP checkpoints are supported (no visual.proj in state_dict)")
-    vision_width = state_dict["visual.conv1.weight"].shape[0]
-    vision_layers = len([k for k in state_dict if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
-    vision_patch_size = state_dict["visual.conv1.weight"].shape[-1]
-    grid_size = round((state_dict["visual.positional_embedding"].shape[0] - 1) ** 0.5)
-    image_resolution = vision_patch_size * grid_size
-    embed_dim = state_dict["text_projection"].shape[1]
-    context_length = state_dict["positional_embedding"].shape[0]
-    vocab_size = state_dict["token_embedding.weight"].shape[0]
-    transformer_width = state_dict["ln_final.weight"].shape[0]
-    transformer_heads = transformer_width // 64
-    transformer_layers = len(set(k.split(".")[2] for k in state_dict if k.startswith("transformer.resblocks")))
-    model = CLIP(embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size, context_length,
-                 vocab_size, transformer_width, transformer_heads, transformer_layers)
+    patch = state_dict["visual.conv1.weight"].shape[-1]
+    width = state_dict["ln_final.weight"].shape[0]
+    return dict(embed_dim=state_dict["text_projection"].shape[1],
+                image_resolution=patch * round((state_dict["visual.positional_embedding"].shape[0] - 1) ** 0.5),
+                vision_layers=len([k for k in state_dict if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")]),
+                vision_width=state_dict["visual.conv1.weight"].shape[0], vision_patch_size=patch,
+                context_length=state_dict["positional_embedding"].shape[0], vocab_size=state_dict["token_embedding.weight"].shape[0],
+                transformer_width=width, transformer_heads=width // 64,
+                transformer_layers=len(set(k.split(".")[2] for k in state_dict if k.startswith("transformer.resblocks"))))
+
+
+def build_model(state_dict: dict, cls=CLIP, accept=None):
+    """Reference :415-455: infer the architecture from tensor shapes, fp16-convert, load strict.  `accept(shapes)` may refuse them."""
+    shapes = infer_shapes(state_dict)
+    if accept is not None:
+        accept(shapes)
+    model = cls(**shapes)
     for key in ["input_resolution", "context_length", "vocab_size"]:
         if key in state_dict:
             del state_dict[key]
     convert_weights(model)
     model.load_state_dict(state_dict)
     return model
+

@@ -1,7 +1,10 @@
 """Every forward entry point of the two towers, once, on seeded inputs: the check behind a change of the block sequencing
 (csrc/encoders.hip, csrc/encoders_bwd.hip), which must leave every output bit and every launch as they were.
 
-    python tools/entry_points_ab.py run OUT.json                      one library (CMH_LIB picks it), a fresh process each
+    python tools/entry_points_ab.py run OUT.json [towers|mith]        one library (CMH_LIB picks it), a fresh process each; every leg
+                                                                       or one: the towers' entry points, or MITH (trunk + HashingModel:
+                                                                       forward, three BertAdam steps) - the check behind a change of
+                                                                       the Python layer, run on two Python trees over ONE library
     python tools/entry_points_ab.py compare A.json B.json [A2.json]   per-entry-point verdict; exit status 1 on any difference
                                                                        (A2: a second run of A - what it does not reproduce is named, not compared)
     python tools/entry_points_ab.py launches TRACE_DIR [TRACE_DIR_B]  digest of the ordered (kernel, grid, workgroup) list per stream
@@ -33,7 +36,7 @@ MIXED = dict(embed_dim=256, image_resolution=224, vision_layers=3, vision_width=
              vocab_size=49408, transformer_width=384, transformer_heads=6, transformer_layers=2)             # fp16 / f32 streams, 3 / 2 blocks
 
 
-def run(out_path):
+def run(out_path, legs="all"):
     import numpy as np
     import torch
     import cmh_native as N
@@ -174,7 +177,47 @@ def run(out_path):
             keep(f"{tag}/{mode}/blocks_backward/dx", x.grad)
             grads_of(f"{tag}/{mode}/blocks_backward", bp)
 
-    try:
+    def mith(tag, B=6, L=16, steps=3):
+        """MITH at tiny shapes (token-returning trunk + HashingModel): the forward in both modes, then `steps` BertAdam steps on a
+        fixed cotangent, with the loss and the codes of every step.  The token embedding stays out of the optimiser: its gradient
+        is a float atomicAdd scatter, and a step on it would make every later array irreproducible."""
+        from types import SimpleNamespace
+        from model.MITH import HashingModel, build_model
+        from model.base.optimization import BertAdam
+        cfg = dict(recipe.CLIP_TINY, embed_dim=512)
+        args = SimpleNamespace(output_dim=16, dropout=0.0, transformer_layers=2, activation="gelu", top_k_label=8, res_mlp_layers=2)
+        img, txt, kpm = inputs(cfg, B, L, 6)
+        for mode in ("f32", "bf16"):
+            torch.manual_seed(6)
+            clip = build_model({k: torch.from_numpy(v) for k, v in recipe.clip_state_dict(cfg, 6).items()}).to(dev).float()
+            clip.set_gemm_dtype(mode).padded_tokens_unused = True
+            clip.token_embedding.weight.requires_grad_(False)
+            hm = HashingModel(clip_embed_dim=512, args=args).to(dev).set_gemm_dtype(mode)
+
+            def forward():
+                (it, _, ic), (tt, _, nk, te) = clip.encode_image(img), clip.encode_text(txt, kpm)
+                return sorted(hm(it, tt, ic, te, nk).items())
+            with torch.no_grad():
+                for name, v in forward():
+                    keep(f"{tag}/{mode}/forward/{name}", v)
+            params = [p for p in list(clip.parameters()) + list(hm.parameters()) if p.requires_grad and p is not clip.logit_scale]
+            opt = BertAdam(params, lr=1e-3, warmup=0.1, t_total=10 * steps)
+            gen = torch.Generator(dev).manual_seed(8)
+            for step in range(steps):
+                out = forward()
+                loss = sum((v * torch.randn(v.shape, device=dev, generator=gen)).sum() for _, v in out)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+                keep(f"{tag}/{mode}/train/step{step}/loss", loss)
+                for name, v in out:
+                    if name.endswith("_hash"):
+                        keep(f"{tag}/{mode}/train/step{step}/{name}", v)
+            with torch.no_grad():                                  # the weights the steps left, through the inference path
+                for name, v in forward():
+                    keep(f"{tag}/{mode}/after/{name}", v)
+
+    def towers():
         cfg = recipe.CLIP_VITB32
         m = model(cfg, 1)
         img, txt, kpm = inputs(cfg, 32, 77, 1)
@@ -195,6 +238,12 @@ def run(out_path):
         img, txt, kpm = inputs(cfg, 32, 16, 4)
         inference("tiny", m, img, txt, kpm, ("f32", "bf16"), True)
         training("tiny", m, img, txt, kpm, ("f32", "bf16"), True, switches=True)
+
+    try:
+        if legs in ("all", "towers"):
+            towers()
+        if legs in ("all", "mith"):
+            mith("mith")
     finally:
         N.set_pooled_tail(True)
         N.set_grad_stream16(-1)
@@ -253,7 +302,7 @@ def launches(dirs):
 if __name__ == "__main__":
     cmd = sys.argv[1] if len(sys.argv) > 1 else ""
     if cmd == "run":
-        run(sys.argv[2])
+        run(*sys.argv[2:4])
     elif cmd == "compare":
         sys.exit(compare(*sys.argv[2:5]))
     elif cmd == "launches":
