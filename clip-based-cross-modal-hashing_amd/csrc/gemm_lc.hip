@@ -73,6 +73,24 @@ __device__ __forceinline__ lc_u32x4_t lc_lds_read(uint32_t addr) { return *reint
                    // wall clock over the same span (clock = ticks / wall)
 __device__ unsigned long long g_lc_stamps[256 * 8];
 #define LC_T() __builtin_amdgcn_s_memtime()
+// the 12-wave 160-row forms (lc3, lc3g; tools/lc3_stamps.py): ticks in front of the first stage | inside the K loops (lc3g: the K-steps that
+// carry parked pieces included) | from a K loop's end to its epilogue's end | from there to the next K loop's start; slot 7 = the last
+#define LC3_ST_BEGIN() const unsigned long long st_t0 = LC_T(), st_r0 = __builtin_amdgcn_s_memrealtime(); unsigned long long st_first = 0, st_k = 0, st_e = 0, st_g = 0, st_mark = 0
+#define LC3_ST_FIRST() do { st_mark = LC_T(); st_first = st_mark - st_t0; } while (0)
+#define LC3_ST_LAP(sum) do { const unsigned long long t_ = LC_T(); sum += t_ - st_mark; st_mark = t_; } while (0)
+#define LC3_ST_END(S_, TILES_)                                                                                              \
+  do {                                                                                                                      \
+    if (c == 0 && lane == 0 && blockIdx.x < 256) {                                                                          \
+      unsigned long long* o = g_lc_stamps + blockIdx.x * 8;                                                                 \
+      o[0] = LC_T() - st_t0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0; o[2] = st_first; o[3] = st_k; o[4] = st_e;    \
+      o[5] = static_cast<unsigned long long>(S_); o[6] = static_cast<unsigned long long>(TILES_); o[7] = st_g;              \
+    }                                                                                                                       \
+  } while (0)
+#else
+#define LC3_ST_BEGIN() do {} while (0)
+#define LC3_ST_FIRST() do {} while (0)
+#define LC3_ST_LAP(sum) do {} while (0)
+#define LC3_ST_END(S_, TILES_) do {} while (0)
 #endif
 
 // ---- what the four kernels share: the tile schedule, the loader waves, the 12-wave forms' epilogue pieces --------------------------------
@@ -1045,6 +1063,7 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   };
   [[maybe_unused]] auto add_piece = [&](int b, int pr, const lc_u32x4_t& qv) __attribute__((always_inline)) { lc_add_piece(acc, b, pr, qv); };
 
+  LC3_ST_BEGIN();
   int cur = 0;
   if constexpr (RES == 1) {                        // the first tile's accumulators start as its residual rows (0 + r: the wide kernel's bits)
     const uint16_t* rb; int ld, rows;
@@ -1060,6 +1079,7 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
   }
   __builtin_amdgcn_s_barrier();                    // stage 0 has landed
   asm volatile("" ::: "memory");
+  LC3_ST_FIRST();
 #pragma unroll
   for (int b = 0; b < 5; ++b) fx[b] = lc_lds_read(aX + b * 2048);
 #pragma unroll
@@ -1159,10 +1179,12 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
     if constexpr (RES == 1) { res_kt = ti + 1 < my_tiles ? 4 : -1; if (ti + 1 < my_tiles) residual_of(ti + 1, rq_base, rq_ld, rq_rows); }
     if constexpr (RES == 2) { res_kt = 4; residual_of(ti, rq_base, rq_ld, rq_rows); }
     if constexpr (RES != 0) asm volatile("" : "+s"(res_kt));
+    LC3_ST_LAP(st_g);
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("" : "+s"(kt));
       kstep(kt);
     }
+    LC3_ST_LAP(st_k);
     // nk >= 8 (host): every parked piece has left after four K-steps
 
     // row block 4's residual (not parked): RES 2 this tile's, RES 1 the next tile's
@@ -1232,10 +1254,272 @@ __global__ __launch_bounds__(768) void gemm_lc3_kernel(LcProblem p0, LcProblem p
               *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + static_cast<uint32_t>(b * 16) * ldn + pr * 64)) = pend[2 * b + pr];
       }
     }
+    LC3_ST_LAP(st_e);
   }
+  LC3_ST_END(S, my_tiles);
 #undef L3_GROUP
 #undef L3_LAST
 #undef L3_REFILL_W
+}
+
+// ---- "lc3g": lc3 for bias + QuickGELU launches (c_fc), the activation of three output pieces under the next tile's MFMAs --------------
+// lc3's epilogue runs lc_quickgelu on 80 accumulators per lane (160 v_exp_f32 / v_rcp_f32) in both MFMA waves of every SIMD at once,
+// with no MFMA in flight.  Here the parked registers hold f32 PRE-activations (accumulator + bias) instead of packed outputs: NPARK = 3
+// of a tile's ten 16-byte pieces (b, pr) per lane - row block 0 and the first half of row block 1, 24 registers - while the epilogue
+// activates, packs and stores the other seven; the next tile's first three K-steps each finish one parked piece - its 8 values
+// through the QuickGELU sequence, the pack, the lane-pair exchange and the store - in the issue slots behind the wave's own MFMAs,
+// the wide kernel's deferred QuickGELU (gemm_wide.hip, DGE).  The piece is a compile-time index: the three K-steps are straight-line
+// copies of the K-step with named registers.  Spacing: at most two plain VALU instructions, or one transcendental and one plain one,
+// behind an MFMA (a transcendental weighs 5/3), scalar f32 only - v_pk_*_f32 beside MFMAs is an anti-lever, and v * c, e + 1,
+// v * r are the same IEEE operations packed or not.  Same MFMA chain per element, same expression and order (bias, QuickGELU per
+// value pair, pack): lc3's and the wide kernel's bits.  Nothing is parked behind a workgroup's last tile, a ragged tile or a
+// timing-only launch (epi & 256): those finish in the epilogue, all ten pieces.  Measured: DESIGN 4.5, profiles/r10_b.
+// (The bias-only launches - QKV - ran this form too, without the activation: slower in the encoder step; they stay on lc3.)
+// lc_quickgelu on the 8 values of output piece (b, pr): n-fragments 2 pr and 2 pr + 1 of row block b
+template <int MF>
+__device__ __forceinline__ void lc_quickgelu_piece(lc_f32x4_t (&acc)[4][MF], int b, int pr) {
+#pragma unroll
+  for (int a = 2 * pr; a < 2 * pr + 2; ++a)
+#pragma unroll
+    for (int j = 0; j < 4; j += 2) {
+      const lc_f32x2_t v = {acc[a][b][j], acc[a][b][j + 1]};
+      const lc_f32x2_t t = v * lc_f32x2_t{-2.4554669595930157f, -2.4554669595930157f};
+      const lc_f32x2_t d = lc_f32x2_t{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + lc_f32x2_t{1.0f, 1.0f};
+      const lc_f32x2_t o = v * lc_f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+      acc[a][b][j] = o[0];
+      acc[a][b][j + 1] = o[1];
+    }
+}
+
+// NPARK: pieces parked per tile.  3 = row block 0 and the first half of row block 1, 24 registers: with the fourth piece the four
+// instantiations want 171-175 registers and keep part of it in scratch through the K-steps
+template <bool GRP, bool F16O, int NPARK = 3>
+__global__ __launch_bounds__(768) void gemm_lc3g_kernel(LcProblem p0, LcProblem p1, int epi) {
+  __shared__ __attribute__((aligned(1024))) char lds[3 * lc3STG + 2 * 1024];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const char* const X0 = p0.X; const char* const W0 = p0.W; const float* const B0 = p0.bias; void* const O0 = p0.out;
+  const int N0 = p0.N, K0 = p0.K;
+  const char* const X1 = p1.X; const char* const W1 = p1.W; const float* const B1 = p1.bias; void* const O1 = p1.out;
+  const int N1 = p1.N, K1 = p1.K;
+  LcSchedule<lc3BM, GRP> sc(p0, p1);
+  if (sc.my_tiles == 0) return;
+  sc.count_ksteps(p0, p1);
+  const int n_first = sc.n_first, my_tiles = sc.my_tiles;
+
+  if (wid < 4) {
+    lc_loader_wave<lc3BM, GRP>(sc, lds, wid, lane, epi, X0, W0, B0, K0, X1, W1, B1, K1);
+    return;
+  }
+
+  // ---- MFMA waves: lc3's 2 (m) x 4 (n) waves of 80 x 64, the same fragments, refills and barrier ----
+  const int c = wid - 4;
+  const int wm = c >> 2, wn = c & 3;
+  const int frow = lane & 15, fq = lane >> 4;
+  const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lc_lptr_t)lds));
+  const uint32_t aW = lds_base + lc_swz(wn * 64 + frow, fq);
+  const uint32_t aX = lds_base + lcWBytes + lc_swz(wm * 80 + frow, fq);
+
+  lc_f32x4_t acc[4][5];                            // [n-fragment][m-fragment]
+  lc_u32x4_t fw[4], fx[5];
+  lc_f32x4_t park[4][2];                           // the previous tile's parked pieces: (b, pr) at [2 pr][b], [2 pr + 1][b]; accumulator + bias
+  bool parked = false;                             // (uniform) the next tile's first K-steps finish them
+  char* pend_base = nullptr;                       // ... at the parking tile's own place: its problem's out and row stride
+  uint32_t pend_ldn = 0;
+
+  void* out = O0;
+  int N = N0, M = sc.M0, nk = sc.nk0;
+  [[maybe_unused]] auto to_problem1 = [&]() { out = O1; N = N1; M = sc.M1; nk = sc.nk1; };
+  if constexpr (GRP) { if (n_first == 0) to_problem1(); }
+
+  LC3_ST_BEGIN();
+  int cur = 0;
+  __builtin_amdgcn_s_barrier();                    // stage 0 has landed
+  asm volatile("" ::: "memory");
+  LC3_ST_FIRST();
+#pragma unroll
+  for (int b = 0; b < 5; ++b) fx[b] = lc_lds_read(aX + b * 2048);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) fw[a] = lc_lds_read(aW + a * 2048);
+
+  // Slot s (0..39: behind the K-step's s-th MFMA) of the K-step that carries piece J = 2 b + pr, whose 8 values lie in A = park[2 pr][b]
+  // and B = park[2 pr + 1][b].  Eight slots take one value pair through lc_quickgelu's sequence; the pairs go in the order A[0..1],
+  // A[2..3], B[0..1], B[2..3] and each packed word goes where a spent value of A lay - A[0], A[1], A[2], A[3] - so that after the
+  // lane-pair exchange (slot 33: A[0] with A[2] = lc_pack_piece's lo[0], hi[0]; A[1] with A[3] = lo[1], hi[1]) A itself is the
+  // 16 bytes to store: a piece in flight needs two registers of its own.
+  struct Piece { float g0, g1; };
+  auto micro = [&](auto jc, Piece& pc, auto sc_) __attribute__((always_inline)) {
+    constexpr int J = decltype(jc)::value;
+    constexpr int s = decltype(sc_)::value;
+    if constexpr (J >= 0) {
+      constexpr int PB = J >> 1, PR = J & 1;
+      lc_f32x4_t& A = park[2 * PR][PB];
+      if constexpr (s < 32) {
+        constexpr int q = s >> 3;                      // pair q: q < 2 from A, else from B; values 2 (q & 1), 2 (q & 1) + 1
+        const lc_f32x4_t& src = q < 2 ? A : park[2 * PR + 1][PB];
+        const float v0 = src[2 * (q & 1)], v1 = src[2 * (q & 1) + 1];
+        switch (s & 7) {                           // (a constant: one case per slot)
+          case 0: pc.g0 = v0 * -2.4554669595930157f; break;
+          case 1: pc.g0 = __builtin_amdgcn_exp2f(pc.g0); break;
+          case 2: pc.g1 = v1 * -2.4554669595930157f; pc.g0 = pc.g0 + 1.0f; break;
+          case 3: pc.g1 = __builtin_amdgcn_exp2f(pc.g1); break;
+          case 4: pc.g0 = __builtin_amdgcn_rcpf(pc.g0); break;
+          case 5: pc.g1 = pc.g1 + 1.0f; pc.g0 = v0 * pc.g0; break;
+          case 6: pc.g1 = __builtin_amdgcn_rcpf(pc.g1); break;
+          default:
+            pc.g1 = v1 * pc.g1;
+            A[q] = __builtin_bit_cast(float, F16O ? pack_f16x2(pc.g0, pc.g1) : pack_bf16x2(pc.g0, pc.g1));
+            break;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      } else if constexpr (s == 33) {
+        const float w0 = A[0], w1 = A[1], w2 = A[2], w3 = A[3];      // (copies: a bit cast of a vector ELEMENT reads element 0 whatever the index)
+        const lc_u2_t s0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, w0), __builtin_bit_cast(uint32_t, w2), false, false);
+        const lc_u2_t s1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, w1), __builtin_bit_cast(uint32_t, w3), false, false);
+        // (the lane's offset is formed again from a fresh lane count: kept, it would be one more register alive through every K-step)
+        int ln = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+        asm volatile("" : "+v"(ln));               // (opaque, or every piece's offset is formed in front of the tile loop and kept)
+        const uint32_t po = static_cast<uint32_t>(wm * 80 + PB * 16 + (ln & 15)) * pend_ldn +
+                            static_cast<uint32_t>(wn * 64 + ((ln >> 4) & 1) * 16 + ((ln >> 4) & 2) * 4) * 2 + PR * 64;
+        *reinterpret_cast<lc_u32x4_t*>(pend_base + po) = lc_u32x4_t{s0[0], s1[0], s0[1], s1[1]};
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+
+  // lc3's half-step (group a = fw[a] x fx[0..4], W-outer; fw[a] refilled after its group, fx[b] after MFMA (3, b), fw[3] last) with
+  // slot S0 + 5 a + b behind MFMA (a, b)
+#define G3_MFMA(jc, a, b, S0)                                                                          \
+  do {                                                                                                 \
+    acc[a][b] = lc_mfma_bf16(fw[a], fx[b], acc[a][b]);                                                 \
+    micro(jc, pc, std::integral_constant<int, (S0) + 5 * (a) + (b)>{});                                                                   \
+  } while (0)
+#define G3_GROUP(jc, a, S0)                                                                            \
+  do {                                                                                                 \
+    G3_MFMA(jc, a, 0, S0); G3_MFMA(jc, a, 1, S0); G3_MFMA(jc, a, 2, S0); G3_MFMA(jc, a, 3, S0); G3_MFMA(jc, a, 4, S0); \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+#define G3_LAST(jc, S0, wsrc, xsrc)                                                                    \
+  do {                                                                                                 \
+    G3_MFMA(jc, 3, 0, S0);                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[0] = lc_lds_read((xsrc));                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    G3_MFMA(jc, 3, 1, S0);                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[1] = lc_lds_read((xsrc) + 2048);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    G3_MFMA(jc, 3, 2, S0);                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[2] = lc_lds_read((xsrc) + 4096);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    G3_MFMA(jc, 3, 3, S0);                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[3] = lc_lds_read((xsrc) + 6144);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    G3_MFMA(jc, 3, 4, S0);                                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    fx[4] = lc_lds_read((xsrc) + 8192);                                                                \
+    fw[3] = lc_lds_read((wsrc) + 6144);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+#define G3_REFILL_W(a, wsrc)                                                                           \
+  do {                                                                                                 \
+    fw[a] = lc_lds_read((wsrc) + (a) * 2048);                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+
+  auto kstep = [&](auto jc) __attribute__((always_inline)) {
+    [[maybe_unused]] Piece pc;
+    const uint32_t bo = static_cast<uint32_t>(cur) * lc3STG;
+    const uint32_t w1 = (aW + bo) ^ 64u, x1 = (aX + bo) ^ 64u;      // k 32..63 of this stage
+    // ---------------- half 0: slots 0..19 ----------------
+    G3_GROUP(jc, 0, 0); G3_REFILL_W(0, w1);
+    G3_GROUP(jc, 1, 0); G3_REFILL_W(1, w1);
+    G3_GROUP(jc, 2, 0); G3_REFILL_W(2, w1);
+    G3_LAST(jc, 0, w1, x1);
+    // ---------------- half 1: slots 20..39 ----------------
+    const int nxt = cur == 2 ? 0 : cur + 1;
+    const uint32_t bn = static_cast<uint32_t>(nxt) * lc3STG;
+    const uint32_t w0 = aW + bn, x0 = aX + bn;      // k 0..31 of the next stage
+    G3_GROUP(jc, 0, 20);
+    G3_GROUP(jc, 1, 20);
+    __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): every fragment of this stage is in registers ...
+    __builtin_amdgcn_s_barrier();                  // ... in every MFMA wave; the next stage has landed
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    G3_REFILL_W(0, w0); G3_REFILL_W(1, w0);
+    G3_GROUP(jc, 2, 20); G3_REFILL_W(2, w0);
+    G3_LAST(jc, 20, w0, x0);
+    cur = nxt;
+  };
+
+  for (int ti = 0; ti < my_tiles; ++ti) {
+    bool second; int m0, n0;
+    sc.tile_of(ti, second, m0, n0);
+    if constexpr (GRP) { if (ti == n_first && ti > 0) to_problem1(); }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 5; ++b) acc[a][b] = lc_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // (opaque zeros: with C = 0 folded into the first MFMAs of the straight-line K-steps the accumulators get registers of their own
+    // there, and the allocator brings them to the K loop's through scratch)
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 5; ++b) asm volatile("" : "+v"(acc[a][b]));
+    LC3_ST_LAP(st_g);
+    int kt = 0;
+    if (parked) {                                  // nk >= 8 (host): the K-steps that carry the pieces exist
+      kstep(std::integral_constant<int, 0>{});
+      if constexpr (NPARK > 1) kstep(std::integral_constant<int, 1>{});
+      if constexpr (NPARK > 2) kstep(std::integral_constant<int, 2>{});
+      if constexpr (NPARK > 3) kstep(std::integral_constant<int, 3>{});
+      kt = NPARK;
+    }
+    for (; kt < nk; ++kt) {
+      asm volatile("" : "+s"(kt));
+      kstep(std::integral_constant<int, -1>{});
+    }
+    LC3_ST_LAP(st_k);
+
+    // (the lane's place in the tile is formed HERE, from a lane number counted afresh and opaque to the optimizer: left to itself the
+    // compiler forms every piece's offset and row mask in front of the K loop and carries them through it - 40 registers the K
+    // loop does not have - and a copy of `lane` would be one more)
+    int lane_e = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+    asm volatile("" : "+v"(lane_e));
+    const int frow_e = lane_e & 15, fq_e = lane_e >> 4;
+    lc_add_bias(acc, lds_base + 3 * lc3STG + (ti & 1) * 1024 + (wn * 64 + fq_e * 4) * 4);
+    __builtin_amdgcn_sched_barrier(0);
+    char* const obase = static_cast<char*>(out) + (static_cast<size_t>(m0) * N + n0) * 2;       // uniform
+    const uint32_t ldn = static_cast<uint32_t>(N) * 2;
+    const uint32_t off0 = static_cast<uint32_t>(wm * 80 + frow_e) * ldn + static_cast<uint32_t>(wn * 64 + (fq_e & 1) * 16 + (fq_e & 2) * 4) * 2;
+    const bool full = m0 + lc3BM <= M;
+    parked = full && ti + 1 < my_tiles && !(epi & 256);
+    if (parked) { pend_base = obase; pend_ldn = ldn; }
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr) {
+        if (2 * b + pr < NPARK) {      // (copied on either path: a path that left `park` alone would keep its old value alive through every K loop)
+          park[2 * pr][b < 2 ? b : 0] = acc[2 * pr][b]; park[2 * pr + 1][b < 2 ? b : 0] = acc[2 * pr + 1][b];
+          if (parked) continue;
+        }
+        __builtin_amdgcn_sched_barrier(0);         // one piece's temporaries at a time
+        lc_quickgelu_piece(acc, b, pr);
+        const lc_u32x4_t val = lc_pack_piece<F16O>(acc, b, pr);
+        if (full && !(epi & 256)) *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + static_cast<uint32_t>(b * 16) * ldn + pr * 64)) = val;
+        else if (m0 + wm * 80 + b * 16 + frow_e < M && !(epi & 256)) *reinterpret_cast<lc_u32x4_t*>(obase + (off0 + static_cast<uint32_t>(b * 16) * ldn + pr * 64)) = val;
+      }
+    LC3_ST_LAP(st_e);
+  }
+  LC3_ST_END(sc.S, my_tiles);
+#undef G3_MFMA
+#undef G3_GROUP
+#undef G3_LAST
+#undef G3_REFILL_W
 }
 
 // ---- "lc2q": the 12-wave form on e4m3 operands (the fp8 mode, BASELINE configs[4]) -------------------------------------------------------
@@ -1460,6 +1744,9 @@ static int lc_env_mode() { static const int m = []() { const char* e = getenv("C
 static int g_lc_mode = -1;         // cmh_set_gemm_lc: -1 = environment (CMH_GEMM_LC, default 8 = per-launch route; 0 = the wide kernel only)
 int gemm_lc_mode() { return g_lc_mode < 0 ? lc_env_mode() : g_lc_mode; }
 void gemm_lc_set_mode(int m) { g_lc_mode = m; }
+// CMH_LC3_DGE=0: bias + QuickGELU launches of the 160-row form run gemm_lc3_kernel, not gemm_lc3g_kernel (A/B runs; read at every
+// launch, so that one process can compare the two)
+static bool lc3_dge_enabled() { const char* e = getenv("CMH_LC3_DGE"); return !(e && e[0] == '0' && e[1] == 0); }
 
 // bf16 operands, 16-bit output, the forward epilogues of a transformer block (bias, + QuickGELU, + fp16 residual), N % 256 == 0
 bool gemm_lc_takes(int dt, int N, int K, int epi) {
@@ -1499,7 +1786,12 @@ int launch_gemm_lc(const GemmProblem& a, const GemmProblem* b, int epi, const Ge
   } while (0)
 #define LC_GO_ALL(KERNEL, THREADS) do { if (b) LC_GO_G(KERNEL, THREADS, true); else LC_GO_G(KERNEL, THREADS, false); } while (0)
   static const int abl = []() { const char* e = getenv("CMH_LC_ABL"); return e ? atoi(e) : 0; }();
-  if (p.family == GEMM_LC3) {      // the 160-row 12-wave form
+  if (p.family == GEMM_LC3 && res == 0 && (epi & EPI_BIAS) && (epi & EPI_QUICKGELU) && lc3_dge_enabled()) {
+    // c_fc: two row blocks' QuickGELU under the next tile's MFMAs
+    if (b) { if (f16) LC_GO(gemm_lc3g_kernel, 768, true, true); else LC_GO(gemm_lc3g_kernel, 768, true, false); }
+    else { if (f16) LC_GO(gemm_lc3g_kernel, 768, false, true); else LC_GO(gemm_lc3g_kernel, 768, false, false); }
+    CMH_CHECK_LAUNCH("gemm (lc3g)");
+  } else if (p.family == GEMM_LC3) {      // the 160-row 12-wave form
     LC_GO_ALL(gemm_lc3_kernel, 768);
     CMH_CHECK_LAUNCH("gemm (lc3)");
   } else if (p.family == GEMM_LC2) {
