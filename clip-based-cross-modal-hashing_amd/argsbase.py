@@ -24,6 +24,7 @@ BASE_FLAGS = [
     ("--map-tie-order", str, "reference", "mAP ties: reference = the reference's torch.sort order (up to 524 287 database items); stable = by ascending database index, by counting, any database size (this build)"),
     ("--eval-curves", str2bool, False, "test(): also log P@H<=2 / P@N and store the precision-recall and top-N curves in the .mat (this build)"),
     ("--eval-recall", str2bool, False, "test(): also log Recall@1/5/10 and MedR of the paired query items (image i <-> caption i) and store the rank counts in the .mat (this build)"),
+    ("--eval-codes", str2bool, False, "test(): also log the bit balance, dead / duplicated bits, bit correlations and the image / caption agreement of the database codes and store the tables in the .mat (this build)"),
     ("--eval-graded", str2bool, False, "test(): also log NDCG@N / ACG@N / WAP@N (relevance graded by the number of shared labels) and store them in the .mat (this build)"),
 ]
 

@@ -169,6 +169,8 @@ SIGNATURES = {
     "cmh_soft_topk_masked": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_mask_from_labels": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p]),
     "cmh_mask_from_ids": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p]),
+    "cmh_code_gram_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "cmh_code_gram": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -997,6 +999,33 @@ def mask_from_ids(allow, ids, n, value):
     if int(bad.item()):
         raise NativeError(f"mask_from_ids: an id outside [0, {int(n)})")
     return allow
+
+
+GRAM_BITS_MAX = 256          # include/cmh.h CMH_GRAM_BITS_MAX, CMH_GRAM_CHUNK_MAX: the limits of cmh_code_gram
+GRAM_CHUNK_MAX = 1 << 20     # the most items one workgroup of it owns: the unit its 32-bit partial sums are bounded over
+
+
+def code_gram(a_planes, b_planes, abits, bbits, chunk_items=0):
+    """The integers of the code diagnostics from two packed operands over the same N items (each a (sign, nz) pair of contiguous
+    int32 planes [N, ceil(bits / 32)]; packed labels as (lab, lab), |code| as (nz, nz)) -> (gram int64 [abits, bbits], a_sum,
+    a_abs int64 [abits], b_sum, b_abs int64 [bbits]); gram[i][j] = sum_n a_i(n) b_j(n), exact.  chunk_items: 0 = the plan's
+    choice, else the items per workgroup (a multiple of 64 up to GRAM_CHUNK_MAX)."""
+    (a_s, a_n), (b_s, b_n) = a_planes, b_planes
+    require_gpu(a_s, a_n, b_s, b_n)
+    n, abits, bbits = a_s.shape[0], int(abits), int(bbits)
+    fit("code_gram", (a_s, (n, (abits + 31) // 32)), (a_n, (n, (abits + 31) // 32)), (b_s, (n, (bbits + 31) // 32)),
+        (b_n, (n, (bbits + 31) // 32)))
+    for t in (a_s, a_n, b_s, b_n):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("code_gram: packed operands are contiguous int32 tensors (pack_codes / pack_labels)")
+    dev = a_s.device
+    gram = torch.empty(abits, bbits, dtype=torch.int64, device=dev)
+    sums = [torch.empty(k, dtype=torch.int64, device=dev) for k in (abits, abits, bbits, bbits)]
+    need = lib().cmh_code_gram_workspace_bytes(n, abits, bbits, int(chunk_items))      # 0 outside the limits: the call refuses with the reason
+    ws = workspace(need, dev, "code_gram")
+    check(lib().cmh_code_gram(ptr(a_s), ptr(a_n), ptr(b_s), ptr(b_n), n, abits, bbits, int(chunk_items), ptr(gram), *(ptr(t) for t in sums),
+                              ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_code_gram")
+    return (gram, *sums)
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte

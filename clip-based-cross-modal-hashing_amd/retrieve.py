@@ -55,7 +55,16 @@ filters the search: only the items of the index that carry at least one of the c
 of --no-label (class numbers, comma-separated; the index must hold labels), that are listed in --only-ids FILE and not listed in
 --exclude-ids FILE (one database index per line) are searched; the conditions given combine by AND.  The filters go with --index in
 the neighbour modes (--text / --image, also with --soft, and --codes --index), not with --map, --graded, --radius or --recall.  The
-indices printed are the index's own.  A query with fewer than --k admitted items prints only those it found."""
+indices printed are the index's own.  A query with fewer than --k admitted items prints only those it found.
+
+    python retrieve.py --codes <file>.mat --stats [--stats-out stats.npz]
+    python retrieve.py --index db.npz --stats
+
+prints the code diagnostics (utils/code_stats.py) in place of a search: per modality (r_img, r_txt; with --index the index alone) the
+bit balance, the dead and duplicated bits, the mean and largest |correlation| between two bits with the pair that has it; for the
+.mat's pairing (database image i <-> caption i) the mean agreement of the two codes and the three bits that agree least; with labels
+(r_l, or an index that holds some) per bit the class it tells most about, as bit:class:mutual information.  --stats-out stores
+every array, the integers behind them included, as one .npz.  --stats excludes --map, --radius, --recall, --text and --image."""
 import argparse
 import sys
 
@@ -103,8 +112,19 @@ def parse(argv=None):
     p.add_argument("--no-label", default=None, metavar="C1,C2,...", help="with --index: only items that carry none of these classes")
     p.add_argument("--only-ids", default=None, metavar="FILE", help="with --index: only the database indices listed in FILE, one per line")
     p.add_argument("--exclude-ids", default=None, metavar="FILE", help="with --index: not the database indices listed in FILE, one per line")
+    p.add_argument("--stats", action="store_true", help="print the code diagnostics of the file's database sides (or of --index) in place of a search")
+    p.add_argument("--stats-out", default=None, metavar="FILE", help="with --stats: store every array as FILE (.npz)")
     args = p.parse_args(argv)
     args.ask = getattr(args, "ask", None) or []
+    if args.stats:
+        for flag, given in (("--map", args.map), ("--radius", args.radius is not None), ("--recall", args.recall),
+                            ("--text / --image", bool(args.ask))):
+            if given:
+                p.error(f"--stats and {flag} exclude each other")
+        if args.codes is None and not args.index:
+            p.error("--stats: --codes FILE or --index FILE is required")
+    elif args.stats_out is not None:
+        p.error("--stats-out goes with --stats")
     args.filtered = False
     for flag in FILTERS:
         value = getattr(args, flag[2:].replace("-", "_"))
@@ -139,7 +159,7 @@ def parse(argv=None):
             p.error("--k: at least 1")
     elif args.soft:
         p.error("--soft goes with --text / --image: a soft query is the model's output, a --codes file holds only signs")
-    elif args.codes is None:
+    elif args.codes is None and not args.stats:
         p.error("the following arguments are required: --codes")
     if args.recall:
         for flag, given in (("--radius", args.radius is not None), ("--map", args.map), ("--graded", args.graded), ("--k", args.k is not None)):
@@ -239,6 +259,37 @@ def recall(args, m, q_key, r_key, lo, hi):
     return 0
 
 
+def stats(args):
+    """--stats: the diagnostics of the index, or of both database sides of the .mat and their pairing."""
+    import numpy as np
+    import torch
+
+    from utils import code_stats as S
+    from utils.retrieval import CodeIndex
+    if args.index:
+        sides = {"index": S.code_stats(CodeIndex.load(args.index))}
+    else:
+        import scipy.io as scio
+        m = scio.loadmat(args.codes)
+        labels = torch.from_numpy(m["r_l"]).float() if "r_l" in m else None
+        img, txt = (torch.from_numpy(m[k]).float() if k in m else None for k in ("r_img", "r_txt"))
+        if img is None and txt is None:
+            raise SystemExit(f"--stats: {args.codes} holds neither r_img nor r_txt")
+        paired = img is not None and txt is not None and img.shape[0] == txt.shape[0]
+        sides = {name: S.code_stats(own, labels=labels, paired=other if paired else None)
+                 for name, own, other in (("r_img", img, txt), ("r_txt", txt, img)) if own is not None}
+    out = {}
+    for i, (name, st) in enumerate(sides.items()):
+        if i:                                                      # the pairing is one fact: shown with the first side
+            st = {k: v for k, v in st.items() if k != "bit_agreement"}
+        print("\n".join(S.summary_lines(name, st)))
+        out.update(S.arrays(sides[name], name + "_"))
+    if args.stats_out:
+        with open(args.stats_out, "wb") as f:
+            np.savez(f, **out)
+    return 0
+
+
 def ask(args):
     """--text / --image: encode the questions, search the index, print one block per question."""
     from query import QueryEncoder, check_method
@@ -279,6 +330,8 @@ def main(argv=None):
     args = parse(argv)
     if args.ask:
         return ask(args)
+    if args.stats:
+        return stats(args)
     import scipy.io as scio
     import torch
 

@@ -355,6 +355,8 @@ class TrainBase(object):
             extra = dict(extra or {}, **self._eval_graded(query_img, query_txt, retrieval_img, retrieval_txt))
         if getattr(self.args, "eval_recall", False):
             extra = dict(extra or {}, **self._eval_recall(query_img, query_txt))
+        if getattr(self.args, "eval_codes", False):
+            extra = dict(extra or {}, **self._eval_codes(retrieval_img, retrieval_txt))
         self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
 
@@ -416,6 +418,26 @@ class TrainBase(object):
                     extra[f"recall_mrr_{ties}_{name}"] = m["mrr"]
                 shown.append(f"{ties}: " + ", ".join([f"R@{k}: {float(v):.6f}" for k, v in zip(ks, m["recall"])] + [f"MedR: {m['median_rank']:g}"]))
             self.logger.info(f">>>>>> recall({name}): " + "; ".join(shown))
+        return extra
+
+    def _eval_codes(self, retrieval_img, retrieval_txt):
+        """--eval-codes: the diagnostics of the database codes (utils/code_stats.py): per modality the bit balance, the dead and
+        duplicated bits, the bit correlations and the class / bit tables, and for the pairing (image i <-> caption i) the per-bit
+        agreement.  The log shows one line per modality and one for the pairing; the .mat gets every array as codes_<img|txt>_<name>,
+        the integers behind them included.  Every rank holds all codes (like _map); only the main one writes."""
+        from utils import code_stats as S
+        extra = {}
+        for name, (codes, other) in {"img": (retrieval_img, retrieval_txt), "txt": (retrieval_txt, retrieval_img)}.items():
+            st = S.code_stats(codes, labels=self.retrieval_labels, paired=other)
+            extra.update(S.arrays(st, f"codes_{name}_"))
+            pair = st["max_corr_pair"]
+            self.logger.info(f">>>>>> codes({name}): balance: {st['balance']:.6f}, entropy: {float(st['bit_entropy'].mean()):.6f}, "
+                             f"dead: {st['dead_bits']}, duplicates: {st['duplicate_bits']}, mean|corr|: {st['mean_abs_corr']:.6f}, "
+                             f"max|corr|: {st['max_abs_corr']:.6f}" + (f" at {pair[0]},{pair[1]}" if pair else ""))
+            if name == "img":
+                worst = st["bit_agreement"].argsort(kind="stable")[:3]
+                self.logger.info(f">>>>>> codes(pair): agreement: {st['mean_agreement']:.6f}, distance: {st['pair_distance']:.6f}, "
+                                 "least agreeing bits: " + ", ".join(f"{int(k)}: {st['bit_agreement'][k]:.4f}" for k in worst))
         return extra
 
     def compute_loss(self):

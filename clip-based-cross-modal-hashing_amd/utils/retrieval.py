@@ -801,7 +801,7 @@ class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
     search_soft(u, k) -> soft_topk's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
-    rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's.
+    rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's; stats() -> code_stats'.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
     plane that add() grows geometrically, so many small add()s never make many small shards.  save() / load() keep the packed
     planes and labels as one .npz (data only)."""
@@ -984,6 +984,13 @@ class CodeIndex:
         out = recall_from_counts(counts, ks, ties)
         out["counts"] = counts
         return out
+
+    def stats(self, paired=None):
+        """The code diagnostics of the index (utils/code_stats.py: bit balance, dead and duplicated bits, bit correlations; with
+        labels in the index the class / bit tables) -> code_stats' dict.  paired: the other modality's codes of the same items (a
+        CodeIndex, codes or planes): adds the per-bit agreement and the cross-correlation."""
+        from utils.code_stats import code_stats
+        return code_stats(self, paired=paired)
 
     def duplicates(self, radius=0, max_hits=None):
         """The index searched against itself: for every item the OTHER items within `radius`, as hamming_range's CSR tuple (rel when

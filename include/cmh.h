@@ -643,6 +643,28 @@ int cmh_mask_from_labels(const uint32_t* r_label, const uint32_t* need, int32_t 
                          void* stream);
 int cmh_mask_from_ids(const int32_t* ids, int64_t M, int64_t N, int32_t value, uint64_t* allow, int32_t* bad, void* stream);
 
+/* Code diagnostics (csrc/retrieval_stats.hip): the integers behind bit balance, bit correlation, the agreement of an item's two
+ * codes and the class / bit tables, from the packed planes, without a float copy of the codes.
+ *   Operands A and B hold the same N items: each a pair of planes in cmh_pack_codes' layout, sign and nz u32 [N, ceil(bits / 32)].
+ *   Item n carries a in {-1, 0, +1}^abits (a_i = nz_i ? (sign_i ? +1 : -1) : 0) and b in {-1, 0, +1}^bbits.  A packed label matrix
+ *   (cmh_pack_labels) passed as sign = nz gives entries 0 / 1; a code's nz plane passed as both planes gives |a|.
+ *   gram i64 [abits, bbits]: gram[i][j] = sum_n a_i(n) b_j(n);  a_sum, a_abs i64 [abits] = sum_n a_i, sum_n |a_i|;  b_sum, b_abs
+ *   i64 [bbits] likewise (each of the four may be NULL).  Exact integers; the call WRITES every element of every output it is given.
+ * Bits at and above abits / bbits in a row's last word are ignored, whatever they hold.  1 <= N <= 2^31 - 1 in one call, 1 <= abits,
+ * bbits <= CMH_GRAM_BITS_MAX.  chunk_items: 0 = the plan's choice; else the number of items one workgroup owns, a multiple of 64 up
+ * to CMH_GRAM_CHUNK_MAX (for tests that want many chunks and a ragged tail at a small N; the result does not depend on it).
+ * -1 before any launch: null operands or gram, sizes outside the limits, such a chunk_items, B planes whose rows are read as 8-byte
+ * pairs (an even number of words per row) but are not aligned to 8 bytes (A rows are read word by word); -2: a
+ * workspace below cmh_code_gram_workspace_bytes (0 outside the limits).  The partial sums of a chunk are 32-bit (a chunk holds at
+ * most 2^20 items) and meet in int64 by integer atomics, whose sum does not depend on the order: two calls give equal bytes, on any
+ * stream.  No float arithmetic anywhere. */
+#define CMH_GRAM_BITS_MAX 256
+#define CMH_GRAM_CHUNK_MAX 1048576
+size_t cmh_code_gram_workspace_bytes(int64_t N, int32_t abits, int32_t bbits, int64_t chunk_items);
+int cmh_code_gram(const uint32_t* a_sign, const uint32_t* a_nz, const uint32_t* b_sign, const uint32_t* b_nz, int64_t N, int32_t abits,
+                  int32_t bbits, int64_t chunk_items, int64_t* gram, int64_t* a_sum, int64_t* a_abs, int64_t* b_sum, int64_t* b_abs,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */
