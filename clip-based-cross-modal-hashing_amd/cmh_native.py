@@ -165,6 +165,8 @@ SIGNATURES = {
     "cmh_soft_topk": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
     "cmh_topk_few_masked_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_hamming_topk_few_masked": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
+    "cmh_soft_ap_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "cmh_soft_ap": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_soft_topk_masked_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "cmh_soft_topk_masked": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_mask_from_labels": (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p]),
@@ -905,7 +907,36 @@ def soft_topk(q, r_planes, bits, k):
     return idx, wdist
 
 
-MASK_ANY, MASK_ALL, MASK_NONE = 0, 1, 2      # include/cmh.h CMH_MASK_*: the modes of cmh_mask_from_labels
+def soft_ap(q, r_planes, bits, q_lab, r_lab, k=None):
+    """AP, relevant count and rank sum of every soft query over the WHOLE database by counting (cmh_soft_ap, csrc/retrieval_soft.hip):
+    no ranking, any database up to 2^31 - 1 items in one call.  q = (q_sign, q_mag[, ...]) of soft_query_planes, r_planes = pack_codes',
+    q_lab / r_lab = pack_labels' -> (ap f32 [Q], relevant int32 [Q], rank_sum int64 [Q]): ap over the first k (None: all) items in
+    ascending (wdist, database index), 0 without a relevant item; rank_sum = the sum of the ranks of ALL relevant items.
+    1 <= Q <= SOFT_Q_MAX, bits <= SOFT_BITS_MAX, 1 <= k <= N."""
+    if q_lab is None or r_lab is None:
+        raise NativeError("soft_ap: needs the labels of both sides")
+    (qs, qm), (rs, rn) = q[:2], r_planes
+    require_gpu(qs, qm, rs, rn, q_lab, r_lab)
+    Q, N = qs.shape[0], rs.shape[0]
+    W, LW = (int(bits) + 31) // 32, q_lab.shape[-1]
+    fit("soft_ap", (qs, (Q, W)), (qm, (Q, 4, W)), (rs, (N, W)), (rn, (N, W)), (q_lab, (Q, LW)), (r_lab, (N, LW)))
+    for t in (qs, qm, rs, rn, q_lab, r_lab):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise NativeError("soft_ap: packed operands are contiguous int32 tensors (soft_query_planes / pack_codes / pack_labels)")
+    if k is not None and not 1 <= int(k) <= N:
+        raise NativeError(f"soft_ap: k={k} outside [1, N={N}]")
+    dev = qs.device
+    ap = torch.empty(Q, dtype=torch.float32, device=dev)
+    relevant = torch.empty(Q, dtype=torch.int32, device=dev)
+    rank_sum = torch.empty(Q, dtype=torch.int64, device=dev)
+    need = lib().cmh_soft_ap_workspace_bytes(Q, N, int(bits), LW)    # 0 outside the limits: the call below refuses with the reason
+    ws = workspace(need, dev, "retrieval_soft_ap")
+    check(lib().cmh_soft_ap(ptr(qs), ptr(qm), ptr(rs), ptr(rn), ptr(q_lab), ptr(r_lab), LW, Q, N, int(bits), 0 if k is None else int(k),
+                            ptr(ap), ptr(relevant), ptr(rank_sum), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_soft_ap")
+    return ap, relevant, rank_sum
+
+
+MASK_ANY, MASK_ALL, MASK_NONE = 0, 1, 2     # include/cmh.h CMH_MASK_*: the modes of cmh_mask_from_labels
 
 
 def mask_words(n):

@@ -148,6 +148,23 @@ def row_counts(n_local: int, device) -> list[int] | None:
     return [int(t.item()) for t in every]
 
 
+def gather_float_rows(mine: torch.Tensor, *buffers: torch.Tensor) -> None:
+    """With one process per GPU every rank has filled rows `mine` (int positions, possibly none) of each f32 buffer [n, w_i]: ONE
+    all_gather_rows carries the positions (an int32 column, its bits travelling as an f32 column: nothing computes on them) and
+    the rows of every buffer, and each rank writes all of them into its buffers.  What _gather_code_shards does for codes, for
+    rows that are real numbers (soft queries).  One rank: nothing to do."""
+    if not active():
+        return
+    pos = mine.to(device=buffers[0].device, dtype=torch.int32).reshape(-1)
+    cols = [pos.view(torch.float32).unsqueeze(1)] + [b[pos.long()].float() for b in buffers]
+    widths = [c.shape[1] for c in cols]
+    fused = torch.cat(cols, dim=1).contiguous()
+    parts = torch.split(all_gather_rows(fused, row_counts(pos.numel(), fused.device)), widths, dim=1)
+    at = parts[0].contiguous().view(torch.int32).reshape(-1).long()
+    for buf, rows in zip(buffers, parts[1:]):
+        buf[at] = rows.to(buf.dtype)
+
+
 def gather_query_sharded_ap(ap_local: torch.Tensor, n_query: int) -> torch.Tensor:
     """Per-query APs computed on query shards -> the full [Q] vector in QUERY ORDER on every rank, so the final
     mean is accumulated in the same order as a single-GPU run (the reference sums in query order)."""

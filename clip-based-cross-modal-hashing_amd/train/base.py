@@ -18,7 +18,7 @@ from torch.utils.data import DataLoader
 
 import cmh_native as N
 import dist_utils as du
-from code_rules import first_sign_code, pair_argmax_code, sign_code
+from code_rules import SOFT_RULES, first_sign_code, pair_argmax_code, sign_code, soft_rule
 from streams import AlternatingStreams
 from utils import get_logger, get_summary_writer
 from utils.calc_utils import calc_map_k_matrix as calc_map_k
@@ -33,6 +33,9 @@ class TrainBase(object):
         os.makedirs(args.save_dir, exist_ok=True)
         self._init_writer()
         self.logger.info(self.args)
+        if getattr(args, "eval_soft", False) and args.method not in SOFT_RULES:      # before anything is loaded or encoded
+            raise ValueError(f"--eval-soft: method {args.method} has no soft rule (its code is not the sign of one real-valued "
+                             f"output); the methods that have one: {', '.join(sorted(SOFT_RULES))}")
         self.rank = getattr(args, "rank", rank)   # GPU ID
         self._init_dataset()
         self._init_model()
@@ -183,7 +186,7 @@ class TrainBase(object):
                 dispatch(held)
         pipe.join()
 
-    def _code_loop(self, data_loader, length, encode):
+    def _code_loop(self, data_loader, length, encode, soft=False):
         img_buffer = torch.empty(length, self.args.output_dim, dtype=torch.float).to(self.rank)
         text_buffer = torch.empty(length, self.args.output_dim, dtype=torch.float).to(self.rank)
         seen = []
@@ -202,7 +205,11 @@ class TrainBase(object):
         start_encoder_time = time.time()
         self._pipelined_batches(data_loader, to_device, work)
         encoder_time = time.time() - start_encoder_time
-        self._gather_code_shards(seen, img_buffer, text_buffer)
+        if soft:      # real-valued rows: nothing to pack
+            du.gather_float_rows(torch.cat(seen) if seen else torch.empty(0, dtype=torch.int64, device=img_buffer.device),
+                                 img_buffer, text_buffer)
+        else:
+            self._gather_code_shards(seen, img_buffer, text_buffer)
         return img_buffer, text_buffer, encoder_time
 
     def _gather_code_shards(self, seen, *buffers):
@@ -241,6 +248,12 @@ class TrainBase(object):
     def get_code_DNPH(self, data_loader, length: int):
         return self._code_loop(data_loader, length, lambda i, t, b: (
             first_sign_code(self.model.encode_image(i)), first_sign_code(self.model.encode_text(t))))
+
+    def get_soft(self, data_loader, length: int):
+        """The real-valued output behind the method's code rule (code_rules.soft_rule) of every item, as f32 buffers."""
+        rule = soft_rule(self.args.method)
+        return self._code_loop(data_loader, length, lambda i, t, b: (rule(self.model.encode_image(i)), rule(self.model.encode_text(t))),
+                               soft=True)
 
     def backward(self, loss, *loss_modules):
         """loss.backward(); with one process per GPU also the gradient means over the ranks, each tower's all-reduce queued from
@@ -357,6 +370,8 @@ class TrainBase(object):
             extra = dict(extra or {}, **self._eval_recall(query_img, query_txt))
         if getattr(self.args, "eval_codes", False):
             extra = dict(extra or {}, **self._eval_codes(retrieval_img, retrieval_txt))
+        if getattr(self.args, "eval_soft", False):
+            extra = dict(extra or {}, **self._eval_soft(query_img, query_txt, retrieval_img, retrieval_txt))
         self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
 
@@ -438,6 +453,33 @@ class TrainBase(object):
                 worst = st["bit_agreement"].argsort(kind="stable")[:3]
                 self.logger.info(f">>>>>> codes(pair): agreement: {st['mean_agreement']:.6f}, distance: {st['pair_distance']:.6f}, "
                                  "least agreeing bits: " + ", ".join(f"{int(k)}: {st['bit_agreement'][k]:.4f}" for k in worst))
+        return extra
+
+    def _eval_soft(self, query_img, query_txt, retrieval_img, retrieval_txt):
+        """--eval-soft: what sign() costs the queries.  The query set is encoded once more into the real-valued outputs behind the
+        code rule (get_soft); per direction the mAP over the whole database, the per-query ROC-AUC and P@N of the soft ranking
+        (utils/retrieval.py: soft_mean_average_precision, auc_from_rank_sum, soft_topn_precision) next to the same numbers of the
+        sign codes by mean_average_precision / topn_precision: both sides break ties by database index, so the difference is the
+        soft information alone.  Every rank holds all rows (like _map); only the main one writes."""
+        from utils import retrieval as R
+        soft_img, soft_txt, _ = self.get_soft(self.query_loader, self.args.query_num)
+        sides = {"i2t": (soft_img, query_img, retrieval_txt), "t2i": (soft_txt, query_txt, retrieval_img),
+                 "i2i": (soft_img, query_img, retrieval_img), "t2t": (soft_txt, query_txt, retrieval_txt)}
+        n = retrieval_img.shape[0]
+        topn = tuple(t for t in R.DEFAULT_TOPN if t <= min(n, N.SOFT_K_MAX))
+        shown = topn.index(100) if 100 in topn else len(topn) - 1
+        extra = {"soft_q_img": soft_img.cpu().numpy(), "soft_q_txt": soft_txt.cpu().numpy(), "soft_topn": torch.tensor(topn).numpy()}
+        for name, (u, q, r) in sides.items():
+            mp, ap, relevant, rank_sum = R.soft_mean_average_precision(u, r, self.query_labels, self.retrieval_labels, return_ap=True)
+            auc = R.auc_from_rank_sum(rank_sum, relevant, n)
+            tp = R.soft_topn_precision(u, r, self.query_labels, self.retrieval_labels, topn)[0]
+            b_mp = R.mean_average_precision(q, r, self.query_labels, self.retrieval_labels)
+            b_tp = R.topn_precision(q, r, self.query_labels, self.retrieval_labels, topn)[0]
+            extra.update({f"soft_ap_{name}": ap.cpu().numpy(), f"soft_map_{name}": mp.numpy(), f"soft_auc_{name}": auc.numpy(),
+                          f"soft_rank_sum_{name}": rank_sum.cpu().numpy(), f"soft_relevant_{name}": relevant.cpu().numpy(),
+                          f"soft_topn_precision_{name}": tp.numpy()})
+            self.logger.info(f">>>>>> soft({name}): mAP: {float(mp):.6f} (binary, ties by index: {float(b_mp):.6f}), "
+                             f"AUC: {float(torch.nanmean(auc)):.6f}, P@{topn[shown]}: {float(tp[shown]):.6f} (binary: {float(b_tp[shown]):.6f})")
         return extra
 
     def compute_loss(self):

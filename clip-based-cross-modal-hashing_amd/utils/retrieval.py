@@ -523,14 +523,104 @@ def _soft_search(what, u, rp, bits, k, mask=None):
     return idx, wdist.float() * unit[:, None], wdist
 
 
-def soft_topk(u, rB, k, mask=None):
+def _soft_rel(out, ql, rl):
+    """A soft search's tuple with the hit flags of its idx appended: rel uint8 [Q, k] gathered from the label words of the k results
+    as _search's few route gathers them; 0 in the pad columns (idx = -1) of a masked search."""
+    idx = out[0]
+    rel = ((rl[idx.clamp(min=0).long()] & ql[:, None, :]) != 0).any(-1) & (idx >= 0)
+    return out + (rel.to(torch.uint8),)
+
+
+def _check_soft(what, u, bits, query_L, retrieval_L, both=False):
+    """What a soft call refuses by name before anything touches the GPU -> u as [Q, bits]."""
+    if u.dim() < 2:
+        u = u.unsqueeze(0)
+    if (query_L is None) != (retrieval_L is None):
+        raise N.NativeError(f"{what}: labels on one side only")
+    if both and query_L is None:
+        raise N.NativeError(f"{what}: needs the labels of both sides")
+    if u.shape[1] != bits:
+        raise N.NativeError(f"{what}: {u.shape[1]}-entry soft queries for codes of {bits} bits")
+    if bits > N.SOFT_BITS_MAX:
+        raise N.NativeError(f"{what}: bits={bits} exceeds {N.SOFT_BITS_MAX}, the limit of the soft search (no other route computes its distance)")
+    if query_L is not None and query_L.shape[0] != u.shape[0]:
+        raise N.NativeError(f"{what}: labels of {query_L.shape[0]} queries for {u.shape[0]} soft queries")
+    if not u.is_cuda and not bool(torch.isfinite(u).all()):
+        raise N.NativeError(f"{what}: a soft query must be finite (NaN or Inf in the head's output)")
+    return u
+
+
+def soft_topk(u, rB, k, mask=None, query_L=None, retrieval_L=None):
     """-> (idx int32 [Q, k], dist f32 [Q, k], wdist int32 [Q, k]): the k nearest database codes rB (f32 in {-1, 0, +1}) of every
     soft query u (f32 [Q, K], the head's output before its code rule), by (wdist, database index); dist = wdist * (max|u| / 30).
-    mask=ItemMask: among the items it admits -> (idx, dist, wdist, found int32 [Q])."""
+    mask=ItemMask: among the items it admits -> (idx, dist, wdist, found int32 [Q]).  With the labels of both sides rel uint8 [Q, k]
+    (the result shares a label with the query; 0 in pad columns) is appended as the last element."""
+    if query_L is not None or retrieval_L is not None:
+        u = _check_soft("soft_topk", u, rB.shape[-1], query_L, retrieval_L)
     if mask is not None:
         _check_mask("soft_topk", mask, rB.shape[0], rB.shape[-1], k)
     dev = _dev(u, rB)
-    return _soft_search("soft_topk", u, _codes(rB, dev), rB.shape[-1], k, mask)
+    out = _soft_search("soft_topk", u, _codes(rB, dev), rB.shape[-1], k, mask)
+    return out if query_L is None else _soft_rel(out, _labels(query_L, dev), _labels(retrieval_L, dev))
+
+
+def _soft_map(what, u, rp, bits, ql, rl, k=None):
+    """mAP of soft queries by counting over any number of queries -> (map 0-dim f32 on the GPU, ap f32 [Q], relevant int32 [Q],
+    rank_sum int64 [Q]): blocks of SOFT_Q_MAX queries, one cmh_soft_ap each over the whole database; ONE f32 mean over all the
+    queries in query order (cmh_map_mean)."""
+    n = rp[0].shape[0]
+    if k is not None and not 1 <= int(k) <= n:
+        raise N.NativeError(f"{what}: k={k} outside [1, N={n}]")
+    if u.shape[0] < 1 or n > ITEMS_MAX:
+        raise N.NativeError(f"{what}: Q={u.shape[0]} N={n}")
+    q = N.soft_query_planes(u.to(rp[0].device).float())
+    parts = [N.soft_ap((q[0][a:b], q[1][a:b]), rp, bits, ql[a:b], rl, k) for a, b in _cuts(u.shape[0], N.SOFT_Q_MAX)]
+    ap, relevant, rank_sum = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+    return N.map_mean(ap), ap, relevant, rank_sum
+
+
+def soft_mean_average_precision(u, rB, query_L, retrieval_L, k=None, return_ap=False):
+    """mean_average_precision for soft queries u (f32 [Q, K], the head's output before its code rule): the mAP over the first k
+    (None: all) database codes in ascending (wdist, database index), by counting: no ranking, any number of queries, any database up
+    to 2^31 - 1 items.  -> mAP as a 0-dim f32 CPU tensor; return_ap: (mAP, ap f32 [Q], relevant int32 [Q], rank_sum int64 [Q]) with
+    the three on the GPU: relevant = the query's relevant items, rank_sum = the sum of their ranks (auc_from_rank_sum)."""
+    u = _check_soft("soft_mean_average_precision", u, rB.shape[-1], query_L, retrieval_L, both=True)
+    dev = _dev(u, rB)
+    mp, ap, relevant, rank_sum = _soft_map("soft_mean_average_precision", u, _codes(rB, dev), rB.shape[-1], _labels(query_L, dev),
+                                           _labels(retrieval_L, dev), k)
+    mp = mp.cpu()
+    return (mp, ap, relevant, rank_sum) if return_ap else mp
+
+
+def auc_from_rank_sum(rank_sum, relevant, n):
+    """Per-query ROC-AUC from the rank sums of the relevant items (ties broken by database index like the ranks): U = rank_sum -
+    R (R + 1) / 2 pairs (relevant, other) are in the wrong order; AUC = 1 - U / (R (n - R)).  Integers in Python / int64, one float64
+    division -> float64 CPU tensor [Q]; NaN where R = 0 or R = n."""
+    s = torch.as_tensor(rank_sum).detach().cpu().to(torch.int64).reshape(-1)
+    r = torch.as_tensor(relevant).detach().cpu().to(torch.int64).reshape(-1)
+    n = int(n)
+    if s.numel() != r.numel():
+        raise ValueError(f"auc_from_rank_sum: {s.numel()} rank sums for {r.numel()} relevant counts")
+    out = torch.full((s.numel(),), float("nan"), dtype=torch.float64)
+    for i, (si, ri) in enumerate(zip(s.tolist(), r.tolist())):
+        if not 0 <= ri <= n or (ri and not ri * (ri + 1) // 2 <= si <= ri * (ri + 1) // 2 + ri * (n - ri)):
+            raise ValueError(f"auc_from_rank_sum: rank_sum={si} is not the rank sum of R={ri} among n={n} items")
+        if 0 < ri < n:
+            out[i] = 1.0 - (si - ri * (ri + 1) // 2) / (ri * (n - ri))
+    return out
+
+
+def soft_topn_precision(u, rB, query_L, retrieval_L, topn=DEFAULT_TOPN):
+    """topn_precision for soft queries -> (precision [len(topn)], recall [len(topn)], rel uint8 [Q, max(topn)] on the GPU) of the
+    soft ranking's first N items; max(topn) <= SOFT_K_MAX.  The recall's denominators are cmh_soft_ap's relevant counts."""
+    u = _check_soft("soft_topn_precision", u, rB.shape[-1], query_L, retrieval_L, both=True)
+    topn = [int(t) for t in topn]
+    dev = _dev(u, rB)
+    rp, ql, rl = _codes(rB, dev), _labels(query_L, dev), _labels(retrieval_L, dev)
+    rel = _soft_rel(_soft_search("soft_topn_precision", u, rp, rB.shape[-1], max(topn)), ql, rl)[-1]
+    relevant = _soft_map("soft_topn_precision", u, rp, rB.shape[-1], ql, rl)[2]
+    precision, recall = topn_from_rel(rel, relevant, topn)
+    return precision, recall, rel
 
 
 def _classes(what, query_L, retrieval_L):
@@ -799,7 +889,7 @@ def recall_at_k(qB, rB, targets=None, ks=RECALL_KS, ties="index", shard_items=No
 
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
-    search_soft(u, k) -> soft_topk's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
+    search_soft(u, k) -> soft_topk's; map_soft(u, query_labels) -> soft_mean_average_precision's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's; stats() -> code_stats'.
     Any size up to 2^31 - 1 items: the search runs over shards of `shard_items` rows (None: SHARD_ITEMS), views of ONE buffer per
@@ -950,12 +1040,32 @@ class CodeIndex:
                                     self.shard_items)
         return (idx, dist) if rel is None else (idx, dist, rel)
 
-    def search_soft(self, u, k, mask=None):
+    def search_soft(self, u, k, mask=None, query_labels=None):
         """soft_topk of the soft queries u (f32 [Q, bits], QueryEncoder.encode_*(..., soft=True)) against the index: (idx, dist,
-        wdist).  Any number of queries; bits <= 128 and k <= 4096.  mask=ItemMask: (idx, dist, wdist, found)."""
+        wdist).  Any number of queries; bits <= 128 and k <= 4096.  mask=ItemMask: (idx, dist, wdist, found).  query_labels (the
+        index must hold labels): rel uint8 [Q, k] is appended as the last element."""
         if u.shape[-1] != self.bits:
             raise N.NativeError(f"CodeIndex.search_soft: {u.shape[-1]}-entry soft queries for an index of {self.bits} bits")
-        return _soft_search("CodeIndex.search_soft", u, self.planes, self.bits, k, mask)
+        if query_labels is not None:
+            if self.labels is None:
+                raise N.NativeError("CodeIndex.search_soft: query labels given, but the index has none")
+            if query_labels.dim() != 2 or query_labels.shape[1] != self.classes:
+                raise N.NativeError(f"CodeIndex.search_soft: needs query labels of {self.classes} classes")
+            u = _check_soft("CodeIndex.search_soft", u, self.bits, query_labels, query_labels)
+        out = _soft_search("CodeIndex.search_soft", u, self.planes, self.bits, k, mask)
+        return out if query_labels is None else _soft_rel(out, _labels(query_labels, self.device), self.labels)
+
+    def map_soft(self, u, query_labels, k=None, return_ap=False):
+        """soft_mean_average_precision of the soft queries u against the index (which must hold labels)."""
+        if self.labels is None:
+            raise N.NativeError("CodeIndex.map_soft: the index holds no labels")
+        if query_labels is None or query_labels.dim() != 2 or query_labels.shape[1] != self.classes:
+            raise N.NativeError(f"CodeIndex.map_soft: needs query labels of {self.classes} classes")
+        u = _check_soft("CodeIndex.map_soft", u, self.bits, query_labels, query_labels, both=True)
+        mp, ap, relevant, rank_sum = _soft_map("CodeIndex.map_soft", u, self.planes, self.bits, _labels(query_labels, self.device),
+                                               self.labels, k)
+        mp = mp.cpu()
+        return (mp, ap, relevant, rank_sum) if return_ap else mp
 
     def range_search(self, query_codes, radius, query_labels=None, max_hits=None):
         """hamming_range of the queries against the index: (offsets, idx, dist[, rel with query labels])."""

@@ -627,6 +627,25 @@ size_t cmh_soft_topk_masked_workspace_bytes(int32_t Q, int64_t N, int32_t bits);
 int cmh_soft_topk_masked(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz,
                          const uint64_t* allow, int32_t Q, int64_t N, int32_t bits, int32_t k, int32_t* idx, int32_t* wdist,
                          int32_t* found, void* workspace, size_t workspace_bytes, void* stream);
+/* mAP, relevant counts and rank sums of soft queries over the WHOLE database, by counting (csrc/retrieval_soft.hip).
+ * Distance, quantiser and planes are cmh_soft_topk's; the ranking is by (wdist, database index) ascending; item j is relevant to
+ * query q iff (q_lab[q] & r_lab[j]) != 0 on cmh_pack_labels' words (q_lab u32 [Q, label_words], r_lab u32 [N, label_words]).
+ *   rank(j)    = #{items with wdist < wdist(j)} + #{items with equal wdist and index < j} + 1
+ *   relrank(j) = the same two counts over the relevant items + 1
+ *   relevant i32 [Q] = R, the number of relevant items; total = min(k, R), k = 0 meaning N
+ *   ap f32 [Q]       = (1 / total) sum over the relevant j with relrank(j) <= total of relrank(j) / rank(j); 0 when R = 0.  Every term
+ *                      is the f32 quotient of two f32 numbers, the terms are added in float64 (per lane in index order, the lanes by
+ *                      a fixed tree, the chunks in chunk order), the sum is divided by total in float64 and rounded to f32 once
+ *   rank_sum i64 [Q] = sum over ALL relevant j of rank(j), whatever k: exact, and 1 - (rank_sum - R (R + 1) / 2) / (R (N - R)) is the
+ *                      query's ROC-AUC with ties broken by index
+ * No ranking is formed and nothing of Q x N entries exists; no atomics on any output: two calls give equal bytes, on any stream.
+ * Limits as cmh_soft_topk: 1 <= Q <= CMH_SOFT_Q_MAX, 1 <= N <= 2^31 - 1 in one call, 1 <= bits <= CMH_SOFT_BITS_MAX; label_words >= 1;
+ * k in [1, N] or 0.  -1 before any launch: null operands, sizes outside the limits, misaligned planes or rank_sum; -2: a workspace
+ * below cmh_soft_ap_workspace_bytes (0 outside the limits; it holds 8 bytes per database item beside the histograms). */
+size_t cmh_soft_ap_workspace_bytes(int32_t Q, int64_t N, int32_t bits, int32_t label_words);
+int cmh_soft_ap(const uint32_t* q_sign, const uint32_t* q_mag, const uint32_t* r_sign, const uint32_t* r_nz, const uint32_t* q_lab,
+                const uint32_t* r_lab, int32_t label_words, int32_t Q, int64_t N, int32_t bits, int32_t k, float* ap, int32_t* relevant,
+                int64_t* rank_sum, void* workspace, size_t workspace_bytes, void* stream);
 /* Allow-masks made on the GPU (csrc/retrieval_mask.hip).
  * cmh_mask_from_labels: r_label u32 [N, LW] (cmh_pack_labels, LW = ceil(classes / 32)), need u32 [LW] on the GPU -> allow.  Item j is
  * admitted under mode CMH_MASK_ANY iff (label & need) != 0, CMH_MASK_ALL iff (label & need) == need, CMH_MASK_NONE iff (label &

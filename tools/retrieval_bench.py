@@ -74,6 +74,15 @@ database.  Reported per (shape, Q, k): both times and soft / few, and both works
 pins g queries per workgroup, CMH_SOFT_MIN_CHUNK=c the fewest items of a chunk, in place of the plan's choices, for an A/B of the
 same line.  ONE JSON line.
 
+--soft-map runs the soft-mAP legs instead: utils.retrieval's soft mAP by counting over the whole database (cmh_soft_ap, blocks of 64
+queries; csrc/retrieval_soft.hip) at the two shapes of --shapes, alternating with `binary`, mean_average_precision's counting route
+(cmh_hamming_ap_partial + cmh_ap_finish, kernels of csrc/retrieval.hip) on the SIGN codes of the same queries.  A soft query is
+tanh of the label projection plus noise, the database the sign of the same model.  Same rules (warm-up, legs alternating, device
+events around regions of one call, median [min - max], packed resident operands; the quantiser is inside the soft leg).  The first
+16 queries' AP, R and rank sum are compared with a float64 stable sort on the timed inputs.  Reported per shape: both times, soft /
+binary, both mAPs and the mean AUC.  The stages of one call (relevance words, histogram pass, totals, prefixes, bases, rank pass,
+finish) are separate kernels: a kernel trace of this leg gives the time of each.  One JSON line per shape.
+
 --masked runs the filtered-search legs instead: cmh_hamming_topk_few_masked (the allow-mask in the walk: one 64-bit word per 64
 items) on both databases of --few at Q = 1, 64 and k = 10, 1000 under random masks that admit a share 1.0 / 0.5 / 0.1 / 0.01 of the
 items, against (b) `few`, the unmasked cmh_hamming_topk_few on the same operands (at share 1.0 the difference is the price of the
@@ -572,6 +581,63 @@ def soft_legs(args):
         raise SystemExit("the soft search disagrees with the few-query search on queries whose weights are all 15")
 
 
+def soft_map_legs(args):
+    import torch
+    import cmh_native as N
+    import utils.retrieval as R
+    dev = torch.device("cuda:0")
+    for name in args.shapes:
+        Q, n, K, C = SHAPES[name]
+        g = torch.Generator(device=dev).manual_seed(1)
+        rL = (torch.rand(n, C, generator=g, device=dev) < 0.1).float()
+        qL = (torch.rand(Q, C, generator=g, device=dev) < 0.1).float()
+        rL[:, 0] = 1.0                                            # as map_legs: every query has relevant items, not every pair is relevant
+        qL[:, 0] = 1.0
+        qL[:, 0][::7] = 0.0
+        rL[:, 0][::3] = 0.0
+        Wm = torch.randn(C, K, generator=g, device=dev)
+        mk = lambda lab: torch.tanh(0.5 * (lab @ Wm) + 0.5 * torch.randn(lab.shape[0], K, generator=g, device=dev) + 1e-3)
+        u, rB = mk(qL), torch.sign(mk(rL))
+        qp, rp, ql, rl = N.pack_codes(torch.sign(u)), N.pack_codes(rB), N.pack_labels(qL), N.pack_labels(rL)
+
+        def binary():
+            s, counts = N.hamming_ap_partial(qp, rp, K, ql, rl, want_counts=True)
+            return N.ap_finish(s, counts, K)
+
+        legs = {"soft_map": (1, lambda: R._soft_map("bench", u, rp, K, ql, rl)), "binary": (args.reps, binary)}
+        mp, ap, relevant, rank_sum = legs["soft_map"][1]()        # warm-up, and the outputs on the timed inputs
+        b_mp, _ = binary()
+        rows = 16
+        qs, qm, _, _ = N.soft_query_planes(u[:rows].contiguous())
+        w = torch.zeros(rows, K, device=dev, dtype=torch.float64)
+        for i in range(K):
+            bit = ((qm[:, :, i // 32] >> (i % 32)) & 1).double() @ torch.tensor([1.0, 2.0, 4.0, 8.0], device=dev, dtype=torch.float64)
+            w[:, i] = bit * (2.0 * ((qs[:, i // 32] >> (i % 32)) & 1).double() - 1.0)
+        order = torch.sort(w.abs().sum(1, keepdim=True) - w @ rB.double().T, dim=1, stable=True)[1]
+        hits = ((qL[:rows] @ rL.T) > 0).gather(1, order)
+        del order
+        pos = torch.arange(1, n + 1, device=dev, dtype=torch.float64)
+        want = ((hits.cumsum(1).double() / pos) * hits).sum(1) / hits.sum(1).clamp(min=1)
+        d_ap = float((ap[:rows].double() - want).abs().max())
+        exact = bool(torch.equal(relevant[:rows].long(), hits.sum(1))) and \
+            bool(torch.equal(rank_sum[:rows], (hits * torch.arange(1, n + 1, device=dev)).sum(1)))
+        auc = R.auc_from_rank_sum(rank_sum, relevant, n)
+        del hits, pos, want
+        torch.cuda.synchronize()
+        line = {"tool": "retrieval_bench", "leg": "soft_map", "shape": name, "Q": Q, "N": n, "bits": K, "classes": C, "regions": REGIONS,
+                "blocks": len(R._cuts(Q, N.SOFT_Q_MAX)), "map_soft": float(mp), "map_binary": float(b_mp),
+                "mean_auc": float(torch.nanmean(auc)), "max_ap_diff_vs_float64_sort": d_ap, "integers_equal": exact,
+                "outputs_equal": exact and d_ap <= 2.4e-7,
+                "workspace_mib": round(N.lib().cmh_soft_ap_workspace_bytes(min(Q, N.SOFT_Q_MAX), n, K, ql.shape[1]) / 2 ** 20, 2),
+                "ms": _timed(legs, REGIONS)}
+        line["ms"]["soft_map"]["soft_over_binary"] = round(line["ms"]["soft_map"]["median"] / line["ms"]["binary"]["median"], 2)
+        line["ms"]["soft_map"]["per_block"] = round(line["ms"]["soft_map"]["median"] / line["blocks"], 4)
+        _emit(args, line)
+        if not line["outputs_equal"]:
+            raise SystemExit(f"{name}: the soft mAP by counting disagrees with the float64 AP on a stable sort")
+        del u, rB, qp, rp, ql, rl, legs
+
+
 MASKED_SHARES = (1.0, 0.5, 0.1, 0.01)
 
 
@@ -650,6 +716,7 @@ def main():
     ap.add_argument("--rank", action="store_true", help="run the target-rank legs (see above) instead of the others")
     ap.add_argument("--few", action="store_true", help="run the few-query legs (see above) instead of the others")
     ap.add_argument("--soft", action="store_true", help="run the soft-query legs (see above) instead of the others")
+    ap.add_argument("--soft-map", action="store_true", help="run the soft-mAP legs (see above) instead of the others")
     ap.add_argument("--masked", action="store_true", help="run the filtered-search legs (see above) instead of the others")
     args = ap.parse_args()
     import torch
@@ -668,6 +735,8 @@ def main():
         return few_legs(args)
     if args.soft:
         return soft_legs(args)
+    if args.soft_map:
+        return soft_map_legs(args)
     if args.masked:
         return masked_legs(args)
     dev = torch.device("cuda:0")

@@ -5,7 +5,9 @@ is indexed (utils.retrieval.CodeIndex) and the query side asks it twice, image -
   soft     CodeIndex.search_soft(head outputs, k)    the weighted distance of csrc/retrieval_soft.hip, ties by database index
 Per (bits, direction, kind): P@10, mAP@50 (AP@50 = the mean of the precisions at the relevant positions among the first 50, 0 when
 there is none; relevance = a shared label, labels gathered from idx on the host) and the mean size of the tie group at the 10th
-place (database items at exactly the 10th neighbour's distance, counted inside the first min(N, 4096) results).  ONE JSON line.
+place (database items at exactly the 10th neighbour's distance, counted inside the first min(N, 4096) results); and over the WHOLE
+database, by counting, the project's headline metric: mAP = CodeIndex.map (binary) / CodeIndex.map_soft (soft), both with ties by
+database index, and for the soft ranking the mean per-query ROC-AUC (auc_from_rank_sum).  ONE JSON line.
 
     python tools/soft_quality.py [--epochs 6] [--bits 16 32 64] [--out FILE]
 
@@ -41,7 +43,7 @@ def one(bits, args, clip_file):
     import dataset.synthetic as ds
     import main
     from code_rules import sign_code
-    from utils.retrieval import CodeIndex
+    from utils.retrieval import CodeIndex, auc_from_rank_sum
     ds.SOT, ds.EOT = 510, 511                                      # the tiny CLIP's vocabulary
     ds.SyntheticPairs.signal = 2.0
     run = tempfile.mkdtemp(prefix="cmh_soft_quality_")
@@ -63,10 +65,14 @@ def one(bits, args, clip_file):
     k = min(r_img.shape[0], 4096)
     out = {"queries": q_img.shape[0], "database": r_img.shape[0], "k": k}
     for name, u, r in (("i2t", q_img, r_txt), ("t2i", q_txt, r_img)):
-        index = CodeIndex(sign_code(r))
+        index = CodeIndex(sign_code(r), rL)
         out[name] = {"distinct_database_codes": int(torch.unique(sign_code(r), dim=0).shape[0]),
-                     "binary": metrics(*index.search(sign_code(u), k), qL, rL),
+                     "binary": metrics(*index.search(sign_code(u), k)[:2], qL, rL),
                      "soft": metrics(*index.search_soft(u, k)[:2], qL, rL)}
+        mp, _, relevant, rank_sum = index.map_soft(u, qL, return_ap=True)
+        out[name]["binary"]["mAP"] = round(float(index.map(sign_code(u), qL)), 4)
+        out[name]["soft"]["mAP"] = round(float(mp), 4)
+        out[name]["soft"]["AUC"] = round(float(torch.nanmean(auc_from_rank_sum(rank_sum, relevant, index.size))), 4)
     return out
 
 
