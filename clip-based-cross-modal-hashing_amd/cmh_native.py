@@ -1432,6 +1432,15 @@ def assign_rows(emb, rows, return_col=False):
 
 
 # ------------------------------------------------------------------------------------------ optimiser
+def bf16_copy_of(p):
+    """the encoder's bf16 GEMM copy of a parameter (model/base/model.py::_gemm_w) if it has one the fused step can rewrite - bf16,
+    contiguous, of p's size, on p's device - else None: anything else hung on `_cmh_bf16` is left alone and never stamped current"""
+    copy = getattr(p, "_cmh_bf16", None)
+    if copy is None or copy.dtype != torch.bfloat16 or copy.numel() != p.numel() or copy.device != p.device or not copy.is_contiguous():
+        return None
+    return copy
+
+
 def bert_adam_step(entries, b1, b2, eps):
     """One fused BertAdam step over `entries` = [(param, grad, next_m, next_v, lr_scheduled, weight_decay, max_grad_norm)]
     (all f32, contiguous, on one GPU).  Updates param / next_m / next_v in place and, like clip_grad_norm_, the clipped grad."""
@@ -1445,10 +1454,7 @@ def bert_adam_step(entries, b1, b2, eps):
         for t in (p, g, m, v):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
                 raise NativeError("bert_adam_step: tensors must be contiguous f32 of one size")
-        # the encoder's bf16 GEMM copy of this parameter (model/base/model.py::_gemm_w), if one exists: the step rewrites it
-        copy = getattr(p, "_cmh_bf16", None)
-        if copy is not None and (copy.numel() != p.numel() or copy.device != p.device or copy.dtype != torch.bfloat16):
-            copy = None
+        copy = bf16_copy_of(p)
         arr[i] = AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(wd), float(mx),
                             None if copy is None else copy.data_ptr())
         total += p.numel()

@@ -75,7 +75,9 @@ __device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v
   if (clip) g = __fmul_rn(g, coef);
   m = __fmaf_rn(g, omb1, __fmul_rn(m, b1));
   v = __fadd_rn(__fmul_rn(v, b2), __fmul_rn(__fmul_rn(omb2, g), g));
-  float upd = __fdiv_rn(m, __fadd_rn(__fsqrt_rn(v), eps));
+  // sqrtf, not __fsqrt_rn: the latter is the hardware's approximate v_sqrt_f32 (1 ulp) in this toolchain, and one step in about a
+  // thousand then lands one ulp off the reference's; sqrtf and `/` are the correctly rounded expansions (hipcc's default)
+  float upd = __fdiv_rn(m, __fadd_rn(sqrtf(v), eps));
   if (wd > 0.f) upd = __fadd_rn(upd, __fmul_rn(wd, p));
   p = __fadd_rn(p, -__fmul_rn(lr, upd));
 }

@@ -122,7 +122,7 @@ def _gemm_w(p: torch.Tensor, dt: int, keep: list, transpose: bool = False) -> to
         # the bf16 copy lives on the parameter: the fused BertAdam step rewrites it together with the f32 values (cmh_adam_tensor.
         # p_bf16) and stamps the version it is current for, so a training step pays no cast pass over the weights
         t = getattr(p, "_cmh_bf16", None)
-        if t is None or t.device != p.device or t.numel() != p.numel() or getattr(p, "_cmh_bf16_version", None) != (p.data_ptr(), p._version):
+        if N.bf16_copy_of(p) is None or getattr(p, "_cmh_bf16_version", None) != (p.data_ptr(), p._version):
             t = N.cast_bf16(p.detach().reshape(p.shape[0], -1))
             p._cmh_bf16, p._cmh_bf16_version = t, (p.data_ptr(), p._version)
         keep.append(t)

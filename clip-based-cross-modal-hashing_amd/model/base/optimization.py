@@ -105,6 +105,6 @@ class BertAdam(Optimizer):
             # the kernel wrote through raw pointers: tell autograd / the weight caches (model/base/model.py::_key)
             torch._C._increment_version([t for p, g, *_ in entries for t in (p, g)])
             for p, *_ in entries:       # bf16 GEMM copies rewritten by the kernel are current for the new version
-                if getattr(p, "_cmh_bf16", None) is not None:
+                if N.bf16_copy_of(p) is not None:       # (one the step refused to write - wrong size or type - stays stale)
                     p._cmh_bf16_version = (p.data_ptr(), p._version)
         return loss
