@@ -26,6 +26,7 @@ BASE_FLAGS = [
     ("--eval-recall", str2bool, False, "test(): also log Recall@1/5/10 and MedR of the paired query items (image i <-> caption i) and store the rank counts in the .mat (this build)"),
     ("--eval-codes", str2bool, False, "test(): also log the bit balance, dead / duplicated bits, bit correlations and the image / caption agreement of the database codes and store the tables in the .mat (this build)"),
     ("--eval-soft", str2bool, False, "test(): also encode the queries' real-valued outputs and log mAP / AUC / P@100 of the soft ranking next to the sign codes' (ties by index on both sides), and store the per-query arrays in the .mat; methods with a soft rule only (this build)"),
+    ("--eval-buckets", str2bool, False, "test(): also log, per database side, the distinct codes, the singletons, the largest bucket and the collision probability, and store the bucket occupancy tables in the .mat; a method whose codes hold zeros logs why it has none (this build)"),
     ("--eval-graded", str2bool, False, "test(): also log NDCG@N / ACG@N / WAP@N (relevance graded by the number of shared labels) and store them in the .mat (this build)"),
 ]
 

@@ -173,6 +173,12 @@ SIGNATURES = {
     "cmh_mask_from_ids": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p]),
     "cmh_code_gram_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "cmh_code_gram": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_code_sort_workspace_bytes": (_sz, [_i64, _i32]),
+    "cmh_code_sort": (C.c_int, [_p, _i64, _i32, _p, _p, _sz, _p]),
+    "cmh_code_bucket_count": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _sz, _p]),
+    "cmh_code_bucket_fill": (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p]),
+    "cmh_bucket_probe_count": (C.c_int, [_p, _i32, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "cmh_bucket_probe_fill": (C.c_int, [_p, _i32, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -1057,6 +1063,102 @@ def code_gram(a_planes, b_planes, abits, bbits, chunk_items=0):
     check(lib().cmh_code_gram(ptr(a_s), ptr(a_n), ptr(b_s), ptr(b_n), n, abits, bbits, int(chunk_items), ptr(gram), *(ptr(t) for t in sums),
                               ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_code_gram")
     return (gram, *sums)
+
+
+SORT_TILE = 2048             # include/cmh.h CMH_SORT_TILE: sorted positions per workgroup of a pass of cmh_code_sort
+BUCKET_BITS_MAX = 128        # ... CMH_BUCKET_BITS_MAX, CMH_BUCKET_RADIUS_MAX: the limits of cmh_bucket_probe_count / _fill
+BUCKET_RADIUS_MAX = 2
+SORT_BITS_MAX = 2048         # the longest code cmh_code_sort takes: pack_codes' limit
+
+
+def _sign_plane(what, sign, bits):
+    """A contiguous int32 sign plane [n, ceil(bits / 32)] on the GPU -> (n, bits)."""
+    require_gpu(sign)
+    bits = int(bits)
+    if sign.dtype != torch.int32 or sign.dim() != 2 or not sign.is_contiguous():
+        raise NativeError(f"{what}: the sign plane is a contiguous int32 tensor [n, words] (pack_codes)")
+    if not 1 <= bits <= SORT_BITS_MAX:
+        raise NativeError(f"{what}: bits={bits} outside [1, {SORT_BITS_MAX}]")
+    fit(what, (sign, (sign.shape[0], (bits + 31) // 32)))
+    return sign.shape[0], bits
+
+
+def code_sort(sign, bits):
+    """-> order int32 [n]: the item indices in ascending key order (a row's sign words cut to `bits` bits, word W - 1 most
+    significant), equal keys by ascending index (stable)."""
+    n, bits = _sign_plane("code_sort", sign, bits)
+    dev = sign.device
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_code_sort_workspace_bytes(n, bits), dev, "code_sort")      # 0 outside the limits: the call refuses with the reason
+    check(lib().cmh_code_sort(ptr(sign), n, bits, ptr(order), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_code_sort")
+    return order
+
+
+def code_buckets(sign, order, bits):
+    """The groups of equal keys of a sorted plane -> (starts int32 [U + 1], codes int32 [U, W]): bucket b holds the items
+    order[starts[b]:starts[b + 1]], all of key codes[b]; the buckets ascend by key.  U comes to the host: the one read."""
+    n, bits = _sign_plane("code_buckets", sign, bits)
+    dev = sign.device
+    fit("code_buckets", (order, (n,)))
+    if order.dtype != torch.int32 or not order.is_contiguous() or order.device != dev:
+        raise NativeError("code_buckets: order is code_sort's contiguous int32 tensor [n] on the plane's device")
+    head = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = workspace(lib().cmh_code_sort_workspace_bytes(n, bits), dev, "code_sort")
+    check(lib().cmh_code_bucket_count(ptr(sign), ptr(order), n, bits, ptr(head), ptr(count), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_code_bucket_count")
+    U = int(count)
+    starts = torch.empty(U + 1, dtype=torch.int32, device=dev)
+    codes = torch.empty(U, sign.shape[1], dtype=torch.int32, device=dev)
+    check(lib().cmh_code_bucket_fill(ptr(sign), ptr(order), ptr(head), n, bits, U, ptr(starts), ptr(codes), stream_ptr(dev)),
+          "cmh_code_bucket_fill")
+    return starts, codes
+
+
+def _probe_operands(what, q_sign, codes, starts, bits, radius):
+    require_gpu(q_sign, codes, starts)
+    bits, radius = int(bits), int(radius)
+    if not 1 <= bits <= BUCKET_BITS_MAX:
+        raise NativeError(f"{what}: bits={bits} outside [1, BUCKET_BITS_MAX = {BUCKET_BITS_MAX}]")
+    if not 0 <= radius <= BUCKET_RADIUS_MAX:
+        raise NativeError(f"{what}: radius={radius} outside [0, BUCKET_RADIUS_MAX = {BUCKET_RADIUS_MAX}]")
+    W = (bits + 31) // 32
+    Q, U = q_sign.shape[0], codes.shape[0]
+    if not 1 <= Q <= QUERIES_MAX:
+        raise NativeError(f"{what}: Q={Q} outside [1, {QUERIES_MAX}] per call")
+    fit(what, (q_sign, (Q, W)), (codes, (U, W)), (starts, (U + 1,)))
+    for t in (q_sign, codes, starts):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != q_sign.device:
+            raise NativeError(f"{what}: query planes, codes and starts are contiguous int32 tensors on one device")
+    return Q, U, bits, radius
+
+
+def bucket_probe_count(q_sign, codes, starts, bits, radius):
+    """-> (n_hit_buckets int32 [Q], n_hit_items int64 [Q]): of each query's probes (its key with at most `radius` bits flipped) the
+    ones that are a bucket's key, and the items of those buckets."""
+    Q, U, bits, radius = _probe_operands("bucket_probe_count", q_sign, codes, starts, bits, radius)
+    dev = q_sign.device
+    nb = torch.empty(Q, dtype=torch.int32, device=dev)
+    ni = torch.empty(Q, dtype=torch.int64, device=dev)
+    check(lib().cmh_bucket_probe_count(ptr(q_sign), Q, ptr(codes), ptr(starts), U, bits, radius, ptr(nb), ptr(ni), stream_ptr(dev)),
+          "cmh_bucket_probe_count")
+    return nb, ni
+
+
+def bucket_probe_fill(q_sign, codes, starts, bits, radius, bucket_offsets, total):
+    """bucket_offsets int64 [Q + 1] = the exclusive prefix sum of bucket_probe_count's n_hit_buckets, total = its last entry (>= 1)
+    -> (hit_bucket int32 [total], hit_dist int32 [total]): query q's hits from bucket_offsets[q] on, in probe order."""
+    Q, U, bits, radius = _probe_operands("bucket_probe_fill", q_sign, codes, starts, bits, radius)
+    dev = q_sign.device
+    total = int(total)
+    if bucket_offsets.dtype != torch.int64 or tuple(bucket_offsets.shape) != (Q + 1,) or not bucket_offsets.is_contiguous() \
+            or bucket_offsets.device != dev:
+        raise NativeError("bucket_probe_fill: bucket_offsets is a contiguous int64 tensor [Q + 1] on the operands' device")
+    hb = torch.empty(total, dtype=torch.int32, device=dev)
+    hd = torch.empty(total, dtype=torch.int32, device=dev)
+    check(lib().cmh_bucket_probe_fill(ptr(q_sign), Q, ptr(codes), ptr(starts), U, bits, radius, ptr(bucket_offsets), total, ptr(hb),
+                                      ptr(hd), stream_ptr(dev)), "cmh_bucket_probe_fill")
+    return hb, hd
 
 
 GRADE_CLASSES_MAX = 255      # a grade is one byte

@@ -64,7 +64,22 @@ prints the code diagnostics (utils/code_stats.py) in place of a search: per moda
 bit balance, the dead and duplicated bits, the mean and largest |correlation| between two bits with the pair that has it; for the
 .mat's pairing (database image i <-> caption i) the mean agreement of the two codes and the three bits that agree least; with labels
 (r_l, or an index that holds some) per bit the class it tells most about, as bit:class:mutual information.  --stats-out stores
-every array, the integers behind them included, as one .npz.  --stats excludes --map, --radius, --recall, --text and --image."""
+every array, the integers behind them included, as one .npz.  --stats excludes --map, --radius, --recall, --text and --image.
+
+    python retrieve.py --codes <file>.mat --direction i2t --lookup 2 [--queries a:b]
+
+prints what --radius 2 prints, line for line, from the index's bucket table (CodeIndex.lookup: the database items grouped by equal
+code, each query's ball found by key at a cost that does not grow with the database).  R is 0, 1 or 2 whole bits; codes up to 128
+bit without zero entries (--radius takes the others).  --lookup excludes --radius, --k, --map, --graded, --recall, --soft, --stats
+and the filters.
+
+    python retrieve.py --codes <file>.mat --bucket-stats [--stats-out buckets.npz]
+    python retrieve.py --index db.npz --bucket-stats
+
+prints, per database side (r_img, r_txt; with --index the index alone), how the items spread over their distinct codes: the distinct
+codes, the singletons, the largest bucket, the share of the possible codes in use, the colliding pairs, the collision probability
+and the entropy of the bucket sizes.  --stats-out stores the numbers and the (size, buckets) occupancy tables; with --stats both
+reports are printed and stored.  The exclusions are those of --stats."""
 import argparse
 import sys
 
@@ -113,17 +128,29 @@ def parse(argv=None):
     p.add_argument("--only-ids", default=None, metavar="FILE", help="with --index: only the database indices listed in FILE, one per line")
     p.add_argument("--exclude-ids", default=None, metavar="FILE", help="with --index: not the database indices listed in FILE, one per line")
     p.add_argument("--stats", action="store_true", help="print the code diagnostics of the file's database sides (or of --index) in place of a search")
-    p.add_argument("--stats-out", default=None, metavar="FILE", help="with --stats: store every array as FILE (.npz)")
+    p.add_argument("--stats-out", default=None, metavar="FILE", help="with --stats / --bucket-stats: store every array as FILE (.npz)")
+    p.add_argument("--lookup", type=int, default=None, metavar="R", help="print every database item within R = 0, 1 or 2 bits of each query, as --radius does, from the index's bucket table")
+    p.add_argument("--bucket-stats", action="store_true", help="print how the items of the file's database sides (or of --index) spread over their distinct codes in place of a search")
     args = p.parse_args(argv)
     args.ask = getattr(args, "ask", None) or []
-    if args.stats:
+    if args.lookup is not None:
+        for flag, given in (("--radius", args.radius is not None), ("--k", args.k is not None), ("--map", args.map), ("--graded", args.graded),
+                            ("--recall", args.recall), ("--soft", args.soft), ("--stats", args.stats), ("--bucket-stats", args.bucket_stats),
+                            ("--text / --image", bool(args.ask))) + tuple((f, getattr(args, f[2:].replace("-", "_")) is not None) for f in FILTERS):
+            if given:
+                p.error(f"--lookup and {flag} exclude each other")
+        if not 0 <= args.lookup <= 2:
+            p.error(f"--lookup {args.lookup}: 0, 1 or 2 bits (--radius takes any radius)")
+    for name, on in (("--stats", args.stats), ("--bucket-stats", args.bucket_stats)):
+        if not on:
+            continue
         for flag, given in (("--map", args.map), ("--radius", args.radius is not None), ("--recall", args.recall),
                             ("--text / --image", bool(args.ask))):
             if given:
-                p.error(f"--stats and {flag} exclude each other")
+                p.error(f"{name} and {flag} exclude each other")
         if args.codes is None and not args.index:
-            p.error("--stats: --codes FILE or --index FILE is required")
-    elif args.stats_out is not None:
+            p.error(f"{name}: --codes FILE or --index FILE is required")
+    if args.stats_out is not None and not (args.stats or args.bucket_stats):
         p.error("--stats-out goes with --stats")
     args.filtered = False
     for flag in FILTERS:
@@ -159,7 +186,7 @@ def parse(argv=None):
             p.error("--k: at least 1")
     elif args.soft:
         p.error("--soft goes with --text / --image: a soft query is the model's output, a --codes file holds only signs")
-    elif args.codes is None and not args.stats:
+    elif args.codes is None and not (args.stats or args.bucket_stats):
         p.error("the following arguments are required: --codes")
     if args.recall:
         for flag, given in (("--radius", args.radius is not None), ("--map", args.map), ("--graded", args.graded), ("--k", args.k is not None)):
@@ -260,14 +287,18 @@ def recall(args, m, q_key, r_key, lo, hi):
 
 
 def stats(args):
-    """--stats: the diagnostics of the index, or of both database sides of the .mat and their pairing."""
+    """--stats: the diagnostics of the index, or of both database sides of the .mat and their pairing.  --bucket-stats: how the
+    items of the same sides spread over their distinct codes."""
     import numpy as np
     import torch
 
     from utils import code_stats as S
     from utils.retrieval import CodeIndex
+    sides, indexes = {}, {}
     if args.index:
-        sides = {"index": S.code_stats(CodeIndex.load(args.index))}
+        indexes["index"] = CodeIndex.load(args.index)
+        if args.stats:
+            sides = {"index": S.code_stats(indexes["index"])}
     else:
         import scipy.io as scio
         m = scio.loadmat(args.codes)
@@ -276,14 +307,26 @@ def stats(args):
         if img is None and txt is None:
             raise SystemExit(f"--stats: {args.codes} holds neither r_img nor r_txt")
         paired = img is not None and txt is not None and img.shape[0] == txt.shape[0]
-        sides = {name: S.code_stats(own, labels=labels, paired=other if paired else None)
-                 for name, own, other in (("r_img", img, txt), ("r_txt", txt, img)) if own is not None}
+        if args.stats:
+            sides = {name: S.code_stats(own, labels=labels, paired=other if paired else None)
+                     for name, own, other in (("r_img", img, txt), ("r_txt", txt, img)) if own is not None}
+        if args.bucket_stats:
+            indexes = {name: CodeIndex(own) for name, own in (("r_img", img), ("r_txt", txt)) if own is not None}
     out = {}
     for i, (name, st) in enumerate(sides.items()):
         if i:                                                      # the pairing is one fact: shown with the first side
             st = {k: v for k, v in st.items() if k != "bit_agreement"}
         print("\n".join(S.summary_lines(name, st)))
         out.update(S.arrays(sides[name], name + "_"))
+    if args.bucket_stats:
+        import cmh_native as N
+        for name, index in indexes.items():
+            try:
+                st = index.bucket_stats()
+            except N.NativeError as e:                             # codes with zeros have no bucket table
+                raise SystemExit(f"--bucket-stats: {name}: {e}")
+            print("\n".join(S.bucket_summary_lines(name, st)))
+            out.update({f"{name}_bucket_{k}": np.asarray(v) for k, v in st.items()})
     if args.stats_out:
         with open(args.stats_out, "wb") as f:
             np.savez(f, **out)
@@ -330,7 +373,7 @@ def main(argv=None):
     args = parse(argv)
     if args.ask:
         return ask(args)
-    if args.stats:
+    if args.stats or args.bucket_stats:
         return stats(args)
     import scipy.io as scio
     import torch
@@ -360,8 +403,15 @@ def main(argv=None):
         return 0
     if hi == lo:
         return 0
-    if args.radius is not None:
-        out = [t.cpu().numpy() for t in index.range_search(queries, args.radius, labels, max_hits=args.max_hits)]
+    if args.radius is not None or args.lookup is not None:
+        if args.lookup is not None:
+            import cmh_native as N
+            try:
+                out = [t.cpu().numpy() for t in index.lookup(queries, args.lookup, labels)]
+            except N.NativeError as e:                             # zeros in the codes, more than 128 bits: --radius takes them
+                raise SystemExit(f"--lookup: {e}")
+        else:
+            out = [t.cpu().numpy() for t in index.range_search(queries, args.radius, labels, max_hits=args.max_hits)]
         for i in range(hi - lo):
             cols = [f"{out[1][j]}:{out[2][j]:g}" + (f":{out[3][j]}" if len(out) == 4 else "") for j in range(out[0][i], out[0][i + 1])]
             print(" ".join([str(lo + i)] + cols))

@@ -372,6 +372,8 @@ class TrainBase(object):
             extra = dict(extra or {}, **self._eval_codes(retrieval_img, retrieval_txt))
         if getattr(self.args, "eval_soft", False):
             extra = dict(extra or {}, **self._eval_soft(query_img, query_txt, retrieval_img, retrieval_txt))
+        if getattr(self.args, "eval_buckets", False):
+            extra = dict(extra or {}, **self._eval_buckets(retrieval_img, retrieval_txt))
         self.save_mat(query_img, query_txt, retrieval_img, retrieval_txt, mode_name=mode_name, extra=extra)
         self.logger.info(">>>>>> save all data!")
 
@@ -453,6 +455,25 @@ class TrainBase(object):
                 worst = st["bit_agreement"].argsort(kind="stable")[:3]
                 self.logger.info(f">>>>>> codes(pair): agreement: {st['mean_agreement']:.6f}, distance: {st['pair_distance']:.6f}, "
                                  "least agreeing bits: " + ", ".join(f"{int(k)}: {st['bit_agreement'][k]:.4f}" for k in worst))
+        return extra
+
+    def _eval_buckets(self, retrieval_img, retrieval_txt):
+        """--eval-buckets: how the database items spread over their distinct codes (CodeIndex.bucket_stats: the items grouped by
+        equal code on the GPU).  The log shows one line per modality; the .mat gets the (size, buckets) occupancy table and the
+        integers as buckets_<img|txt>_<name>.  Codes with zeros have no bucket table: the refusal is logged and the run goes on.
+        Every rank holds all codes (like _map); only the main one writes."""
+        from utils import retrieval as R
+        extra = {}
+        for name, codes in {"img": retrieval_img, "txt": retrieval_txt}.items():
+            try:
+                st = R.CodeIndex(codes).bucket_stats()
+            except N.NativeError as e:
+                self.logger.info(f">>>>>> buckets({name}): none: {e}")
+                continue
+            extra.update({f"buckets_{name}_{k}": st[k] for k in ("occupancy", "distinct", "singletons", "largest", "collisions",
+                                                                 "collision_probability")})
+            self.logger.info(f">>>>>> buckets({name}): distinct: {st['distinct']}, singletons: {st['singletons']}, largest: {st['largest']}, "
+                             f"collision probability: {st['collision_probability']:.6e}")
         return extra
 
     def _eval_soft(self, query_img, query_txt, retrieval_img, retrieval_txt):

@@ -180,6 +180,41 @@ def code_stats(codes, labels=None, paired=None, chunk_items=0):
     return stats_from_counts(n, gram.cpu(), s.cpu(), ab.cpu(), pair=pair, classes=classes)
 
 
+def bucket_stats_from_sizes(n, sizes, size_counts, bits=None):
+    """How n items spread over their distinct codes, from the occupancy table of a BucketTable: sizes = the distinct bucket sizes,
+    size_counts = how many buckets have each (torch.unique(counts, return_counts=True): at most about sqrt(2 n) rows).  Pure host
+    arithmetic; the counts are exact Python integers -> a dict:
+      distinct, singletons, largest; collisions = sum n_b (n_b - 1) / 2, the pairs of items with equal codes;
+      collision_probability = sum n_b^2 / n^2, the chance that two items drawn with replacement share a code;
+      bucket_entropy_bits = -sum (n_b / n) log2 (n_b / n) (float64); occupancy = int64 [rows, 2] (size, buckets), ascending by size;
+      with bits (the code length): bits and used_share = distinct / min(n, 2^bits), the share of the codes the items could occupy
+      that they do."""
+    n = int(n)
+    table = sorted(zip((int(s) for s in _ints(sizes)), (int(c) for c in _ints(size_counts))))
+    if n < 1 or not table or any(s < 1 or c < 1 for s, c in table) or sum(s * c for s, c in table) != n \
+            or len({s for s, _ in table}) != len(table):
+        raise ValueError(f"bucket_stats_from_sizes: (size, buckets) rows of distinct sizes >= 1 that add up to n={n}")
+    shares = np.array([s for s, _ in table], dtype=np.float64) / n
+    out = {"n": n, "distinct": sum(c for _, c in table), "singletons": sum(c for s, c in table if s == 1), "largest": table[-1][0],
+           "collisions": sum(c * (s * (s - 1) // 2) for s, c in table),
+           "collision_probability": sum(c * s * s for s, c in table) / (n * n),
+           "bucket_entropy_bits": float(-(np.array([c for _, c in table], dtype=np.float64) * _plogp(shares)).sum()),
+           "occupancy": np.array(table, dtype=np.int64).reshape(-1, 2)}
+    if bits is not None:
+        out["bits"] = int(bits)
+        out["used_share"] = out["distinct"] / min(n, 1 << int(bits))
+    return out
+
+
+def bucket_summary_lines(name, st):
+    """The bucket statistics as lines of text (retrieve.py --bucket-stats)."""
+    top = st["occupancy"][-3:][::-1]
+    return [f"{name}: {st['n']} items x {st['bits']} bit  distinct {st['distinct']}  singletons {st['singletons']}  largest {st['largest']}  "
+            f"used share {st['used_share']:.6f}",
+            f"{name}: collisions {st['collisions']}  collision probability {st['collision_probability']:.6e}  "
+            f"bucket entropy {st['bucket_entropy_bits']:.6f} bit  largest sizes " + " ".join(f"{int(s)}x{int(c)}" for s, c in top)]
+
+
 def summary_lines(name, st, top=3):
     """The short table of retrieve.py --stats and the trainer's log, as lines of text."""
     pair = st["max_corr_pair"]

@@ -887,8 +887,128 @@ def recall_at_k(qB, rB, targets=None, ks=RECALL_KS, ties="index", shard_items=No
     return out
 
 
+def _nz_mask(bits, dev):
+    """int32 [W]: the nz words of a code without zeros - every word full, the last one up to `bits`."""
+    mask = torch.full(((bits + 31) // 32,), -1, dtype=torch.int32, device=dev)
+    if bits % 32:
+        mask[-1] = (1 << (bits % 32)) - 1
+    return mask
+
+
+def _no_zeros(what, whose, planes, bits):
+    """The table's keys are sign words: a code with a 0 entry (a cleared nz bit inside `bits`) has no key and is refused."""
+    mask = _nz_mask(bits, planes[1].device)
+    if not bool(((planes[1] & mask) == mask).all()):
+        raise N.NativeError(f"{what}: {whose} with a 0 entry: the bucket table holds codes in {{-1, +1}} only (hamming_range / "
+                            "range_search take codes with zeros)")
+
+
+def _check_lookup(what, bits, query_bits, radius):
+    """What a lookup refuses by name before anything is packed, built or launched."""
+    if query_bits != bits:
+        raise N.NativeError(f"{what}: {query_bits}-bit queries for an index of {bits} bits")
+    if bits > N.BUCKET_BITS_MAX:
+        raise N.NativeError(f"{what}: {bits}-bit codes exceed BUCKET_BITS_MAX = {N.BUCKET_BITS_MAX} (range_search takes them)")
+    if isinstance(radius, bool) or radius != int(radius) or not 0 <= int(radius) <= N.BUCKET_RADIUS_MAX:
+        raise N.NativeError(f"{what}: radius={radius} is not a whole number of bits in [0, BUCKET_RADIUS_MAX = {N.BUCKET_RADIUS_MAX}] "
+                            "(range_search takes any radius)")
+
+
+class BucketTable:
+    """The items of a packed database grouped by equal code (csrc/retrieval_buckets.hip), all on the GPU:
+      order  int32 [n]      the item indices sorted by key (the sign words cut to `bits`, word W - 1 most significant), equal keys
+                            by ascending index
+      starts int32 [U + 1]  bucket b = order[starts[b]:starts[b + 1]]
+      codes  int32 [U, W]   the key of each bucket, ascending
+      bits, n, n_buckets (= U)
+    build(planes, bits) sorts once (cmh_code_sort, cmh_code_bucket_count / _fill; U is the one number read back);
+    lookup(...) answers "the items whose code is the query's with at most `radius` bits flipped" at a cost that does not grow
+    with n.  Codes in {-1, +1} only."""
+
+    def __init__(self, order, starts, codes, bits, n):
+        self.order, self.starts, self.codes, self.bits, self.n, self.n_buckets = order, starts, codes, int(bits), int(n), codes.shape[0]
+
+    @classmethod
+    def build(cls, planes, bits):
+        """planes: (sign, nz) of pack_codes, int32 [n, ceil(bits / 32)] on the GPU, any n up to 2^31 - 1."""
+        bits = int(bits)
+        sign, nz = planes
+        N.fit("BucketTable.build", (nz, tuple(sign.shape)))
+        _no_zeros("BucketTable.build", "a database code", planes, bits)
+        sign = sign.contiguous()
+        order = N.code_sort(sign, bits)
+        starts, codes = N.code_buckets(sign, order, bits)
+        return cls(order, starts, codes, bits, sign.shape[0])
+
+    def counts(self):
+        """int32 [U]: the items of each bucket."""
+        return self.starts[1:] - self.starts[:-1]
+
+    def lookup(self, query_codes, radius=0, query_labels=None, retrieval_L=None):
+        """-> hamming_range's tuple (offsets int64 [Q+1], idx int32 [T], dist f32 [T][, rel uint8 [T] with labels]): every item
+        within `radius` (0, 1 or 2 whole bits) of every query, by (distance, database index) inside a query's list.  query_codes
+        f32 [Q, bits] in {-1, +1}; query_labels / retrieval_L: multi-hot [Q, C] / [n, C], both or neither."""
+        if (query_labels is None) != (retrieval_L is None):
+            raise N.NativeError("BucketTable.lookup: labels on one side only")
+        if retrieval_L is not None and retrieval_L.shape[0] != self.n:
+            raise N.NativeError(f"BucketTable.lookup: labels of {retrieval_L.shape[0]} items for a table of {self.n}")
+        _check_lookup("BucketTable.lookup", self.bits, query_codes.shape[-1], radius)
+        dev = self.order.device
+        return self._lookup("BucketTable.lookup", _codes(query_codes, dev), radius, _labels(query_labels, dev), _labels(retrieval_L, dev))
+
+    def _lookup(self, what, qp, radius, ql, rl):
+        """The packed form: qp = the queries' planes, ql / rl = packed labels or None -> (offsets, idx, dist, rel or None).  Per block
+        of queries: count pass, cumsum, the two totals read back, fill pass, the hit buckets expanded to items through `order`,
+        and for radius >= 1 one stable sort on (query, distance, item)."""
+        radius = int(radius)
+        _no_zeros(what, "a query", qp, self.bits)
+        dev = self.order.device
+        Q = qp[0].shape[0]
+        parts = []
+        for cut in _cuts(Q, N.QUERIES_MAX):
+            qs = _rows(qp[0], cut, Q).contiguous()
+            nq = cut[1] - cut[0]
+            n_buckets, n_items = N.bucket_probe_count(qs, self.codes, self.starts, self.bits, radius)
+            boff = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(n_buckets, 0, out=boff[1:])
+            off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(n_items, 0, out=off[1:])
+            TB, T = torch.stack((boff[-1], off[-1])).tolist()
+            if T > ITEMS_MAX:
+                raise N.NativeError(f"{what}: T={T} hits exceed {ITEMS_MAX}")
+            if TB == 0:
+                idx, dist = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+                query = torch.empty(0, dtype=torch.int64, device=dev)
+            else:
+                bucket, bdist = N.bucket_probe_fill(qs, self.codes, self.starts, self.bits, radius, boff, TB)
+                bucket = bucket.long()
+                first = self.starts[bucket].long()
+                size = self.starts[bucket + 1].long() - first
+                hit = torch.repeat_interleave(torch.arange(TB, device=dev), size, output_size=T)      # the hit each item came from
+                begin = torch.cumsum(size, 0) - size
+                idx = self.order[first[hit] + (torch.arange(T, device=dev) - begin[hit])]
+                dist = bdist[hit]
+                query = torch.repeat_interleave(torch.arange(nq, device=dev), n_buckets.long(), output_size=TB)[hit]
+                if radius >= 1:      # a distance level is many buckets: merge them by index (radius 0: one bucket, already ascending)
+                    by = torch.sort(((query * (N.BUCKET_RADIUS_MAX + 1) + dist) << 31) + idx, stable=True)[1]
+                    idx, dist, query = idx[by], dist[by], query[by]
+                dist = dist.to(torch.float32)
+            rel = None if ql is None else ((_rows(ql, cut, Q)[query] & rl[idx.long()]) != 0).any(-1).to(torch.uint8)
+            parts.append((off, idx, dist, rel))
+        if len(parts) == 1:
+            return parts[0]
+        offs, base = [parts[0][0]], parts[0][0][-1]
+        for p in parts[1:]:
+            offs.append(p[0][1:] + base)
+            base = offs[-1][-1]
+        return (torch.cat(offs),) + tuple(None if ts[0] is None else torch.cat(ts) for ts in zip(*[p[1:] for p in parts]))
+
+
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
+    buckets() -> the BucketTable of the index (built on first use, dropped by add()); lookup(query_codes, radius) -> the radius
+    search of range_search through that table (radius 0, 1, 2; codes without zeros); bucket_stats() -> how the items spread over
+    their distinct codes;
     search_soft(u, k) -> soft_topk's; map_soft(u, query_labels) -> soft_mean_average_precision's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's; stats() -> code_stats'.
@@ -935,6 +1055,7 @@ class CodeIndex:
         if lab is not None:
             self._lab = grown(self._lab, lab)
         self.size += new
+        self._buckets = None                                       # derived from the items: buckets() builds it again
 
     def add(self, codes, labels=None):
         """Appends items behind the ones the index holds (their indices: size, size + 1, ...); only the new rows are packed."""
@@ -1078,6 +1199,32 @@ class CodeIndex:
                                      radius_half_units(radius, self.bits), ql, self.labels if ql is not None else None,
                                      self.shard_items, max_hits)
         return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+    def buckets(self):
+        """The BucketTable of the index as it is now: built on first use and kept until add() changes the items.  Derived data:
+        save() does not store it.  An index with a code that holds a 0 is refused."""
+        if self._buckets is None:
+            self._buckets = BucketTable.build(self.planes, self.bits)
+        return self._buckets
+
+    def lookup(self, query_codes, radius=0, query_labels=None):
+        """range_search(query_codes, radius) through the bucket table: the same tuple, element for element, for radius 0, 1 or 2
+        whole bits, codes up to 128 bit and no 0 entry on either side; at a cost that does not grow with the index."""
+        if query_labels is not None and self.labels is None:
+            raise N.NativeError("CodeIndex.lookup: query labels given, but the index has none")
+        _check_lookup("CodeIndex.lookup", self.bits, query_codes.shape[-1], radius)
+        ql = _labels(query_labels, self.device)
+        off, idx, dist, rel = self.buckets()._lookup("CodeIndex.lookup", _codes(query_codes, self.device), radius, ql,
+                                                     self.labels if ql is not None else None)
+        return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+    def bucket_stats(self):
+        """How the items spread over their distinct codes (utils/code_stats.py::bucket_stats_from_sizes): distinct, singletons,
+        largest, collisions, collision_probability, bucket_entropy_bits, used_share and the (size, buckets) occupancy table.  Only
+        the table of distinct bucket sizes comes to the host."""
+        from utils.code_stats import bucket_stats_from_sizes
+        sizes, size_counts = torch.unique(self.buckets().counts(), return_counts=True)
+        return bucket_stats_from_sizes(self.size, sizes.cpu(), size_counts.cpu(), bits=self.bits)
 
     def rank_of(self, query_codes, targets):
         """target_counts of the queries against the index: int64 [Q, G, 3] = (less, ties_before, ties) of item targets[q, g]."""

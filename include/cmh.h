@@ -684,6 +684,50 @@ int cmh_code_gram(const uint32_t* a_sign, const uint32_t* a_nz, const uint32_t* 
                   int32_t bbits, int64_t chunk_items, int64_t* gram, int64_t* a_sum, int64_t* a_abs, int64_t* b_sum, int64_t* b_abs,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Hash-table lookup (csrc/retrieval_buckets.hip): the items of a database grouped by equal code, and the groups
+ * found by key, at a cost that does not grow with N.  The table holds codes in {-1, +1} (every nz bit inside `bits` set: the caller
+ * checks, no entry point reads an nz plane); for those, calc_hammingDist (utils/calc_utils.py:8-13) of two codes is the number of
+ * sign bits that differ, a whole number, which is the distance the probes reproduce.
+ *   The KEY of a row is its W = ceil(bits / 32) sign words with the bits at and behind `bits` cleared (whatever the plane holds
+ *   there), compared as one W-word unsigned integer, word W - 1 most significant.
+ * cmh_code_sort: sign u32 [N, W] -> order i32 [N], the item indices in ascending key order, equal keys by ascending item index
+ * (stable).  A least-significant-digit radix sort, ceil(bits / 8) passes of 8 bits; a pass in which every key has the same digit is
+ * skipped on the device.  `sign` is only read.  1 <= N <= 2^31 - 1, 1 <= bits <= 2048.
+ * cmh_code_bucket_count: sorted position i is a bucket head when its key differs from position i - 1's (position 0 always is);
+ * head i32 [N] = the inclusive scan of those marks (position i lies in bucket head[i] - 1), *n_buckets (i64 on the GPU, aligned
+ * to 8 bytes) = U, the number of heads = of distinct codes.  The caller reads this one number to size the next call's outputs.
+ * Workspace: cmh_code_sort_workspace_bytes(N, bits), as cmh_code_sort.
+ * cmh_code_bucket_fill: starts i32 [U + 1], bucket b is order[starts[b] : starts[b + 1]] (starts[U] = N); codes i32 [U, W] = the
+ * key of each bucket, ascending.  1 <= U <= N.  No workspace.
+ * cmh_bucket_probe_count / cmh_bucket_probe_fill: q_sign u32 [Q, W] (keys are cut to `bits` in the kernel) against a table's codes
+ * and starts.  A query's probes, in this order: its own key; the key with bit i flipped, i ascending (radius >= 1); with bits
+ * i < j flipped, (i, j) in lexicographic order (radius 2): P = 1 + bits + bits (bits - 1) / 2 keys at radius 2, each found or not
+ * by one binary search over codes.
+ *   count: n_hit_buckets i32 [Q] = the probes that are a bucket's key, n_hit_items i64 [Q] (aligned to 8 bytes) = the items of
+ *          those buckets = the query's Hamming ball
+ *   fill:  bucket_offsets i64 [Q + 1] = the exclusive prefix sum of n_hit_buckets (aligned to 8 bytes); hit_bucket, hit_dist i32
+ *          [capacity], capacity >= bucket_offsets[Q]: query q's hits at bucket_offsets[q] .., in probe order (so ascending distance),
+ *          as (bucket, whole-bit distance 0 / 1 / 2).  Nothing at or behind min(bucket_offsets[q + 1], capacity) is written.
+ * 1 <= Q <= 65535 per call, 1 <= U <= 2^31 - 1, 1 <= bits <= CMH_BUCKET_BITS_MAX, 0 <= radius <= CMH_BUCKET_RADIUS_MAX.  Both
+ * passes search; nothing per probe is kept between them.
+ * All six: -1 before any launch for null operands, sizes outside the limits (the message names the limit), misaligned 64-bit
+ * operands; -2 for a workspace below cmh_code_sort_workspace_bytes (0 outside the limits).  No atomics on any output, every output
+ * word written once, no kernel waits for another workgroup: two calls give equal bytes, on any stream. */
+#define CMH_SORT_TILE 2048          /* sorted positions per workgroup of a pass: the unit whose edges the tests aim at */
+#define CMH_BUCKET_BITS_MAX 128
+#define CMH_BUCKET_RADIUS_MAX 2
+size_t cmh_code_sort_workspace_bytes(int64_t N, int32_t bits);
+int cmh_code_sort(const uint32_t* sign, int64_t N, int32_t bits, int32_t* order, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_code_bucket_count(const uint32_t* sign, const int32_t* order, int64_t N, int32_t bits, int32_t* head, int64_t* n_buckets,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int cmh_code_bucket_fill(const uint32_t* sign, const int32_t* order, const int32_t* head, int64_t N, int32_t bits, int64_t U,
+                         int32_t* starts, int32_t* codes, void* stream);
+int cmh_bucket_probe_count(const uint32_t* q_sign, int32_t Q, const int32_t* codes, const int32_t* starts, int64_t U, int32_t bits,
+                           int32_t radius, int32_t* n_hit_buckets, int64_t* n_hit_items, void* stream);
+int cmh_bucket_probe_fill(const uint32_t* q_sign, int32_t Q, const int32_t* codes, const int32_t* starts, int64_t U, int32_t bits,
+                          int32_t radius, const int64_t* bucket_offsets, int64_t capacity, int32_t* hit_bucket, int32_t* hit_dist,
+                          void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */
