@@ -179,6 +179,10 @@ SIGNATURES = {
     "cmh_code_bucket_fill": (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p]),
     "cmh_bucket_probe_count": (C.c_int, [_p, _i32, _p, _p, _i64, _i32, _i32, _p, _p, _p]),
     "cmh_bucket_probe_fill": (C.c_int, [_p, _i32, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "cmh_mih_build_workspace_bytes": (_sz, [_i64, _i32]),
+    "cmh_mih_build": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _sz, _p]),
+    "cmh_mih_count": (C.c_int, [_p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
+    "cmh_mih_fill": (C.c_int, [_p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -1161,7 +1165,77 @@ def bucket_probe_fill(q_sign, codes, starts, bits, radius, bucket_offsets, total
     return hb, hd
 
 
-GRADE_CLASSES_MAX = 255      # a grade is one byte
+MIH_SUB_BITS = 16            # include/cmh.h CMH_MIH_SUB_BITS, CMH_MIH_SUB_RADIUS_MAX: the substring width of cmh_mih_* and the
+MIH_SUB_RADIUS_MAX = 2       # largest radius a substring is probed at (csrc/retrieval_mih.hip)
+MIH_KEYS = 1 << MIH_SUB_BITS
+
+
+def mih_substrings(bits):
+    """m = ceil(bits / MIH_SUB_BITS): the substrings (tables) of a code."""
+    return (int(bits) + MIH_SUB_BITS - 1) // MIH_SUB_BITS
+
+
+def _mih_table(what, sign, bits):
+    n, bits = _sign_plane(what, sign, bits)
+    if bits > BUCKET_BITS_MAX:
+        raise NativeError(f"{what}: bits={bits} outside [1, BUCKET_BITS_MAX = {BUCKET_BITS_MAX}]")
+    return n, bits, mih_substrings(bits)
+
+
+def mih_build(sign, bits):
+    """-> (order int32 [m, n], starts int32 [m, 65537]), m = ceil(bits / 16): per 16-bit substring of the sign plane the item indices
+    by ascending (key, index), and the first position of every key; bucket `key` of table j is order[j, starts[j, key]:starts[j, key + 1]]."""
+    n, bits, m = _mih_table("mih_build", sign, bits)
+    dev = sign.device
+    order = torch.empty(m, n, dtype=torch.int32, device=dev)
+    starts = torch.empty(m, MIH_KEYS + 1, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_mih_build_workspace_bytes(n, bits), dev, "code_sort")
+    check(lib().cmh_mih_build(ptr(sign), n, bits, ptr(order), ptr(starts), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_mih_build")
+    return order, starts
+
+
+def _mih_operands(what, q_sign, db_sign, bits, radius, order, starts):
+    require_gpu(q_sign, db_sign, order, starts)
+    n, bits, m = _mih_table(what, db_sign, bits)
+    radius = int(radius)
+    if not 0 <= radius <= (MIH_SUB_RADIUS_MAX + 1) * m - 1:
+        raise NativeError(f"{what}: radius={radius} outside [0, {(MIH_SUB_RADIUS_MAX + 1) * m - 1}] at {bits} bits")
+    Q = q_sign.shape[0]
+    if not 1 <= Q <= QUERIES_MAX:
+        raise NativeError(f"{what}: Q={Q} outside [1, {QUERIES_MAX}] per call")
+    fit(what, (q_sign, (Q, db_sign.shape[1])), (order, (m, n)), (starts, (m, MIH_KEYS + 1)))
+    for t in (q_sign, order, starts):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != db_sign.device:
+            raise NativeError(f"{what}: query planes, order and starts are contiguous int32 tensors on the database's device")
+    return Q, n, bits, radius
+
+
+def mih_count(q_sign, db_sign, bits, radius, order, starts):
+    """-> n_hits int32 [Q]: the database items within `radius` whole bits of each query, found through mih_build's tables."""
+    Q, n, bits, radius = _mih_operands("mih_count", q_sign, db_sign, bits, radius, order, starts)
+    dev = q_sign.device
+    hits = torch.empty(Q, dtype=torch.int32, device=dev)
+    check(lib().cmh_mih_count(ptr(q_sign), Q, ptr(db_sign), n, bits, radius, ptr(order), ptr(starts), ptr(hits), stream_ptr(dev)),
+          "cmh_mih_count")
+    return hits
+
+
+def mih_fill(q_sign, db_sign, bits, radius, order, starts, offsets, total):
+    """offsets int64 [Q + 1] = the exclusive prefix sum of mih_count's n_hits, total = its last entry (>= 1) -> (idx int32 [total],
+    dist int32 [total]): query q's items from offsets[q] on, each once, in the order of the kernel's walk (the same on every call)."""
+    Q, n, bits, radius = _mih_operands("mih_fill", q_sign, db_sign, bits, radius, order, starts)
+    dev = q_sign.device
+    total = int(total)
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (Q + 1,) or not offsets.is_contiguous() or offsets.device != dev:
+        raise NativeError("mih_fill: offsets is a contiguous int64 tensor [Q + 1] on the operands' device")
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.int32, device=dev)
+    check(lib().cmh_mih_fill(ptr(q_sign), Q, ptr(db_sign), n, bits, radius, ptr(order), ptr(starts), ptr(offsets), total, ptr(idx),
+                             ptr(dist), stream_ptr(dev)), "cmh_mih_fill")
+    return idx, dist
+
+
+GRADE_CLASSES_MAX = 255     # a grade is one byte
 TOPK_MAX = 524287            # include/cmh.h CMH_TOPK_MAX: the largest N (and k) of the four retrieval entry points
 QUERIES_MAX = 65535          # ... and their largest Q
 

@@ -10,20 +10,9 @@
 // distance of utils/calc_utils.py:8-13 in whole units.
 //
 // The sort is a least-significant-digit radix sort over ceil(bits / 8) digits of 8 bits (the digits behind them are zero for every
-// key: no pass).  A pass is, over tiles of kSortTile positions of the current index buffer,
-//   sort_hist_kernel      counts[bin][tile]: per-tile digit histogram (LDS counters), stored bin-major, so that
-//   scan (three launches) ONE exclusive scan of the flat array is, at [bin][tile], the first destination of the tile's keys of that bin
-//   sort_decide_kernel    all N keys in one bin?  Then the pass would be the identity permutation: it is skipped, and the next pass
-//                         reads the same buffer.  Writes skip[pass] and src[pass + 1] in the workspace; the host reads nothing
-//   sort_scatter_kernel   the stable scatter.  A wave owns kSortTile / 4 consecutive positions and takes them 64 at a time in order;
-//                         a key's rank among the wave's keys of its digit = the wave's LDS counter of that digit before the round +
-//                         the number of lower lanes with the same digit (eight ballots: the lanes that agree with me on every digit
-//                         bit).  After the rounds the counters hold the wave's histogram; a 256-thread step turns them into the
-//                         wave's first destination per digit (the tile's, from the scan, plus the waves before it).  No atomics.
-// Two index buffers in the workspace ping-pong (the first pass reads no buffer: position = item); cmh_code_sort's last launch copies
-// the final one to `order`.  No kernel waits for another workgroup: every scan over workgroups is block sums / a one-workgroup scan
-// of the sums / apply, as separate launches.  Every loop is bounded by an argument, every access checked against N, U or Q, every
-// offset 64-bit.  Every output word is written once, without atomics: two calls give equal bytes, on any stream.
+// key: no pass): the passes and the scans of retrieval_sort.h, which the substring tables of retrieval_mih.hip share.  No kernel
+// waits for another workgroup.  Every loop is bounded by an argument, every access checked against N, U or Q, every offset 64-bit.
+// Every output word is written once, without atomics: two calls give equal bytes, on any stream.
 //
 // The probes.  A query has P = 1 + bits + bits (bits - 1) / 2 candidate keys within radius 2: itself, one flipped bit i ascending,
 // pairs (i, j), i < j, in lexicographic order (radius 0 / 1: the first 1 / 1 + bits of them).  One workgroup owns a query and takes
@@ -32,218 +21,14 @@
 // + the hits of the waves before it in this round (LDS) + the hits of the lower lanes (ballot): the list is in probe order on every
 // run.  Distinct probes are distinct keys, so a bucket is hit at most once per query.  The count pass and the fill pass both
 // search; nothing per probe is stored.
-#include "cmh_common.h"
+#include "retrieval_sort.h"
 
 namespace cmh {
 namespace {
 
-constexpr int kBktMaxWords = 64;           // bits <= 2048: what cmh_pack_codes takes
-constexpr int kSortTile = CMH_SORT_TILE;   // positions per workgroup of a pass
-constexpr int kSortThreads = 256;
-constexpr int kSortWaves = kSortThreads / 64;
-constexpr int kSortRounds = kSortTile / kSortThreads;      // 64-position rounds of a wave, positions per thread
-constexpr int kSortMaxPasses = 4 * kBktMaxWords;
-constexpr int kScanBlock = 2048;           // elements per workgroup of the scans
-constexpr int kScanPer = kScanBlock / 256;
 constexpr int kProbeThreads = 1024;
 constexpr int kProbeWaves = kProbeThreads / 64;
 constexpr int kProbeWords = CMH_BUCKET_BITS_MAX / 32;
-
-static_assert(kSortTile == kSortThreads * kSortRounds && kSortTile / kSortWaves <= (1 << 24), "a rank shares a word with its 8-bit digit");
-
-// src[p]: the buffer pass p reads (-1: none, position = item; 0 / 1: the workspace's buffers); skip[p]: pass p moves nothing
-struct SortState {
-  int src[kSortMaxPasses + 1];
-  int skip[kSortMaxPasses];
-};
-
-struct SortArgs {
-  const uint32_t* sign;
-  int64_t N;
-  int W, bits, T;                // words per row, code length, tiles
-  int32_t* buf[2];
-  uint32_t* counts;              // [256][T], scanned in place
-  SortState* state;
-};
-
-__device__ __forceinline__ uint32_t word_mask(int w, int bits) {
-  const int rest = bits - 32 * w;
-  return rest >= 32 ? 0xffffffffu : rest <= 0 ? 0u : ((1u << rest) - 1u);
-}
-
-__device__ __forceinline__ uint32_t key_word(const uint32_t* __restrict__ sign, int64_t item, int W, int w, int bits) {
-  return sign[static_cast<size_t>(item) * W + w] & word_mask(w, bits);
-}
-
-// item at position pos of the pass's source (pos < N checked by the caller)
-__device__ __forceinline__ int32_t sort_item(const SortArgs& a, int src, int64_t pos) {
-  return src < 0 ? static_cast<int32_t>(pos) : a.buf[src][pos];
-}
-
-__device__ __forceinline__ uint32_t sort_digit(const SortArgs& a, int32_t item, int pass) {
-  return (key_word(a.sign, item, a.W, pass >> 2, a.bits) >> (8 * (pass & 3))) & 0xffu;
-}
-
-__global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(SortArgs a, int pass) {
-  __shared__ uint32_t hist[256];
-  const int tid = threadIdx.x, tile = blockIdx.x;
-  const int src = a.state->src[pass];
-  hist[tid] = 0;
-  __syncthreads();
-  const int64_t base = static_cast<int64_t>(tile) * kSortTile;
-#pragma unroll
-  for (int r = 0; r < kSortRounds; ++r) {
-    const int64_t pos = base + r * kSortThreads + tid;
-    if (pos < a.N) atomicAdd(&hist[sort_digit(a, sort_item(a, src, pos), pass)], 1u);      // LDS counters: an integer sum
-  }
-  __syncthreads();
-  if (tile < a.T) a.counts[static_cast<size_t>(tid) * a.T + tile] = hist[tid];
-}
-
-// ---- exclusive / inclusive scan of a uint32 array over workgroups: sums, scan of the sums, apply --------------------------------
-__device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
-// inclusive prefix of v over the 256 threads of the workgroup; *total = the sum.  wsum: 4 words of LDS
-__device__ __forceinline__ uint32_t block_inclusive(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_inclusive(v, lane);
-  __syncthreads();                        // (wsum may still be read from the caller's previous round)
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t s = wsum[w];
-    before += w < wave ? s : 0u;
-    all += s;
-  }
-  *total = all;
-  return v + before;
-}
-
-__global__ __launch_bounds__(256) void scan_block_sums_kernel(const uint32_t* __restrict__ data, int64_t n, uint32_t* __restrict__ sums,
-                                                              int64_t nb) {
-  __shared__ uint32_t wsum[4];
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * kScanBlock;
-  uint32_t v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    const int64_t i = base + j * 256 + threadIdx.x;
-    if (i < n) v += data[i];
-  }
-  uint32_t total;
-  block_inclusive(v, wsum, &total);
-  if (threadIdx.x == 0 && blockIdx.x < nb) sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[nb] -> its exclusive scan in place; the total to *total64 (optional)
-__global__ __launch_bounds__(256) void scan_sums_kernel(uint32_t* __restrict__ sums, int64_t nb, long long* __restrict__ total64) {
-  __shared__ uint32_t wsum[4];
-  uint32_t carry = 0;
-  for (int64_t base = 0; base < nb; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const uint32_t v = i < nb ? sums[i] : 0u;
-    uint32_t total;
-    const uint32_t inc = block_inclusive(v, wsum, &total);
-    if (i < nb) sums[i] = carry + inc - v;
-    carry += total;
-  }
-  if (total64 && threadIdx.x == 0) *total64 = static_cast<long long>(carry);
-}
-
-template <bool INCLUSIVE>
-__global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ data, int64_t n, const uint32_t* __restrict__ sums,
-                                                         int64_t nb) {
-  __shared__ uint32_t wsum[4];
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * kScanBlock + static_cast<int64_t>(threadIdx.x) * kScanPer;
-  uint32_t e[kScanPer], v = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    e[j] = first + j < n ? data[first + j] : 0u;
-    v += e[j];
-  }
-  uint32_t total;
-  uint32_t run = block_inclusive(v, wsum, &total) - v + (blockIdx.x < nb ? sums[blockIdx.x] : 0u);
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    if (INCLUSIVE) run += e[j];
-    if (first + j < n) data[first + j] = run;
-    if (!INCLUSIVE) run += e[j];
-  }
-}
-
-// after the scan: bin b starts at counts[b][0]; the pass is the identity iff every bin starts at 0 or at N
-__global__ __launch_bounds__(256) void sort_decide_kernel(SortArgs a, int pass) {
-  const uint32_t start = a.counts[static_cast<size_t>(threadIdx.x) * a.T];
-  const int skip = __syncthreads_and(start == 0u || static_cast<int64_t>(start) == a.N);
-  if (threadIdx.x == 0) {
-    const int src = a.state->src[pass];
-    a.state->skip[pass] = skip;
-    a.state->src[pass + 1] = skip ? src : (src == 0 ? 1 : 0);
-  }
-}
-
-__global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(SortArgs a, int pass) {
-  __shared__ uint32_t cnt[kSortWaves][256];
-  if (a.state->skip[pass]) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
-  const int src = a.state->src[pass];
-  int32_t* __restrict__ dst = a.buf[src == 0 ? 1 : 0];
-#pragma unroll
-  for (int w = 0; w < kSortWaves; ++w) cnt[w][tid] = 0;
-  __syncthreads();
-  const int64_t base = static_cast<int64_t>(tile) * kSortTile + static_cast<int64_t>(wave) * (kSortTile / kSortWaves);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int32_t item[kSortRounds];
-  uint32_t place[kSortRounds];            // rank among the wave's keys of the digit << 8 | digit
-#pragma unroll
-  for (int r = 0; r < kSortRounds; ++r) {
-    const int64_t pos = base + r * 64 + lane;
-    const bool live = pos < a.N;
-    item[r] = live ? sort_item(a, src, pos) : 0;
-    const uint32_t d = live ? sort_digit(a, item[r], pass) : 0u;
-    unsigned long long same = __ballot(live);          // the live lanes with my digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const unsigned long long vote = __ballot((d >> b) & 1u);
-      same &= ((d >> b) & 1u) ? vote : ~vote;
-    }
-    const uint32_t before = cnt[wave][d];              // every lane reads before the round's leaders write
-    __builtin_amdgcn_wave_barrier();
-    if (live && (same & below) == 0ull) cnt[wave][d] = before + static_cast<uint32_t>(__popcll(same));
-    __builtin_amdgcn_wave_barrier();
-    place[r] = ((before + static_cast<uint32_t>(__popcll(same & below))) << 8) | d;
-  }
-  __syncthreads();
-  {                                                    // thread = digit: the waves' histograms -> their first destinations
-    uint32_t run = tile < a.T ? a.counts[static_cast<size_t>(tid) * a.T + tile] : 0u;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) {
-      const uint32_t c = cnt[w][tid];
-      cnt[w][tid] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kSortRounds; ++r) {
-    const int64_t pos = base + r * 64 + lane;
-    const int64_t to = static_cast<int64_t>(cnt[wave][place[r] & 0xffu]) + (place[r] >> 8);
-    if (pos < a.N && to < a.N) dst[to] = item[r];
-  }
-}
-
-__global__ __launch_bounds__(256) void sort_finish_kernel(SortArgs a, int passes, int32_t* __restrict__ order) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i < a.N) order[i] = sort_item(a, a.state->src[passes], i);
-}
 
 // ---- buckets ------------------------------------------------------------------------------------------------------------------
 // head[i] = 1 when sorted position i starts a new key
@@ -408,32 +193,6 @@ __global__ __launch_bounds__(kProbeThreads) void probe_kernel(ProbeArgs a) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-struct SortPlan {
-  int W, passes;
-  int64_t T, n_counts, nb_counts, nb_items;
-  size_t off_buf[2], off_counts, off_sums, bytes;
-};
-
-SortPlan sort_plan(int64_t N, int bits) {
-  SortPlan p = {};
-  p.W = (bits + 31) / 32;
-  p.passes = (bits + 7) / 8;
-  p.T = (N + kSortTile - 1) / kSortTile;
-  p.n_counts = 256 * p.T;
-  p.nb_counts = (p.n_counts + kScanBlock - 1) / kScanBlock;
-  p.nb_items = (N + kScanBlock - 1) / kScanBlock;
-  size_t at = align_up(sizeof(SortState), 256);
-  for (int b = 0; b < 2; ++b) {
-    p.off_buf[b] = at;
-    at += align_up(static_cast<size_t>(N) * 4, 256);
-  }
-  p.off_counts = at;
-  at += align_up(static_cast<size_t>(p.n_counts) * 4, 256);
-  p.off_sums = at;                                     // the sums of the counts' scan, or of cmh_code_bucket_count's
-  at += align_up(static_cast<size_t>(p.nb_counts > p.nb_items ? p.nb_counts : p.nb_items) * 4, 256);
-  p.bytes = at + 256;                                  // + the slack of aligning the caller's pointer
-  return p;
-}
 
 int check_sort_shape(const char* what, int64_t N, int bits) {
   if (N < 1 || N > 2147483647ll)
@@ -453,22 +212,6 @@ int check_probe_shape(const char* what, int Q, int64_t U, int bits, int radius) 
 
 int probe_count_of(int bits, int radius) { return radius == 0 ? 1 : radius == 1 ? 1 + bits : 1 + bits + bits * (bits - 1) / 2; }
 
-uint8_t* aligned_ws(void* workspace) {
-  return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-}
-
-// data[n] -> its scan in place (sums: nb words of scratch); total64 (optional) gets the sum
-template <bool INCLUSIVE>
-int launch_scan(uint32_t* data, int64_t n, uint32_t* sums, long long* total64, const char* what, hipStream_t st) {
-  const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
-  hipLaunchKernelGGL(scan_block_sums_kernel, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, data, n, sums, nb);
-  CMH_CHECK_LAUNCH(what);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, st, sums, nb, total64);
-  CMH_CHECK_LAUNCH(what);
-  hipLaunchKernelGGL(scan_apply_kernel<INCLUSIVE>, dim3(static_cast<unsigned>(nb)), dim3(256), 0, st, data, n, sums, nb);
-  CMH_CHECK_LAUNCH(what);
-  return CMH_OK;
-}
 
 }  // namespace
 }  // namespace cmh
@@ -486,33 +229,7 @@ extern "C" int cmh_code_sort(const uint32_t* sign, int64_t N, int32_t bits, int3
   if (rc != CMH_OK) return rc;
   const SortPlan p = sort_plan(N, bits);
   if (!workspace || workspace_bytes < p.bytes) return fail(CMH_ERR_WORKSPACE, "code_sort: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
-  uint8_t* ws = aligned_ws(workspace);
-  SortArgs a = {};
-  a.sign = sign; a.N = N; a.W = p.W; a.bits = bits; a.T = static_cast<int>(p.T);
-  a.buf[0] = reinterpret_cast<int32_t*>(ws + p.off_buf[0]);
-  a.buf[1] = reinterpret_cast<int32_t*>(ws + p.off_buf[1]);
-  a.counts = reinterpret_cast<uint32_t*>(ws + p.off_counts);
-  a.state = reinterpret_cast<SortState*>(ws);
-  uint32_t* sums = reinterpret_cast<uint32_t*>(ws + p.off_sums);
-  hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(&a.state->src[0], 0xff, sizeof(int), st) != hipSuccess) {      // src[0] = -1: the first pass reads no buffer
-    (void)hipGetLastError();
-    return fail(CMH_ERR_LAUNCH, "code_sort: setting the workspace failed");
-  }
-  const dim3 tiles(static_cast<unsigned>(p.T));
-  for (int pass = 0; pass < p.passes; ++pass) {
-    hipLaunchKernelGGL(sort_hist_kernel, tiles, dim3(kSortThreads), 0, st, a, pass);
-    CMH_CHECK_LAUNCH("code_sort (histogram)");
-    const int s = launch_scan<false>(a.counts, p.n_counts, sums, nullptr, "code_sort (scan)", st);
-    if (s != CMH_OK) return s;
-    hipLaunchKernelGGL(sort_decide_kernel, dim3(1), dim3(256), 0, st, a, pass);
-    CMH_CHECK_LAUNCH("code_sort (decide)");
-    hipLaunchKernelGGL(sort_scatter_kernel, tiles, dim3(kSortThreads), 0, st, a, pass);
-    CMH_CHECK_LAUNCH("code_sort (scatter)");
-  }
-  hipLaunchKernelGGL(sort_finish_kernel, dim3(static_cast<unsigned>((N + 255) / 256)), dim3(256), 0, st, a, p.passes, order);
-  CMH_CHECK_LAUNCH("code_sort (finish)");
-  return CMH_OK;
+  return run_sort("code_sort", sign, N, bits, 0, p.passes, p, aligned_ws(workspace), order, as_stream(stream));
 }
 
 extern "C" int cmh_code_bucket_count(const uint32_t* sign, const int32_t* order, int64_t N, int32_t bits, int32_t* head,

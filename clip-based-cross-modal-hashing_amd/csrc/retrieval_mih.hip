@@ -1,0 +1,327 @@
+// Radius search past 2 bits by multi-index hashing on 16-bit substrings (Norouzi, Punjani, Fleet 2012).
+//   cmh_mih_build           order[m, N] and starts[m, 65537]: per substring the item indices by ascending (key, index) and the
+//                           first position of every key: m direct-addressed tables, no search at lookup time
+//   cmh_mih_count / _fill   per query every item within `radius` whole bits, each exactly once
+//
+// Codes are in {-1, +1} (the caller checks; no entry point reads an nz plane) and at most 128 bit.  m = ceil(bits / 16); SUBSTRING j
+// is bits [16 j, 16 j + s_j) of a row's sign words, s_j = 16 but for a shorter last one, and its KEY those bits as an unsigned
+// integer.  For a radius r let a, b = divmod(r, m): substring j is probed at radius a_j = a for j <= b and a - 1 behind (-1: not
+// probed).  If every probed j had d_j > a_j, then d >= (b + 1)(a + 1) + (m - b - 1) a = m a + b + 1 > r: an item within r is in a
+// probed bucket of some substring.  a <= CMH_MIH_SUB_RADIUS_MAX, so r <= 3 m - 1.
+//
+// The build.  Key j is digits 2 j and 2 j + 1 of the row in the terms of retrieval_sort.h (the bits at and behind `bits` are
+// cleared there, which is the short last substring): table j is that file's stable sort over those two digits from position =
+// item, so equal keys keep ascending index.  starts is a per-key lower bound over the sorted keys (<= 32 steps per key).
+//
+// The lookup.  The PROBES of substring j are the query's key with at most a_j of its s_j bits flipped: none, single bits ascending,
+// pairs (i, i'), i < i', in lexicographic order; distinct probes are distinct keys.  A query's probes over all substrings are
+// numbered in (substring, probe) order.  One workgroup of 256 threads owns a query and takes its probes 256 at a time: a thread
+// reads its probe's bucket bounds, and the inclusive prefix of the bucket lengths (LDS) makes the round's buckets ONE list of
+// candidates in (substring, probe, bucket position) order.  The workgroup walks that list 256 candidates at a time, whatever the
+// lengths of the buckets behind it: a thread finds its candidate's probe by a binary search over the 256 prefixes, reads the item
+// from `order`, checks it against N, loads its row and verifies.
+// EXACTLY ONCE: item x reached through substring j is emitted iff d(q, x) <= r and no probed j' < j has d_j'(q, x) <= a_j' (x is
+// then emitted through the first such j').  The d_j' are popcounts on the row that the verification loaded: no visited set, no
+// hash, no atomics.  A hit's place in the query's list is the hits of the steps before + of the waves before it in this step (LDS)
+// + of the lower lanes (ballot).  The count pass and the fill pass walk identically; nothing per candidate is stored.  The list is
+// in walk order on every run; the caller sorts it by (distance, index).
+// No kernel waits for another workgroup.  Every loop is bounded by an argument (a bucket's bounds are clamped to [0, N]), every
+// offset is 64-bit, every index read out of a table is checked against N before it addresses anything, every output word is
+// written once.
+#include "retrieval_sort.h"
+
+namespace cmh {
+namespace {
+
+constexpr int kMihSub = CMH_MIH_SUB_BITS;
+constexpr int kMihKeys = 1 << kMihSub;
+constexpr int kMihMaxSubs = CMH_BUCKET_BITS_MAX / kMihSub;
+constexpr int kMihThreads = 256;
+constexpr int kMihWaves = kMihThreads / 64;
+
+static_assert(kMihSub == 16, "a key is two 8-bit digits of the sort");
+
+__host__ __device__ __forceinline__ int mih_subs(int bits) { return (bits + kMihSub - 1) / kMihSub; }
+__host__ __device__ __forceinline__ int mih_sub_bits(int bits, int j) { return bits - kMihSub * j < kMihSub ? bits - kMihSub * j : kMihSub; }
+
+// ---- build --------------------------------------------------------------------------------------------------------------------
+// starts[j][key] = the first position of row j of order whose key is not below `key`; starts[j][65536] = N
+__global__ __launch_bounds__(256) void mih_starts_kernel(const uint32_t* __restrict__ sign, const int32_t* __restrict__ order, int64_t N,
+                                                         int W, int bits, int32_t* __restrict__ starts) {
+  const int key = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  if (key > kMihKeys) return;
+  const int32_t* __restrict__ row = order + static_cast<size_t>(j) * N;
+  int64_t lo = 0, hi = N;
+  for (int s = 0; s < 32 && lo < hi; ++s) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    const int64_t item = row[mid];
+    const bool legal = item >= 0 && item < N;           // (not a row of cmh_mih_build: nothing is read outside the plane)
+    const uint32_t k = legal ? (key_word(sign, item, W, j >> 1, bits) >> (kMihSub * (j & 1))) & 0xffffu : 0xffffffffu;
+    if (k < static_cast<uint32_t>(key)) lo = mid + 1; else hi = mid;
+  }
+  starts[static_cast<size_t>(j) * (kMihKeys + 1) + key] = static_cast<int32_t>(lo);
+}
+
+// ---- lookup -------------------------------------------------------------------------------------------------------------------
+struct MihArgs {
+  const uint32_t* q_sign;
+  const uint32_t* db_sign;
+  const int32_t* order;          // [m, N]
+  const int32_t* starts;         // [m, 65537]
+  int64_t N;
+  int Q, bits, radius, m, probes;
+  int sub_radius[kMihMaxSubs];   // a_j; -1 = not probed
+  int first[kMihMaxSubs + 1];    // the probes of the substrings before j
+  int32_t* n_hits;               // count pass
+  const long long* offsets;      // fill pass: [Q + 1]
+  int64_t capacity;
+  int32_t* idx;
+  int32_t* dist;
+};
+
+// inclusive prefix of v over the 256 threads of the workgroup.  wsum: kMihWaves words of LDS
+__device__ __forceinline__ unsigned long long block_inclusive64(unsigned long long v, unsigned long long* wsum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  __syncthreads();                        // (wsum, and the caller's LDS, may still be read from the previous round)
+  if (lane == 63) wsum[wave] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < kMihWaves; ++w) v += w < wave ? wsum[w] : 0ull;
+  return v;
+}
+
+// the substring of probe p (p < a.probes: the unprobed substrings lie behind the probed ones and own no probe)
+__device__ __forceinline__ int mih_sub_of(const MihArgs& a, int p) {
+  int j = 0;
+#pragma unroll
+  for (int jj = 1; jj < kMihMaxSubs; ++jj) j = (jj < a.m && p >= a.first[jj]) ? jj : j;
+  return j;
+}
+
+template <bool FILL, int W>
+__global__ __launch_bounds__(kMihThreads) void mih_kernel(MihArgs a) {
+  __shared__ unsigned long long incl[kMihThreads];     // the round's bucket lengths, inclusive prefix
+  __shared__ long long begin[kMihThreads];             // the round's buckets: first position in order (row j included)
+  __shared__ unsigned long long wsum[kMihWaves];
+  __shared__ uint32_t wave_hits[kMihWaves];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (q >= a.Q) return;
+  uint32_t qw[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) qw[w] = a.q_sign[static_cast<size_t>(q) * W + w] & word_mask(w, a.bits);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int64_t done = 0;                                    // hits of the steps before this one
+  int64_t list_lo = 0, list_hi = 0;
+  if (FILL) {
+    list_lo = a.offsets[q];
+    list_hi = a.offsets[q + 1] < a.capacity ? a.offsets[q + 1] : a.capacity;
+  }
+  for (int first = 0; first < a.probes; first += kMihThreads) {
+    const int p = first + tid;
+    unsigned long long len = 0;
+    long long at = 0;
+    if (p < a.probes) {
+      const int j = mih_sub_of(a, p), s = mih_sub_bits(a.bits, j);
+      int t = p - a.first[j];
+      uint32_t word = 0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) word = (j >> 1) == w ? qw[w] : word;
+      uint32_t key = (word >> (kMihSub * (j & 1))) & ((1u << s) - 1u);
+      bool legal = true;
+      if (t >= 1 && t <= s) {
+        key ^= 1u << (t - 1);
+      } else if (t > s) {                              // pair number t - 1 - s of (i, i'), i < i' < s, in lexicographic order
+        t -= 1 + s;
+        int i = 0;
+        for (int row = 0; row < kMihSub - 1 && row < s - 1 && t >= s - 1 - row; ++row) {
+          t -= s - 1 - row;
+          i = row + 1;
+        }
+        const int i2 = i + 1 + t;
+        legal = i2 < s;
+        key ^= legal ? (1u << i) ^ (1u << i2) : 0u;
+      }
+      if (legal) {
+        const int32_t* bounds = a.starts + static_cast<size_t>(j) * (kMihKeys + 1) + key;
+        int64_t lo = bounds[0], hi = bounds[1];
+        lo = lo < 0 ? 0 : lo > a.N ? a.N : lo;
+        hi = hi < lo ? lo : hi > a.N ? a.N : hi;
+        len = static_cast<unsigned long long>(hi - lo);
+        at = static_cast<long long>(j) * a.N + lo;
+      }
+    }
+    const unsigned long long inc = block_inclusive64(len, wsum);
+    incl[tid] = inc;
+    begin[tid] = at;
+    __syncthreads();
+    const unsigned long long total = incl[kMihThreads - 1];
+    for (unsigned long long c0 = 0; c0 < total; c0 += kMihThreads) {
+      const unsigned long long c = c0 + tid;
+      bool hit = false;
+      int64_t item = 0;
+      int d = 0;
+      if (c < total) {
+        int lo = 0, hi = kMihThreads - 1;              // the first slot whose inclusive prefix is above c
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          const int mid = (lo + hi) >> 1;
+          if (incl[mid] > c) hi = mid; else lo = mid + 1;
+        }
+        const unsigned long long before = lo ? incl[lo - 1] : 0ull;
+        const int j = mih_sub_of(a, first + lo);
+        item = a.order[begin[lo] + static_cast<long long>(c - before)];
+        if (item >= 0 && item < a.N) {
+          uint32_t x[W];
+          const uint32_t* row = a.db_sign + static_cast<size_t>(item) * W;
+          if constexpr (W == 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(row);
+            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+          } else if constexpr (W == 2) {
+            const uint2 v = *reinterpret_cast<const uint2*>(row);
+            x[0] = v.x; x[1] = v.y;
+          } else {
+#pragma unroll
+            for (int w = 0; w < W; ++w) x[w] = row[w];
+          }
+          bool earlier = false;                        // a probed substring before j reaches the item: emitted there
+#pragma unroll
+          for (int w = 0; w < W; ++w) {
+            x[w] = (x[w] ^ qw[w]) & word_mask(w, a.bits);
+            d += __popc(x[w]);
+            earlier = earlier || (2 * w < j && a.sub_radius[2 * w] >= 0 && __popc(x[w] & 0xffffu) <= a.sub_radius[2 * w]);
+            earlier = earlier || (2 * w + 1 < j && a.sub_radius[2 * w + 1] >= 0 && __popc(x[w] >> kMihSub) <= a.sub_radius[2 * w + 1]);
+          }
+          hit = d <= a.radius && !earlier;
+        }
+      }
+      const unsigned long long votes = __ballot(hit);
+      __syncthreads();                                 // (the previous step's wave_hits are read)
+      if (lane == 0) wave_hits[wave] = static_cast<uint32_t>(__popcll(votes));
+      __syncthreads();
+      uint32_t before = 0, all = 0;
+#pragma unroll
+      for (int w = 0; w < kMihWaves; ++w) {
+        const uint32_t h = wave_hits[w];
+        before += w < wave ? h : 0u;
+        all += h;
+      }
+      if (FILL && hit) {
+        const int64_t to = list_lo + done + before + __popcll(votes & below);
+        if (to >= list_lo && to < list_hi) {
+          a.idx[to] = static_cast<int32_t>(item);
+          a.dist[to] = d;
+        }
+      }
+      done += all;
+    }
+  }
+  if (!FILL && tid == 0) a.n_hits[q] = static_cast<int32_t>(done);
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+int mih_probes_of(int s, int radius) { return radius < 0 ? 0 : radius == 0 ? 1 : radius == 1 ? 1 + s : 1 + s + s * (s - 1) / 2; }
+
+int check_mih_table(const char* what, int64_t N, int bits) {
+  CMH_CHECK_ARG(N >= 1 && N <= 2147483647ll, "%s: N=%lld outside [1, 2^31 - 1]", what, static_cast<long long>(N));
+  CMH_CHECK_ARG(bits >= 1 && bits <= CMH_BUCKET_BITS_MAX, "%s: bits=%d outside [1, %d]", what, bits, CMH_BUCKET_BITS_MAX);
+  return CMH_OK;
+}
+
+// the shape checks of a lookup, then the call's arguments: the substring radii and the numbering of the probes
+int mih_args(const char* what, const uint32_t* q_sign, int Q, const uint32_t* db_sign, int64_t N, int bits, int radius,
+             const int32_t* order, const int32_t* starts, MihArgs* a) {
+  CMH_CHECK_ARG(Q >= 1 && Q <= 65535, "%s: Q=%d outside [1, 65535]", what, Q);
+  const int rc = check_mih_table(what, N, bits);
+  if (rc != CMH_OK) return rc;
+  const int m = mih_subs(bits), W = (bits + 31) / 32;
+  CMH_CHECK_ARG(radius >= 0 && radius <= (CMH_MIH_SUB_RADIUS_MAX + 1) * m - 1,
+                "%s: radius=%d outside [0, %d] (%d substrings of %d bits, each probed within %d)", what, radius,
+                (CMH_MIH_SUB_RADIUS_MAX + 1) * m - 1, m, CMH_MIH_SUB_BITS, CMH_MIH_SUB_RADIUS_MAX);
+  const uintptr_t row = W == 4 ? 16 : W == 2 ? 8 : 4;      // a row is read with one load
+  CMH_CHECK_ARG(reinterpret_cast<uintptr_t>(db_sign) % row == 0, "%s: db_sign holds rows of %d words: aligned to %d bytes", what, W,
+                static_cast<int>(row));
+  *a = MihArgs{};
+  a->q_sign = q_sign; a->db_sign = db_sign; a->order = order; a->starts = starts;
+  a->N = N; a->Q = Q; a->bits = bits; a->radius = radius; a->m = m;
+  const int each = radius / m, more = radius % m;
+  int probes = 0;
+  for (int j = 0; j < kMihMaxSubs; ++j) {
+    a->sub_radius[j] = j >= m ? -1 : j <= more ? each : each - 1;
+    a->first[j] = probes;
+    if (j < m) probes += mih_probes_of(mih_sub_bits(bits, j), a->sub_radius[j]);
+  }
+  a->first[kMihMaxSubs] = probes;
+  a->probes = probes;
+  return CMH_OK;
+}
+
+template <bool FILL>
+void launch_mih(const MihArgs& a, hipStream_t st) {
+  const dim3 grid(static_cast<unsigned>(a.Q)), block(kMihThreads);
+  switch ((a.bits + 31) / 32) {
+    case 1: hipLaunchKernelGGL((mih_kernel<FILL, 1>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((mih_kernel<FILL, 2>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((mih_kernel<FILL, 3>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((mih_kernel<FILL, 4>), grid, block, 0, st, a); break;
+  }
+}
+
+}  // namespace
+}  // namespace cmh
+
+using namespace cmh;
+
+extern "C" size_t cmh_mih_build_workspace_bytes(int64_t N, int32_t bits) {
+  return N >= 1 && N <= 2147483647ll && bits >= 1 && bits <= CMH_BUCKET_BITS_MAX ? sort_plan(N, bits).bytes : 0;
+}
+
+extern "C" int cmh_mih_build(const uint32_t* sign, int64_t N, int32_t bits, int32_t* order, int32_t* starts, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(sign && order && starts, "mih_build: null pointer");
+  const int rc = check_mih_table("mih_build", N, bits);
+  if (rc != CMH_OK) return rc;
+  const SortPlan p = sort_plan(N, bits);
+  if (!workspace || workspace_bytes < p.bytes) return fail(CMH_ERR_WORKSPACE, "mih_build: workspace %zu < %zu bytes", workspace_bytes, p.bytes);
+  uint8_t* ws = aligned_ws(workspace);
+  hipStream_t st = as_stream(stream);
+  const int m = mih_subs(bits);
+  for (int j = 0; j < m; ++j) {
+    const int s = run_sort("mih_build", sign, N, bits, 2 * j, (mih_sub_bits(bits, j) + 7) / 8, p, ws, order + static_cast<size_t>(j) * N, st);
+    if (s != CMH_OK) return s;
+  }
+  hipLaunchKernelGGL(mih_starts_kernel, dim3(kMihKeys / 256 + 1, m), dim3(256), 0, st, sign, order, N, p.W, bits, starts);
+  CMH_CHECK_LAUNCH("mih_build (starts)");
+  return CMH_OK;
+}
+
+extern "C" int cmh_mih_count(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, int32_t radius,
+                             const int32_t* order, const int32_t* starts, int32_t* n_hits, void* stream) {
+  CMH_CHECK_ARG(q_sign && db_sign && order && starts && n_hits, "mih_count: null pointer");
+  MihArgs a;
+  const int rc = mih_args("mih_count", q_sign, Q, db_sign, N, bits, radius, order, starts, &a);
+  if (rc != CMH_OK) return rc;
+  a.n_hits = n_hits;
+  launch_mih<false>(a, as_stream(stream));
+  CMH_CHECK_LAUNCH("mih_count");
+  return CMH_OK;
+}
+
+extern "C" int cmh_mih_fill(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, int32_t radius,
+                            const int32_t* order, const int32_t* starts, const int64_t* offsets, int64_t capacity, int32_t* idx,
+                            int32_t* dist, void* stream) {
+  CMH_CHECK_ARG(q_sign && db_sign && order && starts && offsets && idx && dist, "mih_fill: null pointer");
+  MihArgs a;
+  CMH_CHECK_ARG(capacity >= 1, "mih_fill: capacity=%lld below 1 (no hits: no call)", static_cast<long long>(capacity));
+  CMH_CHECK_ARG(reinterpret_cast<uintptr_t>(offsets) % 8 == 0, "mih_fill: offsets holds 64-bit integers: aligned to 8 bytes");
+  const int rc = mih_args("mih_fill", q_sign, Q, db_sign, N, bits, radius, order, starts, &a);
+  if (rc != CMH_OK) return rc;
+  a.offsets = reinterpret_cast<const long long*>(offsets); a.capacity = capacity; a.idx = idx; a.dist = dist;
+  launch_mih<true>(a, as_stream(stream));
+  CMH_CHECK_LAUNCH("mih_fill");
+  return CMH_OK;
+}

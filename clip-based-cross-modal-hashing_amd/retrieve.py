@@ -79,7 +79,14 @@ and the filters.
 prints, per database side (r_img, r_txt; with --index the index alone), how the items spread over their distinct codes: the distinct
 codes, the singletons, the largest bucket, the share of the possible codes in use, the colliding pairs, the collision probability
 and the entropy of the bucket sizes.  --stats-out stores the numbers and the (size, buckets) occupancy tables; with --stats both
-reports are printed and stored.  The exclusions are those of --stats."""
+reports are printed and stored.  The exclusions are those of --stats.
+
+    python retrieve.py --codes <file>.mat --direction i2t --near 4 [--index db.npz] [--queries a:b]
+
+prints what --radius 4 prints, line for line, from the index's substring tables (CodeIndex.lookup_far: multi-index hashing on 16-bit
+substrings, the candidates verified with the full distance).  R is a whole number of bits up to 3 ceil(bits / 16) - 1 (11 at 64
+bit, 23 at 128); codes up to 128 bit without zero entries (--radius takes the others).  --near excludes what --lookup excludes,
+and --lookup."""
 import argparse
 import sys
 
@@ -131,8 +138,18 @@ def parse(argv=None):
     p.add_argument("--stats-out", default=None, metavar="FILE", help="with --stats / --bucket-stats: store every array as FILE (.npz)")
     p.add_argument("--lookup", type=int, default=None, metavar="R", help="print every database item within R = 0, 1 or 2 bits of each query, as --radius does, from the index's bucket table")
     p.add_argument("--bucket-stats", action="store_true", help="print how the items of the file's database sides (or of --index) spread over their distinct codes in place of a search")
+    p.add_argument("--near", type=int, default=None, metavar="R", help="print every database item within R whole bits of each query, as --radius does, from the index's substring tables (R up to 3 ceil(bits / 16) - 1)")
     args = p.parse_args(argv)
     args.ask = getattr(args, "ask", None) or []
+    if args.near is not None:
+        for flag, given in (("--radius", args.radius is not None), ("--lookup", args.lookup is not None), ("--k", args.k is not None),
+                            ("--map", args.map), ("--graded", args.graded), ("--recall", args.recall), ("--soft", args.soft),
+                            ("--stats", args.stats), ("--bucket-stats", args.bucket_stats), ("--text / --image", bool(args.ask))) \
+                + tuple((f, getattr(args, f[2:].replace("-", "_")) is not None) for f in FILTERS):
+            if given:
+                p.error(f"--near and {flag} exclude each other")
+        if args.near < 0:
+            p.error(f"--near {args.near}: a whole number of bits >= 0 (--radius takes any radius)")
     if args.lookup is not None:
         for flag, given in (("--radius", args.radius is not None), ("--k", args.k is not None), ("--map", args.map), ("--graded", args.graded),
                             ("--recall", args.recall), ("--soft", args.soft), ("--stats", args.stats), ("--bucket-stats", args.bucket_stats),
@@ -403,13 +420,14 @@ def main(argv=None):
         return 0
     if hi == lo:
         return 0
-    if args.radius is not None or args.lookup is not None:
-        if args.lookup is not None:
+    if args.radius is not None or args.lookup is not None or args.near is not None:
+        if args.lookup is not None or args.near is not None:
             import cmh_native as N
             try:
-                out = [t.cpu().numpy() for t in index.lookup(queries, args.lookup, labels)]
-            except N.NativeError as e:                             # zeros in the codes, more than 128 bits: --radius takes them
-                raise SystemExit(f"--lookup: {e}")
+                found = index.lookup(queries, args.lookup, labels) if args.near is None else index.lookup_far(queries, args.near, labels)
+                out = [t.cpu().numpy() for t in found]
+            except N.NativeError as e:                             # zeros in the codes, more than 128 bits, a radius beyond the tables': --radius takes them
+                raise SystemExit(f"{'--lookup' if args.near is None else '--near'}: {e}")
         else:
             out = [t.cpu().numpy() for t in index.range_search(queries, args.radius, labels, max_hits=args.max_hits)]
         for i in range(hi - lo):

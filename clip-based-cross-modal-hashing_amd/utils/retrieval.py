@@ -1004,11 +1004,125 @@ class BucketTable:
         return (torch.cat(offs),) + tuple(None if ts[0] is None else torch.cat(ts) for ts in zip(*[p[1:] for p in parts]))
 
 
+def substring_radii(bits, radius):
+    """The radius each 16-bit substring of a `bits`-bit code is probed at for a whole-bit search radius (multi-index hashing,
+    csrc/retrieval_mih.hip): with m = ceil(bits / 16) and a, b = divmod(radius, m), a_j = a for j <= b and a - 1 behind; -1 = the
+    substring is not probed.  If every probed j had d_j > a_j, then d >= (b + 1)(a + 1) + (m - b - 1) a = m a + b + 1 > radius, so
+    an item within the radius is within a_j of the query in some probed substring.  a <= MIH_SUB_RADIUS_MAX: radius <= 3 m - 1."""
+    if isinstance(bits, bool) or bits != int(bits) or not 1 <= int(bits) <= N.BUCKET_BITS_MAX:
+        raise N.NativeError(f"substring_radii: {bits}-bit codes outside [1, BUCKET_BITS_MAX = {N.BUCKET_BITS_MAX}] (range_search takes them)")
+    m = N.mih_substrings(bits)
+    top = (N.MIH_SUB_RADIUS_MAX + 1) * m - 1
+    if isinstance(radius, bool) or radius != int(radius) or not 0 <= int(radius) <= top:
+        raise N.NativeError(f"substring_radii: radius={radius} is not a whole number of bits in [0, {top}] for {int(bits)}-bit codes "
+                            f"({m} substrings, each probed within {N.MIH_SUB_RADIUS_MAX}; range_search takes any radius)")
+    a, b = divmod(int(radius), m)
+    return [a if j <= b else a - 1 for j in range(m)]
+
+
+def _check_far(what, bits, query_bits, radius):
+    """What a substring lookup refuses by name before anything is packed, built or launched."""
+    if query_bits != bits:
+        raise N.NativeError(f"{what}: {query_bits}-bit queries for an index of {bits} bits")
+    try:
+        substring_radii(bits, radius)
+    except N.NativeError as e:
+        raise N.NativeError(f"{what}: {e}") from None
+
+
+class SubstringTables:
+    """Multi-index hashing over a packed database (csrc/retrieval_mih.hip), all on the GPU: one direct-addressed
+    table per 16-bit substring of the codes.
+      order  int32 [m, n]       row j = the item indices by ascending (key of substring j, index)
+      starts int32 [m, 65537]   bucket `key` of table j = order[j, starts[j, key]:starts[j, key + 1]]
+      sign   int32 [n, W]       the database's sign plane (candidates are verified against it)
+      bits, n, m (= ceil(bits / 16)), max_radius (= 3 m - 1)
+    build(planes, bits) sorts m times (cmh_mih_build); lookup(...) answers "every item within `radius` whole bits" by probing each
+    table at substring_radii(bits, radius) and verifying the buckets' items: the cost follows the buckets' sizes, not n.  Codes in
+    {-1, +1} only, up to 128 bit."""
+
+    def __init__(self, order, starts, sign, bits, n):
+        self.order, self.starts, self.sign, self.bits, self.n, self.m = order, starts, sign, int(bits), int(n), order.shape[0]
+
+    @property
+    def max_radius(self):
+        return (N.MIH_SUB_RADIUS_MAX + 1) * self.m - 1
+
+    @classmethod
+    def build(cls, planes, bits):
+        """planes: (sign, nz) of pack_codes, int32 [n, ceil(bits / 32)] on the GPU, any n up to 2^31 - 1."""
+        bits = int(bits)
+        sign, nz = planes
+        N.fit("SubstringTables.build", (nz, tuple(sign.shape)))
+        if bits > N.BUCKET_BITS_MAX:
+            raise N.NativeError(f"SubstringTables.build: {bits}-bit codes exceed BUCKET_BITS_MAX = {N.BUCKET_BITS_MAX} (range_search takes them)")
+        _no_zeros("SubstringTables.build", "a database code", planes, bits)
+        sign = sign.contiguous()
+        order, starts = N.mih_build(sign, bits)
+        return cls(order, starts, sign, bits, sign.shape[0])
+
+    def lookup(self, query_codes, radius, query_labels=None, retrieval_L=None, max_hits=None):
+        """-> hamming_range's tuple (offsets int64 [Q+1], idx int32 [T], dist f32 [T][, rel uint8 [T] with labels]): every item
+        within `radius` whole bits (0 .. max_radius) of every query, by (distance, database index) inside a query's list.
+        query_codes f32 [Q, bits] in {-1, +1}; query_labels / retrieval_L: multi-hot [Q, C] / [n, C], both or neither; more than
+        max_hits (default 2^31 - 1) entries are refused before they are allocated."""
+        if (query_labels is None) != (retrieval_L is None):
+            raise N.NativeError("SubstringTables.lookup: labels on one side only")
+        if retrieval_L is not None and retrieval_L.shape[0] != self.n:
+            raise N.NativeError(f"SubstringTables.lookup: labels of {retrieval_L.shape[0]} items for tables of {self.n}")
+        _check_far("SubstringTables.lookup", self.bits, query_codes.shape[-1], radius)
+        dev = self.order.device
+        off, idx, dist, rel = self._lookup("SubstringTables.lookup", _codes(query_codes, dev), radius, _labels(query_labels, dev),
+                                           _labels(retrieval_L, dev), max_hits)
+        return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
+    def _lookup(self, what, qp, radius, ql, rl, max_hits=None):
+        """The packed form: qp = the queries' planes, ql / rl = packed labels or None -> (offsets, idx, dist, rel or None).  Per block
+        of queries: count pass, cumsum, the total read back and checked, fill pass, one stable sort on (query, distance, item)."""
+        radius = int(radius)
+        _no_zeros(what, "a query", qp, self.bits)
+        limit = ITEMS_MAX if max_hits is None else int(max_hits)
+        if limit < 0:
+            raise N.NativeError(f"{what}: max_hits={max_hits} below 0")
+        dev = self.order.device
+        Q = qp[0].shape[0]
+        parts, hits = [], 0
+        for cut in _cuts(Q, N.QUERIES_MAX):
+            qs = _rows(qp[0], cut, Q).contiguous()
+            nq = cut[1] - cut[0]
+            n_hits = N.mih_count(qs, self.sign, self.bits, radius, self.order, self.starts)
+            off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(n_hits, 0, out=off[1:])
+            T = int(off[-1])
+            hits += T
+            if hits > limit:
+                raise N.NativeError(f"{what}: T={hits} hits exceed max_hits={limit}")
+            if T == 0:
+                idx, dist = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+                query = torch.empty(0, dtype=torch.int64, device=dev)
+            else:
+                idx, dist = N.mih_fill(qs, self.sign, self.bits, radius, self.order, self.starts, off, T)
+                query = torch.repeat_interleave(torch.arange(nq, device=dev), n_hits.long(), output_size=T)
+                by = torch.sort(((query * (self.bits + 1) + dist) << 31) + idx, stable=True)[1]      # the walk's order -> (distance, item)
+                idx, dist = idx[by], dist[by].to(torch.float32)
+            rel = None if ql is None else ((_rows(ql, cut, Q)[query] & rl[idx.long()]) != 0).any(-1).to(torch.uint8)
+            parts.append((off, idx, dist, rel))
+        if len(parts) == 1:
+            return parts[0]
+        offs, base = [parts[0][0]], parts[0][0][-1]
+        for p in parts[1:]:
+            offs.append(p[0][1:] + base)
+            base = offs[-1][-1]
+        return (torch.cat(offs),) + tuple(None if ts[0] is None else torch.cat(ts) for ts in zip(*[p[1:] for p in parts]))
+
+
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
     buckets() -> the BucketTable of the index (built on first use, dropped by add()); lookup(query_codes, radius) -> the radius
     search of range_search through that table (radius 0, 1, 2; codes without zeros); bucket_stats() -> how the items spread over
-    their distinct codes;
+    their distinct codes; substrings() -> the SubstringTables of the index (likewise built on first use), lookup_far(query_codes,
+    radius) -> range_search's tuple through them for a whole-bit radius up to 3 ceil(bits / 16) - 1, near_duplicates(radius) ->
+    duplicates' tuple through them;
     search_soft(u, k) -> soft_topk's; map_soft(u, query_labels) -> soft_mean_average_precision's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's; stats() -> code_stats'.
@@ -1055,7 +1169,7 @@ class CodeIndex:
         if lab is not None:
             self._lab = grown(self._lab, lab)
         self.size += new
-        self._buckets = None                                       # derived from the items: buckets() builds it again
+        self._buckets = self._substrings = None                    # derived from the items: buckets() / substrings() build them again
 
     def add(self, codes, labels=None):
         """Appends items behind the ones the index holds (their indices: size, size + 1, ...); only the new rows are packed."""
@@ -1218,6 +1332,25 @@ class CodeIndex:
                                                      self.labels if ql is not None else None)
         return (off, idx, dist) if rel is None else (off, idx, dist, rel)
 
+    def substrings(self):
+        """The SubstringTables of the index as it is now: built on first use and kept until add() changes the items.  Derived data:
+        save() does not store them.  An index with a code that holds a 0, or of more than 128 bits, is refused."""
+        if self._substrings is None:
+            self._substrings = SubstringTables.build(self.planes, self.bits)
+        return self._substrings
+
+    def lookup_far(self, query_codes, radius, query_labels=None, max_hits=None):
+        """range_search(query_codes, radius) through the substring tables: the same tuple, element for element, for a whole-bit
+        radius up to 3 ceil(bits / 16) - 1 (11 at 64 bit, 23 at 128), codes up to 128 bit and no 0 entry on either side; the
+        cost follows the sizes of the probed buckets, not the size of the index (DESIGN.md 9.12 says when that wins)."""
+        if query_labels is not None and self.labels is None:
+            raise N.NativeError("CodeIndex.lookup_far: query labels given, but the index has none")
+        _check_far("CodeIndex.lookup_far", self.bits, query_codes.shape[-1], radius)
+        ql = _labels(query_labels, self.device)
+        off, idx, dist, rel = self.substrings()._lookup("CodeIndex.lookup_far", _codes(query_codes, self.device), radius, ql,
+                                                        self.labels if ql is not None else None, max_hits)
+        return (off, idx, dist) if rel is None else (off, idx, dist, rel)
+
     def bucket_stats(self):
         """How the items spread over their distinct codes (utils/code_stats.py::bucket_stats_from_sizes): distinct, singletons,
         largest, collisions, collision_probability, bucket_entropy_bits, used_share and the (size, buckets) occupancy table.  Only
@@ -1255,6 +1388,17 @@ class CodeIndex:
         radius of itself: a code with z zeros is at distance z / 2 from itself).  max_hits bounds the lists before that."""
         off, idx, dist, rel = _range("CodeIndex.duplicates", self.planes, self.planes, self.bits, radius_half_units(radius, self.bits),
                                      self.labels, self.labels, self.shard_items, max_hits)
+        return self._without_own(off, idx, dist, rel)
+
+    def near_duplicates(self, radius, max_hits=None):
+        """duplicates(radius), element for element, through the substring tables: the index looked up against itself in blocks of
+        queries, an item's own entry taken out.  The limits are lookup_far's."""
+        _check_far("CodeIndex.near_duplicates", self.bits, self.bits, radius)
+        off, idx, dist, rel = self.substrings()._lookup("CodeIndex.near_duplicates", self.planes, radius, self.labels, self.labels, max_hits)
+        return self._without_own(off, idx, dist, rel)
+
+    def _without_own(self, off, idx, dist, rel):
+        """The lists of the index against itself without each item's own entry."""
         ball = off[1:] - off[:-1]
         item = torch.repeat_interleave(torch.arange(self.size, device=self.device), ball, output_size=idx.numel())
         keep = idx != item

@@ -728,6 +728,38 @@ int cmh_bucket_probe_fill(const uint32_t* q_sign, int32_t Q, const int32_t* code
                           int32_t radius, const int64_t* bucket_offsets, int64_t capacity, int32_t* hit_bucket, int32_t* hit_dist,
                           void* stream);
 
+/* Radius search past 2 bits: multi-index hashing on 16-bit substrings (csrc/retrieval_mih.hip).  Codes in
+ * {-1, +1} as above, 1 <= bits <= CMH_BUCKET_BITS_MAX.  m = ceil(bits / 16); substring j is bits [16 j, 16 j + s_j) of a row's
+ * sign words (s_j = 16 but for a shorter last one) and its key those bits as an unsigned integer below 2^s_j.
+ * cmh_mih_build: sign u32 [N, W] -> order i32 [m, N], row j = the item indices by ascending (key_j, index), and starts i32
+ * [m, 65537]: bucket `key` of table j is order[j][starts[j][key] : starts[j][key + 1]]; the starts of the keys >= 2^s_j of a short
+ * last substring, and starts[j][65536], are N.  1 <= N <= 2^31 - 1.  Workspace: cmh_mih_build_workspace_bytes(N, bits) (0 outside
+ * the limits).
+ * cmh_mih_count / cmh_mih_fill: q_sign u32 [Q, W] against db_sign u32 [N, W] (rows of 2 / 4 words aligned to 8 / 16 bytes) and its
+ * tables.  With a, b = divmod(radius, m), substring j is probed at radius a_j = a for j <= b and a - 1 behind (-1: not probed):
+ * the keys that are the query's with at most a_j bits flipped, in the order none, single bits ascending, pairs (i, i'), i < i', in
+ * lexicographic order.  Every item of a probed bucket is verified with the full distance d, and item x reached through substring j
+ * is emitted iff d <= radius and no probed j' < j has d_j' <= a_j': every item within `radius` whole bits, exactly once.
+ *   count: n_hits i32 [Q] = the items within `radius` of each query
+ *   fill:  offsets i64 [Q + 1] = the exclusive prefix sum of n_hits (aligned to 8 bytes); idx, dist i32 [capacity], capacity >=
+ *          offsets[Q] >= 1: query q's items at offsets[q] .., as (database index, whole-bit distance), in the order of the walk
+ *          (substring, probe, position in the bucket) - the same on every call; the caller sorts by (distance, index).  Nothing at
+ *          or behind min(offsets[q + 1], capacity) is written.
+ * 1 <= Q <= 65535 per call, 0 <= radius <= 3 m - 1 (a <= CMH_MIH_SUB_RADIUS_MAX).  Both passes walk; nothing per candidate is kept
+ * between them.  All: -1 before any launch for null operands, sizes outside the limits (the message names the limit), misaligned
+ * operands; -2 for a workspace that is too small.  No atomics on any output, every output word written once, every index read from
+ * a table checked against N, no kernel waits for another workgroup: two calls give equal bytes, on any stream. */
+#define CMH_MIH_SUB_BITS 16
+#define CMH_MIH_SUB_RADIUS_MAX 2
+size_t cmh_mih_build_workspace_bytes(int64_t N, int32_t bits);
+int cmh_mih_build(const uint32_t* sign, int64_t N, int32_t bits, int32_t* order, int32_t* starts, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int cmh_mih_count(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, int32_t radius,
+                  const int32_t* order, const int32_t* starts, int32_t* n_hits, void* stream);
+int cmh_mih_fill(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, int32_t radius,
+                 const int32_t* order, const int32_t* starts, const int64_t* offsets, int64_t capacity, int32_t* idx, int32_t* dist,
+                 void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */
