@@ -123,6 +123,11 @@ SIGNATURES = {
     "cmh_qmi_workspace_bytes": (_sz, [_i32]),
     "cmh_qmi_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _f, _p, _p, _p, _sz, _p]),
     "cmh_qmi_loss_backward": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_ddbh_workspace_bytes": (_sz, [_i32]),
+    "cmh_ddbh_bp_loss": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32] + [C.c_double] * 6 + [_p, _p, _p, _p, _sz, _p]),
+    "cmh_ddbh_bp_loss_backward": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32] + [C.c_double] * 6 + [_p, _p, _p, _p, _p, _p]),
+    "cmh_ddbh_quant_loss": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "cmh_ddbh_quant_loss_backward": (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _p]),
     "cmh_fp8_quantize_weight": (C.c_int, [_p, _p, _p, _i32, _i32, _p]),
     "cmh_fp8_quantize": (C.c_int, [_p, _i32, _p, _i64, _f, _p]),
     "cmh_fp8_dequantize": (C.c_int, [_p, _p, _i64, _f, _p]),
@@ -1511,6 +1516,74 @@ def qmi_loss_backward(img, txt, packed, classes, sum_d, dloss, eps=1e-8):
     check(lib().cmh_qmi_loss_backward(ptr(img), ptr(txt), ptr(packed), B, K, int(classes), float(eps), ptr(sum_d), ptr(f32c(dloss).reshape(1)),
                                       ptr(dimg), ptr(dtxt), ptr(ws), ws.numel(), stream_ptr(img.device)), "cmh_qmi_loss_backward")
     return dimg, dtxt
+
+
+def _ptr_array(tensors):
+    """a host array of device pointers (the `const float* const*` operands of the DDBH entry points)"""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _ddbh_operands(what, pairs, label):
+    made = {}                                                   # one f32 contiguous copy per distinct operand: `v is u` stays so
+    pairs = [tuple(made.setdefault(id(t), f32c(t)) for t in pr) for pr in pairs]
+    label = f32c(label)
+    require_gpu(label, *[t for pr in pairs for t in pr])
+    if pairs[0][0].dim() != 2 or label.dim() != 2:
+        raise NativeError(f"{what}: codes [B, K] and labels [B, C] are expected")
+    B, K = pairs[0][0].shape
+    fit(what, (label, (B, label.shape[1])), *[(t, (B, K)) for pr in pairs for t in pr])
+    return pairs, label, B, K, label.shape[1]
+
+
+def ddbh_bp_loss(pairs, label, scalars):
+    """DDBH BPLoss.forward (train/DDBH/loss.py:15-78) for up to four (u, v) pairs over one label matrix in one launch; scalars =
+    (y_p, right, left, lowerBound, upperBound, percent) -> (loss [n], rows and count for the backward, the operands as passed)"""
+    pairs, label, B, K, Cn = _ddbh_operands("ddbh_bp_loss", pairs, label)
+    n, dev = len(pairs), label.device
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    rows = torch.empty(n, B, 8, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = workspace(lib().cmh_ddbh_workspace_bytes(B), dev, "loss")
+    check(lib().cmh_ddbh_bp_loss(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, ptr(label), B, K, Cn,
+                                 *[float(s) for s in scalars], ptr(loss), ptr(rows), ptr(count), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_ddbh_bp_loss")
+    return loss, rows, count, pairs, label
+
+
+def ddbh_bp_loss_backward(pairs, label, scalars, rows, count, dloss):
+    """-> [(du, dv)] per pair, each f32 [B, K] (two buffers even where u is v)"""
+    B, K = pairs[0][0].shape
+    n = len(pairs)
+    du = [torch.empty_like(u) for u, _ in pairs]
+    dv = [torch.empty_like(v) for _, v in pairs]
+    dloss = f32c(dloss).reshape(n)
+    check(lib().cmh_ddbh_bp_loss_backward(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, ptr(label), B, K,
+                                          label.shape[1], *[float(s) for s in scalars], ptr(rows), ptr(count), ptr(dloss),
+                                          _ptr_array(du), _ptr_array(dv), stream_ptr(label.device)), "cmh_ddbh_bp_loss_backward")
+    return list(zip(du, dv))
+
+
+def ddbh_quant_loss(hs, label):
+    """DDBH's quantisation term mean(s @ (h - sign h)^2) (train/DDBH/hash_train.py:64-76) of up to four matrices over one label
+    matrix -> (loss [n], colsum [B] for the backward, the operands as passed)"""
+    pairs, label, B, K, Cn = _ddbh_operands("ddbh_quant_loss", [(h, h) for h in hs], label)
+    hs = [h for h, _ in pairs]
+    n, dev = len(hs), label.device
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    colsum = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = workspace(lib().cmh_ddbh_workspace_bytes(B), dev, "loss")
+    check(lib().cmh_ddbh_quant_loss(_ptr_array(hs), n, ptr(label), B, K, Cn, ptr(loss), ptr(colsum), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_ddbh_quant_loss")
+    return loss, colsum, hs
+
+
+def ddbh_quant_loss_backward(hs, colsum, dloss):
+    B, K = hs[0].shape
+    dh = [torch.empty_like(h) for h in hs]
+    dloss = f32c(dloss).reshape(len(hs))
+    check(lib().cmh_ddbh_quant_loss_backward(_ptr_array(hs), len(hs), ptr(colsum), B, K, ptr(dloss), _ptr_array(dh), stream_ptr(colsum.device)),
+          "cmh_ddbh_quant_loss_backward")
+    return dh
 
 
 def dchmt_loss(img, txt, label, output_dim, similarity="euclidean", loss_type="l2", vartheta=0.5, sim_threshold=0.1):

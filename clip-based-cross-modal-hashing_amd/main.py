@@ -15,8 +15,9 @@ _REGISTRY = {
     'DNpH': ("train.DNpH_TMM.hash_train", "DNpHTMMTrainer"),
     'DMsH_LN': ("train.DMsH_LN.hash_train", "DMsH_LNTrainer"),
     'DHaPH': ("train.DHaPH.hash_train", "DHaPHTrainer"),
+    'DDBH': ("train.DDBH.hash_train", "DDBHTrainer"),
 }
-_NOT_BUILT = ['DPBE', 'DDWSH', 'DDBH', 'DScPH', 'DPSIH', 'DGHDGH']
+_NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
 
 
 class _LazyTrainers(dict):

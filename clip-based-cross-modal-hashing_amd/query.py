@@ -16,7 +16,8 @@ whose sign that code is."""
 import importlib
 
 MODELS = {"DSPH": ("model.DSPH", "MDSPH"), "DCHMT": ("model.DCHMT", "MDCMHT"), "DNPH": ("model.DNPH_TOMM", "MDNPH"),
-          "DNpH": ("model.DNpH_TMM", "MDNpH"), "DMsH_LN": ("model.DMsH_LN", "MDMsH_LN"), "DHaPH": ("model.DHaPH", "MDHaPH")}
+          "DNpH": ("model.DNpH_TMM", "MDNpH"), "DMsH_LN": ("model.DMsH_LN", "MDMsH_LN"), "DHaPH": ("model.DHaPH", "MDHaPH"),
+          "DDBH": ("model.DDBH", "MDDBH")}
 REFUSED = {"MITH": "its encoders take key padding masks and the towers' token trunks (train/MITH/hash_train.py::get_code)",
            "TwDH": "it hashes into long and short codes through centre assets (train/TwDH/hash_train.py)"}
 

@@ -334,6 +334,29 @@ int cmh_qmi_loss_backward(const float* img, const float* txt, const uint32_t* la
                           float eps, const float* sum_d, const float* dloss, float* dimg, float* dtxt, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* DDBH base-point loss, reference train/DDBH/loss.py:5-101 `BPLoss.forward(u, v, y)` (the Python walk over the rows with its two
+ * sorts and four host reads per row), for `calls` (1 .. 4) pairs (u[q], v[q]) of f32 [B,K] code matrices that share the f32 [B,C]
+ * labels: u, v are HOST arrays of `calls` device pointers (u[q] == v[q] is the intra-modal call).  The six scalars are BPLoss's
+ * attributes y_p, right, left, lowerBound, upperBound, percent (:8-13) -> loss f32 [calls], count i32 [calls] (active rows) and rows
+ * [calls, B, 8] 32-bit words (per row: the f32 roundings of BP, BP_ds and the four offsets; the kept counts; kept for the backward).
+ * Backward: du[q], dv[q] f32 [B,K] = dloss[q] * d loss[q] / d u[q], v[q] (two separate buffers even where u[q] == v[q]; their sum is
+ * that tensor's gradient); it recomputes the inner products and reads no stored matrix.  B <= 8192, K <= 1024, any C >= 1. */
+size_t cmh_ddbh_workspace_bytes(int32_t B);
+int cmh_ddbh_bp_loss(const float* const* u, const float* const* v, int32_t calls, const float* labels, int32_t B, int32_t K, int32_t C,
+                     double y_p, double right, double left, double lower_bound, double upper_bound, double percent, float* loss,
+                     void* rows, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_ddbh_bp_loss_backward(const float* const* u, const float* const* v, int32_t calls, const float* labels, int32_t B, int32_t K,
+                              int32_t C, double y_p, double right, double left, double lower_bound, double upper_bound,
+                              double percent, const void* rows, const int32_t* count, const float* dloss, float* const* du,
+                              float* const* dv, void* stream);
+/* DDBH quantisation term, reference train/DDBH/hash_train.py:64-76 `matmul(s, (h - h.sign()).pow(2)).mean()` with s the float
+ * indicator (y y^T > 0), for `calls` (1 .. 4) matrices h[q] f32 [B,K] (a HOST array of device pointers) -> loss f32 [calls] and
+ * colsum f32 [B] (the column sums of s, kept for the backward).  Backward: dh[q] = dloss[q] * d loss[q] / d h[q]. */
+int cmh_ddbh_quant_loss(const float* const* h, int32_t calls, const float* labels, int32_t B, int32_t K, int32_t C, float* loss,
+                        float* colsum, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_ddbh_quant_loss_backward(const float* const* h, int32_t calls, const float* colsum, int32_t B, int32_t K, const float* dloss,
+                                 float* const* dh, void* stream);
+
 /* DMsH-LN multi-similarity loss, reference train/DMsH_LN/MSLOSS.py:13-55 `MultiSimilarityLoss.forward(feats, labels, feat2)` in the
  * branch its trainer takes (train/DMsH_LN/hash_train.py:58-60; not the "cifar10-1" branch): feats (and feat2, NULL = feats) f32
  * [B,K] hash outputs, labels f32 [B,Kl] = the LabelNet codes (two samples are similar when their codes' dot product is > 0)
