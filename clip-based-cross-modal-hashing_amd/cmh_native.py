@@ -188,6 +188,8 @@ SIGNATURES = {
     "cmh_mih_build": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _sz, _p]),
     "cmh_mih_count": (C.c_int, [_p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _p]),
     "cmh_mih_fill": (C.c_int, [_p, _i32, _p, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p]),
+    "cmh_mih_knn_count": (C.c_int, [_p, _i32, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "cmh_mih_knn_fill": (C.c_int, [_p, _i32, _p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p]),
     "cmh_topk_merge": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cmh_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_dsph_hyp_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
@@ -1199,12 +1201,12 @@ def mih_build(sign, bits):
     return order, starts
 
 
-def _mih_operands(what, q_sign, db_sign, bits, radius, order, starts):
+def _mih_operands(what, q_sign, db_sign, bits, radius, order, starts, radius_name="radius"):
     require_gpu(q_sign, db_sign, order, starts)
     n, bits, m = _mih_table(what, db_sign, bits)
     radius = int(radius)
     if not 0 <= radius <= (MIH_SUB_RADIUS_MAX + 1) * m - 1:
-        raise NativeError(f"{what}: radius={radius} outside [0, {(MIH_SUB_RADIUS_MAX + 1) * m - 1}] at {bits} bits")
+        raise NativeError(f"{what}: {radius_name}={radius} outside [0, {(MIH_SUB_RADIUS_MAX + 1) * m - 1}] at {bits} bits")
     Q = q_sign.shape[0]
     if not 1 <= Q <= QUERIES_MAX:
         raise NativeError(f"{what}: Q={Q} outside [1, {QUERIES_MAX}] per call")
@@ -1237,6 +1239,39 @@ def mih_fill(q_sign, db_sign, bits, radius, order, starts, offsets, total):
     dist = torch.empty(total, dtype=torch.int32, device=dev)
     check(lib().cmh_mih_fill(ptr(q_sign), Q, ptr(db_sign), n, bits, radius, ptr(order), ptr(starts), ptr(offsets), total, ptr(idx),
                              ptr(dist), stream_ptr(dev)), "cmh_mih_fill")
+    return idx, dist
+
+
+def mih_knn_count(q_sign, db_sign, bits, k, r_cap, order, starts):
+    """-> (radius, n_ball, n_less) int32 [Q]: per query the smallest radius r* <= r_cap whose ball holds at least k items, found by
+    growing it through mih_build's tables, |ball(r*)| and |ball(r* - 1)|; radius = -1 and n_ball = n_less = |ball(r_cap)| where
+    fewer than k items lie within r_cap."""
+    Q, n, bits, r_cap = _mih_operands("mih_knn_count", q_sign, db_sign, bits, r_cap, order, starts, "r_cap")
+    k = int(k)
+    if not 1 <= k <= n:
+        raise NativeError(f"mih_knn_count: k={k} outside [1, N={n}]")
+    dev = q_sign.device
+    radius, n_ball, n_less = (torch.empty(Q, dtype=torch.int32, device=dev) for _ in range(3))
+    check(lib().cmh_mih_knn_count(ptr(q_sign), Q, ptr(db_sign), n, bits, k, r_cap, ptr(order), ptr(starts), ptr(radius), ptr(n_ball),
+                                  ptr(n_less), stream_ptr(dev)), "cmh_mih_knn_count")
+    return radius, n_ball, n_less
+
+
+def mih_knn_fill(q_sign, db_sign, bits, radius, order, starts, offsets, total):
+    """radius int32 [Q] (mih_knn_count's; a query with a radius below 0 is not walked), offsets int64 [Q + 1] = the exclusive prefix
+    sum of the walked queries' n_ball (0 for the others), total = its last entry (>= 1) -> (idx int32 [total], dist int32 [total]):
+    query q's ball from offsets[q] on, each item once, in the order of the kernel's walk (the same on every call)."""
+    Q, n, bits, _ = _mih_operands("mih_knn_fill", q_sign, db_sign, bits, 0, order, starts)
+    dev = q_sign.device
+    total = int(total)
+    if radius.dtype != torch.int32 or tuple(radius.shape) != (Q,) or not radius.is_contiguous() or radius.device != dev:
+        raise NativeError("mih_knn_fill: radius is a contiguous int32 tensor [Q] on the operands' device")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (Q + 1,) or not offsets.is_contiguous() or offsets.device != dev:
+        raise NativeError("mih_knn_fill: offsets is a contiguous int64 tensor [Q + 1] on the operands' device")
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.int32, device=dev)
+    check(lib().cmh_mih_knn_fill(ptr(q_sign), Q, ptr(db_sign), n, bits, ptr(radius), ptr(order), ptr(starts), ptr(offsets), total,
+                                 ptr(idx), ptr(dist), stream_ptr(dev)), "cmh_mih_knn_fill")
     return idx, dist
 
 

@@ -86,7 +86,15 @@ reports are printed and stored.  The exclusions are those of --stats.
 prints what --radius 4 prints, line for line, from the index's substring tables (CodeIndex.lookup_far: multi-index hashing on 16-bit
 substrings, the candidates verified with the full distance).  R is a whole number of bits up to 3 ceil(bits / 16) - 1 (11 at 64
 bit, 23 at 128); codes up to 128 bit without zero entries (--radius takes the others).  --near excludes what --lookup excludes,
-and --lookup."""
+and --lookup.
+
+    python retrieve.py --codes <file>.mat --direction i2t --k 10 --tables [--index db.npz] [--queries a:b]
+    python retrieve.py --text "a dog on a beach" --tables --index db.npz --method DSPH ... --k 10
+
+prints what the same command prints without --tables, line for line, from the index's substring tables (CodeIndex.search_tables:
+every query's radius grown until its ball holds k items; a query whose ball is too wide, or not within 3 ceil(bits / 16) - 1 bits,
+is answered by the scan).  Codes up to 128 bit without zero entries.  --tables excludes --soft, the filters, --graded, --radius,
+--lookup, --near, --map, --recall, --stats and --bucket-stats."""
 import argparse
 import sys
 
@@ -139,8 +147,16 @@ def parse(argv=None):
     p.add_argument("--lookup", type=int, default=None, metavar="R", help="print every database item within R = 0, 1 or 2 bits of each query, as --radius does, from the index's bucket table")
     p.add_argument("--bucket-stats", action="store_true", help="print how the items of the file's database sides (or of --index) spread over their distinct codes in place of a search")
     p.add_argument("--near", type=int, default=None, metavar="R", help="print every database item within R whole bits of each query, as --radius does, from the index's substring tables (R up to 3 ceil(bits / 16) - 1)")
+    p.add_argument("--tables", action="store_true", help="find the k nearest through the index's substring tables (the radius grown per query) in place of the scan: the same lines")
     args = p.parse_args(argv)
     args.ask = getattr(args, "ask", None) or []
+    if args.tables:
+        for flag, given in (("--soft", args.soft), ("--graded", args.graded), ("--radius", args.radius is not None),
+                            ("--lookup", args.lookup is not None), ("--near", args.near is not None), ("--map", args.map),
+                            ("--recall", args.recall), ("--stats", args.stats), ("--bucket-stats", args.bucket_stats)) \
+                + tuple((f, getattr(args, f[2:].replace("-", "_")) is not None) for f in FILTERS):
+            if given:
+                p.error(f"--tables and {flag} exclude each other")
     if args.near is not None:
         for flag, given in (("--radius", args.radius is not None), ("--lookup", args.lookup is not None), ("--k", args.k is not None),
                             ("--map", args.map), ("--graded", args.graded), ("--recall", args.recall), ("--soft", args.soft),
@@ -350,6 +366,15 @@ def stats(args):
     return 0
 
 
+def search_tables(index, queries, k, labels):
+    """--tables: CodeIndex.search_tables, its refusals (zeros in the codes, more than 128 bits) as the command's."""
+    import cmh_native as N
+    try:
+        return index.search_tables(queries, k, labels)
+    except N.NativeError as e:
+        raise SystemExit(f"--tables: {e}")
+
+
 def ask(args):
     """--text / --image: encode the questions, search the index, print one block per question."""
     from query import QueryEncoder, check_method
@@ -376,7 +401,10 @@ def ask(args):
         rows.append(codes[kind][at[kind]])
         at[kind] += 1
     mask = item_mask(args, index)
-    got = index.search_soft(torch.stack(rows), k, mask=mask) if args.soft else index.search(torch.stack(rows), k, mask=mask)
+    if args.tables:
+        got = search_tables(index, torch.stack(rows), k, None)
+    else:
+        got = index.search_soft(torch.stack(rows), k, mask=mask) if args.soft else index.search(torch.stack(rows), k, mask=mask)
     idx, dist = (t.cpu().numpy() for t in got[:2])
     count = [k] * len(rows) if mask is None else got[3].cpu().tolist()      # a filtered row holds only what the filter admits
     for i, (kind, value) in enumerate(args.ask):
@@ -437,7 +465,9 @@ def main(argv=None):
     args.k = 10 if args.k is None else args.k
     mask = item_mask(args, index)
     count = [args.k] * (hi - lo)
-    if mask is None:
+    if args.tables:
+        out = [t.cpu().numpy() for t in search_tables(index, queries, args.k, labels)]
+    elif mask is None:
         out = [t.cpu().numpy() for t in index.search(queries, args.k, labels, graded=args.graded)]
     else:
         idx, dist, rel, found = index.search(queries, args.k, labels, mask=mask)

@@ -1020,6 +1020,24 @@ def substring_radii(bits, radius):
     return [a if j <= b else a - 1 for j in range(m)]
 
 
+def knn_steps(bits, r_cap):
+    """The growth steps 0 .. r_cap of the k-nearest search through the substring tables (csrc/retrieval_mih.hip) ->
+    [(substring, level)]: with m = ceil(bits / 16), step s = t m + j (t = 0, 1, 2; j < m) probes substring j at EXACTLY level t,
+    the keys that are the query's with exactly t of the substring's bits flipped.  After steps 0 .. r substring j has been probed
+    at every level up to substring_radii(bits, r)[j], so every item within r whole bits has been reached; item x is first reached
+    at step min_j (d_j m + j), a unique minimum (the j are distinct below m), and counts there alone.  r_cap <= 3 m - 1."""
+    try:
+        m = len(substring_radii(bits, r_cap))
+    except N.NativeError as e:
+        raise N.NativeError(f"knn_steps: {e}".replace("radius=", "r_cap=")) from None
+    return [(s % m, s // m) for s in range(int(r_cap) + 1)]
+
+
+MAX_BALL_SHARE = 64                  # SubstringTables.topk answers a query through the tables while its ball is at most 1 / 64 of the
+                                     # database: set from the measurement of DESIGN.md 9.13 (level with the scan at about 2 %, behind at 5 %)
+MAX_HITS_TOPK = 2 ** 28              # entries of one fill of SubstringTables.topk: 2 GiB of idx + dist.  A memory budget, not a measurement
+
+
 def _check_far(what, bits, query_bits, radius):
     """What a substring lookup refuses by name before anything is packed, built or launched."""
     if query_bits != bits:
@@ -1030,6 +1048,27 @@ def _check_far(what, bits, query_bits, radius):
         raise N.NativeError(f"{what}: {e}") from None
 
 
+def _check_topk(what, bits, n, query_bits, k, r_cap, max_ball, max_hits):
+    """What a k-nearest search through the substring tables refuses by name before anything is packed, built or launched ->
+    (r_cap, max_ball, max_hits) with the defaults in: r_cap = 3 ceil(bits / 16) - 1, max_ball = n // MAX_BALL_SHARE, max_hits =
+    MAX_HITS_TOPK."""
+    if query_bits != bits:
+        raise N.NativeError(f"{what}: {query_bits}-bit queries for an index of {bits} bits")
+    if bits > N.BUCKET_BITS_MAX:
+        raise N.NativeError(f"{what}: {bits}-bit codes exceed BUCKET_BITS_MAX = {N.BUCKET_BITS_MAX} (search takes them)")
+    if isinstance(k, bool) or k != int(k) or not 1 <= int(k) <= n:
+        raise N.NativeError(f"{what}: k={k} outside [1, N={n}]")
+    top = (N.MIH_SUB_RADIUS_MAX + 1) * N.mih_substrings(bits) - 1
+    r_cap = top if r_cap is None else r_cap
+    if isinstance(r_cap, bool) or r_cap != int(r_cap) or not 0 <= int(r_cap) <= top:
+        raise N.NativeError(f"{what}: r_cap={r_cap} is not a whole number of bits in [0, {top}] for {bits}-bit codes")
+    max_ball = n // MAX_BALL_SHARE if max_ball is None else int(max_ball)
+    max_hits = MAX_HITS_TOPK if max_hits is None else int(max_hits)
+    if max_ball < 0 or max_hits < 0:
+        raise N.NativeError(f"{what}: max_ball={max_ball}, max_hits={max_hits}: below 0")
+    return int(r_cap), max_ball, max_hits
+
+
 class SubstringTables:
     """Multi-index hashing over a packed database (csrc/retrieval_mih.hip), all on the GPU: one direct-addressed
     table per 16-bit substring of the codes.
@@ -1038,11 +1077,13 @@ class SubstringTables:
       sign   int32 [n, W]       the database's sign plane (candidates are verified against it)
       bits, n, m (= ceil(bits / 16)), max_radius (= 3 m - 1)
     build(planes, bits) sorts m times (cmh_mih_build); lookup(...) answers "every item within `radius` whole bits" by probing each
-    table at substring_radii(bits, radius) and verifying the buckets' items: the cost follows the buckets' sizes, not n.  Codes in
+    table at substring_radii(bits, radius) and verifying the buckets' items: the cost follows the buckets' sizes, not n;
+    topk(...) answers "the k nearest items" by growing every query's radius (knn_steps; cmh_mih_knn_count / _fill).  Codes in
     {-1, +1} only, up to 128 bit."""
 
     def __init__(self, order, starts, sign, bits, n):
         self.order, self.starts, self.sign, self.bits, self.n, self.m = order, starts, sign, int(bits), int(n), order.shape[0]
+        self._nz = None                                            # the scan route's nz plane: _planes() makes it on first use
 
     @property
     def max_radius(self):
@@ -1115,6 +1156,74 @@ class SubstringTables:
             base = offs[-1][-1]
         return (torch.cat(offs),) + tuple(None if ts[0] is None else torch.cat(ts) for ts in zip(*[p[1:] for p in parts]))
 
+    def topk(self, query_codes, k, query_labels=None, retrieval_L=None, r_cap=None, max_ball=None, max_hits=None):
+        """-> hamming_topk's tuple (idx int32 [Q, k], dist f32 [Q, k][, rel uint8 [Q, k] with labels]), bit for bit: the k nearest
+        items of every query, distance ascending, ties by database index, found by growing each query's radius through the tables
+        (knn_steps) until its ball holds k items: the cost follows that ball, not n.  A query whose ball within r_cap (default
+        max_radius) holds fewer than k items, or whose ball holds more than max_ball (default n // MAX_BALL_SHARE) items, is
+        answered by the scan instead; max_hits (default MAX_HITS_TOPK) bounds the entries of one fill, and a ball beyond it goes
+        to the scan too.
+        query_codes f32 [Q, bits] in {-1, +1}; query_labels / retrieval_L: multi-hot [Q, C] / [n, C], both or neither."""
+        if (query_labels is None) != (retrieval_L is None):
+            raise N.NativeError("SubstringTables.topk: labels on one side only")
+        if retrieval_L is not None and retrieval_L.shape[0] != self.n:
+            raise N.NativeError(f"SubstringTables.topk: labels of {retrieval_L.shape[0]} items for tables of {self.n}")
+        caps = _check_topk("SubstringTables.topk", self.bits, self.n, query_codes.shape[-1], k, r_cap, max_ball, max_hits)
+        dev = self.order.device
+        idx, dist, rel = self._topk("SubstringTables.topk", _codes(query_codes, dev), k, _labels(query_labels, dev),
+                                    _labels(retrieval_L, dev), *caps)
+        return (idx, dist) if rel is None else (idx, dist, rel)
+
+    def _planes(self):
+        """(sign, nz) of the database for the scan route: the codes hold no 0, so nz is _nz_mask in every row (made on first use)."""
+        if self._nz is None:
+            self._nz = _nz_mask(self.bits, self.sign.device).repeat(self.n, 1).contiguous()
+        return self.sign, self._nz
+
+    def _topk(self, what, qp, k, ql, rl, r_cap, max_ball, max_hits, shard_items=None):
+        """The packed form -> (idx, dist, rel or None).  Per block of queries: the count pass (r*, |ball(r*)| per query), ONE host read
+        of both, then the admitted queries (r* >= 0, ball within max_ball and max_hits) in groups of consecutive queries whose balls
+        sum to at most max_hits: cumsum, fill, one stable sort on (query, distance, item), the first k of every list gathered; the
+        other queries go through _search (the scan) as gathered rows and are scattered back."""
+        k = int(k)
+        _no_zeros(what, "a query", qp, self.bits)
+        dev = self.order.device
+        Q = qp[0].shape[0]
+        out_idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        out_dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        for cut in _cuts(Q, N.QUERIES_MAX):
+            qs = _rows(qp[0], cut, Q).contiguous()
+            nq = cut[1] - cut[0]
+            radius, n_ball, _ = N.mih_knn_count(qs, self.sign, self.bits, k, r_cap, self.order, self.starts)
+            admitted = (radius >= 0) & (n_ball <= min(max_ball, max_hits))
+            walk = torch.where(admitted, radius, torch.full_like(radius, -1))
+            sizes = torch.where(admitted, n_ball, torch.zeros_like(n_ball)).long()
+            ends = torch.cumsum(sizes, 0)
+            host_admitted, host_ends = torch.stack((admitted.long(), ends)).cpu()        # the block's one read (two small vectors)
+            begin = 0
+            while begin < nq:                                                          # groups of consecutive queries within max_hits
+                base = int(host_ends[begin - 1]) if begin else 0
+                end = max(begin + 1, int(torch.searchsorted(host_ends, base + max_hits, right=True)))
+                T = int(host_ends[end - 1]) - base
+                if T:
+                    off = torch.zeros(end - begin + 1, dtype=torch.int64, device=dev)
+                    off[1:] = ends[begin:end] - base
+                    idx, dist = N.mih_knn_fill(qs[begin:end], self.sign, self.bits, walk[begin:end].contiguous(), self.order,
+                                               self.starts, off, T)
+                    query = torch.repeat_interleave(torch.arange(end - begin, device=dev), sizes[begin:end], output_size=T)
+                    by = torch.sort(((query * (self.bits + 1) + dist) << 31) + idx, stable=True)[1]   # the walk's order -> (distance, item)
+                    rows = torch.nonzero(admitted[begin:end]).squeeze(1)                # an admitted ball holds at least k items
+                    first = by[(off[rows][:, None] + torch.arange(k, device=dev)[None, :]).reshape(-1)]
+                    out_idx[cut[0] + begin + rows] = idx[first].view(-1, k)
+                    out_dist[cut[0] + begin + rows] = dist[first].view(-1, k).to(torch.float32)
+                begin = end
+            if not bool(host_admitted.all()):
+                rows = torch.nonzero(~admitted).squeeze(1) + cut[0]
+                scan = _search(what, tuple(p[rows] for p in qp), self._planes(), self.bits, k, None, None, shard_items)
+                out_idx[rows], out_dist[rows] = scan[0], scan[1]
+        rel = None if ql is None else ((rl[out_idx.long()] & ql[:, None, :]) != 0).any(-1).to(torch.uint8)
+        return out_idx, out_dist, rel
+
 
 class CodeIndex:
     """A database of hash codes, packed once.  search(query_codes, k) -> hamming_topk's tuple (graded=True: graded_topk's);
@@ -1122,7 +1231,7 @@ class CodeIndex:
     search of range_search through that table (radius 0, 1, 2; codes without zeros); bucket_stats() -> how the items spread over
     their distinct codes; substrings() -> the SubstringTables of the index (likewise built on first use), lookup_far(query_codes,
     radius) -> range_search's tuple through them for a whole-bit radius up to 3 ceil(bits / 16) - 1, near_duplicates(radius) ->
-    duplicates' tuple through them;
+    duplicates' tuple through them, search_tables(query_codes, k) -> search's tuple through them (the radius grown per query);
     search_soft(u, k) -> soft_topk's; map_soft(u, query_labels) -> soft_mean_average_precision's; mask(...) -> an ItemMask for search(..., mask=) / search_soft(..., mask=);
     range_search(query_codes, radius) -> hamming_range's; duplicates(radius) -> the index's near-duplicate lists;
     rank_of(query_codes, targets) -> target_counts'; recall(query_codes, targets) -> recall_at_k's; stats() -> code_stats'.
@@ -1338,6 +1447,23 @@ class CodeIndex:
         if self._substrings is None:
             self._substrings = SubstringTables.build(self.planes, self.bits)
         return self._substrings
+
+    def search_tables(self, query_codes, k, query_labels=None, **caps):
+        """search(query_codes, k) through the substring tables (SubstringTables.topk; caps: r_cap, max_ball, max_hits): the same
+        tuple, bit for bit, for codes up to 128 bit and no 0 entry on either side; the cost follows the size of the k-th
+        neighbour's Hamming ball, not the size of the index (DESIGN.md 9.13 says when that wins).  Nothing routes here by itself."""
+        if query_labels is not None and self.labels is None:
+            raise N.NativeError("CodeIndex.search_tables: query labels given, but the index has none")
+        unknown = set(caps) - {"r_cap", "max_ball", "max_hits"}
+        if unknown:
+            raise TypeError(f"CodeIndex.search_tables: unknown option {sorted(unknown)[0]!r} (r_cap, max_ball, max_hits)")
+        limits = _check_topk("CodeIndex.search_tables", self.bits, self.size, query_codes.shape[-1], k, caps.get("r_cap"),
+                             caps.get("max_ball"), caps.get("max_hits"))
+        tables = self.substrings()
+        ql = _labels(query_labels, self.device)
+        idx, dist, rel = tables._topk("CodeIndex.search_tables", _codes(query_codes, self.device), k, ql,
+                                      self.labels if ql is not None else None, *limits, shard_items=self.shard_items)
+        return (idx, dist) if rel is None else (idx, dist, rel)
 
     def lookup_far(self, query_codes, radius, query_labels=None, max_hits=None):
         """range_search(query_codes, radius) through the substring tables: the same tuple, element for element, for a whole-bit

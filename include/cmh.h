@@ -783,6 +783,31 @@ int cmh_mih_fill(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int
                  const int32_t* order, const int32_t* starts, const int64_t* offsets, int64_t capacity, int32_t* idx, int32_t* dist,
                  void* stream);
 
+/* The k nearest through the same tables, the radius grown per query (csrc/retrieval_mih.hip).  GROWTH STEP
+ * s = t m + j (t = 0, 1, 2; j < m) probes substring j at exactly level t: the keys that are the query's with exactly t of its s_j
+ * bits flipped, in the order above (1, s_j or s_j (s_j - 1) / 2 probes).  After steps 0 .. r the substrings have been probed at
+ * the radii a_j of radius r, so every item within r has been reached; item x is first reached at step f(x) = min_j (d_j m + j), a
+ * unique minimum, and a candidate reached through (j, t) counts, or is emitted, iff f(x) = t m + j.  One workgroup of 256 threads
+ * per query walks the steps in order and verifies every candidate with the full distance d.
+ *   cmh_mih_knn_count: r*(q) = the smallest r <= r_cap with |ball(q, r)| >= k, decided after step r (the numbers of the items at
+ *          every distance d <= r are complete then).  radius i32 [Q] = r*, n_ball i32 [Q] = |ball(r*)|, n_less i32 [Q] =
+ *          |ball(r* - 1)| (0 at r* = 0); fewer than k items within r_cap: radius = -1 and n_ball = n_less = |ball(r_cap)|.
+ *   cmh_mih_knn_fill: radius i32 [Q] is READ; the walk over steps 0 .. radius[q] emits every item with d <= radius[q] exactly once
+ *          at offsets[q] .. as (database index, whole-bit distance), in walk order (step, probe, position in the bucket) - the
+ *          same on every call.  offsets i64 [Q + 1] (aligned to 8 bytes) = the exclusive prefix sum of the lists' sizes (n_ball,
+ *          0 where nothing is walked); idx, dist i32 [capacity], capacity >= 1.  Nothing is written for radius[q] < 0 or
+ *          radius[q] > 3 m - 1 (such a query is not walked: the loop bound is never an operand's word beyond 3 m - 1), and
+ *          nothing at or behind min(offsets[q + 1], capacity).
+ * 1 <= Q <= 65535 per call, 1 <= N <= 2^31 - 1, 1 <= bits <= CMH_BUCKET_BITS_MAX, 1 <= k <= N, 0 <= r_cap <= 3 m - 1, db_sign rows
+ * aligned as for cmh_mih_count.  -1 before any launch for null operands, sizes outside the limits (the message names the limit),
+ * misaligned operands.  No atomics on any output, every output word written once, every index read from a table checked against
+ * N, bucket bounds clamped to [0, N], no kernel waits for another workgroup: two calls give equal bytes, on any stream. */
+int cmh_mih_knn_count(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, int32_t k, int32_t r_cap,
+                      const int32_t* order, const int32_t* starts, int32_t* radius, int32_t* n_ball, int32_t* n_less, void* stream);
+int cmh_mih_knn_fill(const uint32_t* q_sign, int32_t Q, const uint32_t* db_sign, int64_t N, int32_t bits, const int32_t* radius,
+                     const int32_t* order, const int32_t* starts, const int64_t* offsets, int64_t capacity, int32_t* idx,
+                     int32_t* dist, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pairwise similarity / quantisation losses (forward).  All f32; `loss` is a device scalar.
  * ------------------------------------------------------------------------------------------- */
