@@ -44,6 +44,10 @@ def add_flags(parser, table):
             kw["choices"] = ["reference", "stable"]
         if flag == "--noise-assign":
             kw["choices"] = ["gpu", "host"]
+        if flag == "--projection":
+            kw["choices"] = ["pca", "random"]
+        if flag == "--rotation":
+            kw["choices"] = ["itq", "none"]
         parser.add_argument(flag, **kw)
     return parser
 

@@ -200,6 +200,20 @@ SIGNATURES = {
     "cmh_dnph_loss": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _p, _p, _sz, _p]),
     "cmh_assign_rows_workspace_bytes": (_sz, [_i32, _i32]),
     "cmh_assign_rows": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
+    # training-free heads (csrc/itq.hip): none of the cmh_itq_* entries has an upstream counterpart
+    "cmh_itq_moments_workspace_bytes": (_sz, [_i64, _i32]),             # no upstream counterpart
+    "cmh_itq_moments": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _sz, _p]),             # no upstream counterpart
+    "cmh_itq_covariance": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p]),     # no upstream counterpart
+    "cmh_itq_eigh_workspace_bytes": (_sz, [_i32, _i32]),                # no upstream counterpart
+    "cmh_itq_eigh": (C.c_int, [_p, _i32, _i32, _p, _p, C.POINTER(C.c_int32), _p, _sz, _p]),   # no upstream counterpart
+    "cmh_itq_project": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),              # no upstream counterpart
+    "cmh_itq_step_workspace_bytes": (_sz, [_i64, _i32]),                # no upstream counterpart
+    "cmh_itq_step": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),          # no upstream counterpart
+    "cmh_itq_polar_workspace_bytes": (_sz, [_i32]),                     # no upstream counterpart
+    "cmh_itq_polar": (C.c_int, [_p, _i32, _p, _p, _p, _sz, _p]),                            # no upstream counterpart
+    "cmh_itq_rotate_workspace_bytes": (_sz, [_i64, _i32]),              # no upstream counterpart
+    "cmh_itq_rotate": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _sz, _p]),      # no upstream counterpart
+    "cmh_itq_heads": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),   # no upstream counterpart
     "cmh_vit_encode_tokens": (C.c_int, [C.POINTER(VitWeights), _p, _i32, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens_packed": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
@@ -1713,6 +1727,147 @@ def assign_rows(emb, rows, return_col=False):
     if single:
         out, col = out[0], (None if col is None else col[0])
     return (out, col) if return_col else out
+
+
+# ------------------------------------------------------------------------------------------ training-free heads (csrc/itq.hip)
+ITQ_MAX_D, ITQ_MAX_K, ITQ_EIGH_SWEEPS = 1024, 128, 60
+
+
+def _f64c(t):
+    if t.dtype != torch.float64:
+        raise NativeError(f"the fit runs in f64: operand of dtype {t.dtype}")
+    return t.contiguous()
+
+
+def itq_moments(F, sums=None):
+    """Running f64 sums of one batch of f32 features F [N, D]: (sum [D], sq [D, D]) (+)= (sum_n f, sum_n f f^T).  `sums`: the pair a
+    previous call returned, updated in place; None starts new ones."""
+    F = f32c(F)
+    require_gpu(F)
+    if F.dim() != 2 or F.shape[0] < 1:
+        raise NativeError(f"itq_moments: features {tuple(F.shape)}, expected [N, D] with N >= 1")
+    n, d = F.shape
+    dev = F.device
+    if sums is None:
+        sums, acc = (torch.empty(d, dtype=torch.float64, device=dev), torch.empty(d, d, dtype=torch.float64, device=dev)), 0
+    else:
+        fit("itq_moments", (sums[0], (d,)), (sums[1], (d, d)))
+        _f64c(sums[0]), _f64c(sums[1])
+        acc = 1
+    ws = workspace(lib().cmh_itq_moments_workspace_bytes(n, d), dev, "itq")
+    check(lib().cmh_itq_moments(ptr(F), n, d, ptr(sums[0]), ptr(sums[1]), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_moments")
+    return sums
+
+
+def itq_covariance(sums_i, sums_t, n):
+    """-> mu_i [D], mu_t [D], alpha [2], C [D, D] (f64) from the running sums of both modalities over n pairs."""
+    d = sums_i[0].shape[0]
+    fit("itq_covariance", (sums_i[0], (d,)), (sums_i[1], (d, d)), (sums_t[0], (d,)), (sums_t[1], (d, d)))
+    ops = [_f64c(t) for t in (sums_i[0], sums_i[1], sums_t[0], sums_t[1])]
+    require_gpu(*ops)
+    dev = ops[0].device
+    mu_i, mu_t = (torch.empty(d, dtype=torch.float64, device=dev) for _ in range(2))
+    alpha = torch.empty(2, dtype=torch.float64, device=dev)
+    cov = torch.empty(d, d, dtype=torch.float64, device=dev)
+    check(lib().cmh_itq_covariance(*(ptr(t) for t in ops), int(n), d, ptr(mu_i), ptr(mu_t), ptr(alpha), ptr(cov), stream_ptr(dev)),
+          "cmh_itq_covariance")
+    return mu_i, mu_t, alpha, cov
+
+
+def itq_eigh(cov, max_sweeps=ITQ_EIGH_SWEEPS):
+    """Symmetric eigen-decomposition of cov [D, D] f64 (upper triangle) by cyclic Jacobi -> evals [D] descending, evecs [D, D]
+    (column j goes with evals[j], largest entry positive), sweeps run, converged."""
+    cov = _f64c(cov)
+    require_gpu(cov)
+    if cov.dim() != 2 or cov.shape[0] != cov.shape[1]:
+        raise NativeError(f"itq_eigh: matrix {tuple(cov.shape)}, expected [D, D]")
+    d, dev = cov.shape[0], cov.device
+    evals = torch.empty(d, dtype=torch.float64, device=dev)
+    evecs = torch.empty(d, d, dtype=torch.float64, device=dev)
+    info = (C.c_int32 * 2)(0, 0)
+    ws = workspace(lib().cmh_itq_eigh_workspace_bytes(d, max_sweeps), dev, "itq")
+    check(lib().cmh_itq_eigh(ptr(cov), d, max_sweeps, ptr(evals), ptr(evecs), info, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_eigh")
+    return evals, evecs, int(info[0]), bool(info[1])
+
+
+def itq_project(F, mu, alpha, P, out=None):
+    """V [N, K] f64 = alpha * (F - mu) P; alpha: one f64 element on the device; out: a [N, K] f64 view to fill (rows of a larger V)."""
+    F, mu, alpha, P = f32c(F), _f64c(mu), _f64c(alpha), _f64c(P)
+    require_gpu(F, mu, alpha, P)
+    n, d = F.shape
+    k = P.shape[1]
+    fit("itq_project", (mu, (d,)), (P, (d, k)))
+    if alpha.numel() != 1:
+        raise NativeError("itq_project: alpha must hold one element")
+    if out is None:
+        out = torch.empty(n, k, dtype=torch.float64, device=F.device)
+    fit("itq_project", (out, (n, k)))
+    if out.dtype != torch.float64 or not out.is_contiguous():
+        raise NativeError("itq_project: out must be a contiguous f64 tensor")
+    check(lib().cmh_itq_project(ptr(F), n, d, k, ptr(mu), ptr(alpha), ptr(P), ptr(out), stream_ptr(F.device)), "cmh_itq_project")
+    return out
+
+
+def itq_step(V, R):
+    """One pass: Z = V R [rows, K] f64, B = (Z >= 0 ? +1 : -1) int8, M = B^T V [K, K], obj2 = (|B - Z|^2, |Z|^2)."""
+    V, R = _f64c(V), _f64c(R)
+    require_gpu(V, R)
+    rows, k = V.shape
+    fit("itq_step", (R, (k, k)))
+    dev = V.device
+    Z = torch.empty(rows, k, dtype=torch.float64, device=dev)
+    B = torch.empty(rows, k, dtype=torch.int8, device=dev)
+    M = torch.empty(k, k, dtype=torch.float64, device=dev)
+    obj2 = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = workspace(lib().cmh_itq_step_workspace_bytes(rows, k), dev, "itq")
+    check(lib().cmh_itq_step(ptr(V), rows, k, ptr(R), ptr(Z), ptr(B), ptr(M), ptr(obj2), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_step")
+    return Z, B, M, obj2
+
+
+def itq_polar(M, want_sweeps=False):
+    """(orthogonal polar factor of M [K, K] f64)^T, ITQ's rotation update."""
+    M = _f64c(M)
+    require_gpu(M)
+    if M.dim() != 2 or M.shape[0] != M.shape[1]:
+        raise NativeError(f"itq_polar: matrix {tuple(M.shape)}, expected [K, K]")
+    k, dev = M.shape[0], M.device
+    R = torch.empty(k, k, dtype=torch.float64, device=dev)
+    sweeps = torch.zeros(1, dtype=torch.int32, device=dev) if want_sweeps else None
+    ws = workspace(lib().cmh_itq_polar_workspace_bytes(k), dev, "itq")
+    check(lib().cmh_itq_polar(ptr(M), k, ptr(R), ptr(sweeps), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_polar")
+    return (R, sweeps) if want_sweeps else R
+
+
+def itq_rotate(V, R0, iters):
+    """ITQ from R0 -> R [K, K], obj [iters + 1] (|B - Z|^2 at the start of each iteration, then for R), zz = |V R|^2; all on the
+    device, nothing is read back."""
+    V, R0 = _f64c(V), _f64c(R0)
+    require_gpu(V, R0)
+    rows, k = V.shape
+    fit("itq_rotate", (R0, (k, k)))
+    dev = V.device
+    R = torch.empty(k, k, dtype=torch.float64, device=dev)
+    obj = torch.empty(int(iters) + 1, dtype=torch.float64, device=dev)
+    zz = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = workspace(lib().cmh_itq_rotate_workspace_bytes(rows, k), dev, "itq")
+    check(lib().cmh_itq_rotate(ptr(V), rows, k, ptr(R0), int(iters), ptr(R), ptr(obj), ptr(zz), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_itq_rotate")
+    return R, obj, zz
+
+
+def itq_heads(P, R, mu_i, mu_t, alpha, zz, rows):
+    """-> W_i, b_i, W_t, b_t (f32 [K, D] / [K]) and s (f64 [1]): s = 0.5 / rms(V R), W_m = s alpha_m (P R)^T, b_m = -W_m mu_m."""
+    ops = [_f64c(t) for t in (P, R, mu_i, mu_t, alpha, zz)]
+    require_gpu(*ops)
+    d, k = ops[0].shape
+    fit("itq_heads", (ops[1], (k, k)), (ops[2], (d,)), (ops[3], (d,)), (ops[4], (2,)), (ops[5], (1,)))
+    dev = ops[0].device
+    W_i, W_t = (torch.empty(k, d, dtype=torch.float32, device=dev) for _ in range(2))
+    b_i, b_t = (torch.empty(k, dtype=torch.float32, device=dev) for _ in range(2))
+    s = torch.empty(1, dtype=torch.float64, device=dev)
+    check(lib().cmh_itq_heads(*(ptr(t) for t in ops), int(rows), d, k, ptr(W_i), ptr(b_i), ptr(W_t), ptr(b_t), ptr(s), stream_ptr(dev)),
+          "cmh_itq_heads")
+    return W_i, b_i, W_t, b_t, s
 
 
 # ------------------------------------------------------------------------------------------ optimiser

@@ -16,6 +16,7 @@ _REGISTRY = {
     'DMsH_LN': ("train.DMsH_LN.hash_train", "DMsH_LNTrainer"),
     'DHaPH': ("train.DHaPH.hash_train", "DHaPHTrainer"),
     'DDBH': ("train.DDBH.hash_train", "DDBHTrainer"),
+    'ITQ': ("train.ITQ.hash_train", "ITQTrainer"),       # training-free: LSH / PCAH / ITQ heads fitted on the towers' features
 }
 _NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
 

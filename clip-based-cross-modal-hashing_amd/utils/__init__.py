@@ -1,2 +1,3 @@
 from .utils import *  # noqa: F401,F403
 from .logger import get_logger, get_summary_writer  # noqa: F401
+from .itq import fit_hash_heads  # noqa: F401

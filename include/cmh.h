@@ -879,6 +879,54 @@ int cmh_assign_rows(const float* emb, const float* rows, int32_t P, int32_t B, i
                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training-free hash heads from paired features: LSH, PCAH, ITQ (csrc/itq.hip).  No upstream counterpart.  The fit runs in f64 on
+ * f32 features image F_i / text F_t [N, D] and ends in one affine map per modality, code = sign(W_m f + b_m): a LinearHash head.
+ * Limits: 1 <= D <= 1024, 1 <= K <= min(D, 128), rows <= 65535 * 2048.  Every output element is one sum in a fixed order (row
+ * chunks of 2048 summed in row order, then the chunks in order; fixed reduction trees; no atomics), so two calls give equal bits.
+ * Each call checks its arguments on the host before any launch: a null pointer, a size outside the limits or a workspace
+ * smaller than its *_workspace_bytes query (0 for sizes out of range) comes back as CMH_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------- */
+/* sum [D] (+)= sum_n F[n], sq [D,D] (+)= sum_n F[n] F[n]^T, f64; accumulate = 0 overwrites, 1 adds this batch to the running sums. */
+size_t cmh_itq_moments_workspace_bytes(int64_t N, int32_t D);
+int cmh_itq_moments(const float* F, int64_t N, int32_t D, double* sum, double* sq, int32_t accumulate, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* From the running sums over N pairs: mu_m [D] = sum_m / N; alpha2[m] = 1 / sqrt(mean_n |f - mu_m|^2) (0 where that is not
+ * positive), m = 0 image, 1 text; C [D,D] = 1/2 sum_m alpha_m^2 (sq_m / N - mu_m mu_m^T), symmetric bit for bit. */
+int cmh_itq_covariance(const double* sum_i, const double* sq_i, const double* sum_t, const double* sq_t, int64_t N, int32_t D,
+                       double* mu_i, double* mu_t, double* alpha2, double* C, void* stream);
+/* Symmetric eigen-solver: cyclic Jacobi in round-robin order (one launch per set of disjoint rotations) on the upper triangle
+ * of C [D,D].  A pair is rotated where |a_pq| > eps_f64 sqrt(|a_pp a_qq|); a sweep that rotates nothing ends the run (one 4-byte
+ * host read per sweep).  evals [D] descending, ties by index; evecs [D,D], column j the vector of evals[j], signed so that its
+ * entry of largest magnitude (lowest row on a tie) is positive.  info2 (host): sweeps run, and 1 if the run converged within
+ * max_sweeps (1..1024), else 0 (the outputs are then the state after max_sweeps). */
+size_t cmh_itq_eigh_workspace_bytes(int32_t D, int32_t max_sweeps);
+int cmh_itq_eigh(const double* C, int32_t D, int32_t max_sweeps, double* evals, double* evecs, int32_t* info2, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* V [N,K] f64 = alpha[0] * (F - mu) P, the sum over d in index order; mu [D], alpha one f64 on the device, P [D,K] f64. */
+int cmh_itq_project(const float* F, int64_t N, int32_t D, int32_t K, const double* mu, const double* alpha, const double* P,
+                    double* V, void* stream);
+/* One ITQ pass over V [rows,K] with rotation R [K,K]: Z = V R, B i8 = +1 where Z >= 0 else -1, M [K,K] = B^T V,
+ * obj2 = (|B - Z|^2, |Z|^2). */
+size_t cmh_itq_step_workspace_bytes(int64_t rows, int32_t K);
+int cmh_itq_step(const double* V, int64_t rows, int32_t K, const double* R, double* Z, int8_t* B, double* M, double* obj2,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* R [K,K] = (orthogonal polar factor of M [K,K])^T, ITQ's UA UB^T for M = UB S UA^T, by a one-sided Jacobi SVD in one workgroup
+ * (a pair of columns is rotated where |g_p . g_q| > sqrt(K) eps_f64 |g_p| |g_q|, at most 60 sweeps).  Unique for non-singular M; for a singular one the null
+ * directions (column norm <= sqrt(K) eps_f64 |M|_F) are completed to an orthonormal basis, so R is orthogonal and R M symmetric.
+ * sweeps (device i32, may be NULL): sweeps run. */
+size_t cmh_itq_polar_workspace_bytes(int32_t K);
+int cmh_itq_polar(const double* M, int32_t K, double* R, int32_t* sweeps, void* workspace, size_t workspace_bytes, void* stream);
+/* ITQ: R = R0, then `iters` times (step, R <- polar(M)); obj [iters + 1] (device): |B - Z|^2 at the start of each iteration and,
+ * last, for the R returned; zz (device): |V R|^2 for that R.  iters = 0 leaves R = R0.  Nothing is read back in the loop. */
+size_t cmh_itq_rotate_workspace_bytes(int64_t rows, int32_t K);
+int cmh_itq_rotate(const double* V, int64_t rows, int32_t K, const double* R0, int32_t iters, double* R, double* obj, double* zz,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* The heads: s = 0.5 / sqrt(zz[0] / (rows K)) (s_out, device, may be NULL), W_m f32 [K,D] = s alpha2[m] (P R)^T,
+ * b_m f32 [K] = -W_m mu_m (from the f64 products). */
+int cmh_itq_heads(const double* P, const double* R, const double* mu_i, const double* mu_t, const double* alpha2, const double* zz,
+                  int64_t rows, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t, float* b_t, double* s_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * MITH (BASELINE.json config 3): token-returning trunk, HashingModel pieces, losses.
  * Activations are batch-major: [N, K, D] where the reference holds [K, N, D].
  * ------------------------------------------------------------------------------------------- */
