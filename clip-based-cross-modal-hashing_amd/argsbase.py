@@ -45,7 +45,7 @@ def add_flags(parser, table):
         if flag == "--noise-assign":
             kw["choices"] = ["gpu", "host"]
         if flag == "--projection":
-            kw["choices"] = ["pca", "random"]
+            kw["choices"] = ["pca", "random", "cca"]
         if flag == "--rotation":
             kw["choices"] = ["itq", "none"]
         parser.add_argument(flag, **kw)

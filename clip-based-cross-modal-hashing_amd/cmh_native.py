@@ -214,6 +214,12 @@ SIGNATURES = {
     "cmh_itq_rotate_workspace_bytes": (_sz, [_i64, _i32]),              # no upstream counterpart
     "cmh_itq_rotate": (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _sz, _p]),      # no upstream counterpart
     "cmh_itq_heads": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),   # no upstream counterpart
+    "cmh_itq_heads_pair": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p]),   # no upstream counterpart
+    "cmh_itq_cross_moments_workspace_bytes": (_sz, [_i64, _i32]),       # no upstream counterpart
+    "cmh_itq_cross_moments": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _p, _sz, _p]),       # no upstream counterpart
+    "cmh_itq_cca_covariance": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),   # no upstream counterpart
+    "cmh_itq_inv_sqrt": (C.c_int, [_p, _i32, C.c_double, _p, _p, _p]),   # no upstream counterpart
+    "cmh_itq_matmul": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),   # no upstream counterpart
     "cmh_vit_encode_tokens": (C.c_int, [C.POINTER(VitWeights), _p, _i32, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens_packed": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
@@ -1868,6 +1874,91 @@ def itq_heads(P, R, mu_i, mu_t, alpha, zz, rows):
     check(lib().cmh_itq_heads(*(ptr(t) for t in ops), int(rows), d, k, ptr(W_i), ptr(b_i), ptr(W_t), ptr(b_t), ptr(s), stream_ptr(dev)),
           "cmh_itq_heads")
     return W_i, b_i, W_t, b_t, s
+
+
+def itq_heads_pair(P_i, P_t, R, mu_i, mu_t, alpha, zz, rows):
+    """itq_heads with one projection per modality: W_m = s alpha_m (P_m R)^T."""
+    ops = [_f64c(t) for t in (P_i, P_t, R, mu_i, mu_t, alpha, zz)]
+    require_gpu(*ops)
+    d, k = ops[0].shape
+    fit("itq_heads_pair", (ops[1], (d, k)), (ops[2], (k, k)), (ops[3], (d,)), (ops[4], (d,)), (ops[5], (2,)), (ops[6], (1,)))
+    dev = ops[0].device
+    W_i, W_t = (torch.empty(k, d, dtype=torch.float32, device=dev) for _ in range(2))
+    b_i, b_t = (torch.empty(k, dtype=torch.float32, device=dev) for _ in range(2))
+    s = torch.empty(1, dtype=torch.float64, device=dev)
+    check(lib().cmh_itq_heads_pair(*(ptr(t) for t in ops), int(rows), d, k, ptr(W_i), ptr(b_i), ptr(W_t), ptr(b_t), ptr(s), stream_ptr(dev)),
+          "cmh_itq_heads_pair")
+    return W_i, b_i, W_t, b_t, s
+
+
+def itq_cross_moments(Fi, Ft, cross=None):
+    """Running f64 cross sum of one batch of paired f32 features [N, D]: cross [D, D] (+)= sum_n f_i f_t^T (not symmetric).  `cross`:
+    what a previous call returned, updated in place; None starts a new one."""
+    Fi, Ft = f32c(Fi), f32c(Ft)
+    require_gpu(Fi, Ft)
+    if Fi.dim() != 2 or Fi.shape[0] < 1:
+        raise NativeError(f"itq_cross_moments: features {tuple(Fi.shape)}, expected [N, D] with N >= 1")
+    n, d = Fi.shape
+    fit("itq_cross_moments", (Ft, (n, d)))
+    dev = Fi.device
+    if cross is None:
+        cross, acc = torch.empty(d, d, dtype=torch.float64, device=dev), 0
+    else:
+        fit("itq_cross_moments", (cross, (d, d)))
+        if cross.dtype != torch.float64 or not cross.is_contiguous():
+            raise NativeError("itq_cross_moments: the running sum must be a contiguous f64 tensor")
+        require_gpu(cross)
+        acc = 1
+    ws = workspace(lib().cmh_itq_cross_moments_workspace_bytes(n, d), dev, "itq")
+    check(lib().cmh_itq_cross_moments(ptr(Fi), ptr(Ft), n, d, ptr(cross), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_cross_moments")
+    return cross
+
+
+def itq_cca_covariance(sums_i, sums_t, cross, n):
+    """-> mu_i [D], mu_t [D], alpha [2], S_ii, S_tt, S_it [D, D] (f64) from the running sums of both modalities and their cross sum
+    over n pairs: S_mm = alpha_m^2 cov(f_m) (trace 1), S_it = alpha_i alpha_t cov(f_i, f_t)."""
+    d = sums_i[0].shape[0]
+    fit("itq_cca_covariance", (sums_i[0], (d,)), (sums_i[1], (d, d)), (sums_t[0], (d,)), (sums_t[1], (d, d)), (cross, (d, d)))
+    ops = [_f64c(t) for t in (sums_i[0], sums_i[1], sums_t[0], sums_t[1], cross)]
+    require_gpu(*ops)
+    dev = ops[0].device
+    mu_i, mu_t = (torch.empty(d, dtype=torch.float64, device=dev) for _ in range(2))
+    alpha = torch.empty(2, dtype=torch.float64, device=dev)
+    S_ii, S_tt, S_it = (torch.empty(d, d, dtype=torch.float64, device=dev) for _ in range(3))
+    check(lib().cmh_itq_cca_covariance(*(ptr(t) for t in ops), int(n), d, ptr(mu_i), ptr(mu_t), ptr(alpha), ptr(S_ii), ptr(S_tt), ptr(S_it),
+                                       stream_ptr(dev)), "cmh_itq_cca_covariance")
+    return mu_i, mu_t, alpha, S_ii, S_tt, S_it
+
+
+def itq_inv_sqrt(values, shift=0.0, want_root=False):
+    """1 / sqrt(values + shift) (0 where values + shift <= 0) of an f64 vector, and with want_root also sqrt(max(values + shift, 0))."""
+    values = _f64c(values)
+    require_gpu(values)
+    if values.dim() != 1:
+        raise NativeError(f"itq_inv_sqrt: values {tuple(values.shape)}, expected a vector")
+    out = torch.empty_like(values)
+    root = torch.empty_like(values) if want_root else None
+    check(lib().cmh_itq_inv_sqrt(ptr(values), values.shape[0], float(shift), ptr(out), ptr(root), stream_ptr(values.device)), "cmh_itq_inv_sqrt")
+    return (out, root) if want_root else out
+
+
+def itq_matmul(A, B, d=None, col_scale=None, trans_a=False, trans_b=False):
+    """C [M, N] f64 = op(A) diag(d) op(B) diag(col_scale): op(A) = A [M, Kc] or, with trans_a, the transpose of A [Kc, M]; op(B) =
+    B [Kc, N] or, with trans_b, the transpose of B [N, Kc]; d [Kc] and col_scale [N] optional.  One fma chain per element over the
+    contraction index in ascending order: two calls give equal bits, and A A^T is symmetric bit for bit."""
+    A, B = _f64c(A), _f64c(B)
+    d = None if d is None else _f64c(d)
+    col_scale = None if col_scale is None else _f64c(col_scale)
+    require_gpu(A, B, d, col_scale)
+    if A.dim() != 2 or B.dim() != 2:
+        raise NativeError(f"itq_matmul: operands {tuple(A.shape)} and {tuple(B.shape)}, expected two matrices")
+    m, kc = (A.shape[1], A.shape[0]) if trans_a else A.shape
+    n = B.shape[0] if trans_b else B.shape[1]
+    fit("itq_matmul", (B, (n, kc) if trans_b else (kc, n)), (d, (kc,)), (col_scale, (n,)))
+    out = torch.empty(m, n, dtype=torch.float64, device=A.device)
+    check(lib().cmh_itq_matmul(ptr(A), ptr(B), ptr(d), ptr(col_scale), m, n, kc, int(bool(trans_a)), int(bool(trans_b)), ptr(out),
+                               stream_ptr(A.device)), "cmh_itq_matmul")
+    return out
 
 
 # ------------------------------------------------------------------------------------------ optimiser

@@ -8,7 +8,14 @@
 //   step         Z = V R, B = (Z >= 0 ? +1 : -1), M = B^T V, |B - Z|^2, |Z|^2
 //   polar        R <- (orthogonal polar factor of M)^T by a one-sided Jacobi SVD, one workgroup
 //   rotate       `iters` times step + polar, then one more step for the final objective; no host read in the loop
-//   heads        s = 0.5 / rms(V R), W_m = s alpha_m (P R)^T as f32, b_m = -W_m mu_m
+//   heads        s = 0.5 / rms(V R), W_m = s alpha_m (P_m R)^T as f32, b_m = -W_m mu_m
+//
+// CCA projections (one P_m per modality, the cross-modal variant of the same paper) add
+//   cross moments    running sum  sum_n f_i f_t^T  (the X^T Y kernel with X != Y)
+//   cca covariance   S_mm = alpha_m^2 (sum f f^T / N - mu_m mu_m^T), S_it = alpha_i alpha_t (sum f_i f_t^T / N - mu_i mu_t^T)
+//   inv_sqrt         1 / sqrt(lambda + shift): the whitener's spectrum and 1 / sigma
+//   matmul           C = op(A) diag(d) op(B) diag(cs), sizes up to 1024: the whiteners H_m = E_m diag((lambda + r)^-1/2) E_m^T,
+//                    T = H_i S_it H_t, G = T T^T, v_j = T^T u_j / sigma_j and A_m = H_m [U_K | V_K]
 //
 // Determinism: every output element is one sum in a fixed order.  The O(N) products cut the rows into chunks of kChunk (a constant,
 // not a property of the device), sum each chunk in row order and then the chunks in chunk order; block reductions are fixed trees;
@@ -144,6 +151,93 @@ __global__ __launch_bounds__(256) void covariance_kernel(const double* __restric
   const double ai = alpha2[0] * alpha2[0], at = alpha2[1] * alpha2[1];
   const double ci = sq_i[e] * inv_n - mu_i[i] * mu_i[j], ct = sq_t[e] * inv_n - mu_t[i] * mu_t[j];
   C[e] = 0.5 * (ai * ci + at * ct);
+}
+
+// S_ii, S_tt (symmetric bit for bit: sq is, and mu[i] mu[j] commutes) and S_it for the CCA projections
+__global__ __launch_bounds__(256) void cca_covariance_kernel(const double* __restrict__ sq_i, const double* __restrict__ sq_t,
+                                                             const double* __restrict__ cross, const double* __restrict__ mu_i,
+                                                             const double* __restrict__ mu_t, const double* __restrict__ alpha2, double inv_n,
+                                                             int D, double* __restrict__ S_ii, double* __restrict__ S_tt,
+                                                             double* __restrict__ S_it) {
+  const size_t e = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= static_cast<size_t>(D) * D) return;
+  const int i = static_cast<int>(e / D), j = static_cast<int>(e % D);
+  const double ai = alpha2[0], at = alpha2[1];
+  S_ii[e] = (ai * ai) * (sq_i[e] * inv_n - mu_i[i] * mu_i[j]);
+  S_tt[e] = (at * at) * (sq_t[e] * inv_n - mu_t[i] * mu_t[j]);
+  S_it[e] = (ai * at) * (cross[e] * inv_n - mu_i[i] * mu_t[j]);
+}
+
+// out[j] = 1 / sqrt(v[j] + shift), 0 where v[j] + shift is not positive; root[j] (optional) = sqrt(max(v[j] + shift, 0))
+__global__ __launch_bounds__(256) void inv_sqrt_kernel(const double* __restrict__ v, int n, double shift, double* __restrict__ out,
+                                                       double* __restrict__ root) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double x = v[j] + shift;
+  const double r = x > 0.0 ? sqrt(x) : 0.0;
+  out[j] = x > 0.0 ? 1.0 / r : 0.0;
+  if (root) root[j] = r;
+}
+
+// ---- a small dense product ----------------------------------------------------------------------------------------------------
+// C[i][j] = cs[j] * sum_k op(A)[i][k] d[k] op(B)[k][j], k ascending: one chain acc = fma(a b, d, acc) (fma(a, b, acc) without d),
+// whatever the grid is.  a b is rounded before d comes in, and a b = b a, so op(A) = op(B)^T gives C[i][j] and C[j][i] the same
+// bits, with or without d.  op(A) is A [M, Kc] or (TA) the transpose of A [Kc, M]; op(B) is B [Kc, N] or (TB) the transpose of
+// B [N, Kc]; d [Kc] and cs [N] are optional.  Every operand goes through LDS: an operand whose contraction index is the fast one in
+// memory is read 16 consecutive doubles per row of the tile, the other 64, so no read strides through memory.  One block: a
+// 64 x 64 tile of C, thread (ti, tj) holds i = 4 ti + a, j = tj + 16 b, as in the X^T Y kernel.
+template <bool TA, bool TB, bool HasD>
+__global__ __launch_bounds__(256) void matmul_kernel(const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ d,
+                                                     const double* __restrict__ cs, double* __restrict__ C, int M, int N, int Kc) {
+  __shared__ double xs[kStage][kTile + 1];      // op(A)[i0 + c][k0 + r]
+  __shared__ double ys[kStage][kTile + 1];      // op(B)[k0 + r][j0 + c]
+  __shared__ double ds[kStage];
+  const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+  const int j0 = blockIdx.x * kTile, i0 = blockIdx.y * kTile;
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+  for (int k0 = 0; k0 < Kc; k0 += kStage) {
+    for (int t = tid; t < kStage * kTile; t += 256) {
+      {
+        const int r = TA ? t >> 6 : t & 15, c = TA ? t & 63 : t >> 4;
+        const bool in = k0 + r < Kc && i0 + c < M;
+        xs[r][c] = in ? (TA ? A[static_cast<size_t>(k0 + r) * M + i0 + c] : A[static_cast<size_t>(i0 + c) * Kc + k0 + r]) : 0.0;
+      }
+      {
+        const int r = TB ? t & 15 : t >> 6, c = TB ? t >> 4 : t & 63;
+        const bool in = k0 + r < Kc && j0 + c < N;
+        ys[r][c] = in ? (TB ? B[static_cast<size_t>(j0 + c) * Kc + k0 + r] : B[static_cast<size_t>(k0 + r) * N + j0 + c]) : 0.0;
+      }
+    }
+    if (HasD && tid < kStage) ds[tid] = k0 + tid < Kc ? d[k0 + tid] : 0.0;
+    __syncthreads();
+#pragma unroll 4
+    for (int r = 0; r < kStage; ++r) {
+      double xv[4], yv[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) xv[a] = xs[r][ti * 4 + a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) yv[b] = ys[r][tj + 16 * b];
+      const double dv = HasD ? ds[r] : 1.0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = HasD ? fma(xv[a] * yv[b], dv, acc[a][b]) : fma(xv[a], yv[b], acc[a][b]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = i0 + ti * 4 + a;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int j = j0 + tj + 16 * b;
+      if (i < M && j < N) C[static_cast<size_t>(i) * N + j] = cs ? cs[j] * acc[a][b] : acc[a][b];
+    }
+  }
 }
 
 // ---- symmetric eigen-solver: cyclic Jacobi, round-robin order ----------------------------------------------------------------
@@ -540,10 +634,10 @@ __global__ __launch_bounds__(kPolarT) void polar_kernel(const double* __restrict
 }
 
 // ---- heads --------------------------------------------------------------------------------------------------------------------
-// block (k, m): W_m[k][d] = s alpha_m sum_j P[d][j] R[j][k] (j in index order) as f32; b_m[k] = -sum_d W_m[k][d] mu_m[d] from the
+// block (k, m): W_m[k][d] = s alpha_m sum_j P_m[d][j] R[j][k] (j in index order) as f32; b_m[k] = -sum_d W_m[k][d] mu_m[d] from the
 // f64 products (each thread its d in order, then the block's tree); s = 0.5 / sqrt(zz / (M2 K)), 0 where zz is not positive
-__global__ __launch_bounds__(256) void heads_kernel(const double* __restrict__ P, const double* __restrict__ R, const double* __restrict__ mu_i,
-                                                    const double* __restrict__ mu_t, const double* __restrict__ alpha2,
+__global__ __launch_bounds__(256) void heads_kernel(const double* __restrict__ P_i, const double* __restrict__ P_t, const double* __restrict__ R,
+                                                    const double* __restrict__ mu_i, const double* __restrict__ mu_t, const double* __restrict__ alpha2,
                                                     const double* __restrict__ zz, double count, int D, int K, float* __restrict__ W_i,
                                                     float* __restrict__ b_i, float* __restrict__ W_t, float* __restrict__ b_t,
                                                     double* __restrict__ s_out) {
@@ -551,6 +645,7 @@ __global__ __launch_bounds__(256) void heads_kernel(const double* __restrict__ P
   __shared__ double rk[kMaxK];
   const int k = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
   const double* mu = m ? mu_t : mu_i;
+  const double* P = m ? P_t : P_i;
   float* W = m ? W_t : W_i;
   float* bias = m ? b_t : b_i;
   for (int j = tid; j < K; j += 256) rk[j] = R[static_cast<size_t>(j) * K + k];
@@ -825,13 +920,93 @@ extern "C" int cmh_itq_rotate(const double* V, int64_t M2, int32_t K, const doub
   return CMH_OK;
 }
 
-extern "C" int cmh_itq_heads(const double* P, const double* R, const double* mu_i, const double* mu_t, const double* alpha2, const double* zz,
-                             int64_t M2, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t, float* b_t, double* s_out, void* stream) {
+extern "C" int cmh_itq_heads_pair(const double* P_i, const double* P_t, const double* R, const double* mu_i, const double* mu_t,
+                                  const double* alpha2, const double* zz, int64_t M2, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t,
+                                  float* b_t, double* s_out, void* stream) {
   CMH_CHECK_ARG(M2 >= 1, "itq_heads: rows = %lld, need rows >= 1", static_cast<long long>(M2));
   CMH_CHECK_ARG(dims_ok(D, K), "itq_heads: D = %d, K = %d, need 1 <= D <= %d and 1 <= K <= min(D, %d)", D, K, kMaxD, kMaxK);
-  CMH_CHECK_ARG(P && R && mu_i && mu_t && alpha2 && zz && W_i && b_i && W_t && b_t, "itq_heads: null pointer");
-  hipLaunchKernelGGL(heads_kernel, dim3(K, 2), dim3(256), 0, as_stream(stream), P, R, mu_i, mu_t, alpha2, zz,
+  CMH_CHECK_ARG(P_i && P_t && R && mu_i && mu_t && alpha2 && zz && W_i && b_i && W_t && b_t, "itq_heads: null pointer");
+  hipLaunchKernelGGL(heads_kernel, dim3(K, 2), dim3(256), 0, as_stream(stream), P_i, P_t, R, mu_i, mu_t, alpha2, zz,
                      static_cast<double>(M2) * static_cast<double>(K), D, K, W_i, b_i, W_t, b_t, s_out);
   CMH_CHECK_LAUNCH("itq_heads");
+  return CMH_OK;
+}
+
+extern "C" int cmh_itq_heads(const double* P, const double* R, const double* mu_i, const double* mu_t, const double* alpha2, const double* zz,
+                             int64_t M2, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t, float* b_t, double* s_out, void* stream) {
+  return cmh_itq_heads_pair(P, P, R, mu_i, mu_t, alpha2, zz, M2, D, K, W_i, b_i, W_t, b_t, s_out, stream);
+}
+
+// ---- CCA projections ----------------------------------------------------------------------------------------------------------
+extern "C" size_t cmh_itq_cross_moments_workspace_bytes(int64_t N, int32_t D) {
+  if (N < 1 || N > kMaxRows || D < 1 || D > kMaxD) return 0;
+  return align_up(static_cast<size_t>(chunks_of(N)) * D * static_cast<size_t>(D) * sizeof(double), 256);
+}
+
+extern "C" int cmh_itq_cross_moments(const float* F_i, const float* F_t, int64_t N, int32_t D, double* cross, int32_t accumulate,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  CMH_CHECK_ARG(N >= 1 && N <= kMaxRows, "itq_cross_moments: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
+  CMH_CHECK_ARG(D >= 1 && D <= kMaxD, "itq_cross_moments: D = %d, need 1 <= D <= %d", D, kMaxD);
+  CMH_CHECK_ARG(F_i && F_t && cross && workspace, "itq_cross_moments: null pointer");
+  const size_t need = cmh_itq_cross_moments_workspace_bytes(N, D);
+  CMH_CHECK_ARG(workspace_bytes >= need, "itq_cross_moments: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  const int ch = chunks_of(N), tiles = (D + kTile - 1) / kTile;
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL((xty_partial_kernel<float, float>), dim3(tiles, tiles, ch), dim3(256), 0, st, F_i, F_t, part, static_cast<long long>(N), D, D);
+  const size_t e2 = static_cast<size_t>(D) * D;
+  hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((e2 + 255) / 256)), dim3(256), 0, st, static_cast<const double*>(part), cross,
+                     ch, e2, accumulate ? 1 : 0);
+  CMH_CHECK_LAUNCH("itq_cross_moments");
+  return CMH_OK;
+}
+
+extern "C" int cmh_itq_cca_covariance(const double* sum_i, const double* sq_i, const double* sum_t, const double* sq_t, const double* cross,
+                                      int64_t N, int32_t D, double* mu_i, double* mu_t, double* alpha2, double* S_ii, double* S_tt,
+                                      double* S_it, void* stream) {
+  CMH_CHECK_ARG(N >= 1, "itq_cca_covariance: N = %lld, need N >= 1", static_cast<long long>(N));
+  CMH_CHECK_ARG(D >= 1 && D <= kMaxD, "itq_cca_covariance: D = %d, need 1 <= D <= %d", D, kMaxD);
+  CMH_CHECK_ARG(sum_i && sq_i && sum_t && sq_t && cross && mu_i && mu_t && alpha2 && S_ii && S_tt && S_it, "itq_cca_covariance: null pointer");
+  hipStream_t st = as_stream(stream);
+  const double inv_n = 1.0 / static_cast<double>(N);
+  hipLaunchKernelGGL(moments_finish_kernel, dim3(2), dim3(256), 0, st, sum_i, sq_i, sum_t, sq_t, inv_n, D, mu_i, mu_t, alpha2);
+  const size_t e2 = static_cast<size_t>(D) * D;
+  hipLaunchKernelGGL(cca_covariance_kernel, dim3(static_cast<unsigned>((e2 + 255) / 256)), dim3(256), 0, st, sq_i, sq_t, cross,
+                     static_cast<const double*>(mu_i), static_cast<const double*>(mu_t), static_cast<const double*>(alpha2), inv_n, D, S_ii,
+                     S_tt, S_it);
+  CMH_CHECK_LAUNCH("itq_cca_covariance");
+  return CMH_OK;
+}
+
+extern "C" int cmh_itq_inv_sqrt(const double* values, int32_t n, double shift, double* out, double* root, void* stream) {
+  CMH_CHECK_ARG(n >= 1 && n <= kMaxD, "itq_inv_sqrt: n = %d, need 1 <= n <= %d", n, kMaxD);
+  CMH_CHECK_ARG(shift >= 0.0, "itq_inv_sqrt: shift = %g, need shift >= 0", shift);      // a NaN fails the comparison too
+  CMH_CHECK_ARG(values && out, "itq_inv_sqrt: null pointer");
+  hipLaunchKernelGGL(inv_sqrt_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), values, n, shift, out, root);
+  CMH_CHECK_LAUNCH("itq_inv_sqrt");
+  return CMH_OK;
+}
+
+extern "C" int cmh_itq_matmul(const double* A, const double* B, const double* d, const double* col_scale, int32_t M, int32_t N, int32_t Kc,
+                              int32_t trans_a, int32_t trans_b, double* C, void* stream) {
+  CMH_CHECK_ARG(M >= 1 && M <= kMaxD && N >= 1 && N <= kMaxD && Kc >= 1 && Kc <= kMaxD,
+                "itq_matmul: M = %d, N = %d, Kc = %d, need 1 <= M, N, Kc <= %d", M, N, Kc, kMaxD);
+  CMH_CHECK_ARG((trans_a == 0 || trans_a == 1) && (trans_b == 0 || trans_b == 1), "itq_matmul: trans_a = %d, trans_b = %d, need 0 or 1",
+                trans_a, trans_b);
+  CMH_CHECK_ARG(A && B && C, "itq_matmul: null pointer");
+  CMH_CHECK_ARG(C != A && C != B, "itq_matmul: the output must not be an operand");
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((N + kTile - 1) / kTile, (M + kTile - 1) / kTile);
+#define CMH_MATMUL_CASE(TA_, TB_)                                                                                                       \
+  if (trans_a == TA_ && trans_b == TB_) {                                                                                                \
+    if (d) hipLaunchKernelGGL((matmul_kernel<TA_ != 0, TB_ != 0, true>), grid, dim3(256), 0, st, A, B, d, col_scale, C, M, N, Kc);      \
+    else hipLaunchKernelGGL((matmul_kernel<TA_ != 0, TB_ != 0, false>), grid, dim3(256), 0, st, A, B, d, col_scale, C, M, N, Kc);       \
+  }
+  CMH_MATMUL_CASE(0, 0)
+  CMH_MATMUL_CASE(0, 1)
+  CMH_MATMUL_CASE(1, 0)
+  CMH_MATMUL_CASE(1, 1)
+#undef CMH_MATMUL_CASE
+  CMH_CHECK_LAUNCH("itq_matmul");
   return CMH_OK;
 }

@@ -925,6 +925,31 @@ int cmh_itq_rotate(const double* V, int64_t rows, int32_t K, const double* R0, i
  * b_m f32 [K] = -W_m mu_m (from the f64 products). */
 int cmh_itq_heads(const double* P, const double* R, const double* mu_i, const double* mu_t, const double* alpha2, const double* zz,
                   int64_t rows, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t, float* b_t, double* s_out, void* stream);
+/* The same with one projection per modality: W_m = s alpha2[m] (P_m R)^T.  cmh_itq_heads is the case P_i = P_t, bit for bit. */
+int cmh_itq_heads_pair(const double* P_i, const double* P_t, const double* R, const double* mu_i, const double* mu_t,
+                       const double* alpha2, const double* zz, int64_t rows, int32_t D, int32_t K, float* W_i, float* b_i, float* W_t,
+                       float* b_t, double* s_out, void* stream);
+/* CCA projections (the cross-modal variant of the ITQ paper): one P_m per modality from the whitened cross-covariance.  The same
+ * limits, determinism and host checks as the block above.
+ * cross [D,D] (+)= sum_n F_i[n] F_t[n]^T, f64, not symmetric: the row chunks, chunk order and accumulate flag of cmh_itq_moments. */
+size_t cmh_itq_cross_moments_workspace_bytes(int64_t N, int32_t D);
+int cmh_itq_cross_moments(const float* F_i, const float* F_t, int64_t N, int32_t D, double* cross, int32_t accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* mu_m and alpha2 as cmh_itq_covariance; S_ii, S_tt [D,D] = alpha_m^2 (sq_m / N - mu_m mu_m^T) (trace 1, symmetric bit for bit),
+ * S_it [D,D] = alpha_i alpha_t (cross / N - mu_i mu_t^T). */
+int cmh_itq_cca_covariance(const double* sum_i, const double* sq_i, const double* sum_t, const double* sq_t, const double* cross,
+                           int64_t N, int32_t D, double* mu_i, double* mu_t, double* alpha2, double* S_ii, double* S_tt, double* S_it,
+                           void* stream);
+/* out[j] = 1 / sqrt(values[j] + shift), 0 where values[j] + shift <= 0; root[j] (may be NULL) = sqrt(max(values[j] + shift, 0)).
+ * 1 <= n <= 1024, shift >= 0: the whitener's (lambda + r)^-1/2, and sigma and 1 / sigma from the eigenvalues of T T^T. */
+int cmh_itq_inv_sqrt(const double* values, int32_t n, double shift, double* out, double* root, void* stream);
+/* C [M,N] = op(A) diag(d) op(B) diag(col_scale), f64, 1 <= M, N, Kc <= 1024.  op(A) is A [M,Kc], or with trans_a = 1 the
+ * transpose of A [Kc,M]; op(B) is B [Kc,N], or with trans_b = 1 the transpose of B [N,Kc]; d [Kc] and col_scale [N] may be NULL.
+ * Each C[i][j] is one chain over k ascending, acc = fma(a b, d_k, acc) (fma(a, b, acc) without d), whatever the grid: two calls
+ * give equal bits, a transposed operand gives the bits of its materialised transpose, and op(A) = op(B)^T gives a C that is
+ * symmetric bit for bit.  C must not be an operand. */
+int cmh_itq_matmul(const double* A, const double* B, const double* d, const double* col_scale, int32_t M, int32_t N, int32_t Kc,
+                   int32_t trans_a, int32_t trans_b, double* C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MITH (BASELINE.json config 3): token-returning trunk, HashingModel pieces, losses.
