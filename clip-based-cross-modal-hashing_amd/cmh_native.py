@@ -220,6 +220,19 @@ SIGNATURES = {
     "cmh_itq_cca_covariance": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),   # no upstream counterpart
     "cmh_itq_inv_sqrt": (C.c_int, [_p, _i32, C.c_double, _p, _p, _p]),   # no upstream counterpart
     "cmh_itq_matmul": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),   # no upstream counterpart
+    # supervised training-free heads (csrc/dch.hip): none of the cmh_dch_* entries has an upstream counterpart
+    "cmh_dch_covariance": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),                     # no upstream counterpart
+    "cmh_dch_start": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),                              # no upstream counterpart
+    "cmh_dch_xtb_workspace_bytes": (_sz, [_i64, _i32, _i32]),           # no upstream counterpart
+    "cmh_dch_xtb": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _i32, _p, _sz, _p]),       # no upstream counterpart
+    "cmh_dch_btb_workspace_bytes": (_sz, [_i64, _i32]),                 # no upstream counterpart
+    "cmh_dch_btb": (C.c_int, [_p, _i64, _i32, _p, _p, _sz, _p]),                            # no upstream counterpart
+    "cmh_dch_center": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _p, _p]),               # no upstream counterpart
+    "cmh_dch_solve": (C.c_int, [_p, C.c_double, _p, _i32, _i32, _p, _p, _p]),              # no upstream counterpart
+    "cmh_dch_targets_workspace_bytes": (_sz, [_i64]),                   # no upstream counterpart
+    "cmh_dch_targets": (C.c_int, [_p, _p, _p, _p, _p, C.c_double, C.c_double, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),   # no upstream counterpart
+    "cmh_dch_dcc_workspace_bytes": (_sz, [_i64, _i32]),                 # no upstream counterpart
+    "cmh_dch_dcc": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),         # no upstream counterpart
     "cmh_vit_encode_tokens": (C.c_int, [C.POINTER(VitWeights), _p, _i32, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "cmh_text_encode_tokens_packed": (C.c_int, [C.POINTER(TextWeights), _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
@@ -1959,6 +1972,153 @@ def itq_matmul(A, B, d=None, col_scale=None, trans_a=False, trans_b=False):
     check(lib().cmh_itq_matmul(ptr(A), ptr(B), ptr(d), ptr(col_scale), m, n, kc, int(bool(trans_a)), int(bool(trans_b)), ptr(out),
                                stream_ptr(A.device)), "cmh_itq_matmul")
     return out
+
+
+# ------------------------------------------------------------------------------------------ supervised training-free heads (csrc/dch.hip)
+DCH_MAX_C, DCH_MAX_ROUNDS = 1024, 64
+
+
+def _codes(B, what):
+    if B.dtype != torch.int8 or B.dim() != 2 or not B.is_contiguous():
+        raise NativeError(f"{what}: B must be a contiguous int8 [N, K] tensor of +1 / -1")
+    require_gpu(B)
+    return B
+
+
+def dch_covariance(sq, mu, alpha, n):
+    """S [D, D] f64 = alpha^2 (sq / n - mu mu^T) of one modality; alpha: one f64 element on the device."""
+    sq, mu, alpha = _f64c(sq), _f64c(mu), _f64c(alpha)
+    require_gpu(sq, mu, alpha)
+    d = mu.shape[0]
+    fit("dch_covariance", (sq, (d, d)), (alpha, (1,)))
+    S = torch.empty(d, d, dtype=torch.float64, device=sq.device)
+    check(lib().cmh_dch_covariance(ptr(sq), ptr(mu), ptr(alpha), int(n), d, ptr(S), stream_ptr(sq.device)), "cmh_dch_covariance")
+    return S
+
+
+def dch_start(Za, Zb):
+    """B int8 [N, K] = +1 where Za + Zb >= 0, else -1."""
+    Za, Zb = _f64c(Za), _f64c(Zb)
+    require_gpu(Za, Zb)
+    n, k = Za.shape
+    fit("dch_start", (Zb, (n, k)))
+    B = torch.empty(n, k, dtype=torch.int8, device=Za.device)
+    check(lib().cmh_dch_start(ptr(Za), ptr(Zb), n, k, ptr(B), stream_ptr(Za.device)), "cmh_dch_start")
+    return B
+
+
+def dch_xtb(X, B, want_bsum=False, into=None):
+    """X^T B [Dx, K] f64 for X f32 [N, Dx] and B int8 [N, K]; with want_bsum also 1^T B [K].  `into`: what a previous call returned (the
+    matrix, or the pair with want_bsum), added to in place."""
+    X, B = f32c(X), _codes(B, "dch_xtb")
+    require_gpu(X)
+    if X.dim() != 2 or X.shape[0] < 1:
+        raise NativeError(f"dch_xtb: rows {tuple(X.shape)}, expected [N, Dx] with N >= 1")
+    n, dx = X.shape
+    k = B.shape[1]
+    fit("dch_xtb", (B, (n, k)))
+    dev = X.device
+    if into is None:
+        out, bsum, acc = torch.empty(dx, k, dtype=torch.float64, device=dev), None, 0
+        if want_bsum:
+            bsum = torch.empty(k, dtype=torch.float64, device=dev)
+    else:
+        out, bsum = into if want_bsum else (into, None)
+        fit("dch_xtb", (out, (dx, k)), (bsum, (k,)))
+        for t in (out, bsum):
+            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+                raise NativeError("dch_xtb: the running sums must be contiguous f64 tensors")
+        require_gpu(out, bsum)
+        acc = 1
+    ws = workspace(lib().cmh_dch_xtb_workspace_bytes(n, dx, k), dev, "dch")
+    check(lib().cmh_dch_xtb(ptr(X), ptr(B), n, dx, k, ptr(out), ptr(bsum), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dch_xtb")
+    return (out, bsum) if want_bsum else out
+
+
+def dch_btb(B):
+    """B^T B [K, K] f64 (exact integers)."""
+    B = _codes(B, "dch_btb")
+    n, k = B.shape
+    out = torch.empty(k, k, dtype=torch.float64, device=B.device)
+    ws = workspace(lib().cmh_dch_btb_workspace_bytes(n, k), B.device, "dch")
+    check(lib().cmh_dch_btb(ptr(B), n, k, ptr(out), ptr(ws), ws.numel(), stream_ptr(B.device)), "cmh_dch_btb")
+    return out
+
+
+def dch_center(T, bsum, mu, alpha, n):
+    """U [D, K] = alpha (T - mu bsum^T) / n for T = F^T B: X^T B / n with X = alpha (F - mu)."""
+    T, bsum, mu, alpha = _f64c(T), _f64c(bsum), _f64c(mu), _f64c(alpha)
+    require_gpu(T, bsum, mu, alpha)
+    d, k = T.shape
+    fit("dch_center", (bsum, (k,)), (mu, (d,)), (alpha, (1,)))
+    U = torch.empty(d, k, dtype=torch.float64, device=T.device)
+    check(lib().cmh_dch_center(ptr(T), ptr(bsum), ptr(mu), ptr(alpha), int(n), d, k, ptr(U), stream_ptr(T.device)), "cmh_dch_center")
+    return U
+
+
+def dch_solve(A, R, shift=0.0, info=None):
+    """W [K, C] = (A + shift I)^-1 R by Cholesky for a symmetric positive definite A [K, K] -> W, info (int32 [1] on the device: 0, or
+    1 + the first pivot that is not positive, W then zeros).  `info`: a one-element int32 view to fill."""
+    A, R = _f64c(A), _f64c(R)
+    require_gpu(A, R)
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or R.dim() != 2:
+        raise NativeError(f"dch_solve: operands {tuple(A.shape)} and {tuple(R.shape)}, expected [K, K] and [K, C]")
+    k, c = R.shape
+    fit("dch_solve", (A, (k, k)))
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int32, device=A.device)
+    if info.dtype != torch.int32 or info.numel() != 1:
+        raise NativeError("dch_solve: info must hold one int32")
+    require_gpu(info)
+    W = torch.empty(k, c, dtype=torch.float64, device=A.device)
+    check(lib().cmh_dch_solve(ptr(A), float(shift), ptr(R), k, c, ptr(W), ptr(info), stream_ptr(A.device)), "cmh_dch_solve")
+    return W, info
+
+
+def dch_targets(Y, B, W, Z_i, Z_t, mu, lam, want_q=True, obj2=None):
+    """-> Qt [K, N] f64 (bit-major; None without want_q) = (Y W^T + mu Z_i + mu Z_t)^T and obj2 [2] = (the objective |Y - B W|^2 +
+    lam |W|^2 + mu (|B - Z_i|^2 + |B - Z_t|^2), |Z_i|^2 + |Z_t|^2).  `obj2`: a two-element f64 view to fill."""
+    Y, B, W, Z_i, Z_t = f32c(Y), _codes(B, "dch_targets"), _f64c(W), _f64c(Z_i), _f64c(Z_t)
+    require_gpu(Y, W, Z_i, Z_t)
+    n, k = B.shape
+    if Y.dim() != 2:
+        raise NativeError(f"dch_targets: labels {tuple(Y.shape)}, expected [N, C]")
+    c = Y.shape[1]
+    fit("dch_targets", (Y, (n, c)), (W, (k, c)), (Z_i, (n, k)), (Z_t, (n, k)))
+    dev = B.device
+    Qt = torch.empty(k, n, dtype=torch.float64, device=dev) if want_q else None
+    if obj2 is None:
+        obj2 = torch.empty(2, dtype=torch.float64, device=dev)
+    fit("dch_targets", (obj2, (2,)))
+    if obj2.dtype != torch.float64 or not obj2.is_contiguous():
+        raise NativeError("dch_targets: obj2 must be a contiguous f64 pair")
+    require_gpu(obj2)
+    ws = workspace(lib().cmh_dch_targets_workspace_bytes(n), dev, "dch")
+    check(lib().cmh_dch_targets(ptr(Y), ptr(B), ptr(W), ptr(Z_i), ptr(Z_t), float(mu), float(lam), n, k, c, ptr(Qt), ptr(obj2), ptr(ws),
+                                ws.numel(), stream_ptr(dev)), "cmh_dch_targets")
+    return Qt, obj2
+
+
+def dch_dcc(Qt, G, B, rounds, flips=None, min_margin=None):
+    """`rounds` rounds of the bit-cyclic coordinate descent on B int8 [N, K], IN PLACE, from the targets Qt [K, N] and G [K, K] ->
+    flips int64 [rounds], min_margin f64 [1] (device).  `flips` / `min_margin`: views of that shape to fill."""
+    Qt, G, B = _f64c(Qt), _f64c(G), _codes(B, "dch_dcc")
+    require_gpu(Qt, G)
+    n, k = B.shape
+    rounds = int(rounds)
+    fit("dch_dcc", (Qt, (k, n)), (G, (k, k)))
+    dev = B.device
+    if flips is None:
+        flips = torch.empty(max(rounds, 0), dtype=torch.int64, device=dev)
+    if min_margin is None:
+        min_margin = torch.empty(1, dtype=torch.float64, device=dev)
+    fit("dch_dcc", (flips, (rounds,)), (min_margin, (1,)))
+    if flips.dtype != torch.int64 or min_margin.dtype != torch.float64 or not flips.is_contiguous():
+        raise NativeError("dch_dcc: flips must be a contiguous int64 vector and min_margin one f64")
+    require_gpu(flips, min_margin)
+    ws = workspace(lib().cmh_dch_dcc_workspace_bytes(n, rounds), dev, "dch")
+    check(lib().cmh_dch_dcc(ptr(Qt), ptr(G), ptr(B), n, k, rounds, ptr(flips), ptr(min_margin), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dch_dcc")
+    return flips, min_margin
 
 
 # ------------------------------------------------------------------------------------------ optimiser

@@ -17,6 +17,7 @@ _REGISTRY = {
     'DHaPH': ("train.DHaPH.hash_train", "DHaPHTrainer"),
     'DDBH': ("train.DDBH.hash_train", "DDBHTrainer"),
     'ITQ': ("train.ITQ.hash_train", "ITQTrainer"),       # training-free: LSH / PCAH / ITQ heads fitted on the towers' features
+    'DCH': ("train.DCH.hash_train", "DCHTrainer"),       # training-free, supervised: discrete cross-modal hashing on the towers' features
 }
 _NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
 

@@ -952,6 +952,50 @@ int cmh_itq_matmul(const double* A, const double* B, const double* d, const doub
                    int32_t trans_a, int32_t trans_b, double* C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Supervised training-free heads (csrc/dch.hip).  No upstream counterpart: discrete cross-modal hashing on frozen features (DCH,
+ * Xu et al., TIP 2017; the cross-modal form of SDH, Shen et al., CVPR 2015), the fit utils/dch.py runs with the cmh_itq_* pieces
+ * above (moments, eigen-solver, small products, projection, heads).  B int8 [N,K] holds +1 / -1; labels Y are f32 [N,C]; everything
+ * else is f64.  Limits: 1 <= D <= 1024, 1 <= K <= min(D, 128) (K <= 128 where no D is passed), 1 <= C <= 1024, 1 <= N <= 65535 * 2048.
+ * Determinism as the block above: every output element is one sum in a fixed order (rows in chunks of 2048, chunks in chunk order,
+ * block trees, partials in block order), no atomics, no kernel waits for another workgroup; two calls give equal bits.  Every call
+ * refuses, before any launch, a null pointer, a size out of range or a workspace one byte short with CMH_ERR_INVALID and a message
+ * that names it; the *_workspace_bytes queries return 0 for sizes out of range.
+ * S [D,D] = alpha[0]^2 (sq / N - mu mu^T) of one modality (trace 1; cmh_itq_cca_covariance's S_mm without a cross moment). */
+int cmh_dch_covariance(const double* sq, const double* mu, const double* alpha, int64_t N, int32_t D, double* S, void* stream);
+/* The start: B[n][k] = +1 where Za[n][k] + Zb[n][k] >= 0, else -1 (Za, Zb [N,K]: both modalities' rows on the leading eigenvectors). */
+int cmh_dch_start(const double* Za, const double* Zb, int64_t N, int32_t K, int8_t* B, void* stream);
+/* out [Dx,K] (+)= X^T B for X f32 [N,Dx] (F_m with Dx = D, Y with Dx = C; 1 <= Dx <= 1024) and, where bsum is not NULL,
+ * bsum [K] (+)= 1^T B: one fma per row in row order within a chunk, the chunks in chunk order; accumulate = 1 adds to out / bsum. */
+size_t cmh_dch_xtb_workspace_bytes(int64_t N, int32_t Dx, int32_t K);
+int cmh_dch_xtb(const float* X, const int8_t* B, int64_t N, int32_t Dx, int32_t K, double* out, double* bsum, int32_t accumulate,
+                void* workspace, size_t workspace_bytes, void* stream);
+/* out [K,K] = B^T B: integers below 2^53, so exact, symmetric and free of any order. */
+size_t cmh_dch_btb_workspace_bytes(int64_t N, int32_t K);
+int cmh_dch_btb(const int8_t* B, int64_t N, int32_t K, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* U [D,K] = (alpha[0] (T[d][k] - mu[d] bsum[k])) / N for T = F^T B [D,K]: X^T B / N with X = alpha (F - mu), the right-hand side of
+ * the feature regression P = A U. */
+int cmh_dch_center(const double* T, const double* bsum, const double* mu, const double* alpha, int64_t N, int32_t D, int32_t K, double* U,
+                   void* stream);
+/* W [K,C] = (A + shift I)^-1 R for a symmetric positive definite A [K,K] (the lower triangle is read) and R [K,C], shift >= 0, by
+ * a Cholesky factorisation in one workgroup with the factor in LDS (pitch K + 1: 132 096 bytes at K = 128), then a forward and a
+ * backward substitution per column of R; every inner sum is one fma chain over k ascending.  info (device): 0, or 1 + the index of
+ * the first pivot that is not positive - then W is zeros.  W must not be an operand. */
+int cmh_dch_solve(const double* A, double shift, const double* R, int32_t K, int32_t C, double* W, int32_t* info, void* stream);
+/* Qt [K,N] (bit-major; may be NULL) = (Y W^T + mu Z_i + mu Z_t)^T: q = sum_c Y[n][c] W[l][c] (c ascending), then fma(mu, z_i, q),
+ * then fma(mu, z_t, .).  obj2 (device): obj2[0] = (|Y - B W|^2 + lam |W|^2) + mu (|B - Z_i|^2 + |B - Z_t|^2), obj2[1] = |Z_i|^2 +
+ * |Z_t|^2; W [K,C], Z_i, Z_t [N,K].  Per-block partials, added in block order by a finishing kernel. */
+size_t cmh_dch_targets_workspace_bytes(int64_t N);
+int cmh_dch_targets(const float* Y, const int8_t* B, const double* W, const double* Z_i, const double* Z_t, double mu, double lam,
+                    int64_t N, int32_t K, int32_t C, double* Qt, double* obj2, void* workspace, size_t workspace_bytes, void* stream);
+/* Discrete cyclic coordinate descent, in place on B: `rounds` (1 .. 64) Gauss-Seidel rounds over the bits l = 0 .. K - 1 of every
+ * item n: t = Qt[l][n], then t = fma(-b_k, G[k][l], t) for k ascending, k != l; b_l = +1 where t > 0, -1 where t < 0, unchanged
+ * where t == 0.  G [K,K].  flips int64 [rounds] (device): the bits changed in each round; min_margin (device): the smallest |t|
+ * over all rounds x K x N decisions of the call. */
+size_t cmh_dch_dcc_workspace_bytes(int64_t N, int32_t rounds);
+int cmh_dch_dcc(const double* Qt, const double* G, int8_t* B, int64_t N, int32_t K, int32_t rounds, int64_t* flips, double* min_margin,
+                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * MITH (BASELINE.json config 3): token-returning trunk, HashingModel pieces, losses.
  * Activations are batch-major: [N, K, D] where the reference holds [K, N, D].
  * ------------------------------------------------------------------------------------------- */
