@@ -136,6 +136,9 @@ SIGNATURES = {
     "cmh_prof_gemm_begin": (C.c_int, [_i32]),
     "cmh_prof_gemm_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "cmh_prof_gemm_by_kernel": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "cmh_prof_gemm_conv1_fused": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "cmh_set_conv1_fused": (C.c_int, [_i32]),
+    "cmh_vit_patch_embed": (C.c_int, [C.POINTER(VitWeights), _p, _i32, _p, _i32, _i32, _p, _sz, _p, _p]),
     "cmh_cast_f32_to_bf16": (C.c_int, [_p, _p, _i64, _p]),
     "cmh_linear_act": (C.c_int, [_p, _p, _p, _p, _f, _i32, _p, _i32, _i32, _i32, _p]),
     "cmh_pair_softmax": (C.c_int, [_p, _p, _i32, _i32, _p]),
@@ -493,6 +496,12 @@ def set_pooled_tail(on: bool):
     check(lib().cmh_set_pooled_tail(1 if on else 0), "cmh_set_pooled_tail")
 
 
+def set_conv1_fused(on: int = -1):
+    """The image tower's inference stem as one implicit-GEMM launch (csrc/conv1_stem.hip): 1 on (default), 0 = patchify + GEMM,
+    -1 = environment (CMH_CONV1_FUSED).  Same bits either way."""
+    check(lib().cmh_set_conv1_fused(int(on)), "cmh_set_conv1_fused")
+
+
 def set_gemm_rows(on: int = -1):
     """Few-row GEMMs (M <= 512) on 64 x 64 tiles (csrc/gemm_rows.hip): 1 on (default), 0 = the wide kernel takes them, -1 = environment."""
     check(lib().cmh_set_gemm_rows(int(on)), "cmh_set_gemm_rows")
@@ -560,7 +569,12 @@ def prof_gemm_by_kernel():
     """after prof_gemm_end(): {kernel: (ms, flops, launches)} of the timed launches, split by the kernel that ran them"""
     ms, fl, n = (C.c_double * 3)(), (C.c_double * 3)(), (C.c_int64 * 3)()
     check(lib().cmh_prof_gemm_by_kernel(ms, fl, n), "cmh_prof_gemm_by_kernel")
-    return {k: (ms[i], fl[i], n[i]) for i, k in enumerate(("gemm_wide_kernel", "gemm_rows_kernel", "fallback"))}
+    by = {k: (ms[i], fl[i], n[i]) for i, k in enumerate(("gemm_wide_kernel", "gemm_rows_kernel", "fallback"))}
+    c_ms, c_fl, c_n = C.c_double(), C.c_double(), C.c_int64()
+    check(lib().cmh_prof_gemm_conv1_fused(C.byref(c_ms), C.byref(c_fl), C.byref(c_n)), "cmh_prof_gemm_conv1_fused")
+    if c_n.value:           # the fused conv1 stem (set_conv1_fused), listed in the sessions that launched it
+        by["conv1_stem_kernel"] = (c_ms.value, c_fl.value, c_n.value)
+    return by
 
 
 # ------------------------------------------------------------------------------------------ tower blocks

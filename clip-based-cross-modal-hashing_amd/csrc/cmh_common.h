@@ -220,6 +220,18 @@ static inline int conv1_k(int p, int dt) {
 }
 // image [B,3,R,R] f32 -> patches [B*g*g, ld] (dt), columns [0, 3p^2) the patch, [3p^2, ld) zeros; ld >= 3p^2
 int launch_patchify(const float* image, void* patches, int dt, int B, int R, int p, int ld, hipStream_t st);
+// conv1_stem.hip: conv1 as an implicit GEMM whose loader waves build the patch tile from the image - no patch matrix.  image_b /
+// batch_a: the batch as two tensors (rows of the first batch_a images from `image`); W [d, 3p^2] bf16; out [B*g*g, d] f32 with the
+// bits of launch_patchify + launch_gemm.  conv1_fused_takes: the shapes it is built for; conv1_fused_enabled: cmh_set_conv1_fused /
+// CMH_CONV1_FUSED (default on)
+bool conv1_fused_enabled();
+bool conv1_fused_takes(int dt, int p, int R, int d);
+int launch_conv1_fused(const float* image, const float* image_b, int batch_a, int B, int R, int p, const void* W, float* out, int d,
+                       hipStream_t st);
+// gemm.hip: the measurement hook (cmh_prof_gemm_*) for that launch, which does not pass through launch_gemm: the events of a timed
+// launch (false: no session, nothing to stamp), then its shape - counted under a name of its own (cmh_prof_gemm_conv1_fused)
+bool gemm_prof_open_conv1(hipEvent_t* ev0, hipEvent_t* ev1);
+void gemm_prof_close_conv1(int M, int N, int K);
 // dst[r, 0:cols) = src[r, 0:cols), dst[r, cols:ldd) = 0 for r < rows; elements of esz = 2 or 4 bytes (the padded conv1 weight and the
 // compaction of its gradient)
 int launch_copy_cols(const void* src, int lds, void* dst, int ldd, int rows, int cols, int esz, hipStream_t st);

@@ -51,8 +51,10 @@ int resid_f16(int dt, int d);
 
 // conv1 (kernel = stride = patch, no bias) as a patch-matrix GEMM into patch_out [B*g2, d] f32  (model/base/model.py:215,231-235).
 // image_b / batch_a: the batch comes as two tensors, rows [0, batch_a) from `image`.  conv1_w_pad: scratch of the K-padded weight.
+// keep_patches: the caller reads the patch matrix afterwards (training: conv1's weight gradient), so it must be written; false lets
+// the fused stem (conv1_stem.hip) run instead where it is built for the shape and switched on - `patches` is then left untouched.
 int conv1_stem(const cmh_vit_weights* w, int dt, const float* image, const float* image_b, int batch_a, int B, void* patches,
-               void* conv1_w_pad, float* patch_out, hipStream_t st);
+               bool keep_patches, void* conv1_w_pad, float* patch_out, hipStream_t st);
 
 // feat [B, embed] f32 = pool [B, d] . w_t^T: the last projection of either tower (no bias)
 int final_projection(int dt, const void* pool, const void* w_t, float* feat, int B, int embed, int d, hipStream_t st);

@@ -312,14 +312,18 @@ static int tower_xh(int dtb, int d, const cmh_taps* taps) {
 
 // K-padded (conv1_k): the patch rows and a copy of the weight carry zero columns pk..pkp-1, which add exact zeros - the K = pk
 // product in the same k order.
+// keep_patches false (inference: nothing reads the patch matrix but this GEMM) and a shape conv1_stem.hip's kernel is built for: ONE
+// launch whose loader waves build the patch tile from the image, `patches` untouched; the same bits in patch_out.
 int conv1_stem(const cmh_vit_weights* w, int dt, const float* image, const float* image_b, int batch_a, int B, void* patches,
-               void* conv1_w_pad, float* patch_out, hipStream_t st) {
+               bool keep_patches, void* conv1_w_pad, float* patch_out, hipStream_t st) {
   const int g = w->resolution / w->patch, g2 = g * g, d = w->width;
   const int pk = 3 * w->patch * w->patch, pkp = conv1_k(w->patch, dt);    // pkp != pk: the K-padded conv1
   const size_t e = dt == CMH_BF16 ? 2 : 4;
   int rc;
+  if (image_b) CMH_CHECK_ARG(batch_a > 0 && batch_a < B, "vit_encode: split batch %d of %d", batch_a, B);
+  if (!keep_patches && conv1_fused_enabled() && conv1_fused_takes(dt, w->patch, w->resolution, d))
+    return launch_conv1_fused(image, image_b, batch_a, B, w->resolution, w->patch, w->conv1_w, patch_out, d, st);
   if (image_b) {
-    CMH_CHECK_ARG(batch_a > 0 && batch_a < B, "vit_encode: split batch %d of %d", batch_a, B);
     if ((rc = launch_patchify(image, patches, dt, batch_a, w->resolution, w->patch, pkp, st))) return rc;
     if ((rc = launch_patchify(image_b, static_cast<char*>(patches) + static_cast<size_t>(batch_a) * g2 * pkp * e, dt, B - batch_a, w->resolution,
                               w->patch, pkp, st))) return rc;
@@ -353,6 +357,22 @@ extern "C" int cmh_set_text_token_packing(int32_t on) {
   return CMH_OK;
 }
 extern "C" int cmh_version(void) { return CMH_VERSION; }
+
+extern "C" int cmh_vit_patch_embed(const cmh_vit_weights* w, const float* image, int32_t batch_a, const float* image_b, int32_t batch,
+                                   int32_t keep_patches, void* scratch, size_t scratch_bytes, float* patch_out, void* stream) {
+  CMH_CHECK_ARG(w && image && scratch && patch_out && batch > 0, "vit_patch_embed: null pointer or empty batch");
+  CMH_CHECK_ARG(w->gemm_dtype == CMH_F32 || w->gemm_dtype == CMH_BF16 || w->gemm_dtype == CMH_FP8, "bad gemm_dtype %d", w->gemm_dtype);
+  CMH_CHECK_ARG(w->patch > 0 && w->resolution % w->patch == 0 && w->width % 128 == 0, "vit_patch_embed: resolution %d / patch %d / width %d",
+                w->resolution, w->patch, w->width);
+  const int dt = w->gemm_dtype == CMH_FP8 ? CMH_BF16 : w->gemm_dtype;
+  const size_t e = dt == CMH_BF16 ? 2 : 4, g = w->resolution / w->patch, pk = 3ull * w->patch * w->patch, pkp = conv1_k(w->patch, dt);
+  Arena a(scratch);
+  void* patches = a.take(static_cast<size_t>(batch) * g * g * pkp * e);
+  void* w_pad = a.take(pkp != pk ? static_cast<size_t>(w->width) * pkp * e : 0);
+  if (scratch_bytes < a.off) return fail(CMH_ERR_WORKSPACE, "vit_patch_embed: scratch %zu < %zu bytes", scratch_bytes, a.off);
+  CMH_CHECK_ARG((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "vit_patch_embed: scratch must be 256-byte aligned");
+  return conv1_stem(w, dt, image, image_b, batch_a, batch, patches, keep_patches != 0, w_pad, patch_out, as_stream(stream));
+}
 
 extern "C" size_t cmh_vit_workspace_bytes(const cmh_vit_weights* w, int32_t batch) {
   if (!w || batch <= 0 || w->patch <= 0) return 0;
@@ -390,7 +410,7 @@ static int vit_begin(const cmh_vit_weights* w, const float* image, int32_t batch
   r.dtb = dtb; r.xh = tower_xh(dtb, d, taps); r.d = d; r.B = B; r.T = T; r.M = M; r.causal = 0;
   lane_in_place(r);
   float* patch_out = static_cast<float*>(t.qkv);
-  if ((rc = conv1_stem(w, dt, image, image_b, batch_a, B, /*patches=*/t.mlp, t.conv1_w, patch_out, st))) return rc;
+  if ((rc = conv1_stem(w, dt, image, image_b, batch_a, B, /*patches=*/t.mlp, /*keep_patches=*/false, t.conv1_w, patch_out, st))) return rc;
   // [class ; patches] + positional, ln_pre  (:237-239)
   if ((rc = launch_vit_assemble_lnpre(patch_out, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                                       w->ln_pre_b, t.x, r.xh, B, g2, d, st))) return rc;

@@ -656,7 +656,8 @@ static int vit_forward_train_impl(const cmh_vit_weights* w, const float* image, 
   const int B = D.B, T = D.T, M = D.M, d = D.d;
   const Head head{w->ln_post_w, w->ln_post_b, w->proj_t};
   hipStream_t st = as_stream(stream);
-  if ((rc = conv1_stem(w, D.dt, image, nullptr, 0, B, t.patches, t.conv1_w, t.patch_out, st))) return rc;
+  // (the tape keeps the patch matrix: conv1's weight gradient reads it)
+  if ((rc = conv1_stem(w, D.dt, image, nullptr, 0, B, t.patches, /*keep_patches=*/true, t.conv1_w, t.patch_out, st))) return rc;
   // x_pre = [cls ; patches] + positional (kept for ln_pre's backward), x_0 = ln_pre(x_pre)
   if ((rc = launch_vit_assemble(t.patch_out, w->class_embedding, w->positional_embedding, t.x_pre, B, T - 1, d, st))) return rc;
   if ((rc = launch_layernorm_any(t.x_pre, kF32, nullptr, w->ln_pre_w, w->ln_pre_b, t.L[0].x_in, xkind(D.xh), M, d, st))) return rc;

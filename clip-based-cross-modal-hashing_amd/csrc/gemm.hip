@@ -303,6 +303,7 @@ static GemmProf g_prof;
 // AND every loader / consumer form (lc, lc2, lc3, lc2q: other schedules of its arithmetic on the same launches), [1]
 // "gemm_rows_kernel" the few-row kernel, [2] "fallback" the 128 x 128 kernel.
 static int kind_of(int family) { return family == GEMM_ROWS ? 1 : (family == GEMM_FALLBACK ? 2 : 0); }
+constexpr int kKindConv1 = 3;      // a fourth name, outside the three: the fused conv1 stem (conv1_stem.hip; cmh_prof_gemm_conv1_fused)
 
 // the measurement hook counts algorithmic FLOPs on REAL rows: FLOPs of `flops_per_row` x the rows of launch `launch` (the entry
 // g_prof.flops[launch] is created by the caller with the upper bound's FLOPs and corrected by _end() once the count has arrived)
@@ -348,6 +349,20 @@ static void prof_close(const GemmTimer& t, const GemmPlan& p, const GemmProblem&
   if (b) g_prof.dims.push_back({a.M + b->M, a.N + b->N, a.K, epi | (1 << 20)});   // (1 << 20: a grouped launch; rows / columns summed)
   else g_prof.dims.push_back({a.M, a.N, a.K, epi});
   g_prof.kind.push_back(kind_of(p.family));
+  g_prof.used += 2;
+}
+
+// The same hook for the one GEMM that launches outside run_gemm (conv1_stem.hip: it stamps the pair through hipExtLaunchKernelGGL)
+bool gemm_prof_open_conv1(hipEvent_t* ev0, hipEvent_t* ev1) {
+  if (!g_prof.on || g_prof.used + 2 > g_prof.ev.size()) return false;
+  *ev0 = g_prof.ev[g_prof.used];
+  *ev1 = g_prof.ev[g_prof.used + 1];
+  return true;
+}
+void gemm_prof_close_conv1(int M, int N, int K) {
+  g_prof.flops.push_back(2.0 * M * static_cast<double>(N) * K);
+  g_prof.dims.push_back({M, N, K, 0});
+  g_prof.kind.push_back(kKindConv1);
   g_prof.used += 2;
 }
 
@@ -496,7 +511,23 @@ extern "C" int cmh_prof_gemm_by_kernel(double* ms3, double* flops3, int64_t* lau
     if (hipEventElapsedTime(&t, g_prof.ev[i], g_prof.ev[i + 1]) != hipSuccess)
       return fail(CMH_ERR_LAUNCH, "prof_gemm_by_kernel: hipEventElapsedTime failed");
     const int k = g_prof.kind[i / 2];
+    if (k == kKindConv1) continue;      // (cmh_prof_gemm_conv1_fused's)
     ms3[k] += t; flops3[k] += g_prof.flops[i / 2]; launches3[k] += 1;
+  }
+  return CMH_OK;
+}
+
+extern "C" int cmh_prof_gemm_conv1_fused(double* ms, double* flops, int64_t* launches) {
+  using namespace cmh;
+  CMH_CHECK_ARG(ms && flops && launches, "prof_gemm_conv1_fused: null pointer");
+  CMH_CHECK_ARG(!g_prof.on, "prof_gemm_conv1_fused: call cmh_prof_gemm_end first");
+  *ms = 0.0; *flops = 0.0; *launches = 0;
+  for (size_t i = 0; i + 1 < g_prof.used; i += 2) {
+    if (g_prof.kind[i / 2] != kKindConv1) continue;
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, g_prof.ev[i], g_prof.ev[i + 1]) != hipSuccess)
+      return fail(CMH_ERR_LAUNCH, "prof_gemm_conv1_fused: hipEventElapsedTime failed");
+    *ms += t; *flops += g_prof.flops[i / 2]; *launches += 1;
   }
   return CMH_OK;
 }

@@ -428,6 +428,24 @@ class CLIP(nn.Module):
                                        None if tp is None else C.byref(tp), c.stream), "cmh_vit_encode")
         return self._finish(c)[0]
 
+    def patch_embed(self, image, image_b=None, keep_patches=False):
+        """conv1 alone, as the image tower runs it (cmh_vit_patch_embed): image f32 [B,3,R,R] (+ image_b: the batch as two tensors)
+        -> (patch_out f32 [B*g*g, width], the patch matrix [B*g*g, K] in the GEMM dtype or None).  keep_patches=False is the
+        inference stem (one fused launch where N.set_conv1_fused allows), True the training forward's two launches."""
+        images, _ = self._operands("patch_embed", images=[image] if image_b is None else [image, image_b])
+        s = self._tower_struct(T.VIT)
+        B, g2, dev = sum(x.shape[0] for x in images), (s.resolution // s.patch) ** 2, images[0].device
+        f32 = self._gemm_dtype == N.F32
+        e, pk = (4 if f32 else 2), 3 * s.patch * s.patch
+        K = pk if s.patch % 4 == 0 and pk % (32 if f32 else 64) == 0 else -(-pk // 256) * 256      # (csrc/cmh_common.h: conv1_k)
+        scratch = torch.empty(-(-B * g2 * K * e // 256) * 256 + s.width * K * e + 256, dtype=torch.uint8, device=dev)
+        out = torch.empty(B * g2, s.width, dtype=torch.float32, device=dev)
+        N.check(N.lib().cmh_vit_patch_embed(C.byref(s), N.ptr(images[0]), images[0].shape[0], N.ptr(images[1]) if image_b is not None else None,
+                                            B, 1 if keep_patches else 0, N.ptr(scratch), scratch.numel(), N.ptr(out), N.stream_ptr(dev)),
+                "cmh_vit_patch_embed")
+        patches = scratch[:B * g2 * K * e].view(torch.float32 if f32 else torch.bfloat16).view(B * g2, K) if keep_patches else None
+        return out, patches
+
     def encode_text(self, text, key_padding_mask=None, taps=None):
         """text i64 [B,L] -> [B, embed_dim] f32  (reference model/base/model.py:359-372)."""
         kpm = None if key_padding_mask is None else key_padding_mask.to(torch.uint8).contiguous()

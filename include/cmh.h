@@ -242,6 +242,9 @@ int cmh_attention_pair(int32_t dtype, const void* qkv0, void* o0, int32_t B0, in
 int cmh_prof_gemm_begin(int32_t max_launches);
 int cmh_prof_gemm_end(double* total_ms, double* total_flops, int64_t* launches);
 int cmh_prof_gemm_by_kernel(double* ms3, double* flops3, int64_t* launches3);
+/* ... and (after _end) the share of the fused conv1 stem (cmh_set_conv1_fused: conv1_stem_kernel), which _end's sums include and the
+ * three names of _by_kernel do not. */
+int cmh_prof_gemm_conv1_fused(double* ms, double* flops, int64_t* launches);
 
 /* Tuning overrides of the N % 256 == 0 GEMM kernel, for A/B measurements and for tests that must reach every variant:
  * tile_rows in {96, 128, 160} pins the tile height (-1: chosen per launch from M, N, K and the CU count); order_group picks the
@@ -285,6 +288,21 @@ int cmh_gemm_plan(int32_t dt, int32_t epi, const int32_t* a5, const int32_t* b5,
  * block's out_proj, ln_2 and MLP (bit-identical features, three GEMMs of M = B instead of M = B*T).  on = 0 switches that off
  * (A/B measurements, the equality test); also CMH_POOLED_TAIL=0 in the environment.  Process-wide, not thread-safe. */
 int cmh_set_pooled_tail(int32_t on);
+
+/* The image tower's stem in inference (cmh_vit_encode, cmh_clip_encode_pair[2], ...): conv1 (kernel = stride = patch, no bias;
+ * model/base/model.py:215,231-235) runs as ONE implicit-GEMM launch (csrc/conv1_stem.hip) whose loader waves build the bf16 patch tile
+ * from the f32 image, instead of a patch-matrix kernel followed by a GEMM.  Taken for bf16 conv1 (the bf16 and fp8 modes), patch 16 / 32
+ * / 64, resolution % 4 == 0, width % 256 == 0; every other shape, the f32 mode and the training forward (whose
+ * tape keeps the patch matrix for conv1's weight gradient) run the two launches.  Same bits either way.  on = 0 switches it off (A/B
+ * measurements, the equality test), 1 on, -1 = environment (CMH_CONV1_FUSED=0 is off; default on).  Process-wide, not thread-safe. */
+int cmh_set_conv1_fused(int32_t on);
+/* conv1 alone, as the towers run it: patch_out [batch * g^2, width] f32 from image [batch_a, 3, R, R] f32 (+ image_b
+ * [batch - batch_a, 3, R, R] when the batch comes as two tensors; NULL / batch_a ignored otherwise).  Only w's resolution, patch,
+ * width, gemm_dtype and conv1_w are read.  keep_patches != 0: the caller wants the patch matrix [batch * g^2, K] (K = 3 patch^2, or
+ * padded as the GEMMs need it) at the start of `scratch` - the two-launch stem; 0: the inference stem, fused where cmh_set_conv1_fused
+ * allows, `scratch` then untouched.  scratch: 256-byte aligned, the patch matrix (+ a K-padded copy of the weight behind it). */
+int cmh_vit_patch_embed(const cmh_vit_weights* w, const float* image, int32_t batch_a, const float* image_b, int32_t batch,
+                        int32_t keep_patches, void* scratch, size_t scratch_bytes, float* patch_out, void* stream);
 
 /* bf16 training mode: the residual-gradient stream between the blocks of a tower's backward pass (cmh_vit_backward[_part],
  * cmh_text_backward[_part], cmh_blocks_backward; reference: autograd through model/base/model.py:167-207) is carried as bf16 - the
