@@ -128,6 +128,11 @@ SIGNATURES = {
     "cmh_ddbh_bp_loss_backward": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32] + [C.c_double] * 6 + [_p, _p, _p, _p, _p, _p]),
     "cmh_ddbh_quant_loss": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _sz, _p]),
     "cmh_ddbh_quant_loss_backward": (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _p]),
+    # label-free joint-semantics loss (csrc/djsrh.hip): none of the cmh_djsrh_* entries has an upstream counterpart
+    "cmh_djsrh_workspace_bytes": (_sz, [_i32, _i32, _i32]),             # no upstream counterpart
+    "cmh_djsrh_target": (C.c_int, [_p, _p, _i32, _i32, _f, _f, _f, _p, _p, _sz, _p]),      # no upstream counterpart
+    "cmh_djsrh_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
+    "cmh_djsrh_loss_backward": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
     "cmh_fp8_quantize_weight": (C.c_int, [_p, _p, _p, _i32, _i32, _p]),
     "cmh_fp8_quantize": (C.c_int, [_p, _i32, _p, _i64, _f, _p]),
     "cmh_fp8_dequantize": (C.c_int, [_p, _p, _i64, _f, _p]),
@@ -1666,6 +1671,64 @@ def ddbh_quant_loss_backward(hs, colsum, dloss):
     check(lib().cmh_ddbh_quant_loss_backward(_ptr_array(hs), len(hs), ptr(colsum), B, K, ptr(dloss), _ptr_array(dh), stream_ptr(colsum.device)),
           "cmh_ddbh_quant_loss_backward")
     return dh
+
+
+DJSRH_MAX_B, DJSRH_MAX_K, DJSRH_MAX_D = 1024, 128, 4096      # csrc/djsrh.hip's limits, for the wrappers' messages
+
+
+def _djsrh_pair(what, a, b):
+    a, b = f32c(a), f32c(b)
+    require_gpu(a, b)
+    if a.dim() != 2:
+        raise NativeError(f"{what}: two f32 matrices [B, n] are expected")
+    fit(what, (b, a.shape))
+    return a, b
+
+
+def _djsrh_ws(what, B, K, D, dev):
+    need = lib().cmh_djsrh_workspace_bytes(B, K, D)
+    if need == 0:
+        raise NativeError(f"{what}: B={B} K={K} D={D}: 1 <= B <= {DJSRH_MAX_B}, 1 <= K <= {DJSRH_MAX_K}, 1 <= D <= {DJSRH_MAX_D} are built")
+    return workspace(need, dev, "loss")
+
+
+def djsrh_target(fi, ft, beta, eta, mu):
+    """DJSRH's joint-semantics affinity of a batch from the stock towers' features fi, ft [B, D] -> S f32 [B, B] =
+    mu ((1 - eta) St + (eta / B) St St^T), St = beta (2 cos(fi) - 1) + (1 - beta) (2 cos(ft) - 1); symmetric bit for bit"""
+    fi, ft = _djsrh_pair("djsrh_target", fi, ft)
+    B, D = fi.shape
+    ws = _djsrh_ws("djsrh_target", B, 1, D, fi.device)
+    S = torch.empty(B, B, dtype=torch.float32, device=fi.device)
+    check(lib().cmh_djsrh_target(ptr(fi), ptr(ft), B, D, float(beta), float(eta), float(mu), ptr(S), ptr(ws), ws.numel(), stream_ptr(fi.device)),
+          "cmh_djsrh_target")
+    return S
+
+
+def djsrh_loss(hi, ht, S, lambda1, lambda2, keep=False):
+    """lambda1 mean((b_I b_I^T - S)^2) + mean((b_I b_T^T - S)^2) + lambda2 mean((b_T b_T^T - S)^2), b the row-normalised hi, ht [B, K]
+    -> (loss [1], terms [3], tape for the backward or None, the operands as passed)"""
+    hi, ht = _djsrh_pair("djsrh_loss", hi, ht)
+    S = f32c(S)
+    require_gpu(S)
+    B, K = hi.shape
+    fit("djsrh_loss", (S, (B, B)))
+    dev = hi.device
+    ws = _djsrh_ws("djsrh_loss", B, K, 1, dev)
+    loss, terms = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(3, dtype=torch.float32, device=dev)
+    tape = torch.empty(2 * B + 3 * B * B, dtype=torch.float32, device=dev) if keep else None
+    check(lib().cmh_djsrh_loss(ptr(hi), ptr(ht), ptr(S), B, K, float(lambda1), float(lambda2), ptr(terms), ptr(loss), ptr(tape), ptr(ws),
+                               ws.numel(), stream_ptr(dev)), "cmh_djsrh_loss")
+    return loss, terms, tape, hi, ht
+
+
+def djsrh_loss_backward(hi, ht, tape, lambda1, lambda2, dloss):
+    """-> d_hi, d_ht f32 [B, K] = dloss * d loss / d hi, ht from the forward's tape"""
+    B, K = hi.shape
+    d_hi, d_ht = torch.empty_like(hi), torch.empty_like(ht)
+    ws = _djsrh_ws("djsrh_loss_backward", B, K, 1, hi.device)
+    check(lib().cmh_djsrh_loss_backward(ptr(hi), ptr(ht), ptr(tape), B, K, float(lambda1), float(lambda2), ptr(f32c(dloss).reshape(1)),
+                                        ptr(d_hi), ptr(d_ht), ptr(ws), ws.numel(), stream_ptr(hi.device)), "cmh_djsrh_loss_backward")
+    return d_hi, d_ht
 
 
 def dchmt_loss(img, txt, label, output_dim, similarity="euclidean", loss_type="l2", vartheta=0.5, sim_threshold=0.1):

@@ -18,6 +18,7 @@ _REGISTRY = {
     'DDBH': ("train.DDBH.hash_train", "DDBHTrainer"),
     'ITQ': ("train.ITQ.hash_train", "ITQTrainer"),       # training-free: LSH / PCAH / ITQ heads fitted on the towers' features
     'DCH': ("train.DCH.hash_train", "DCHTrainer"),       # training-free, supervised: discrete cross-modal hashing on the towers' features
+    'DJSRH': ("train.DJSRH.hash_train", "DJSRHTrainer"), # label-free fine-tuning: joint-semantics reconstruction (ICCV 2019)
 }
 _NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
 

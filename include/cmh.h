@@ -375,6 +375,24 @@ int cmh_ddbh_quant_loss(const float* const* h, int32_t calls, const float* label
 int cmh_ddbh_quant_loss_backward(const float* const* h, int32_t calls, const float* colsum, int32_t B, int32_t K, const float* dloss,
                                  float* const* dh, void* stream);
 
+/* DJSRH joint-semantics target and reconstruction loss (Su, Zhong, Zhang: Deep Joint-Semantics Reconstructing Hashing, ICCV 2019;
+ * no upstream counterpart), label-free.  n(x) = x / max(|x|, 1e-12) per row.  1 <= B <= 1024, 1 <= K <= 128, 1 <= D <= 4096; every
+ * workspace is 256-byte aligned and holds cmh_djsrh_workspace_bytes(B, K, D) bytes (0 for a shape out of range).
+ * Target: fi, ft f32 [B,D] the stock towers' features of the batch -> S f32 [B,B] =
+ * mu ((1 - eta) St + (eta / B) St St^T) with St = beta (2 n(fi) n(fi)^T - 1) + (1 - beta) (2 n(ft) n(ft)^T - 1); symmetric bit for bit.
+ * Loss: hi, ht f32 [B,K] the heads' outputs, b = n(h) -> terms f32 [3] = the means of (b_I b_I^T - S)^2, (b_I b_T^T - S)^2,
+ * (b_T b_T^T - S)^2 and loss f32 [1] = lambda1 terms[0] + terms[1] + lambda2 terms[2]; tape (NULL: nothing is kept) f32
+ * [2B + 3 B^2] receives the row norms of hi and ht and the three residual matrices.  Backward: d_hi, d_ht f32 [B,K] = dloss[0] *
+ * d loss / d hi, ht from the tape (it takes S as symmetric, as the target is; S and the features get no gradient).  f32 sums in a
+ * fixed order, no atomics: two calls give the same bits. */
+size_t cmh_djsrh_workspace_bytes(int32_t B, int32_t K, int32_t D);
+int cmh_djsrh_target(const float* fi, const float* ft, int32_t B, int32_t D, float beta, float eta, float mu, float* S, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cmh_djsrh_loss(const float* hi, const float* ht, const float* S, int32_t B, int32_t K, float lambda1, float lambda2, float* terms,
+                   float* loss, float* tape, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_djsrh_loss_backward(const float* hi, const float* ht, const float* tape, int32_t B, int32_t K, float lambda1, float lambda2,
+                            const float* dloss, float* d_hi, float* d_ht, void* workspace, size_t workspace_bytes, void* stream);
+
 /* DMsH-LN multi-similarity loss, reference train/DMsH_LN/MSLOSS.py:13-55 `MultiSimilarityLoss.forward(feats, labels, feat2)` in the
  * branch its trainer takes (train/DMsH_LN/hash_train.py:58-60; not the "cifar10-1" branch): feats (and feat2, NULL = feats) f32
  * [B,K] hash outputs, labels f32 [B,Kl] = the LabelNet codes (two samples are similar when their codes' dot product is > 0)
