@@ -1835,6 +1835,33 @@ def _f64c(t):
     return t.contiguous()
 
 
+def _running(what, *pairs):
+    """Running sums passed back in to be added to, as (tensor, shape) pairs: each contiguous f64 of its shape, on the GPU (None passes)."""
+    fit(what, *pairs)
+    for t, _ in pairs:
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
+            raise NativeError(f"{what}: the running sums must be contiguous f64 tensors")
+    require_gpu(*(t for t, _ in pairs))
+
+
+def _out_view(what, name, t, shape, dtype, dev):
+    """An output the caller may hand in as a view to fill: made here where None, else contiguous, of this shape and dtype, on the GPU."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    fit(what, (t, shape))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise NativeError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor")
+    require_gpu(t)
+    return t
+
+
+def _head_outputs(d, k, dev):
+    """-> W_i, b_i, W_t, b_t (f32 [K, D] / [K]) and s (f64 [1]) for the heads entries to fill"""
+    W_i, W_t = (torch.empty(k, d, dtype=torch.float32, device=dev) for _ in range(2))
+    b_i, b_t = (torch.empty(k, dtype=torch.float32, device=dev) for _ in range(2))
+    return W_i, b_i, W_t, b_t, torch.empty(1, dtype=torch.float64, device=dev)
+
+
 def itq_moments(F, sums=None):
     """Running f64 sums of one batch of f32 features F [N, D]: (sum [D], sq [D, D]) (+)= (sum_n f, sum_n f f^T).  `sums`: the pair a
     previous call returned, updated in place; None starts new ones."""
@@ -1847,8 +1874,7 @@ def itq_moments(F, sums=None):
     if sums is None:
         sums, acc = (torch.empty(d, dtype=torch.float64, device=dev), torch.empty(d, d, dtype=torch.float64, device=dev)), 0
     else:
-        fit("itq_moments", (sums[0], (d,)), (sums[1], (d, d)))
-        _f64c(sums[0]), _f64c(sums[1])
+        _running("itq_moments", (sums[0], (d,)), (sums[1], (d, d)))
         acc = 1
     ws = workspace(lib().cmh_itq_moments_workspace_bytes(n, d), dev, "itq")
     check(lib().cmh_itq_moments(ptr(F), n, d, ptr(sums[0]), ptr(sums[1]), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_moments")
@@ -1895,11 +1921,7 @@ def itq_project(F, mu, alpha, P, out=None):
     fit("itq_project", (mu, (d,)), (P, (d, k)))
     if alpha.numel() != 1:
         raise NativeError("itq_project: alpha must hold one element")
-    if out is None:
-        out = torch.empty(n, k, dtype=torch.float64, device=F.device)
-    fit("itq_project", (out, (n, k)))
-    if out.dtype != torch.float64 or not out.is_contiguous():
-        raise NativeError("itq_project: out must be a contiguous f64 tensor")
+    out = _out_view("itq_project", "out", out, (n, k), torch.float64, F.device)
     check(lib().cmh_itq_project(ptr(F), n, d, k, ptr(mu), ptr(alpha), ptr(P), ptr(out), stream_ptr(F.device)), "cmh_itq_project")
     return out
 
@@ -1958,12 +1980,9 @@ def itq_heads(P, R, mu_i, mu_t, alpha, zz, rows):
     d, k = ops[0].shape
     fit("itq_heads", (ops[1], (k, k)), (ops[2], (d,)), (ops[3], (d,)), (ops[4], (2,)), (ops[5], (1,)))
     dev = ops[0].device
-    W_i, W_t = (torch.empty(k, d, dtype=torch.float32, device=dev) for _ in range(2))
-    b_i, b_t = (torch.empty(k, dtype=torch.float32, device=dev) for _ in range(2))
-    s = torch.empty(1, dtype=torch.float64, device=dev)
-    check(lib().cmh_itq_heads(*(ptr(t) for t in ops), int(rows), d, k, ptr(W_i), ptr(b_i), ptr(W_t), ptr(b_t), ptr(s), stream_ptr(dev)),
-          "cmh_itq_heads")
-    return W_i, b_i, W_t, b_t, s
+    outs = _head_outputs(d, k, dev)
+    check(lib().cmh_itq_heads(*(ptr(t) for t in ops), int(rows), d, k, *(ptr(t) for t in outs), stream_ptr(dev)), "cmh_itq_heads")
+    return outs
 
 
 def itq_heads_pair(P_i, P_t, R, mu_i, mu_t, alpha, zz, rows):
@@ -1973,12 +1992,9 @@ def itq_heads_pair(P_i, P_t, R, mu_i, mu_t, alpha, zz, rows):
     d, k = ops[0].shape
     fit("itq_heads_pair", (ops[1], (d, k)), (ops[2], (k, k)), (ops[3], (d,)), (ops[4], (d,)), (ops[5], (2,)), (ops[6], (1,)))
     dev = ops[0].device
-    W_i, W_t = (torch.empty(k, d, dtype=torch.float32, device=dev) for _ in range(2))
-    b_i, b_t = (torch.empty(k, dtype=torch.float32, device=dev) for _ in range(2))
-    s = torch.empty(1, dtype=torch.float64, device=dev)
-    check(lib().cmh_itq_heads_pair(*(ptr(t) for t in ops), int(rows), d, k, ptr(W_i), ptr(b_i), ptr(W_t), ptr(b_t), ptr(s), stream_ptr(dev)),
-          "cmh_itq_heads_pair")
-    return W_i, b_i, W_t, b_t, s
+    outs = _head_outputs(d, k, dev)
+    check(lib().cmh_itq_heads_pair(*(ptr(t) for t in ops), int(rows), d, k, *(ptr(t) for t in outs), stream_ptr(dev)), "cmh_itq_heads_pair")
+    return outs
 
 
 def itq_cross_moments(Fi, Ft, cross=None):
@@ -1994,10 +2010,7 @@ def itq_cross_moments(Fi, Ft, cross=None):
     if cross is None:
         cross, acc = torch.empty(d, d, dtype=torch.float64, device=dev), 0
     else:
-        fit("itq_cross_moments", (cross, (d, d)))
-        if cross.dtype != torch.float64 or not cross.is_contiguous():
-            raise NativeError("itq_cross_moments: the running sum must be a contiguous f64 tensor")
-        require_gpu(cross)
+        _running("itq_cross_moments", (cross, (d, d)))
         acc = 1
     ws = workspace(lib().cmh_itq_cross_moments_workspace_bytes(n, d), dev, "itq")
     check(lib().cmh_itq_cross_moments(ptr(Fi), ptr(Ft), n, d, ptr(cross), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_itq_cross_moments")
@@ -2101,11 +2114,7 @@ def dch_xtb(X, B, want_bsum=False, into=None):
             bsum = torch.empty(k, dtype=torch.float64, device=dev)
     else:
         out, bsum = into if want_bsum else (into, None)
-        fit("dch_xtb", (out, (dx, k)), (bsum, (k,)))
-        for t in (out, bsum):
-            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous()):
-                raise NativeError("dch_xtb: the running sums must be contiguous f64 tensors")
-        require_gpu(out, bsum)
+        _running("dch_xtb", (out, (dx, k)), (bsum, (k,)))
         acc = 1
     ws = workspace(lib().cmh_dch_xtb_workspace_bytes(n, dx, k), dev, "dch")
     check(lib().cmh_dch_xtb(ptr(X), ptr(B), n, dx, k, ptr(out), ptr(bsum), acc, ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dch_xtb")
@@ -2164,12 +2173,7 @@ def dch_targets(Y, B, W, Z_i, Z_t, mu, lam, want_q=True, obj2=None):
     fit("dch_targets", (Y, (n, c)), (W, (k, c)), (Z_i, (n, k)), (Z_t, (n, k)))
     dev = B.device
     Qt = torch.empty(k, n, dtype=torch.float64, device=dev) if want_q else None
-    if obj2 is None:
-        obj2 = torch.empty(2, dtype=torch.float64, device=dev)
-    fit("dch_targets", (obj2, (2,)))
-    if obj2.dtype != torch.float64 or not obj2.is_contiguous():
-        raise NativeError("dch_targets: obj2 must be a contiguous f64 pair")
-    require_gpu(obj2)
+    obj2 = _out_view("dch_targets", "obj2", obj2, (2,), torch.float64, dev)
     ws = workspace(lib().cmh_dch_targets_workspace_bytes(n), dev, "dch")
     check(lib().cmh_dch_targets(ptr(Y), ptr(B), ptr(W), ptr(Z_i), ptr(Z_t), float(mu), float(lam), n, k, c, ptr(Qt), ptr(obj2), ptr(ws),
                                 ws.numel(), stream_ptr(dev)), "cmh_dch_targets")
@@ -2185,14 +2189,8 @@ def dch_dcc(Qt, G, B, rounds, flips=None, min_margin=None):
     rounds = int(rounds)
     fit("dch_dcc", (Qt, (k, n)), (G, (k, k)))
     dev = B.device
-    if flips is None:
-        flips = torch.empty(max(rounds, 0), dtype=torch.int64, device=dev)
-    if min_margin is None:
-        min_margin = torch.empty(1, dtype=torch.float64, device=dev)
-    fit("dch_dcc", (flips, (rounds,)), (min_margin, (1,)))
-    if flips.dtype != torch.int64 or min_margin.dtype != torch.float64 or not flips.is_contiguous():
-        raise NativeError("dch_dcc: flips must be a contiguous int64 vector and min_margin one f64")
-    require_gpu(flips, min_margin)
+    flips = _out_view("dch_dcc", "flips", flips, (max(rounds, 0),), torch.int64, dev)
+    min_margin = _out_view("dch_dcc", "min_margin", min_margin, (1,), torch.float64, dev)
     ws = workspace(lib().cmh_dch_dcc_workspace_bytes(n, rounds), dev, "dch")
     check(lib().cmh_dch_dcc(ptr(Qt), ptr(G), ptr(B), n, k, rounds, ptr(flips), ptr(min_margin), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dch_dcc")
     return flips, min_margin

@@ -12,10 +12,9 @@
 //   targets      Qt [K, N] = (Y W^T + mu Z_i + mu Z_t)^T and the objective of (B, W, Z)
 //   dcc          `rounds` Gauss-Seidel rounds over the bits of every item; flips per round and the smallest |t|
 //
-// Determinism, as in itq.hip: every output element is one sum in a fixed order.  The O(N) products cut the rows into chunks of
-// kChunk (a constant), sum each chunk in row order and then the chunks in chunk order; block reductions are fixed trees and the
-// per-block partials are added in block order; nothing is accumulated with atomics, and no kernel waits for another workgroup.
-#include "cmh_common.h"
+// Determinism: fit_common.h states it, with the chunked products (X^T B and B^T B are its X^T Y kernel with int8 operands), the column
+// sum, the block reductions and the covariance element, all shared with itq.hip.
+#include "fit_common.h"
 
 #include <cfloat>
 #include <cmath>
@@ -23,115 +22,7 @@
 namespace cmh {
 namespace {
 
-constexpr int kMaxD = 1024, kMaxK = 128, kMaxC = 1024, kMaxRounds = 64;
-constexpr int kChunk = 2048;                  // rows per partial sum of the O(N) products (itq.hip's)
-constexpr int kTile = 64, kStage = 16;        // X^T B: output tile and rows per LDS stage
-constexpr long long kMaxRows = 65535ll * kChunk;      // the chunk index is a grid dimension (y or z: at most 65535)
-
-inline int chunks_of(long long n) { return static_cast<int>((n + kChunk - 1) / kChunk); }
-inline bool rows_ok(long long n) { return n >= 1 && n <= kMaxRows; }
-
-// ---- X^T B over row chunks (itq.hip's X^T Y kernel with an int8 right operand) ---------------------------------------------------
-// part[c][i][j] = sum over the rows n of chunk c, in row order, of X[n][i] * B[n][j] (one fma per row).  One block: a 64 x 64 tile
-// of (i, j) for one chunk; thread (ti, tj) holds i = 4 ti + a, j = tj + 16 b.
-template <typename TX>
-__global__ __launch_bounds__(256) void xtb_partial_kernel(const TX* __restrict__ X, const int8_t* __restrict__ B, double* __restrict__ part,
-                                                          long long N, int Da, int Db) {
-  __shared__ double xs[kStage][kTile];
-  __shared__ double ys[kStage][kTile];
-  const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-  const int j0 = blockIdx.x * kTile, i0 = blockIdx.y * kTile;
-  const long long n_lo = static_cast<long long>(blockIdx.z) * kChunk;
-  const long long n_hi = n_lo + kChunk < N ? n_lo + kChunk : N;
-  double acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-  for (long long n0 = n_lo; n0 < n_hi; n0 += kStage) {
-    for (int t = tid; t < kStage * kTile; t += 256) {
-      const int r = t >> 6, c = t & 63;
-      const long long n = n0 + r;
-      const bool row = n < n_hi;
-      xs[r][c] = (row && i0 + c < Da) ? static_cast<double>(X[n * Da + i0 + c]) : 0.0;
-      ys[r][c] = (row && j0 + c < Db) ? static_cast<double>(B[n * Db + j0 + c]) : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int r = 0; r < kStage; ++r) {
-      double xv[4], yv[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) xv[a] = xs[r][ti * 4 + a];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) yv[b] = ys[r][tj + 16 * b];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = fma(xv[a], yv[b], acc[a][b]);
-    }
-    __syncthreads();
-  }
-  double* out = part + static_cast<size_t>(blockIdx.z) * Da * Db;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int i = i0 + ti * 4 + a;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int j = j0 + tj + 16 * b;
-      if (i < Da && j < Db) out[static_cast<size_t>(i) * Db + j] = acc[a][b];
-    }
-  }
-}
-
-// part[c][k] = sum over the rows of chunk c, in row order, of B[n][k]
-__global__ __launch_bounds__(64) void bsum_partial_kernel(const int8_t* __restrict__ B, double* __restrict__ part, long long N, int K) {
-  const int k = blockIdx.x * 64 + threadIdx.x;
-  if (k >= K) return;
-  const long long n_lo = static_cast<long long>(blockIdx.y) * kChunk;
-  const long long n_hi = n_lo + kChunk < N ? n_lo + kChunk : N;
-  double acc = 0.0;
-  for (long long n = n_lo; n < n_hi; ++n) acc += static_cast<double>(B[n * K + k]);
-  part[static_cast<size_t>(blockIdx.y) * K + k] = acc;
-}
-
-// out[e] = (accumulate ? out[e] : 0) + (part[0][e] + part[1][e] + ...), the chunks in order
-__global__ __launch_bounds__(256) void chunk_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int chunks, size_t elems,
-                                                           int accumulate) {
-  const size_t e = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= elems) return;
-  double acc = 0.0;
-  for (int c = 0; c < chunks; ++c) acc += part[static_cast<size_t>(c) * elems + e];
-  out[e] = accumulate ? out[e] + acc : acc;
-}
-
-// ---- block reductions: fixed trees ---------------------------------------------------------------------------------------------
-template <int T>
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
-
-template <int T>
-__device__ __forceinline__ double block_min(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) sh[threadIdx.x] = fmin(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
+constexpr int kMaxC = 1024, kMaxRounds = 64;
 
 // ---- small element-wise pieces -------------------------------------------------------------------------------------------------
 // S[i][j] = alpha^2 (sq[i][j] / N - mu[i] mu[j]): cmh_itq_cca_covariance's S_mm, symmetric bit for bit where sq is
@@ -141,7 +32,7 @@ __global__ __launch_bounds__(256) void covariance_kernel(const double* __restric
   if (e >= static_cast<size_t>(D) * D) return;
   const int i = static_cast<int>(e / D), j = static_cast<int>(e % D);
   const double a = alpha[0];
-  S[e] = (a * a) * (sq[e] * inv_n - mu[i] * mu[j]);
+  S[e] = cov_element(a * a, sq[e], inv_n, mu[i], mu[j]);
 }
 
 // B = +1 where za + zb >= 0, else -1 (a NaN gives -1)
@@ -447,14 +338,10 @@ struct TargetsWs {
   double* rpart;      // [ceil(N / 256)]
   size_t total;
 };
-TargetsWs carve_targets(char* base, long long N) {
-  TargetsWs w;
+TargetsWs carve_targets(void* ws, long long N) {
+  Carver c(ws);
   const size_t fb = static_cast<size_t>((N + 63) / 64), rb = static_cast<size_t>((N + 255) / 256);
-  w.fpart = reinterpret_cast<double*>(base);
-  const size_t off = align_up(fb * 2 * sizeof(double), 256);
-  w.rpart = reinterpret_cast<double*>(base + off);
-  w.total = off + align_up(rb * sizeof(double), 256);
-  return w;
+  return {c.take<double>(fb * 2 * sizeof(double)), c.take<double>(rb * sizeof(double)), c.total()};
 }
 
 struct DccWs {
@@ -462,14 +349,10 @@ struct DccWs {
   double* mpart;      // [ceil(N / 256)]
   size_t total;
 };
-DccWs carve_dcc(char* base, long long N, int rounds) {
-  DccWs w;
+DccWs carve_dcc(void* ws, long long N, int rounds) {
+  Carver c(ws);
   const size_t blocks = static_cast<size_t>((N + 255) / 256);
-  w.fpart = reinterpret_cast<long long*>(base);
-  const size_t off = align_up(blocks * rounds * sizeof(long long), 256);
-  w.mpart = reinterpret_cast<double*>(base + off);
-  w.total = off + align_up(blocks * sizeof(double), 256);
-  return w;
+  return {c.take<long long>(blocks * rounds * sizeof(long long)), c.take<double>(blocks * sizeof(double)), c.total()};
 }
 
 bool reserve_lds(const void* kernel, size_t lds) {
@@ -504,7 +387,7 @@ extern "C" int cmh_dch_start(const double* Za, const double* Zb, int64_t N, int3
 
 extern "C" size_t cmh_dch_xtb_workspace_bytes(int64_t N, int32_t Dx, int32_t K) {
   if (!rows_ok(N) || Dx < 1 || Dx > kMaxD || K < 1 || K > kMaxK) return 0;
-  return align_up(static_cast<size_t>(chunks_of(N)) * (static_cast<size_t>(Dx) + 1) * K * sizeof(double), 256);
+  return carve_product(nullptr, N, Dx, K, true).total;
 }
 
 extern "C" int cmh_dch_xtb(const float* X, const int8_t* B, int64_t N, int32_t Dx, int32_t K, double* out, double* bsum, int32_t accumulate,
@@ -516,26 +399,16 @@ extern "C" int cmh_dch_xtb(const float* X, const int8_t* B, int64_t N, int32_t D
   const size_t need = cmh_dch_xtb_workspace_bytes(N, Dx, K);
   CMH_CHECK_ARG(workspace_bytes >= need, "dch_xtb: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const int ch = chunks_of(N);
-  const size_t elems = static_cast<size_t>(Dx) * K;
-  double* part = static_cast<double*>(workspace);
-  double* part_sum = part + static_cast<size_t>(ch) * elems;
-  hipLaunchKernelGGL((xtb_partial_kernel<float>), dim3((K + kTile - 1) / kTile, (Dx + kTile - 1) / kTile, ch), dim3(256), 0, st, X, B, part,
-                     static_cast<long long>(N), Dx, K);
-  hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((elems + 255) / 256)), dim3(256), 0, st, static_cast<const double*>(part), out,
-                     ch, elems, accumulate ? 1 : 0);
-  if (bsum) {
-    hipLaunchKernelGGL(bsum_partial_kernel, dim3((K + 63) / 64, ch), dim3(64), 0, st, B, part_sum, static_cast<long long>(N), K);
-    hipLaunchKernelGGL(chunk_reduce_kernel, dim3((K + 255) / 256), dim3(256), 0, st, static_cast<const double*>(part_sum), bsum, ch,
-                       static_cast<size_t>(K), accumulate ? 1 : 0);
-  }
+  const ProductWs w = carve_product(workspace, N, Dx, K, true);
+  launch_xty(X, B, N, Dx, K, w.part, out, accumulate, st);
+  if (bsum) launch_colsum(B, N, K, w.part_sum, bsum, accumulate, st);
   CMH_CHECK_LAUNCH("dch_xtb");
   return CMH_OK;
 }
 
 extern "C" size_t cmh_dch_btb_workspace_bytes(int64_t N, int32_t K) {
   if (!rows_ok(N) || K < 1 || K > kMaxK) return 0;
-  return align_up(static_cast<size_t>(chunks_of(N)) * K * K * sizeof(double), 256);
+  return carve_product(nullptr, N, K, K, false).total;
 }
 
 extern "C" int cmh_dch_btb(const int8_t* B, int64_t N, int32_t K, double* out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -544,13 +417,7 @@ extern "C" int cmh_dch_btb(const int8_t* B, int64_t N, int32_t K, double* out, v
   CMH_CHECK_ARG(B && out && workspace, "dch_btb: null pointer");
   const size_t need = cmh_dch_btb_workspace_bytes(N, K);
   CMH_CHECK_ARG(workspace_bytes >= need, "dch_btb: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
-  const int ch = chunks_of(N), tiles = (K + kTile - 1) / kTile;
-  const size_t elems = static_cast<size_t>(K) * K;
-  double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL((xtb_partial_kernel<int8_t>), dim3(tiles, tiles, ch), dim3(256), 0, st, B, B, part, static_cast<long long>(N), K, K);
-  hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((elems + 255) / 256)), dim3(256), 0, st, static_cast<const double*>(part), out,
-                     ch, elems, 0);
+  launch_xty(B, B, N, K, K, carve_product(workspace, N, K, K, false).part, out, 0, as_stream(stream));
   CMH_CHECK_LAUNCH("dch_btb");
   return CMH_OK;
 }
@@ -594,7 +461,7 @@ extern "C" int cmh_dch_targets(const float* Y, const int8_t* B, const double* W,
   const size_t need = cmh_dch_targets_workspace_bytes(N);
   CMH_CHECK_ARG(workspace_bytes >= need, "dch_targets: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const TargetsWs w = carve_targets(static_cast<char*>(workspace), N);
+  const TargetsWs w = carve_targets(workspace, N);
   const unsigned fb = static_cast<unsigned>((N + 63) / 64), rb = static_cast<unsigned>((N + 255) / 256);
   if (Qt)
     hipLaunchKernelGGL((targets_kernel<true>), dim3(fb), dim3(256), 0, st, Y, B, W, Z_i, Z_t, mu, static_cast<long long>(N), K, C, Qt, w.fpart);
@@ -621,7 +488,7 @@ extern "C" int cmh_dch_dcc(const double* Qt, const double* G, int8_t* B, int64_t
   const size_t need = cmh_dch_dcc_workspace_bytes(N, rounds);
   CMH_CHECK_ARG(workspace_bytes >= need, "dch_dcc: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const DccWs w = carve_dcc(static_cast<char*>(workspace), N, rounds);
+  const DccWs w = carve_dcc(workspace, N, rounds);
   const unsigned blocks = static_cast<unsigned>((N + 255) / 256);
   const size_t lds = static_cast<size_t>(K) * K * sizeof(double);
 #define CMH_DCC_CASE(NW_)                                                                                                              \

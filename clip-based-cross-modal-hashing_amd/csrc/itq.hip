@@ -17,110 +17,14 @@
 //   matmul           C = op(A) diag(d) op(B) diag(cs), sizes up to 1024: the whiteners H_m = E_m diag((lambda + r)^-1/2) E_m^T,
 //                    T = H_i S_it H_t, G = T T^T, v_j = T^T u_j / sigma_j and A_m = H_m [U_K | V_K]
 //
-// Determinism: every output element is one sum in a fixed order.  The O(N) products cut the rows into chunks of kChunk (a constant,
-// not a property of the device), sum each chunk in row order and then the chunks in chunk order; block reductions are fixed trees;
-// nothing is accumulated with atomics, and no kernel waits for another workgroup.
-#include "cmh_common.h"
+// Determinism: fit_common.h states it, with the chunked products, the block reduction and the covariance element that dch.hip shares.
+#include "fit_common.h"
 
 #include <cfloat>
 #include <cmath>
 
 namespace cmh {
 namespace {
-
-constexpr int kMaxD = 1024, kMaxK = 128;
-constexpr int kChunk = 2048;                  // rows per partial sum of the O(N) products
-constexpr int kTile = 64, kStage = 16;        // X^T Y: output tile and rows per LDS stage
-
-inline int chunks_of(long long n) { return static_cast<int>((n + kChunk - 1) / kChunk); }
-
-// ---- X^T Y over row chunks ----------------------------------------------------------------------------------------------------
-// part[c][i][j] = sum over the rows n of chunk c, in row order, of X[n][i] * Y[n][j] (one fma per row).  One block: a 64 x 64 tile
-// of (i, j) for one chunk; thread (ti, tj) holds i = 4 ti + a, j = tj + 16 b.
-template <typename TX, typename TY>
-__global__ __launch_bounds__(256) void xty_partial_kernel(const TX* __restrict__ X, const TY* __restrict__ Y, double* __restrict__ part,
-                                                          long long N, int Da, int Db) {
-  __shared__ double xs[kStage][kTile];
-  __shared__ double ys[kStage][kTile];
-  const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-  const int j0 = blockIdx.x * kTile, i0 = blockIdx.y * kTile;
-  const long long n_lo = static_cast<long long>(blockIdx.z) * kChunk;
-  const long long n_hi = n_lo + kChunk < N ? n_lo + kChunk : N;
-  double acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-  for (long long n0 = n_lo; n0 < n_hi; n0 += kStage) {
-    for (int t = tid; t < kStage * kTile; t += 256) {
-      const int r = t >> 6, c = t & 63;
-      const long long n = n0 + r;
-      const bool row = n < n_hi;
-      xs[r][c] = (row && i0 + c < Da) ? static_cast<double>(X[n * Da + i0 + c]) : 0.0;
-      ys[r][c] = (row && j0 + c < Db) ? static_cast<double>(Y[n * Db + j0 + c]) : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int r = 0; r < kStage; ++r) {
-      double xv[4], yv[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) xv[a] = xs[r][ti * 4 + a];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) yv[b] = ys[r][tj + 16 * b];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = fma(xv[a], yv[b], acc[a][b]);
-    }
-    __syncthreads();
-  }
-  double* out = part + static_cast<size_t>(blockIdx.z) * Da * Db;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int i = i0 + ti * 4 + a;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int j = j0 + tj + 16 * b;
-      if (i < Da && j < Db) out[static_cast<size_t>(i) * Db + j] = acc[a][b];
-    }
-  }
-}
-
-// part[c][d] = sum over the rows of chunk c, in row order, of X[n][d]
-__global__ __launch_bounds__(64) void colsum_partial_kernel(const float* __restrict__ X, double* __restrict__ part, long long N, int D) {
-  const int d = blockIdx.x * 64 + threadIdx.x;
-  if (d >= D) return;
-  const long long n_lo = static_cast<long long>(blockIdx.y) * kChunk;
-  const long long n_hi = n_lo + kChunk < N ? n_lo + kChunk : N;
-  double acc = 0.0;
-  for (long long n = n_lo; n < n_hi; ++n) acc += static_cast<double>(X[n * D + d]);
-  part[static_cast<size_t>(blockIdx.y) * D + d] = acc;
-}
-
-// out[e] = (accumulate ? out[e] : 0) + (part[0][e] + part[1][e] + ...), the chunks in order
-__global__ __launch_bounds__(256) void chunk_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int chunks, size_t elems,
-                                                           int accumulate) {
-  const size_t e = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (e >= elems) return;
-  double acc = 0.0;
-  for (int c = 0; c < chunks; ++c) acc += part[static_cast<size_t>(c) * elems + e];
-  out[e] = accumulate ? out[e] + acc : acc;
-}
-
-// ---- block reduction: a fixed tree -------------------------------------------------------------------------------------------
-template <int T>
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = T / 2; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 
 // ---- covariance ---------------------------------------------------------------------------------------------------------------
 // block m (0 image, 1 text): mu_m = sum / N; alpha_m = 1 / sqrt(sum_d (sq[d][d] / N - mu[d]^2)), 0 where that trace is not positive
@@ -149,7 +53,8 @@ __global__ __launch_bounds__(256) void covariance_kernel(const double* __restric
   if (e >= static_cast<size_t>(D) * D) return;
   const int i = static_cast<int>(e / D), j = static_cast<int>(e % D);
   const double ai = alpha2[0] * alpha2[0], at = alpha2[1] * alpha2[1];
-  const double ci = sq_i[e] * inv_n - mu_i[i] * mu_i[j], ct = sq_t[e] * inv_n - mu_t[i] * mu_t[j];
+  // the scales come in below, where ai ci + at ct is one contraction: the elements are taken with scale 1, which is no operation
+  const double ci = cov_element(1.0, sq_i[e], inv_n, mu_i[i], mu_i[j]), ct = cov_element(1.0, sq_t[e], inv_n, mu_t[i], mu_t[j]);
   C[e] = 0.5 * (ai * ci + at * ct);
 }
 
@@ -163,9 +68,9 @@ __global__ __launch_bounds__(256) void cca_covariance_kernel(const double* __res
   if (e >= static_cast<size_t>(D) * D) return;
   const int i = static_cast<int>(e / D), j = static_cast<int>(e % D);
   const double ai = alpha2[0], at = alpha2[1];
-  S_ii[e] = (ai * ai) * (sq_i[e] * inv_n - mu_i[i] * mu_i[j]);
-  S_tt[e] = (at * at) * (sq_t[e] * inv_n - mu_t[i] * mu_t[j]);
-  S_it[e] = (ai * at) * (cross[e] * inv_n - mu_i[i] * mu_t[j]);
+  S_ii[e] = cov_element(ai * ai, sq_i[e], inv_n, mu_i[i], mu_i[j]);
+  S_tt[e] = cov_element(at * at, sq_t[e], inv_n, mu_t[i], mu_t[j]);
+  S_it[e] = cov_element(ai * at, cross[e], inv_n, mu_i[i], mu_t[j]);
 }
 
 // out[j] = 1 / sqrt(v[j] + shift), 0 where v[j] + shift is not positive; root[j] (optional) = sqrt(max(v[j] + shift, 0))
@@ -477,13 +382,8 @@ __global__ void obj_reduce_kernel(const double* __restrict__ part, int chunks, d
 // to the others, so R is orthogonal for every M (and not unique for a singular one).  G and J are kept
 // transposed (a column is contiguous) in the workspace; the block's waves share them through L2 between barriers, and a wave
 // issues the loads of all its pairs of a step before it reduces the first, so a step costs one round trip, not one per pair.
+// The butterfly is head_common.h's wave_sum (xor, 32 down to 1).
 constexpr int kPolarT = 1024, kPolarSweeps = 60, kPolarWaves = kPolarT / 64, kPolarPairs = (kMaxK / 2 + kPolarWaves - 1) / kPolarWaves;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kPolarT) void polar_kernel(const double* __restrict__ M, int K, double* Gt, double* Jt,
                                                         double* __restrict__ sig, double* __restrict__ R, int32_t* __restrict__ sweeps_out,
@@ -674,82 +574,65 @@ struct StepWs {
   double* objpart;    // [chunks][2]
   size_t total;
 };
-StepWs carve_step(char* base, long long M2, int K) {
-  const size_t ch = static_cast<size_t>(chunks_of(M2));
-  StepWs w;
-  size_t off = 0;
-  w.part = reinterpret_cast<double*>(base + off);
-  off += align_up(ch * K * K * sizeof(double), 256);
-  w.objpart = reinterpret_cast<double*>(base + off);
-  off += align_up(ch * 2 * sizeof(double), 256);
-  w.total = off;
-  return w;
+StepWs carve_step(void* ws, long long M2, int K) {
+  Carver c(ws);
+  return {c.take<double>(xty_part_bytes(M2, K, K)), c.take<double>(static_cast<size_t>(chunks_of(M2)) * 2 * sizeof(double)), c.total()};
 }
 
 struct PolarWs {
-  double *Gt, *Jt, *sig;
+  double *Gt, *Jt, *sig;      // [K][K], [K][K], [K]
   size_t total;
 };
-PolarWs carve_polar(char* base, int K) {
-  PolarWs w;
-  const size_t kk = align_up(static_cast<size_t>(K) * K * sizeof(double), 256);
-  w.Gt = reinterpret_cast<double*>(base);
-  w.Jt = reinterpret_cast<double*>(base + kk);
-  w.sig = reinterpret_cast<double*>(base + 2 * kk);
-  w.total = 2 * kk + align_up(static_cast<size_t>(K) * sizeof(double), 256);
-  return w;
+PolarWs carve_polar(void* ws, int K) {
+  Carver c(ws);
+  const size_t kk = static_cast<size_t>(K) * K * sizeof(double);
+  return {c.take<double>(kk), c.take<double>(kk), c.take<double>(static_cast<size_t>(K) * sizeof(double)), c.total()};
 }
 
 struct RotateWs {
   double* Z;          // [M2][K]
   int8_t* B;          // [M2][K]
   double* Mm;         // [K][K]
-  char* step;
-  char* polar;
+  char* step;         // carve_step's
+  char* polar;        // carve_polar's
   size_t total;
 };
-RotateWs carve_rotate(char* base, long long M2, int K) {
-  RotateWs w;
-  size_t off = 0;
-  w.Z = reinterpret_cast<double*>(base + off);
-  off += align_up(static_cast<size_t>(M2) * K * sizeof(double), 256);
-  w.B = reinterpret_cast<int8_t*>(base + off);
-  off += align_up(static_cast<size_t>(M2) * K, 256);
-  w.Mm = reinterpret_cast<double*>(base + off);
-  off += align_up(static_cast<size_t>(K) * K * sizeof(double), 256);
-  w.step = base + off;
-  off += carve_step(nullptr, M2, K).total;
-  w.polar = base + off;
-  off += carve_polar(nullptr, K).total;
-  w.total = off;
-  return w;
+RotateWs carve_rotate(void* ws, long long M2, int K) {
+  Carver c(ws);
+  const size_t rows = static_cast<size_t>(M2) * K;
+  return {c.take<double>(rows * sizeof(double)), c.take<int8_t>(rows),   c.take<double>(static_cast<size_t>(K) * K * sizeof(double)),
+          c.take<char>(carve_step(nullptr, M2, K).total), c.take<char>(carve_polar(nullptr, K).total), c.total()};
+}
+
+struct EighWs {
+  double *A0, *A1, *E;      // [D][D] each: the matrix before and after a step, the vectors
+  int32_t* cnt;             // [max_sweeps]
+  size_t total;
+};
+EighWs carve_eigh(void* ws, int D, int max_sweeps) {
+  Carver c(ws);
+  const size_t mat = static_cast<size_t>(D) * D * sizeof(double);
+  return {c.take<double>(mat), c.take<double>(mat), c.take<double>(mat), c.take<int32_t>(static_cast<size_t>(max_sweeps) * sizeof(int32_t)), c.total()};
 }
 
 // Z = V R, B, M = B^T V, *obj = |B - Z|^2, *zz = |Z|^2 (M, obj, zz optional)
 void run_step(const double* V, long long M2, int K, const double* R, double* Z, int8_t* B, double* Mout, double* obj, double* zz,
-              char* ws, hipStream_t st) {
+              void* ws, hipStream_t st) {
   const StepWs w = carve_step(ws, M2, K);
   const int ch = chunks_of(M2);
   hipLaunchKernelGGL((rows_times_kernel<double>), dim3(static_cast<unsigned>((M2 + 31) / 32), (K + 63) / 64), dim3(256), 0, st, V,
                      static_cast<const double*>(nullptr), static_cast<const double*>(nullptr), R, Z, M2, K, K);
   hipLaunchKernelGGL(sign_obj_kernel, dim3(ch), dim3(256), 0, st, static_cast<const double*>(Z), B, w.objpart, M2, K);
   hipLaunchKernelGGL(obj_reduce_kernel, dim3(1), dim3(64), 0, st, static_cast<const double*>(w.objpart), ch, obj, zz);
-  if (Mout) {
-    hipLaunchKernelGGL((xty_partial_kernel<int8_t, double>), dim3((K + kTile - 1) / kTile, (K + kTile - 1) / kTile, ch), dim3(256), 0, st,
-                       static_cast<const int8_t*>(B), V, w.part, M2, K, K);
-    const size_t elems = static_cast<size_t>(K) * K;
-    hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((elems + 255) / 256)), dim3(256), 0, st,
-                       static_cast<const double*>(w.part), Mout, ch, elems, 0);
-  }
+  if (Mout) launch_xty(static_cast<const int8_t*>(B), V, M2, K, K, w.part, Mout, 0, st);
 }
 
-void run_polar(const double* M, int K, double* R, int32_t* sweeps, char* ws, hipStream_t st) {
+void run_polar(const double* M, int K, double* R, int32_t* sweeps, void* ws, hipStream_t st) {
   const PolarWs w = carve_polar(ws, K);
   hipLaunchKernelGGL(polar_kernel, dim3(1), dim3(kPolarT), 0, st, M, K, w.Gt, w.Jt, w.sig, R, sweeps, sqrt(static_cast<double>(K)) * DBL_EPSILON);
 }
 
 bool dims_ok(long long D, long long K) { return D >= 1 && D <= kMaxD && K >= 1 && K <= kMaxK && K <= D; }
-constexpr long long kMaxRows = 65535ll * kChunk;      // the chunk index is a grid dimension (y or z: at most 65535)
 
 }  // namespace
 }  // namespace cmh
@@ -757,28 +640,21 @@ constexpr long long kMaxRows = 65535ll * kChunk;      // the chunk index is a gr
 using namespace cmh;
 
 extern "C" size_t cmh_itq_moments_workspace_bytes(int64_t N, int32_t D) {
-  if (N < 1 || N > kMaxRows || D < 1 || D > kMaxD) return 0;
-  return align_up(static_cast<size_t>(chunks_of(N)) * D * (static_cast<size_t>(D) + 1) * sizeof(double), 256);
+  if (!rows_ok(N) || D < 1 || D > kMaxD) return 0;
+  return carve_product(nullptr, N, D, D, true).total;
 }
 
 extern "C" int cmh_itq_moments(const float* F, int64_t N, int32_t D, double* sum, double* sq, int32_t accumulate, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(N >= 1 && N <= kMaxRows, "itq_moments: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
+  CMH_CHECK_ARG(rows_ok(N), "itq_moments: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
   CMH_CHECK_ARG(D >= 1 && D <= kMaxD, "itq_moments: D = %d, need 1 <= D <= %d", D, kMaxD);
   CMH_CHECK_ARG(F && sum && sq && workspace, "itq_moments: null pointer");
   const size_t need = cmh_itq_moments_workspace_bytes(N, D);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_moments: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const int ch = chunks_of(N), tiles = (D + kTile - 1) / kTile;
-  double* part_sq = static_cast<double*>(workspace);
-  double* part_sum = part_sq + static_cast<size_t>(ch) * D * D;
-  hipLaunchKernelGGL((xty_partial_kernel<float, float>), dim3(tiles, tiles, ch), dim3(256), 0, st, F, F, part_sq, static_cast<long long>(N), D, D);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3((D + 63) / 64, ch), dim3(64), 0, st, F, part_sum, static_cast<long long>(N), D);
-  const size_t e2 = static_cast<size_t>(D) * D;
-  hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((e2 + 255) / 256)), dim3(256), 0, st, static_cast<const double*>(part_sq), sq,
-                     ch, e2, accumulate ? 1 : 0);
-  hipLaunchKernelGGL(chunk_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, st, static_cast<const double*>(part_sum), sum, ch,
-                     static_cast<size_t>(D), accumulate ? 1 : 0);
+  const ProductWs w = carve_product(workspace, N, D, D, true);
+  launch_xty(F, F, N, D, D, w.part, sq, accumulate, st);
+  launch_colsum(F, N, D, w.part_sum, sum, accumulate, st);
   CMH_CHECK_LAUNCH("itq_moments");
   return CMH_OK;
 }
@@ -800,7 +676,7 @@ extern "C" int cmh_itq_covariance(const double* sum_i, const double* sq_i, const
 
 extern "C" size_t cmh_itq_eigh_workspace_bytes(int32_t D, int32_t max_sweeps) {
   if (D < 1 || D > kMaxD || max_sweeps < 1 || max_sweeps > 1024) return 0;
-  return 3 * align_up(static_cast<size_t>(D) * D * sizeof(double), 256) + align_up(static_cast<size_t>(max_sweeps) * sizeof(int32_t), 256);
+  return carve_eigh(nullptr, D, max_sweeps).total;
 }
 
 extern "C" int cmh_itq_eigh(const double* C, int32_t D, int32_t max_sweeps, double* evals, double* evecs, int32_t* info2, void* workspace,
@@ -811,12 +687,11 @@ extern "C" int cmh_itq_eigh(const double* C, int32_t D, int32_t max_sweeps, doub
   const size_t need = cmh_itq_eigh_workspace_bytes(D, max_sweeps);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_eigh: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const size_t mat = align_up(static_cast<size_t>(D) * D * sizeof(double), 256), e2 = static_cast<size_t>(D) * D;
-  char* base = static_cast<char*>(workspace);
-  double* A[2] = {reinterpret_cast<double*>(base), reinterpret_cast<double*>(base + mat)};
-  double* E = reinterpret_cast<double*>(base + 2 * mat);
-  int32_t* cnt = reinterpret_cast<int32_t*>(base + 3 * mat);
-  const size_t init = e2 > static_cast<size_t>(max_sweeps) ? e2 : static_cast<size_t>(max_sweeps);
+  const EighWs w = carve_eigh(workspace, D, max_sweeps);
+  double* A[2] = {w.A0, w.A1};
+  double* E = w.E;
+  int32_t* cnt = w.cnt;
+  const size_t e2 = static_cast<size_t>(D) * D, init = e2 > static_cast<size_t>(max_sweeps) ? e2 : static_cast<size_t>(max_sweeps);
   hipLaunchKernelGGL(jacobi_init_kernel, dim3(static_cast<unsigned>((init + 255) / 256)), dim3(256), 0, st, C, A[0], E, cnt, D, max_sweeps);
   const int n = (D + 1) & ~1, half = n / 2;
   int cur = 0, sweeps = 0, converged = 0;
@@ -851,7 +726,7 @@ extern "C" int cmh_itq_eigh(const double* C, int32_t D, int32_t max_sweeps, doub
 
 extern "C" int cmh_itq_project(const float* F, int64_t N, int32_t D, int32_t K, const double* mu, const double* alpha, const double* P,
                                double* V, void* stream) {
-  CMH_CHECK_ARG(N >= 1 && N <= kMaxRows, "itq_project: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
+  CMH_CHECK_ARG(rows_ok(N), "itq_project: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
   CMH_CHECK_ARG(dims_ok(D, K), "itq_project: D = %d, K = %d, need 1 <= D <= %d and 1 <= K <= min(D, %d)", D, K, kMaxD, kMaxK);
   CMH_CHECK_ARG(F && mu && alpha && P && V, "itq_project: null pointer");
   hipLaunchKernelGGL((rows_times_kernel<float>), dim3(static_cast<unsigned>((N + 31) / 32), (K + 63) / 64), dim3(256), 0, as_stream(stream), F, mu,
@@ -861,18 +736,18 @@ extern "C" int cmh_itq_project(const float* F, int64_t N, int32_t D, int32_t K, 
 }
 
 extern "C" size_t cmh_itq_step_workspace_bytes(int64_t M2, int32_t K) {
-  if (M2 < 1 || M2 > kMaxRows || K < 1 || K > kMaxK) return 0;
+  if (!rows_ok(M2) || K < 1 || K > kMaxK) return 0;
   return carve_step(nullptr, M2, K).total;
 }
 
 extern "C" int cmh_itq_step(const double* V, int64_t M2, int32_t K, const double* R, double* Z, int8_t* B, double* M, double* obj2,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(M2 >= 1 && M2 <= kMaxRows, "itq_step: rows = %lld, need 1 <= rows <= %lld", static_cast<long long>(M2), kMaxRows);
+  CMH_CHECK_ARG(rows_ok(M2), "itq_step: rows = %lld, need 1 <= rows <= %lld", static_cast<long long>(M2), kMaxRows);
   CMH_CHECK_ARG(K >= 1 && K <= kMaxK, "itq_step: K = %d, need 1 <= K <= %d", K, kMaxK);
   CMH_CHECK_ARG(V && R && Z && B && M && obj2 && workspace, "itq_step: null pointer");
   const size_t need = cmh_itq_step_workspace_bytes(M2, K);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_step: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  run_step(V, M2, K, R, Z, B, M, obj2, obj2 + 1, static_cast<char*>(workspace), as_stream(stream));
+  run_step(V, M2, K, R, Z, B, M, obj2, obj2 + 1, workspace, as_stream(stream));
   CMH_CHECK_LAUNCH("itq_step");
   return CMH_OK;
 }
@@ -887,26 +762,26 @@ extern "C" int cmh_itq_polar(const double* M, int32_t K, double* R, int32_t* swe
   CMH_CHECK_ARG(M && R && workspace, "itq_polar: null pointer");
   const size_t need = cmh_itq_polar_workspace_bytes(K);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_polar: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  run_polar(M, K, R, sweeps, static_cast<char*>(workspace), as_stream(stream));
+  run_polar(M, K, R, sweeps, workspace, as_stream(stream));
   CMH_CHECK_LAUNCH("itq_polar");
   return CMH_OK;
 }
 
 extern "C" size_t cmh_itq_rotate_workspace_bytes(int64_t M2, int32_t K) {
-  if (M2 < 1 || M2 > kMaxRows || K < 1 || K > kMaxK) return 0;
+  if (!rows_ok(M2) || K < 1 || K > kMaxK) return 0;
   return carve_rotate(nullptr, M2, K).total;
 }
 
 extern "C" int cmh_itq_rotate(const double* V, int64_t M2, int32_t K, const double* R0, int32_t iters, double* R, double* obj, double* zz,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(M2 >= 1 && M2 <= kMaxRows, "itq_rotate: rows = %lld, need 1 <= rows <= %lld", static_cast<long long>(M2), kMaxRows);
+  CMH_CHECK_ARG(rows_ok(M2), "itq_rotate: rows = %lld, need 1 <= rows <= %lld", static_cast<long long>(M2), kMaxRows);
   CMH_CHECK_ARG(K >= 1 && K <= kMaxK, "itq_rotate: K = %d, need 1 <= K <= %d", K, kMaxK);
   CMH_CHECK_ARG(iters >= 0 && iters <= 100000, "itq_rotate: iters = %d, need 0 <= iters <= 100000", iters);
   CMH_CHECK_ARG(V && R0 && R && obj && zz && workspace, "itq_rotate: null pointer");
   const size_t need = cmh_itq_rotate_workspace_bytes(M2, K);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_rotate: workspace of %zu bytes, need %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
-  const RotateWs w = carve_rotate(static_cast<char*>(workspace), M2, K);
+  const RotateWs w = carve_rotate(workspace, M2, K);
   if (R != R0) {
     const hipError_t e = hipMemcpyAsync(R, R0, static_cast<size_t>(K) * K * sizeof(double), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return fail(CMH_ERR_LAUNCH, "itq_rotate: %s", hipGetErrorString(e));
@@ -939,24 +814,18 @@ extern "C" int cmh_itq_heads(const double* P, const double* R, const double* mu_
 
 // ---- CCA projections ----------------------------------------------------------------------------------------------------------
 extern "C" size_t cmh_itq_cross_moments_workspace_bytes(int64_t N, int32_t D) {
-  if (N < 1 || N > kMaxRows || D < 1 || D > kMaxD) return 0;
-  return align_up(static_cast<size_t>(chunks_of(N)) * D * static_cast<size_t>(D) * sizeof(double), 256);
+  if (!rows_ok(N) || D < 1 || D > kMaxD) return 0;
+  return carve_product(nullptr, N, D, D, false).total;
 }
 
 extern "C" int cmh_itq_cross_moments(const float* F_i, const float* F_t, int64_t N, int32_t D, double* cross, int32_t accumulate,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  CMH_CHECK_ARG(N >= 1 && N <= kMaxRows, "itq_cross_moments: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
+  CMH_CHECK_ARG(rows_ok(N), "itq_cross_moments: N = %lld, need 1 <= N <= %lld", static_cast<long long>(N), kMaxRows);
   CMH_CHECK_ARG(D >= 1 && D <= kMaxD, "itq_cross_moments: D = %d, need 1 <= D <= %d", D, kMaxD);
   CMH_CHECK_ARG(F_i && F_t && cross && workspace, "itq_cross_moments: null pointer");
   const size_t need = cmh_itq_cross_moments_workspace_bytes(N, D);
   CMH_CHECK_ARG(workspace_bytes >= need, "itq_cross_moments: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
-  const int ch = chunks_of(N), tiles = (D + kTile - 1) / kTile;
-  double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL((xty_partial_kernel<float, float>), dim3(tiles, tiles, ch), dim3(256), 0, st, F_i, F_t, part, static_cast<long long>(N), D, D);
-  const size_t e2 = static_cast<size_t>(D) * D;
-  hipLaunchKernelGGL(chunk_reduce_kernel, dim3(static_cast<unsigned>((e2 + 255) / 256)), dim3(256), 0, st, static_cast<const double*>(part), cross,
-                     ch, e2, accumulate ? 1 : 0);
+  launch_xty(F_i, F_t, N, D, D, carve_product(workspace, N, D, D, false).part, cross, accumulate, as_stream(stream));
   CMH_CHECK_LAUNCH("itq_cross_moments");
   return CMH_OK;
 }

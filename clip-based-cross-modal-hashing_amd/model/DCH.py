@@ -1,18 +1,8 @@
-"""Model of the supervised training-free method (DCH; no upstream counterpart): Baseclip with LinearHash heads, the keys of MDSPH
-(`clip.*`, `image_hash.fc.{weight,bias}`, `text_hash.fc.{weight,bias}`), so its checkpoints also load as DSPH and as ITQ.  The heads
-are written by the fit (utils/dch.py), never trained."""
-import logging
-
-from model.modelbase import Baseclip
-from streams import overlapped
+"""Model of the supervised training-free method (DCH; no upstream counterpart): MITQ under the method's own name - Baseclip with
+LinearHash heads and DSPH's keys, so its checkpoints also load as DSPH and as ITQ.  The heads are written by the fit (utils/dch.py),
+never trained."""
+from model.ITQ import MITQ
 
 
-class MDCH(Baseclip):
-
-    def __init__(self, outputDim=64, clipPath="./ViT-B-32.pt", writer=None, saveDir="./result/log",
-                 logger: logging.Logger = None, is_train=True):
-        super(MDCH, self).__init__(outputDim=outputDim, clipPath=clipPath, writer=writer,
-                                   saveDir=saveDir, logger=logger, is_train=is_train)
-
-    def forward(self, image, text):
-        return overlapped(lambda: self.encode_image(image), lambda: self.encode_text(text))
+class MDCH(MITQ):
+    pass

@@ -1,18 +1,11 @@
-"""Model of the training-free methods (LSH, PCAH, ITQ; no upstream counterpart): Baseclip with LinearHash heads, the keys of MDSPH
-(`clip.*`, `image_hash.fc.{weight,bias}`, `text_hash.fc.{weight,bias}`), so its checkpoints also load as DSPH.  The heads are
-written by the fit (utils/itq.py), never trained."""
-import logging
-
+"""Model of the training-free methods (LSH, PCAH, ITQ, and through model/DCH.py the supervised DCH; no upstream counterpart): Baseclip
+with LinearHash heads, the keys of MDSPH (`clip.*`, `image_hash.fc.{weight,bias}`, `text_hash.fc.{weight,bias}`), so its checkpoints
+also load as DSPH.  The heads are written by the fit (utils/itq.py), never trained."""
 from model.modelbase import Baseclip
 from streams import overlapped
 
 
 class MITQ(Baseclip):
-
-    def __init__(self, outputDim=64, clipPath="./ViT-B-32.pt", writer=None, saveDir="./result/log",
-                 logger: logging.Logger = None, is_train=True):
-        super(MITQ, self).__init__(outputDim=outputDim, clipPath=clipPath, writer=writer,
-                                   saveDir=saveDir, logger=logger, is_train=is_train)
 
     def forward(self, image, text):
         return overlapped(lambda: self.encode_image(image), lambda: self.encode_text(text))

@@ -23,7 +23,7 @@ are the eigen-solver's word per sweep."""
 import torch
 
 import cmh_native as N
-from .itq import MomentStream
+from .itq import MomentStream, check_dims, whitener
 
 # Choices made on the synthetic fixture of tests/dchutil.py, not optima measured on a real dataset.
 DCH_ITERS = 10            # outer iterations: on the fixtures the flips per iteration fall by 10x to 100x within five
@@ -48,8 +48,7 @@ def _check(Fi, Ft, Y, bits, iters, rounds, lam, mu, reg):
     n, dim = Fi.shape
     if Y.dim() != 2 or Y.shape[0] != n:
         raise ValueError(f"fit_supervised_heads: labels {tuple(Y.shape)} for {n} pairs, expected [{n}, C]")
-    if not (1 <= dim <= N.ITQ_MAX_D and 1 <= bits <= min(dim, N.ITQ_MAX_K)):
-        raise ValueError(f"fit_supervised_heads: D = {dim}, bits = {bits}: need 1 <= D <= {N.ITQ_MAX_D} and 1 <= bits <= min(D, {N.ITQ_MAX_K})")
+    check_dims("fit_supervised_heads", dim, bits)
     if not 1 <= Y.shape[1] <= N.DCH_MAX_C:
         raise ValueError(f"fit_supervised_heads: C = {Y.shape[1]} classes: need 1 <= C <= {N.DCH_MAX_C}")
     if n < 1 or iters < 0 or not 1 <= rounds <= N.DCH_MAX_ROUNDS:
@@ -70,8 +69,7 @@ def fit_from_moments(Fi, Ft, Y, moments, bits, iters=DCH_ITERS, rounds=DCH_ROUND
     # 2. the feature regressions' inverse, once
     A, sweeps, converged = [], [], []
     for S in (S_ii, S_tt):
-        lam_s, E, sw, ok = N.itq_eigh(S)
-        H = N.itq_matmul(E, E, d=N.itq_inv_sqrt(lam_s, reg / dim), trans_b=True)
+        H, sw, ok = whitener(S, reg / dim)
         A.append(N.itq_matmul(H, H, trans_b=True))
         sweeps.append(sw)
         converged.append(ok)

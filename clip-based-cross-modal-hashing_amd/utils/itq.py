@@ -62,22 +62,36 @@ def random_projection(dim, bits, seed, device):
     return torch.randn(dim, bits, generator=g, dtype=torch.float64).to(device)
 
 
+def whitener(S, ridge):
+    """H = E diag((lambda + ridge)^-1/2) E^T of a symmetric S [D, D] f64 on the GPU (H H^T = (S + ridge I)^-1) -> H, the
+    eigen-solve's sweeps, converged."""
+    lam, E, sweeps, converged = N.itq_eigh(S)
+    return N.itq_matmul(E, E, d=N.itq_inv_sqrt(lam, ridge), trans_b=True), sweeps, converged
+
+
+def check_dims(what, dim, bits):
+    """The D / bits bounds of every fit (the library's own, refused here before any launch)."""
+    if not (1 <= dim <= N.ITQ_MAX_D and 1 <= bits <= min(dim, N.ITQ_MAX_K)):
+        raise ValueError(f"{what}: D = {dim}, bits = {bits}: need 1 <= D <= {N.ITQ_MAX_D} and 1 <= bits <= min(D, {N.ITQ_MAX_K})")
+
+
+def _check_names(projection, rotation, reg):
+    if projection not in PROJECTIONS or rotation not in ROTATIONS:
+        raise ValueError(f"projection {projection!r} / rotation {rotation!r}: one of {PROJECTIONS} and one of {ROTATIONS}")
+    if projection == "cca" and not float(reg) > 0.0:
+        raise ValueError(f"fit_hash_heads: reg = {reg!r}: the cca ridge must be positive")
+
+
 def cca_directions(S_ii, S_tt, S_it, bits, reg=CCA_REG):
     """The CCA projections from the normalised covariances [D, D] f64 on the GPU -> dict with P_i, P_t [D, bits], correlations [D]
     (descending), the whiteners H_i, H_t, T = H_i S_it H_t, U (all D left vectors), and the sweeps / convergence of the three
     eigen-solves (S_ii, S_tt, T T^T).  ValueError where sigma_bits <= 1e-6 sigma_1."""
     dim = S_ii.shape[0]
     r = float(reg) / dim
-    H, sweeps, converged = [], [], []
-    for S in (S_ii, S_tt):
-        lam, E, sw, ok = N.itq_eigh(S)
-        H.append(N.itq_matmul(E, E, d=N.itq_inv_sqrt(lam, r), trans_b=True))
-        sweeps.append(sw)
-        converged.append(ok)
-    T = N.itq_matmul(H[0], N.itq_matmul(S_it, H[1]))
+    (H_i, sw_i, ok_i), (H_t, sw_t, ok_t) = whitener(S_ii, r), whitener(S_tt, r)
+    T = N.itq_matmul(H_i, N.itq_matmul(S_it, H_t))
     g_evals, U, sw, ok = N.itq_eigh(N.itq_matmul(T, T, trans_b=True))
-    sweeps.append(sw)
-    converged.append(ok)
+    sweeps, converged = (sw_i, sw_t, sw), (ok_i, ok_t, ok)
     inv_sigma, sigma = N.itq_inv_sqrt(g_evals, 0.0, want_root=True)
     first, last = (float(v) for v in sigma[[0, bits - 1]].cpu())             # the fit's one read before the heads
     if not last > CCA_FLOOR * first:
@@ -85,21 +99,17 @@ def cca_directions(S_ii, S_tt, S_it, bits, reg=CCA_REG):
         raise ValueError(f"cca: {above} canonical directions stand above {CCA_FLOOR:g} of the largest correlation, {bits} bits were asked")
     U_K = U[:, :bits].contiguous()
     V_K = N.itq_matmul(T, U_K, col_scale=inv_sigma[:bits].contiguous(), trans_a=True)
-    return {"P_i": N.itq_matmul(H[0], U_K), "P_t": N.itq_matmul(H[1], V_K), "correlations": sigma, "H_i": H[0], "H_t": H[1], "T": T,
-            "U": U, "eigh_sweeps": tuple(sweeps), "eigh_converged": all(converged), "eigh_converged_each": tuple(converged)}
+    return {"P_i": N.itq_matmul(H_i, U_K), "P_t": N.itq_matmul(H_t, V_K), "correlations": sigma, "H_i": H_i, "H_t": H_t, "T": T,
+            "U": U, "eigh_sweeps": sweeps, "eigh_converged": all(converged), "eigh_converged_each": converged}
 
 
 def fit_from_moments(Fi, Ft, moments, bits, projection="pca", rotation="itq", iters=50, R0=None, seed=0, reg=CCA_REG):
     """The fit behind fit_hash_heads, from features and their finished moments: (mu_i, mu_t, alpha, C), or for `cca`
     (mu_i, mu_t, alpha, S_ii, S_tt, S_it) from MomentStream(cross=True).finish_cca()."""
-    if projection not in PROJECTIONS or rotation not in ROTATIONS:
-        raise ValueError(f"projection {projection!r} / rotation {rotation!r}: one of {PROJECTIONS} and one of {ROTATIONS}")
-    if projection == "cca" and not float(reg) > 0.0:
-        raise ValueError(f"fit_hash_heads: reg = {reg!r}: the cca ridge must be positive")
+    _check_names(projection, rotation, reg)
     n, dim = Fi.shape
     bits = int(bits)
-    if not (1 <= dim <= N.ITQ_MAX_D and 1 <= bits <= min(dim, N.ITQ_MAX_K)):
-        raise ValueError(f"fit_hash_heads: D = {dim}, bits = {bits}: need 1 <= D <= {N.ITQ_MAX_D} and 1 <= bits <= min(D, {N.ITQ_MAX_K})")
+    check_dims("fit_hash_heads", dim, bits)
     dev = Fi.device
     if projection == "cca":
         if len(moments) != 6:
@@ -138,10 +148,7 @@ def fit_hash_heads(Fi, Ft, bits, projection="pca", rotation="itq", iters=50, R0=
     one entry without ITQ), and with `pca` evals [D], eigh_sweeps, eigh_converged.  With `cca` the record has P_i, P_t in the place
     of P, correlations [D], reg, and eigh_sweeps / eigh_converged_each as triples (S_ii, S_tt, T T^T; eigh_converged: all three).
     All tensors stay on the device."""
-    if projection not in PROJECTIONS or rotation not in ROTATIONS:
-        raise ValueError(f"projection {projection!r} / rotation {rotation!r}: one of {PROJECTIONS} and one of {ROTATIONS}")
-    if projection == "cca" and not float(reg) > 0.0:
-        raise ValueError(f"fit_hash_heads: reg = {reg!r}: the cca ridge must be positive")
+    _check_names(projection, rotation, reg)         # before the moments are taken
     stream = MomentStream(cross=projection == "cca").add(Fi, Ft)
     moments = stream.finish_cca() if projection == "cca" else stream.finish()
     return fit_from_moments(Fi, Ft, moments, bits, projection, rotation, iters, R0, seed, reg)

@@ -128,6 +128,29 @@ def test_xtb_streamed_in_unequal_batches_matches_the_whole():
     assert np.array_equal(_np(into[1]), b.sum(0))
 
 
+@pytest.mark.parametrize("d", [1, 33, 65])                                  # one column, inside a tile, past a tile of 64
+@pytest.mark.parametrize("n", [1, 2047, 2049, 4100])                       # around the chunk of 2048 rows, and three chunks
+def test_the_products_are_the_unsupervised_fits_bit_for_bit(n, d):
+    """X^T B, B^T B and 1^T B are one chunked product and one column sum (csrc/fit_common.h) with itq_moments / itq_cross_moments:
+    the casts of +-1 from int8 and from f32 to f64 are both exact, and each output element is one fma chain in row order, then the
+    chunks in chunk order, so the two families agree to the bit - as long as the product is written once.  K = D."""
+    import cmh_native as N
+    rng = np.random.default_rng(1000 * d + n)
+    x = (rng.standard_normal((n, d)) + 8.0 * rng.standard_normal(d)).astype(np.float32)
+    X, B = _dev(x), _codes(U.random_codes(n, d, 200 + n + d))
+    Bf = B.float()
+    out, bsum = N.dch_xtb(X, B, want_bsum=True)
+    cross, sums, btb = N.itq_cross_moments(X, Bf), N.itq_moments(Bf), N.dch_btb(B)
+    assert torch.equal(out, cross)
+    assert torch.equal(btb, sums[1])
+    assert torch.equal(bsum, sums[0])
+    N.dch_xtb(X, B, want_bsum=True, into=(out, bsum))                       # one accumulate step on either side
+    assert N.itq_cross_moments(X, Bf, cross=cross) is cross and N.itq_moments(Bf, sums=sums) is sums
+    assert torch.equal(out, cross)
+    assert torch.equal(bsum, sums[0])
+    assert torch.equal(btb + btb, sums[1])                                  # dch_btb does not accumulate; integers, so the sum is exact
+
+
 # ---------------------------------------------------------------------------------------------------- the label regression's solve
 SOLVE_C = [1, 7, 130]
 SOLVE_CASES = [("random", k) for k in (1, 2, 33, 64, 128)] + [("equal_columns", k) for k in (2, 33, 64, 128)]

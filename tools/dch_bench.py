@@ -95,7 +95,7 @@ def shape_line(n, d, k, c, iters, dev):
     import dchutil as U
     import itqutil as IU
     from utils.dch import fit_supervised_heads, supervised_moments
-    from utils.itq import MomentStream
+    from utils.itq import MomentStream, whitener
     fi, ft, y = U.make_labelled(n, d, c, 1)
     gi, gt, gy = torch.from_numpy(fi).to(dev), torch.from_numpy(ft).to(dev), torch.from_numpy(y).float().to(dev)
     r = REG / d
@@ -106,8 +106,7 @@ def shape_line(n, d, k, c, iters, dev):
     def inverses():
         out = []
         for S in (S_ii, S_tt):
-            lam, E, sw, ok = N.itq_eigh(S)
-            H = N.itq_matmul(E, E, d=N.itq_inv_sqrt(lam, r), trans_b=True)
+            H, sw, ok = whitener(S, r)
             out.append((N.itq_matmul(H, H, trans_b=True), sw, ok))
         return out
     inv = inverses()
