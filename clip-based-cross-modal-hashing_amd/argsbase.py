@@ -48,6 +48,8 @@ def add_flags(parser, table):
             kw["choices"] = ["pca", "random", "cca"]
         if flag == "--rotation":
             kw["choices"] = ["itq", "none"]
+        if flag == "--msc-mining":
+            kw["choices"] = ["all", "semi-hard"]
         if flag == "--init-heads":
             kw["choices"] = ["random", "itq", "cca"]
         parser.add_argument(flag, **kw)

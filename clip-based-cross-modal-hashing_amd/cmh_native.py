@@ -131,6 +131,9 @@ SIGNATURES = {
     # label-free joint-semantics loss (csrc/djsrh.hip): none of the cmh_djsrh_* entries has an upstream counterpart
     "cmh_djsrh_workspace_bytes": (_sz, [_i32, _i32, _i32]),             # no upstream counterpart
     "cmh_djsrh_target": (C.c_int, [_p, _p, _i32, _i32, _f, _f, _f, _p, _p, _sz, _p]),      # no upstream counterpart
+    "cmh_msc_triplet_workspace_bytes": (_sz, [_i32]),
+    "cmh_msc_triplet_loss": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _f, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_msc_triplet_loss_backward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "cmh_djsrh_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
     "cmh_djsrh_loss_backward": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
     "cmh_fp8_quantize_weight": (C.c_int, [_p, _p, _p, _i32, _i32, _p]),
@@ -1673,7 +1676,48 @@ def ddbh_quant_loss_backward(hs, colsum, dloss):
     return dh
 
 
-DJSRH_MAX_B, DJSRH_MAX_K, DJSRH_MAX_D = 1024, 128, 4096      # csrc/djsrh.hip's limits, for the wrappers' messages
+MSC_MAX_B, MSC_MAX_K = 1024, 128                            # csrc/msc.hip's limits, for the wrapper's message
+MSC_MINING = {"all": 0, "semi-hard": 1}                      # the two rules of the reference (train/DPSIH/Loss.py:118-120)
+
+
+def msc_triplet_loss(pairs, label, margin, mining="all", normalize=False):
+    """Multi_Semantic_Correlation_Loss.forward (train/DPSIH/Loss.py:85-137) for up to four (u, v) pairs over one label matrix in one
+    call -> (loss f32 [n], count i64 [n], sim f32 [n, B, B], saved = what msc_triplet_loss_backward takes)"""
+    if mining not in MSC_MINING:
+        raise NativeError(f"msc_triplet_loss: mining {mining!r}: one of {sorted(MSC_MINING)}")
+    pairs, label, B, K, Cn = _ddbh_operands("msc_triplet_loss", pairs, label)
+    if not (1 <= B <= MSC_MAX_B and 1 <= K <= MSC_MAX_K):
+        raise NativeError(f"msc_triplet_loss: B={B} K={K}: 1 <= B <= {MSC_MAX_B} and 1 <= K <= {MSC_MAX_K} are built")
+    n, dev = len(pairs), label.device
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    sim = torch.empty(n, B, B, dtype=torch.float32, device=dev)
+    coef = torch.empty(n, B, B, dtype=torch.int32, device=dev)
+    unit = torch.empty(2 * n, B, K, dtype=torch.float32, device=dev) if normalize else None
+    divisor = torch.empty(2 * n, B, dtype=torch.float32, device=dev) if normalize else None
+    ws = workspace(lib().cmh_msc_triplet_workspace_bytes(B), dev, "loss")
+    check(lib().cmh_msc_triplet_loss(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, ptr(label), B, K, Cn,
+                                     float(margin), MSC_MINING[mining], int(bool(normalize)), ptr(loss), ptr(count), ptr(sim), ptr(coef),
+                                     ptr(unit), ptr(divisor), ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_msc_triplet_loss")
+    return loss, count, sim, (pairs, coef, count, unit, divisor)
+
+
+def msc_triplet_loss_backward(saved, dloss):
+    """-> [(du, dv)] per pair, each f32 [B, K]; an intra-modal pair (v is u) gets its whole gradient in du and dv = None"""
+    pairs, coef, count, unit, divisor = saved
+    B, K = pairs[0][0].shape
+    n = len(pairs)
+    du = [torch.empty_like(u) for u, _ in pairs]
+    dv = [None if v.data_ptr() == u.data_ptr() else torch.empty_like(v) for u, v in pairs]     # as the library tells them apart
+    dloss = f32c(dloss).reshape(n)
+    dv_ptrs = (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in dv])
+    check(lib().cmh_msc_triplet_loss_backward(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, B, K,
+                                              int(unit is not None), ptr(coef), ptr(count), ptr(unit), ptr(divisor), ptr(dloss),
+                                              _ptr_array(du), dv_ptrs, stream_ptr(coef.device)), "cmh_msc_triplet_loss_backward")
+    return list(zip(du, dv))
+
+
+DJSRH_MAX_B, DJSRH_MAX_K, DJSRH_MAX_D = 1024, 128, 4096     # csrc/djsrh.hip's limits, for the wrappers' messages
 
 
 def _djsrh_pair(what, a, b):

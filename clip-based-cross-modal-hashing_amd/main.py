@@ -19,6 +19,7 @@ _REGISTRY = {
     'ITQ': ("train.ITQ.hash_train", "ITQTrainer"),       # training-free: LSH / PCAH / ITQ heads fitted on the towers' features
     'DCH': ("train.DCH.hash_train", "DCHTrainer"),       # training-free, supervised: discrete cross-modal hashing on the towers' features
     'DJSRH': ("train.DJSRH.hash_train", "DJSRHTrainer"), # label-free fine-tuning: joint-semantics reconstruction (ICCV 2019)
+    'MSCH': ("train.MSCH.hash_train", "MSCHTrainer"),    # DSPH's model under DPSIH's all-triplets margin loss (DPSIH itself is not built)
 }
 _NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
 

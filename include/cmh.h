@@ -375,6 +375,29 @@ int cmh_ddbh_quant_loss(const float* const* h, int32_t calls, const float* label
 int cmh_ddbh_quant_loss_backward(const float* const* h, int32_t calls, const float* colsum, int32_t B, int32_t K, const float* dloss,
                                  float* const* dh, void* stream);
 
+/* MSCH all-triplets margin loss, reference train/DPSIH/Loss.py:78-137 `Multi_Semantic_Correlation_Loss.forward(batch_inputs,
+ * batch_labels, inputs)` (the [B, B, B] mask, the two gathers of its index vectors and the length read on the host, :105-137; the
+ * three calls of a step, :61-62), for `calls` (1 .. 4) pairs (u[q], v[q]) of f32 [B,K] matrices over one f32 [B,C] label matrix:
+ * u, v are HOST arrays of `calls` device pointers, u[q] == v[q] is the intra-modal call.  s = -n(u) n(v)^T with n the row normaliser
+ * F.normalize (eps 1e-12) when `normalize` is set and the identity otherwise; positives share a label with the anchor and are not
+ * the anchor's own column (the reference clears the diagonal of every square mask, :107), negatives share none; a triplet is active
+ * when s_an - s_ap <= margin (mining 0, "all") or 0 < s_an - s_ap <= margin (mining 1, "semi-hard") -> loss f32 [calls] = the mean
+ * of relu(s_ap - s_an + margin) over the active triplets (0 without any), count i64 [calls] = their number, sim f32 [calls,B,B] = s,
+ * coef i32 [calls,B,B] = +(active negatives with a violation > 0) at a positive column, -(such positives) at a negative one, and with
+ * `normalize` unit f32 [2 calls,B,K] / divisor f32 [2 calls,B]: the unit rows and norms of every distinct operand, in the slot of
+ * its first appearance in u[0], v[0], u[1], ... (both may be NULL otherwise).  Backward, reference: autograd through :99-135:
+ * du[q], dv[q] f32 [B,K] = dloss[q] * d loss[q] / d u[q], v[q] from coef, count and the unit rows; on an intra-modal call du[q]
+ * holds the whole gradient and dv[q] is not written (it may be NULL).  1 <= B <= 1024, 1 <= K <= 128, any C >= 1; the workspace
+ * holds cmh_msc_triplet_workspace_bytes(B) bytes (0 for a B out of range).  Integer counts, fixed-order sums, no atomics: two
+ * calls give the same bits. */
+size_t cmh_msc_triplet_workspace_bytes(int32_t B);
+int cmh_msc_triplet_loss(const float* const* u, const float* const* v, int32_t calls, const float* labels, int32_t B, int32_t K, int32_t C,
+                         float margin, int32_t mining, int32_t normalize, float* loss, int64_t* count, float* sim, int32_t* coef,
+                         float* unit, float* divisor, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_msc_triplet_loss_backward(const float* const* u, const float* const* v, int32_t calls, int32_t B, int32_t K, int32_t normalize,
+                                  const int32_t* coef, const int64_t* count, const float* unit, const float* divisor, const float* dloss,
+                                  float* const* du, float* const* dv, void* stream);
+
 /* DJSRH joint-semantics target and reconstruction loss (Su, Zhong, Zhang: Deep Joint-Semantics Reconstructing Hashing, ICCV 2019;
  * no upstream counterpart), label-free.  n(x) = x / max(|x|, 1e-12) per row.  1 <= B <= 1024, 1 <= K <= 128, 1 <= D <= 4096; every
  * workspace is 256-byte aligned and holds cmh_djsrh_workspace_bytes(B, K, D) bytes (0 for a shape out of range).
