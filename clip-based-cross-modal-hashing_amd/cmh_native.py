@@ -134,6 +134,10 @@ SIGNATURES = {
     "cmh_msc_triplet_workspace_bytes": (_sz, [_i32]),
     "cmh_msc_triplet_loss": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _f, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_msc_triplet_loss_backward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cmh_cpf_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "cmh_cpf_tape_bytes": (_sz, [_i32, _i32, _i32]),
+    "cmh_cpf_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "cmh_cpf_loss_backward": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p]),
     "cmh_djsrh_loss": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
     "cmh_djsrh_loss_backward": (C.c_int, [_p, _p, _p, _i32, _i32, _f, _f, _p, _p, _p, _p, _sz, _p]),   # no upstream counterpart
     "cmh_fp8_quantize_weight": (C.c_int, [_p, _p, _p, _i32, _i32, _p]),
@@ -1715,6 +1719,47 @@ def msc_triplet_loss_backward(saved, dloss):
                                               int(unit is not None), ptr(coef), ptr(count), ptr(unit), ptr(divisor), ptr(dloss),
                                               _ptr_array(du), dv_ptrs, stream_ptr(coef.device)), "cmh_msc_triplet_loss_backward")
     return list(zip(du, dv))
+
+
+CPF_MAX_B, CPF_MAX_K, CPF_MAX_C = 1024, 128, 1024           # csrc/cpf.hip's limits, for the wrapper's message
+CPF_ROWS, CPF_CHUNK, CPF_SLICE = 16, 64, 256                # its rows per workgroup, classes per staged proxy tile, partners per backward slice
+CPF_SCALARS = dict(tau=0.9, psi=0.7, sp=1.3, sn=1.3, mu=1.0, b=2.0)       # reference train/DScPH/CPF_loss.py:17-22
+
+
+def cpf_loss(hi, ht, label, proxies, scalars=None, quant_weight=1.0, keep=False, cos=None):
+    """CPF.forward (train/DScPH/CPF_loss.py:24-54) plus the step's two quantisation terms (train/DScPH/hash_train.py:64-70) in one call
+    -> (loss f32 [1], terms f32 [4] = L_img, L_txt, q_img, q_txt, cos f32 [2, B, C], saved = what cpf_loss_backward takes, or None
+    without `keep`).  `cos` may be handed in as a view to fill."""
+    hi, ht, label, proxies = f32c(hi), f32c(ht), f32c(label), f32c(proxies)
+    require_gpu(hi, ht, label, proxies)
+    if hi.dim() != 2 or label.dim() != 2 or proxies.dim() != 2:
+        raise NativeError("cpf_loss: hi, ht f32 [B, K], labels f32 [B, C] and proxies f32 [C, K] are expected")
+    (B, K), Cn = hi.shape, label.shape[1]
+    fit("cpf_loss", (ht, (B, K)), (label, (B, Cn)), (proxies, (Cn, K)))
+    need = lib().cmh_cpf_workspace_bytes(B, K, Cn)
+    if need == 0:
+        raise NativeError(f"cpf_loss: B={B} K={K} C={Cn}: 1 <= B <= {CPF_MAX_B}, 1 <= K <= {CPF_MAX_K}, 1 <= C <= {CPF_MAX_C} are built")
+    s = dict(CPF_SCALARS, **(scalars or {}))
+    dev = hi.device
+    ws = workspace(need, dev, "loss")
+    loss, terms = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(4, dtype=torch.float32, device=dev)
+    cos = _out_view("cpf_loss", "cos", cos, (2, B, Cn), torch.float32, dev)
+    tape = torch.empty(lib().cmh_cpf_tape_bytes(B, K, Cn) // 4, dtype=torch.float32, device=dev) if keep else None
+    check(lib().cmh_cpf_loss(ptr(hi), ptr(ht), ptr(label), ptr(proxies), B, K, Cn, s["tau"], s["psi"], s["sp"], s["sn"], s["mu"], s["b"],
+                             float(quant_weight), ptr(terms), ptr(loss), ptr(cos), ptr(tape), ptr(ws), ws.numel(), stream_ptr(dev)),
+          "cmh_cpf_loss")
+    return loss, terms, cos, ((label, cos, tape, (B, K, Cn), s, float(quant_weight)) if keep else None)
+
+
+def cpf_loss_backward(saved, dloss):
+    """-> d_hi, d_ht f32 [B, K], d_proxies f32 [C, K] = dloss * d loss / d hi, ht, proxies from the forward's cosines and tape"""
+    label, cos, tape, (B, K, Cn), s, quant_weight = saved
+    dev = cos.device
+    d_hi, d_ht = (torch.empty(B, K, dtype=torch.float32, device=dev) for _ in range(2))
+    d_w = torch.empty(Cn, K, dtype=torch.float32, device=dev)
+    check(lib().cmh_cpf_loss_backward(ptr(label), ptr(cos), ptr(tape), B, K, Cn, s["tau"], s["sp"], s["sn"], s["mu"], quant_weight,
+                                      ptr(f32c(dloss).reshape(1)), ptr(d_hi), ptr(d_ht), ptr(d_w), stream_ptr(dev)), "cmh_cpf_loss_backward")
+    return d_hi, d_ht, d_w
 
 
 DJSRH_MAX_B, DJSRH_MAX_K, DJSRH_MAX_D = 1024, 128, 4096     # csrc/djsrh.hip's limits, for the wrappers' messages

@@ -20,8 +20,9 @@ _REGISTRY = {
     'DCH': ("train.DCH.hash_train", "DCHTrainer"),       # training-free, supervised: discrete cross-modal hashing on the towers' features
     'DJSRH': ("train.DJSRH.hash_train", "DJSRHTrainer"), # label-free fine-tuning: joint-semantics reconstruction (ICCV 2019)
     'MSCH': ("train.MSCH.hash_train", "MSCHTrainer"),    # DSPH's model under DPSIH's all-triplets margin loss (DPSIH itself is not built)
+    'CPFH': ("train.DScPH.hash_train", "DScPHTrainer"),   # the reference's DScPH (proxy-fusion loss, proxies in BertAdam's fourth group) under this build's name
 }
-_NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']
+_NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']      # (the name DScPH stays unbuilt: see train/DScPH/hash_train.py)
 
 
 class _LazyTrainers(dict):

@@ -398,6 +398,28 @@ int cmh_msc_triplet_loss_backward(const float* const* u, const float* const* v, 
                                   const int32_t* coef, const int64_t* count, const float* unit, const float* divisor, const float* dloss,
                                   float* const* du, float* const* dv, void* stream);
 
+/* DScPH proxy-fusion (CPF) loss with the step's quantisation term, reference train/DScPH/CPF_loss.py:24-54 `CPF.forward(image, text,
+ * labels)` and train/DScPH/hash_train.py:64-70, both modalities in one call.  hi, ht f32 [B,K] head outputs, proxies f32 [C,K],
+ * labels f32 [B,C] in {0, 1}; n(x) = x / max(|x|, 1e-12) per row; per modality c = n(h) n(proxies)^T, tp = 2 sum max(c, 0) Y + b,
+ * lp = sum (1 - c) exp((1 - c) sp) Y, ln = sum_{c > tau} (c - psi) exp((c - mu) sn) (1 - Y) (the exponentials are constants of the
+ * backward), L = 1 - tp / (tp + lp + ln); q = mean(sigma(z) (1 - sigma(z))) over z = n(h) (the reference's identity HouseHolder
+ * rotation is z -> -z and the summand is even) -> terms f32 [4] = L_img, L_txt, q_img, q_txt, loss f32 [1] = L_img + L_txt +
+ * quant_weight (q_img + q_txt), cos f32 [2,B,C] = the two cosine matrices the thresholds c >= 0 and c > tau were decided on (one
+ * k-ascending f32 fmaf chain per element).  tape f32 [cmh_cpf_tape_bytes / 4], 8-byte aligned, or NULL for a forward alone: the six
+ * f64 sums (tp, lp, ln per modality), the unit rows and the divisors.  Backward, reference: autograd through the same lines: from
+ * labels, cos and the tape, d_hi, d_ht f32 [B,K] and d_proxies f32 [C,K] = dloss[0] * d loss / d hi, ht, proxies (d_proxies adds the
+ * image rows in ascending order, then the text rows).  1 <= B <= 1024, 1 <= K <= 128, 1 <= C <= 1024; the workspace is 256-byte
+ * aligned and holds cmh_cpf_workspace_bytes(B, K, C) bytes (0 for a shape out of range, as cmh_cpf_tape_bytes).  f64 sums in a fixed
+ * order, no atomics: two calls give the same bits.  Launches: forward 5, backward 1. */
+size_t cmh_cpf_workspace_bytes(int32_t B, int32_t K, int32_t C);
+size_t cmh_cpf_tape_bytes(int32_t B, int32_t K, int32_t C);
+int cmh_cpf_loss(const float* hi, const float* ht, const float* labels, const float* proxies, int32_t B, int32_t K, int32_t C, float tau,
+                 float psi, float sp, float sn, float mu, float b, float quant_weight, float* terms, float* loss, float* cos,
+                 float* tape, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_cpf_loss_backward(const float* labels, const float* cos, const float* tape, int32_t B, int32_t K, int32_t C, float tau, float sp,
+                          float sn, float mu, float quant_weight, const float* dloss, float* d_hi, float* d_ht, float* d_proxies,
+                          void* stream);
+
 /* DJSRH joint-semantics target and reconstruction loss (Su, Zhong, Zhang: Deep Joint-Semantics Reconstructing Hashing, ICCV 2019;
  * no upstream counterpart), label-free.  n(x) = x / max(|x|, 1e-12) per row.  1 <= B <= 1024, 1 <= K <= 128, 1 <= D <= 4096; every
  * workspace is 256-byte aligned and holds cmh_djsrh_workspace_bytes(B, K, D) bytes (0 for a shape out of range).
