@@ -134,6 +134,11 @@ SIGNATURES = {
     "cmh_msc_triplet_workspace_bytes": (_sz, [_i32]),
     "cmh_msc_triplet_loss": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _f, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cmh_msc_triplet_loss_backward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cmh_dws_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "cmh_dws_distances": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p]),
+    "cmh_dws_mine": (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _f, _i32, _p, _p, _p, _p, _sz, _p]),
+    "cmh_dws_margin_loss": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _f, _p, _p, _p, _p, _sz, _p]),
+    "cmh_dws_margin_loss_backward": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "cmh_cpf_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_cpf_tape_bytes": (_sz, [_i32, _i32, _i32]),
     "cmh_cpf_loss": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
@@ -1760,6 +1765,98 @@ def cpf_loss_backward(saved, dloss):
     check(lib().cmh_cpf_loss_backward(ptr(label), ptr(cos), ptr(tape), B, K, Cn, s["tau"], s["sp"], s["sn"], s["mu"], quant_weight,
                                       ptr(f32c(dloss).reshape(1)), ptr(d_hi), ptr(d_ht), ptr(d_w), stream_ptr(dev)), "cmh_cpf_loss_backward")
     return d_hi, d_ht, d_w
+
+
+DWS_MAX_B, DWS_MAX_K, DWS_MAX_C, DWS_MAX_PAIRS = 1024, 128, 1024, 3       # csrc/dws.hip's limits, for the wrappers' messages
+DWS_SPACES = {"distances": 0, "embeddings": 1}              # what the miner measures: the rows of D (upstream), or D itself (the paper)
+
+
+def _dws_ws(what, B, K, Cn, dev):
+    need = lib().cmh_dws_workspace_bytes(B, K, Cn)
+    if need == 0:
+        raise NativeError(f"{what}: B={B} K={K} C={Cn}: 1 <= B <= {DWS_MAX_B}, 1 <= K <= {DWS_MAX_K}, 1 <= C <= {DWS_MAX_C} are built")
+    return workspace(need, dev, "loss")
+
+
+def dws_distances(pairs):
+    """MarginLoss.forward's distances (train/DDWSH/loss.py:17-20) for up to three (u, v) pairs -> (dist f32 [n, B, B], saved = the
+    operands as passed, their unit rows [2n, B, K] and divisors [2n, B])"""
+    made = {}                                                   # one f32 contiguous copy per distinct operand: `v is u` stays so
+    pairs = [tuple(made.setdefault(id(t), f32c(t)) for t in pr) for pr in pairs]
+    require_gpu(*[t for pr in pairs for t in pr])
+    if not 1 <= len(pairs) <= DWS_MAX_PAIRS or pairs[0][0].dim() != 2:
+        raise NativeError(f"dws_distances: 1 .. {DWS_MAX_PAIRS} pairs of codes [B, K] are expected")
+    B, K = pairs[0][0].shape
+    fit("dws_distances", *[(t, (B, K)) for pr in pairs for t in pr])
+    if not (1 <= B <= DWS_MAX_B and 1 <= K <= DWS_MAX_K):
+        raise NativeError(f"dws_distances: B={B} K={K}: 1 <= B <= {DWS_MAX_B} and 1 <= K <= {DWS_MAX_K} are built")
+    n, dev = len(pairs), pairs[0][0].device
+    dist = torch.empty(n, B, B, dtype=torch.float32, device=dev)
+    unit = torch.empty(2 * n, B, K, dtype=torch.float32, device=dev)
+    divisor = torch.empty(2 * n, B, dtype=torch.float32, device=dev)
+    check(lib().cmh_dws_distances(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, B, K, ptr(dist), ptr(unit),
+                                  ptr(divisor), stream_ptr(dev)), "cmh_dws_distances")
+    return dist, (pairs, unit, divisor)
+
+
+def dws_mine(dist, label, K, uniforms, cutoff=0.5, space="distances", weights=False):
+    """DistanceWeightedMiner.__call__ (train/DDWSH/loss.py:91-128) on dist [n, B, B] with the uniforms [n, B, 2] = (u_p, u_n) handed in
+    -> (triplets i32 [n, B, 2] = (positive, negative) or (-1, -1), w f64 [n, B, B] with `weights`, else None)"""
+    if space not in DWS_SPACES:
+        raise NativeError(f"dws_mine: space {space!r}: one of {sorted(DWS_SPACES)}")
+    dist, label, uniforms = f32c(dist), f32c(label), f32c(uniforms)
+    require_gpu(dist, label, uniforms)
+    if dist.dim() != 3 or label.dim() != 2:
+        raise NativeError("dws_mine: dist f32 [n, B, B] and labels f32 [B, C] are expected")
+    n, B, Cn = dist.shape[0], dist.shape[1], label.shape[1]
+    fit("dws_mine", (dist, (n, B, B)), (label, (B, Cn)), (uniforms, (n, B, 2)))
+    if not 1 <= n <= DWS_MAX_PAIRS:
+        raise NativeError(f"dws_mine: pairs={n}: 1 .. {DWS_MAX_PAIRS} are built")
+    dev = dist.device
+    ws = _dws_ws("dws_mine", B, K, Cn, dev)
+    trip = torch.empty(n, B, 2, dtype=torch.int32, device=dev)
+    w = torch.empty(n, B, B, dtype=torch.float64, device=dev) if weights else None
+    check(lib().cmh_dws_mine(ptr(dist), n, ptr(label), B, int(K), Cn, float(cutoff), DWS_SPACES[space], ptr(uniforms), ptr(trip), ptr(w),
+                             ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dws_mine")
+    return trip, w
+
+
+def dws_margin_loss(pairs, label, beta, triplets, margin=0.2, pre=None):
+    """MarginLoss.forward (train/DDWSH/loss.py:16-49) for up to three (u, v) pairs over one label matrix, on the triplets i32 [n, B, 2]
+    given -> (loss f32 [n], count i64 [n], dist f32 [n, B, B], saved = what dws_margin_loss_backward takes).  pre: what dws_distances
+    returned for these pairs, when the caller has it already (the sampler ran on it)"""
+    dist, (pairs, unit, divisor) = pre if pre is not None else dws_distances(pairs)
+    label, beta = f32c(label), f32c(beta)
+    require_gpu(label, beta, triplets)
+    n, B, Cn = dist.shape[0], dist.shape[1], label.shape[-1]
+    if label.dim() != 2 or triplets.dtype != torch.int32:
+        raise NativeError("dws_margin_loss: labels f32 [B, C] and triplets i32 [n, B, 2] are expected")
+    triplets = triplets.contiguous()
+    fit("dws_margin_loss", (label, (B, Cn)), (beta, (Cn,)), (triplets, (n, B, 2)))
+    dev = dist.device
+    ws = _dws_ws("dws_margin_loss", B, pairs[0][0].shape[1], Cn, dev)
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    tape = torch.empty(n, B, 4, dtype=torch.float32, device=dev)
+    check(lib().cmh_dws_margin_loss(ptr(dist), ptr(triplets), n, ptr(label), ptr(beta), B, Cn, float(margin), ptr(loss), ptr(count), ptr(tape),
+                                    ptr(ws), ws.numel(), stream_ptr(dev)), "cmh_dws_margin_loss")
+    return loss, count, dist, (pairs, label, dist, triplets, tape, count, unit, divisor)
+
+
+def dws_margin_loss_backward(saved, dloss):
+    """-> ([(du, dv)] per pair, each f32 [B, K]; an intra-modal pair (v is u) gets its whole gradient in du and dv = None), dbeta f32 [C]"""
+    pairs, label, dist, triplets, tape, count, unit, divisor = saved
+    B, K = pairs[0][0].shape
+    n, Cn = len(pairs), label.shape[1]
+    du = [torch.empty_like(u) for u, _ in pairs]
+    dv = [None if v.data_ptr() == u.data_ptr() else torch.empty_like(v) for u, v in pairs]     # as the library tells them apart
+    dbeta = torch.empty(Cn, dtype=torch.float32, device=label.device)
+    dloss = f32c(dloss).reshape(n)
+    dv_ptrs = (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in dv])
+    check(lib().cmh_dws_margin_loss_backward(_ptr_array([u for u, _ in pairs]), _ptr_array([v for _, v in pairs]), n, ptr(label), B, K, Cn,
+                                             ptr(dist), ptr(triplets), ptr(tape), ptr(count), ptr(unit), ptr(divisor), ptr(dloss),
+                                             _ptr_array(du), dv_ptrs, ptr(dbeta), stream_ptr(label.device)), "cmh_dws_margin_loss_backward")
+    return list(zip(du, dv)), dbeta
 
 
 DJSRH_MAX_B, DJSRH_MAX_K, DJSRH_MAX_D = 1024, 128, 4096     # csrc/djsrh.hip's limits, for the wrappers' messages

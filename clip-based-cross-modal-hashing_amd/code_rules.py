@@ -6,7 +6,7 @@ import cmh_native as N
 
 
 def sign_code(out) -> torch.Tensor:
-    """sign() of the tanh head's output (DSPH, DNpH, DMsH_LN, DHaPH, DDBH, ITQ, DCH, DJSRH, MSCH, CPFH; reference train/base.py:130-148)."""
+    """sign() of the tanh head's output (DSPH, DNpH, DMsH_LN, DHaPH, DDBH, ITQ, DCH, DJSRH, MSCH, CPFH, DWSH; reference train/base.py:130-148)."""
     return N.sign_codes(out)
 
 
@@ -23,7 +23,7 @@ def first_sign_code(out) -> torch.Tensor:
 
 
 CODE_RULES = {"DSPH": sign_code, "DNpH": sign_code, "DMsH_LN": sign_code, "DHaPH": sign_code, "DDBH": sign_code, "ITQ": sign_code,
-              "DCH": sign_code, "DJSRH": sign_code, "MSCH": sign_code, "CPFH": sign_code,
+              "DCH": sign_code, "DJSRH": sign_code, "MSCH": sign_code, "CPFH": sign_code, "DWSH": sign_code,
               "DCHMT": pair_argmax_code, "DNPH": first_sign_code}
 
 
@@ -48,7 +48,7 @@ def first_soft_output(out) -> torch.Tensor:
 # The real-valued output behind each rule of CODE_RULES, for soft queries (utils/retrieval.py::soft_topk): wherever it is
 # non-zero, its sign is the code the method's rule writes.
 SOFT_RULES = {"DSPH": soft_output, "DNpH": soft_output, "DMsH_LN": soft_output, "DHaPH": soft_output, "DDBH": soft_output,
-              "ITQ": soft_output, "DCH": soft_output, "DJSRH": soft_output, "MSCH": soft_output, "CPFH": soft_output,
+              "ITQ": soft_output, "DCH": soft_output, "DJSRH": soft_output, "MSCH": soft_output, "CPFH": soft_output, "DWSH": soft_output,
               "DCHMT": pair_margin, "DNPH": first_soft_output}
 
 

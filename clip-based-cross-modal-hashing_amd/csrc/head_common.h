@@ -1,4 +1,4 @@
-// Shared by the head and loss translation units (heads, heads2, heads_bwd, losses, msl, qmi, mith, ddbh, djsrh, msc, cpf): the wave and workgroup reductions,
+// Shared by the head and loss translation units (heads, heads2, heads_bwd, losses, msl, qmi, mith, ddbh, djsrh, msc, cpf, dws): the wave and workgroup reductions,
 // the workspace carver with its size check, and the row kernels of losses.hip that the other files launch.  The training-free fits (itq, dch)
 // take wave_sum and the Carver from here through fit_common.h.
 #pragma once

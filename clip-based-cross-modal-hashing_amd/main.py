@@ -21,8 +21,9 @@ _REGISTRY = {
     'DJSRH': ("train.DJSRH.hash_train", "DJSRHTrainer"), # label-free fine-tuning: joint-semantics reconstruction (ICCV 2019)
     'MSCH': ("train.MSCH.hash_train", "MSCHTrainer"),    # DSPH's model under DPSIH's all-triplets margin loss (DPSIH itself is not built)
     'CPFH': ("train.DScPH.hash_train", "DScPHTrainer"),   # the reference's DScPH (proxy-fusion loss, proxies in BertAdam's fourth group) under this build's name
+    'DWSH': ("train.DDWSH.hash_train", "DDWSHTrainer"),   # the reference's DDWSH (distance-weighted triplets, margin loss with per-class boundaries) under this build's name
 }
-_NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']      # (the name DScPH stays unbuilt: see train/DScPH/hash_train.py)
+_NOT_BUILT = ['DPBE', 'DDWSH', 'DScPH', 'DPSIH', 'DGHDGH']      # (the names DScPH and DDWSH stay unbuilt: see train/DScPH/hash_train.py, train/DDWSH/hash_train.py)
 
 
 class _LazyTrainers(dict):

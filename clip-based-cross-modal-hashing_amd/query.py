@@ -19,7 +19,7 @@ MODELS = {"DSPH": ("model.DSPH", "MDSPH"), "DCHMT": ("model.DCHMT", "MDCMHT"), "
           "DNpH": ("model.DNpH_TMM", "MDNpH"), "DMsH_LN": ("model.DMsH_LN", "MDMsH_LN"), "DHaPH": ("model.DHaPH", "MDHaPH"),
           "DDBH": ("model.DDBH", "MDDBH"), "ITQ": ("model.ITQ", "MITQ"), "DCH": ("model.DCH", "MDCH"),
           "DJSRH": ("model.DJSRH", "MDJSRH"), "MSCH": ("model.MSCH", "MMSCH"),
-          "CPFH": ("model.DScPH", "MDScPH")}
+          "CPFH": ("model.DScPH", "MDScPH"), "DWSH": ("model.DDWSH", "MDDWSH")}
 REFUSED = {"MITH": "its encoders take key padding masks and the towers' token trunks (train/MITH/hash_train.py::get_code)",
            "TwDH": "it hashes into long and short codes through centre assets (train/TwDH/hash_train.py)"}
 

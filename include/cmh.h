@@ -420,6 +420,49 @@ int cmh_cpf_loss_backward(const float* labels, const float* cos, const float* ta
                           float sn, float mu, float quant_weight, const float* dloss, float* d_hi, float* d_ht, float* d_proxies,
                           void* stream);
 
+/* DDWSH: distance-weighted triplet sampling and the margin loss with per-class boundaries, for `pairs` (1 .. 3) pairs (u[q], v[q]) of
+ * f32 [B,K] matrices over one f32 [B,C] label matrix in {0, 1}: u, v are HOST arrays of `pairs` device pointers, u[q] == v[q] is the
+ * intra-modal call.  1 <= B <= 1024, 1 <= K <= 128, 1 <= C <= 1024; the workspace is 256-byte aligned and holds
+ * cmh_dws_workspace_bytes(B, K, C) bytes (0 for a shape out of range).  f64 sums in a fixed order, no atomics, nothing read back: two
+ * calls give the same bits.
+ *
+ * cmh_dws_distances, reference train/DDWSH/loss.py:17-20: dist f32 [pairs,B,B], D_ij = max(|n(u)_i - n(v)_j|, 1e-8) with n =
+ * F.normalize (eps 1e-12), the squared difference summed as one k-ascending fmaf chain (the diagonal of an intra-modal pair is exactly
+ * 1e-8); unit f32 [2 pairs,B,K] / divisor f32 [2 pairs,B]: the unit rows and norms of every distinct operand, in the slot of its first
+ * appearance in u[0], v[0], u[1], ...
+ *
+ * cmh_dws_mine, reference train/DDWSH/loss.py:22, :52-72 `inverse_sphere_distances`, :75-79 `pdist`, :91-128
+ * `DistanceWeightedMiner.__call__` (the host loop over the anchors, one row read back and two numpy draws per anchor).  space 0
+ * ("distances", what the reference runs): M_ij = max(sqrt(max(|D_i: - D_j:|^2, 1e-4)), cutoff), the B terms summed in f64, dim = B;
+ * space 1 ("embeddings", the paper's): M = max(D, cutoff), dim = K.  Anchor i is used when it has another positive (an item sharing a label) and not every item is
+ * one; log w_j = (2 - dim) log M_ij - ((dim - 3) / 2) log max(1 - M_ij^2 / 4, 1e-8) in f64, 0 on the positives before the maximum is
+ * taken, w = exp(log w - max), 0 on the positives.  uniforms f32 [pairs,B,2] in [0, 1) = (u_p, u_n) per anchor: the negative is the
+ * first j whose ascending-index running sum of w exceeds u_n times the total (an item of weight 0 is never picked), the positive the
+ * floor(u_p n)-th of the n other positives in index order -> triplets i32 [pairs,B,2] = (positive, negative), (-1, -1) for an anchor
+ * that is not used; weights f64 [pairs,B,B] = w (zero rows for such anchors), or NULL.
+ *
+ * cmh_dws_margin_loss, reference train/DDWSH/loss.py:28-49: beta f32 [C]; beta_i = sum_c Y_ic beta_c / sum_c Y_ic, pos_i =
+ * relu((D[i,p_i] - beta_i) + margin), neg_i = relu((beta_i - D[i,n_i]) + margin) -> count i64 [pairs] = the anchors with pos_i > 0 or
+ * neg_i > 0, loss f32 [pairs] = sum (pos + neg) / count (0 without any), tape f32 [pairs,B,4] = beta_i, [pos_i > 0], [neg_i > 0],
+ * sum_c Y_ic.  The triplets may be cmh_dws_mine's or handed in; an entry outside [0, B) skips its anchor.
+ *
+ * cmh_dws_margin_loss_backward, reference: autograd through train/DDWSH/loss.py:17-47: du[q], dv[q] f32 [B,K] and dbeta f32 [C] =
+ * sum_q dloss[q] * d loss[q] / d u[q], v[q], beta (no gradient through an entry of D at its clamp); on an intra-modal pair du[q] holds
+ * the whole gradient and dv[q] is not written (it may be NULL).  Launches for three pairs: distances 3, mine 3 (space 1: 2), loss 2,
+ * backward 2. */
+size_t cmh_dws_workspace_bytes(int32_t B, int32_t K, int32_t C);
+int cmh_dws_distances(const float* const* u, const float* const* v, int32_t pairs, int32_t B, int32_t K, float* dist, float* unit,
+                      float* divisor, void* stream);
+int cmh_dws_mine(const float* dist, int32_t pairs, const float* labels, int32_t B, int32_t K, int32_t C, float cutoff, int32_t space,
+                 const float* uniforms, int32_t* triplets, double* weights, void* workspace, size_t workspace_bytes, void* stream);
+int cmh_dws_margin_loss(const float* dist, const int32_t* triplets, int32_t pairs, const float* labels, const float* beta, int32_t B,
+                        int32_t C, float margin, float* loss, int64_t* count, float* tape, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int cmh_dws_margin_loss_backward(const float* const* u, const float* const* v, int32_t pairs, const float* labels, int32_t B, int32_t K,
+                                 int32_t C, const float* dist, const int32_t* triplets, const float* tape, const int64_t* count,
+                                 const float* unit, const float* divisor, const float* dloss, float* const* du, float* const* dv,
+                                 float* dbeta, void* stream);
+
 /* DJSRH joint-semantics target and reconstruction loss (Su, Zhong, Zhang: Deep Joint-Semantics Reconstructing Hashing, ICCV 2019;
  * no upstream counterpart), label-free.  n(x) = x / max(|x|, 1e-12) per row.  1 <= B <= 1024, 1 <= K <= 128, 1 <= D <= 4096; every
  * workspace is 256-byte aligned and holds cmh_djsrh_workspace_bytes(B, K, D) bytes (0 for a shape out of range).
